@@ -8,7 +8,12 @@ on synthetic overlap batches, one process per GPU.
 A step = one pass of the hot path over one batch of `--batch` (128) 4096-bp windows with 32 overlaps each
 (BASELINE.json configs[2]): featurise the windows on the GPU, batch the windows with >= 1 informative position across
 reads, run the model, decode the corrected bases on the device.  `value` counts exactly `--steps` steps with the inputs
-(2-bit read store, window descriptors) resident in HBM before the timed region starts.  The same JSON line also carries
+(2-bit read store, window descriptors) resident in HBM before the timed region starts.
+
+A plain run sets up, warms up, times the `--steps` steps and prints the line (value, ms_per_step, dtype, config).
+`--dump-outputs DIR` writes what the last timed step computed — the corrected reads' FASTA records and the model's logits
+of that step's windows — as DIR/<name>.npy; the inputs are the same from run to run, so two builds compare output for output.
+With `--full` the same JSON line also carries
   end_to_end    the same work with herro_job_create (CIGAR text staged and scanned on the GPU, windowing, descriptor
                 upload) and the D2H of the corrected bases INSIDE the timed region, fresh inputs every job, six feeder
                 threads (contexts) per GPU; N = 1 only by default;
@@ -47,6 +52,22 @@ DTYPE = {0: "f32", 1: "bf16x3", 2: "f32-valu", 3: "bf16x3", 4: "f16 (encoder pro
 MFMA_TERMS = {1: 3, 3: 3, 4: 1.75, 5: 1, 6: 1.375, 7: 13 / 12, 8: 20 / 12}
 
 
+def model_file():
+    """(path, raw) of the random-init weight file.  tests/_cache of the tree when it can be written; otherwise (a checkout the
+    running user does not own) the user's cache directory, or else the temporary directory.  The choice is made here as well
+    as in model_io, so that this script also drives builds of the package whose default_model_file only knows tests/_cache."""
+    import tempfile
+    from herro_amd import model_io
+    user_cache = os.path.join(os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache"), "herro_amd")
+    err = None
+    for d in (os.path.join(ROOT, "tests", "_cache"), user_cache, os.path.join(tempfile.gettempdir(), f"herro_amd_{os.getuid()}")):
+        try:
+            return model_io.default_model_file(d)
+        except OSError as e:
+            err = e
+    raise err
+
+
 def cpu_baseline(seed: int) -> dict:
     """Reference algorithm on the host: oracle restatement (features) + PyTorch-CPU twin (model) on a bounded sample of
     the same workload.  The reference runs the two stages on different threads (lib.rs:154-200), so the pipeline rate is
@@ -80,7 +101,7 @@ def cpu_baseline(seed: int) -> dict:
     # model: dense fp32 twin — what libtorch executes for the TorchScript graph — on ONE collated batch of `mb`
     # windows of one read group (a batch of 128 such windows takes minutes on the CPU; the batch size is stated)
     torch.set_num_threads(cores)
-    _, raw = model_io.default_model_file(os.path.join(ROOT, "tests", "_cache"))
+    _, raw = model_file()
     twin = MR.build(raw, model_io.Hyper())
     # ONE collated batch of 128 windows across reads — the grouping of the GPU run (identical batch grouping):
     # the windows with informative rows of as many reads as it takes, padded to the batch's longest window with token 11 / quality 126 as
@@ -158,6 +179,40 @@ def self_check(job, sb, targets, n_check: int, seed: int) -> dict:
     return {"ok": True, "windows": n_win, "targets": len(picks), "what": "pileup bit-exact vs oracle, device FASTA == oracle consensus of the job's logits"}
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(job, batch: int, out_dir: str) -> dict:
+    """What a caller of the timed path receives for the last timed step — the last `batch` windows of `job` (the step's
+    targets, WINS_PER_TARGET windows each): the FASTA records of the corrected reads (bytes as float32, one id per target)
+    and the model's logits of the step's windows in window order.  Written as out_dir/<name>.npy, float32 / float64, at
+    most DUMP_CAP_BYTES in all (beyond that a seeded, sorted sample of the logit rows)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n_t = max(1, batch // WINS_PER_TARGET)
+    t0 = job.n_targets - n_t
+    recs = [job.consensus_fasta(t, f"target{t - t0}").encode() for t in range(t0, job.n_targets)]
+    info, base, n_sup = [], [], []
+    for w in range(job.n_windows - batch, job.n_windows):
+        i_, b_ = job.logits(w)
+        info.append(i_)
+        base.append(b_)
+        n_sup.append(len(i_))
+    arrays = {"fasta": np.frombuffer(b"".join(recs), np.uint8).astype(np.float32),
+              "fasta_record_bytes": np.array([len(r) for r in recs], np.float64),
+              "window_informative_rows": np.array(n_sup, np.float64),
+              "info_logits": np.concatenate(info).astype(np.float32) if info else np.zeros(0, np.float32),
+              "base_logits": np.concatenate(base).astype(np.float32) if base else np.zeros((0, 5), np.float32)}
+    left = DUMP_CAP_BYTES - sum(a.nbytes for k, a in arrays.items() if not k.endswith("_logits"))
+    n_rows = len(arrays["info_logits"])
+    if n_rows * 6 * 4 > left:   # 6 float32 per row, and 8 bytes more for each kept row's index
+        keep = np.sort(np.random.default_rng(0).choice(n_rows, size=max(0, left // (6 * 4 + 8)), replace=False))
+        arrays["logit_rows"] = keep.astype(np.float64)
+        arrays["info_logits"], arrays["base_logits"] = arrays["info_logits"][keep], arrays["base_logits"][keep]
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 T_PROCESS_START = time.time()
 
 
@@ -212,6 +267,11 @@ def main():
                     help="1: `value` re-measured, one pass each, on data sets with more informative rows per window (p_snp 8e-3, 3e-2 next to the workload's 2e-3): "
                          "the throughput is roughly inversely proportional to that mean (default 1 on one GPU, 0: skip)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure (repeats, sustained, sensitivity, end_to_end, per-kernel roofline, "
+                         "self_check, cpu_baseline, strong, long_run); without it only the timed steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (FASTA records of its targets, logits of its windows) as DIR/<name>.npy")
     args = ap.parse_args()
 
     import torch
@@ -237,7 +297,7 @@ def main():
         args.e2e_jobs = 32 if world == 1 else 0
 
     from herro_amd import api, model_io, synth
-    path, _ = model_io.default_model_file(os.path.join(ROOT, "tests", "_cache"))
+    path, _ = model_file()
     precision_choice = {"how": "requested (--precision)"}
     if args.scaling == "strong":
         from herro_amd import shard
@@ -261,7 +321,7 @@ def main():
     tpj = G * targets_per_step                                  # targets per job
     NF = max(NS, args.e2e_feeders)                              # feeder threads (= contexts) of the end_to_end leg
     E2E_DISTINCT = 8   # distinct jobs per feeder of the end_to_end leg (cycled when it runs more: 8 x 6 x 31 MB of CIGAR text and ~100 MB of reads per job are far beyond any cache)
-    n_e2e = min(args.e2e_jobs, E2E_DISTINCT) * NF if (args.e2e_jobs > 0 and n_full) else 0
+    n_e2e = min(args.e2e_jobs, E2E_DISTINCT) * NF if (args.full and args.e2e_jobs > 0 and n_full) else 0
     n_t = (n_jobs + n_e2e) * tpj + rem * targets_per_step
 
     def job_targets(i):
@@ -300,12 +360,14 @@ def main():
         j.consensus()      # corrected bases stay in HBM (≈4 KB/window); only they would cross PCIe
 
     rot = [0]   # launch groups issued so far per stream: the pool is walked on across passes
+    last_job = [None]   # the job whose windows the last step of the last pass ran (its last `batch` windows)
 
     def run_steps(n_steps):
         """exactly n_steps batches of `batch` windows, launch groups dealt round-robin to the streams"""
         nf, r = divmod(n_steps, G)
         base = rot[0]
         rot[0] += (nf + NS - 1) // NS
+        last_job[0] = rem_job if r else jobs[(nf - 1) % NS][(base + (nf - 1) // NS) % pool]
 
         def worker(s_i):
             seq = [jobs[s_i][(base + i // NS) % pool] for i in range(s_i, nf, NS)]
@@ -357,8 +419,10 @@ def main():
             run_job(jobs[s_i][i % pool])
     # ... and at least `--settle` seconds of the same steps: W = 5 steps is 0.7 ms of GPU work, after which clocks and
     # caches are still moving (measured: the pass after a one-job warm-up runs 8 % slower than the following ones)
+    # The settle passes end where the pool's rotation starts over, so that the timed pass runs the same jobs in every run
+    # (the outputs of its last step are then the same from run to run) and still not the job a stream ran just before it.
     t_settle = time.perf_counter()
-    while time.perf_counter() - t_settle < args.settle:
+    while time.perf_counter() - t_settle < args.settle or (rot[0] and rot[0] % pool):
         run_steps(args.steps)
         for c in ctxs:
             c.synchronize()
@@ -374,11 +438,13 @@ def main():
         barrier()
         return el_
     el = timed_pass()                                    # THE measurement: exactly K steps
-    repeats = [timed_pass() for _ in range(max(0, args.repeats))]   # reported beside it (run-to-run spread), never used for `value`
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_job[0], args.batch, args.dump_outputs)
+    repeats = [timed_pass() for _ in range(max(0, args.repeats) if args.full else 0)]   # reported beside it (run-to-run spread), never used for `value`
     # ---- sustained: the same device-resident steps for seconds instead of milliseconds — is the figure above a transient of clocks and caches?
     sustained = None
     sus_s = args.sustained if args.sustained is not None else (2.0 if (world == 1 and args.steps >= 64) else 0.0)
-    if sus_s > 0 and world == 1:
+    if args.full and sus_s > 0 and world == 1:
         marks, clocks = [], []
         t0_ = time.perf_counter()
         next_probe, done_w = 0.0, 0
@@ -413,7 +479,7 @@ def main():
                              "queued behind a pass (herro_clock_probe)"}
     # ---- sensitivity: the workload's 2e-3 SNP rate gives ~15 informative rows per window; throughput falls with that mean (the transformer's share grows)
     sensitivity = None
-    if (args.sensitivity if args.sensitivity is not None else 1) and world == 1:
+    if args.full and (args.sensitivity if args.sensitivity is not None else 1) and world == 1:
         sensitivity = []
         s_steps = max(1, min(args.steps, 32))
         for p_snp in (8e-3, 3e-2):
@@ -556,23 +622,24 @@ def main():
                                                      else "one feeder thread per context: create(k+1) runs on the host while the GPU works on job k"),
                "mode": args.e2e_mode}
 
-    # ---- per-kernel durations with HIP events on the launch stream (separate pass, same jobs, single stream, so
-    # that kernel durations are not inflated by the other stream's kernels)
     st = jobs[0][0].stats()
-    ctx.timing_enable(True)
-    ctx.timing_reset()
-    n_timed = max(1, min(n_full, 4)) if n_full else 0
-    for i in range(n_timed):
-        run_job(jobs[0][i % pool])
-    if not n_full:
-        run_job(rem_job)
-    ctx.synchronize()
-    tm = ctx.timing()
-    ctx.timing_enable(False)
-    timed_steps = n_timed * G if n_full else rem
+    if args.full:
+        # ---- per-kernel durations with HIP events on the launch stream (separate pass, same jobs, single stream, so
+        # that kernel durations are not inflated by the other stream's kernels)
+        ctx.timing_enable(True)
+        ctx.timing_reset()
+        n_timed = max(1, min(n_full, 4)) if n_full else 0
+        for i in range(n_timed):
+            run_job(jobs[0][i % pool])
+        if not n_full:
+            run_job(rem_job)
+        ctx.synchronize()
+        tm = ctx.timing()
+        ctx.timing_enable(False)
+        timed_steps = n_timed * G if n_full else rem
 
     check = None
-    if rank == 0 and args.self_check > 0 and n_full:
+    if args.full and rank == 0 and args.self_check > 0 and n_full:
         try:
             check = self_check(jobs[0][0], sb, list(job_targets(0)), args.self_check, 7)
         except Exception as e:   # the checker must never take the measurement down with it
@@ -580,66 +647,6 @@ def main():
 
     if rank == 0:
         total_windows = args.steps * args.batch * world
-        kern = {k: {"ms_total": v[0], "calls": v[1], "avg_us": 1e3 * v[0] / max(v[1], 1)} for k, v in tm.items()}
-        lean = os.environ.get("HERRO_FEATURIZE_PLANES", "0") in ("", "0")   # the library's default path (k_rows); HERRO_FEATURIZE_PLANES=1: the planes path (k_tokens), for the A/B
-        feat_names = ["cols", "win", "layout", "rows", "tokens", "supgather", "rf_quals"]
-        feat_ms = sum(tm[k][0] for k in feat_names if k in tm) / timed_steps
-        model_ms = sum(v[0] for k, v in tm.items() if k not in feat_names) / timed_steps
-        # ---- algorithmic work per launch (one launch = G steps = G*batch windows); DESIGN.md §4/§5
-        per_job = {k: float(v) for k, v in st.items()}
-        n_cols = 1 + N_OVL
-        tokens = per_job["sum_supported"]
-        D, FF, C1, C2, KW, NL = 256, 1024, 64, 128, 3, 4
-        # What featurize has to move.  In: the 2-bit bases (1/5 of bases + qualities) and the binary ops.  Out, planes
-        # path: the TOKEN planes (31 L' bytes per window) + the receptive-field records.  Out, lean path (round 5): no planes — the
-        # receptive-field records (16 bytes per informative row and column, 5 quality bytes read for each), the decoder's votes (three
-        # bit planes over the window's positions + a byte per insertion row) and the informative-row lists (8 bytes per row).
-        n_launch_windows = G * args.batch
-        rf_bytes = tokens * 31 * (16.0 + 5.0)
-        vote_bytes = n_launch_windows * 3 * ((W + 31) // 32) * 4 + max(per_job["sum_len"] - n_launch_windows * W, 0.0) + 8.0 * tokens
-        plane_bytes = per_job["out_bytes"] / 2.0
-        feat_bytes = per_job["read_bytes"] / 5.0 + per_job["op_bytes"] + rf_bytes + (vote_bytes if lean else plane_bytes)
-        alg = {  # name -> (bound, work per launch, unit)
-            "tokens": ("hbm", per_job["out_bytes"] / 2.0, "B"),                                      # the token planes written
-            "conv_fused": ("mfma", 2.0 * tokens * 31 * (KW * C1) * C2, "F"),
-            "layers_fused": ("mfma", NL * (2.0 * tokens * D * 3 * D + 2.0 * tokens * D * D + 4.0 * tokens * D * FF), "F"),
-            "cols": ("hbm", per_job["read_bytes"] / 5.0 + per_job["op_bytes"], "B"),              # 2-bit bases + ops read
-            "rows": ("hbm", n_launch_windows * 30 * 3 * ((W + 31) // 32) * 4 + vote_bytes, "B"),  # the selected columns' planes read once more, votes + lists written
-            "patch_conv1": ("hbm", tokens * 31 * KW * C1 * 4, "B"),                               # y1 hi/lo written
-            "conv2_gemm": ("mfma", 2.0 * tokens * 31 * (KW * C1) * C2, "F"),
-            "fc_gemm": ("mfma", 2.0 * tokens * (31 * C2) * D, "F"),
-            "qkv_gemm": ("mfma", 2.0 * tokens * D * 3 * D, "F"),
-            "proj_gemm": ("mfma", 2.0 * tokens * D * D, "F"),
-            "ff1_gemm": ("mfma", 2.0 * tokens * D * FF, "F"),
-            "ff2_gemm": ("mfma", 2.0 * tokens * FF * D, "F"),
-        }
-        tj = None
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")     # written by tools/pmc_traffic.py from a --pmc run
-        if os.path.exists(tpath):
-            tj = json.load(open(tpath))
-            if tj.get("precision", 1) != args.precision:
-                tj = None                                           # counters of another operand format: not this run's traffic
-
-        def roof_of(k):
-            avg_s = tm[k][0] / max(tm[k][1], 1) * 1e-3
-            bound, work, _ = alg[k]
-            # PMC bytes were collected per launch of tj["windows_per_launch"] windows; every kernel's traffic is proportional to
-            # the windows it processes, so it is scaled to this run's launch size
-            traffic = (tj["kernels"][k]["hbm_bytes_corrected"] / tj.get("windows_per_launch", tj["group"] * 128) * G * args.batch
-                       if tj and k in tj.get("kernels", {}) else None)
-            if bound == "hbm":
-                return {"kernel": k, "bound": "hbm", "achieved": work / avg_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": work / avg_s / 1e9 / HBM_PEAK_GBS, "traffic": traffic,
-                        "algorithmic_bytes_per_launch": work, "launch_us": avg_s * 1e6, "windows_per_launch": G * args.batch}
-            terms = MFMA_TERMS.get(args.precision, 1)
-            return {"kernel": k, "bound": "mfma", "achieved": work / avg_s / 1e12, "peak": MFMA_PEAK_TF,
-                    "unit": "TFLOP/s", "frac": work / avg_s / 1e12 / MFMA_PEAK_TF, "traffic": traffic,
-                    "algorithmic_flops_per_launch": work, "launch_us": avg_s * 1e6, "windows_per_launch": G * args.batch,
-                    "note": f"algorithmic 2MNK flops; this precision issues {terms} MFMA product(s) per algorithmic product in the "
-                            "encoder GEMMs (issued-MFMA fraction = frac x that)"}
-        ranked = sorted((k for k in tm if k in alg), key=lambda k: -tm[k][0])
-        roof = roof_of(ranked[0])                                   # the dominant kernel
-        roof_next = [roof_of(k) for k in ranked[1:3]]               # the two behind it (the top two trade places between launch sizes)
         out = {
             "metric": "4096-bp windows corrected/sec at batch=128",
             "value": total_windows / el,
@@ -659,33 +666,96 @@ def main():
                        "mean_len": st["sum_len"] / (G * args.batch), "mean_informative": st["sum_supported"] / (G * args.batch),
                        "model_windows_per_batch": st["n_model_windows"] / G, "batches_per_launch_group": G,
                        "streams_per_gpu": NS, "distinct_windows_cycled": n_jobs * G * args.batch, "precision": args.precision, "precision_choice": precision_choice,
-                       "total_windows": total_windows, "strong_leg_windows": args.strong_windows},
+                       "total_windows": total_windows, "strong_leg_windows": args.strong_windows if args.full else 0},
             "mbases_per_s": total_windows / el * W / 1e6,
-            "roofline": roof,
-            "roofline_featurize_group": {
-                "kernels": feat_names, "path": "lean (no token planes)" if lean else "planes", "bound": "hbm", "achieved": feat_bytes / G / (feat_ms * 1e-3) / 1e9,
-                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": feat_bytes / G / (feat_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "algorithmic_bytes_per_step": feat_bytes / G, "ms_per_step": feat_ms,
-                # the same time against what a design that writes the token planes has to move (rounds 3-4: 2-bit bases + ops in, planes + receptive
-                # fields out): the lean path does not move those bytes — it removed them — so its own fraction above is the smaller number
-                "planes_path_equivalent": {"algorithmic_bytes_per_step": (per_job["read_bytes"] / 5.0 + per_job["op_bytes"] + plane_bytes + tokens * 5 * 31 * 2.0) / G,
-                                           "frac": (per_job["read_bytes"] / 5.0 + per_job["op_bytes"] + plane_bytes + tokens * 5 * 31 * 2.0) / G / (feat_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}},
-            "roofline_next_kernels": roof_next, "repeat_ms_per_step": [r * 1e3 / args.steps for r in repeats], "stage_ms_per_step": {"featurize": feat_ms, "model": model_ms},
-            "end_to_end": e2e,
-            "sustained": sustained,
-            "sensitivity": sensitivity,
-            "self_check": check,
-            "kernels": kern,
         }
-        if not args.no_cpu_baseline and world == 1:   # the CPU leg is reported at N=1 only
-            out["cpu_baseline"] = cpu_baseline(synth.SEED + 2)
+        if args.full:
+            kern = {k: {"ms_total": v[0], "calls": v[1], "avg_us": 1e3 * v[0] / max(v[1], 1)} for k, v in tm.items()}
+            lean = os.environ.get("HERRO_FEATURIZE_PLANES", "0") in ("", "0")   # the library's default path (k_rows); HERRO_FEATURIZE_PLANES=1: the planes path (k_tokens), for the A/B
+            feat_names = ["cols", "win", "layout", "rows", "tokens", "supgather", "rf_quals"]
+            feat_ms = sum(tm[k][0] for k in feat_names if k in tm) / timed_steps
+            model_ms = sum(v[0] for k, v in tm.items() if k not in feat_names) / timed_steps
+            # ---- algorithmic work per launch (one launch = G steps = G*batch windows); DESIGN.md §4/§5
+            per_job = {k: float(v) for k, v in st.items()}
+            n_cols = 1 + N_OVL
+            tokens = per_job["sum_supported"]
+            D, FF, C1, C2, KW, NL = 256, 1024, 64, 128, 3, 4
+            # What featurize has to move.  In: the 2-bit bases (1/5 of bases + qualities) and the binary ops.  Out, planes
+            # path: the TOKEN planes (31 L' bytes per window) + the receptive-field records.  Out, lean path (round 5): no planes — the
+            # receptive-field records (16 bytes per informative row and column, 5 quality bytes read for each), the decoder's votes (three
+            # bit planes over the window's positions + a byte per insertion row) and the informative-row lists (8 bytes per row).
+            n_launch_windows = G * args.batch
+            rf_bytes = tokens * 31 * (16.0 + 5.0)
+            vote_bytes = n_launch_windows * 3 * ((W + 31) // 32) * 4 + max(per_job["sum_len"] - n_launch_windows * W, 0.0) + 8.0 * tokens
+            plane_bytes = per_job["out_bytes"] / 2.0
+            feat_bytes = per_job["read_bytes"] / 5.0 + per_job["op_bytes"] + rf_bytes + (vote_bytes if lean else plane_bytes)
+            alg = {  # name -> (bound, work per launch, unit)
+                "tokens": ("hbm", per_job["out_bytes"] / 2.0, "B"),                                      # the token planes written
+                "conv_fused": ("mfma", 2.0 * tokens * 31 * (KW * C1) * C2, "F"),
+                "layers_fused": ("mfma", NL * (2.0 * tokens * D * 3 * D + 2.0 * tokens * D * D + 4.0 * tokens * D * FF), "F"),
+                "cols": ("hbm", per_job["read_bytes"] / 5.0 + per_job["op_bytes"], "B"),              # 2-bit bases + ops read
+                "rows": ("hbm", n_launch_windows * 30 * 3 * ((W + 31) // 32) * 4 + vote_bytes, "B"),  # the selected columns' planes read once more, votes + lists written
+                "patch_conv1": ("hbm", tokens * 31 * KW * C1 * 4, "B"),                               # y1 hi/lo written
+                "conv2_gemm": ("mfma", 2.0 * tokens * 31 * (KW * C1) * C2, "F"),
+                "fc_gemm": ("mfma", 2.0 * tokens * (31 * C2) * D, "F"),
+                "qkv_gemm": ("mfma", 2.0 * tokens * D * 3 * D, "F"),
+                "proj_gemm": ("mfma", 2.0 * tokens * D * D, "F"),
+                "ff1_gemm": ("mfma", 2.0 * tokens * D * FF, "F"),
+                "ff2_gemm": ("mfma", 2.0 * tokens * FF * D, "F"),
+            }
+            tj = None
+            tpath = os.path.join(ROOT, "profiles", "traffic.json")     # written by tools/pmc_traffic.py from a --pmc run
+            if os.path.exists(tpath):
+                tj = json.load(open(tpath))
+                if tj.get("precision", 1) != args.precision:
+                    tj = None                                           # counters of another operand format: not this run's traffic
+
+            def roof_of(k):
+                avg_s = tm[k][0] / max(tm[k][1], 1) * 1e-3
+                bound, work, _ = alg[k]
+                # PMC bytes were collected per launch of tj["windows_per_launch"] windows; every kernel's traffic is proportional to
+                # the windows it processes, so it is scaled to this run's launch size
+                traffic = (tj["kernels"][k]["hbm_bytes_corrected"] / tj.get("windows_per_launch", tj["group"] * 128) * G * args.batch
+                           if tj and k in tj.get("kernels", {}) else None)
+                if bound == "hbm":
+                    return {"kernel": k, "bound": "hbm", "achieved": work / avg_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "frac": work / avg_s / 1e9 / HBM_PEAK_GBS, "traffic": traffic,
+                            "algorithmic_bytes_per_launch": work, "launch_us": avg_s * 1e6, "windows_per_launch": G * args.batch}
+                terms = MFMA_TERMS.get(args.precision, 1)
+                return {"kernel": k, "bound": "mfma", "achieved": work / avg_s / 1e12, "peak": MFMA_PEAK_TF,
+                        "unit": "TFLOP/s", "frac": work / avg_s / 1e12 / MFMA_PEAK_TF, "traffic": traffic,
+                        "algorithmic_flops_per_launch": work, "launch_us": avg_s * 1e6, "windows_per_launch": G * args.batch,
+                        "note": f"algorithmic 2MNK flops; this precision issues {terms} MFMA product(s) per algorithmic product in the "
+                                "encoder GEMMs (issued-MFMA fraction = frac x that)"}
+            ranked = sorted((k for k in tm if k in alg), key=lambda k: -tm[k][0])
+            roof = roof_of(ranked[0])                                   # the dominant kernel
+            roof_next = [roof_of(k) for k in ranked[1:3]]               # the two behind it (the top two trade places between launch sizes)
+            out.update({
+                "roofline": roof,
+                "roofline_featurize_group": {
+                    "kernels": feat_names, "path": "lean (no token planes)" if lean else "planes", "bound": "hbm", "achieved": feat_bytes / G / (feat_ms * 1e-3) / 1e9,
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": feat_bytes / G / (feat_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                    "algorithmic_bytes_per_step": feat_bytes / G, "ms_per_step": feat_ms,
+                    # the same time against what a design that writes the token planes has to move (rounds 3-4: 2-bit bases + ops in, planes + receptive
+                    # fields out): the lean path does not move those bytes — it removed them — so its own fraction above is the smaller number
+                    "planes_path_equivalent": {"algorithmic_bytes_per_step": (per_job["read_bytes"] / 5.0 + per_job["op_bytes"] + plane_bytes + tokens * 5 * 31 * 2.0) / G,
+                                               "frac": (per_job["read_bytes"] / 5.0 + per_job["op_bytes"] + plane_bytes + tokens * 5 * 31 * 2.0) / G / (feat_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}},
+                "roofline_next_kernels": roof_next, "repeat_ms_per_step": [r * 1e3 / args.steps for r in repeats], "stage_ms_per_step": {"featurize": feat_ms, "model": model_ms},
+                "end_to_end": e2e,
+                "sustained": sustained,
+                "sensitivity": sensitivity,
+                "self_check": check,
+                "kernels": kern,
+            })
+            if not args.no_cpu_baseline and world == 1:   # the CPU leg is reported at N=1 only
+                out["cpu_baseline"] = cpu_baseline(synth.SEED + 2)
     for j in [j for js in jobs for j in js] + ([rem_job] if rem_job else []):
         j.close()
     for c in ctxs:
         c.close()
     # ---- the sharded data path on ONE fixed job (every rank takes part; figures on rank 0, same JSON line)
     strong_failed = strong_hung = False
-    if args.strong_windows > 0:
+    if args.full and args.strong_windows > 0:
         from herro_amd import shard
         # The measured line must not be lost to the extra leg — neither to an exception nor to a hang (a rank that fails before a
         # send leaves its peers waiting in a receive for ever).  The leg runs on a worker thread under a deadline; a rank on which
@@ -712,12 +782,12 @@ def main():
             if isinstance(strong, dict) and "windows_per_s" in strong and out.get("end_to_end"):
                 strong["vs_end_to_end"] = strong["windows_per_s"] / (out["end_to_end"]["windows_per_s"] or 1.0)
     # ---- a short run's timed region is a millisecond or two: the default-size figure of the same leg goes into the same line
-    lr_steps = 256 if args.long_run_steps is None else args.long_run_steps
+    lr_steps = (256 if args.long_run_steps is None else args.long_run_steps) if args.full else 0
     if rank == 0 and world == 1 and lr_steps > 0 and args.steps < 64 and time.time() - T_PROCESS_START > 240:
         out["long_run"] = {"skipped": "the legs above took more than 240 s: the extra run is left out so that the line goes out in time"}
     elif rank == 0 and world == 1 and lr_steps > 0 and args.steps < 64:
         import subprocess
-        cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(lr_steps), "--warmup", "8", "--no-cpu-baseline", "--self-check", "0", "--e2e-jobs", "0",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--steps", str(lr_steps), "--warmup", "8", "--no-cpu-baseline", "--self-check", "0", "--e2e-jobs", "0",
                "--strong-windows", "0", "--repeats", "1", "--long-run-steps", "0", "--precision", str(args.precision), "--batch", str(args.batch),
                "--sustained", str(2.0 if args.sustained is None else args.sustained), "--sensitivity", "0"]
         try:
@@ -731,7 +801,8 @@ def main():
         except Exception as e:   # never the measured line
             out["long_run"] = {"error": repr(e)}
     if rank == 0:
-        out["strong_ok"] = (not strong_failed) if args.strong_windows > 0 else None
+        if args.full:
+            out["strong_ok"] = (not strong_failed) if args.strong_windows > 0 else None
         print(json.dumps(out), flush=True)
     if strong_failed:
         # The measured line is out (with strong_ok = false).  On one GPU a broken sharded path also shows in the exit status (3); on

@@ -174,13 +174,28 @@ def save_raw(path: str, raw: dict[str, np.ndarray], hp: Hyper) -> None:
 
 
 def default_model_file(cache_dir: str, hp: Hyper = Hyper(), seed: int = 0x48455252) -> tuple[str, dict[str, np.ndarray]]:
-    """Writes (once) the random-init flat file used by tests / smoke / bench; returns (path, raw)."""
+    """Writes (once) the random-init flat file used by tests / smoke / bench; returns (path, raw).  When cache_dir cannot be
+    written (a checkout the running user does not own), the file goes to the user's cache directory, or else to the
+    temporary directory: its bytes are the same wherever it lies."""
     import os
-    os.makedirs(cache_dir, exist_ok=True)
+    import tempfile
     raw = random_raw_params(hp, seed)
     var = "" if (hp.act, hp.norm_first, hp.pe, hp.final_norm, hp.bn, hp.n_heads, hp.d_ff) == (0, 1, 0, 1, 1, 8, 1024) else f"_v{hp.act}{hp.norm_first}{hp.pe}{hp.final_norm}{hp.bn}_{hp.n_heads}_{hp.d_ff}"
-    path = os.path.join(cache_dir, f"herro_random_{seed:x}_{hp.kw}_{hp.c1}_{hp.c2}_{hp.d_model}_{hp.n_layers}{var}.hrro")
-    if not os.path.exists(path):
-        export(raw, hp, path + ".tmp")
-        os.replace(path + ".tmp", path)
-    return path, raw
+    name = f"herro_random_{seed:x}_{hp.kw}_{hp.c1}_{hp.c2}_{hp.d_model}_{hp.n_layers}{var}.hrro"
+    user_cache = os.path.join(os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache"), "herro_amd")
+    err = None
+    for d in (cache_dir, user_cache, os.path.join(tempfile.gettempdir(), f"herro_amd_{os.getuid()}")):
+        path = os.path.join(d, name)
+        if os.path.exists(path):
+            return path, raw
+        tmp = f"{path}.{os.getpid()}.tmp"   # one name per process: several ranks may write the file at once
+        try:
+            os.makedirs(d, exist_ok=True)
+            export(raw, hp, tmp)
+            os.replace(tmp, path)
+            return path, raw
+        except OSError as e:
+            err = e
+            if os.path.exists(tmp):
+                os.remove(tmp)
+    raise err

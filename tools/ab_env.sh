@@ -6,7 +6,7 @@
 tag=$1; var=$2; vals=$3; shift 3
 mkdir -p gpurun_out/$tag
 if [ -n "$*" ]; then timeout 600 python -m pytest "$@" -x -q -m gpu 2>&1 | grep -v Warn | tail -4 | tee gpurun_out/$tag/tests.log; fi
-q="--no-cpu-baseline --self-check 2 --e2e-jobs 0 --strong-windows 0 --repeats 1"
+q="--full --no-cpu-baseline --self-check 2 --e2e-jobs 0 --strong-windows 0 --repeats 1"
 for v in $vals; do
   env $var=$v timeout 100 python bench.py $q > gpurun_out/$tag/${var}${v}.json 2>> gpurun_out/$tag/bench.err < /dev/null
   env $var=$v timeout 100 python bench.py $q --steps 20 --warmup 5 > gpurun_out/$tag/${var}${v}_driver.json 2>> gpurun_out/$tag/bench.err < /dev/null

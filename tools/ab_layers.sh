@@ -4,7 +4,7 @@
 tag=${1:-ab}
 mkdir -p gpurun_out/$tag
 timeout 500 python -m pytest ${TESTS:-tests/test_gpu_model.py tests/test_gpu_e2e.py} -x -q -m gpu 2>&1 | grep -v Warning | tail -6 > gpurun_out/$tag/tests.log; tail -3 gpurun_out/$tag/tests.log
-q="--no-cpu-baseline --self-check 2 --e2e-jobs 0 --strong-windows 0 --repeats 1"
+q="--full --no-cpu-baseline --self-check 2 --e2e-jobs 0 --strong-windows 0 --repeats 1"
 for v in 1 0; do
 HERRO_LAYERS_Q=$v timeout 100 python bench.py $q --streams 1 > gpurun_out/$tag/q${v}_s1.json 2>> gpurun_out/$tag/bench.err < /dev/null
 HERRO_LAYERS_Q=$v timeout 100 python bench.py $q > gpurun_out/$tag/q${v}_s2.json 2>> gpurun_out/$tag/bench.err < /dev/null

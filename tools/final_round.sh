@@ -8,7 +8,7 @@ timeout 600 python -m pytest tests -x -q -m gpu 2>&1 | grep -v Warning | tail -1
 cat gpurun_out/$tag/tests.log | tail -5
 bash tools/profile_round.sh $tag > gpurun_out/$tag/profile_round.log 2>&1
 bash tools/pmc_round.sh $tag > gpurun_out/$tag/pmc_round.log 2>&1
-q="--no-cpu-baseline --self-check 0 --e2e-jobs 0 --strong-windows 0 --repeats 1"
+q="--full --no-cpu-baseline --self-check 0 --e2e-jobs 0 --strong-windows 0 --repeats 1"
 HERRO_TILE_PACK=0 timeout 120 python bench.py $q > gpurun_out/$tag/ab_pack0.json 2> /dev/null < /dev/null
 HERRO_TILE_PACK=0 timeout 120 python bench.py $q --steps 20 --warmup 5 > gpurun_out/$tag/ab_pack0_driver.json 2> /dev/null < /dev/null
 python - <<PY

@@ -5,7 +5,7 @@ tag=${1:-rX}
 out=gpurun_out/${tag}_pmc
 mkdir -p $out
 export TMPDIR=/tmp
-cmd="python bench.py --no-cpu-baseline --self-check 0 --streams 1 --e2e-jobs 0 --repeats 0 --settle 0 --steps 96 --warmup 32"
+cmd="python bench.py --full --no-cpu-baseline --self-check 0 --streams 1 --e2e-jobs 0 --repeats 0 --settle 0 --steps 96 --warmup 32"
 timeout 240 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/f -o f -- $cmd > $out/f.json 2> $out/f.err < /dev/null
 timeout 240 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/w -o w -- $cmd > $out/w.json 2> $out/w.err < /dev/null
 ff=$(find $out/f -name "*counter_collection.csv" | head -1)

@@ -6,7 +6,7 @@
 tag=${1:-prof}; shift
 mkdir -p gpurun_out/$tag
 for size in "" "--steps 20 --warmup 5"; do
-HERRO_LIB=$PWD/herro_amd/libherro_amd_prof.so HERRO_PROF=1 timeout 200 python bench.py --no-cpu-baseline --self-check 0 --streams 1 --e2e-jobs 0 --strong-windows 0 --repeats 0 --settle 0 $size "$@" 2>&1 | grep -E "^PROF|^\{" | python -c "
+HERRO_LIB=$PWD/herro_amd/libherro_amd_prof.so HERRO_PROF=1 timeout 200 python bench.py --full --no-cpu-baseline --self-check 0 --streams 1 --e2e-jobs 0 --strong-windows 0 --repeats 0 --settle 0 $size "$@" 2>&1 | grep -E "^PROF|^\{" | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -6,7 +6,7 @@ out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o $tag -- \
-  python bench.py --no-cpu-baseline --self-check 0 --streams 1 --e2e-jobs 0 --repeats 0 --settle 0 > $out/bench_streams1.json 2> $out/prof.err < /dev/null
+  python bench.py --full --no-cpu-baseline --self-check 0 --streams 1 --e2e-jobs 0 --repeats 0 --settle 0 > $out/bench_streams1.json 2> $out/prof.err < /dev/null
 f=$(find $out/prof -name "*kernel_stats.csv" | head -1)
 if [ -n "$f" ]; then cp "$f" $out/kernel_stats.csv; fi
 rm -rf $out/prof

@@ -4,7 +4,7 @@
 tag=${1:-q}
 mkdir -p gpurun_out/$tag
 timeout 400 python -m pytest ${TESTS:-tests/test_gpu_model.py tests/test_gpu_e2e.py} -x -q -m gpu 2>&1 | grep -v Warning | tail -6 > gpurun_out/$tag/tests.log; tail -3 gpurun_out/$tag/tests.log
-q="--no-cpu-baseline --self-check 2 --e2e-jobs 0 --strong-windows 0 --repeats 1"
+q="--full --no-cpu-baseline --self-check 2 --e2e-jobs 0 --strong-windows 0 --repeats 1"
 timeout 100 python bench.py $q ${BENCH_ARGS} > gpurun_out/$tag/bench.json 2> gpurun_out/$tag/bench.err < /dev/null
 timeout 100 python bench.py $q --steps 20 --warmup 5 ${BENCH_ARGS} > gpurun_out/$tag/bench_driver.json 2>> gpurun_out/$tag/bench.err < /dev/null
 cat gpurun_out/e2e_errors.json 2>/dev/null | head -c 600; echo

@@ -5,7 +5,7 @@
 tag=$1; out=gpurun_out/$tag; mkdir -p $out
 timeout 300 python -m pytest tests/test_gpu_sib_retry.py tests/test_gpu_model.py -x -q -m gpu -s 2>&1 | grep -v Warn | grep -E "passed|failed|Error|error|sibling tiles vs|assert" | tail -12 | tee $out/tests.log
 export HERRO_LIB=$PWD/herro_amd/libherro_amd_prof.so
-q="--no-cpu-baseline --self-check 2 --e2e-jobs 0 --strong-windows 0 --repeats 1 --long-run-steps 0"
+q="--full --no-cpu-baseline --self-check 2 --e2e-jobs 0 --strong-windows 0 --repeats 1 --long-run-steps 0"
 for rep in 1 2; do for v in 0 16384 32768; do
   HERRO_CONV_CHUNK=$v timeout 100 python bench.py $q --streams 1 > $out/chunk${v}_s1_$rep.json 2>> $out/bench.err < /dev/null
 done; done

@@ -2,7 +2,7 @@
 # same-box A/B of two builds of the library (release defaults): herro_amd/libherro_old.so (the tree before the precision-6 work: r5y) against the current one
 # usage: gpurun --timeout 500 -- bash tools/r5_ab_old.sh r5z2
 tag=$1; out=gpurun_out/$tag; mkdir -p $out
-q="--no-cpu-baseline --self-check 2 --e2e-jobs 0 --strong-windows 0 --repeats 1 --long-run-steps 0"
+q="--full --no-cpu-baseline --self-check 2 --e2e-jobs 0 --strong-windows 0 --repeats 1 --long-run-steps 0"
 for rep in 1 2; do for v in old new; do
   lib=$PWD/herro_amd/libherro_amd.so; [ $v = old ] && lib=$PWD/herro_amd/libherro_old.so
   HERRO_LIB=$lib timeout 100 python bench.py $q --steps 20 --warmup 5 > $out/${v}_driver_$rep.json 2>> $out/err < /dev/null

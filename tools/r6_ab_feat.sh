@@ -3,7 +3,7 @@
 # usage: gpurun --timeout 900 -- bash tools/r6_ab_feat.sh tag libA.so libB.so [timerA.so timerB.so]
 tag=$1; shift
 out=gpurun_out/$tag; mkdir -p $out
-q="--no-cpu-baseline --self-check 0 --e2e-jobs 0 --strong-windows 0 --repeats 0 --settle 0 --long-run-steps 0 --sustained 0 --sensitivity 0"
+q="--full --no-cpu-baseline --self-check 0 --e2e-jobs 0 --strong-windows 0 --repeats 0 --settle 0 --long-run-steps 0 --sustained 0 --sensitivity 0"
 for rep in 1 2; do
 for lib in "$@"; do
   for st in 1 0; do

@@ -3,7 +3,7 @@
 # usage: gpurun --timeout 900 -- bash tools/r6_ab_layers.sh tag [more libs]
 tag=$1; shift
 out=gpurun_out/$tag; mkdir -p $out
-q="--no-cpu-baseline --self-check 0 --e2e-jobs 0 --strong-windows 0 --repeats 0 --settle 0 --long-run-steps 0 --streams 1"
+q="--full --no-cpu-baseline --self-check 0 --e2e-jobs 0 --strong-windows 0 --repeats 0 --settle 0 --long-run-steps 0 --streams 1"
 for rep in 1 2; do
 for lib in ${@:-libherro_amd_r5prof.so libherro_amd_prof.so}; do
   for p in 4 5; do

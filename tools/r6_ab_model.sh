@@ -3,7 +3,7 @@
 # usage: gpurun --timeout 900 -- bash tools/r6_ab_model.sh tag libA.so libB.so
 tag=$1; shift
 out=gpurun_out/$tag; mkdir -p $out
-q="--no-cpu-baseline --self-check 0 --e2e-jobs 0 --strong-windows 0 --repeats 2 --long-run-steps 0 --sustained 0 --sensitivity 0"
+q="--full --no-cpu-baseline --self-check 0 --e2e-jobs 0 --strong-windows 0 --repeats 2 --long-run-steps 0 --sustained 0 --sensitivity 0"
 for rep in 1 2; do
 for lib in "$@"; do
   for sz in 20 256; do

@@ -2,7 +2,7 @@
 # round 6: the end_to_end leg with the job's windows / descriptors built on the device (default) against the host build of rounds 3-5, one box; + the host timeline of both
 # usage: gpurun --timeout 1200 -- bash tools/r6_e2e_ab.sh tag
 tag=${1:-r6e2e}; out=gpurun_out/$tag; mkdir -p $out
-q="--no-cpu-baseline --self-check 0 --strong-windows 0 --repeats 0 --steps 64 --warmup 32 --sustained 0 --sensitivity 0 --long-run-steps 0"
+q="--full --no-cpu-baseline --self-check 0 --strong-windows 0 --repeats 0 --steps 64 --warmup 32 --sustained 0 --sensitivity 0 --long-run-steps 0"
 for rep in 1 2; do
   for hb in 0 1; do
     for nf in 4 6; do

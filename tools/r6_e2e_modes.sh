@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 6: end_to_end leg, feeder modes and counts with the device build (one box)   usage: gpurun --timeout 1200 -- bash tools/r6_e2e_modes.sh tag
 tag=${1:-r6m}; out=gpurun_out/$tag; mkdir -p $out
-q="--no-cpu-baseline --self-check 0 --strong-windows 0 --repeats 0 --steps 64 --warmup 32 --sustained 0 --sensitivity 0 --long-run-steps 0"
+q="--full --no-cpu-baseline --self-check 0 --strong-windows 0 --repeats 0 --steps 64 --warmup 32 --sustained 0 --sensitivity 0 --long-run-steps 0"
 for rep in 1 2; do
   for mode in serial producer; do
     for nf in 2 3 4 6; do

@@ -3,7 +3,7 @@
 # against the number of hardware queues.   usage: gpurun --timeout 1200 -- bash tools/r6_e2e_trace.sh tag
 tag=${1:-r6t}; out=gpurun_out/$tag; mkdir -p $out
 export TMPDIR=/tmp
-q="--no-cpu-baseline --self-check 0 --strong-windows 0 --repeats 0 --steps 64 --warmup 32 --sustained 0 --sensitivity 0 --long-run-steps 0"
+q="--full --no-cpu-baseline --self-check 0 --strong-windows 0 --repeats 0 --steps 64 --warmup 32 --sustained 0 --sensitivity 0 --long-run-steps 0"
 for hq in ${QUEUES:-4 8 16}; do
   GPU_MAX_HW_QUEUES=$hq timeout 200 python bench.py $q 2>/dev/null | python -c "
 import sys,json

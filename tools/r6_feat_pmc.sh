@@ -2,7 +2,7 @@
 # round 6: the three figures VERDICT r5 item 2 names — featurize ms per step with the driver's arguments, SQ_INSTS_VALU of the featurize kernels, their HBM traffic (separate --pmc passes).
 # usage: gpurun --timeout 900 -- bash tools/r6_feat_pmc.sh tag
 tag=${1:-r6pmc}; out=gpurun_out/$tag; mkdir -p $out; export TMPDIR=/tmp
-q="--no-cpu-baseline --self-check 0 --e2e-jobs 0 --strong-windows 0 --long-run-steps 0 --sustained 0 --sensitivity 0"
+q="--full --no-cpu-baseline --self-check 0 --e2e-jobs 0 --strong-windows 0 --long-run-steps 0 --sustained 0 --sensitivity 0"
 timeout 200 python bench.py $q --steps 20 --warmup 5 > $out/driver.json 2> $out/bench.err < /dev/null
 cmd="python bench.py $q --streams 1 --repeats 0 --settle 0 --steps 64 --warmup 32"
 timeout 150 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/f -o f -- $cmd > /dev/null 2> $out/f.err < /dev/null

@@ -3,7 +3,7 @@
 # (A/B switches exist only in the timer build; HERRO_PROF unset: no phase timers run).   usage: gpurun --timeout 600 -- bash tools/r6_plan_gap.sh tag
 tag=${1:-r6pg}; out=gpurun_out/$tag; mkdir -p $out
 timeout 200 python tools/r6_infer_host_time.py 2>&1 | grep -v Warn | tee $out/infer_host_time.txt
-q="--no-cpu-baseline --self-check 0 --e2e-jobs 0 --strong-windows 0 --long-run-steps 0 --sustained 0 --sensitivity 0 --steps 20 --warmup 5"
+q="--full --no-cpu-baseline --self-check 0 --e2e-jobs 0 --strong-windows 0 --long-run-steps 0 --sustained 0 --sensitivity 0 --steps 20 --warmup 5"
 for rep in 1 2; do
   for f in -1 1 0; do
     HERRO_LIB=$PWD/herro_amd/libherro_amd_prof.so HERRO_RF_FUSED=$f timeout 200 python bench.py $q > $out/fused${f}_$rep.log 2>&1

@@ -5,7 +5,7 @@ tag=${1:-r6q}
 out=gpurun_out/$tag; mkdir -p $out
 timeout 800 python -m pytest ${2:-tests/test_gpu_model.py tests/test_gpu_e2e.py tests/test_gpu_lean.py tests/test_gpu_sib_retry.py} -x -q -m gpu -s 2>&1 | grep -v Warning | tail -60 > $out/tests.log; tail -5 $out/tests.log
 cp gpurun_out/e2e_errors.json $out/e2e_logit_errors.json 2>/dev/null
-q="--no-cpu-baseline --self-check 2 --e2e-jobs 0 --strong-windows 0 --repeats 1 --long-run-steps 0"
+q="--full --no-cpu-baseline --self-check 2 --e2e-jobs 0 --strong-windows 0 --repeats 1 --long-run-steps 0"
 timeout 150 python bench.py $q --streams 1 > $out/s1.json 2>> $out/bench.err < /dev/null
 timeout 150 python bench.py $q --streams 1 --precision 4 > $out/s1_p4.json 2>> $out/bench.err < /dev/null
 timeout 150 python bench.py $q > $out/default.json 2>> $out/bench.err < /dev/null

@@ -3,7 +3,7 @@
 # usage: gpurun --timeout 900 -- bash tools/r6_value_streams.sh tag
 tag=${1:-r6vs}; out=gpurun_out/$tag; mkdir -p $out
 ( time timeout 900 python -m pytest tests -q -m gpu -x 2>&1 | grep -v Warning | tail -6 ) > $out/gpu_tests.log 2>&1; tail -4 $out/gpu_tests.log
-q="--no-cpu-baseline --self-check 0 --e2e-jobs 0 --strong-windows 0 --long-run-steps 0 --sustained 0 --sensitivity 0 --steps 20 --warmup 5"
+q="--full --no-cpu-baseline --self-check 0 --e2e-jobs 0 --strong-windows 0 --long-run-steps 0 --sustained 0 --sensitivity 0 --steps 20 --warmup 5"
 for rep in 1 2; do
   for mj in 1 2; do
     timeout 200 python bench.py $q --min-jobs $mj > $out/mj${mj}_$rep.log 2>&1

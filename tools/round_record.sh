@@ -7,7 +7,7 @@ out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
 ( time timeout 900 python -m pytest tests -q -m gpu 2>&1 | grep -v Warning | tail -12 ) > $out/gpu_tests.log 2>&1; tail -6 $out/gpu_tests.log
-q="--no-cpu-baseline --self-check 0 --e2e-jobs 0 --strong-windows 0 --long-run-steps 0 --sustained 0 --sensitivity 0"
+q="--full --no-cpu-baseline --self-check 0 --e2e-jobs 0 --strong-windows 0 --long-run-steps 0 --sustained 0 --sensitivity 0"
 timeout 150 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o $tag -- python bench.py $q --streams 1 --repeats 0 > $out/bench_streams1.json 2> $out/prof.err < /dev/null
 f=$(find $out/prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $out/kernel_stats.csv; rm -rf $out/prof
 cmd="python bench.py $q --streams 1 --repeats 0 --settle 0 --steps 64 --warmup 32"
@@ -21,7 +21,7 @@ timeout 200 rocprofv3 --pmc SQ_WAVES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_WAIT_AN
 fm=$(find $out/m -name "*counter_collection.csv" | head -1); [ -n "$fm" ] && python tools/pmc_summary.py "$fm" "k_" > $out/pmc_sq_mfma_counters.txt 2>&1; rm -rf $out/m
 # (the full default-size line is left out since round 5: the driver-arguments line carries the default-size figure as long_run; GPU budget)
 : > $out/bench.err
-timeout 500 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_args.json 2>> $out/bench.err < /dev/null
+timeout 500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_args.json 2>> $out/bench.err < /dev/null
 head -14 $out/kernel_stats.csv 2>/dev/null | cut -c1-140; cat $out/traffic_summary.txt; grep -E "k_layers|k_conv|k_fc|k_cols|k_rows|k_win|k_rfq|k_layout" $out/pmc_sq_mfma_counters.txt | cut -c1-330
 python - <<PY
 import json,glob
