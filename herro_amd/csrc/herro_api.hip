@@ -3073,6 +3073,27 @@ int64_t herro_debug_job_rf(herro_job* job, uint32_t w, uint8_t* out, uint64_t ca
   return (int64_t)n;
 }
 
+// the base logits of every informative row of the job (job order, n_rows x 5) replace the model's, on the device and in the host copy; the consensus
+// is dropped, so the next herro_job_consensus / herro_job_consensus_fasta decodes these (tests plant ties, infinities and NaNs for the argmax)
+int herro_debug_job_set_base_logits(herro_job* job, const float* base, uint64_t n_rows) {
+  if (!job || (n_rows && !base)) return HERRO_E_INVALID;
+  herro_ctx* ctx = job->ctx;
+  int rc = job_sync(job);
+  if (rc) return rc;
+  if (!job->inferred) { ctx->err = "herro_job_infer has not run"; return HERRO_E_STATE; }
+  const uint64_t tot = job->sup_off.back();
+  if (n_rows != tot) { ctx->err = "n_rows " + std::to_string(n_rows) + " != the job's informative rows " + std::to_string(tot); return HERRO_E_INVALID; }
+  if ((rc = logits_to_host(job))) return rc;   // the model pass is settled (and its info logits on the host) before its base logits are replaced
+  if (tot) {
+    std::memcpy(job->h_base.data(), base, tot * 20);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpy(job->d_base, base, tot * 20, hipMemcpyHostToDevice));
+  }
+  job->consensus_done = false;
+  job->consensus_on_host = false;
+  return HERRO_OK;
+}
+
 // which: 0 ops (u32), 1 OwDesc, 2 WinDesc, 3 tile_win (u32), 4 tile_r0 (u32), 5 tgt_win_off (u32).
 // Returns the element count, *ptr the array, *elem_bytes the element size.
 int64_t herro_debug_job_array(herro_job* job, int which, const void** ptr, uint32_t* elem_bytes) {

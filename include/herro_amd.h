@@ -283,6 +283,9 @@ uint32_t herro_debug_e4m3(float x);                   /* host f32 -> OCP e4m3 (r
 int herro_debug_sib_fault(herro_ctx* ctx);            /* raises the context's sibling-tile error word as a tile that timed out would: the next fetch repeats its job's model pass without sibling tiles */
 int herro_debug_force_precision(herro_ctx* ctx, int on); /* tests: herro_set_precision / herro_load_model skip the calibration gate (to MEASURE a mode the model's calibration refuses) */
 int herro_debug_sib_retries(const herro_ctx* ctx);    /* model passes repeated that way on this context */
+/* tests: replaces the base logits of the job's informative rows (after herro_job_infer; n_rows must be all of them, job order, 5 floats each) on the device and
+ * in the host copy, and drops the consensus: the next herro_job_consensus or herro_job_consensus_fasta decodes these */
+int herro_debug_job_set_base_logits(herro_job* job, const float* base, uint64_t n_rows);
 
 /* Host-only test hook for the token-tile plan of the fused transformer stack (herro_job_infer): n windows of cnt[i]
  * informative rows (1..64) -> order[k] = the window that is k-th in the launch's token stream; returns the number of
