@@ -32,6 +32,8 @@ EXPORTS = [
     "herro_pool_correct", "herro_pool_result", "herro_pool_groups_taken", "herro_pool_skipped", "herro_debug_pool_fake", "herro_job_create_status", "herro_host_register", "herro_host_unregister", "herro_debug_zero_copy_jobs",
     "herro_fastx_read", "herro_reads_count", "herro_reads_seq", "herro_reads_qual", "herro_reads_off", "herro_reads_ids",
     "herro_reads_descs", "herro_reads_free", "herro_write_window_features", "herro_job_write_features",
+    "herro_paf_parse_coords", "herro_align_overlaps", "herro_aligned_alignments", "herro_aligned_scores", "herro_aligned_failed",
+    "herro_aligned_free",
 ]
 
 
@@ -156,6 +158,17 @@ def lib():
         L.herro_oec_read_indexed.argtypes = [C.c_char_p, vp, vp, i32, vp, u64]
         L.herro_paf_parse_view.restype = vp
         L.herro_paf_parse_view.argtypes = [C.c_char_p, u64, vp, vp, i32, vp, u64]
+        L.herro_paf_parse_coords.restype = vp
+        L.herro_paf_parse_coords.argtypes = [C.c_char_p, u64, vp, vp, i32, vp, u64]
+        L.herro_align_overlaps.argtypes = [vp, u32, vp, vp]
+        L.herro_aligned_alignments.restype = vp
+        L.herro_aligned_alignments.argtypes = [vp]
+        L.herro_aligned_scores.restype = vp
+        L.herro_aligned_scores.argtypes = [vp]
+        L.herro_aligned_failed.restype = u32
+        L.herro_aligned_failed.argtypes = [vp]
+        L.herro_aligned_free.restype = None
+        L.herro_aligned_free.argtypes = [vp]
         L.herro_debug_host_ctx.restype = vp
         L.herro_debug_host_ctx.argtypes = [u32, vp, vp]
         L.herro_debug_job_array.restype = C.c_int64
@@ -461,6 +474,33 @@ class Context:
             raise HerroError(code, msg)
         return Job(self, h, len(rids))
 
+    def align(self, rows: np.ndarray):
+        """Base-level alignment of overlaps given by coordinates only (herro_align_overlaps; the `minimap2 -c` step of mm2.rs:15-30
+        plus fix_cigar, aligners.rs:138-250).  rows: u32 [n, >=9] in create_job's layout (qid, qlen, qstart, qend, strand, tid, tlen,
+        tstart, tend).  Returns (rows_out u32 [n, 10] with the trimmed coordinates and the CIGAR lengths, cigars: list of bytes,
+        scores: i32 [n], ok: bool [n]); a failed record keeps its coordinates and gets an empty CIGAR."""
+        rows = np.ascontiguousarray(rows, np.uint32)
+        n = len(rows)
+        arr = (Alignment * max(n, 1))()
+        view = np.frombuffer(arr, dtype=np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True), count=max(n, 1))
+        if n:
+            view["f"][:n, :9] = rows[:, :9]
+        h = C.c_void_p()
+        self._chk(self._l.herro_align_overlaps(self.h, n, C.byref(arr), C.byref(h)))
+        try:
+            out = np.zeros((n, 10), np.uint32)
+            scores = np.zeros(n, np.int32)
+            cigars: list[bytes] = []
+            if n:
+                res = (Alignment * n).from_address(self._l.herro_aligned_alignments(h))
+                rv = np.frombuffer(res, dtype=np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True), count=n)
+                out[:] = rv["f"]
+                scores[:] = np.ctypeslib.as_array(C.cast(self._l.herro_aligned_scores(h), C.POINTER(C.c_int32)), (n,))
+                cigars = [C.string_at(int(p), int(k)) if k else b"" for p, k in zip(rv["p"], out[:, 9])]
+        finally:
+            self._l.herro_aligned_free(h)
+        return out, cigars, scores, out[:, 9] > 0
+
     def create_job_from_paf(self, paf: "Paf", window_size: int) -> "Job":
         """herro_job_create straight from a parsed PAF batch (targets in its order); `paf` must outlive the call."""
         h = self._l.herro_job_create(self.h, len(paf.targets), paf.targets.ctypes.data, paf.aln_off.ctypes.data,
@@ -683,15 +723,26 @@ class Paf:
     appearance, their alignments in file order.  `targets`, `aln_off`, `alns` are what herro_job_create takes;
     the CIGAR pointers inside `alns` stay valid while this object lives.  `names`: the read ids, or a NameIndex built once."""
 
-    def __init__(self, names, text: bytes | None = None, path: str | None = None, core=None, threads: int = 0, view: bool = False):
-        """view=True (with a NameIndex and `text`): no copy of the text — this object keeps `text` alive instead."""
+    def __init__(self, names, text: bytes | None = None, path: str | None = None, core=None, threads: int = 0, view: bool = False,
+                 cigars: bool = True):
+        """view=True (with a NameIndex and `text`): no copy of the text — this object keeps `text` alive instead.
+        cigars=False: a PAF without CIGARs (herro_paf_parse_coords; `text` only) — records for Context.align, cigar_len 0."""
         self.h = None
         self._text = text if view else None
         L = lib()
         core_a = None if core is None else np.ascontiguousarray(core, np.uint8)
         err = C.create_string_buffer(512)
         cptr = None if core_a is None else core_a.ctypes.data
-        if isinstance(names, NameIndex):
+        if not cigars:
+            if text is None:
+                raise ValueError("Paf(cigars=False) parses PAF text only")
+            ix = names if isinstance(names, NameIndex) else NameIndex(names)
+            try:
+                h = L.herro_paf_parse_coords(text, len(text), ix.h, cptr, threads, err, 512)
+            finally:
+                if ix is not names:
+                    ix.close()
+        elif isinstance(names, NameIndex):
             if text is not None and view:
                 h = L.herro_paf_parse_view(text, len(text), names.h, cptr, threads, err, 512)
             elif text is not None:
@@ -717,12 +768,19 @@ class Paf:
         self._alns_ptr = L.herro_paf_alignments(h)
         self.alns = (Alignment * na).from_address(self._alns_ptr) if na else []
 
+    def coords(self) -> np.ndarray:
+        """u32 [n, 10]: qid, qlen, qstart, qend, strand, tid, tlen, tstart, tend, cigar_len in output order (Context.align's rows)."""
+        if not self.n_alns:
+            return np.zeros((0, 10), np.uint32)
+        v = np.frombuffer(self.alns, dtype=np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True), count=self.n_alns)
+        return v["f"].copy()
+
     def rows(self):
         """[(qid, qlen, qstart, qend, strand, tid, tlen, tstart, tend, cigar bytes)] in output order."""
         out = []
         for a in self.alns:
             out.append((a.qid, a.qlen, a.qstart, a.qend, a.strand, a.tid, a.tlen, a.tstart, a.tend,
-                        C.string_at(a.cigar, a.cigar_len)))
+                        C.string_at(a.cigar, a.cigar_len) if a.cigar_len else b""))
         return out
 
     def close(self):
@@ -791,3 +849,14 @@ def job_from_synth(ctx: Context, sb, window_size: int, targets=None) -> Job:
     off[1:] = np.cumsum([y - x for x, y in zip(a0, a1)])
     rows = sb.aln[sel]
     return ctx.create_job(sb.tgt_rid[ts], rows, off, None, window_size, cig_blob=sb.cig, cig_off=sb.cig_off[sel])
+
+
+def aligned_job_args(rids, aln_off, rows_out: np.ndarray, cigars: list[bytes], ok: np.ndarray):
+    """The AlnMode::None counterpart of parse_paf's output (overlaps.rs:340-344): drops the records Context.align failed, regroups
+    aln_off over the targets and returns (rids, rows, aln_off, cigars) for Context.create_job.  Targets keep their place even when
+    all their records failed."""
+    rids = np.ascontiguousarray(rids, np.uint32)
+    aln_off = np.asarray(aln_off, np.int64)
+    ok = np.asarray(ok, bool)
+    kept = np.concatenate([[0], np.cumsum(ok)]).astype(np.int64)
+    return rids, np.ascontiguousarray(rows_out[ok]), kept[aln_off].astype(np.uint64), [c for c, k in zip(cigars, ok) if k]

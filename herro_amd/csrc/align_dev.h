@@ -1,0 +1,38 @@
+// align_dev.h — base-level alignment of overlaps given by coordinates only (align_dev.hip): the GPU counterpart of the
+// `minimap2 -c` step that `herro inference` runs without --read-alns (mm2.rs:15-30), followed by the reference's
+// fix_cigar normalisation (aligners.rs:138-250).  One wave64 per record; the specification is DESIGN.md §9.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace herro {
+
+constexpr int ALIGN_W = 128;                      // == HERRO_ALIGN_BAND: band cells per anti-diagonal
+constexpr uint32_t ALIGN_MAX_CELLS = 1u << 25;    // n + m above this: refused (the -inf sentinel needs the headroom)
+
+struct AlignIn {          // one record (40 B)
+  uint64_t t_woff, q_woff;   // first 2-bit word of the target / query read in the store
+  uint64_t scr_off;          // byte offset of the record's scratch (align_scratch_bytes)
+  uint32_t t0, m;            // T = target bases [t0, t0 + m)
+  uint32_t q0, n;            // query bases [q0, q0 + n) as stored; strand 1 reads them reversed and complemented
+  uint32_t strand, pad;
+};
+
+struct AlignOut {         // (32 B)
+  int32_t score;             // INT32_MIN: failed
+  uint32_t n_ops, ops_off;   // final ops: dense[ops_off .. ops_off + n_ops), each len << 2 | (0 M, 1 I, 2 D)
+  uint32_t failed;
+  uint32_t tdrop0, qdrop0;   // bases the dropped leading indel consumed
+  uint32_t tdrop1, qdrop1;   // ... and the dropped trailing one
+};
+
+// per record: traceback rows (64 B per anti-diagonal: 4 bits per band cell), the band's lo per anti-diagonal, the op list
+inline uint64_t align_scratch_bytes(uint32_t n, uint32_t m) {
+  const uint64_t nd = (uint64_t)n + m + 1;
+  return (nd * (64 + 4 + 4) + 255) & ~(uint64_t)255;
+}
+
+void launch_align(const uint64_t* d_words, const AlignIn* d_in, AlignOut* d_out, uint8_t* d_scr, uint32_t* d_dense,
+                  uint32_t* d_count, uint32_t n_rec, hipStream_t st);
+
+}  // namespace herro

@@ -1,0 +1,282 @@
+// align_dev.hip — banded Gotoh alignment of overlaps given by coordinates only, one wave64 per record.
+//
+// Stands in for the base-level step of `minimap2 -cx ava-ont` that `herro inference` runs when it is not given
+// --read-alns (mm2.rs:15-30), then applies the reference's fix_cigar (aligners.rs:138-250) and drops a trailing indel.
+// The exact specification (scores, band rule, tie order, normalisation) is DESIGN.md §9; tests/align_ref.py restates it
+// in numpy and the kernel is held to it bit for bit.
+//
+// Layout.  The band has W = 128 cells per anti-diagonal d = i + j; lane L holds cells k = 2L and 2L + 1 (i = lo_d + k).
+// Every lane keeps, re-indexed to the band of the diagonal being computed, H / I / D of diagonal d - 1, H of d - 2 and
+// the two sequence codes of its cells.  A cell needs its neighbours at k - 1 (up, diagonal) and k (left): one DPP
+// wave_shr:1 per array.  When the band moves (lo_{d+1} = lo_d + 1) the arrays and the query codes shift down one cell
+// (DPP wave_shl:1, the new top query code enters in lane 63); otherwise the target codes shift up one cell (the new
+// target code enters in lane 0).  The codes that may enter are read before the diagonal is computed (one uniform load
+// each), so the read is off the decision's path.
+//
+// -inf is a sentinel NEG = -2^30.  No cell is masked: cells with i < 0 or j < 0 only ever see -inf-ish inputs and stay
+// below NEG / 2 (n + m <= 2^25 keeps the drift inside int32), cells with i > n or j > m feed no cell of the matrix, and the
+// band decision tests its two cells against the matrix explicitly.  Finite scores are >= -6 (n + m) > NEG / 2.
+//
+// Traceback bits per cell: bits 0-1 the source of H (0 diagonal, 1 I, 2 D), bit 2 "I opened" (from H), bit 3 "D opened";
+// one byte per lane, one coalesced 64-byte row per anti-diagonal, plus lo_d (4 B) — written to the record's scratch.
+// The walk back from (n, m) stages 64 rows at a time in the LDS; every lane walks the same path (uniform control flow,
+// broadcast LDS reads) and lane 0 writes the ops.  fix_cigar, the trim and the score then stream once over the op list.
+#include "align_dev.h"
+
+namespace herro {
+namespace {
+
+constexpr int W = ALIGN_W;
+constexpr int32_t NEG = -(1 << 30);
+constexpr int32_t FINITE = -(1 << 29);   // values below this are -inf
+
+// lane L receives lane L - 1's v (lane 0: fill) / lane L + 1's v (lane 63: fill)
+__device__ __forceinline__ int32_t from_below(int32_t v, int32_t fill) {
+  return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xf, 0xf, false);   // wave_shr:1
+}
+__device__ __forceinline__ int32_t from_above(int32_t v, int32_t fill) {
+  return __builtin_amdgcn_update_dpp(fill, v, 0x130, 0xf, 0xf, false);   // wave_shl:1
+}
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// 2-bit codes of T or Q (strand 1: reversed and complemented, as k_cols stages a reverse-strand query)
+struct Seq {
+  const uint64_t* w;
+  int32_t start, len;
+  uint32_t rev;
+  __device__ __forceinline__ uint32_t at(int32_t x) const {   // 0 outside [0, len): such cells never reach the matrix
+    if (x < 0 || x >= len) return 0;
+    const uint32_t p = (uint32_t)(rev ? start + len - 1 - x : start + x);
+    return ((uint32_t)(w[p >> 5] >> ((p & 31u) * 2u)) & 3u) ^ (rev ? 3u : 0u);
+  }
+};
+
+// one cell: returns H, writes I, D and the traceback nibble
+__device__ __forceinline__ int32_t cell(int32_t up_h, int32_t up_i, int32_t left_h, int32_t left_d, int32_t diag_h,
+                                        uint32_t qc, uint32_t tc, int32_t& I, int32_t& Dv, uint32_t& nib) {
+  const int32_t io = up_h - 6, ie = up_i - 2, dop = left_h - 6, de = left_d - 2;
+  I = max(io, ie);
+  Dv = max(dop, de);
+  const int32_t sd = diag_h + (qc == tc ? 2 : -4);
+  const int32_t H = max(sd, max(I, Dv));
+  const uint32_t src = H == sd ? 0u : (H == I ? 1u : 2u);
+  nib = src | (io >= ie ? 4u : 0u) | (dop >= de ? 8u : 0u);
+  return H;
+}
+
+__global__ __launch_bounds__(64) void k_align(const uint64_t* __restrict__ words, const AlignIn* __restrict__ in,
+                                              AlignOut* __restrict__ out, uint8_t* __restrict__ scr,
+                                              uint32_t* __restrict__ dense, uint32_t* __restrict__ count) {
+  __shared__ __attribute__((aligned(16))) uint8_t s_rows[64 * 64];
+  __shared__ int32_t s_lo[64];
+  const uint32_t r = blockIdx.x;
+  const int L = (int)threadIdx.x;
+  const AlignIn a = in[r];
+  const int32_t n = (int32_t)a.n, m = (int32_t)a.m, D = n + m;
+  const Seq T{words + a.t_woff, (int32_t)a.t0, m, 0u}, Q{words + a.q_woff, (int32_t)a.q0, n, a.strand};
+  uint8_t* rows = scr + a.scr_off;
+  int32_t* lo_arr = (int32_t*)(rows + (size_t)(D + 1) * 64);
+  uint32_t* ops = (uint32_t*)(lo_arr + (D + 1));
+  const uint32_t C = (uint32_t)D + 1;
+  auto fail = [&]() {
+    if (L == 0) {
+      AlignOut f{INT32_MIN, 0u, 0u, 1u, 0u, 0u, 0u, 0u};
+      out[r] = f;
+    }
+  };
+  if (D == 0) { fail(); return; }
+
+  // ---- sweep ------------------------------------------------------------------------------------------------------
+  int32_t lo = -W / 2;
+  const int k0 = 2 * L, k1 = 2 * L + 1;
+  // diagonal 0 (only (0, 0) is a cell: H = 0 at k = W / 2) and diagonal -1; the band does not move after d = 0 (both
+  // decision cells lie outside the matrix)
+  int32_t h1a = k0 == W / 2 ? 0 : NEG, h1b = NEG, i1a = NEG, i1b = NEG, d1a = NEG, d1b = NEG, h2a = NEG, h2b = NEG;
+  if (L == 0) lo_arr[0] = lo;
+  uint32_t qa = Q.at(lo + k0 - 1), qb = Q.at(lo + k1 - 1);   // Q[i - 1]
+  uint32_t ta = T.at(-lo - k0), tb = T.at(-lo - k1);         // T[j - 1] on d = 1
+  int32_t hend = NEG;
+  bool in_band = false;
+  for (int32_t d = 1; d <= D; ++d) {
+    const uint32_t q_in = Q.at(lo + W - 1);   // enters at the top if the band moves
+    const uint32_t t_in = T.at(d - lo);       // enters at the bottom if it does not
+    const int32_t h1m = from_below(h1b, NEG), i1m = from_below(i1b, NEG), h2m = from_below(h2b, NEG);
+    int32_t Ia, Da, Ib, Db;
+    uint32_t na, nb;
+    const int32_t Ha = cell(h1m, i1m, h1a, d1a, h2m, qa, ta, Ia, Da, na);
+    const int32_t Hb = cell(h1a, i1a, h1b, d1b, h2a, qb, tb, Ib, Db, nb);
+    rows[(size_t)d * 64 + L] = (uint8_t)(na | (nb << 4));
+    if (L == 0) lo_arr[d] = lo;
+    if (d == D) {
+      const int32_t k = n - lo;
+      in_band = k >= 0 && k < W;
+      const int32_t sel = (k & 1) ? Hb : Ha;
+      hend = __shfl(sel, in_band ? (k >> 1) : 0, 64);
+      break;
+    }
+    const int32_t top = __builtin_amdgcn_readlane(Hb, 63), bot = __builtin_amdgcn_readlane(Ha, 0);
+    const int32_t it = lo + W - 1, jt = d - it, ib = lo, jb = d - lo;
+    const int32_t vt = (it >= 0 && it <= n && jt >= 0 && jt <= m && top >= FINITE) ? top : NEG;
+    const int32_t vb = (ib >= 0 && ib <= n && jb >= 0 && jb <= m && bot >= FINITE) ? bot : NEG;
+    if (vt > vb) {   // lo_{d+1} = lo_d + 1: every array moves down one cell
+      h2a = h1b; h2b = from_above(h1a, NEG);
+      h1a = Hb; h1b = from_above(Ha, NEG);
+      i1a = Ib; i1b = from_above(Ia, NEG);
+      d1a = Db; d1b = from_above(Da, NEG);
+      const uint32_t qn = (uint32_t)from_above((int32_t)qa, (int32_t)q_in);
+      qa = qb; qb = qn;
+      ++lo;
+    } else {         // lo_{d+1} = lo_d: the target codes move up one cell
+      h2a = h1a; h2b = h1b;
+      h1a = Ha; h1b = Hb;
+      i1a = Ia; i1b = Ib;
+      d1a = Da; d1b = Db;
+      const uint32_t tn = (uint32_t)from_below((int32_t)tb, (int32_t)t_in);
+      tb = ta; ta = tn;
+    }
+  }
+  if (!in_band || hend < FINITE) { fail(); return; }
+  wave_sync();
+
+  // ---- traceback: ops in reverse order into ops[C - 1 - cnt] ------------------------------------------------------
+  int32_t d = D, i = n, mat = 0;
+  uint32_t cnt = 0;
+  int32_t run_t = -1, run_len = 0, gap_dp = 0;
+  bool bad = false;
+  auto emit = [&](int32_t t, int32_t len) {
+    if (L == 0) ops[C - 1 - cnt] = ((uint32_t)len << 2) | (uint32_t)t;
+    ++cnt;
+    if (t) gap_dp += 4 + 2 * len;
+  };
+  while (d > 0 && !bad) {
+    const int32_t blo = max(d - 63, 0);
+    const int32_t rr = blo + L;
+    if (rr <= d) {
+      const uint4* src = (const uint4*)(rows + (size_t)rr * 64);
+      uint4* dst = (uint4*)(s_rows + L * 64);
+      const uint4 x0 = src[0], x1 = src[1], x2 = src[2], x3 = src[3];
+      dst[0] = x0; dst[1] = x1; dst[2] = x2; dst[3] = x3;
+      s_lo[L] = lo_arr[rr];
+    }
+    wave_sync();
+    while (d >= blo && d > 0) {
+      const int32_t k = i - s_lo[d - blo];
+      if (k < 0 || k >= W) { bad = true; break; }
+      const uint32_t nib = (s_rows[(d - blo) * 64 + (k >> 1)] >> ((k & 1) * 4)) & 15u;
+      int32_t t;
+      if (mat == 0) {
+        const uint32_t s = nib & 3u;
+        if (s) { mat = (int32_t)s; continue; }   // the same cell, in I or D
+        t = 0; i -= 1; d -= 2;
+      } else if (mat == 1) {
+        t = 1; i -= 1; d -= 1;
+        if (nib & 4u) mat = 0;
+      } else {
+        t = 2; d -= 1;
+        if (nib & 8u) mat = 0;
+      }
+      if (t == run_t) ++run_len;
+      else {
+        if (run_len) emit(run_t, run_len);
+        run_t = t; run_len = 1;
+      }
+    }
+    wave_sync();   // every lane is done with this block before the next one overwrites it
+  }
+  if (bad || d != 0 || i != 0 || mat != 0) { fail(); return; }
+  if (run_len) emit(run_t, run_len);
+  wave_sync();
+
+  // ---- fix_cigar (aligners.rs:138-250), streamed: F[j] = ops[C - cnt + j] --------------------------------------------
+  // Left shift: op j is final once op j + 1 has been looked at, so it goes straight on into the retain / merge stage,
+  // which writes the result to ops[0 ..) (never ahead of what is still to be read: nout <= j < C - cnt + j).
+  const uint32_t* F = ops + (C - cnt);
+  uint32_t nout = 0;
+  bool is_start = true, have_last = false;
+  uint32_t last = 0, first_t = 3, last_t = 3;
+  uint32_t tsh0 = 0, qsh0 = 0, tsh1 = 0, qsh1 = 0;
+  int32_t gap_fin = 0;
+  auto write = [&](uint32_t op) {
+    if (L == 0) ops[nout] = op;
+    ++nout;
+    const uint32_t t = op & 3u;
+    if (first_t == 3) first_t = t;
+    last_t = t;
+    if (t) gap_fin += 4 + 2 * (int32_t)(op >> 2);
+  };
+  auto stage2 = [&](uint32_t op) {
+    const uint32_t t = op & 3u, len = op >> 2;
+    if (is_start) {
+      if (t == 0 && len == 0) return;
+      is_start = false;
+      if (t == 1) { qsh0 = len; return; }
+      if (t == 2) { tsh0 = len; return; }
+    } else if (len == 0) {
+      return;
+    }
+    if (have_last && (last & 3u) == t) { last += len << 2; return; }
+    if (have_last) write(last);
+    last = op; have_last = true;
+  };
+  int32_t tpos = 0, qpos = 0;
+  uint32_t prev = 0, cur = F[0], nxt = cnt > 1 ? F[1] : 0u;
+  for (uint32_t j = 0; j < cnt; ++j) {
+    const uint32_t t = cur & 3u;
+    const int32_t len = (int32_t)(cur >> 2);
+    if (t == 0) {
+      tpos += len; qpos += len;
+    } else {
+      if (j > 0 && j + 1 < cnt && (prev & 3u) == 0 && (nxt & 3u) == 0) {
+        const int32_t prev_len = (int32_t)(prev >> 2);
+        int32_t l = 0;
+        if (t == 1) {
+          while (l < prev_len && Q.at(qpos - 1 - l) == Q.at(qpos + len - 1 - l)) ++l;
+        } else {
+          while (l < prev_len && T.at(tpos - 1 - l) == T.at(tpos + len - 1 - l)) ++l;
+        }
+        if (l > 0) {
+          prev -= (uint32_t)l << 2;
+          nxt += (uint32_t)l << 2;
+          tpos -= l; qpos -= l;
+        }
+      }
+      if (t == 1) qpos += len; else tpos += len;
+    }
+    if (j > 0) stage2(prev);
+    prev = cur; cur = nxt;
+    nxt = j + 2 < cnt ? F[j + 2] : 0u;
+  }
+  stage2(prev);
+  if (have_last) {   // a trailing indel is dropped too
+    const uint32_t t = last & 3u;
+    if (t == 1) qsh1 = last >> 2;
+    else if (t == 2) tsh1 = last >> 2;
+    else write(last);
+  }
+  if (nout == 0 || first_t != 0 || last_t != 0) { fail(); return; }
+
+  // ---- result: ops to the dense output, the record's header -------------------------------------------------------
+  uint32_t base = 0;
+  if (L == 0) base = atomicAdd(count, nout);
+  base = (uint32_t)__shfl((int32_t)base, 0, 64);
+  wave_sync();
+  for (uint32_t x = (uint32_t)L; x < nout; x += 64) dense[base + x] = ops[x];
+  if (L == 0) {
+    AlignOut o{hend + gap_dp - gap_fin, nout, base, 0u, tsh0, qsh0, tsh1, qsh1};
+    out[r] = o;
+  }
+}
+
+}  // namespace
+
+void launch_align(const uint64_t* d_words, const AlignIn* d_in, AlignOut* d_out, uint8_t* d_scr, uint32_t* d_dense,
+                  uint32_t* d_count, uint32_t n_rec, hipStream_t st) {
+  if (n_rec == 0) return;
+  hipLaunchKernelGGL(k_align, dim3(n_rec), dim3(64), 0, st, d_words, d_in, d_out, d_scr, d_dense, d_count);
+}
+
+}  // namespace herro

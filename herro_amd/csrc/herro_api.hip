@@ -25,6 +25,7 @@
 #include "windowing.hpp"
 #include "build_dev.h"
 #include "cigar_dev.h"
+#include "align_dev.h"
 
 using namespace herro;
 
@@ -3250,5 +3251,146 @@ int herro_job_stats(herro_job* job, uint64_t* out) {
   out[3] = sumL; out[4] = sumS; out[5] = nz;
   return HERRO_OK;
 }
+
+}  // extern "C"
+
+// ---- base-level alignment of coordinate-only overlaps (align_dev.hip) ------------------------------------------------
+// The step `herro inference` hands to `minimap2 -cx ava-ont` when it is not given --read-alns (mm2.rs:15-30), followed by
+// fix_cigar (aligners.rs:138-250): records in chunks that fit HERRO_ALIGN_SCRATCH_MB of traceback scratch, one kernel per
+// chunk on the context's stream, the ops back to the host and formatted into one text block there.
+struct herro_aligned {
+  std::vector<herro_alignment> alns;
+  std::vector<int32_t> scores;
+  std::string text;
+  uint32_t failed = 0;
+};
+
+extern "C" {
+
+int herro_align_overlaps(herro_ctx* ctx, uint32_t n, const herro_alignment* in, herro_aligned** out) {
+  if (!ctx || !out || (n && !in)) return HERRO_E_INVALID;
+  *out = nullptr;
+  if (ctx->host_only) { ctx->err = "herro_align_overlaps: the context has no device"; return HERRO_E_NO_DEVICE; }
+  if (!ctx->d_words) { ctx->err = "herro_set_reads must be called first"; return HERRO_E_STATE; }
+  for (uint32_t r = 0; r < n; r++) {
+    const herro_alignment& a = in[r];
+    std::string why;
+    if (a.qid >= ctx->n_reads || a.tid >= ctx->n_reads) why = "read id outside the read store";
+    else if (a.qstart > a.qend || a.qend > ctx->read_len[a.qid]) why = "query coordinates outside the read";
+    else if (a.tstart > a.tend || a.tend > ctx->read_len[a.tid]) why = "target coordinates outside the read";
+    else if (a.strand > 1) why = "strand must be 0 or 1";
+    else if ((uint64_t)(a.qend - a.qstart) + (a.tend - a.tstart) > herro::ALIGN_MAX_CELLS) why = "overlap longer than 2^25 bases in all";
+    if (!why.empty()) {
+      ctx->err = "herro_align_overlaps: record " + std::to_string(r) + ": " + why;
+      return HERRO_E_INVALID;
+    }
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  uint64_t budget = 4096ull << 20;
+  if (const char* e = getenv("HERRO_ALIGN_SCRATCH_MB")) budget = (uint64_t)std::max(1ll, atoll(e)) << 20;
+  std::vector<herro::AlignIn> recs(n);
+  std::vector<herro::AlignOut> res(n);
+  std::vector<uint32_t> ops;            // every record's final ops, record order
+  std::vector<uint64_t> ops_at(n + 1, 0);
+  // chunks: consecutive records whose scratch fits the budget (a record larger than the budget runs alone)
+  uint64_t max_scr = 0, max_dense = 0;
+  std::vector<uint32_t> cut{0};
+  {
+    uint64_t acc = 0, dn = 0;
+    for (uint32_t r = 0; r < n; r++) {
+      const uint32_t qn = in[r].qend - in[r].qstart, tm = in[r].tend - in[r].tstart;
+      const uint64_t need = herro::align_scratch_bytes(qn, tm);
+      if (acc && acc + need > budget) { cut.push_back(r); acc = 0; dn = 0; }
+      recs[r] = herro::AlignIn{ctx->h_word_off[in[r].tid], ctx->h_word_off[in[r].qid], acc, in[r].tstart, tm, in[r].qstart, qn, in[r].strand, 0};
+      acc += need;
+      dn += (uint64_t)qn + tm + 1;
+      max_scr = std::max(max_scr, acc);
+      max_dense = std::max(max_dense, dn);
+    }
+    if (cut.back() != n) cut.push_back(n);
+  }
+  uint8_t* d_scr = nullptr;
+  herro::AlignIn* d_in = nullptr;
+  herro::AlignOut* d_out = nullptr;
+  uint32_t* d_dense = nullptr;
+  uint32_t* d_count = nullptr;
+  auto release = [&]() {
+    if (d_scr) (void)hipFree(d_scr);
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    if (d_dense) (void)hipFree(d_dense);
+    if (d_count) (void)hipFree(d_count);
+  };
+  auto hip_fail = [&](hipError_t e, const char* what) {
+    ctx->err = std::string("herro_align_overlaps: ") + what + ": " + hipGetErrorString(e);
+    release();
+    return HERRO_E_NO_DEVICE;
+  };
+  hipError_t e = hipSuccess;
+  if (n) {
+    if ((e = hipMalloc((void**)&d_scr, std::max<uint64_t>(max_scr, 256))) != hipSuccess) return hip_fail(e, "scratch");
+    if ((e = hipMalloc((void**)&d_in, sizeof(herro::AlignIn) * n)) != hipSuccess) return hip_fail(e, "records");
+    if ((e = hipMalloc((void**)&d_out, sizeof(herro::AlignOut) * n)) != hipSuccess) return hip_fail(e, "results");
+    if ((e = hipMalloc((void**)&d_dense, 4 * std::max<uint64_t>(max_dense, 1))) != hipSuccess) return hip_fail(e, "ops");
+    if ((e = hipMalloc((void**)&d_count, 4)) != hipSuccess) return hip_fail(e, "counter");
+    if ((e = hipMemcpyAsync(d_in, recs.data(), sizeof(herro::AlignIn) * n, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
+      return hip_fail(e, "record upload");
+  }
+  for (size_t c = 0; c + 1 < cut.size(); c++) {
+    const uint32_t r0 = cut[c], r1 = cut[c + 1];
+    if ((e = hipMemsetAsync(d_count, 0, 4, ctx->stream)) != hipSuccess) return hip_fail(e, "counter reset");
+    herro::launch_align(ctx->d_words, d_in + r0, d_out + r0, d_scr, d_dense, d_count, r1 - r0, ctx->stream);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_align launch");
+    uint32_t total = 0;
+    if ((e = hipMemcpyAsync(&total, d_count, 4, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) return hip_fail(e, "count");
+    if ((e = hipMemcpyAsync(res.data() + r0, d_out + r0, sizeof(herro::AlignOut) * (r1 - r0), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess)
+      return hip_fail(e, "results");
+    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return hip_fail(e, "k_align");
+    const size_t at = ops.size();
+    ops.resize(at + total);
+    if (total && (e = hipMemcpy(ops.data() + at, d_dense, 4ull * total, hipMemcpyDeviceToHost)) != hipSuccess) return hip_fail(e, "ops");
+    for (uint32_t r = r0; r < r1; r++) res[r].ops_off += (uint32_t)at;
+  }
+  release();
+  // text: "<len><M|I|D>" per op, records back to back
+  auto digits = [](uint32_t v) { uint32_t k = 1; while (v >= 10) { v /= 10; k++; } return k; };
+  std::vector<uint64_t> toff(n + 1, 0);
+  for (uint32_t r = 0; r < n; r++) {
+    uint64_t b = 0;
+    if (!res[r].failed)
+      for (uint32_t x = 0; x < res[r].n_ops; x++) b += digits(ops[res[r].ops_off + x] >> 2) + 1;
+    toff[r + 1] = toff[r] + b;
+  }
+  auto* h = new herro_aligned();
+  h->text.resize(std::max<uint64_t>(toff[n], 1));
+  h->alns.assign(in, in + n);
+  h->scores.resize(n);
+  host_pool(ctx).run(n, [&](uint32_t r) {
+    herro_alignment& a = h->alns[r];
+    const herro::AlignOut& o = res[r];
+    a.cigar = reinterpret_cast<const uint8_t*>(h->text.data() + toff[r]);
+    a.cigar_len = (uint32_t)(toff[r + 1] - toff[r]);
+    if (o.failed) { h->scores[r] = INT32_MIN; a.cigar_len = 0; return; }
+    h->scores[r] = o.score;
+    char* p = &h->text[toff[r]];
+    for (uint32_t x = 0; x < o.n_ops; x++) {
+      const uint32_t op = ops[o.ops_off + x];
+      p += snprintf(p, 12, "%u", op >> 2);
+      *p++ = "MID"[op & 3u];
+    }
+    a.tstart += o.tdrop0;
+    a.tend -= o.tdrop1;
+    if (a.strand == 0) { a.qstart += o.qdrop0; a.qend -= o.qdrop1; }
+    else { a.qend -= o.qdrop0; a.qstart += o.qdrop1; }
+  });
+  for (uint32_t r = 0; r < n; r++) h->failed += res[r].failed ? 1u : 0u;
+  *out = h;
+  return HERRO_OK;
+}
+
+const herro_alignment* herro_aligned_alignments(const herro_aligned* a) { return a ? a->alns.data() : nullptr; }
+const int32_t* herro_aligned_scores(const herro_aligned* a) { return a ? a->scores.data() : nullptr; }
+uint32_t herro_aligned_failed(const herro_aligned* a) { return a ? a->failed : 0; }
+void herro_aligned_free(herro_aligned* a) { delete a; }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 //   * tlen/tstart/tend digits; CIGAR = last tab field minus its first 5 bytes ("cg:Z:"; shorter -> panic,
 //     a line with no 10th field -> panic);
 //   * self overlap -> skip; a (query, target) pair already seen -> skip (first one wins);
+//   * herro_paf_parse_coords: the same rules up to tend; no CIGAR column is needed or read (a PAF of `minimap2 -x ava-ont`);
 //   * kept lines are grouped by target.  The reference groups in a HashMap (iteration order unspecified);
 //     here targets come out in order of first appearance, alignments in file order.
 // A name that occurs more than once maps to its LAST index (HashMap::collect, lib.rs).
@@ -68,7 +69,8 @@ bool parse_u32(std::string_view f, uint32_t& v) {
 }
 
 // one line (without its dropped last byte) -> record
-void parse_line(std::string_view ln, const NameMap& names, const uint8_t* core, Rec& r) {
+// coords: a PAF without CIGARs (herro_paf_parse_coords): nothing after tend is needed or read
+void parse_line(std::string_view ln, const NameMap& names, const uint8_t* core, Rec& r, bool coords) {
   r.status = 1;
   r.msg = nullptr;
   size_t pos = 0;
@@ -107,6 +109,11 @@ void parse_line(std::string_view ln, const NameMap& names, const uint8_t* core, 
   for (uint32_t* p : tn) {
     if (!next(f)) return panic("called `Option::unwrap()` on a `None` value");
     if (!parse_u32(f, *p)) return panic("Character is not a valid digit");
+  }
+  if (coords) {
+    if (r.a.tid == r.a.qid) return;  // self overlap
+    r.status = 0;
+    return;
   }
   if (exhausted) return panic("called `Option::unwrap()` on a `None` value");  // data.last() on an empty iterator
   // (memrchr, not string_view::rfind: the last field is the CIGAR, ~1.6 KB per line, and rfind walks it a byte at a time —
@@ -158,7 +165,7 @@ void fill_map(NameMap& map, uint32_t n_reads, const char* names, const uint64_t*
 }
 
 herro_paf* parse_owned(const char* src, size_t src_len, std::string&& owned, size_t body, uint32_t n_reads, const NameMap& map,
-                       const uint8_t* core, int n_threads, char* err, uint64_t err_cap, bool borrow = false) {
+                       const uint8_t* core, int n_threads, char* err, uint64_t err_cap, bool borrow = false, bool coords = false) {
   auto out = new herro_paf();
   size_t len;
   if (src && borrow) len = src_len;   // the caller keeps the bytes alive (herro_paf_parse_view): nothing is copied
@@ -215,7 +222,7 @@ herro_paf* parse_owned(const char* src, size_t src_len, std::string&& owned, siz
         const size_t l0 = ls[i], l1 = ls[i + 1];  // read_until: bytes l0..l1 incl. the delimiter if present
         recs[i].line = i;
         memset(&recs[i].a, 0, sizeof(herro_alignment));
-        parse_line(std::string_view(base + l0, l1 - l0 - 1), map, core, recs[i]);  // `buffer[..len - 1]`
+        parse_line(std::string_view(base + l0, l1 - l0 - 1), map, core, recs[i], coords);  // `buffer[..len - 1]`
       }
     }
   });
@@ -365,6 +372,13 @@ herro_paf* herro_paf_parse_view(const char* text, uint64_t len, const herro_name
                                 char* err, uint64_t err_cap) {
   if ((!text && len) || !ix) { set_err(err, err_cap, "invalid argument"); return nullptr; }
   return parse_owned(text ? text : "", (size_t)len, std::string(), 0, ix->n_reads, ix->map, core, n_threads, err, err_cap, true);
+}
+
+// nothing in the result refers to the text (no CIGARs): it is parsed where it lies
+herro_paf* herro_paf_parse_coords(const char* text, uint64_t len, const herro_name_index* ix, const uint8_t* core, int n_threads,
+                                  char* err, uint64_t err_cap) {
+  if ((!text && len) || !ix) { set_err(err, err_cap, "invalid argument"); return nullptr; }
+  return parse_owned(text ? text : "", (size_t)len, std::string(), 0, ix->n_reads, ix->map, core, n_threads, err, err_cap, true, true);
 }
 
 herro_paf* herro_oec_read_indexed(const char* path, const herro_name_index* ix, const uint8_t* core, int n_threads, char* err,

@@ -340,11 +340,35 @@ herro_paf* herro_paf_parse(const char* text, uint64_t len, uint32_t n_reads, con
                            uint64_t err_cap);
 herro_paf* herro_oec_read(const char* path, uint32_t n_reads, const char* names, const uint64_t* name_off,
                           const uint8_t* core, int n_threads, char* err, uint64_t err_cap);
+/* PAF without CIGARs (`minimap2 -x ava-ont`, no -c: mm2.rs:15-30 then asks for -c): every rule of herro_paf_parse_indexed — self overlaps
+ * and repeated (query, target) pairs dropped, grouping and order by first appearance, u32 wrap, the reference's messages on malformed
+ * numbers or strand — but no CIGAR column is needed or read; the records carry cigar = NULL, cigar_len = 0 and go to herro_align_overlaps. */
+herro_paf* herro_paf_parse_coords(const char* text, uint64_t len, const herro_name_index* index, const uint8_t* core, int n_threads,
+                                  char* err, uint64_t err_cap);
 uint32_t herro_paf_n_targets(const herro_paf* p);
 const uint32_t* herro_paf_target_ids(const herro_paf* p);
 const uint64_t* herro_paf_aln_off(const herro_paf* p);        /* [n_targets + 1] */
 const herro_alignment* herro_paf_alignments(const herro_paf* p);
 void herro_paf_free(herro_paf* p);
+
+/* ---- base-level alignment on the device (csrc/align_dev.hip) ------------------------------------------------------------------
+ * Stands in for the base-level step `herro inference` asks of minimap2 when it is not given --read-alns (`minimap2 -cx ava-ont`,
+ * mm2.rs:15-30; the -c), followed by the reference's fix_cigar (aligners.rs:138-250): every record's query region is aligned to its
+ * target region on the context's read store — banded Gotoh (+2 / -4, gaps 4 + 2k), HERRO_ALIGN_BAND cells per anti-diagonal, the
+ * band following the better of its two edge cells — then indels are left-shifted and a leading and a trailing indel dropped, so
+ * every CIGAR starts and ends with M.  The exact specification is DESIGN.md section 9.  A record fails (no CIGAR) when its end cell
+ * leaves the band or nothing but indels would remain.  Runs on the context's execution stream and returns when done (threading as
+ * herro_job_featurize).  Scratch: (n + m + 1) x 72 bytes per record, in chunks of HERRO_ALIGN_SCRATCH_MB (default 4096).
+ * HERRO_E_STATE: no reads; HERRO_E_INVALID: a read id outside the store or coordinates outside a read (message names the record). */
+#define HERRO_ALIGN_BAND 128
+typedef struct herro_aligned herro_aligned;
+/* Base-level alignment of n overlaps given by coordinates only (cigar / cigar_len ignored), on the context's read store. */
+int herro_align_overlaps(herro_ctx* ctx, uint32_t n, const herro_alignment* in, herro_aligned** out);
+/* n records in input order: coordinates after the trim; cigar points into the handle's text (cigar_len 0 = failed). */
+const herro_alignment* herro_aligned_alignments(const herro_aligned* a);
+const int32_t* herro_aligned_scores(const herro_aligned* a);   /* INT32_MIN for failed records */
+uint32_t herro_aligned_failed(const herro_aligned* a);
+void herro_aligned_free(herro_aligned* a);
 
 /* ---- reads and the `herro features` sink -----------------------------------------------------
  * herro_fastx_read = get_reads (haec_io.rs:37-75) over needletail's parse_fastx_file: FASTA or FASTQ by the first byte,
