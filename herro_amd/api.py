@@ -34,6 +34,8 @@ EXPORTS = [
     "herro_reads_descs", "herro_reads_free", "herro_write_window_features", "herro_job_write_features",
     "herro_paf_parse_coords", "herro_align_overlaps", "herro_aligned_alignments", "herro_aligned_scores", "herro_aligned_failed",
     "herro_aligned_free",
+    "herro_find_overlaps", "herro_overlaps_n", "herro_overlaps_n_targets", "herro_overlaps_target_ids", "herro_overlaps_aln_off",
+    "herro_overlaps_alignments", "herro_overlaps_scores", "herro_overlaps_free", "herro_debug_sketch",
 ]
 
 
@@ -47,6 +49,10 @@ class Alignment(C.Structure):  # herro_alignment
     _fields_ = [(n, C.c_uint32) for n in
                 ("qid", "qlen", "qstart", "qend", "strand", "tid", "tlen", "tstart", "tend", "cigar_len")] + \
                [("cigar", C.c_void_p)]
+
+
+class OverlapParams(C.Structure):  # herro_overlap_params (0 = the field's default)
+    _fields_ = [(n, C.c_uint32) for n in ("k", "w", "max_occ", "bandwidth", "max_gap", "min_score", "min_anchors", "reserved")]
 
 
 class WindowInfo(C.Structure):  # herro_window_info
@@ -169,6 +175,17 @@ def lib():
         L.herro_aligned_failed.argtypes = [vp]
         L.herro_aligned_free.restype = None
         L.herro_aligned_free.argtypes = [vp]
+        L.herro_find_overlaps.argtypes = [vp, vp, vp]
+        for f in (L.herro_overlaps_n, L.herro_overlaps_n_targets):
+            f.restype = u32
+            f.argtypes = [vp]
+        for f in (L.herro_overlaps_target_ids, L.herro_overlaps_aln_off, L.herro_overlaps_alignments, L.herro_overlaps_scores):
+            f.restype = vp
+            f.argtypes = [vp]
+        L.herro_overlaps_free.restype = None
+        L.herro_overlaps_free.argtypes = [vp]
+        L.herro_debug_sketch.restype = C.c_int64
+        L.herro_debug_sketch.argtypes = [vp, vp, vp, vp, vp, vp, u64]
         L.herro_debug_host_ctx.restype = vp
         L.herro_debug_host_ctx.argtypes = [u32, vp, vp]
         L.herro_debug_job_array.restype = C.c_int64
@@ -500,6 +517,57 @@ class Context:
         finally:
             self._l.herro_aligned_free(h)
         return out, cigars, scores, out[:, 9] > 0
+
+    def _overlap_params(self, params: dict) -> OverlapParams:
+        """keyword arguments -> herro_overlap_params.  A field left out (or None) takes its default, which the struct spells 0; an
+        explicit k or w outside 5 .. 31 / 1 .. 64 — 0 included, which the struct could not carry — is HERRO_E_INVALID here."""
+        p = OverlapParams()
+        for name, v in params.items():
+            if name not in ("k", "w", "max_occ", "bandwidth", "max_gap", "min_score", "min_anchors"):
+                raise TypeError(f"unknown overlap parameter {name!r}")
+            if v is None:
+                continue
+            v = int(v)
+            if (name == "k" and not 5 <= v <= 31) or (name == "w" and not 1 <= v <= 64) or not 0 <= v <= 0xFFFFFFFF:
+                raise HerroError(-1, "overlap parameters: 5 <= k <= 31 and 1 <= w <= 64")
+            setattr(p, name, v)
+        return p
+
+    def find_overlaps(self, **params):
+        """Which reads of the store overlap, where, on which strand (herro_find_overlaps; the seeding and chaining of the
+        `minimap2 -x ava-ont` run of mm2.rs:15-30).  params: k, w, max_occ, bandwidth, max_gap, min_score, min_anchors.
+        Returns (rids u32 [n_targets], rows u32 [n, 10] in create_job's layout with cigar_len 0, aln_off u64 [n_targets + 1],
+        scores i32 [n]): rows goes into Context.align, (rids, aln_off) with its result into aligned_job_args."""
+        p = self._overlap_params(params)
+        h = C.c_void_p()
+        self._chk(self._l.herro_find_overlaps(self.h, C.byref(p), C.byref(h)))
+        try:
+            n, nt = self._l.herro_overlaps_n(h), self._l.herro_overlaps_n_targets(h)
+            rids = np.ctypeslib.as_array(C.cast(self._l.herro_overlaps_target_ids(h), C.POINTER(C.c_uint32)), (nt,)).copy() if nt else np.zeros(0, np.uint32)
+            aln_off = np.ctypeslib.as_array(C.cast(self._l.herro_overlaps_aln_off(h), C.POINTER(C.c_uint64)), (nt + 1,)).copy()
+            rows = np.zeros((n, 10), np.uint32)
+            scores = np.zeros(n, np.int32)
+            if n:
+                res = (Alignment * n).from_address(self._l.herro_overlaps_alignments(h))
+                rows[:] = np.frombuffer(res, dtype=np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True), count=n)["f"]
+                scores[:] = np.ctypeslib.as_array(C.cast(self._l.herro_overlaps_scores(h), C.POINTER(C.c_int32)), (n,))
+        finally:
+            self._l.herro_overlaps_free(h)
+        return rids, rows, aln_off, scores
+
+    def sketch(self, **params):
+        """The store's minimizers sorted by (rid, pos) (herro_debug_sketch): (hash u64, rid u32, pos u32, strand u8)."""
+        p = self._overlap_params(params)
+        n = self._l.herro_debug_sketch(self.h, C.byref(p), None, None, None, None, 0)
+        if n < 0:
+            self._chk(int(n))
+        hs, rid, pos, st = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+        if n:
+            got = self._l.herro_debug_sketch(self.h, C.byref(p), hs.ctypes.data, rid.ctypes.data, pos.ctypes.data, st.ctypes.data, n)
+            if got < 0:
+                self._chk(int(got))
+            assert got == n
+        return hs, rid, pos, st
 
     def create_job_from_paf(self, paf: "Paf", window_size: int) -> "Job":
         """herro_job_create straight from a parsed PAF batch (targets in its order); `paf` must outlive the call."""

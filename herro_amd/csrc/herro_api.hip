@@ -26,6 +26,7 @@
 #include "build_dev.h"
 #include "cigar_dev.h"
 #include "align_dev.h"
+#include "overlap_dev.h"
 
 using namespace herro;
 
@@ -3392,5 +3393,126 @@ const herro_alignment* herro_aligned_alignments(const herro_aligned* a) { return
 const int32_t* herro_aligned_scores(const herro_aligned* a) { return a ? a->scores.data() : nullptr; }
 uint32_t herro_aligned_failed(const herro_aligned* a) { return a ? a->failed : 0; }
 void herro_aligned_free(herro_aligned* a) { delete a; }
+
+}  // extern "C"
+
+// ---- overlap finding (overlap_dev.hip) ---------------------------------------------------------------------------------------
+// The seeding and chaining the reference leaves to `minimap2 -x ava-ont` (mm2.rs:15-30): the device returns the kept chains per
+// (t, q, strand); the strand choice, the dual records and their grouping by target are a few lines of host code over them.
+struct herro_overlaps {
+  std::vector<uint32_t> rids;
+  std::vector<uint64_t> aln_off;
+  std::vector<herro_alignment> alns;
+  std::vector<int32_t> scores;
+};
+
+static int overlap_params(herro_ctx* ctx, const herro_overlap_params* in, herro::OvlParams& P) {
+  const herro_overlap_params z{};
+  const herro_overlap_params& p = in ? *in : z;
+  P.k = p.k ? p.k : 25;
+  P.w = p.w ? p.w : 17;
+  P.max_occ = p.max_occ ? p.max_occ : 128;
+  P.bandwidth = p.bandwidth ? p.bandwidth : 150;
+  P.max_gap = p.max_gap ? p.max_gap : 5000;
+  P.min_score = p.min_score ? p.min_score : 2500;
+  P.min_anchors = p.min_anchors ? p.min_anchors : 3;
+  if (P.k < 5 || P.k > 31 || P.w > 64) {
+    ctx->err = "overlap parameters: 5 <= k <= 31 and 1 <= w <= 64";
+    return HERRO_E_INVALID;
+  }
+  return HERRO_OK;
+}
+
+static int overlap_ready(herro_ctx* ctx, const char* who) {
+  if (ctx->host_only) { ctx->err = std::string(who) + ": the context has no device"; return HERRO_E_NO_DEVICE; }
+  if (!ctx->d_words) { ctx->err = "herro_set_reads must be called first"; return HERRO_E_STATE; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return HERRO_OK;
+}
+
+static int overlap_rc(herro_ctx* ctx, int rc, const std::string& msg) {
+  if (rc == herro::OVL_OK) return HERRO_OK;
+  ctx->err = msg;
+  return rc == herro::OVL_UNSUPPORTED ? HERRO_E_UNSUPPORTED : HERRO_E_NO_DEVICE;
+}
+
+extern "C" {
+
+int herro_find_overlaps(herro_ctx* ctx, const herro_overlap_params* params, herro_overlaps** out) {
+  if (!ctx || !out) return HERRO_E_INVALID;
+  *out = nullptr;
+  herro::OvlParams P;
+  if (int rc = overlap_params(ctx, params, P)) return rc;
+  if (int rc = overlap_ready(ctx, "herro_find_overlaps")) return rc;
+  uint64_t budget = 4096ull << 20;
+  if (const char* e = getenv("HERRO_OVL_SCRATCH_MB")) budget = (uint64_t)std::max(1ll, atoll(e)) << 20;
+  const herro::OvlStore S{ctx->d_words, ctx->d_word_off, ctx->d_qual_off, ctx->read_len.data(), ctx->n_reads};
+  std::vector<herro::OvlPair> chains;
+  herro::OvlStats stats;
+  std::string msg;
+  if (int rc = overlap_rc(ctx, herro::ovl_find(S, P, budget, ctx->stream, chains, stats, msg), msg)) return rc;
+  if (const char* e = getenv("HERRO_OVL_STATS"))   // tools/overlaprate.py: the sizes of the stages, one line on stderr
+    if (atoi(e)) fprintf(stderr, "OVL kmers=%llu minimizers=%llu anchors=%llu groups=%llu chained=%llu chunks=%llu\n", (unsigned long long)stats.kmers,
+                         (unsigned long long)stats.minimizers, (unsigned long long)stats.anchors, (unsigned long long)stats.groups,
+                         (unsigned long long)stats.chained, (unsigned long long)stats.chunks);
+  // one overlap per pair: chains arrive in ascending (t, q, rel), so the two strands of a pair are neighbours
+  std::vector<herro::OvlPair> best;
+  for (const herro::OvlPair& c : chains) {
+    if (!best.empty() && best.back().t == c.t && best.back().q == c.q) {
+      if (c.score > best.back().score) best.back() = c;
+    } else {
+      best.push_back(c);
+    }
+  }
+  struct Rec { herro_alignment a; int32_t score; };
+  std::vector<Rec> recs;
+  recs.reserve(best.size() * 2);
+  for (const herro::OvlPair& c : best) {
+    const uint32_t tl = ctx->read_len[c.t], ql = ctx->read_len[c.q];
+    recs.push_back(Rec{herro_alignment{c.q, ql, c.qstart, c.qend, c.rel, c.t, tl, c.tstart, c.tend, 0, nullptr}, c.score});
+    recs.push_back(Rec{herro_alignment{c.t, tl, c.tstart, c.tend, c.rel, c.q, ql, c.qstart, c.qend, 0, nullptr}, c.score});   // the dual
+  }
+  std::sort(recs.begin(), recs.end(), [](const Rec& x, const Rec& y) { return x.a.tid != y.a.tid ? x.a.tid < y.a.tid : x.a.qid < y.a.qid; });
+  auto* h = new herro_overlaps();
+  h->alns.reserve(recs.size());
+  h->scores.reserve(recs.size());
+  for (const Rec& r : recs) {
+    if (h->rids.empty() || h->rids.back() != r.a.tid) { h->rids.push_back(r.a.tid); h->aln_off.push_back(h->alns.size()); }
+    h->alns.push_back(r.a);
+    h->scores.push_back(r.score);
+  }
+  h->aln_off.push_back(h->alns.size());
+  *out = h;
+  return HERRO_OK;
+}
+
+uint32_t herro_overlaps_n(const herro_overlaps* o) { return o ? (uint32_t)o->alns.size() : 0; }
+uint32_t herro_overlaps_n_targets(const herro_overlaps* o) { return o ? (uint32_t)o->rids.size() : 0; }
+const uint32_t* herro_overlaps_target_ids(const herro_overlaps* o) { return o ? o->rids.data() : nullptr; }
+const uint64_t* herro_overlaps_aln_off(const herro_overlaps* o) { return o ? o->aln_off.data() : nullptr; }
+const herro_alignment* herro_overlaps_alignments(const herro_overlaps* o) { return o ? o->alns.data() : nullptr; }
+const int32_t* herro_overlaps_scores(const herro_overlaps* o) { return o ? o->scores.data() : nullptr; }
+void herro_overlaps_free(herro_overlaps* o) { delete o; }
+
+int64_t herro_debug_sketch(herro_ctx* ctx, const herro_overlap_params* params, uint64_t* hash, uint32_t* rid, uint32_t* pos,
+                           uint8_t* strand, uint64_t cap) {
+  if (!ctx) return HERRO_E_INVALID;
+  herro::OvlParams P;
+  if (int rc = overlap_params(ctx, params, P)) return rc;
+  if (int rc = overlap_ready(ctx, "herro_debug_sketch")) return rc;
+  const herro::OvlStore S{ctx->d_words, ctx->d_word_off, ctx->d_qual_off, ctx->read_len.data(), ctx->n_reads};
+  std::vector<uint64_t> h, m;
+  std::string msg;
+  if (int rc = overlap_rc(ctx, herro::ovl_sketch(S, P, ctx->stream, h, m, msg), msg)) return rc;
+  if (h.size() <= cap && hash && rid && pos && strand) {
+    for (size_t i = 0; i < h.size(); i++) {
+      hash[i] = h[i];
+      rid[i] = (uint32_t)(m[i] >> 32);
+      pos[i] = ((uint32_t)m[i]) >> 1;
+      strand[i] = (uint8_t)(m[i] & 1u);
+    }
+  }
+  return (int64_t)h.size();
+}
 
 }  // extern "C"

@@ -1,0 +1,49 @@
+// overlap_dev.h — which reads overlap, where, on which strand (overlap_dev.hip): the GPU counterpart of the seeding and chaining
+// half of the `minimap2 -x ava-ont` run that `herro inference` starts without --read-alns (mm2.rs:15-30, overlaps.rs:340-344).
+// Minimizer sketch of the resident 2-bit store, radix sort by hash, frequency cut, anchor expansion, radix sort by
+// (t, q, rel, tpos, qpos), one wave64 per (t, q, rel) group for the chain.  The specification is DESIGN.md §10 and
+// tests/overlap_ref.py; the kernels equal it bit for bit, whatever the scratch budget.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+namespace herro {
+
+constexpr uint32_t OVL_LOOKBACK = 64;          // predecessors a chain step looks at: the lanes of a wave
+constexpr uint64_t OVL_ANCHOR_BYTES = 128;     // scratch the budget charges per anchor of a chunk (keys, payloads, both sort buffers, groups)
+constexpr uint64_t OVL_MAX_KMERS = 0xfffff000ull;   // k-mers of the whole store (32-bit minimizer indices)
+constexpr uint32_t OVL_MAX_READ_LEN = 0x7fffffffu;  // pos << 1 | strand is one 32-bit field
+constexpr uint32_t OVL_MAX_READS = 0x7fffffffu;     // q << 1 | rel is one 33-bit field of the anchor key
+
+struct OvlParams { uint32_t k, w, max_occ, bandwidth, max_gap, min_score, min_anchors; };   // defaults already filled in
+
+struct OvlStore {            // the context's read store
+  const uint64_t* d_words;      // 2-bit codes, 32 bases per word (+ one pad word)
+  const uint64_t* d_word_off;   // [n_reads + 1] first word of a read
+  const uint64_t* d_base_off;   // [n_reads + 1] first base of a read (its length by difference)
+  const uint32_t* h_len;        // host: read lengths
+  uint32_t n_reads;
+};
+
+struct OvlPair {             // one kept chain, t < q, forward coordinates on both reads
+  uint32_t t, q, rel, n_anchors;
+  int32_t score;
+  uint32_t tstart, tend, qstart, qend;
+};
+
+struct OvlStats { uint64_t kmers = 0, minimizers = 0, anchors = 0, groups = 0, chained = 0, chunks = 0; };
+
+enum { OVL_OK = 0, OVL_HIP = 1, OVL_UNSUPPORTED = 2 };
+
+// minimizers of the whole store sorted by (rid, pos): hash[i], meta[i] = rid << 32 | pos << 1 | strand (host vectors)
+int ovl_sketch(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vector<uint64_t>& hash, std::vector<uint64_t>& meta,
+               std::string& err);
+
+// every kept (t, q) chain per strand, ascending (t, q, rel); the caller picks the strand and writes the dual records
+int ovl_find(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hipStream_t st, std::vector<OvlPair>& out, OvlStats& stats,
+             std::string& err);
+
+}  // namespace herro

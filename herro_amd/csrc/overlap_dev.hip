@@ -1,0 +1,697 @@
+// overlap_dev.hip — minimizer seeding and chaining on the read store (overlap_dev.h; specification: DESIGN.md §10,
+// tests/overlap_ref.py).  Stages:
+//   k_sketch     a block per 256 k-mers of one read: f / r / hash per k-mer, window minima in LDS, every k-mer equal to the
+//                minimum of a window it lies in is selected.  Run twice: count per tile, scan, write — so the output is in
+//                (rid, pos) order without any atomic deciding a place.
+//   radix sort   LSD, 8-bit digits, 64-bit key + 64-bit payload, stable (per-block histogram, scan, ranked scatter).
+//   k_runs       per hash run: length, frequency cut, anchors every occurrence has with the later reads of its run.
+//   k_expand     the anchors of the targets of one chunk: A = tpos << 32 | qpos, B = (t - t_lo) << 33 | q << 1 | rel;
+//                sorted by A carrying B, then by B carrying A (stable): order (t, q, rel, tpos, qpos).
+//   k_chain      one wave64 per (t, q, rel) group: the 64 predecessors of an anchor are the 64 lanes.
+//   k_walk       back through the stored predecessors: first anchor, anchor count, coordinates.
+// Nothing an atomic orders reaches the output: the only atomics are integer sums (histograms, anchors per read).
+#include "overlap_dev.h"
+
+#include <algorithm>
+#include <climits>
+
+namespace herro {
+namespace {
+
+constexpr uint64_t INF64 = 0xffffffffffffffffull;
+constexpr int SK_T = 256;                    // k-mers (threads) of a sketch tile
+constexpr int SK_H = SK_T + 2 * 63 + 2;      // hashes a tile needs: w - 1 <= 63 on either side
+constexpr int SC_ITEMS = 8;                  // scan / sort: items per thread, 256 threads
+constexpr uint32_t SC_TILE = 256 * SC_ITEMS;
+
+// ---- block helpers (256 threads = 4 waves) ------------------------------------------------------------------------------------
+__device__ inline uint32_t block_excl_scan(uint32_t v, uint32_t* lds4, uint32_t& total) {
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t t = __shfl_up(inc, o, 64);
+    if ((int)lane >= o) inc += t;
+  }
+  if (lane == 63) lds4[wave] = inc;
+  __syncthreads();
+  uint32_t base = 0;
+  total = 0;
+#pragma unroll
+  for (uint32_t i = 0; i < 4; i++) {
+    const uint32_t c = lds4[i];
+    if (i < wave) base += c;
+    total += c;
+  }
+  __syncthreads();
+  return base + inc - v;
+}
+
+// ---- exclusive scan of u32 (out has n + 1 entries: out[n] = total) ---------------------------------------------------------
+__global__ __launch_bounds__(256) void k_scan_partial(const uint32_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ partial) {
+  __shared__ uint32_t lds4[4];
+  const uint64_t i0 = (uint64_t)blockIdx.x * SC_TILE + threadIdx.x * SC_ITEMS;
+  uint32_t s = 0;
+#pragma unroll
+  for (int e = 0; e < SC_ITEMS; e++) if (i0 + e < n) s += in[i0 + e];
+  uint32_t total;
+  (void)block_excl_scan(s, lds4, total);
+  if (threadIdx.x == 0) partial[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(256) void k_scan_top(uint32_t* __restrict__ partial, uint32_t nb) {
+  __shared__ uint32_t lds4[4];
+  uint32_t carry = 0;
+  for (uint32_t b0 = 0; b0 < nb; b0 += 256) {
+    const uint32_t i = b0 + threadIdx.x;
+    const uint32_t v = i < nb ? partial[i] : 0u;
+    uint32_t total;
+    const uint32_t ex = block_excl_scan(v, lds4, total);
+    if (i < nb) partial[i] = carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0) partial[nb] = carry;
+}
+
+__global__ __launch_bounds__(256) void k_scan_final(const uint32_t* __restrict__ in, uint32_t n, const uint32_t* __restrict__ partial,
+                                                    uint32_t nb, uint32_t* __restrict__ out) {
+  __shared__ uint32_t lds4[4];
+  const uint64_t i0 = (uint64_t)blockIdx.x * SC_TILE + threadIdx.x * SC_ITEMS;
+  uint32_t v[SC_ITEMS], s = 0;
+#pragma unroll
+  for (int e = 0; e < SC_ITEMS; e++) { v[e] = i0 + e < n ? in[i0 + e] : 0u; s += v[e]; }
+  uint32_t total;
+  uint32_t at = block_excl_scan(s, lds4, total) + partial[blockIdx.x];
+#pragma unroll
+  for (int e = 0; e < SC_ITEMS; e++) { if (i0 + e < n) out[i0 + e] = at; at += v[e]; }
+  if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = partial[nb];
+}
+
+// ---- sketch -----------------------------------------------------------------------------------------------------------------
+__device__ inline uint64_t hash64(uint64_t x, uint64_t m) {   // minimap2's invertible mix on 2k bits
+  x = (~x + (x << 21)) & m;
+  x ^= x >> 24;
+  x = (x + (x << 3) + (x << 8)) & m;
+  x ^= x >> 14;
+  x = (x + (x << 2) + (x << 4)) & m;
+  x ^= x >> 28;
+  x = (x + (x << 31)) & m;
+  return x;
+}
+
+// hash and strand of the k-mer that starts at base p of the read whose first word is w0
+__device__ inline uint64_t kmer_hash(const uint64_t* __restrict__ words, uint64_t w0, uint32_t p, uint32_t k, uint64_t mask, uint32_t& strand) {
+  const uint64_t wi = w0 + (p >> 5);
+  const uint32_t sh = (p & 31u) * 2u;
+  uint64_t v = words[wi] >> sh;
+  if (sh + 2u * k > 64u) v |= words[wi + 1] << (64u - sh);   // (sh > 0 here)
+  v &= mask;                                 // base p + i at bits 2i: this is the reverse complement's value once complemented
+  const uint64_t r = ~v & mask;
+  uint64_t x = __brevll(v);                  // base order reversed; the two bits of a base swapped back below
+  x = ((x & 0x5555555555555555ull) << 1) | ((x >> 1) & 0x5555555555555555ull);
+  const uint64_t f = x >> (64u - 2u * k);    // first base most significant
+  strand = r < f ? 1u : 0u;
+  if (f == r) return INF64;
+  return hash64(f < r ? f : r, mask);
+}
+
+// tile_off[r]: first tile of read r (reads shorter than k + w - 1 have none)
+__global__ __launch_bounds__(SK_T) void k_sketch(const uint64_t* __restrict__ words, const uint64_t* __restrict__ word_off,
+                                                 const uint64_t* __restrict__ base_off, const uint32_t* __restrict__ tile_off,
+                                                 uint32_t n_reads, uint32_t k, uint32_t w, uint32_t* __restrict__ tile_cnt,
+                                                 const uint32_t* __restrict__ tile_at, uint64_t* __restrict__ hash_out,
+                                                 uint64_t* __restrict__ meta_out, int write) {
+  __shared__ uint64_t sh[SK_H];
+  __shared__ uint64_t wm[SK_H];
+  __shared__ uint8_t ss[SK_H];
+  __shared__ uint32_t wc[4];
+  const uint32_t b = blockIdx.x, tid = threadIdx.x;
+  uint32_t lo_r = 0, hi_r = n_reads;          // largest r with tile_off[r] <= b
+  while (hi_r - lo_r > 1) {
+    const uint32_t mid = (lo_r + hi_r) >> 1;
+    if (tile_off[mid] <= b) lo_r = mid; else hi_r = mid;
+  }
+  const uint32_t rid = lo_r;
+  const uint32_t len = (uint32_t)(base_off[rid + 1] - base_off[rid]);
+  const uint32_t nk = len - k + 1;            // >= w (the read has tiles)
+  const uint32_t base = (b - tile_off[rid]) * SK_T;
+  const uint64_t w0 = word_off[rid];
+  const uint64_t mask = (1ull << (2 * k)) - 1;
+  const uint32_t lo = base >= w - 1 ? base - (w - 1) : 0u;
+  const uint32_t hi = min(nk, base + SK_T + (w - 1));
+  for (uint32_t i = lo + tid; i < hi; i += SK_T) {
+    uint32_t s;
+    sh[i - lo] = kmer_hash(words, w0, i, k, mask, s);
+    ss[i - lo] = (uint8_t)s;
+  }
+  __syncthreads();
+  const uint32_t s_hi = min(nk - w, base + SK_T - 1);   // last window start any k-mer of the tile lies in
+  for (uint32_t s = lo + tid; s <= s_hi; s += SK_T) {
+    uint64_t m = INF64;
+    for (uint32_t o = 0; o < w; o++) { const uint64_t v = sh[s - lo + o]; m = v < m ? v : m; }
+    wm[s - lo] = m;
+  }
+  __syncthreads();
+  const uint32_t j = base + tid;
+  bool sel = false;
+  uint64_t hj = INF64;
+  if (j < nk) {
+    hj = sh[j - lo];
+    if (hj != INF64) {
+      const uint32_t s0 = j >= w - 1 ? j - (w - 1) : 0u, s1 = min(j, nk - w);
+      for (uint32_t s = s0; s <= s1; s++) sel |= wm[s - lo] == hj;
+    }
+  }
+  const uint64_t bal = __ballot(sel);
+  const uint32_t lane = tid & 63, wave = tid >> 6;
+  if (lane == 0) wc[wave] = (uint32_t)__popcll(bal);
+  __syncthreads();
+  uint32_t before = 0, total = 0;
+  for (uint32_t i = 0; i < 4; i++) { if (i < wave) before += wc[i]; total += wc[i]; }
+  if (!write) {
+    if (tid == 0) tile_cnt[b] = total;
+    return;
+  }
+  if (sel) {
+    const uint32_t at = tile_at[b] + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1));
+    hash_out[at] = hj;
+    meta_out[at] = ((uint64_t)rid << 32) | ((uint64_t)(j + k - 1) << 1) | ss[j - lo];
+  }
+}
+
+// ---- radix sort: one 8-bit digit per pass ----------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_rs_hist(const uint64_t* __restrict__ keys, uint32_t n, uint32_t shift, uint32_t nb,
+                                                 uint32_t* __restrict__ hist) {
+  __shared__ uint32_t h[256];
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  const uint64_t i0 = (uint64_t)blockIdx.x * SC_TILE;
+#pragma unroll
+  for (int e = 0; e < SC_ITEMS; e++) {
+    const uint64_t i = i0 + e * 256 + threadIdx.x;
+    if (i < n) atomicAdd(&h[(keys[i] >> shift) & 255u], 1u);
+  }
+  __syncthreads();
+  hist[(uint64_t)threadIdx.x * nb + blockIdx.x] = h[threadIdx.x];   // digit-major: the scan gives every (digit, block) its place
+}
+
+__global__ __launch_bounds__(256) void k_rs_scatter(const uint64_t* __restrict__ keys, const uint64_t* __restrict__ pays, uint32_t n,
+                                                    uint32_t shift, uint32_t nb, const uint32_t* __restrict__ offs,
+                                                    uint64_t* __restrict__ keys_out, uint64_t* __restrict__ pays_out) {
+  __shared__ uint32_t running[256];
+  __shared__ uint32_t wcnt[4][256];
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  running[tid] = offs[(uint64_t)tid * nb + blockIdx.x];
+#pragma unroll
+  for (int v = 0; v < 4; v++) wcnt[v][tid] = 0;
+  __syncthreads();
+  const uint64_t i0 = (uint64_t)blockIdx.x * SC_TILE;
+  for (int e = 0; e < SC_ITEMS; e++) {          // elements in index order: round e holds i0 + 256 e .. + 255
+    const uint64_t i = i0 + e * 256 + tid;
+    const bool valid = i < n;
+    uint64_t key = 0, pay = 0;
+    if (valid) { key = keys[i]; pay = pays[i]; }
+    const uint32_t d = (uint32_t)(key >> shift) & 255u;
+    uint64_t peers = __ballot(valid);          // lanes of this wave with my digit
+#pragma unroll
+    for (int bit = 0; bit < 8; bit++) {
+      const bool one = (d >> bit) & 1u;
+      const uint64_t bm = __ballot(valid && one);
+      peers &= one ? bm : ~bm;
+    }
+    const uint32_t rank = (uint32_t)__popcll(peers & ((1ull << lane) - 1));
+    if (valid && rank == 0) wcnt[wave][d] = (uint32_t)__popcll(peers);
+    __syncthreads();
+    if (valid) {
+      uint32_t at = running[d] + rank;
+      for (uint32_t v = 0; v < wave; v++) at += wcnt[v][d];
+      keys_out[at] = key;
+      pays_out[at] = pay;
+    }
+    __syncthreads();
+    running[tid] += wcnt[0][tid] + wcnt[1][tid] + wcnt[2][tid] + wcnt[3][tid];
+#pragma unroll
+    for (int v = 0; v < 4; v++) wcnt[v][tid] = 0;
+    __syncthreads();
+  }
+}
+
+// ---- runs of one hash, frequency cut, anchors per occurrence --------------------------------------------------------------
+// cnt[x]: anchors occurrence x has as the target side = occurrences behind it in its run that lie in another (later) read;
+// run_end[x]: end of its run.  Runs longer than max_occ (and single occurrences) keep cnt 0 (cleared before the launch).
+__global__ __launch_bounds__(256) void k_runs(const uint64_t* __restrict__ hash, const uint64_t* __restrict__ meta, uint32_t n,
+                                              uint32_t max_occ, uint32_t* __restrict__ cnt, uint32_t* __restrict__ run_end,
+                                              unsigned long long* __restrict__ per_read) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t h = hash[i];
+  if (i > 0 && hash[i - 1] == h) return;       // the head of a run does the run
+  uint64_t e = i + 1;
+  while (e < n && hash[e] == h && e - i <= max_occ) e++;
+  const uint64_t c = e - i;
+  if (c < 2 || c > max_occ) return;
+  uint64_t nxt = e;                            // first occurrence of the next read
+  uint32_t rid_after = 0;
+  for (uint64_t j = e; j-- > i;) {
+    const uint32_t rid = (uint32_t)(meta[j] >> 32);
+    if (j + 1 < e && rid != rid_after) nxt = j + 1;
+    rid_after = rid;
+    const uint32_t m = (uint32_t)(e - nxt);
+    cnt[j] = m;
+    run_end[j] = (uint32_t)e;
+    if (m) atomicAdd(&per_read[rid], (unsigned long long)m);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_mask(const uint64_t* __restrict__ meta, const uint32_t* __restrict__ cnt, uint32_t n,
+                                              uint32_t t_lo, uint32_t t_hi, uint32_t* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t rid = (uint32_t)(meta[i] >> 32);
+  out[i] = rid >= t_lo && rid < t_hi ? cnt[i] : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_expand(const uint64_t* __restrict__ meta, const uint32_t* __restrict__ cntm,
+                                                const uint32_t* __restrict__ run_end, const uint32_t* __restrict__ aoff, uint32_t n,
+                                                const uint64_t* __restrict__ base_off, uint32_t k, uint32_t t_lo,
+                                                uint64_t* __restrict__ A, uint64_t* __restrict__ B) {
+  const uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (x >= n) return;
+  const uint32_t c = cntm[x];
+  if (!c) return;
+  const uint64_t mx = meta[x];
+  const uint32_t t = (uint32_t)(mx >> 32), tpos = ((uint32_t)mx) >> 1, st = (uint32_t)mx & 1u;
+  const uint32_t e = run_end[x];
+  uint32_t at = aoff[x];
+  for (uint32_t y = e - c; y < e; y++, at++) {
+    const uint64_t my = meta[y];
+    const uint32_t q = (uint32_t)(my >> 32), qp = ((uint32_t)my) >> 1, rel = ((uint32_t)my & 1u) ^ st;
+    const uint32_t qlen = (uint32_t)(base_off[q + 1] - base_off[q]);
+    const uint32_t qpos = rel ? qlen - qp + k - 2 : qp;     // last base of the same k-mer on the query's reverse complement
+    A[at] = ((uint64_t)tpos << 32) | qpos;
+    B[at] = ((uint64_t)(t - t_lo) << 33) | ((uint64_t)q << 1) | rel;
+  }
+}
+
+// ---- groups -------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_heads(const uint64_t* __restrict__ B, uint32_t n, uint32_t* __restrict__ flag) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) flag[i] = (i == 0 || B[i] != B[i - 1]) ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_gstart(const uint32_t* __restrict__ flag, const uint32_t* __restrict__ gidx, uint32_t n,
+                                                uint32_t* __restrict__ gstart) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n && flag[i]) gstart[gidx[i]] = (uint32_t)i;
+  if (i == 0) gstart[gidx[n]] = n;
+}
+
+__global__ __launch_bounds__(256) void k_gflag(const uint32_t* __restrict__ gstart, uint32_t ng, uint32_t min_anchors,
+                                               uint32_t* __restrict__ gf) {
+  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g < ng) gf[g] = gstart[g + 1] - gstart[g] >= min_anchors ? 1u : 0u;
+}
+
+// groups worth chaining, in group order: start, size; sort key = largest first, so that a launch does not end on one long group
+__global__ __launch_bounds__(256) void k_gcompact(const uint32_t* __restrict__ gstart, const uint32_t* __restrict__ gf,
+                                                  const uint32_t* __restrict__ cidx, uint32_t ng, uint32_t* __restrict__ cstart,
+                                                  uint32_t* __restrict__ csize, uint64_t* __restrict__ ckey, uint64_t* __restrict__ cpay) {
+  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= ng || !gf[g]) return;
+  const uint32_t c = cidx[g], s = gstart[g], sz = gstart[g + 1] - s;
+  cstart[c] = s;
+  csize[c] = sz;
+  ckey[c] = 0xffffffffu - sz;
+  cpay[c] = c;
+}
+
+// ---- chain ----------------------------------------------------------------------------------------------------------------------
+__device__ inline int32_t wave_max_i32(int32_t v) {
+  const int32_t ident = INT32_MIN;
+  v = max(v, __builtin_amdgcn_update_dpp(ident, v, 0x111, 0xf, 0xf, false));   // row_shr:1
+  v = max(v, __builtin_amdgcn_update_dpp(ident, v, 0x112, 0xf, 0xf, false));   // row_shr:2
+  v = max(v, __builtin_amdgcn_update_dpp(ident, v, 0x114, 0xf, 0xf, false));   // row_shr:4
+  v = max(v, __builtin_amdgcn_update_dpp(ident, v, 0x118, 0xf, 0xf, false));   // row_shr:8 -> lane 15 of a row holds the row
+  v = max(v, __builtin_amdgcn_update_dpp(ident, v, 0x142, 0xa, 0xf, false));   // row_bcast:15 into rows 1 and 3
+  v = max(v, __builtin_amdgcn_update_dpp(ident, v, 0x143, 0xc, 0xf, false));   // row_bcast:31 into rows 2 and 3
+  return __builtin_amdgcn_readlane(v, 63);
+}
+
+struct ChainEnd { int32_t score; uint32_t last; };
+
+// One wave per group.  Lane l holds anchor (i & 63) == l of the current block of 64 anchors (cur_*) and of the one before
+// (prev_*), and in `fr` the f of the newest anchor with that residue: for anchor i = base + m the predecessor of lane l is
+// base + l (l < m) or base - 64 + l (l >= m) — exactly i - 1 ... i - 64.
+__global__ __launch_bounds__(64) void k_chain(const uint64_t* __restrict__ A, const uint64_t* __restrict__ order,
+                                              const uint32_t* __restrict__ cstart, const uint32_t* __restrict__ csize,
+                                              uint8_t* __restrict__ pred, ChainEnd* __restrict__ ends, int32_t k, int32_t bandwidth,
+                                              int32_t max_gap) {
+  const uint32_t c = (uint32_t)order[blockIdx.x];
+  const uint32_t s0 = cstart[c], n = csize[c];
+  const uint32_t lane = threadIdx.x;
+  int32_t fr = 0, cur_t = 0, cur_q = 0, prev_t = 0, prev_q = 0;
+  int32_t best_f = -1;
+  uint32_t best_i = 0;
+  for (uint32_t base = 0; base < n; base += 64) {
+    prev_t = cur_t;
+    prev_q = cur_q;
+    if (base + lane < n) {
+      const uint64_t a = A[(uint64_t)s0 + base + lane];
+      cur_t = (int32_t)(a >> 32);
+      cur_q = (int32_t)(uint32_t)a;
+    }
+    const uint32_t m_end = min(64u, n - base);
+    uint32_t my_pd = 0;
+    for (uint32_t m = 0; m < m_end; m++) {
+      const int32_t ti = __builtin_amdgcn_readlane(cur_t, m), qi = __builtin_amdgcn_readlane(cur_q, m);
+      const bool newer = lane < m;
+      const int32_t tj = newer ? cur_t : prev_t, qj = newer ? cur_q : prev_q;
+      const bool exists = newer || base >= 64;
+      const int32_t dt = ti - tj, dq = qi - qj;
+      const int32_t diff = dt - dq;
+      const int32_t dd = diff < 0 ? -diff : diff;
+      const bool ok = exists && dt > 0 && dq > 0 && dt <= max_gap && dq <= max_gap && dd <= bandwidth;
+      int32_t sc = INT32_MIN;
+      if (ok) {
+        const int64_t cost = (((int64_t)dd * k) >> 6) + ((31 - __clz(dd + 1)) >> 1);
+        const int64_t v = (int64_t)fr + min(k, min(dt, dq)) - cost;
+        if (v > k) sc = (int32_t)v;
+      }
+      const int32_t mx = wave_max_i32(sc);
+      int32_t f_i = k;
+      uint32_t pd = 0;                          // distance to the chosen predecessor, 0: none
+      if (mx > k) {
+        const uint64_t hit = __ballot(sc == mx);
+        const uint64_t low = hit & ((1ull << m) - 1);          // the nearest: the highest lane below m, else the highest of all
+        const uint32_t lj = 63u - (uint32_t)__clzll(low ? low : hit);
+        pd = lj < m ? m - lj : m - lj + 64u;
+        f_i = mx;
+      }
+      if (lane == m) { fr = f_i; my_pd = pd; }
+      if (f_i > best_f) { best_f = f_i; best_i = base + m; }    // strictly better: the smallest i wins ties
+    }
+    if (base + lane < n) pred[(uint64_t)s0 + base + lane] = (uint8_t)my_pd;
+  }
+  if (lane == 0) ends[c] = ChainEnd{best_f, best_i};
+}
+
+struct GroupOut { uint32_t t, q, rel, n_anchors; int32_t score; uint32_t tstart, tend, qstart, qend, kept; };
+
+__global__ __launch_bounds__(256) void k_walk(const uint64_t* __restrict__ A, const uint64_t* __restrict__ B,
+                                              const uint32_t* __restrict__ cstart, const uint8_t* __restrict__ pred,
+                                              const ChainEnd* __restrict__ ends, uint32_t nc, const uint64_t* __restrict__ base_off,
+                                              uint32_t k, uint32_t t_lo, uint32_t min_score, uint32_t min_anchors,
+                                              GroupOut* __restrict__ out) {
+  const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= nc) return;
+  const uint64_t s0 = cstart[c];
+  const ChainEnd e = ends[c];
+  uint32_t i = e.last, cnt = 1;
+  for (uint32_t pd = pred[s0 + i]; pd; pd = pred[s0 + i]) { i -= pd; cnt++; }
+  const uint64_t b = B[s0], a0 = A[s0 + i], a1 = A[s0 + e.last];
+  GroupOut g;
+  g.t = t_lo + (uint32_t)(b >> 33);
+  g.q = (uint32_t)(b >> 1);
+  g.rel = (uint32_t)b & 1u;
+  g.n_anchors = cnt;
+  g.score = e.score;
+  g.tstart = (uint32_t)(a0 >> 32) - k + 1;
+  g.tend = (uint32_t)(a1 >> 32) + 1;
+  const uint32_t qs = (uint32_t)a0 - k + 1, qe = (uint32_t)a1 + 1;      // on the oriented query
+  const uint32_t qlen = (uint32_t)(base_off[g.q + 1] - base_off[g.q]);
+  g.qstart = g.rel ? qlen - qe : qs;
+  g.qend = g.rel ? qlen - qs : qe;
+  g.kept = ((int64_t)e.score >= (int64_t)min_score && cnt >= min_anchors) ? 1u : 0u;
+  out[c] = g;
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------
+struct Bufs {   // device allocations of one call, freed together
+  std::vector<void*> p;
+  ~Bufs() { for (void* q : p) if (q) (void)hipFree(q); }
+  template <typename T>
+  hipError_t get(T** out, uint64_t count) {
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, std::max<uint64_t>(count, 1) * sizeof(T) + 64);
+    if (e == hipSuccess) p.push_back(q);
+    *out = (T*)q;
+    return e;
+  }
+};
+
+#define OVL_TRY(expr)                                                                  \
+  do {                                                                                 \
+    const hipError_t _e = (expr);                                                      \
+    if (_e != hipSuccess) {                                                            \
+      err = std::string("overlap finder: " #expr ": ") + hipGetErrorString(_e);        \
+      return OVL_HIP;                                                                  \
+    }                                                                                  \
+  } while (0)
+
+inline uint32_t nblk(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
+inline uint32_t bits_of(uint64_t v) { uint32_t b = 0; while (v) { b++; v >>= 1; } return b; }   // bits to hold 0 .. v
+
+// exclusive scan of in[0 .. n) into out[0 .. n], out[n] = total; partial: nblk(n, SC_TILE) + 1 entries
+int scan_u32(const uint32_t* in, uint32_t n, uint32_t* out, uint32_t* partial, hipStream_t st, std::string& err) {
+  if (n == 0) { OVL_TRY(hipMemsetAsync(out, 0, 4, st)); return OVL_OK; }
+  const uint32_t nb = nblk(n, SC_TILE);
+  k_scan_partial<<<nb, 256, 0, st>>>(in, n, partial);
+  k_scan_top<<<1, 256, 0, st>>>(partial, nb);
+  k_scan_final<<<nb, 256, 0, st>>>(in, n, partial, nb, out);
+  OVL_TRY(hipGetLastError());
+  return OVL_OK;
+}
+
+struct SortScratch {       // for up to `cap` elements
+  uint32_t* hist = nullptr;     // 256 x blocks
+  uint32_t* offs = nullptr;     // + 1
+  uint32_t* partial = nullptr;
+  hipError_t alloc(Bufs& B, uint64_t cap) {
+    const uint64_t nb = nblk(cap, SC_TILE) + 1;
+    hipError_t e;
+    if ((e = B.get(&hist, 256 * nb)) != hipSuccess) return e;
+    if ((e = B.get(&offs, 256 * nb + 1)) != hipSuccess) return e;
+    return B.get(&partial, std::max<uint64_t>(nblk(256 * nb, SC_TILE), nb) + 2);   // scans of the histogram and of per-element arrays
+  }
+};
+
+// stable LSD sort by the digits at `shifts` (ascending significance).  The sorted arrays end up in (*k0, *p0): the pointers
+// are swapped after every pass.
+int radix_sort(uint64_t** k0, uint64_t** p0, uint64_t** k1, uint64_t** p1, uint32_t n, const std::vector<uint32_t>& shifts,
+               const SortScratch& S, hipStream_t st, std::string& err) {
+  if (n < 2) return OVL_OK;
+  const uint32_t nb = nblk(n, SC_TILE);
+  for (uint32_t sh : shifts) {
+    k_rs_hist<<<nb, 256, 0, st>>>(*k0, n, sh, nb, S.hist);
+    if (int rc = scan_u32(S.hist, 256 * nb, S.offs, S.partial, st, err)) return rc;
+    k_rs_scatter<<<nb, 256, 0, st>>>(*k0, *p0, n, sh, nb, S.offs, *k1, *p1);
+    OVL_TRY(hipGetLastError());
+    std::swap(*k0, *k1);
+    std::swap(*p0, *p1);
+  }
+  return OVL_OK;
+}
+
+void field_shifts(std::vector<uint32_t>& v, uint32_t lo, uint32_t nbits) {
+  for (uint32_t s = lo; s < lo + nbits; s += 8) v.push_back(s);
+}
+
+struct Sketch {            // device: minimizers in (rid, pos) order
+  uint64_t* hash = nullptr;
+  uint64_t* meta = nullptr;
+  uint32_t n = 0;
+  uint64_t kmers = 0;
+};
+
+int check_store(const OvlStore& S, std::string& err) {
+  if (S.n_reads > OVL_MAX_READS) { err = "overlap finder: more than 2^31 - 1 reads"; return OVL_UNSUPPORTED; }
+  for (uint32_t r = 0; r < S.n_reads; r++)
+    if (S.h_len[r] > OVL_MAX_READ_LEN) { err = "overlap finder: read " + std::to_string(r) + " is longer than 2^31 - 1 bases"; return OVL_UNSUPPORTED; }
+  return OVL_OK;
+}
+
+// extra: elements the two arrays are allocated for beyond the minimizers (they double as a sort buffer)
+int sketch_dev(const OvlStore& S, const OvlParams& P, hipStream_t st, Bufs& B, Sketch& out, std::string& err) {
+  if (int rc = check_store(S, err)) return rc;
+  std::vector<uint32_t> tile_off(S.n_reads + 1, 0);
+  uint64_t tiles = 0, kmers = 0;
+  for (uint32_t r = 0; r < S.n_reads; r++) {
+    tile_off[r] = (uint32_t)tiles;
+    if ((uint64_t)S.h_len[r] >= (uint64_t)P.k + P.w - 1) {
+      const uint64_t nk = (uint64_t)S.h_len[r] - P.k + 1;
+      kmers += nk;
+      tiles += (nk + SK_T - 1) / SK_T;
+    }
+    if (kmers > OVL_MAX_KMERS) { err = "overlap finder: more than 2^32 k-mers in the read store"; return OVL_UNSUPPORTED; }
+  }
+  tile_off[S.n_reads] = (uint32_t)tiles;
+  out.kmers = kmers;
+  out.n = 0;
+  if (!tiles) return OVL_OK;
+  const uint32_t nt = (uint32_t)tiles;
+  uint32_t *d_tile_off, *d_cnt, *d_at, *d_partial;
+  OVL_TRY(B.get(&d_tile_off, (uint64_t)S.n_reads + 1));
+  OVL_TRY(B.get(&d_cnt, nt));
+  OVL_TRY(B.get(&d_at, (uint64_t)nt + 1));
+  OVL_TRY(B.get(&d_partial, nblk(nt, SC_TILE) + 2));
+  OVL_TRY(hipMemcpyAsync(d_tile_off, tile_off.data(), 4ull * (S.n_reads + 1), hipMemcpyHostToDevice, st));
+  k_sketch<<<nt, SK_T, 0, st>>>(S.d_words, S.d_word_off, S.d_base_off, d_tile_off, S.n_reads, P.k, P.w, d_cnt, nullptr, nullptr, nullptr, 0);
+  OVL_TRY(hipGetLastError());
+  if (int rc = scan_u32(d_cnt, nt, d_at, d_partial, st, err)) return rc;
+  uint32_t total = 0;
+  OVL_TRY(hipMemcpyAsync(&total, d_at + nt, 4, hipMemcpyDeviceToHost, st));
+  OVL_TRY(hipStreamSynchronize(st));           // (also keeps tile_off alive until its copy is done)
+  out.n = total;
+  OVL_TRY(B.get(&out.hash, total));
+  OVL_TRY(B.get(&out.meta, total));
+  if (total) {
+    k_sketch<<<nt, SK_T, 0, st>>>(S.d_words, S.d_word_off, S.d_base_off, d_tile_off, S.n_reads, P.k, P.w, d_cnt, d_at, out.hash, out.meta, 1);
+    OVL_TRY(hipGetLastError());
+  }
+  return OVL_OK;
+}
+
+}  // namespace
+
+int ovl_sketch(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vector<uint64_t>& hash, std::vector<uint64_t>& meta,
+               std::string& err) {
+  Bufs B;
+  Sketch sk;
+  if (int rc = sketch_dev(S, P, st, B, sk, err)) return rc;
+  hash.resize(sk.n);
+  meta.resize(sk.n);
+  if (sk.n) {
+    OVL_TRY(hipMemcpyAsync(hash.data(), sk.hash, 8ull * sk.n, hipMemcpyDeviceToHost, st));
+    OVL_TRY(hipMemcpyAsync(meta.data(), sk.meta, 8ull * sk.n, hipMemcpyDeviceToHost, st));
+  }
+  OVL_TRY(hipStreamSynchronize(st));
+  return OVL_OK;
+}
+
+int ovl_find(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hipStream_t st, std::vector<OvlPair>& out, OvlStats& stats,
+             std::string& err) {
+  out.clear();
+  stats = OvlStats{};
+  Bufs B;
+  Sketch sk;
+  if (int rc = sketch_dev(S, P, st, B, sk, err)) return rc;
+  stats.kmers = sk.kmers;
+  stats.minimizers = sk.n;
+  const uint32_t nm = sk.n;
+  if (nm < 2) { OVL_TRY(hipStreamSynchronize(st)); return OVL_OK; }
+
+  // minimizers by hash (stable: (rid, pos) order inside a hash)
+  uint64_t *mk1, *mp1;
+  OVL_TRY(B.get(&mk1, nm));
+  OVL_TRY(B.get(&mp1, nm));
+  SortScratch ms;
+  OVL_TRY(ms.alloc(B, nm));
+  {
+    std::vector<uint32_t> shifts;
+    field_shifts(shifts, 0, 2 * P.k);
+    if (int rc = radix_sort(&sk.hash, &sk.meta, &mk1, &mp1, nm, shifts, ms, st, err)) return rc;
+  }
+  uint32_t *d_cnt, *d_run_end, *d_cntm, *d_aoff;
+  unsigned long long* d_per_read;
+  OVL_TRY(B.get(&d_cnt, nm));
+  OVL_TRY(B.get(&d_run_end, nm));
+  OVL_TRY(B.get(&d_cntm, nm));
+  OVL_TRY(B.get(&d_aoff, (uint64_t)nm + 1));
+  OVL_TRY(B.get(&d_per_read, S.n_reads));
+  OVL_TRY(hipMemsetAsync(d_cnt, 0, 4ull * nm, st));
+  OVL_TRY(hipMemsetAsync(d_per_read, 0, 8ull * S.n_reads, st));
+  k_runs<<<nblk(nm, 256), 256, 0, st>>>(sk.hash, sk.meta, nm, P.max_occ, d_cnt, d_run_end, d_per_read);
+  OVL_TRY(hipGetLastError());
+  std::vector<unsigned long long> per_read(S.n_reads);
+  OVL_TRY(hipMemcpyAsync(per_read.data(), d_per_read, 8ull * S.n_reads, hipMemcpyDeviceToHost, st));
+  OVL_TRY(hipStreamSynchronize(st));
+
+  // chunks: consecutive targets whose anchors fit the budget (a target with more runs alone)
+  const uint64_t want = std::max<uint64_t>(budget_bytes / OVL_ANCHOR_BYTES, 1);
+  std::vector<uint32_t> cut{0};
+  uint64_t cap = 0, total = 0;
+  {
+    uint64_t acc = 0;
+    for (uint32_t t = 0; t < S.n_reads; t++) {
+      if (per_read[t] > 0xfffff000ull) { err = "overlap finder: read " + std::to_string(t) + " has more than 2^32 anchors"; return OVL_UNSUPPORTED; }
+      if (acc && acc + per_read[t] > want) { cut.push_back(t); acc = 0; }
+      acc += per_read[t];
+      total += per_read[t];
+      cap = std::max(cap, acc);
+    }
+    cut.push_back(S.n_reads);
+  }
+  stats.anchors = total;
+  if (!total) return OVL_OK;
+  if (cap > 0xfffff000ull) { err = "overlap finder: more than 2^32 anchors in one chunk (lower HERRO_OVL_SCRATCH_MB)"; return OVL_UNSUPPORTED; }
+
+  uint64_t *A0, *B0, *A1, *B1, *ck0, *cp0, *ck1, *cp1;
+  uint32_t *flag, *gidx, *gstart, *gf, *cidx, *cstart, *csize;
+  uint8_t* pred;
+  ChainEnd* ends;
+  GroupOut* gout;
+  OVL_TRY(B.get(&A0, cap)); OVL_TRY(B.get(&B0, cap)); OVL_TRY(B.get(&A1, cap)); OVL_TRY(B.get(&B1, cap));
+  OVL_TRY(B.get(&flag, cap)); OVL_TRY(B.get(&gidx, cap + 1)); OVL_TRY(B.get(&gstart, cap + 1)); OVL_TRY(B.get(&gf, cap));
+  OVL_TRY(B.get(&cidx, cap + 1)); OVL_TRY(B.get(&cstart, cap)); OVL_TRY(B.get(&csize, cap));
+  const uint64_t ccap = cap / std::max(1u, P.min_anchors) + 1;     // groups of >= min_anchors anchors
+  OVL_TRY(B.get(&ck0, ccap)); OVL_TRY(B.get(&cp0, ccap)); OVL_TRY(B.get(&ck1, ccap)); OVL_TRY(B.get(&cp1, ccap));
+  OVL_TRY(B.get(&pred, cap));
+  OVL_TRY(B.get(&ends, ccap));
+  OVL_TRY(B.get(&gout, ccap));
+  SortScratch as;
+  OVL_TRY(as.alloc(B, cap));
+  uint32_t max_len = 0;
+  for (uint32_t r = 0; r < S.n_reads; r++) max_len = std::max(max_len, S.h_len[r]);
+  std::vector<GroupOut> h_out;
+
+  for (size_t ch = 0; ch + 1 < cut.size(); ch++) {
+    const uint32_t t_lo = cut[ch], t_hi = cut[ch + 1];
+    uint64_t na64 = 0;
+    for (uint32_t t = t_lo; t < t_hi; t++) na64 += per_read[t];
+    if (!na64) continue;
+    stats.chunks++;
+    const uint32_t na = (uint32_t)na64;
+    k_mask<<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cnt, nm, t_lo, t_hi, d_cntm);
+    if (int rc = scan_u32(d_cntm, nm, d_aoff, ms.partial, st, err)) return rc;
+    k_expand<<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0);
+    OVL_TRY(hipGetLastError());
+    {
+      std::vector<uint32_t> sa, sb;
+      field_shifts(sa, 0, bits_of(max_len));
+      field_shifts(sa, 32, bits_of(max_len));
+      field_shifts(sb, 0, 1 + bits_of(S.n_reads - 1));
+      field_shifts(sb, 33, bits_of(t_hi - t_lo - 1));
+      if (int rc = radix_sort(&A0, &B0, &A1, &B1, na, sa, as, st, err)) return rc;     // by (tpos, qpos)
+      if (int rc = radix_sort(&B0, &A0, &B1, &A1, na, sb, as, st, err)) return rc;     // then by (t, q, rel), stable
+    }
+    k_heads<<<nblk(na, 256), 256, 0, st>>>(B0, na, flag);
+    if (int rc = scan_u32(flag, na, gidx, as.partial, st, err)) return rc;
+    k_gstart<<<nblk(na, 256), 256, 0, st>>>(flag, gidx, na, gstart);
+    uint32_t ng = 0;
+    OVL_TRY(hipMemcpyAsync(&ng, gidx + na, 4, hipMemcpyDeviceToHost, st));
+    OVL_TRY(hipStreamSynchronize(st));
+    stats.groups += ng;
+    k_gflag<<<nblk(ng, 256), 256, 0, st>>>(gstart, ng, P.min_anchors, gf);
+    if (int rc = scan_u32(gf, ng, cidx, as.partial, st, err)) return rc;
+    uint32_t nc = 0;
+    OVL_TRY(hipMemcpyAsync(&nc, cidx + ng, 4, hipMemcpyDeviceToHost, st));
+    OVL_TRY(hipStreamSynchronize(st));
+    if (!nc) continue;
+    stats.chained += nc;
+    k_gcompact<<<nblk(ng, 256), 256, 0, st>>>(gstart, gf, cidx, ng, cstart, csize, ck0, cp0);
+    OVL_TRY(hipGetLastError());
+    if (int rc = radix_sort(&ck0, &cp0, &ck1, &cp1, nc, {0, 8, 16, 24}, as, st, err)) return rc;
+    k_chain<<<nc, 64, 0, st>>>(A0, cp0, cstart, csize, pred, ends, (int32_t)P.k, (int32_t)std::min<uint32_t>(P.bandwidth, 0x3fffffffu),
+                               (int32_t)std::min<uint32_t>(P.max_gap, 0x7fffffffu));
+    k_walk<<<nblk(nc, 256), 256, 0, st>>>(A0, B0, cstart, pred, ends, nc, S.d_base_off, P.k, t_lo, P.min_score, P.min_anchors, gout);
+    OVL_TRY(hipGetLastError());
+    h_out.resize(nc);
+    OVL_TRY(hipMemcpyAsync(h_out.data(), gout, sizeof(GroupOut) * (uint64_t)nc, hipMemcpyDeviceToHost, st));
+    OVL_TRY(hipStreamSynchronize(st));
+    for (const GroupOut& g : h_out)
+      if (g.kept) out.push_back(OvlPair{g.t, g.q, g.rel, g.n_anchors, g.score, g.tstart, g.tend, g.qstart, g.qend});
+  }
+  return OVL_OK;
+}
+
+}  // namespace herro

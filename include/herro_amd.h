@@ -370,6 +370,46 @@ const int32_t* herro_aligned_scores(const herro_aligned* a);   /* INT32_MIN for 
 uint32_t herro_aligned_failed(const herro_aligned* a);
 void herro_aligned_free(herro_aligned* a);
 
+/* ---- overlap finding on the device (csrc/overlap_dev.hip) ------------------------------------------------------------------------
+ * Stands in for the seeding and chaining half of the `minimap2 -x ava-ont` run `herro inference` starts itself without --read-alns
+ * (AlnMode::None, overlaps.rs:340-344 -> generate_batches -> call_mm2, mm2.rs:15-30): which reads of the context's store overlap,
+ * where, on which strand.  Not minimap2's output (no two-piece gaps, no z-drop extension, no -f fraction, no secondary chains) but
+ * a small specification of its own, DESIGN.md section 10 and tests/overlap_ref.py, which the kernels equal bit for bit: (k, w)
+ * minimizers under minimap2's hash64 with every tied window minimum selected; hashes with more than max_occ occurrences in the
+ * store dropped; anchors between every two occurrences in different reads; per (t, q, strand) a chain over the 64 nearest
+ * predecessors (gaps <= max_gap, diagonal drift <= bandwidth, minimap2's one-piece gap cost); kept with score >= min_score and
+ * >= min_anchors anchors.  Coordinates are the anchor span of the chain: there is no extension to the read ends.  One overlap per
+ * read pair (overlaps.rs:181-185; the better strand, forward on a tie), no self overlaps (overlaps.rs:175-179), and every pair
+ * yields two records, (t, q) and (q, t) — minimap2's --dual=yes.  Records come grouped by target in ascending read id, each
+ * target's records in ascending qid, with cigar = NULL and cigar_len = 0: the shape herro_paf_parse_coords produces, so they go into
+ * herro_align_overlaps unchanged.
+ * Parameters: a 0 field means its default — k 25, w 17, bandwidth 150, min_score 2500 (the -k -w -r -m of mm2.rs:22-26), max_gap
+ * 5000, min_anchors 3 (minimap2's -g, -n), max_occ 128.  5 <= k <= 31 and 1 <= w <= 64, else HERRO_E_INVALID (checked before
+ * anything else).  min_score 2500 is a threshold for reads of ~10 kb and more; short reads need their own.  max_occ must stay above
+ * the read depth: a true minimizer occurs once per read that covers it, and a cut below the depth removes the anchors of true
+ * overlaps.  Known limit: the chain looks back 64 ANCHORS, not bases — a tandem repeat that survives max_occ (a set of very few
+ * reads) can put more than 64 off-diagonal anchors between two anchors of the true diagonal, and the overlap comes out shorter.
+ * Limits (HERRO_E_UNSUPPORTED): 2^31 - 1 reads, reads of 2^31 - 1 bases, 2^32 k-mers in the store, 2^32 anchors per target.
+ * Scratch: 128 bytes per anchor, targets processed in read-id ranges that fit HERRO_OVL_SCRATCH_MB (default 4096; a target that
+ * needs more runs alone) — the result is byte-identical for every budget — plus 40 bytes per minimizer of the store.
+ * Runs on the context's execution stream and returns when done.  HERRO_E_STATE: no reads; HERRO_E_NO_DEVICE: a context without
+ * a device. */
+typedef struct { uint32_t k, w, max_occ, bandwidth, max_gap, min_score, min_anchors, reserved; } herro_overlap_params;
+typedef struct herro_overlaps herro_overlaps;
+int herro_find_overlaps(herro_ctx* ctx, const herro_overlap_params* params /* NULL: defaults */, herro_overlaps** out);
+uint32_t herro_overlaps_n(const herro_overlaps* o);                       /* records (two per pair) */
+uint32_t herro_overlaps_n_targets(const herro_overlaps* o);
+const uint32_t* herro_overlaps_target_ids(const herro_overlaps* o);
+const uint64_t* herro_overlaps_aln_off(const herro_overlaps* o);          /* [n_targets + 1] */
+const herro_alignment* herro_overlaps_alignments(const herro_overlaps* o);
+const int32_t* herro_overlaps_scores(const herro_overlaps* o);            /* chain score per record */
+void herro_overlaps_free(herro_overlaps* o);
+/* Test hook: stage 1 alone — the store's minimizers sorted by (rid, pos); pos = index of the k-mer's last base on the forward
+ * read, strand = 1 when the reverse complement is the canonical k-mer.  Returns their number (nothing is written when cap is
+ * smaller) or a negative error. */
+int64_t herro_debug_sketch(herro_ctx* ctx, const herro_overlap_params* params, uint64_t* hash, uint32_t* rid, uint32_t* pos,
+                           uint8_t* strand, uint64_t cap);
+
 /* ---- reads and the `herro features` sink -----------------------------------------------------
  * herro_fastx_read = get_reads (haec_io.rs:37-75) over needletail's parse_fastx_file: FASTA or FASTQ by the first byte,
  * gzip by magic, multi-line records, '\r' dropped; records shorter than min_length dropped; header split at the first blank
