@@ -34,6 +34,8 @@ EXPORTS = [
     "herro_reads_descs", "herro_reads_free", "herro_write_window_features", "herro_job_write_features",
     "herro_paf_parse_coords", "herro_align_overlaps", "herro_aligned_alignments", "herro_aligned_scores", "herro_aligned_failed",
     "herro_aligned_free",
+    "herro_align_overlaps_dev", "herro_aligned_dev_from_ops", "herro_aligned_dev_n", "herro_aligned_dev_alignments", "herro_aligned_dev_scores",
+    "herro_aligned_dev_n_ops", "herro_aligned_dev_failed", "herro_aligned_dev_cigar", "herro_aligned_dev_free", "herro_job_create_aligned",
     "herro_find_overlaps", "herro_overlaps_n", "herro_overlaps_n_targets", "herro_overlaps_target_ids", "herro_overlaps_aln_off",
     "herro_overlaps_alignments", "herro_overlaps_scores", "herro_overlaps_free", "herro_debug_sketch",
 ]
@@ -175,6 +177,20 @@ def lib():
         L.herro_aligned_failed.argtypes = [vp]
         L.herro_aligned_free.restype = None
         L.herro_aligned_free.argtypes = [vp]
+        L.herro_align_overlaps_dev.argtypes = [vp, u32, vp, vp]
+        L.herro_aligned_dev_from_ops.argtypes = [vp, u32, vp, vp, vp, vp]
+        for f in (L.herro_aligned_dev_n, L.herro_aligned_dev_failed):
+            f.restype = u32
+            f.argtypes = [vp]
+        for f in (L.herro_aligned_dev_alignments, L.herro_aligned_dev_scores, L.herro_aligned_dev_n_ops):
+            f.restype = vp
+            f.argtypes = [vp]
+        L.herro_aligned_dev_cigar.restype = C.c_int64
+        L.herro_aligned_dev_cigar.argtypes = [vp, u32, vp, u64]
+        L.herro_aligned_dev_free.restype = None
+        L.herro_aligned_dev_free.argtypes = [vp]
+        L.herro_job_create_aligned.restype = vp
+        L.herro_job_create_aligned.argtypes = [vp, u32, vp, vp, vp, vp, u32]
         L.herro_find_overlaps.argtypes = [vp, vp, vp]
         for f in (L.herro_overlaps_n, L.herro_overlaps_n_targets):
             f.restype = u32
@@ -518,6 +534,52 @@ class Context:
             self._l.herro_aligned_free(h)
         return out, cigars, scores, out[:, 9] > 0
 
+    def align_dev(self, rows: np.ndarray) -> "AlignedDev":
+        """Context.align with the ops left on the device (herro_align_overlaps_dev): a handle for create_job_aligned.  No CIGAR text
+        exists unless AlignedDev.cigar asks for one."""
+        rows = np.ascontiguousarray(rows, np.uint32)
+        n = len(rows)
+        arr = (Alignment * max(n, 1))()
+        view = np.frombuffer(arr, dtype=np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True), count=max(n, 1))
+        if n:
+            view["f"][:n, :9] = rows[:, :9]
+        h = C.c_void_p()
+        self._chk(self._l.herro_align_overlaps_dev(self.h, n, C.byref(arr), C.byref(h)))
+        return AlignedDev(self, h)
+
+    def aligned_dev_from_ops(self, rows: np.ndarray, op_off, ops) -> "AlignedDev":
+        """A handle over the caller's binary CIGARs (herro_aligned_dev_from_ops): record r has ops[op_off[r] : op_off[r + 1]], each
+        len << 2 | (0 M, 1 I, 2 D); rows as for align, taken as given."""
+        rows = np.ascontiguousarray(rows, np.uint32)
+        op_off = np.ascontiguousarray(op_off, np.uint64)
+        ops = np.ascontiguousarray(ops, np.uint32)
+        n = len(rows)
+        if len(op_off) != n + 1 or (n and int(op_off[-1]) > len(ops)):
+            raise ValueError("op_off has one entry per record + 1 and ends inside ops")
+        arr = (Alignment * max(n, 1))()
+        view = np.frombuffer(arr, dtype=np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True), count=max(n, 1))
+        if n:
+            view["f"][:n, :9] = rows[:, :9]
+        h = C.c_void_p()
+        self._chk(self._l.herro_aligned_dev_from_ops(self.h, n, C.byref(arr), op_off.ctypes.data, ops.ctypes.data if len(ops) else None, C.byref(h)))
+        return AlignedDev(self, h)
+
+    def create_job_aligned(self, rids, aln_off, rec, handle: "AlignedDev", window_size: int) -> "Job":
+        """herro_job_create_aligned: target t's alignments are records rec[aln_off[t] : aln_off[t + 1]] of `handle` (aligned_dev_job_args
+        makes the three from find_overlaps' grouping).  The handle may be closed as soon as this returns."""
+        rids = np.ascontiguousarray(rids, np.uint32)
+        aln_off = np.ascontiguousarray(aln_off, np.uint64)
+        rec = np.ascontiguousarray(rec, np.uint32)
+        if len(aln_off) != len(rids) + 1 or (len(rids) and int(aln_off[-1]) > len(rec)):
+            raise ValueError("aln_off has one entry per target + 1 and ends inside rec")
+        h = self._l.herro_job_create_aligned(self.h, len(rids), rids.ctypes.data, aln_off.ctypes.data, rec.ctypes.data if len(rec) else None,
+                                             handle.h, window_size)
+        if not h:
+            msg = self._l.herro_last_error(self.h).decode(errors="replace")
+            code = int(msg.rsplit("[code ", 1)[1].rstrip("]")) if "[code " in msg else -1
+            raise HerroError(code, msg)
+        return Job(self, h, len(rids))
+
     def _overlap_params(self, params: dict) -> OverlapParams:
         """keyword arguments -> herro_overlap_params.  A field left out (or None) takes its default, which the struct spells 0; an
         explicit k or w outside 5 .. 31 / 1 .. 64 — 0 included, which the struct could not carry — is HERRO_E_INVALID here."""
@@ -747,6 +809,41 @@ class Job:
         return {a: int(b) for a, b in zip(k, o)}
 
 
+class AlignedDev:
+    """herro_aligned_dev: aligned records whose ops live on the device.  rows u32 [n, 10] (trimmed coordinates, cigar_len 0),
+    scores i32 [n], n_ops u32 [n], ok bool [n] (False: failed, no ops)."""
+
+    def __init__(self, ctx: Context, h):
+        self.ctx, self.h, self._l = ctx, h, ctx._l
+        n = self.n = int(self._l.herro_aligned_dev_n(h))
+        self.rows = np.zeros((n, 10), np.uint32)
+        self.scores = np.zeros(n, np.int32)
+        self.n_ops = np.zeros(n, np.uint32)
+        if n:
+            res = (Alignment * n).from_address(self._l.herro_aligned_dev_alignments(h))
+            self.rows[:] = np.frombuffer(res, dtype=np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True), count=n)["f"]
+            self.scores[:] = np.ctypeslib.as_array(C.cast(self._l.herro_aligned_dev_scores(h), C.POINTER(C.c_int32)), (n,))
+            self.n_ops[:] = np.ctypeslib.as_array(C.cast(self._l.herro_aligned_dev_n_ops(h), C.POINTER(C.c_uint32)), (n,))
+        self.ok = self.n_ops > 0
+        self.failed = int(self._l.herro_aligned_dev_failed(h))
+
+    def cigar(self, r: int) -> bytes:
+        """record r's CIGAR text (herro_aligned_dev_cigar: its ops come down and are formatted for this call); b"" for a failed record"""
+        cap = 11 * int(self.n_ops[r]) + 1 if 0 <= r < self.n else 1
+        buf = C.create_string_buffer(cap)
+        n = self._l.herro_aligned_dev_cigar(self.h, r, buf, cap)
+        if n < 0:
+            raise HerroError(int(n), "herro_aligned_dev_cigar")
+        return C.string_at(buf, n)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._l.herro_aligned_dev_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+
 OW_DTYPE = np.dtype([(n, "<u4") for n in ("win", "qid", "cls", "tstart", "qbeg", "qlen", "op_begin", "op_cnt", "start_off",
                                             "end_off", "scr_off", "strand", "wtstart", "wlen")] +
                     [(n, "<u8") for n in ("t_woff", "q_woff", "q_qual_off")], align=True)   # OwDesc (csrc/pileup_core.h)
@@ -928,3 +1025,14 @@ def aligned_job_args(rids, aln_off, rows_out: np.ndarray, cigars: list[bytes], o
     ok = np.asarray(ok, bool)
     kept = np.concatenate([[0], np.cumsum(ok)]).astype(np.int64)
     return rids, np.ascontiguousarray(rows_out[ok]), kept[aln_off].astype(np.uint64), [c for c, k in zip(cigars, ok) if k]
+
+
+def aligned_dev_job_args(rids, aln_off, ok: np.ndarray):
+    """aligned_job_args for Context.create_job_aligned: (rids, aln_off', rec) with the failed records (ok False) dropped — rec holds the
+    indices of the kept ones in the handle, aln_off' regroups them over the targets.  Targets keep their place even when all their
+    records failed."""
+    rids = np.ascontiguousarray(rids, np.uint32)
+    aln_off = np.asarray(aln_off, np.int64)
+    ok = np.asarray(ok, bool)
+    kept = np.concatenate([[0], np.cumsum(ok)]).astype(np.int64)
+    return rids, kept[aln_off].astype(np.uint64), np.flatnonzero(ok).astype(np.uint32)

@@ -1,5 +1,5 @@
 // cigar_dev.h — device side of herro_job_create's text work: CIGAR text -> binary ops + cut records, one workgroup per
-// alignment (cigar_dev.hip).  The host keeps the windowing itself (window_cuts, windowing.hpp), which reads nothing but
+// alignment (cigar_dev.hip), or the same records from binary ops that already lie on the device (launch_ops_scan).  The host keeps the windowing itself (window_cuts, windowing.hpp), which reads nothing but
 // these records.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -35,5 +35,11 @@ struct CigCut {           // == herro::Cut + padding (32 B); in discovery order,
 
 void launch_cigar_scan(const uint8_t* d_txt, const CigIn* d_in, CigOut* d_out, CigCut* d_cuts, uint32_t* d_ops,
                        uint32_t n_aln, uint32_t W, hipStream_t st);
+
+// The same records from ops that are binary already (k_ops_scan): d_store holds `len << 2 | type` words, CigIn::txt_off is the first WORD of an alignment's
+// slice in it, CigIn::len its op count, CigIn::op_off its place in d_ops with room for exactly that many (skip is not read).  *d_err gets pair_err or-ed in
+// when an alignment has two insertion ops in a row.
+void launch_ops_scan(const uint32_t* d_store, const CigIn* d_in, CigOut* d_out, CigCut* d_cuts, uint32_t* d_ops, uint32_t* d_err, uint32_t pair_err,
+                     uint32_t n_aln, uint32_t W, hipStream_t st);
 
 }  // namespace herro

@@ -1,4 +1,5 @@
-// cigar_dev.hip — CIGAR text -> binary ops + cut records on the GPU, one workgroup per alignment.
+// cigar_dev.hip — CIGAR text -> binary ops + cut records on the GPU, one workgroup per alignment (k_cigar_scan), and the same records from ops that
+// are binary and on the device already (k_ops_scan, at the end: the hand-off from the aligner, herro_job_create_aligned).
 //
 // herro_job_create's host cost was ~95 % text decoding (5 000 ops per 4096-bp window of 32 overlaps, ~4 ns each on the
 // host: 20 us of CPU per window, which on a host with few usable cores caps the end-to-end rate at half the device rate).
@@ -215,12 +216,98 @@ __global__ __launch_bounds__(CW * 64) void k_cigar_scan(const uint8_t* __restric
   }
 }
 
+// k_ops_scan — the binary sibling of k_cigar_scan: the ops are already `len << 2 | type` words in a store on the device (the aligner's dense output,
+// herro_align_overlaps_dev, or a caller's own binary CIGARs, herro_aligned_dev_from_ops) and nothing has to be decoded.  Same records out — the ops in the
+// job's op array (room for exactly n_ops: CigIn::len counts ops here and CigIn::txt_off is the slice's first word in the store), CigOut, one CigCut per
+// non-insertion op whose end reaches the next window boundary — so k_window_cuts and everything behind it (build_dev.hip) run unchanged.  One wave per
+// alignment, a step is 64 ops (one 4-byte load per lane, the next step's issued before this one is looked at); an op's index is its lane's, its running
+// target / query / insertion totals come from three DPP sums and the carries from lane 63.  Two insertion ops in a row raise `pair_err` in *err besides
+// their flag: herro_job_create_aligned then rebuilds the job from the text of its ops.
+__global__ __launch_bounds__(CW * 64) void k_ops_scan(const uint32_t* __restrict__ store, const CigIn* __restrict__ in, CigOut* __restrict__ out,
+                                                      CigCut* __restrict__ cuts, uint32_t* __restrict__ ops, uint32_t* __restrict__ err, uint32_t pair_err,
+                                                      uint32_t W, uint32_t n_aln) {
+  __shared__ uint32_t s_nc[CW], s_fl[CW];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t ai = blockIdx.x * CW + wv;
+  if (ai >= n_aln) return;   // (wave-uniform; no block barrier anywhere below)
+  const CigIn a = in[ai];
+  const uint32_t* s = store + a.txt_off;
+  uint32_t* o = ops + a.op_off;
+  CigCut* cut = cuts + a.cut_off;
+  const uint32_t n = a.len;
+  if (lane == 0) { s_nc[wv] = 0; s_fl[wv] = 0; }
+  wave_lds_sync();
+  uint32_t t_c = a.tstart, q_c = 0, i_c = 0, prev_i_c = 0;   // carries: running totals, "the last op was an insertion"
+  uint32_t flags = 0;
+  uint32_t v = lane < n ? s[lane] : 0u;
+  for (uint32_t base = 0; base < n; base += 64) {
+    const uint32_t k = base + lane;
+    const uint32_t vn = (k + 64 < n && k + 64 > k) ? s[k + 64] : 0u;
+    const bool valid = k < n;
+    uint32_t op = v;
+    if (valid && (op_type(op) == 3u || op_len(op) == 0)) { flags |= CIG_MALFORMED; op = (1u << 2) | OP_M; }   // (what decode() leaves in place of an op it does not read)
+    const uint32_t ty = op_type(op), l = valid ? op_len(op) : 0u;
+    const uint32_t is_i = valid && ty == OP_I;
+    const uint32_t st = ty != OP_I ? l : 0u, sq = ty != OP_D ? l : 0u, si = ty == OP_I ? l : 0u;
+    const uint32_t in_t = wave_incl_sum(st), in_q = wave_incl_sum(sq), in_i = wave_incl_sum(si);
+    const uint32_t t = t_c + in_t - st, q = q_c + in_q - sq, ins = i_c + in_i - si;
+    uint32_t prev_i = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)is_i, 0x138, 0xf, 0xf, false);   // wave_shr:1
+    if (lane == 0) prev_i = prev_i_c;
+    if (valid) {
+      o[k] = op;
+      if (is_i & prev_i) flags |= CIG_INS_PAIR;
+      const unsigned long long wnext = ((unsigned long long)(t / W) + 1ull) * W;   // first window boundary above my running target position
+      const uint32_t tnew = t + st;
+      if (!is_i && (unsigned long long)tnew >= wnext) {
+        const uint32_t slot = atomicAdd(&s_nc[wv], 1u);
+        if (slot < a.cut_cap) {
+          CigCut c{k, t, q, ins, op, 0, 0, 0};
+          cut[slot] = c;
+        } else {
+          flags |= CIG_CUT_OVERFLOW;
+        }
+      }
+    }
+    t_c += lane63(in_t); q_c += lane63(in_q); i_c += lane63(in_i);
+    prev_i_c = lane63(is_i);
+    v = vn;
+  }
+  if (flags) atomicOr(&s_fl[wv], flags);
+  // the lanes read back ops and cuts their neighbours wrote to global memory: release / acquire at workgroup scope (see k_cigar_scan on agent scope)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  auto ld = [&](uint32_t idx) { return __hip_atomic_load(o + idx, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP); };
+  const uint32_t n_cut_all = __hip_atomic_load(&s_nc[wv], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  const uint32_t n_cut = min(n_cut_all, a.cut_cap);
+  for (uint32_t c = lane; c < n_cut; c += 64) {
+    const uint32_t kk = __hip_atomic_load(&cut[c].k, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    cut[c].o1 = kk + 1 < n ? ld(kk + 1) : 0u;
+    cut[c].o2 = kk + 2 < n ? ld(kk + 2) : 0u;
+  }
+  if (lane == 0) {
+    CigOut r;
+    r.n_ops = n; r.t_end = t_c; r.q_end = q_c; r.ins_end = i_c;
+    r.n_cuts = n_cut_all; r.flags = __hip_atomic_load(&s_fl[wv], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    r.op0 = n ? ld(0) : 0u;
+    r.opn = n ? ld(n - 1) : 0u;
+    out[ai] = r;
+    if (r.flags & CIG_INS_PAIR) atomicOr(err, pair_err);
+  }
+}
+
 }  // namespace
 
 void launch_cigar_scan(const uint8_t* d_txt, const CigIn* d_in, CigOut* d_out, CigCut* d_cuts, uint32_t* d_ops, uint32_t n_aln,
                        uint32_t W, hipStream_t st) {
   if (n_aln == 0) return;
   hipLaunchKernelGGL(k_cigar_scan, dim3((n_aln + CW - 1) / CW), dim3(CW * 64), 0, st, d_txt, d_in, d_out, d_cuts, d_ops, W, n_aln);
+}
+
+void launch_ops_scan(const uint32_t* d_store, const CigIn* d_in, CigOut* d_out, CigCut* d_cuts, uint32_t* d_ops, uint32_t* d_err, uint32_t pair_err,
+                     uint32_t n_aln, uint32_t W, hipStream_t st) {
+  if (n_aln == 0) return;
+  hipLaunchKernelGGL(k_ops_scan, dim3((n_aln + CW - 1) / CW), dim3(CW * 64), 0, st, d_store, d_in, d_out, d_cuts, d_ops, d_err, pair_err, W, n_aln);
 }
 
 }  // namespace herro

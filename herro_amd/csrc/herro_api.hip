@@ -243,6 +243,7 @@ struct herro_job {
   std::vector<uint32_t> dbg_ops;   // herro_debug_job_array(ops) of such a job: fetched on demand
   bool dev_built = false;          // windows and descriptors were built on the device (build_dev.hip): the overlap descriptors and the tile list exist there only
   std::vector<OwDesc> dbg_ow;      // ... and come down for herro_debug_job_array
+  bool from_ops_text = false;      // herro_job_create_aligned built it from the TEXT of its ops (its direct path was not taken or did not settle the job)
   std::vector<uint32_t> dbg_tw, dbg_tr;
   uint64_t reads_gen = 0;
   uint32_t n_skipped_alns = 0, n_failed_targets = 0;  // inputs the library does not support, left out (herro_job_skipped)
@@ -1363,7 +1364,7 @@ int herro_debug_set_host_build(herro_ctx* ctx, int on) {
   return HERRO_OK;
 }
 
-int herro_debug_job_dev_built(const herro_job* job) { return job ? (job->dev_built ? 1 : 0) : HERRO_E_INVALID; }
+int herro_debug_job_dev_built(const herro_job* job) { return job ? (job->dev_built && !job->from_ops_text ? 1 : 0) : HERRO_E_INVALID; }
 
 int herro_debug_force_precision(herro_ctx* ctx, int on) {
   if (!ctx) return HERRO_E_INVALID;
@@ -1668,9 +1669,101 @@ int herro_host_unregister(herro_ctx* ctx, const void* p) {
   return HERRO_OK;
 }
 
+// ---- what herro_job_create settles on the host for the device build (round 6) because it needs no CIGAR: who is left out (parse_paf's rules), the ratio
+// classes by read name, the windows of every target, the coordinate checks.  false: something this pass would have to report — the host build words it.
+// Shared by herro_job_create and herro_job_create_aligned: the records are the same whether their ops arrive as text or from a device-resident handle.
+namespace {
+struct JobPrepass {
+  std::vector<TgtMeta> tmeta;
+  std::vector<AlnMeta> ameta;
+  std::vector<uint64_t> cls;          // [n_targets + 1] prefix of the targets' ratio classes
+  std::vector<uint32_t> skip;         // per target: alignments left out
+  std::vector<std::string> first;     // ... and the message for its first
+  uint32_t n_win = 0, n_cls = 0;
+};
+
+bool job_prepass(herro_ctx* ctx, HostPool& hpool, uint32_t n_targets, const uint32_t* rids, const uint64_t* aln_off, const herro_alignment* alns,
+                 uint32_t W, std::vector<uint32_t>& tgt_win_off, JobPrepass& P) {
+  const uint64_t a0 = n_targets ? aln_off[0] : 0, nA = n_targets ? aln_off[n_targets] - a0 : 0;
+  std::vector<TgtMeta>& tmeta = P.tmeta;
+  std::vector<AlnMeta>& ameta = P.ameta;
+  tmeta.resize(n_targets);
+  ameta.resize(nA);
+  uint64_t nwin = 0, ncls = 0;
+  for (uint32_t t = 0; t < n_targets; t++) {
+    const uint32_t rid = rids[t];
+    if (rid >= ctx->n_reads) return false;
+    const uint32_t tlen = ctx->read_len[rid], nwt = (tlen + W - 1) / W;
+    if (nwt > 65535) return false;
+    tmeta[t] = TgtMeta{rid, tlen, nwt, (uint32_t)nwin, (uint32_t)(aln_off[t] - a0), (uint32_t)(aln_off[t + 1] - aln_off[t]), 0, 0};
+    tgt_win_off[t] = (uint32_t)nwin;
+    nwin += nwt;
+  }
+  if (nwin > 0xffffffffull || nwin == 0) return false;
+  tgt_win_off[n_targets] = (uint32_t)nwin;
+  P.cls.assign(n_targets + 1, 0);
+  P.skip.assign(n_targets, 0);
+  P.first.assign(n_targets, std::string());
+  std::atomic<bool> ok{true};
+  hpool.run(n_targets, [&](uint32_t t) {
+    const TgtMeta& tm_ = tmeta[t];
+    std::unordered_map<uint32_t, uint32_t> cls_of_name;
+    std::unordered_map<uint32_t, uint32_t> seen_qid;
+    uint32_t ncl = 0;
+    for (uint32_t a = 0; a < tm_.n_aln; a++) {
+      const herro_alignment& al = alns[a0 + tm_.aln0 + a];
+      AlnMeta& m = ameta[tm_.aln0 + a];
+      m = AlnMeta{al.qid, al.qstart, al.qend, al.tstart, al.tend, al.strand ? 1u : 0u, t, 0};
+      if (al.tid != tm_.rid || al.qid >= ctx->n_reads) { ok = false; return; }
+      const char* why = nullptr;
+      if (al.qid == tm_.rid) why = "self overlap (dropped by parse_paf, overlaps.rs:175-179)";
+      else if (seen_qid.count(al.qid)) why = "second alignment of the same (query,target) pair (dropped by parse_paf, overlaps.rs:181-185)";
+      if (why) {
+        m.flags |= 2u;
+        if (!P.skip[t]++) P.first[t] = "target rid " + std::to_string(tm_.rid) + ", alignment " + std::to_string(a) + " (qid " + std::to_string(al.qid) + "): " + why;
+        continue;
+      }
+      seen_qid[al.qid] = a;
+      if (al.tlen != tm_.tlen || al.qend > ctx->read_len[al.qid] || al.tend > tm_.tlen) { ok = false; return; }
+      const uint32_t nc = ctx->name_class[al.qid];
+      auto it = cls_of_name.find(nc);
+      if (it == cls_of_name.end()) it = cls_of_name.emplace(nc, ncl++).first;
+      m.cls = it->second;   // target-local; the job-level base is added below
+    }
+    P.cls[t + 1] = ncl;
+  });
+  if (!ok) return false;
+  for (uint32_t t = 0; t < n_targets; t++) P.cls[t + 1] += P.cls[t];
+  ncls = P.cls[n_targets];
+  if (ncls > 0xffffffffull) return false;
+  hpool.run(n_targets, [&](uint32_t t) {
+    const TgtMeta& tm_ = tmeta[t];
+    for (uint32_t a = 0; a < tm_.n_aln; a++) ameta[tm_.aln0 + a].cls += (uint32_t)P.cls[t];
+  });
+  P.n_win = (uint32_t)nwin;
+  P.n_cls = (uint32_t)ncls;
+  return true;
+}
+
+// The ops of a job's alignments where they already lie on the device as `len << 2 | type` words (herro_job_create_aligned): alignment i of `alns` has
+// n_ops[i] ops from word off[i] of d_store on.
+struct OpsSrc { const uint32_t* d_store; const uint64_t* off; const uint32_t* n_ops; };
+}  // namespace
+
 // ---- job -------------------------------------------------------------------------------------------
+// herro_job_create (src == nullptr: the ops come as CIGAR text) and the direct path of herro_job_create_aligned (src: they are on the device; the caller
+// has checked that the context builds on the device).  *unsettled is raised, with nothing reported, when the direct path does not settle the job: the
+// caller then goes through the text of the job's ops.
+static herro_job* job_create_from(herro_ctx* ctx, uint32_t n_targets, const uint32_t* rids, const uint64_t* aln_off,
+                                  const herro_alignment* alns, uint32_t W, const OpsSrc* src, bool* unsettled);
+
 herro_job* herro_job_create(herro_ctx* ctx, uint32_t n_targets, const uint32_t* rids, const uint64_t* aln_off,
                             const herro_alignment* alns, uint32_t W) {
+  return job_create_from(ctx, n_targets, rids, aln_off, alns, W, nullptr, nullptr);
+}
+
+static herro_job* job_create_from(herro_ctx* ctx, uint32_t n_targets, const uint32_t* rids, const uint64_t* aln_off,
+                                  const herro_alignment* alns, uint32_t W, const OpsSrc* src, bool* unsettled) {
   if (!ctx) return nullptr;
   auto fail = [&](int code, const std::string& m) -> herro_job* {
     ctx->err = m + " [code " + std::to_string(code) + "]";
@@ -1706,12 +1799,12 @@ herro_job* herro_job_create(herro_ctx* ctx, uint32_t n_targets, const uint32_t* 
   const uint64_t a0 = n_targets ? aln_off[0] : 0, nA = n_targets ? aln_off[n_targets] - a0 : 0;
   auto t_scanned = t_begin;
   bool try_dev = false, dev_built = false;
-  std::vector<TgtMeta> tmeta;
-  std::vector<AlnMeta> ameta;
-  std::vector<uint64_t> pre_cls;
-  std::vector<uint32_t> pre_skip;
-  std::vector<std::string> pre_first;
-  uint32_t pre_nwin = 0, pre_ncls = 0;
+  JobPrepass PP;
+  const std::vector<TgtMeta>& tmeta = PP.tmeta;
+  const std::vector<AlnMeta>& ameta = PP.ameta;
+  const std::vector<uint32_t>& pre_skip = PP.skip;
+  const std::vector<std::string>& pre_first = PP.first;
+  const uint32_t &pre_nwin = PP.n_win, &pre_ncls = PP.n_cls;
   BuildDev BD{};
   BuildTotals btot{};
   if (!ctx->host_only && ctx->dev_scan && nA) {
@@ -1723,8 +1816,14 @@ herro_job* herro_job_create(herro_ctx* ctx, uint32_t n_targets, const uint32_t* 
     const unsigned char *t_lo = nullptr, *t_hi = nullptr;   // the range of the caller's memory that holds the job's texts
     for (uint64_t g = 0; g < nA; g++) {
       const herro_alignment& al = alns[a0 + g];
-      if (al.cigar_len && !al.cigar) return fail(HERRO_E_INVALID, "alignment without cigar");
       const uint32_t cap = (al.tend >= al.tstart ? (al.tend - al.tstart) / W : 0u) + 3u;   // one cut per window boundary the coordinates span, + slack
+      if (src) {   // binary ops on the device (k_ops_scan): the slice's first word and its op count; the job's op array has room for exactly that many
+        in[g] = CigIn{src->off[a0 + g], src->n_ops[a0 + g], al.tstart, (uint32_t)opn, (uint32_t)cutn, cap, 0};
+        opn += src->n_ops[a0 + g];
+        cutn += cap;
+        continue;
+      }
+      if (al.cigar_len && !al.cigar) return fail(HERRO_E_INVALID, "alignment without cigar");
       in[g] = CigIn{txt, al.cigar_len, al.tstart, (uint32_t)opn, (uint32_t)cutn, cap, 0};
       txt += ((uint64_t)al.cigar_len + 15) & ~uint64_t(15);
       opn += (uint64_t)al.cigar_len / 2 + 1;
@@ -1738,70 +1837,8 @@ herro_job* herro_job_create(herro_ctx* ctx, uint32_t n_targets, const uint32_t* 
     if (opn > 0xffffffffull || cutn > 0xffffffffull) return fail(HERRO_E_UNSUPPORTED, "job too large (ops exceed 2^32)");
     // ---- device build (round 6): what needs no CIGAR is settled here — who is left out (parse_paf's rules), the ratio classes, the windows of every target —
     // and goes up beside the text; anything this pass would have to report sends the job down the host path below, which words it.
-    try_dev = ctx->dev_build;
-    if (try_dev) {
-      tmeta.resize(n_targets);
-      ameta.resize(nA);
-      uint64_t nwin = 0, ncls = 0;
-      for (uint32_t t = 0; t < n_targets && try_dev; t++) {
-        const uint32_t rid = rids[t];
-        if (rid >= ctx->n_reads) { try_dev = false; break; }
-        const uint32_t tlen = ctx->read_len[rid], nwt = (tlen + W - 1) / W;
-        if (nwt > 65535) { try_dev = false; break; }
-        tmeta[t] = TgtMeta{rid, tlen, nwt, (uint32_t)nwin, (uint32_t)(aln_off[t] - a0), (uint32_t)(aln_off[t + 1] - aln_off[t]), 0, 0};
-        job->tgt_win_off[t] = (uint32_t)nwin;
-        nwin += nwt;
-      }
-      if (nwin > 0xffffffffull || nwin == 0) try_dev = false;
-      if (try_dev) {
-        job->tgt_win_off[n_targets] = (uint32_t)nwin;
-        pre_cls.assign(n_targets + 1, 0);
-        pre_skip.assign(n_targets, 0);
-        pre_first.assign(n_targets, std::string());
-        std::atomic<bool> ok{true};
-        hpool.run(n_targets, [&](uint32_t t) {
-          const TgtMeta& tm_ = tmeta[t];
-          std::unordered_map<uint32_t, uint32_t> cls_of_name;
-          std::unordered_map<uint32_t, uint32_t> seen_qid;
-          uint32_t ncl = 0;
-          for (uint32_t a = 0; a < tm_.n_aln; a++) {
-            const herro_alignment& al = alns[a0 + tm_.aln0 + a];
-            AlnMeta& m = ameta[tm_.aln0 + a];
-            m = AlnMeta{al.qid, al.qstart, al.qend, al.tstart, al.tend, al.strand ? 1u : 0u, t, 0};
-            if (al.tid != tm_.rid || al.qid >= ctx->n_reads) { ok = false; return; }
-            const char* why = nullptr;
-            if (al.qid == tm_.rid) why = "self overlap (dropped by parse_paf, overlaps.rs:175-179)";
-            else if (seen_qid.count(al.qid)) why = "second alignment of the same (query,target) pair (dropped by parse_paf, overlaps.rs:181-185)";
-            if (why) {
-              m.flags |= 2u;
-              if (!pre_skip[t]++) pre_first[t] = "target rid " + std::to_string(tm_.rid) + ", alignment " + std::to_string(a) + " (qid " + std::to_string(al.qid) + "): " + why;
-              continue;
-            }
-            seen_qid[al.qid] = a;
-            if (al.tlen != tm_.tlen || al.qend > ctx->read_len[al.qid] || al.tend > tm_.tlen) { ok = false; return; }
-            const uint32_t nc = ctx->name_class[al.qid];
-            auto it = cls_of_name.find(nc);
-            if (it == cls_of_name.end()) it = cls_of_name.emplace(nc, ncl++).first;
-            m.cls = it->second;   // target-local; the job-level base is added below
-          }
-          pre_cls[t + 1] = ncl;
-        });
-        if (!ok) try_dev = false;
-        else {
-          for (uint32_t t = 0; t < n_targets; t++) pre_cls[t + 1] += pre_cls[t];
-          ncls = pre_cls[n_targets];
-          if (ncls > 0xffffffffull) try_dev = false;
-        }
-        if (try_dev) {
-          hpool.run(n_targets, [&](uint32_t t) {
-            const TgtMeta& tm_ = tmeta[t];
-            for (uint32_t a = 0; a < tm_.n_aln; a++) ameta[tm_.aln0 + a].cls += (uint32_t)pre_cls[t];
-          });
-          pre_nwin = (uint32_t)nwin;
-          pre_ncls = (uint32_t)ncls;
-        }
-      }
-    }
+    try_dev = ctx->dev_build && job_prepass(ctx, hpool, n_targets, rids, aln_off, alns, W, job->tgt_win_off, PP);
+    if (src && !try_dev) { *unsettled = true; return nullptr; }
     // Zero-copy (round 5): when the texts lie densely inside a range the caller registered (herro_host_register: the PAF text of
     // herro_paf_parse_view, a CIGAR blob), that range goes up in ONE copy from where it is — no staging pass over the bytes (0.9 of the
     // 3.4 ms an unloaded herro_job_create of 4096 windows took, and the part that fights the other feeders for memory bandwidth).  A
@@ -1841,7 +1878,7 @@ herro_job* herro_job_create(herro_ctx* ctx, uint32_t n_targets, const uint32_t* 
     unsigned char* hs = (unsigned char*)stage.p;
     unsigned char* dsb = (unsigned char*)job->scan.p + ops_bytes;
     const uint32_t per = 32, nblk = (uint32_t)((nA + per - 1) / per);
-    if (!direct) hpool.run(nblk, [&](uint32_t b) {
+    if (!direct && !src) hpool.run(nblk, [&](uint32_t b) {
       for (uint64_t g = (uint64_t)b * per; g < std::min<uint64_t>(nA, (uint64_t)(b + 1) * per); g++) {
         const herro_alignment& al = alns[a0 + g];
         unsigned char* d = hs + in[g].txt_off;
@@ -1865,12 +1902,18 @@ herro_job* herro_job_create(herro_ctx* ctx, uint32_t n_targets, const uint32_t* 
     if (direct) {   // the texts from the caller's registered range (same alignment modulo 16), the alignment records from the staging block
       e = read_host ? hipSuccess : hipMemcpyAsync(dsb + lead, t_lo, span, hipMemcpyHostToDevice, ctx->prep_stream);
       if (e == hipSuccess) e = hipMemcpyAsync(dsb + o_in, hs + o_in, o_out - o_in, hipMemcpyHostToDevice, ctx->prep_stream);
+    } else if (src) {   // no text: the alignment records alone
+      e = hipMemcpyAsync(dsb + o_in, hs + o_in, o_out - o_in, hipMemcpyHostToDevice, ctx->prep_stream);
     } else {
       e = hipMemcpyAsync(dsb, hs, o_out, hipMemcpyHostToDevice, ctx->prep_stream);
     }
     if (try_dev && e == hipSuccess) e = hipMemcpyAsync(dsb + o_tot, hs + o_tot, sizeof(BuildTotals), hipMemcpyHostToDevice, ctx->prep_stream);
     if (pe[1]) (void)hipEventRecord(pe[1], ctx->prep_stream);
-    if (e == hipSuccess) {
+    if (e == hipSuccess && src) {
+      launch_ops_scan(src->d_store, (const CigIn*)(dsb + o_in), (CigOut*)(dsb + o_out), (CigCut*)(dsb + o_cut), (uint32_t*)job->scan.p,
+                      &((BuildTotals*)(dsb + o_tot))->err, BLD_SCAN_FLAG, (uint32_t)nA, W, ctx->prep_stream);
+      e = hipGetLastError();
+    } else if (e == hipSuccess) {
       launch_cigar_scan(read_host ? t_dev - lead : dsb, (const CigIn*)(dsb + o_in), (CigOut*)(dsb + o_out), (CigCut*)(dsb + o_cut), (uint32_t*)job->scan.p, (uint32_t)nA, W, ctx->prep_stream);
       e = hipGetLastError();
     }
@@ -1893,6 +1936,11 @@ herro_job* herro_job_create(herro_ctx* ctx, uint32_t n_targets, const uint32_t* 
         std::memcpy(&btot, hs + o_tot, sizeof btot);
         dev_built = btot.err == 0;
       }
+    }
+    if (src && e == hipSuccess && !dev_built) {   // the text path rebuilds the job (the stream is idle: the totals' event has been waited for)
+      for (auto& ev : pe) if (ev) (void)hipEventDestroy(ev);
+      *unsettled = true;
+      return nullptr;
     }
     if (!dev_built) {   // the host cuts the windows from the scan's records (and words whatever is wrong with the input)
       if (e == hipSuccess) e = hipMemcpyAsync(hs + o_out, dsb + o_out, o_tot - o_out, hipMemcpyDeviceToHost, ctx->prep_stream);
@@ -3266,11 +3314,49 @@ struct herro_aligned {
   uint32_t failed = 0;
 };
 
-extern "C" {
+// The same records with their ops left on the device (herro_align_overlaps_dev), or a caller's own binary CIGARs (herro_aligned_dev_from_ops).
+struct herro_aligned_dev {
+  herro_ctx* ctx = nullptr;
+  int device = 0;
+  bool host_only = false;              // a handle of herro_debug_host_ctx (from_ops only): the store is h_ops
+  std::vector<herro_alignment> alns;   // trimmed coordinates; cigar = NULL, cigar_len = 0
+  std::vector<int32_t> scores;
+  std::vector<uint32_t> n_ops;         // 0: failed
+  std::vector<uint64_t> op_off;        // first op of every record in the store
+  uint32_t failed = 0;
+  uint32_t* d_ops = nullptr;           // the op store: every record's ops, `len << 2 | type`
+  uint64_t used = 0, cap = 0;          // ... in ops
+  std::vector<uint32_t> h_ops;
+};
 
-int herro_align_overlaps(herro_ctx* ctx, uint32_t n, const herro_alignment* in, herro_aligned** out) {
-  if (!ctx || !out || (n && !in)) return HERRO_E_INVALID;
-  *out = nullptr;
+namespace {
+uint32_t dec_digits(uint32_t v) { uint32_t k = 1; while (v >= 10) { v /= 10; k++; } return k; }
+// bytes of "<len><M|I|D>" per op
+uint64_t ops_text_bytes(const uint32_t* ops, uint32_t n) {
+  uint64_t b = 0;
+  for (uint32_t x = 0; x < n; x++) b += dec_digits(ops[x] >> 2) + 1;
+  return b;
+}
+char* ops_text(const uint32_t* ops, uint32_t n, char* p) {
+  for (uint32_t x = 0; x < n; x++) {
+    p += snprintf(p, 12, "%u", ops[x] >> 2);
+    *p++ = "MID?"[ops[x] & 3u];   // ('?': type 3 of a caller's own ops; herro_job_create refuses the letter)
+  }
+  return p;
+}
+// coordinates after fix_cigar dropped a leading / trailing indel
+void apply_trim(herro_alignment& a, const herro::AlignOut& o) {
+  a.tstart += o.tdrop0;
+  a.tend -= o.tdrop1;
+  if (a.strand == 0) { a.qstart += o.qdrop0; a.qend -= o.qdrop1; }
+  else { a.qend -= o.qdrop0; a.qstart += o.qdrop1; }
+}
+
+// Validation, chunking (HERRO_ALIGN_SCRATCH_MB) and the kernel runs of herro_align_overlaps and herro_align_overlaps_dev.  Behind every chunk the host
+// reads its op total and its AlignOut records and hands the chunk's dense ops, still on the device, to take(total, d_dense, r_done, at): it stores them and
+// says where (at: the chunk's first op in the caller's store; r_done: records aligned so far, this chunk's included).  ops_at[r]: record r's first op there.
+template <class Take>
+int align_chunks(herro_ctx* ctx, uint32_t n, const herro_alignment* in, std::vector<herro::AlignOut>& res, std::vector<uint64_t>& ops_at, Take take) {
   if (ctx->host_only) { ctx->err = "herro_align_overlaps: the context has no device"; return HERRO_E_NO_DEVICE; }
   if (!ctx->d_words) { ctx->err = "herro_set_reads must be called first"; return HERRO_E_STATE; }
   for (uint32_t r = 0; r < n; r++) {
@@ -3290,9 +3376,8 @@ int herro_align_overlaps(herro_ctx* ctx, uint32_t n, const herro_alignment* in, 
   uint64_t budget = 4096ull << 20;
   if (const char* e = getenv("HERRO_ALIGN_SCRATCH_MB")) budget = (uint64_t)std::max(1ll, atoll(e)) << 20;
   std::vector<herro::AlignIn> recs(n);
-  std::vector<herro::AlignOut> res(n);
-  std::vector<uint32_t> ops;            // every record's final ops, record order
-  std::vector<uint64_t> ops_at(n + 1, 0);
+  res.resize(n);
+  ops_at.assign(n, 0);
   // chunks: consecutive records whose scratch fits the budget (a record larger than the budget runs alone)
   uint64_t max_scr = 0, max_dense = 0;
   std::vector<uint32_t> cut{0};
@@ -3347,21 +3432,33 @@ int herro_align_overlaps(herro_ctx* ctx, uint32_t n, const herro_alignment* in, 
     if ((e = hipMemcpyAsync(res.data() + r0, d_out + r0, sizeof(herro::AlignOut) * (r1 - r0), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess)
       return hip_fail(e, "results");
     if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return hip_fail(e, "k_align");
-    const size_t at = ops.size();
-    ops.resize(at + total);
-    if (total && (e = hipMemcpy(ops.data() + at, d_dense, 4ull * total, hipMemcpyDeviceToHost)) != hipSuccess) return hip_fail(e, "ops");
-    for (uint32_t r = r0; r < r1; r++) res[r].ops_off += (uint32_t)at;
+    uint64_t at = 0;
+    if ((e = take(total, d_dense, r1, at)) != hipSuccess) return hip_fail(e, "ops");
+    for (uint32_t r = r0; r < r1; r++) ops_at[r] = at + res[r].ops_off;
   }
+  if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return hip_fail(e, "ops");   // (a device-resident store: its last copy has landed)
   release();
+  return HERRO_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int herro_align_overlaps(herro_ctx* ctx, uint32_t n, const herro_alignment* in, herro_aligned** out) {
+  if (!ctx || !out || (n && !in)) return HERRO_E_INVALID;
+  *out = nullptr;
+  std::vector<herro::AlignOut> res;
+  std::vector<uint32_t> ops;            // every record's final ops, record order
+  std::vector<uint64_t> ops_at;
+  const int rc = align_chunks(ctx, n, in, res, ops_at, [&](uint32_t total, const uint32_t* d_dense, uint32_t, uint64_t& at) {
+    at = ops.size();
+    ops.resize(at + total);
+    return total ? hipMemcpy(ops.data() + at, d_dense, 4ull * total, hipMemcpyDeviceToHost) : hipSuccess;
+  });
+  if (rc != HERRO_OK) return rc;
   // text: "<len><M|I|D>" per op, records back to back
-  auto digits = [](uint32_t v) { uint32_t k = 1; while (v >= 10) { v /= 10; k++; } return k; };
   std::vector<uint64_t> toff(n + 1, 0);
-  for (uint32_t r = 0; r < n; r++) {
-    uint64_t b = 0;
-    if (!res[r].failed)
-      for (uint32_t x = 0; x < res[r].n_ops; x++) b += digits(ops[res[r].ops_off + x] >> 2) + 1;
-    toff[r + 1] = toff[r] + b;
-  }
+  for (uint32_t r = 0; r < n; r++) toff[r + 1] = toff[r] + (res[r].failed ? 0 : ops_text_bytes(ops.data() + ops_at[r], res[r].n_ops));
   auto* h = new herro_aligned();
   h->text.resize(std::max<uint64_t>(toff[n], 1));
   h->alns.assign(in, in + n);
@@ -3373,16 +3470,8 @@ int herro_align_overlaps(herro_ctx* ctx, uint32_t n, const herro_alignment* in, 
     a.cigar_len = (uint32_t)(toff[r + 1] - toff[r]);
     if (o.failed) { h->scores[r] = INT32_MIN; a.cigar_len = 0; return; }
     h->scores[r] = o.score;
-    char* p = &h->text[toff[r]];
-    for (uint32_t x = 0; x < o.n_ops; x++) {
-      const uint32_t op = ops[o.ops_off + x];
-      p += snprintf(p, 12, "%u", op >> 2);
-      *p++ = "MID"[op & 3u];
-    }
-    a.tstart += o.tdrop0;
-    a.tend -= o.tdrop1;
-    if (a.strand == 0) { a.qstart += o.qdrop0; a.qend -= o.qdrop1; }
-    else { a.qend -= o.qdrop0; a.qstart += o.qdrop1; }
+    ops_text(ops.data() + ops_at[r], o.n_ops, &h->text[toff[r]]);
+    apply_trim(a, o);
   });
   for (uint32_t r = 0; r < n; r++) h->failed += res[r].failed ? 1u : 0u;
   *out = h;
@@ -3393,6 +3482,178 @@ const herro_alignment* herro_aligned_alignments(const herro_aligned* a) { return
 const int32_t* herro_aligned_scores(const herro_aligned* a) { return a ? a->scores.data() : nullptr; }
 uint32_t herro_aligned_failed(const herro_aligned* a) { return a ? a->failed : 0; }
 void herro_aligned_free(herro_aligned* a) { delete a; }
+
+// ---- device-resident hand-off: the aligner's ops stay where k_align wrote them, the job builder reads them there ----------------
+int herro_align_overlaps_dev(herro_ctx* ctx, uint32_t n, const herro_alignment* in, herro_aligned_dev** out) {
+  if (!ctx || !out || (n && !in)) return HERRO_E_INVALID;
+  *out = nullptr;
+  std::unique_ptr<herro_aligned_dev, void (*)(herro_aligned_dev*)> h(new herro_aligned_dev(), herro_aligned_dev_free);
+  h->ctx = ctx; h->device = ctx->device;
+  std::vector<herro::AlignOut> res;
+  // The store grows by chunks: the first chunk's ops per record, projected over all records plus an eighth, sizes it; a chunk that does not fit moves it
+  // to twice the projection (device to device, behind the chunk's synchronisation: nothing reads the old block any more).
+  const int rc = align_chunks(ctx, n, in, res, h->op_off, [&](uint32_t total, const uint32_t* d_dense, uint32_t r_done, uint64_t& at) {
+    at = h->used;
+    if (!total) return hipSuccess;
+    hipError_t e;
+    if (h->used + total > h->cap) {
+      const uint64_t proj = (h->used + total) * (uint64_t)n / std::max(r_done, 1u);
+      const uint64_t cap = std::max<uint64_t>(h->used + total, (h->cap ? 2 : 1) * (proj + proj / 8)) + 1024;
+      uint32_t* d = nullptr;
+      if ((e = hipMalloc((void**)&d, cap * 4)) != hipSuccess) return e;
+      if (h->used && (e = hipMemcpyAsync(d, h->d_ops, h->used * 4, hipMemcpyDeviceToDevice, ctx->stream)) != hipSuccess) { (void)hipFree(d); return e; }
+      if (h->d_ops) {
+        if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) { (void)hipFree(d); return e; }
+        (void)hipFree(h->d_ops);
+      }
+      h->d_ops = d; h->cap = cap;
+    }
+    // (stream order: the next chunk's kernel, which overwrites d_dense, queues behind this copy)
+    if ((e = hipMemcpyAsync(h->d_ops + h->used, d_dense, 4ull * total, hipMemcpyDeviceToDevice, ctx->stream)) != hipSuccess) return e;
+    h->used += total;
+    return hipSuccess;
+  });
+  if (rc != HERRO_OK) return rc;
+  h->alns.assign(in, in + n);
+  h->scores.resize(n);
+  h->n_ops.resize(n);
+  for (uint32_t r = 0; r < n; r++) {
+    herro_alignment& a = h->alns[r];
+    const herro::AlignOut& o = res[r];
+    a.cigar = nullptr; a.cigar_len = 0;
+    if (o.failed) { h->scores[r] = INT32_MIN; h->n_ops[r] = 0; h->failed++; continue; }
+    h->scores[r] = o.score;
+    h->n_ops[r] = o.n_ops;
+    apply_trim(a, o);
+  }
+  *out = h.release();
+  return HERRO_OK;
+}
+
+int herro_aligned_dev_from_ops(herro_ctx* ctx, uint32_t n, const herro_alignment* alns, const uint64_t* op_off, const uint32_t* ops, herro_aligned_dev** out) {
+  if (!ctx || !out || !op_off || (n && !alns)) return HERRO_E_INVALID;
+  *out = nullptr;
+  for (uint32_t r = 0; r < n; r++)
+    if (op_off[r + 1] < op_off[r] || op_off[r + 1] - op_off[r] > 0xffffffffull) {
+      ctx->err = "herro_aligned_dev_from_ops: record " + std::to_string(r) + ": op_off must ascend";
+      return HERRO_E_INVALID;
+    }
+  const uint64_t lo = op_off[0], total = op_off[n] - lo;
+  if (total && !ops) return HERRO_E_INVALID;
+  std::unique_ptr<herro_aligned_dev, void (*)(herro_aligned_dev*)> h(new herro_aligned_dev(), herro_aligned_dev_free);
+  h->ctx = ctx; h->device = ctx->device; h->host_only = ctx->host_only;
+  h->alns.assign(alns, alns + n);
+  h->scores.assign(n, 0);
+  h->n_ops.resize(n);
+  h->op_off.resize(n);
+  for (uint32_t r = 0; r < n; r++) {
+    h->alns[r].cigar = nullptr; h->alns[r].cigar_len = 0;
+    h->n_ops[r] = (uint32_t)(op_off[r + 1] - op_off[r]);
+    h->op_off[r] = op_off[r] - lo;
+    if (!h->n_ops[r]) { h->scores[r] = INT32_MIN; h->failed++; }
+  }
+  h->used = h->cap = total;
+  if (ctx->host_only) {
+    h->h_ops.assign(ops + lo, ops + lo + total);
+  } else if (total) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMalloc((void**)&h->d_ops, total * 4));
+    HIP_TRY(ctx, hipMemcpy(h->d_ops, ops + lo, total * 4, hipMemcpyHostToDevice));
+  }
+  *out = h.release();
+  return HERRO_OK;
+}
+
+uint32_t herro_aligned_dev_n(const herro_aligned_dev* a) { return a ? (uint32_t)a->alns.size() : 0; }
+const herro_alignment* herro_aligned_dev_alignments(const herro_aligned_dev* a) { return a ? a->alns.data() : nullptr; }
+const int32_t* herro_aligned_dev_scores(const herro_aligned_dev* a) { return a ? a->scores.data() : nullptr; }
+const uint32_t* herro_aligned_dev_n_ops(const herro_aligned_dev* a) { return a ? a->n_ops.data() : nullptr; }
+uint32_t herro_aligned_dev_failed(const herro_aligned_dev* a) { return a ? a->failed : 0; }
+
+void herro_aligned_dev_free(herro_aligned_dev* a) {
+  if (!a) return;
+  if (a->d_ops && hipSetDevice(a->device) == hipSuccess) (void)hipFree(a->d_ops);   // (hipFree waits for the device: no kernel is still reading the store)
+  delete a;
+}
+
+// ops [lo, hi) of the handle's store on the host
+static int aligned_dev_fetch(const herro_aligned_dev* a, uint64_t lo, uint64_t hi, std::vector<uint32_t>& v) {
+  v.resize(hi - lo);
+  if (hi == lo) return HERRO_OK;
+  if (a->host_only) { std::memcpy(v.data(), a->h_ops.data() + lo, (hi - lo) * 4); return HERRO_OK; }
+  if (hipSetDevice(a->device) != hipSuccess || hipMemcpy(v.data(), a->d_ops + lo, (hi - lo) * 4, hipMemcpyDeviceToHost) != hipSuccess) return HERRO_E_NO_DEVICE;
+  return HERRO_OK;
+}
+
+int64_t herro_aligned_dev_cigar(const herro_aligned_dev* a, uint32_t r, char* out, uint64_t cap) {
+  if (!a || r >= a->alns.size()) return HERRO_E_INVALID;
+  std::vector<uint32_t> v;
+  const int rc = aligned_dev_fetch(a, a->op_off[r], a->op_off[r] + a->n_ops[r], v);
+  if (rc != HERRO_OK) return rc;
+  const uint64_t need = ops_text_bytes(v.data(), (uint32_t)v.size());
+  if (out && need <= cap) ops_text(v.data(), (uint32_t)v.size(), out);
+  return (int64_t)need;
+}
+
+herro_job* herro_job_create_aligned(herro_ctx* ctx, uint32_t n_targets, const uint32_t* rids, const uint64_t* aln_off, const uint32_t* rec,
+                                    const herro_aligned_dev* a, uint32_t W) {
+  if (!ctx) return nullptr;
+  auto fail = [&](int code, const std::string& m) -> herro_job* {
+    ctx->err = m + " [code " + std::to_string(code) + "]";
+    ctx->create_code = code;
+    return nullptr;
+  };
+  ctx->create_code = HERRO_OK;
+  if (!a) return fail(HERRO_E_INVALID, "herro_job_create_aligned: null handle");
+  if (n_targets && (!rids || !aln_off)) return fail(HERRO_E_INVALID, "null argument");
+  const uint64_t a0 = n_targets ? aln_off[0] : 0, a1 = n_targets ? aln_off[n_targets] : 0;
+  if (a1 < a0) return fail(HERRO_E_INVALID, "aln_off must ascend");
+  if (a1 > a0 && !rec) return fail(HERRO_E_INVALID, "herro_job_create_aligned: null rec");
+  if (a->ctx != ctx) return fail(HERRO_E_INVALID, "herro_job_create_aligned: the handle belongs to another context");
+  // the job's records, in its order: coordinates from the handle, ops by reference
+  std::vector<herro_alignment> sel(a1);
+  std::vector<uint64_t> off(a1, 0);
+  std::vector<uint32_t> nops(a1, 0);
+  uint64_t lo = ~0ull, hi = 0;
+  for (uint64_t g = a0; g < a1; g++) {
+    const uint32_t r = rec[g];
+    if (r >= a->alns.size())
+      return fail(HERRO_E_INVALID, "herro_job_create_aligned: rec[" + std::to_string(g) + "] = " + std::to_string(r) + " is outside the handle's " + std::to_string(a->alns.size()) + " records");
+    if (!a->n_ops[r])
+      return fail(HERRO_E_INVALID, "herro_job_create_aligned: rec[" + std::to_string(g) + "] = " + std::to_string(r) + " is a failed record (no ops)");
+    sel[g] = a->alns[r];
+    off[g] = a->op_off[r];
+    nops[g] = a->n_ops[r];
+    lo = std::min(lo, off[g]);
+    hi = std::max(hi, off[g] + nops[g]);
+  }
+  if (!ctx->host_only && ctx->dev_scan && ctx->dev_build && a1 > a0) {   // direct: k_ops_scan reads the handle's store, no text anywhere
+    const OpsSrc src{a->d_ops, off.data(), nops.data()};
+    bool unsettled = false;
+    herro_job* job = job_create_from(ctx, n_targets, rids, aln_off, sel.data(), W, &src, &unsettled);
+    if (job || !unsettled) return job;
+  }
+  // Not taken (host build, host scan, a device-free context) or not settled (BuildTotals::err, the pre-pass): this job's ops come down, are formatted and
+  // go through herro_job_create, whose results and error texts are then the text path's by construction.  The span [lo, hi) of the store comes down in one copy.
+  std::vector<uint32_t> ops;
+  if (a1 > a0) {
+    const int rc = aligned_dev_fetch(a, lo, hi, ops);
+    if (rc != HERRO_OK) return fail(rc, "herro_job_create_aligned: copying the ops down failed");
+  }
+  std::vector<uint64_t> toff(a1 + 1, 0);
+  for (uint64_t g = a0; g < a1; g++) toff[g + 1] = toff[g] + ops_text_bytes(ops.data() + (off[g] - lo), nops[g]);
+  std::string text(toff[a1] + 1, '\0');
+  host_pool(ctx).run((uint32_t)((a1 - a0 + 63) / 64), [&](uint32_t b) {
+    for (uint64_t g = a0 + (uint64_t)b * 64; g < std::min(a1, a0 + (uint64_t)(b + 1) * 64); g++) {
+      ops_text(ops.data() + (off[g] - lo), nops[g], &text[toff[g]]);
+      sel[g].cigar = reinterpret_cast<const uint8_t*>(text.data() + toff[g]);
+      sel[g].cigar_len = (uint32_t)(toff[g + 1] - toff[g]);
+    }
+  });
+  herro_job* job = herro_job_create(ctx, n_targets, rids, aln_off, sel.data(), W);
+  if (job) job->from_ops_text = true;
+  return job;
+}
 
 }  // extern "C"
 

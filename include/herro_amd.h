@@ -268,7 +268,8 @@ int herro_debug_set_featurize_planes(herro_ctx* ctx, int on);
 /* Test hooks for the two ways a job's windows and descriptors are built (herro_job_create): on the device behind the CIGAR scan (csrc/build_dev.hip, the
  * default since round 6) or by the host from the scan's cut records (rounds 3-5; still what runs when the device meets anything it does not settle itself —
  * a text the scan kernel flags, an input the reference panics on — and what words the error).  herro_debug_set_host_build(ctx, 1) selects the host build for
- * the jobs created from then on; herro_debug_job_dev_built says which one built a job.  tests/test_gpu_build_dev.py compares their descriptor arrays. */
+ * the jobs created from then on; herro_debug_job_dev_built says which one built a job (for a job of
+ * herro_job_create_aligned: 1 when its direct path built it, 0 when it went through the text of its ops).  tests/test_gpu_build_dev.py compares their descriptor arrays. */
 int herro_debug_set_host_build(herro_ctx* ctx, int on);
 int herro_debug_job_dev_built(const herro_job* job);
 /* Host-only test hooks for the rules k_rows applies in position space (csrc/pileup_core.h): n count vectors counts[i][5] (A C G T * on a base row, the
@@ -369,6 +370,39 @@ const herro_alignment* herro_aligned_alignments(const herro_aligned* a);
 const int32_t* herro_aligned_scores(const herro_aligned* a);   /* INT32_MIN for failed records */
 uint32_t herro_aligned_failed(const herro_aligned* a);
 void herro_aligned_free(herro_aligned* a);
+
+/* ---- device-resident hand-off: aligner -> job builder without CIGAR text ---------------------------------
+ * k_align's final ops and herro_job_create's op array use one encoding, `len << 2 | type` with type 0 M, 1 I, 2 D.
+ * herro_align_overlaps_dev is herro_align_overlaps — same validation, chunking, error codes and messages, same coordinates, scores and
+ * failed records — but every record's ops stay in a store on the device: behind each chunk the host reads the chunk's op total and its
+ * per-record results, nothing else.  herro_job_create_aligned builds a job from records of such a handle: the binary sibling of the
+ * CIGAR scan (k_ops_scan, csrc/cigar_dev.hip) reads the store where it is.  No text is printed, staged, uploaded or decoded. */
+typedef struct herro_aligned_dev herro_aligned_dev;
+int herro_align_overlaps_dev(herro_ctx* ctx, uint32_t n, const herro_alignment* in, herro_aligned_dev** out);
+/* A handle over the caller's own binary CIGARs: record r has ops[op_off[r] .. op_off[r + 1]), each `len << 2 | type`; the coordinates
+ * are taken as given; a record without ops counts as failed.  Also made on a device-free context (herro_debug_host_ctx), for the host
+ * half of herro_job_create_aligned.  Ops herro_job_create would refuse as text (length 0, type 3) are refused by herro_job_create_aligned. */
+int herro_aligned_dev_from_ops(herro_ctx* ctx, uint32_t n, const herro_alignment* alns, const uint64_t* op_off /* [n + 1] */,
+                               const uint32_t* ops, herro_aligned_dev** out);
+uint32_t herro_aligned_dev_n(const herro_aligned_dev* a);
+const herro_alignment* herro_aligned_dev_alignments(const herro_aligned_dev* a);   /* trimmed coordinates; cigar = NULL, cigar_len = 0 */
+const int32_t* herro_aligned_dev_scores(const herro_aligned_dev* a);               /* INT32_MIN: failed */
+const uint32_t* herro_aligned_dev_n_ops(const herro_aligned_dev* a);               /* per record; 0: failed */
+uint32_t herro_aligned_dev_failed(const herro_aligned_dev* a);
+/* One record's CIGAR text on demand (the only way its ops reach the host): returns its length in bytes — 0 for a failed record — and
+ * writes it, without a terminator, when out != NULL and cap is large enough; < 0: HERRO_E_*. */
+int64_t herro_aligned_dev_cigar(const herro_aligned_dev* a, uint32_t r, char* out, uint64_t cap);
+/* Safe once herro_job_create_aligned has returned: the job owns a copy of its ops. */
+void herro_aligned_dev_free(herro_aligned_dev* a);
+/* The job herro_job_create builds from the same records, in the same order, with the texts herro_align_overlaps returns for them
+ * (windows, descriptors, skipped counts and message, every later result; only the op array is denser: exactly n_ops slots per record).
+ * Alignments of target t are records rec[aln_off[t] .. aln_off[t + 1]) of the handle.  HERRO_E_INVALID (herro_job_create_status), with
+ * a message that names the record: a failed record, an index outside the handle, a handle of another context.  When the device build
+ * is not taken or does not settle the job — herro_debug_set_host_build, HERRO_HOST_SCAN=1, anything the device flags, a device-free
+ * context — the job's ops come down, are formatted and go through herro_job_create itself: results and error texts are the text
+ * path's.  herro_debug_job_dev_built is 1 for a job the direct path built.  Threading as herro_job_create. */
+herro_job* herro_job_create_aligned(herro_ctx* ctx, uint32_t n_targets, const uint32_t* rids, const uint64_t* aln_off,
+                                    const uint32_t* rec, const herro_aligned_dev* a, uint32_t window_size);
 
 /* ---- overlap finding on the device (csrc/overlap_dev.hip) ------------------------------------------------------------------------
  * Stands in for the seeding and chaining half of the `minimap2 -x ava-ont` run `herro inference` starts itself without --read-alns

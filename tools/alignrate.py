@@ -3,10 +3,17 @@ synthetic generator's default ONT-like error.  Prints one JSON line: records/s, 
 4096-bp-window equivalents/s (one window = 32 records), for the whole call (upload, kernel, ops back, text) — run it under
 `rocprofv3 --kernel-trace --stats` for the kernel alone.
 
-    python tools/alignrate.py [--targets 2048] [--reps 3]"""
+Two legs follow in the same process on the same records, from the records to a job that is ready to featurize (DESIGN.md section 9,
+"device-resident hand-off"), both straight on the C ABI so that neither pays for Python objects per record:
+    text    herro_align_overlaps -> (regroup the records that aligned) -> herro_job_create -> herro_aligned_free
+    dev     herro_align_overlaps_dev -> (the same regrouping, as indices) -> herro_job_create_aligned -> herro_aligned_dev_free
+Each is timed --reps times after a warm-up; "legs" holds the median, the fastest and the slowest run of each and the ratio of the medians.
+
+    python tools/alignrate.py [--targets 2048] [--reps 5] [--window 4096]"""
 from __future__ import annotations
 
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -17,30 +24,95 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from herro_amd import api, synth  # noqa: E402
 
+_ALN = np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True)
+
+
+def _job_or_raise(c, h):
+    if not h:
+        raise api.HerroError(c._l.herro_job_create_status(c.h), c.last_error())
+    return h
+
+
+def text_leg(c, arr, n, rids, aln_off, W):
+    """seconds from the records to the job through CIGAR text; the job is freed outside the clock"""
+    L = c._l
+    t0 = time.perf_counter()
+    h = C.c_void_p()
+    c._chk(L.herro_align_overlaps(c.h, n, C.byref(arr), C.byref(h)))
+    alns = L.herro_aligned_alignments(h)
+    off = aln_off
+    if L.herro_aligned_failed(h):                     # drop the failed records, keep every target's place (api.aligned_job_args)
+        v = np.frombuffer((api.Alignment * n).from_address(alns), _ALN, n)
+        ok = v["f"][:, 9] > 0
+        kept = np.ascontiguousarray(v[ok])
+        alns = kept.ctypes.data
+        off = np.concatenate([[0], np.cumsum(ok)]).astype(np.uint64)[aln_off.astype(np.int64)]
+    job = _job_or_raise(c, L.herro_job_create(c.h, len(rids), rids.ctypes.data, off.ctypes.data, alns, W))
+    L.herro_aligned_free(h)
+    t = time.perf_counter() - t0
+    L.herro_job_free(job)
+    return t
+
+
+def dev_leg(c, arr, n, rids, aln_off, W):
+    """the same through the device-resident handle"""
+    L = c._l
+    t0 = time.perf_counter()
+    h = C.c_void_p()
+    c._chk(L.herro_align_overlaps_dev(c.h, n, C.byref(arr), C.byref(h)))
+    n_ops = np.ctypeslib.as_array(C.cast(L.herro_aligned_dev_n_ops(h), C.POINTER(C.c_uint32)), (n,))
+    _, off, rec = api.aligned_dev_job_args(rids, aln_off, n_ops > 0)
+    job = _job_or_raise(c, L.herro_job_create_aligned(c.h, len(rids), rids.ctypes.data, off.ctypes.data, rec.ctypes.data, h, W))
+    built = L.herro_debug_job_dev_built(job)
+    L.herro_aligned_dev_free(h)
+    t = time.perf_counter() - t0
+    L.herro_job_free(job)
+    assert built == 1, "the direct path was not taken"
+    return t
+
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--targets", type=int, default=2048)
     ap.add_argument("--overlaps", type=int, default=32)
     ap.add_argument("--target-len", type=int, default=4096)
-    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--window", type=int, default=4096)
+    ap.add_argument("--legs-only", action="store_true", help="skip the timing of Context.align (a profiler run wants the two legs alone)")
     a = ap.parse_args()
     sb = synth.generate_parallel(a.targets, a.target_len, a.overlaps, chunk=64)
     rows = np.ascontiguousarray(sb.aln[:, :9])
     c = api.Context(0)
     c.set_reads(sb.seq, sb.qual, sb.off)
-    c.align(rows[: min(len(rows), 4096)])           # warm-up (code objects, allocator)
-    times = []
-    for _ in range(a.reps):
-        t0 = time.perf_counter()
-        out, cig, sc, ok = c.align(rows)
-        times.append(time.perf_counter() - t0)
-    t = min(times)
-    cells = float(((rows[:, 3] - rows[:, 2]).astype(np.int64) + (rows[:, 8] - rows[:, 7]) + 1).sum()) * 128
     n = len(rows)
-    print(json.dumps({"records": n, "failed": int((~ok).sum()), "seconds": t, "records_per_s": n / t, "cells_per_s": cells / t,
-                      "window_equivalents_per_s": n / t / a.overlaps, "mean_record_bp": float((rows[:, 8] - rows[:, 7]).mean()),
-                      "ops_bytes": int(out[:, 9].astype(np.int64).sum())}))
+    res = {"records": n}
+    if not a.legs_only:
+        c.align(rows[: min(len(rows), 4096)])           # warm-up (code objects, allocator)
+        times = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            out, cig, sc, ok = c.align(rows)
+            times.append(time.perf_counter() - t0)
+        t = min(times)
+        cells = float(((rows[:, 3] - rows[:, 2]).astype(np.int64) + (rows[:, 8] - rows[:, 7]) + 1).sum()) * 128
+        res.update({"failed": int((~ok).sum()), "seconds": t, "records_per_s": n / t, "cells_per_s": cells / t,
+                    "window_equivalents_per_s": n / t / a.overlaps, "mean_record_bp": float((rows[:, 8] - rows[:, 7]).mean()),
+                    "ops_bytes": int(out[:, 9].astype(np.int64).sum())})
+        del out, cig
+    arr = (api.Alignment * max(n, 1))()
+    np.frombuffer(arr, _ALN, max(n, 1))["f"][:n, :9] = rows
+    rids = np.ascontiguousarray(sb.tgt_rid, np.uint32)
+    aln_off = np.ascontiguousarray(sb.tgt_aln_off, np.uint64)
+    legs = {}
+    for name, leg in (("text", text_leg), ("dev", dev_leg)):
+        leg(c, arr, n, rids, aln_off, a.window)         # warm-up (arenas of the job, code objects)
+        ts = sorted(leg(c, arr, n, rids, aln_off, a.window) for _ in range(a.reps))
+        legs[name] = {"median_s": ts[len(ts) // 2], "min_s": ts[0], "max_s": ts[-1], "records_per_s": n / ts[len(ts) // 2]}
+    legs["dev_over_text"] = legs["text"]["median_s"] / legs["dev"]["median_s"]
+    legs["window"] = a.window
+    legs["reps"] = a.reps
+    res["legs"] = legs
+    print(json.dumps(res))
     c.close()
 
 
