@@ -38,6 +38,7 @@ EXPORTS = [
     "herro_aligned_dev_n_ops", "herro_aligned_dev_failed", "herro_aligned_dev_cigar", "herro_aligned_dev_free", "herro_job_create_aligned",
     "herro_find_overlaps", "herro_overlaps_n", "herro_overlaps_n_targets", "herro_overlaps_target_ids", "herro_overlaps_aln_off",
     "herro_overlaps_alignments", "herro_overlaps_scores", "herro_overlaps_free", "herro_debug_sketch",
+    "herro_extend_overlaps", "herro_extended_n", "herro_extended_alignments", "herro_extended_ext", "herro_extended_scores", "herro_extended_free",
 ]
 
 
@@ -55,6 +56,10 @@ class Alignment(C.Structure):  # herro_alignment
 
 class OverlapParams(C.Structure):  # herro_overlap_params (0 = the field's default)
     _fields_ = [(n, C.c_uint32) for n in ("k", "w", "max_occ", "bandwidth", "max_gap", "min_score", "min_anchors", "reserved")]
+
+
+class ExtendParams(C.Structure):  # herro_extend_params (0 = the field's default)
+    _fields_ = [("zdrop", C.c_uint32), ("max_ext", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
 class WindowInfo(C.Structure):  # herro_window_info
@@ -200,6 +205,14 @@ def lib():
             f.argtypes = [vp]
         L.herro_overlaps_free.restype = None
         L.herro_overlaps_free.argtypes = [vp]
+        L.herro_extend_overlaps.argtypes = [vp, u32, vp, vp, vp]
+        L.herro_extended_n.restype = u32
+        L.herro_extended_n.argtypes = [vp]
+        for f in (L.herro_extended_alignments, L.herro_extended_ext, L.herro_extended_scores):
+            f.restype = vp
+            f.argtypes = [vp]
+        L.herro_extended_free.restype = None
+        L.herro_extended_free.argtypes = [vp]
         L.herro_debug_sketch.restype = C.c_int64
         L.herro_debug_sketch.argtypes = [vp, vp, vp, vp, vp, vp, u64]
         L.herro_debug_host_ctx.restype = vp
@@ -616,6 +629,36 @@ class Context:
         finally:
             self._l.herro_overlaps_free(h)
         return rids, rows, aln_off, scores
+
+    def extend_overlaps(self, rows: np.ndarray, zdrop: int = 0, max_ext: int = 0):
+        """Extends coordinate-only overlaps to where the reads stop agreeing (herro_extend_overlaps): the step between
+        find_overlaps and align / align_dev.  rows: u32 [n, >=9] as find_overlaps returns and align takes; zdrop, max_ext: 0 = the defaults
+        (400, 2048).  Returns (rows_out u32 [n, 10] with the extended coordinates and cigar_len 0, ext u32 [n, 4]: bases gained as t_left,
+        q_left, t_right, q_right — the q lengths on the oriented query —, scores i32 [n, 2]: left, right)."""
+        rows = np.ascontiguousarray(rows, np.uint32)
+        n = len(rows)
+        if not 0 <= int(zdrop) <= 0xFFFFFFFF or not 0 <= int(max_ext) <= 0xFFFFFFFF:
+            raise HerroError(-1, "extend parameters: zdrop and max_ext are unsigned 32-bit values")
+        arr = (Alignment * max(n, 1))()
+        view = np.frombuffer(arr, dtype=np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True), count=max(n, 1))
+        if n:
+            view["f"][:n, :9] = rows[:, :9]
+        p = ExtendParams(zdrop=int(zdrop), max_ext=int(max_ext))
+        h = C.c_void_p()
+        self._chk(self._l.herro_extend_overlaps(self.h, n, C.byref(arr), C.byref(p), C.byref(h)))
+        try:
+            out = np.zeros((n, 10), np.uint32)
+            ext = np.zeros((n, 4), np.uint32)
+            scores = np.zeros((n, 2), np.int32)
+            if n:
+                assert self._l.herro_extended_n(h) == n
+                res = (Alignment * n).from_address(self._l.herro_extended_alignments(h))
+                out[:] = np.frombuffer(res, dtype=np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True), count=n)["f"]
+                ext[:] = np.ctypeslib.as_array(C.cast(self._l.herro_extended_ext(h), C.POINTER(C.c_uint32)), (n, 4))
+                scores[:] = np.ctypeslib.as_array(C.cast(self._l.herro_extended_scores(h), C.POINTER(C.c_int32)), (n, 2))
+        finally:
+            self._l.herro_extended_free(h)
+        return out, ext, scores
 
     def sketch(self, **params):
         """The store's minimizers sorted by (rid, pos) (herro_debug_sketch): (hash u64, rid u32, pos u32, strand u8)."""

@@ -1,6 +1,7 @@
 // align_dev.h — base-level alignment of overlaps given by coordinates only (align_dev.hip): the GPU counterpart of the
 // `minimap2 -c` step that `herro inference` runs without --read-alns (mm2.rs:15-30), followed by the reference's
 // fix_cigar normalisation (aligners.rs:138-250).  One wave64 per record; the specification is DESIGN.md §9.
+// Before it, the ends-free extension of an overlap's two ends (k_extend: one wave64 per record and side).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,5 +35,26 @@ inline uint64_t align_scratch_bytes(uint32_t n, uint32_t m) {
 
 void launch_align(const uint64_t* d_words, const AlignIn* d_in, AlignOut* d_out, uint8_t* d_scr, uint32_t* d_dense,
                   uint32_t* d_count, uint32_t n_rec, hipStream_t st);
+
+// ---- ends-free extension of an overlap's two ends (k_extend) --------------------------------------------
+constexpr uint32_t EXTEND_ZDROP = 400;            // herro_extend_params.zdrop = 0
+constexpr uint32_t EXTEND_MAX_EXT = 2048;         // herro_extend_params.max_ext = 0
+constexpr uint32_t EXTEND_MAX_EXT_LIMIT = 1u << 20;
+
+struct ExtIn {            // one side of one record (40 B); side 2r is the left, 2r + 1 the right side of record r
+  uint64_t t_woff, q_woff;   // first 2-bit word of the target / query read in the store
+  uint32_t t0, m;            // T' = stored target bases [t0, t0 + m), read downwards and complemented when trev
+  uint32_t q0, n;            // Q' = stored query bases [q0, q0 + n), read downwards and complemented when qrev
+  uint32_t trev, qrev;
+};
+
+struct ExtOut {           // (32 B)
+  int32_t score;             // H of the best cell; 0 with i = j = 0: no extension
+  uint32_t i, j;             // bases of Q' / T' the extension takes
+  uint32_t d_stop;           // the last anti-diagonal computed
+  uint32_t pad[4];
+};
+
+void launch_extend(const uint64_t* d_words, const ExtIn* d_in, ExtOut* d_out, uint32_t zdrop, uint32_t n_sides, hipStream_t st);
 
 }  // namespace herro

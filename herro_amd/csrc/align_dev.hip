@@ -271,7 +271,111 @@ __global__ __launch_bounds__(64) void k_align(const uint64_t* __restrict__ words
   }
 }
 
+// ---- k_extend: ends-free extension of one end of an overlap (tests/extend_ref.py) -----------------------------
+// One wave64 per (record, side).  The sweep is k_align's — the same registers, DPP neighbour reads, band decision and shifts,
+// the same cell() (its traceback nibble is dropped) — over Q' x T', the bases behind (in front of) the aligned span read away
+// from it.  Nothing is written per diagonal: no traceback rows, no LDS, no scratch.  Every lane keeps the best (H, d, i) of its
+// own cells; a cell counts when 1 <= i <= n and 1 <= j <= m (cells past n or m hold finite garbage, k_align never masks them)
+// and replaces the lane's best only when strictly greater — the best starts at 0, so a cell that wins is finite.  Per lane the
+// lower cell is looked at first and diagonals come in order, so the lane holds the earliest diagonal and the smallest i of its
+// maximum; the wave's result is max H, then min d, then min i over the lanes.
+// Stop rule: after every diagonal with d % 16 == 0, stop when max(M_d, M_{d-1}) < best - zdrop, M_d the maximum over the band's
+// in-matrix cells of diagonal d (0 <= i <= n, 0 <= j <= m; -inf cells are below FINITE and lose to every finite threshold).
+// The lane maxima of diagonals 15 and 0 (mod 16) are the only ones taken, and the wave is reduced once per 16 diagonals.
+__device__ __forceinline__ int32_t wave_max(int32_t v) {
+  const int32_t ident = INT32_MIN;
+  v = max(v, __builtin_amdgcn_update_dpp(ident, v, 0x111, 0xf, 0xf, false));   // row_shr:1
+  v = max(v, __builtin_amdgcn_update_dpp(ident, v, 0x112, 0xf, 0xf, false));   // row_shr:2
+  v = max(v, __builtin_amdgcn_update_dpp(ident, v, 0x114, 0xf, 0xf, false));   // row_shr:4
+  v = max(v, __builtin_amdgcn_update_dpp(ident, v, 0x118, 0xf, 0xf, false));   // row_shr:8 -> lane 15 of a row holds the row
+  v = max(v, __builtin_amdgcn_update_dpp(ident, v, 0x142, 0xa, 0xf, false));   // row_bcast:15 into rows 1 and 3
+  v = max(v, __builtin_amdgcn_update_dpp(ident, v, 0x143, 0xc, 0xf, false));   // row_bcast:31 into rows 2 and 3
+  return __builtin_amdgcn_readlane(v, 63);
+}
+
+__global__ __launch_bounds__(64) void k_extend(const uint64_t* __restrict__ words, const ExtIn* __restrict__ in,
+                                               ExtOut* __restrict__ out, uint32_t zdrop) {
+  const uint32_t r = blockIdx.x;
+  const int L = (int)threadIdx.x;
+  const ExtIn a = in[r];
+  const int32_t n = (int32_t)a.n, m = (int32_t)a.m, D = n + m;
+  int32_t bh = 0, bd = 0, bi = 0;   // this lane's best cell
+  int32_t d_stop = 0;
+  if (n > 0 && m > 0) {             // (uniform) an empty flank: zeros
+    const Seq T{words + a.t_woff, (int32_t)a.t0, m, a.trev}, Q{words + a.q_woff, (int32_t)a.q0, n, a.qrev};
+    const int32_t zd = (int32_t)min(zdrop, 1u << 29);   // finite H > -2^24: above 2^29 nothing finite is ever below best - zdrop
+    int32_t lo = -W / 2;
+    const int k0 = 2 * L, k1 = 2 * L + 1;
+    int32_t h1a = k0 == W / 2 ? 0 : NEG, h1b = NEG, i1a = NEG, i1b = NEG, d1a = NEG, d1b = NEG, h2a = NEG, h2b = NEG;
+    uint32_t qa = Q.at(lo + k0 - 1), qb = Q.at(lo + k1 - 1);   // Q'[i - 1]
+    uint32_t ta = T.at(-lo - k0), tb = T.at(-lo - k1);         // T'[j - 1] on d = 1
+    int32_t mprev = NEG;
+    for (int32_t d = 1; d <= D; ++d) {
+      const uint32_t q_in = Q.at(lo + W - 1);   // enters at the top if the band moves
+      const uint32_t t_in = T.at(d - lo);       // enters at the bottom if it does not
+      const int32_t h1m = from_below(h1b, NEG), i1m = from_below(i1b, NEG), h2m = from_below(h2b, NEG);
+      int32_t Ia, Da, Ib, Db;
+      uint32_t na, nb;
+      const int32_t Ha = cell(h1m, i1m, h1a, d1a, h2m, qa, ta, Ia, Da, na);
+      const int32_t Hb = cell(h1a, i1a, h1b, d1b, h2a, qb, tb, Ib, Db, nb);
+      d_stop = d;
+      // candidates of this diagonal: max(1, d - m) <= i <= min(n, d - 1)
+      const int32_t c_lo = max(1, d - m);
+      const uint32_t c_cnt = (uint32_t)max(min(n, d - 1) - c_lo + 1, 0);
+      const uint32_t ca = (uint32_t)(lo + k0 - c_lo);
+      if (ca < c_cnt && Ha > bh) { bh = Ha; bd = d; bi = lo + k0; }
+      if (ca + 1u < c_cnt && Hb > bh) { bh = Hb; bd = d; bi = lo + k1; }
+      const int32_t ph = d & 15;
+      if (ph == 15 || ph == 0) {   // (uniform) the in-matrix cells of this diagonal: max(0, d - m) <= i <= min(n, d)
+        const int32_t m_lo = max(0, d - m);
+        const uint32_t m_cnt = (uint32_t)(min(n, d) - m_lo + 1);
+        const uint32_t ma = (uint32_t)(lo + k0 - m_lo);
+        const int32_t mx = max(ma < m_cnt ? Ha : NEG, ma + 1u < m_cnt ? Hb : NEG);
+        if (ph == 15) {
+          mprev = mx;
+        } else if (wave_max(max(mx, mprev)) < wave_max(bh) - zd) {
+          break;
+        }
+      }
+      if (d == D) break;
+      const int32_t top = __builtin_amdgcn_readlane(Hb, 63), bot = __builtin_amdgcn_readlane(Ha, 0);
+      const int32_t it = lo + W - 1, jt = d - it, ib = lo, jb = d - lo;
+      const int32_t vt = (it >= 0 && it <= n && jt >= 0 && jt <= m && top >= FINITE) ? top : NEG;
+      const int32_t vb = (ib >= 0 && ib <= n && jb >= 0 && jb <= m && bot >= FINITE) ? bot : NEG;
+      if (vt > vb) {   // lo_{d+1} = lo_d + 1: every array moves down one cell
+        h2a = h1b; h2b = from_above(h1a, NEG);
+        h1a = Hb; h1b = from_above(Ha, NEG);
+        i1a = Ib; i1b = from_above(Ia, NEG);
+        d1a = Db; d1b = from_above(Da, NEG);
+        const uint32_t qn = (uint32_t)from_above((int32_t)qa, (int32_t)q_in);
+        qa = qb; qb = qn;
+        ++lo;
+      } else {         // lo_{d+1} = lo_d: the target codes move up one cell
+        h2a = h1a; h2b = h1b;
+        h1a = Ha; h1b = Hb;
+        i1a = Ia; i1b = Ib;
+        d1a = Da; d1b = Db;
+        const uint32_t tn = (uint32_t)from_below((int32_t)tb, (int32_t)t_in);
+        tb = ta; ta = tn;
+      }
+    }
+  }
+  // max H, then the earliest diagonal, then the smallest i (every lane starts from (0, 0, 0): no extension)
+  const int32_t best = wave_max(bh);
+  const int32_t dsel = -wave_max(bh == best ? -bd : INT32_MIN);
+  const int32_t isel = -wave_max(bh == best && bd == dsel ? -bi : INT32_MIN);
+  if (L == 0) {
+    ExtOut o{best, (uint32_t)isel, (uint32_t)(dsel - isel), (uint32_t)d_stop, {0u, 0u, 0u, 0u}};
+    out[r] = o;
+  }
+}
+
 }  // namespace
+
+void launch_extend(const uint64_t* d_words, const ExtIn* d_in, ExtOut* d_out, uint32_t zdrop, uint32_t n_sides, hipStream_t st) {
+  if (n_sides == 0) return;
+  hipLaunchKernelGGL(k_extend, dim3(n_sides), dim3(64), 0, st, d_words, d_in, d_out, zdrop);
+}
 
 void launch_align(const uint64_t* d_words, const AlignIn* d_in, AlignOut* d_out, uint8_t* d_scr, uint32_t* d_dense,
                   uint32_t* d_count, uint32_t n_rec, hipStream_t st) {

@@ -3355,9 +3355,9 @@ void apply_trim(herro_alignment& a, const herro::AlignOut& o) {
 // Validation, chunking (HERRO_ALIGN_SCRATCH_MB) and the kernel runs of herro_align_overlaps and herro_align_overlaps_dev.  Behind every chunk the host
 // reads its op total and its AlignOut records and hands the chunk's dense ops, still on the device, to take(total, d_dense, r_done, at): it stores them and
 // says where (at: the chunk's first op in the caller's store; r_done: records aligned so far, this chunk's included).  ops_at[r]: record r's first op there.
-template <class Take>
-int align_chunks(herro_ctx* ctx, uint32_t n, const herro_alignment* in, std::vector<herro::AlignOut>& res, std::vector<uint64_t>& ops_at, Take take) {
-  if (ctx->host_only) { ctx->err = "herro_align_overlaps: the context has no device"; return HERRO_E_NO_DEVICE; }
+// What herro_align_overlaps[_dev] and herro_extend_overlaps (`who`) ask of a context and of coordinate-only records before anything runs.
+int check_records(herro_ctx* ctx, const char* who, uint32_t n, const herro_alignment* in) {
+  if (ctx->host_only) { ctx->err = std::string(who) + ": the context has no device"; return HERRO_E_NO_DEVICE; }
   if (!ctx->d_words) { ctx->err = "herro_set_reads must be called first"; return HERRO_E_STATE; }
   for (uint32_t r = 0; r < n; r++) {
     const herro_alignment& a = in[r];
@@ -3368,10 +3368,16 @@ int align_chunks(herro_ctx* ctx, uint32_t n, const herro_alignment* in, std::vec
     else if (a.strand > 1) why = "strand must be 0 or 1";
     else if ((uint64_t)(a.qend - a.qstart) + (a.tend - a.tstart) > herro::ALIGN_MAX_CELLS) why = "overlap longer than 2^25 bases in all";
     if (!why.empty()) {
-      ctx->err = "herro_align_overlaps: record " + std::to_string(r) + ": " + why;
+      ctx->err = std::string(who) + ": record " + std::to_string(r) + ": " + why;
       return HERRO_E_INVALID;
     }
   }
+  return HERRO_OK;
+}
+
+template <class Take>
+int align_chunks(herro_ctx* ctx, uint32_t n, const herro_alignment* in, std::vector<herro::AlignOut>& res, std::vector<uint64_t>& ops_at, Take take) {
+  if (const int rc = check_records(ctx, "herro_align_overlaps", n, in)) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   uint64_t budget = 4096ull << 20;
   if (const char* e = getenv("HERRO_ALIGN_SCRATCH_MB")) budget = (uint64_t)std::max(1ll, atoll(e)) << 20;
@@ -3482,6 +3488,89 @@ const herro_alignment* herro_aligned_alignments(const herro_aligned* a) { return
 const int32_t* herro_aligned_scores(const herro_aligned* a) { return a ? a->scores.data() : nullptr; }
 uint32_t herro_aligned_failed(const herro_aligned* a) { return a ? a->failed : 0; }
 void herro_aligned_free(herro_aligned* a) { delete a; }
+
+// ---- extension of coordinate-only overlaps to the read ends (k_extend in align_dev.hip) ----------------------------------------
+// Two sides per record, one wave each; the host turns the four flank lengths into coordinates.  Records go through in slices of 2^20, so the side
+// descriptors and results (72 B per side) stay small whatever n is.
+struct herro_extended {
+  std::vector<herro_alignment> alns;   // extended coordinates; cigar = NULL, cigar_len = 0
+  std::vector<uint32_t> ext;           // [n][4]: t_left, q_left, t_right, q_right
+  std::vector<int32_t> scores;         // [n][2]: left, right
+};
+
+int herro_extend_overlaps(herro_ctx* ctx, uint32_t n, const herro_alignment* in, const herro_extend_params* params, herro_extended** out) {
+  if (!ctx || !out || (n && !in)) return HERRO_E_INVALID;
+  *out = nullptr;
+  const uint32_t zdrop = params && params->zdrop ? params->zdrop : herro::EXTEND_ZDROP;
+  const uint32_t max_ext = params && params->max_ext ? params->max_ext : herro::EXTEND_MAX_EXT;
+  if (max_ext > herro::EXTEND_MAX_EXT_LIMIT) { ctx->err = "herro_extend_overlaps: max_ext must be at most 2^20"; return HERRO_E_INVALID; }
+  if (const int rc = check_records(ctx, "herro_extend_overlaps", n, in)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::unique_ptr<herro_extended> h(new herro_extended());
+  h->alns.assign(in, in + n);
+  h->ext.assign((size_t)n * 4, 0);
+  h->scores.assign((size_t)n * 2, 0);
+  constexpr uint32_t SLICE = 1u << 20;
+  const uint32_t cap = std::min(n, SLICE);
+  std::vector<herro::ExtIn> sides((size_t)cap * 2);
+  std::vector<herro::ExtOut> res((size_t)cap * 2);
+  herro::ExtIn* d_in = nullptr;
+  herro::ExtOut* d_out = nullptr;
+  auto hip_fail = [&](hipError_t e, const char* what) {
+    ctx->err = std::string("herro_extend_overlaps: ") + what + ": " + hipGetErrorString(e);
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    return HERRO_E_NO_DEVICE;
+  };
+  hipError_t e = hipSuccess;
+  if (n) {
+    if ((e = hipMalloc((void**)&d_in, sizeof(herro::ExtIn) * sides.size())) != hipSuccess) return hip_fail(e, "sides");
+    if ((e = hipMalloc((void**)&d_out, sizeof(herro::ExtOut) * res.size())) != hipSuccess) return hip_fail(e, "results");
+  }
+  for (uint32_t r0 = 0; r0 < n; r0 += SLICE) {
+    const uint32_t cnt = std::min(SLICE, n - r0);
+    for (uint32_t x = 0; x < cnt; x++) {
+      const herro_alignment& a = in[r0 + x];
+      const uint64_t tw = ctx->h_word_off[a.tid], qw = ctx->h_word_off[a.qid];
+      const uint32_t t_below = a.tstart, t_above = ctx->read_len[a.tid] - a.tend;
+      const uint32_t q_below = a.qstart, q_above = ctx->read_len[a.qid] - a.qend;
+      // left: the target below tstart read downwards; the oriented query in front of the span read backwards — the forward bases below qstart read
+      // downwards (strand 0) or those from qend upwards (strand 1), complemented like the target's (T rev = 1, Q rev = !strand: the same equalities)
+      const uint32_t ml = std::min(t_below, max_ext), nl = std::min(a.strand ? q_above : q_below, max_ext);
+      sides[2 * x] = herro::ExtIn{tw, qw, a.tstart - ml, ml, a.strand ? a.qend : a.qstart - nl, nl, 1u, a.strand ? 0u : 1u};
+      // right: the target from tend upwards; the oriented query behind the span
+      const uint32_t mr = std::min(t_above, max_ext), nr = std::min(a.strand ? q_below : q_above, max_ext);
+      sides[2 * x + 1] = herro::ExtIn{tw, qw, a.tend, mr, a.strand ? a.qstart - nr : a.qend, nr, 0u, a.strand};
+    }
+    if ((e = hipMemcpyAsync(d_in, sides.data(), sizeof(herro::ExtIn) * 2 * cnt, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) return hip_fail(e, "side upload");
+    herro::launch_extend(ctx->d_words, d_in, d_out, zdrop, 2 * cnt, ctx->stream);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_extend launch");
+    if ((e = hipMemcpyAsync(res.data(), d_out, sizeof(herro::ExtOut) * 2 * cnt, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) return hip_fail(e, "results");
+    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return hip_fail(e, "k_extend");
+    for (uint32_t x = 0; x < cnt; x++) {
+      herro_alignment& a = h->alns[r0 + x];
+      const herro::ExtOut &l = res[2 * x], &r = res[2 * x + 1];
+      a.cigar = nullptr; a.cigar_len = 0;
+      a.tstart -= l.j; a.tend += r.j;
+      if (a.strand == 0) { a.qstart -= l.i; a.qend += r.i; }
+      else { a.qend += l.i; a.qstart -= r.i; }
+      uint32_t* ex = &h->ext[(size_t)(r0 + x) * 4];
+      ex[0] = l.j; ex[1] = l.i; ex[2] = r.j; ex[3] = r.i;
+      h->scores[(size_t)(r0 + x) * 2] = l.score;
+      h->scores[(size_t)(r0 + x) * 2 + 1] = r.score;
+    }
+  }
+  if (d_in) (void)hipFree(d_in);
+  if (d_out) (void)hipFree(d_out);
+  *out = h.release();
+  return HERRO_OK;
+}
+
+uint32_t herro_extended_n(const herro_extended* x) { return x ? (uint32_t)x->alns.size() : 0; }
+const herro_alignment* herro_extended_alignments(const herro_extended* x) { return x ? x->alns.data() : nullptr; }
+const uint32_t* herro_extended_ext(const herro_extended* x) { return x ? x->ext.data() : nullptr; }
+const int32_t* herro_extended_scores(const herro_extended* x) { return x ? x->scores.data() : nullptr; }
+void herro_extended_free(herro_extended* x) { delete x; }
 
 // ---- device-resident hand-off: the aligner's ops stay where k_align wrote them, the job builder reads them there ----------------
 int herro_align_overlaps_dev(herro_ctx* ctx, uint32_t n, const herro_alignment* in, herro_aligned_dev** out) {

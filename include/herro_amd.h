@@ -404,6 +404,34 @@ void herro_aligned_dev_free(herro_aligned_dev* a);
 herro_job* herro_job_create_aligned(herro_ctx* ctx, uint32_t n_targets, const uint32_t* rids, const uint64_t* aln_off,
                                     const uint32_t* rec, const herro_aligned_dev* a, uint32_t window_size);
 
+/* ---- extension of overlaps to the read ends (k_extend, csrc/align_dev.hip) ------------------------------------------------------
+ * The third piece of what `minimap2 -cx ava-ont` does for `herro inference` (mm2.rs:15-30) next to seeding / chaining
+ * (herro_find_overlaps) and base-level alignment (herro_align_overlaps): a chain's anchor span stops short of where the reads stop
+ * agreeing, and the reference's windowing only takes whole windows from an overlap, so a few missing bases cost a window of
+ * coverage.  Every record is extended at both ends, each side on its own: the aligner's recurrence, scores and band (+2 / -4, gaps
+ * 4 + 2k, HERRO_ALIGN_BAND cells per anti-diagonal) swept ends-free over the bases beyond the span — at most max_ext of either read —
+ * ending at the best-scoring cell (the earliest anti-diagonal, then the smallest query length, among equals), which is always a
+ * matching pair; the sweep stops once the two latest anti-diagonals lie more than zdrop (minimap2's -z) below the best, looked at
+ * every 16 anti-diagonals.  The exact specification is DESIGN.md section 11 and tests/extend_ref.py, which the kernel equals bit for
+ * bit.  What this is not: minimap2's extension — no end bonus (a span that stops a few bases short of a read end on an error is
+ * not pulled to the end), no two-piece gaps.  The two records of a pair are extended independently and need not mirror each other.
+ * Parameters: a 0 field means its default — zdrop 400, max_ext 2048; max_ext above 2^20 is HERRO_E_INVALID (checked before anything
+ * else).  Validation, codes and messages otherwise as herro_align_overlaps: HERRO_E_STATE without reads, HERRO_E_INVALID naming the
+ * record, HERRO_E_NO_DEVICE on a context without a device.  Runs on the context's execution stream and returns when done; no
+ * scratch memory. */
+typedef struct { uint32_t zdrop, max_ext, reserved[2]; } herro_extend_params;
+typedef struct herro_extended herro_extended;
+int herro_extend_overlaps(herro_ctx* ctx, uint32_t n, const herro_alignment* in, const herro_extend_params* params /* NULL: defaults */,
+                          herro_extended** out);
+uint32_t herro_extended_n(const herro_extended* x);
+/* n records in input order with the extended coordinates, cigar = NULL, cigar_len = 0: ready for herro_align_overlaps[_dev]. */
+const herro_alignment* herro_extended_alignments(const herro_extended* x);
+/* uint32 [n][4]: bases gained as t_left, q_left, t_right, q_right; the q lengths on the oriented query (strand 1: q_left is added
+ * to qend, q_right taken from qstart). */
+const uint32_t* herro_extended_ext(const herro_extended* x);
+const int32_t* herro_extended_scores(const herro_extended* x);   /* int32 [n][2]: the left and the right side's score */
+void herro_extended_free(herro_extended* x);
+
 /* ---- overlap finding on the device (csrc/overlap_dev.hip) ------------------------------------------------------------------------
  * Stands in for the seeding and chaining half of the `minimap2 -x ava-ont` run `herro inference` starts itself without --read-alns
  * (AlnMode::None, overlaps.rs:340-344 -> generate_batches -> call_mm2, mm2.rs:15-30): which reads of the context's store overlap,
@@ -412,7 +440,8 @@ herro_job* herro_job_create_aligned(herro_ctx* ctx, uint32_t n_targets, const ui
  * minimizers under minimap2's hash64 with every tied window minimum selected; hashes with more than max_occ occurrences in the
  * store dropped; anchors between every two occurrences in different reads; per (t, q, strand) a chain over the 64 nearest
  * predecessors (gaps <= max_gap, diagonal drift <= bandwidth, minimap2's one-piece gap cost); kept with score >= min_score and
- * >= min_anchors anchors.  Coordinates are the anchor span of the chain: there is no extension to the read ends.  One overlap per
+ * >= min_anchors anchors.  Coordinates are the anchor span of the chain: the finder itself does not extend it to the read ends —
+ * herro_extend_overlaps (above) does, as a step of its own between this call and herro_align_overlaps.  One overlap per
  * read pair (overlaps.rs:181-185; the better strand, forward on a tie), no self overlaps (overlaps.rs:175-179), and every pair
  * yields two records, (t, q) and (q, t) — minimap2's --dual=yes.  Records come grouped by target in ascending read id, each
  * target's records in ascending qid, with cigar = NULL and cigar_len = 0: the shape herro_paf_parse_coords produces, so they go into
