@@ -97,6 +97,9 @@ __global__ __launch_bounds__(64) void k_align(const uint64_t* __restrict__ words
   // decision cells lie outside the matrix)
   int32_t h1a = k0 == W / 2 ? 0 : NEG, h1b = NEG, i1a = NEG, i1b = NEG, d1a = NEG, d1b = NEG, h2a = NEG, h2b = NEG;
   if (L == 0) lo_arr[0] = lo;
+  // (uniform) what lane 0 reads below the band's bottom cell: H / I of d - 1 and H of d - 2 at i = lo - 1.  That cell lay in the band of
+  // its own diagonal if the band has moved since (it was the bottom cell then), and is outside it (-inf) otherwise.
+  int32_t h1f = NEG, i1f = NEG, h2f = NEG;
   uint32_t qa = Q.at(lo + k0 - 1), qb = Q.at(lo + k1 - 1);   // Q[i - 1]
   uint32_t ta = T.at(-lo - k0), tb = T.at(-lo - k1);         // T[j - 1] on d = 1
   int32_t hend = NEG;
@@ -104,7 +107,7 @@ __global__ __launch_bounds__(64) void k_align(const uint64_t* __restrict__ words
   for (int32_t d = 1; d <= D; ++d) {
     const uint32_t q_in = Q.at(lo + W - 1);   // enters at the top if the band moves
     const uint32_t t_in = T.at(d - lo);       // enters at the bottom if it does not
-    const int32_t h1m = from_below(h1b, NEG), i1m = from_below(i1b, NEG), h2m = from_below(h2b, NEG);
+    const int32_t h1m = from_below(h1b, h1f), i1m = from_below(i1b, i1f), h2m = from_below(h2b, h2f);
     int32_t Ia, Da, Ib, Db;
     uint32_t na, nb;
     const int32_t Ha = cell(h1m, i1m, h1a, d1a, h2m, qa, ta, Ia, Da, na);
@@ -123,6 +126,7 @@ __global__ __launch_bounds__(64) void k_align(const uint64_t* __restrict__ words
     const int32_t vt = (it >= 0 && it <= n && jt >= 0 && jt <= m && top >= FINITE) ? top : NEG;
     const int32_t vb = (ib >= 0 && ib <= n && jb >= 0 && jb <= m && bot >= FINITE) ? bot : NEG;
     if (vt > vb) {   // lo_{d+1} = lo_d + 1: every array moves down one cell
+      h2f = __builtin_amdgcn_readlane(h1a, 0); h1f = bot; i1f = __builtin_amdgcn_readlane(Ia, 0);
       h2a = h1b; h2b = from_above(h1a, NEG);
       h1a = Hb; h1b = from_above(Ha, NEG);
       i1a = Ib; i1b = from_above(Ia, NEG);
@@ -131,6 +135,7 @@ __global__ __launch_bounds__(64) void k_align(const uint64_t* __restrict__ words
       qa = qb; qb = qn;
       ++lo;
     } else {         // lo_{d+1} = lo_d: the target codes move up one cell
+      h2f = h1f; h1f = NEG; i1f = NEG;
       h2a = h1a; h2b = h1b;
       h1a = Ha; h1b = Hb;
       i1a = Ia; i1b = Ib;
@@ -307,13 +312,14 @@ __global__ __launch_bounds__(64) void k_extend(const uint64_t* __restrict__ word
     int32_t lo = -W / 2;
     const int k0 = 2 * L, k1 = 2 * L + 1;
     int32_t h1a = k0 == W / 2 ? 0 : NEG, h1b = NEG, i1a = NEG, i1b = NEG, d1a = NEG, d1b = NEG, h2a = NEG, h2b = NEG;
+    int32_t h1f = NEG, i1f = NEG, h2f = NEG;   // (uniform) below the band's bottom cell, as in k_align
     uint32_t qa = Q.at(lo + k0 - 1), qb = Q.at(lo + k1 - 1);   // Q'[i - 1]
     uint32_t ta = T.at(-lo - k0), tb = T.at(-lo - k1);         // T'[j - 1] on d = 1
     int32_t mprev = NEG;
     for (int32_t d = 1; d <= D; ++d) {
       const uint32_t q_in = Q.at(lo + W - 1);   // enters at the top if the band moves
       const uint32_t t_in = T.at(d - lo);       // enters at the bottom if it does not
-      const int32_t h1m = from_below(h1b, NEG), i1m = from_below(i1b, NEG), h2m = from_below(h2b, NEG);
+      const int32_t h1m = from_below(h1b, h1f), i1m = from_below(i1b, i1f), h2m = from_below(h2b, h2f);
       int32_t Ia, Da, Ib, Db;
       uint32_t na, nb;
       const int32_t Ha = cell(h1m, i1m, h1a, d1a, h2m, qa, ta, Ia, Da, na);
@@ -343,6 +349,7 @@ __global__ __launch_bounds__(64) void k_extend(const uint64_t* __restrict__ word
       const int32_t vt = (it >= 0 && it <= n && jt >= 0 && jt <= m && top >= FINITE) ? top : NEG;
       const int32_t vb = (ib >= 0 && ib <= n && jb >= 0 && jb <= m && bot >= FINITE) ? bot : NEG;
       if (vt > vb) {   // lo_{d+1} = lo_d + 1: every array moves down one cell
+        h2f = __builtin_amdgcn_readlane(h1a, 0); h1f = bot; i1f = __builtin_amdgcn_readlane(Ia, 0);
         h2a = h1b; h2b = from_above(h1a, NEG);
         h1a = Hb; h1b = from_above(Ha, NEG);
         i1a = Ib; i1b = from_above(Ia, NEG);
@@ -351,6 +358,7 @@ __global__ __launch_bounds__(64) void k_extend(const uint64_t* __restrict__ word
         qa = qb; qb = qn;
         ++lo;
       } else {         // lo_{d+1} = lo_d: the target codes move up one cell
+        h2f = h1f; h1f = NEG; i1f = NEG;
         h2a = h1a; h2b = h1b;
         h1a = Ha; h1b = Hb;
         i1a = Ia; i1b = Ib;

@@ -18,6 +18,9 @@ NEG = -(1 << 30)
 FIN = -(1 << 29)
 MATCH, MISMATCH, GAP_OPEN, GAP_EXT = 2, -4, 4, 2
 M_, I_, D_ = 0, 1, 2
+# A test hook, never set by the specification: True makes the band's bottom cell (k = 0) read -inf above it and diagonally below it,
+# as k_align and k_extend once did after the band had moved.  tests/extend_ref.py reads it too.
+BOTTOM_CELL_FORGETS = False
 LETTER = "MID"
 
 
@@ -108,6 +111,8 @@ def _band_group(Ts, Qs):
         lfH = take(H1, i - lo1[:, None])
         lfD = take(D1, i - lo1[:, None])
         dgH = take(H2, i - 1 - lo2[:, None])
+        if BOTTOM_CELL_FORGETS:
+            upH[:, 0] = NEG; upI[:, 0] = NEG; dgH[:, 0] = NEG
         io, ie = _norm(upH - GAP_OPEN - GAP_EXT), _norm(upI - GAP_EXT)
         dop, de = _norm(lfH - GAP_OPEN - GAP_EXT), _norm(lfD - GAP_EXT)
         Iv = np.maximum(io, ie)

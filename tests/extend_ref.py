@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import numpy as np
 
+import align_ref
 from align_ref import FIN, GAP_EXT, GAP_OPEN, MATCH, MISMATCH, NEG, W, store_codes  # noqa: F401  (store_codes: re-exported)
 
 ZDROP = 400          # zdrop = 0
@@ -103,6 +104,8 @@ def _ext_group(Ts, Qs, zdrop: int):
         lfH = take(H1, i - lo1[:, None])
         lfD = take(D1, i - lo1[:, None])
         dgH = take(H2, i - 1 - lo2[:, None])
+        if align_ref.BOTTOM_CELL_FORGETS:
+            upH[:, 0] = NEG; upI[:, 0] = NEG; dgH[:, 0] = NEG
         Iv = np.maximum(_norm(upH - GAP_OPEN - GAP_EXT), _norm(upI - GAP_EXT))
         Dv = np.maximum(_norm(lfH - GAP_OPEN - GAP_EXT), _norm(lfD - GAP_EXT))
         qc = Qp[rr, np.clip(i - 1 + P, 0, Qp.shape[1] - 1)]
