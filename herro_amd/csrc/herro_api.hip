@@ -3123,6 +3123,19 @@ int64_t herro_debug_job_rf(herro_job* job, uint32_t w, uint8_t* out, uint64_t ca
   return (int64_t)n;
 }
 
+// the directory words k_cols wrote for overlap-window `ow` (JobDev::cwd: one per word of 32 window positions; read-only, valid once herro_job_featurize
+// has run, and meaningful for a slice the long-indel filter kept — a dropped slice's words are never written)
+int64_t herro_debug_job_cwd(herro_job* job, uint32_t ow, uint32_t* out, uint64_t cap) {
+  if (!job || !out) return HERRO_E_INVALID;
+  herro_ctx* ctx = job->ctx;
+  if (ctx->host_only || !job->featurized) { ctx->err = "herro_job_featurize has not run"; return HERRO_E_STATE; }
+  if (ow >= job->J.n_ow || cap < job->J.nw) { ctx->err = "overlap-window index out of range or output buffer too small"; return HERRO_E_INVALID; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipMemcpy(out, job->J.cwd + (uint64_t)ow * job->J.nw, (size_t)job->J.nw * 4, hipMemcpyDeviceToHost));
+  return (int64_t)job->J.nw;
+}
+
 // the base logits of every informative row of the job (job order, n_rows x 5) replace the model's, on the device and in the host copy; the consensus
 // is dropped, so the next herro_job_consensus / herro_job_consensus_fasta decodes these (tests plant ties, infinities and NaNs for the argmax)
 int herro_debug_job_set_base_logits(herro_job* job, const float* base, uint64_t n_rows) {

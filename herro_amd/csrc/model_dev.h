@@ -117,7 +117,7 @@ struct __attribute__((aligned(16))) TokMeta {
   uint64_t plane_off;  // byte offset of the window's token / quality planes
   uint32_t plane_ld;   // plane stride
   uint32_t tok_row;    // row of the token inside the window
-  uint32_t len, lmax;  // L' of the window, max L' of its batch (both < 65536)
+  uint32_t len, lmax;  // L' of the window, max L' of its batch (up to 8192 x 51 rows)
   uint32_t rf_idx;     // job-level index of the token (slot of its receptive-field qualities in BatchDev::rf_q)
   uint32_t pad1;
 };
@@ -128,8 +128,8 @@ struct __attribute__((aligned(16))) TokMeta {
 // [0, lmax).  Rows 0..3 in the 32-bit words, row 4 in the packed bytes.
 struct __attribute__((aligned(16))) TokCv {
   uint64_t plane_off;
-  uint32_t ld_d1;      // plane stride | default token of row 4 << 16 | default quality of row 4 << 24
-  uint32_t row_ok;     // tok_row | validity of conv1 positions tok_row - 1 .. + 1 (inside [0, lmax)) << 16 | mask of row 4 << 24
+  uint32_t ld_d1;      // default token of row 4 << 16 | default quality of row 4 << 24 (the low half is free: the plane stride it held does not fit 16 bits — a window has up to 417 792 rows)
+  uint32_t row_ok;     // validity of conv1 positions tok_row - 1 .. + 1 (inside [0, lmax)) << 16 | mask of row 4 << 24 (the row itself: TokMeta::tok_row)
   uint32_t rf_idx;
   uint32_t mk0, dt0, dq0;
 };

@@ -245,7 +245,10 @@ __global__ __launch_bounds__(CM_NT, WPS) void k_conv_m(ModelDev M, BatchDev B, M
       for (int i = 0; i < 5; i++) { r.t[i] = 0; r.q[i] = 0; }
       return r;
     } else {
-    const uint32_t ld = tm.ld_d1 & 0xffffu, trow = tm.row_ok & 0xffffu;
+    // the plane stride and the token's row come from the token's full record: a window has up to 8192 x 51 = 417 792 rows, and until they were taken out of
+    // TokCv's packed words a stride or row of 2^16 spilled into the default token of row 4 and the validity bits (only this branch ever read them)
+    const TokMeta tf = S.tok_meta[min(m, n_rows - 1u) / HERRO_ROWS];
+    const uint32_t ld = tf.plane_ld, trow = tf.tok_row;
     const uint8_t* pb = B.planes_b + tm.plane_off + (uint64_t)rr * ld;
     r.rf = make_uint4(0, 0, 0, 0);
     const uint8_t* pq = B.planes_q + tm.plane_off + (uint64_t)rr * ld;
@@ -1329,8 +1332,8 @@ __global__ void k_build_tokens_h(BatchDev B, ModelScratch S) {
     }
     TokCv cv;
     cv.plane_off = tm.plane_off;
-    cv.ld_d1 = tm.plane_ld | (dt[1] << 16) | (dq[1] << 24);
-    cv.row_ok = row | (ok << 16) | (mk[1] << 24);
+    cv.ld_d1 = (dt[1] << 16) | (dq[1] << 24);
+    cv.row_ok = (ok << 16) | (mk[1] << 24);
     cv.rf_idx = tm.rf_idx;
     cv.mk0 = mk[0]; cv.dt0 = dt[0]; cv.dq0 = dq[0];
     S.tok_cv[n] = cv;

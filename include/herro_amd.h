@@ -278,7 +278,11 @@ int herro_debug_job_dev_built(const herro_job* job);
 int herro_debug_base_row_votes(const uint8_t* counts, const uint8_t* split, const uint8_t* target, uint32_t n, uint8_t* sup, uint8_t* vote);
 uint32_t herro_debug_vote5(const uint32_t* c5, uint32_t tb);
 int64_t herro_debug_job_rf(herro_job* job, uint32_t w, uint8_t* out, uint64_t cap);
-int herro_debug_job_rf_fused(const herro_job* job);   /* 1: the last herro_job_infer read records k_rows gathered itself; 0: k_rfq's */
+/* The directory words of overlap-window `ow` (job order, herro_debug_job_array which = 1) as the featurize pass wrote them: one u32 per 32 window
+ * positions, query index | insertion events in front << 20, 0xffffffff where either does not fit its field (csrc/job_dev.h, JobDev::cwd).  Read-only;
+ * valid after herro_job_featurize for a slice the long-indel filter kept.  Returns the number of words (ceil(window_size / 32); <0: error). */
+int64_t herro_debug_job_cwd(herro_job* job, uint32_t ow, uint32_t* out, uint64_t cap);
+int herro_debug_job_rf_fused(const herro_job* job);  /* 1: the last herro_job_infer read records k_rows gathered itself; 0: k_rfq's */
 int herro_debug_job_rf_left(const herro_job* job);    /* ... of which this many windows (above the 256 informative rows k_rows stages) were filled by k_rfq behind it, the others staying fused */
 uint32_t herro_debug_e4m3(float x);                   /* host f32 -> OCP e4m3 (round to nearest even, saturating) as used for the precision-6 weight copies */
 int herro_debug_sib_fault(herro_ctx* ctx);            /* raises the context's sibling-tile error word as a tile that timed out would: the next fetch repeats its job's model pass without sibling tiles */

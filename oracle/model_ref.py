@@ -120,7 +120,10 @@ class HerroNet(nn.Module):
     # conv = kw shifted matmuls over a zero-padded window axis, BatchNorm(eval) applied as its affine map,
     # the per-position linear evaluated on the gathered rows only (a row-wise op commutes with the gather).
     @torch.no_grad()
-    def forward_gemm(self, bases, quals, lens, indices, win_chunk: int = 8):
+    def forward_gemm(self, bases, quals, lens, indices, win_chunk: int = 8, positions=None):
+        """positions (optional, per window like indices): the row numbers the positional term is computed from, where they differ from the rows
+        gathered — a caller that cut the rows no informative row's receptive field reaches out of a long window (tests/width_cases.py
+        compact_twin_inputs) gathers at the rows' new places and keeps their positions."""
         hp = self.hp
         assert (getattr(hp, "act", 0), getattr(hp, "norm_first", 1), getattr(hp, "pe", 0), getattr(hp, "final_norm", 1), getattr(hp, "bn", 1)) == (0, 1, 0, 1, 1), \
             "forward_gemm is written for the default variant (the end-to-end test's model); forward() serves every variant"
@@ -158,7 +161,8 @@ class HerroNet(nn.Module):
             for k, i in enumerate(sel):
                 idx = indices[i].to(dev).long()
                 rows = x[k, idx].reshape(idx.shape[0], R * hp.c2)            # index = row * c2 + c, as forward()
-                ang = idx.to(torch.float32)[:, None] * self.pe_div[None, :]
+                pos = idx if positions is None else positions[i].to(dev).long()
+                ang = pos.to(torch.float32)[:, None] * self.pe_div[None, :]
                 pe = torch.zeros(idx.shape[0], D, device=dev)
                 pe[:, 0::2] = torch.sin(ang)
                 pe[:, 1::2] = torch.cos(ang)
@@ -191,18 +195,21 @@ def build(raw: dict, hp) -> HerroNet:
 
 
 def run_batch(model: HerroNet, bases_u8: np.ndarray, quals_u8: np.ndarray, lens: np.ndarray, indices_flat: np.ndarray,
-              gemm: bool = False):
+              gemm: bool = False, positions_flat: np.ndarray | None = None):
     """Drive the twin exactly like `inference` (inference.rs:147-175): raw u8 in, logits out.
-    gemm=True evaluates forward_gemm (device-aware; the model may live on the GPU)."""
+    gemm=True evaluates forward_gemm (device-aware; the model may live on the GPU); positions_flat (gemm only): see forward_gemm."""
     b = torch.from_numpy(bases_u8.astype(np.int32))
     q = normalise_quals(torch.from_numpy(quals_u8))
-    idx, o = [], 0
+    idx, pos, o = [], [], 0
     for n in lens:
         idx.append(torch.from_numpy(indices_flat[o:o + int(n)].astype(np.int32)))
+        if positions_flat is not None:
+            pos.append(torch.from_numpy(positions_flat[o:o + int(n)].astype(np.int32)))
         o += int(n)
+    assert positions_flat is None or gemm
     with torch.no_grad():
         if gemm:
-            info, base = model.forward_gemm(b, q, torch.from_numpy(lens.astype(np.int32)), idx)
+            info, base = model.forward_gemm(b, q, torch.from_numpy(lens.astype(np.int32)), idx, positions=pos if positions_flat is not None else None)
         else:
             info, base = model(b, q, torch.from_numpy(lens.astype(np.int32)), idx)
     return info.cpu().numpy(), base.cpu().numpy()

@@ -62,10 +62,8 @@ def _check_decoders(job, sb, orc, base_of_window, tag):
     return want
 
 
-def _run_lean(job):
-    """featurize + infer + the per-window results that the two paths must agree on"""
-    job.featurize()
-    job.infer(64, 1)
+def _results(job):
+    """the per-window results of a job behind herro_job_infer that the two paths must agree on (asks for no token plane)"""
     wins = []
     for w in range(job.n_windows):
         wi = job.info(w)
@@ -75,6 +73,13 @@ def _run_lean(job):
         info, base = job.logits(w)
         wins.append((wi.length, wi.n_supported, wi.n_alns, sp.tolist(), si.tolist(), info, base))
     return wins
+
+
+def _run_lean(job):
+    """featurize + infer + the per-window results"""
+    job.featurize()
+    job.infer(64, 1)
+    return _results(job)
 
 
 _TWIN = {}

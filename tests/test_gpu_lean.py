@@ -124,6 +124,23 @@ for _i, _ch in enumerate("ACGT*acgt#."):     # inference.rs BASES_MAP: the token
     TOKMAP[ord(_ch)] = _i
 
 
+def records_against_the_oracles_cells(rf, ow, tag):
+    """One window's receptive-field records [n_supported, 31, 16] against the five rows around every informative row of the oracle's window; returns the cells compared."""
+    enc = TOKMAP[ow.bases]
+    L = enc.shape[0]
+    tidx = np.flatnonzero(enc[:, 0] != 4)
+    r0 = (tidx[ow.sup_pos.astype(np.int64)] + ow.sup_ins).astype(np.int64)
+    assert rf.shape[0] == len(r0), tag
+    n_cells = 0
+    for d in range(5):
+        r = r0 - 2 + d
+        ok = (r >= 0) & (r < L)
+        assert np.array_equal(rf[ok][:, :, d], enc[r[ok]]), (tag, d, "tokens")
+        assert np.array_equal(rf[ok][:, :, 8 + d], ow.quals[r[ok]]), (tag, d, "qualities")
+        n_cells += int(ok.sum()) * 31
+    return n_cells
+
+
 @pytest.mark.parametrize("name", ["baseline_w4096", "low_coverage", "noisy_w256", "diverged_haplotypes"])
 def test_receptive_field_records_are_the_oracles_cells(name):
     """the records the model reads on the lean path (written by k_rfq behind a job on its own, by k_rows itself for a
@@ -156,19 +173,8 @@ def test_receptive_field_records_are_the_oracles_cells(name):
         res = store.extract_features(rid, rows, cigs, cs["W"])
         for wi in range(len(res)):
             ow = res.window(wi)
-            enc = TOKMAP[ow.bases]
-            L = enc.shape[0]
-            tidx = np.flatnonzero(enc[:, 0] != 4)
-            r0 = (tidx[ow.sup_pos.astype(np.int64)] + ow.sup_ins).astype(np.int64)
             for who, rr in recs.items():
-                rf = rr[w]
-                assert rf.shape[0] == len(r0), (who, t, wi)
-                for d in range(5):
-                    r = r0 - 2 + d
-                    ok = (r >= 0) & (r < L)
-                    assert np.array_equal(rf[ok][:, :, d], enc[r[ok]]), (who, t, wi, d, "tokens")
-                    assert np.array_equal(rf[ok][:, :, 8 + d], ow.quals[r[ok]]), (who, t, wi, d, "qualities")
-                    n_cells += int(ok.sum()) * 31
+                n_cells += records_against_the_oracles_cells(rr[w], ow, (who, t, wi))
             w += 1
     assert w == job.n_windows and (n_cells > 0 or name == "low_coverage")
     job.close()
