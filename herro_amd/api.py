@@ -34,7 +34,7 @@ EXPORTS = [
     "herro_reads_descs", "herro_reads_free", "herro_write_window_features", "herro_job_write_features",
     "herro_paf_parse_coords", "herro_align_overlaps", "herro_aligned_alignments", "herro_aligned_scores", "herro_aligned_failed",
     "herro_aligned_free",
-    "herro_align_overlaps_dev", "herro_aligned_dev_from_ops", "herro_aligned_dev_n", "herro_aligned_dev_alignments", "herro_aligned_dev_scores",
+    "herro_align_overlaps_dev", "herro_aligned_dev_from_ops", "herro_aligned_dev_mirror", "herro_aligned_dev_n", "herro_aligned_dev_alignments", "herro_aligned_dev_scores",
     "herro_aligned_dev_n_ops", "herro_aligned_dev_failed", "herro_aligned_dev_cigar", "herro_aligned_dev_free", "herro_job_create_aligned",
     "herro_find_overlaps", "herro_overlaps_n", "herro_overlaps_n_targets", "herro_overlaps_target_ids", "herro_overlaps_aln_off",
     "herro_overlaps_alignments", "herro_overlaps_scores", "herro_overlaps_free", "herro_debug_sketch",
@@ -184,6 +184,7 @@ def lib():
         L.herro_aligned_free.argtypes = [vp]
         L.herro_align_overlaps_dev.argtypes = [vp, u32, vp, vp]
         L.herro_aligned_dev_from_ops.argtypes = [vp, u32, vp, vp, vp, vp]
+        L.herro_aligned_dev_mirror.argtypes = [vp, vp, vp]
         for f in (L.herro_aligned_dev_n, L.herro_aligned_dev_failed):
             f.restype = u32
             f.argtypes = [vp]
@@ -890,6 +891,14 @@ class AlignedDev:
             raise HerroError(int(n), "herro_aligned_dev_cigar")
         return C.string_at(buf, n)
 
+    def mirror(self) -> "AlignedDev":
+        """herro_aligned_dev_mirror: a new handle of 2n records — record r is this handle's record r, record n + r its mirror, the
+        alignment with query and target exchanged, derived from the ops on the device instead of aligned again (pair_rows and
+        paired_job_args do the bookkeeping).  This handle may be closed afterwards."""
+        h = C.c_void_p()
+        self.ctx._chk(self._l.herro_aligned_dev_mirror(self.ctx.h, self.h, C.byref(h)))
+        return AlignedDev(self.ctx, h)
+
     def close(self):
         if getattr(self, "h", None):
             self._l.herro_aligned_dev_free(self.h)
@@ -1090,3 +1099,68 @@ def aligned_dev_job_args(rids, aln_off, ok: np.ndarray):
     ok = np.asarray(ok, bool)
     kept = np.concatenate([[0], np.cumsum(ok)]).astype(np.int64)
     return rids, kept[aln_off].astype(np.uint64), np.flatnonzero(ok).astype(np.uint32)
+
+
+def pair_rows(rows: np.ndarray, exact_ids: bool = False):
+    """Pairs the two directions of an overlap, so that one of them is aligned and the other mirrored (AlignedDev.mirror).  Row j is
+    the mate of row i iff it is exactly i's swap — query and target fields exchanged, the same strand — which is what find_overlaps
+    emits for a pair; a row whose other direction differs in any coordinate has no mate and is aligned itself.  Returns (prim,
+    rec_of_row): prim i64 — the first row of every pair and every row without a mate, in row order; rec_of_row u32 [n] — the record
+    that a mirrored handle over rows[prim] holds for row i: p for prim[p] == i, len(prim) + p for the mate of prim[p].  To be called
+    before extend_overlaps: independently extended directions are no longer exact swaps.  exact_ids: class the rows by np.unique
+    instead of by the checked hash (what a hash collision falls back to; for tests)."""
+    rows = np.ascontiguousarray(np.asarray(rows)[:, :9], np.uint32)
+    n = len(rows)
+    swapped = np.ascontiguousarray(rows[:, [5, 6, 7, 8, 4, 0, 1, 2, 3]])
+    if n == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.uint32)
+    # The two directions of an overlap share a canonical row: the smaller of the row and its swap.  `side` says which of the two a
+    # row is; a row equal to its own swap has side 0 and a class of its own kind.
+    differ = rows != swapped
+    col = differ.argmax(axis=1)
+    at = np.arange(n)
+    side = rows[at, col] > swapped[at, col]
+    own = ~differ.any(axis=1)
+    canon = np.where(side[:, None], swapped, rows)
+    # classes by a 64-bit hash of the canonical row, checked: rows that sort together must be equal, else the exact ids are taken
+    mult = np.array([0x9E3779B97F4A7C15, 0xC2B2AE3D27D4EB4F, 0x165667B19E3779F9, 0xD6E8FEB86659FD93, 0xFF51AFD7ED558CCD,
+                     0xC4CEB9FE1A85EC53, 0x2545F4914F6CDD1D, 0x94D049BB133111EB, 0xBF58476D1CE4E5B9], np.uint64)
+    with np.errstate(over="ignore"):
+        key = (canon.astype(np.uint64) * mult).sum(axis=1, dtype=np.uint64)
+        key ^= key >> np.uint64(29)
+    for exact in ((True,) if exact_ids else (False, True)):
+        if exact:
+            key = np.unique(canon.view(np.dtype((np.void, 36))).ravel(), return_inverse=True)[1].astype(np.uint64)
+        o = np.lexsort((side, key))                                       # by class, then side; stable: row order within
+        first = np.ones(n, bool)
+        first[1:] = key[o][1:] != key[o][:-1]
+        if exact or not (canon[o][1:][~first[1:]] != canon[o][:-1][~first[1:]]).any():
+            break
+    # Within a class the k-th row of one side pairs with the k-th row of the other — what taking the rows in order and giving each
+    # the oldest unpaired row of the other direction comes to; rows equal to their own swap pair up two by two.
+    start = np.maximum.accumulate(np.where(first, at, 0))
+    cls = np.cumsum(first) - 1
+    n_a = np.add.reduceat((~side[o]).astype(np.int64), np.flatnonzero(first))[cls]      # rows of side 0 in the class
+    k = at - start
+    second = np.where(own[o], (k & 1) == 1, side[o] & (k - n_a < n_a))   # (sorted position) a row that pairs with an earlier-sorted one
+    partner = np.where(own[o], at - 1, start + k - n_a)
+    x, y = o[second], o[partner[second]]
+    head, mate = np.minimum(x, y), np.maximum(x, y)
+    is_prim = np.ones(n, bool)
+    is_prim[mate] = False
+    prim = np.flatnonzero(is_prim).astype(np.int64)
+    rec = np.cumsum(is_prim) - 1
+    rec[mate] = len(prim) + rec[head]
+    return prim, rec.astype(np.uint32)
+
+
+def paired_job_args(rids, aln_off, rec_of_row, ok: np.ndarray):
+    """aligned_dev_job_args for a mirrored handle: (rids, aln_off', rec) for Context.create_job_aligned, where `ok` is the mirrored
+    handle's (2 len(prim) records) and rec_of_row is pair_rows'.  Rows whose record failed are dropped, aln_off' regroups the rest
+    over the targets (which keep their place), rec holds their handle indices in row order."""
+    rids = np.ascontiguousarray(rids, np.uint32)
+    aln_off = np.asarray(aln_off, np.int64)
+    rec_of_row = np.asarray(rec_of_row, np.int64)
+    keep = np.asarray(ok, bool)[rec_of_row] if len(rec_of_row) else np.zeros(0, bool)
+    kept = np.concatenate([[0], np.cumsum(keep)]).astype(np.int64)
+    return rids, kept[aln_off].astype(np.uint64), rec_of_row[keep].astype(np.uint32)

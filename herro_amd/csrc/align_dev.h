@@ -36,6 +36,20 @@ inline uint64_t align_scratch_bytes(uint32_t n, uint32_t m) {
 void launch_align(const uint64_t* d_words, const AlignIn* d_in, AlignOut* d_out, uint8_t* d_scr, uint32_t* d_dense,
                   uint32_t* d_count, uint32_t n_rec, hipStream_t st);
 
+// ---- mirrored records (k_mirror): the alignment of (q, t) derived from the final ops of (t, q) -------------------------
+struct MirrorIn {         // one record (64 B): AlignIn's sequence fields with the roles exchanged, and where its ops are
+  uint64_t t_woff, q_woff;   // first 2-bit word of the source's QUERY read (the mirror's target) / of its TARGET read
+  uint64_t src_off, dst_off; // first op of the source record / of the mirror's c reserved slots in the store
+  uint32_t t0, m;            // T' = the source's query bases [qstart, qend), forward
+  uint32_t q0, n;            // Q' = the source's target bases [tstart, tend); strand 1 reads them reversed and complemented
+  uint32_t strand, c;        // c: the source's op count (0: a failed source)
+  int32_t score;             // the source's score
+  uint32_t pad;
+};
+
+// d_out[r]: score, n_ops (<= c, in store[dst_off ..)), failed and the four drop lengths; ops_off is not used (0)
+void launch_mirror(const uint64_t* d_words, const MirrorIn* d_in, AlignOut* d_out, uint32_t* d_store, uint32_t n_rec, hipStream_t st);
+
 // ---- ends-free extension of an overlap's two ends (k_extend) --------------------------------------------
 constexpr uint32_t EXTEND_ZDROP = 400;            // herro_extend_params.zdrop = 0
 constexpr uint32_t EXTEND_MAX_EXT = 2048;         // herro_extend_params.max_ext = 0

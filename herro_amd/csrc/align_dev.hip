@@ -68,6 +68,89 @@ __device__ __forceinline__ int32_t cell(int32_t up_h, int32_t up_i, int32_t left
   return H;
 }
 
+// ---- fix_cigar (aligners.rs:138-250), the trailing-indel trim and the gap sums, streamed once over an op list -----------------------
+// One definition for k_align (the ops its traceback left) and k_mirror (another record's ops, swapped and read backwards): F(j) is
+// op j of cnt >= 1 ops, each fetched once and in order, two ahead of the op being looked at.
+// Left shift: op j is final once op j + 1 has been looked at, so it goes straight on into the retain / merge stage, which writes the
+// result to dst[0 ..): at most one op per op read, and op j is written only after F(j + 1) has been fetched.  Every lane runs the same
+// stream (uniform control flow); lane 0 writes.
+struct Fixed {
+  uint32_t nout;                     // final ops in dst[0 .. nout)
+  uint32_t first_t, last_t;          // their first and last type (3: there is none)
+  uint32_t tsh0, qsh0, tsh1, qsh1;   // bases the dropped leading / trailing indel consumed
+  int32_t gap_in, gap_fin;           // sum of 4 + 2 len over the I / D ops read / written
+  bool type3;                        // an op of type 3 was read
+};
+
+template <class Fetch>
+__device__ __forceinline__ Fixed fix_stream(Fetch F, uint32_t cnt, const Seq& T, const Seq& Q, uint32_t* dst, int L) {
+  uint32_t nout = 0;
+  bool is_start = true, have_last = false, type3 = false;
+  uint32_t last = 0, first_t = 3, last_t = 3;
+  uint32_t tsh0 = 0, qsh0 = 0, tsh1 = 0, qsh1 = 0;
+  int32_t gap_in = 0, gap_fin = 0;
+  auto write = [&](uint32_t op) {
+    if (L == 0) dst[nout] = op;
+    ++nout;
+    const uint32_t t = op & 3u;
+    if (first_t == 3) first_t = t;
+    last_t = t;
+    if (t) gap_fin += 4 + 2 * (int32_t)(op >> 2);
+  };
+  auto stage2 = [&](uint32_t op) {
+    const uint32_t t = op & 3u, len = op >> 2;
+    if (is_start) {
+      if (t == 0 && len == 0) return;
+      is_start = false;
+      if (t == 1) { qsh0 = len; return; }
+      if (t == 2) { tsh0 = len; return; }
+    } else if (len == 0) {
+      return;
+    }
+    if (have_last && (last & 3u) == t) { last += len << 2; return; }
+    if (have_last) write(last);
+    last = op; have_last = true;
+  };
+  int32_t tpos = 0, qpos = 0;
+  uint32_t prev = 0, cur = F(0), nxt = cnt > 1 ? F(1) : 0u;
+  for (uint32_t j = 0; j < cnt; ++j) {
+    const uint32_t t = cur & 3u;
+    const int32_t len = (int32_t)(cur >> 2);
+    if (t == 0) {
+      tpos += len; qpos += len;
+    } else {
+      type3 |= t == 3u;
+      gap_in += 4 + 2 * len;
+      if (j > 0 && j + 1 < cnt && (prev & 3u) == 0 && (nxt & 3u) == 0) {
+        const int32_t prev_len = (int32_t)(prev >> 2);
+        int32_t l = 0;
+        if (t == 1) {
+          while (l < prev_len && Q.at(qpos - 1 - l) == Q.at(qpos + len - 1 - l)) ++l;
+        } else {
+          while (l < prev_len && T.at(tpos - 1 - l) == T.at(tpos + len - 1 - l)) ++l;
+        }
+        if (l > 0) {
+          prev -= (uint32_t)l << 2;
+          nxt += (uint32_t)l << 2;
+          tpos -= l; qpos -= l;
+        }
+      }
+      if (t == 1) qpos += len; else tpos += len;
+    }
+    if (j > 0) stage2(prev);
+    prev = cur; cur = nxt;
+    nxt = j + 2 < cnt ? F(j + 2) : 0u;
+  }
+  stage2(prev);
+  if (have_last) {   // a trailing indel is dropped too
+    const uint32_t t = last & 3u;
+    if (t == 1) qsh1 = last >> 2;
+    else if (t == 2) tsh1 = last >> 2;
+    else write(last);
+  }
+  return Fixed{nout, first_t, last_t, tsh0, qsh0, tsh1, qsh1, gap_in, gap_fin, type3};
+}
+
 __global__ __launch_bounds__(64) void k_align(const uint64_t* __restrict__ words, const AlignIn* __restrict__ in,
                                               AlignOut* __restrict__ out, uint8_t* __restrict__ scr,
                                               uint32_t* __restrict__ dense, uint32_t* __restrict__ count) {
@@ -197,72 +280,11 @@ __global__ __launch_bounds__(64) void k_align(const uint64_t* __restrict__ words
   wave_sync();
 
   // ---- fix_cigar (aligners.rs:138-250), streamed: F[j] = ops[C - cnt + j] --------------------------------------------
-  // Left shift: op j is final once op j + 1 has been looked at, so it goes straight on into the retain / merge stage,
-  // which writes the result to ops[0 ..) (never ahead of what is still to be read: nout <= j < C - cnt + j).
-  const uint32_t* F = ops + (C - cnt);
-  uint32_t nout = 0;
-  bool is_start = true, have_last = false;
-  uint32_t last = 0, first_t = 3, last_t = 3;
-  uint32_t tsh0 = 0, qsh0 = 0, tsh1 = 0, qsh1 = 0;
-  int32_t gap_fin = 0;
-  auto write = [&](uint32_t op) {
-    if (L == 0) ops[nout] = op;
-    ++nout;
-    const uint32_t t = op & 3u;
-    if (first_t == 3) first_t = t;
-    last_t = t;
-    if (t) gap_fin += 4 + 2 * (int32_t)(op >> 2);
-  };
-  auto stage2 = [&](uint32_t op) {
-    const uint32_t t = op & 3u, len = op >> 2;
-    if (is_start) {
-      if (t == 0 && len == 0) return;
-      is_start = false;
-      if (t == 1) { qsh0 = len; return; }
-      if (t == 2) { tsh0 = len; return; }
-    } else if (len == 0) {
-      return;
-    }
-    if (have_last && (last & 3u) == t) { last += len << 2; return; }
-    if (have_last) write(last);
-    last = op; have_last = true;
-  };
-  int32_t tpos = 0, qpos = 0;
-  uint32_t prev = 0, cur = F[0], nxt = cnt > 1 ? F[1] : 0u;
-  for (uint32_t j = 0; j < cnt; ++j) {
-    const uint32_t t = cur & 3u;
-    const int32_t len = (int32_t)(cur >> 2);
-    if (t == 0) {
-      tpos += len; qpos += len;
-    } else {
-      if (j > 0 && j + 1 < cnt && (prev & 3u) == 0 && (nxt & 3u) == 0) {
-        const int32_t prev_len = (int32_t)(prev >> 2);
-        int32_t l = 0;
-        if (t == 1) {
-          while (l < prev_len && Q.at(qpos - 1 - l) == Q.at(qpos + len - 1 - l)) ++l;
-        } else {
-          while (l < prev_len && T.at(tpos - 1 - l) == T.at(tpos + len - 1 - l)) ++l;
-        }
-        if (l > 0) {
-          prev -= (uint32_t)l << 2;
-          nxt += (uint32_t)l << 2;
-          tpos -= l; qpos -= l;
-        }
-      }
-      if (t == 1) qpos += len; else tpos += len;
-    }
-    if (j > 0) stage2(prev);
-    prev = cur; cur = nxt;
-    nxt = j + 2 < cnt ? F[j + 2] : 0u;
-  }
-  stage2(prev);
-  if (have_last) {   // a trailing indel is dropped too
-    const uint32_t t = last & 3u;
-    if (t == 1) qsh1 = last >> 2;
-    else if (t == 2) tsh1 = last >> 2;
-    else write(last);
-  }
-  if (nout == 0 || first_t != 0 || last_t != 0) { fail(); return; }
+  // The result goes to ops[0 ..), never ahead of what is still to be read: nout <= j < C - cnt + j.
+  const uint32_t* Fp = ops + (C - cnt);
+  const Fixed fx = fix_stream([&](uint32_t j) { return Fp[j]; }, cnt, T, Q, ops, L);
+  if (fx.nout == 0 || fx.first_t != 0 || fx.last_t != 0) { fail(); return; }
+  const uint32_t nout = fx.nout;
 
   // ---- result: ops to the dense output, the record's header -------------------------------------------------------
   uint32_t base = 0;
@@ -271,7 +293,41 @@ __global__ __launch_bounds__(64) void k_align(const uint64_t* __restrict__ words
   wave_sync();
   for (uint32_t x = (uint32_t)L; x < nout; x += 64) dense[base + x] = ops[x];
   if (L == 0) {
-    AlignOut o{hend + gap_dp - gap_fin, nout, base, 0u, tsh0, qsh0, tsh1, qsh1};
+    AlignOut o{hend + gap_dp - fx.gap_fin, nout, base, 0u, fx.tsh0, fx.qsh0, fx.tsh1, fx.qsh1};
+    out[r] = o;
+  }
+}
+
+// ---- k_mirror: the alignment of (q, t) from the final ops of (t, q) (DESIGN.md §9 "Mirrored records"; tests/mirror_ref.py) ---------
+// One wave64 per record, no sweep: the source's ops are read through F[j] = swap(src[strand ? c - 1 - j : j]) (I <-> D; backwards on the
+// reverse strand, no reversed copy is made) and go through fix_stream against the swapped sequences — on the reverse strand the reversal
+// turns left-most indels into right-most ones, and a target's pileup needs them placed by one rule.  The result goes to the record's own
+// reservation of c slots (the host's prefix sum of the sources' n_ops; the final count may be smaller): no atomic counter, no LDS, no
+// scratch, every loop bounded by c or by an op's length.  Ops that do not add up to the spans read codes of 0 (Seq::at) and give a
+// meaningless but memory-safe result.
+__global__ __launch_bounds__(64) void k_mirror(const uint64_t* __restrict__ words, const MirrorIn* __restrict__ in,
+                                               AlignOut* __restrict__ out, uint32_t* store) {
+  const uint32_t r = blockIdx.x;
+  const int L = (int)threadIdx.x;
+  const MirrorIn a = in[r];
+  auto fail = [&]() {
+    if (L == 0) {
+      AlignOut f{INT32_MIN, 0u, 0u, 1u, 0u, 0u, 0u, 0u};
+      out[r] = f;
+    }
+  };
+  const uint32_t c = a.c, rev = a.strand;
+  if (c == 0) { fail(); return; }   // a failed source
+  const Seq T{words + a.t_woff, (int32_t)a.t0, (int32_t)a.m, 0u}, Q{words + a.q_woff, (int32_t)a.q0, (int32_t)a.n, rev};
+  const uint32_t* src = store + a.src_off;
+  const Fixed fx = fix_stream([&](uint32_t j) {
+    const uint32_t op = src[rev ? c - 1 - j : j];
+    const uint32_t t = op & 3u;
+    return (t == 1u || t == 2u) ? op ^ 3u : op;
+  }, c, T, Q, store + a.dst_off, L);
+  if (fx.type3 || fx.nout == 0 || fx.first_t != 0 || fx.last_t != 0) { fail(); return; }
+  if (L == 0) {
+    AlignOut o{a.score + fx.gap_in - fx.gap_fin, fx.nout, 0u, 0u, fx.tsh0, fx.qsh0, fx.tsh1, fx.qsh1};
     out[r] = o;
   }
 }
@@ -383,6 +439,11 @@ __global__ __launch_bounds__(64) void k_extend(const uint64_t* __restrict__ word
 void launch_extend(const uint64_t* d_words, const ExtIn* d_in, ExtOut* d_out, uint32_t zdrop, uint32_t n_sides, hipStream_t st) {
   if (n_sides == 0) return;
   hipLaunchKernelGGL(k_extend, dim3(n_sides), dim3(64), 0, st, d_words, d_in, d_out, zdrop);
+}
+
+void launch_mirror(const uint64_t* d_words, const MirrorIn* d_in, AlignOut* d_out, uint32_t* d_store, uint32_t n_rec, hipStream_t st) {
+  if (n_rec == 0) return;
+  hipLaunchKernelGGL(k_mirror, dim3(n_rec), dim3(64), 0, st, d_words, d_in, d_out, d_store);
 }
 
 void launch_align(const uint64_t* d_words, const AlignIn* d_in, AlignOut* d_out, uint8_t* d_scr, uint32_t* d_dense,

@@ -3666,6 +3666,82 @@ int herro_aligned_dev_from_ops(herro_ctx* ctx, uint32_t n, const herro_alignment
   return HERRO_OK;
 }
 
+// ---- mirrored records (k_mirror in align_dev.hip): every record's alignment the other way round, without a second sweep ----------
+// The new handle's store is src's ops (device to device) and behind them one reservation per mirror — the prefix sum of src's n_ops, since a mirror never
+// has more ops than its source.  Records go through in slices of 2^20, one synchronisation per slice to fetch the results.
+int herro_aligned_dev_mirror(herro_ctx* ctx, const herro_aligned_dev* src, herro_aligned_dev** out) {
+  if (!ctx || !src || !out) return HERRO_E_INVALID;
+  *out = nullptr;
+  if (src->ctx != ctx) { ctx->err = "herro_aligned_dev_mirror: the handle belongs to another context"; return HERRO_E_INVALID; }
+  if (src->host_only) { ctx->err = "herro_aligned_dev_mirror: the context has no device"; return HERRO_E_NO_DEVICE; }
+  if (src->alns.size() > 0x7fffffffull) { ctx->err = "herro_aligned_dev_mirror: more than 2^31 - 1 records"; return HERRO_E_INVALID; }
+  const uint32_t n = (uint32_t)src->alns.size();
+  if (const int rc = check_records(ctx, "herro_aligned_dev_mirror", n, src->alns.data())) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::unique_ptr<herro_aligned_dev, void (*)(herro_aligned_dev*)> h(new herro_aligned_dev(), herro_aligned_dev_free);
+  h->ctx = ctx; h->device = ctx->device;
+  h->alns = src->alns; h->scores = src->scores; h->n_ops = src->n_ops; h->op_off = src->op_off;
+  h->failed = src->failed;
+  h->alns.resize(2 * (size_t)n); h->scores.resize(2 * (size_t)n, INT32_MIN); h->n_ops.resize(2 * (size_t)n, 0); h->op_off.resize(2 * (size_t)n, 0);
+  uint64_t total = src->used;
+  for (uint32_t r = 0; r < n; r++) {
+    const herro_alignment& s = src->alns[r];
+    herro_alignment& a = h->alns[n + r];
+    a = herro_alignment{};
+    a.qid = s.tid; a.qlen = s.tlen; a.qstart = s.tstart; a.qend = s.tend; a.strand = s.strand;
+    a.tid = s.qid; a.tlen = s.qlen; a.tstart = s.qstart; a.tend = s.qend;
+    h->op_off[n + r] = total;
+    total += src->n_ops[r];
+  }
+  h->used = h->cap = total;
+  constexpr uint32_t SLICE = 1u << 20;
+  const uint32_t cap = std::min(n, SLICE);
+  std::vector<herro::MirrorIn> recs(cap);
+  std::vector<herro::AlignOut> res(cap);
+  herro::MirrorIn* d_in = nullptr;
+  herro::AlignOut* d_out = nullptr;
+  auto hip_fail = [&](hipError_t e, const char* what) {
+    ctx->err = std::string("herro_aligned_dev_mirror: ") + what + ": " + hipGetErrorString(e);
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    return HERRO_E_NO_DEVICE;
+  };
+  hipError_t e = hipSuccess;
+  if (total && (e = hipMalloc((void**)&h->d_ops, total * 4)) != hipSuccess) return hip_fail(e, "op store");
+  if (src->used && (e = hipMemcpyAsync(h->d_ops, src->d_ops, src->used * 4, hipMemcpyDeviceToDevice, ctx->stream)) != hipSuccess) return hip_fail(e, "op copy");
+  if (n) {
+    if ((e = hipMalloc((void**)&d_in, sizeof(herro::MirrorIn) * cap)) != hipSuccess) return hip_fail(e, "records");
+    if ((e = hipMalloc((void**)&d_out, sizeof(herro::AlignOut) * cap)) != hipSuccess) return hip_fail(e, "results");
+  }
+  for (uint32_t r0 = 0; r0 < n; r0 += SLICE) {
+    const uint32_t cnt = std::min(SLICE, n - r0);
+    for (uint32_t x = 0; x < cnt; x++) {
+      const uint32_t r = r0 + x;
+      const herro_alignment& s = src->alns[r];
+      // the mirror's target is the source's query read, forward; its query the source's target read, reversed and complemented on strand 1
+      recs[x] = herro::MirrorIn{ctx->h_word_off[s.qid], ctx->h_word_off[s.tid], src->op_off[r], h->op_off[n + r], s.qstart, s.qend - s.qstart,
+                                s.tstart, s.tend - s.tstart, s.strand, src->n_ops[r], src->n_ops[r] ? src->scores[r] : 0, 0u};
+    }
+    if ((e = hipMemcpyAsync(d_in, recs.data(), sizeof(herro::MirrorIn) * cnt, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) return hip_fail(e, "record upload");
+    herro::launch_mirror(ctx->d_words, d_in, d_out, h->d_ops, cnt, ctx->stream);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_mirror launch");
+    if ((e = hipMemcpyAsync(res.data(), d_out, sizeof(herro::AlignOut) * cnt, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) return hip_fail(e, "results");
+    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return hip_fail(e, "k_mirror");
+    for (uint32_t x = 0; x < cnt; x++) {
+      const herro::AlignOut& o = res[x];
+      if (o.failed) { h->failed++; continue; }   // n_ops 0, INT32_MIN and the swapped coordinates, untrimmed
+      h->scores[n + r0 + x] = o.score;
+      h->n_ops[n + r0 + x] = o.n_ops;
+      apply_trim(h->alns[n + r0 + x], o);
+    }
+  }
+  if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return hip_fail(e, "op copy");   // (n = 0 with ops in src's store: the copy has landed)
+  if (d_in) (void)hipFree(d_in);
+  if (d_out) (void)hipFree(d_out);
+  *out = h.release();
+  return HERRO_OK;
+}
+
 uint32_t herro_aligned_dev_n(const herro_aligned_dev* a) { return a ? (uint32_t)a->alns.size() : 0; }
 const herro_alignment* herro_aligned_dev_alignments(const herro_aligned_dev* a) { return a ? a->alns.data() : nullptr; }
 const int32_t* herro_aligned_dev_scores(const herro_aligned_dev* a) { return a ? a->scores.data() : nullptr; }

@@ -388,6 +388,20 @@ int herro_align_overlaps_dev(herro_ctx* ctx, uint32_t n, const herro_alignment* 
  * half of herro_job_create_aligned.  Ops herro_job_create would refuse as text (length 0, type 3) are refused by herro_job_create_aligned. */
 int herro_aligned_dev_from_ops(herro_ctx* ctx, uint32_t n, const herro_alignment* alns, const uint64_t* op_off /* [n + 1] */,
                                const uint32_t* ops, herro_aligned_dev** out);
+/* Every record of src and, behind them, its mirror — the alignment of the same two reads with query and target exchanged, derived from
+ * the record's final ops on the device (k_mirror, csrc/align_dev.hip; DESIGN.md section 9, "Mirrored records") instead of a second
+ * alignment: out holds 2n records, record r (r < n) is src's record r, record n + r its mirror.  The mirror's coordinates are src's with
+ * the two reads swapped (same strand); its ops are src's with I and D exchanged, in reverse order on strand 1, normalised again by
+ * fix_cigar against the swapped sequences (a dropped leading / trailing indel moves the coordinates as in herro_align_overlaps); its
+ * score is src's score + g(src's ops) - g(its ops), g the sum of 4 + 2 len over the I / D ops — the score of its CIGAR when src's is
+ * the score of src's; for a handle of herro_aligned_dev_from_ops, whose scores are 0, the field is just that difference.  A failed
+ * source, a source with an op of type 3 and a mirror that is empty or does not start and end with M after the normalisation are failed
+ * records: n_ops 0, score INT32_MIN, the swapped coordinates untrimmed.  A host pairs its records (record B is record A's exact swap)
+ * and aligns one of each pair; two directions that differ must both be aligned.
+ * The new handle owns its store (src's ops copied on the device, the mirrors' behind them): src may be freed; every accessor and
+ * herro_job_create_aligned work on it unchanged.  HERRO_E_INVALID: a null argument, a handle of another context, a source record outside
+ * the read store (named); HERRO_E_NO_DEVICE: a device-free context or handle; HERRO_E_STATE: no reads set.  n = 0: an empty handle. */
+int herro_aligned_dev_mirror(herro_ctx* ctx, const herro_aligned_dev* src, herro_aligned_dev** out);
 uint32_t herro_aligned_dev_n(const herro_aligned_dev* a);
 const herro_alignment* herro_aligned_dev_alignments(const herro_aligned_dev* a);   /* trimmed coordinates; cigar = NULL, cigar_len = 0 */
 const int32_t* herro_aligned_dev_scores(const herro_aligned_dev* a);               /* INT32_MIN: failed */
