@@ -1,6 +1,6 @@
 """Helpers shared by tests/test_aligned_dev_host.py and tests/test_gpu_aligned_dev.py: CIGAR text <-> the binary ops of
 herro_aligned_dev_from_ops (len << 2 | {0 M, 1 I, 2 D}), the comparison of an aligned job with the text path's, the hand-made
-alignments at the edges of k_ops_scan and the records of the aligner's test."""
+alignments at the edges of k_ops_scan and of the windowing (the latter for tests/build_cases.py) and the records of the aligner's test."""
 import re
 
 import numpy as np
@@ -92,6 +92,43 @@ def hand_cases():
         "d_across_boundary": (32, [(14, "M"), (5, "D"), (45, "M"), (1, "I"), (64, "M")]), # 5D: 46 -> 51 across 48
         "i_before_boundary": (32, [(16, "M"), (3, "I"), (48, "M"), (1, "D"), (63, "M")]), # 16M ends on 48, the insertion sits on the boundary
         "tstart_odd": (37, [(100, "M"), (1, "D"), (2, "I"), (150, "M")]),
+    }
+
+
+def hand_cases_more():
+    """name -> ((tstart, [(len, type)]), overlaps the alignment gives alone).  More cases at W = 16 beside hand_cases(), which
+    tests/test_gpu_aligned_dev.py reads by name and expects a window from every entry of: ends of the target, gaps on and around a
+    boundary, the shortest alignment that is windowed and the two that just are not.  704 = 44 * 16."""
+    return {
+        "d_three_windows": ((40, [(6, "M"), (40, "D"), (30, "M")]), 4),                       # 40D: 46 -> 86 across 48, 64, 80
+        "ends_on_boundary": ((32, [(20, "M"), (1, "I"), (44, "M")]), 4),                      # 32 -> 96, the last op ends on 96
+        "from_zero_to_tail": ((0, [(300, "M"), (2, "D"), (1, "I"), (402, "M")]), 44),         # the whole target
+        "tail_short": ((600, [(50, "M"), (1, "D"), (53, "M")]), 6),                           # ends at 704, an exact multiple
+        "tail_inexact": ((601, [(50, "M"), (1, "D"), (45, "M")]), 5),                         # ends at 697: the tail window rule
+        "i_then_d_on_boundary": ((32, [(16, "M"), (2, "I"), (3, "D"), (60, "M")]), 4),        # 16M ends on 48, 2I stays, 3D opens the next
+        "d_ends_on_boundary_then_i": ((32, [(10, "M"), (6, "D"), (2, "I"), (60, "M")]), 4),   # 6D ends on 48 with an insertion behind it
+        "exactly_W": ((32, [(16, "M")]), 1),
+        "W_minus_1": ((32, [(15, "M")]), 0),
+        "q_short": ((32, [(5, "M"), (20, "D"), (5, "M")]), 0),                                # 30 target bases, 10 of the query: below W
+    }
+
+
+HAND_W40 = 40
+
+
+def hand_cases_w40():
+    """name -> ((tstart, ops), overlaps alone) at W = 40 on the same target: the zero-threshold rules (windowing.rs:65-85, 261-272)
+    with a threshold of 4 (at W = 16 it is 1 and `tstart < 1` is `tstart == 0`), and a ragged last window: 704 = 17 * 40 + 24,
+    tlen - 4 = 700."""
+    mid = [(100, "M"), (1, "D"), (2, "I"), (150, "M")]                                        # 251 target bases
+    return {
+        "tstart_below_zthr": ((3, mid), 6),                                                   # 3 < 4: window 0 is opened at 3
+        "tstart_at_zthr": ((4, mid), 5),                                                      # 4 is not: the first window is 1
+        "tend_above_nthr": ((500, [(100, "M"), (1, "I"), (101, "M")]), 5),                    # ends at 701 > 700: the tail window
+        "tend_at_nthr": ((500, [(100, "M"), (1, "I"), (100, "M")]), 4),                       # ends at 700: none
+        "tend_at_tlen": ((500, [(100, "M"), (1, "I"), (104, "M")]), 5),                       # ends at 704
+        "whole": ((0, [(704, "M")]), 18),
+        "d_over_tail_boundary": ((600, [(70, "M"), (20, "D"), (14, "M")]), 3),                # 20D: 670 -> 690 across 680, the last boundary
     }
 
 

@@ -1,7 +1,9 @@
 """gpu: the device-resident hand-off from the aligner to the job builder — herro_align_overlaps_dev keeps every
 record's ops on the device, herro_job_create_aligned builds the job from them through k_ops_scan (csrc/cigar_dev.hip), the binary
 sibling of k_cigar_scan.  Everything is held to the text path: the job herro_job_create builds from the texts of the same ops, the
-records herro_align_overlaps returns, the FASTA of the chain through align -> aligned_job_args -> create_job."""
+records herro_align_overlaps returns, the FASTA of the chain through align -> aligned_job_args -> create_job.  Both sides of the
+hand-case comparison below are device builds through the same k_window_cuts: the hand cases (with more of them, and a set at W = 40) are
+held to the host build in tests/test_gpu_build_sizes.py and, through it, to the oracle's extract_windows in tests/test_build_cases.py."""
 import json
 import os
 import subprocess
