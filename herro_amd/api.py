@@ -54,6 +54,37 @@ class Alignment(C.Structure):  # herro_alignment
                [("cigar", C.c_void_p)]
 
 
+ALN_DTYPE = np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True)   # herro_alignment as numpy sees it: f = the ten u32 fields, p = cigar
+
+
+def _aln_array(rows: np.ndarray, ncols: int = 9):
+    """rows u32 [n, >= ncols] -> (an Alignment array of max(n, 1) with those columns filled in and the rest 0, its ALN_DTYPE view)"""
+    n = len(rows)
+    arr = (Alignment * max(n, 1))()
+    view = np.frombuffer(arr, dtype=ALN_DTYPE, count=max(n, 1))   # vectorised fill through a numpy view of the ctypes array
+    if n:
+        view["f"][:n, :ncols] = rows[:, :ncols]
+    return arr, view
+
+
+def _aln_rows(ptr, n: int, with_cigar_ptr: bool = False):
+    """the n herro_alignment at ptr -> rows u32 [n, 10] (a copy; with_cigar_ptr: and their cigar pointers u64 [n])"""
+    rows, cig = np.zeros((n, 10), np.uint32), np.zeros(n, np.uint64)
+    if n:
+        view = np.frombuffer((Alignment * n).from_address(ptr), dtype=ALN_DTYPE, count=n)
+        rows[:], cig[:] = view["f"], view["p"]
+    return (rows, cig) if with_cigar_ptr else rows
+
+
+def _job_or_raise(ctx: "Context", h, n_targets: int) -> "Job":
+    """herro_job_create*'s handle as a Job; NULL: HerroError with the code its message ends on"""
+    if not h:
+        msg = ctx._l.herro_last_error(ctx.h).decode(errors="replace")
+        code = int(msg.rsplit("[code ", 1)[1].rstrip("]")) if "[code " in msg else -1
+        raise HerroError(code, msg)
+    return Job(ctx, h, n_targets)
+
+
 class OverlapParams(C.Structure):  # herro_overlap_params (0 = the field's default)
     _fields_ = [(n, C.c_uint32) for n in ("k", "w", "max_occ", "bandwidth", "max_gap", "min_score", "min_anchors", "reserved")]
 
@@ -506,22 +537,12 @@ class Context:
         else:
             cig_blob = np.ascontiguousarray(cig_blob, np.uint8)
             cl = aln_rows[:, 9].astype(np.uint64)
-        arr = (Alignment * max(n, 1))()
-        base = cig_blob.ctypes.data
-        # vectorised fill through a numpy view of the ctypes array
-        view = np.frombuffer(arr, dtype=np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True), count=max(n, 1))
+        arr, view = _aln_array(aln_rows)
         if n:
-            view["f"][:n, :9] = aln_rows[:, :9]
             view["f"][:n, 9] = cl
-            view["p"][:n] = base + np.asarray(cig_off, np.uint64)
+            view["p"][:n] = cig_blob.ctypes.data + np.asarray(cig_off, np.uint64)
         h = self._l.herro_job_create(self.h, len(rids), rids.ctypes.data, aln_off.ctypes.data, C.byref(arr), window_size)
-        if not h:
-            msg = self._l.herro_last_error(self.h).decode(errors="replace")
-            code = -1
-            if "[code " in msg:
-                code = int(msg.rsplit("[code ", 1)[1].rstrip("]"))
-            raise HerroError(code, msg)
-        return Job(self, h, len(rids))
+        return _job_or_raise(self, h, len(rids))
 
     def align(self, rows: np.ndarray):
         """Base-level alignment of overlaps given by coordinates only (herro_align_overlaps; the `minimap2 -c` step of mm2.rs:15-30
@@ -530,22 +551,15 @@ class Context:
         scores: i32 [n], ok: bool [n]); a failed record keeps its coordinates and gets an empty CIGAR."""
         rows = np.ascontiguousarray(rows, np.uint32)
         n = len(rows)
-        arr = (Alignment * max(n, 1))()
-        view = np.frombuffer(arr, dtype=np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True), count=max(n, 1))
-        if n:
-            view["f"][:n, :9] = rows[:, :9]
+        arr, _ = _aln_array(rows)
         h = C.c_void_p()
         self._chk(self._l.herro_align_overlaps(self.h, n, C.byref(arr), C.byref(h)))
         try:
-            out = np.zeros((n, 10), np.uint32)
+            out, ptr = _aln_rows(self._l.herro_aligned_alignments(h), n, with_cigar_ptr=True)
             scores = np.zeros(n, np.int32)
-            cigars: list[bytes] = []
             if n:
-                res = (Alignment * n).from_address(self._l.herro_aligned_alignments(h))
-                rv = np.frombuffer(res, dtype=np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True), count=n)
-                out[:] = rv["f"]
                 scores[:] = np.ctypeslib.as_array(C.cast(self._l.herro_aligned_scores(h), C.POINTER(C.c_int32)), (n,))
-                cigars = [C.string_at(int(p), int(k)) if k else b"" for p, k in zip(rv["p"], out[:, 9])]
+            cigars = [C.string_at(int(p), int(k)) if k else b"" for p, k in zip(ptr, out[:, 9])]
         finally:
             self._l.herro_aligned_free(h)
         return out, cigars, scores, out[:, 9] > 0
@@ -555,10 +569,7 @@ class Context:
         exists unless AlignedDev.cigar asks for one."""
         rows = np.ascontiguousarray(rows, np.uint32)
         n = len(rows)
-        arr = (Alignment * max(n, 1))()
-        view = np.frombuffer(arr, dtype=np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True), count=max(n, 1))
-        if n:
-            view["f"][:n, :9] = rows[:, :9]
+        arr, _ = _aln_array(rows)
         h = C.c_void_p()
         self._chk(self._l.herro_align_overlaps_dev(self.h, n, C.byref(arr), C.byref(h)))
         return AlignedDev(self, h)
@@ -572,10 +583,7 @@ class Context:
         n = len(rows)
         if len(op_off) != n + 1 or (n and int(op_off[-1]) > len(ops)):
             raise ValueError("op_off has one entry per record + 1 and ends inside ops")
-        arr = (Alignment * max(n, 1))()
-        view = np.frombuffer(arr, dtype=np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True), count=max(n, 1))
-        if n:
-            view["f"][:n, :9] = rows[:, :9]
+        arr, _ = _aln_array(rows)
         h = C.c_void_p()
         self._chk(self._l.herro_aligned_dev_from_ops(self.h, n, C.byref(arr), op_off.ctypes.data, ops.ctypes.data if len(ops) else None, C.byref(h)))
         return AlignedDev(self, h)
@@ -590,11 +598,7 @@ class Context:
             raise ValueError("aln_off has one entry per target + 1 and ends inside rec")
         h = self._l.herro_job_create_aligned(self.h, len(rids), rids.ctypes.data, aln_off.ctypes.data, rec.ctypes.data if len(rec) else None,
                                              handle.h, window_size)
-        if not h:
-            msg = self._l.herro_last_error(self.h).decode(errors="replace")
-            code = int(msg.rsplit("[code ", 1)[1].rstrip("]")) if "[code " in msg else -1
-            raise HerroError(code, msg)
-        return Job(self, h, len(rids))
+        return _job_or_raise(self, h, len(rids))
 
     def _overlap_params(self, params: dict) -> OverlapParams:
         """keyword arguments -> herro_overlap_params.  A field left out (or None) takes its default, which the struct spells 0; an
@@ -623,11 +627,9 @@ class Context:
             n, nt = self._l.herro_overlaps_n(h), self._l.herro_overlaps_n_targets(h)
             rids = np.ctypeslib.as_array(C.cast(self._l.herro_overlaps_target_ids(h), C.POINTER(C.c_uint32)), (nt,)).copy() if nt else np.zeros(0, np.uint32)
             aln_off = np.ctypeslib.as_array(C.cast(self._l.herro_overlaps_aln_off(h), C.POINTER(C.c_uint64)), (nt + 1,)).copy()
-            rows = np.zeros((n, 10), np.uint32)
+            rows = _aln_rows(self._l.herro_overlaps_alignments(h), n)
             scores = np.zeros(n, np.int32)
             if n:
-                res = (Alignment * n).from_address(self._l.herro_overlaps_alignments(h))
-                rows[:] = np.frombuffer(res, dtype=np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True), count=n)["f"]
                 scores[:] = np.ctypeslib.as_array(C.cast(self._l.herro_overlaps_scores(h), C.POINTER(C.c_int32)), (n,))
         finally:
             self._l.herro_overlaps_free(h)
@@ -642,21 +644,16 @@ class Context:
         n = len(rows)
         if not 0 <= int(zdrop) <= 0xFFFFFFFF or not 0 <= int(max_ext) <= 0xFFFFFFFF:
             raise HerroError(-1, "extend parameters: zdrop and max_ext are unsigned 32-bit values")
-        arr = (Alignment * max(n, 1))()
-        view = np.frombuffer(arr, dtype=np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True), count=max(n, 1))
-        if n:
-            view["f"][:n, :9] = rows[:, :9]
+        arr, _ = _aln_array(rows)
         p = ExtendParams(zdrop=int(zdrop), max_ext=int(max_ext))
         h = C.c_void_p()
         self._chk(self._l.herro_extend_overlaps(self.h, n, C.byref(arr), C.byref(p), C.byref(h)))
         try:
-            out = np.zeros((n, 10), np.uint32)
+            assert self._l.herro_extended_n(h) == n
+            out = _aln_rows(self._l.herro_extended_alignments(h), n)
             ext = np.zeros((n, 4), np.uint32)
             scores = np.zeros((n, 2), np.int32)
             if n:
-                assert self._l.herro_extended_n(h) == n
-                res = (Alignment * n).from_address(self._l.herro_extended_alignments(h))
-                out[:] = np.frombuffer(res, dtype=np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True), count=n)["f"]
                 ext[:] = np.ctypeslib.as_array(C.cast(self._l.herro_extended_ext(h), C.POINTER(C.c_uint32)), (n, 4))
                 scores[:] = np.ctypeslib.as_array(C.cast(self._l.herro_extended_scores(h), C.POINTER(C.c_int32)), (n, 2))
         finally:
@@ -681,11 +678,7 @@ class Context:
         """herro_job_create straight from a parsed PAF batch (targets in its order); `paf` must outlive the call."""
         h = self._l.herro_job_create(self.h, len(paf.targets), paf.targets.ctypes.data, paf.aln_off.ctypes.data,
                                      paf._alns_ptr, window_size)
-        if not h:
-            msg = self._l.herro_last_error(self.h).decode(errors="replace")
-            code = int(msg.rsplit("[code ", 1)[1].rstrip("]")) if "[code " in msg else -1
-            raise HerroError(code, msg)
-        return Job(self, h, len(paf.targets))
+        return _job_or_raise(self, h, len(paf.targets))
 
     def model_forward(self, bases: np.ndarray, quals: np.ndarray, lens: np.ndarray, indices: np.ndarray):
         """inference.rs:147-175: tokens u8 [B,L,31], raw quals u8 [B,L,31], lens, flat indices -> logits."""
@@ -871,12 +864,10 @@ class AlignedDev:
     def __init__(self, ctx: Context, h):
         self.ctx, self.h, self._l = ctx, h, ctx._l
         n = self.n = int(self._l.herro_aligned_dev_n(h))
-        self.rows = np.zeros((n, 10), np.uint32)
+        self.rows = _aln_rows(self._l.herro_aligned_dev_alignments(h), n)
         self.scores = np.zeros(n, np.int32)
         self.n_ops = np.zeros(n, np.uint32)
         if n:
-            res = (Alignment * n).from_address(self._l.herro_aligned_dev_alignments(h))
-            self.rows[:] = np.frombuffer(res, dtype=np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True), count=n)["f"]
             self.scores[:] = np.ctypeslib.as_array(C.cast(self._l.herro_aligned_dev_scores(h), C.POINTER(C.c_int32)), (n,))
             self.n_ops[:] = np.ctypeslib.as_array(C.cast(self._l.herro_aligned_dev_n_ops(h), C.POINTER(C.c_uint32)), (n,))
         self.ok = self.n_ops > 0
@@ -998,10 +989,7 @@ class Paf:
 
     def coords(self) -> np.ndarray:
         """u32 [n, 10]: qid, qlen, qstart, qend, strand, tid, tlen, tstart, tend, cigar_len in output order (Context.align's rows)."""
-        if not self.n_alns:
-            return np.zeros((0, 10), np.uint32)
-        v = np.frombuffer(self.alns, dtype=np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True), count=self.n_alns)
-        return v["f"].copy()
+        return _aln_rows(self._alns_ptr, self.n_alns)
 
     def rows(self):
         """[(qid, qlen, qstart, qend, strand, tid, tlen, tstart, tend, cigar bytes)] in output order."""
@@ -1030,10 +1018,8 @@ class PreparedAlignments:
         self.rids = np.ascontiguousarray(sb.tgt_rid, np.uint32)
         self.aln_off = np.ascontiguousarray(sb.tgt_aln_off, np.uint64)
         self._cig = np.ascontiguousarray(sb.cig, np.uint8)
-        self._arr = (Alignment * max(n, 1))()
-        view = np.frombuffer(self._arr, dtype=np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True), count=max(n, 1))
+        self._arr, view = _aln_array(sb.aln, 10)
         if n:
-            view["f"][:n, :10] = sb.aln[:, :10]
             view["p"][:n] = self._cig.ctypes.data + np.asarray(sb.cig_off, np.uint64)
         self.n_targets = len(self.rids)
         self._reg = None
@@ -1060,11 +1046,7 @@ class PreparedAlignments:
         """herro_job_create over targets [t0, t1): rids / aln_off are passed as offsets into the resident arrays"""
         h = ctx._l.herro_job_create(ctx.h, t1 - t0, self.rids.ctypes.data + 4 * t0, self.aln_off.ctypes.data + 8 * t0,
                                     C.byref(self._arr), window_size)
-        if not h:
-            msg = ctx._l.herro_last_error(ctx.h).decode(errors="replace")
-            code = int(msg.rsplit("[code ", 1)[1].rstrip("]")) if "[code " in msg else -1
-            raise HerroError(code, msg)
-        return Job(ctx, h, t1 - t0)
+        return _job_or_raise(ctx, h, t1 - t0)
 
 
 def job_from_synth(ctx: Context, sb, window_size: int, targets=None) -> Job:

@@ -1,0 +1,550 @@
+// frontend_api.hip — the C ABI's front end (include/herro_amd.h): reads alone -> overlap records -> their ops on the device.
+// herro_find_overlaps, herro_extend_overlaps, herro_align_overlaps[_dev], herro_aligned_dev_*.  Host C++ (compiled by hipcc) over
+// overlap_dev.hip and align_dev.hip; contexts, the model and jobs are herro_api.hip.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+
+#include "aligned_dev.h"
+#include "align_dev.h"
+#include "dev_bufs.h"
+#include "overlap_dev.h"
+
+namespace {
+constexpr uint32_t SLICE = 1u << 20;   // records per turn of herro_extend_overlaps and herro_aligned_dev_mirror: their descriptors and results stay small whatever n is
+
+// A HIP call of a front-end entry failed: "<who>: <what>: <HIP's text>" and HERRO_E_NO_DEVICE.  Scratch in a Bufs goes with the return.
+int hip_failed(herro_ctx* ctx, const char* who, const char* what, hipError_t e) {
+  ctx->err = std::string(who) + ": " + what + ": " + hipGetErrorString(e);
+  return HERRO_E_NO_DEVICE;
+}
+#define FRONT_TRY(ctx, who, what, expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) return hip_failed(ctx, who, what, _e); } while (0)
+
+// What every front-end entry (`who`) asks of a context's state before anything runs.
+int device_ready(herro_ctx* ctx, const char* who) {
+  if (ctx->host_only) { ctx->err = std::string(who) + ": the context has no device"; return HERRO_E_NO_DEVICE; }
+  if (!ctx->d_words) { ctx->err = "herro_set_reads must be called first"; return HERRO_E_STATE; }
+  return HERRO_OK;
+}
+
+// 4 GiB of device scratch per call, or what the environment says (in MiB, at least 1)
+uint64_t scratch_budget(const char* env_name) { const char* e = getenv(env_name); return e ? (uint64_t)std::max(1ll, atoll(e)) << 20 : 4096ull << 20; }
+
+herro::OvlStore ovl_store(const herro_ctx* ctx) { return herro::OvlStore{ctx->d_words, ctx->d_word_off, ctx->d_qual_off, ctx->read_len.data(), ctx->n_reads}; }
+
+using AlignedDevPtr = std::unique_ptr<herro_aligned_dev, void (*)(herro_aligned_dev*)>;
+AlignedDevPtr new_aligned_dev(herro_ctx* ctx) {
+  AlignedDevPtr h(new herro_aligned_dev(), herro_aligned_dev_free);
+  h->ctx = ctx; h->device = ctx->device; h->host_only = ctx->host_only;
+  return h;
+}
+
+uint32_t dec_digits(uint32_t v) { uint32_t k = 1; while (v >= 10) { v /= 10; k++; } return k; }
+// bytes of "<len><M|I|D>" per op
+uint64_t ops_text_bytes(const uint32_t* ops, uint32_t n) {
+  uint64_t b = 0;
+  for (uint32_t x = 0; x < n; x++) b += dec_digits(ops[x] >> 2) + 1;
+  return b;
+}
+char* ops_text(const uint32_t* ops, uint32_t n, char* p) {
+  for (uint32_t x = 0; x < n; x++) {
+    p += snprintf(p, 12, "%u", ops[x] >> 2);
+    *p++ = "MID?"[ops[x] & 3u];   // ('?': type 3 of a caller's own ops; herro_job_create refuses the letter)
+  }
+  return p;
+}
+
+// One record's result in its handle: a failed record is counted, gets INT32_MIN and 0 ops and keeps its coordinates; any other its score, its op
+// count and the coordinates after fix_cigar dropped a leading / trailing indel.
+void fold_result(const herro::AlignOut& o, herro_alignment& a, int32_t& score, uint32_t& n_ops, uint32_t& failed) {
+  if (o.failed) { score = INT32_MIN; n_ops = 0; failed++; return; }
+  score = o.score;
+  n_ops = o.n_ops;
+  a.tstart += o.tdrop0; a.tend -= o.tdrop1;
+  if (a.strand == 0) { a.qstart += o.qdrop0; a.qend -= o.qdrop1; }
+  else { a.qend -= o.qdrop0; a.qstart += o.qdrop1; }
+}
+
+// What herro_align_overlaps[_dev], herro_extend_overlaps and herro_aligned_dev_mirror (`who`) ask of a context and of coordinate-only records before anything runs.
+int check_records(herro_ctx* ctx, const char* who, uint32_t n, const herro_alignment* in) {
+  if (const int rc = device_ready(ctx, who)) return rc;
+  for (uint32_t r = 0; r < n; r++) {
+    const herro_alignment& a = in[r];
+    std::string why;
+    if (a.qid >= ctx->n_reads || a.tid >= ctx->n_reads) why = "read id outside the read store";
+    else if (a.qstart > a.qend || a.qend > ctx->read_len[a.qid]) why = "query coordinates outside the read";
+    else if (a.tstart > a.tend || a.tend > ctx->read_len[a.tid]) why = "target coordinates outside the read";
+    else if (a.strand > 1) why = "strand must be 0 or 1";
+    else if ((uint64_t)(a.qend - a.qstart) + (a.tend - a.tstart) > herro::ALIGN_MAX_CELLS) why = "overlap longer than 2^25 bases in all";
+    if (!why.empty()) {
+      ctx->err = std::string(who) + ": record " + std::to_string(r) + ": " + why;
+      return HERRO_E_INVALID;
+    }
+  }
+  return HERRO_OK;
+}
+
+// Validation, chunking (HERRO_ALIGN_SCRATCH_MB) and the kernel runs of herro_align_overlaps and herro_align_overlaps_dev.  Behind every chunk the host
+// reads its op total and its AlignOut records and hands the chunk's dense ops, still on the device, to take(total, d_dense, r_done, at): it stores them and
+// says where (at: the chunk's first op in the caller's store; r_done: records aligned so far, this chunk's included).  ops_at[r]: record r's first op there.
+template <class Take>
+int align_chunks(herro_ctx* ctx, uint32_t n, const herro_alignment* in, std::vector<herro::AlignOut>& res, std::vector<uint64_t>& ops_at, Take take) {
+  const char* const who = "herro_align_overlaps";
+  if (const int rc = check_records(ctx, who, n, in)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const uint64_t budget = scratch_budget("HERRO_ALIGN_SCRATCH_MB");
+  std::vector<herro::AlignIn> recs(n);
+  res.resize(n);
+  ops_at.assign(n, 0);
+  // chunks: consecutive records whose scratch fits the budget (a record larger than the budget runs alone)
+  uint64_t max_scr = 0, max_dense = 0;
+  std::vector<uint32_t> cut{0};
+  {
+    uint64_t acc = 0, dn = 0;
+    for (uint32_t r = 0; r < n; r++) {
+      const uint32_t qn = in[r].qend - in[r].qstart, tm = in[r].tend - in[r].tstart;
+      const uint64_t need = herro::align_scratch_bytes(qn, tm);
+      if (acc && acc + need > budget) { cut.push_back(r); acc = 0; dn = 0; }
+      recs[r] = herro::AlignIn{ctx->h_word_off[in[r].tid], ctx->h_word_off[in[r].qid], acc, in[r].tstart, tm, in[r].qstart, qn, in[r].strand, 0};
+      acc += need;
+      dn += (uint64_t)qn + tm + 1;
+      max_scr = std::max(max_scr, acc);
+      max_dense = std::max(max_dense, dn);
+    }
+    if (cut.back() != n) cut.push_back(n);
+  }
+  herro::Bufs B;
+  uint8_t* d_scr = nullptr;
+  herro::AlignIn* d_in = nullptr;
+  herro::AlignOut* d_out = nullptr;
+  uint32_t *d_dense = nullptr, *d_count = nullptr;
+  if (n) {
+    FRONT_TRY(ctx, who, "scratch", B.bytes(&d_scr, std::max<uint64_t>(max_scr, 256)));
+    FRONT_TRY(ctx, who, "records", B.bytes(&d_in, sizeof(herro::AlignIn) * n));
+    FRONT_TRY(ctx, who, "results", B.bytes(&d_out, sizeof(herro::AlignOut) * n));
+    FRONT_TRY(ctx, who, "ops", B.bytes(&d_dense, 4 * std::max<uint64_t>(max_dense, 1)));
+    FRONT_TRY(ctx, who, "counter", B.bytes(&d_count, 4));
+    FRONT_TRY(ctx, who, "record upload", hipMemcpyAsync(d_in, recs.data(), sizeof(herro::AlignIn) * n, hipMemcpyHostToDevice, ctx->stream));
+  }
+  for (size_t c = 0; c + 1 < cut.size(); c++) {
+    const uint32_t r0 = cut[c], r1 = cut[c + 1];
+    FRONT_TRY(ctx, who, "counter reset", hipMemsetAsync(d_count, 0, 4, ctx->stream));
+    herro::launch_align(ctx->d_words, d_in + r0, d_out + r0, d_scr, d_dense, d_count, r1 - r0, ctx->stream);
+    FRONT_TRY(ctx, who, "k_align launch", hipGetLastError());
+    uint32_t total = 0;
+    FRONT_TRY(ctx, who, "count", hipMemcpyAsync(&total, d_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+    FRONT_TRY(ctx, who, "results", hipMemcpyAsync(res.data() + r0, d_out + r0, sizeof(herro::AlignOut) * (r1 - r0), hipMemcpyDeviceToHost, ctx->stream));
+    FRONT_TRY(ctx, who, "k_align", hipStreamSynchronize(ctx->stream));
+    uint64_t at = 0;
+    FRONT_TRY(ctx, who, "ops", take(total, d_dense, r1, at));
+    for (uint32_t r = r0; r < r1; r++) ops_at[r] = at + res[r].ops_off;
+  }
+  FRONT_TRY(ctx, who, "ops", hipStreamSynchronize(ctx->stream));   // (a device-resident store: its last copy has landed)
+  return HERRO_OK;
+}
+
+int overlap_params(herro_ctx* ctx, const herro_overlap_params* in, herro::OvlParams& P) {
+  const herro_overlap_params z{};
+  const herro_overlap_params& p = in ? *in : z;
+  P.k = p.k ? p.k : 25;
+  P.w = p.w ? p.w : 17;
+  P.max_occ = p.max_occ ? p.max_occ : 128;
+  P.bandwidth = p.bandwidth ? p.bandwidth : 150;
+  P.max_gap = p.max_gap ? p.max_gap : 5000;
+  P.min_score = p.min_score ? p.min_score : 2500;
+  P.min_anchors = p.min_anchors ? p.min_anchors : 3;
+  if (P.k < 5 || P.k > 31 || P.w > 64) {
+    ctx->err = "overlap parameters: 5 <= k <= 31 and 1 <= w <= 64";
+    return HERRO_E_INVALID;
+  }
+  return HERRO_OK;
+}
+
+int overlap_rc(herro_ctx* ctx, int rc, const std::string& msg) {
+  if (rc == herro::OVL_OK) return HERRO_OK;
+  ctx->err = msg;
+  return rc == herro::OVL_UNSUPPORTED ? HERRO_E_UNSUPPORTED : HERRO_E_NO_DEVICE;
+}
+}  // namespace
+
+int aligned_dev_fetch(const herro_aligned_dev* a, uint64_t lo, uint64_t hi, std::vector<uint32_t>& v) {
+  v.resize(hi - lo);
+  if (hi == lo) return HERRO_OK;
+  if (a->host_only) { std::memcpy(v.data(), a->h_ops.data() + lo, (hi - lo) * 4); return HERRO_OK; }
+  if (hipSetDevice(a->device) != hipSuccess || hipMemcpy(v.data(), a->d_ops + lo, (hi - lo) * 4, hipMemcpyDeviceToHost) != hipSuccess) return HERRO_E_NO_DEVICE;
+  return HERRO_OK;
+}
+
+void ops_text_block(herro_ctx* ctx, const uint32_t* ops, const uint64_t* at, const uint32_t* n_ops, uint64_t r0, uint64_t r1, herro_alignment* alns,
+                    std::string& text) {
+  std::vector<uint64_t> toff(r1 + 1, 0);
+  for (uint64_t r = r0; r < r1; r++) toff[r + 1] = toff[r] + ops_text_bytes(ops + at[r], n_ops[r]);
+  text.assign(toff[r1] + 1, '\0');
+  host_pool(ctx).run((uint32_t)((r1 - r0 + 63) / 64), [&](uint32_t b) {
+    for (uint64_t r = r0 + (uint64_t)b * 64; r < std::min(r1, r0 + (uint64_t)(b + 1) * 64); r++) {
+      ops_text(ops + at[r], n_ops[r], &text[toff[r]]);
+      alns[r].cigar = reinterpret_cast<const uint8_t*>(text.data() + toff[r]);
+      alns[r].cigar_len = (uint32_t)(toff[r + 1] - toff[r]);
+    }
+  });
+}
+
+extern "C" {
+
+// ---- base-level alignment of coordinate-only overlaps (align_dev.hip) ------------------------------------------------
+// The step `herro inference` hands to `minimap2 -cx ava-ont` when it is not given --read-alns (mm2.rs:15-30), followed by
+// fix_cigar (aligners.rs:138-250): records in chunks that fit HERRO_ALIGN_SCRATCH_MB of traceback scratch, one kernel per
+// chunk on the context's stream, the ops back to the host and formatted into one text block there.
+struct herro_aligned {
+  std::vector<herro_alignment> alns;
+  std::vector<int32_t> scores;
+  std::string text;
+  uint32_t failed = 0;
+};
+
+int herro_align_overlaps(herro_ctx* ctx, uint32_t n, const herro_alignment* in, herro_aligned** out) {
+  if (!ctx || !out || (n && !in)) return HERRO_E_INVALID;
+  *out = nullptr;
+  std::vector<herro::AlignOut> res;
+  std::vector<uint32_t> ops;            // every record's final ops, record order
+  std::vector<uint64_t> ops_at;
+  const int rc = align_chunks(ctx, n, in, res, ops_at, [&](uint32_t total, const uint32_t* d_dense, uint32_t, uint64_t& at) {
+    at = ops.size();
+    ops.resize(at + total);
+    return total ? hipMemcpy(ops.data() + at, d_dense, 4ull * total, hipMemcpyDeviceToHost) : hipSuccess;
+  });
+  if (rc != HERRO_OK) return rc;
+  auto* h = new herro_aligned();
+  h->alns.assign(in, in + n);
+  h->scores.resize(n);
+  std::vector<uint32_t> n_ops(n);
+  for (uint32_t r = 0; r < n; r++) fold_result(res[r], h->alns[r], h->scores[r], n_ops[r], h->failed);
+  ops_text_block(ctx, ops.data(), ops_at.data(), n_ops.data(), 0, n, h->alns.data(), h->text);
+  *out = h;
+  return HERRO_OK;
+}
+
+const herro_alignment* herro_aligned_alignments(const herro_aligned* a) { return a ? a->alns.data() : nullptr; }
+const int32_t* herro_aligned_scores(const herro_aligned* a) { return a ? a->scores.data() : nullptr; }
+uint32_t herro_aligned_failed(const herro_aligned* a) { return a ? a->failed : 0; }
+void herro_aligned_free(herro_aligned* a) { delete a; }
+
+// ---- extension of coordinate-only overlaps to the read ends (k_extend in align_dev.hip) ----------------------------------------
+// Two sides per record, one wave each; the host turns the four flank lengths into coordinates.  Records go through in slices of 2^20, so the side
+// descriptors and results (72 B per side) stay small whatever n is.
+struct herro_extended {
+  std::vector<herro_alignment> alns;   // extended coordinates; cigar = NULL, cigar_len = 0
+  std::vector<uint32_t> ext;           // [n][4]: t_left, q_left, t_right, q_right
+  std::vector<int32_t> scores;         // [n][2]: left, right
+};
+
+int herro_extend_overlaps(herro_ctx* ctx, uint32_t n, const herro_alignment* in, const herro_extend_params* params, herro_extended** out) {
+  if (!ctx || !out || (n && !in)) return HERRO_E_INVALID;
+  *out = nullptr;
+  const char* const who = "herro_extend_overlaps";
+  const uint32_t zdrop = params && params->zdrop ? params->zdrop : herro::EXTEND_ZDROP;
+  const uint32_t max_ext = params && params->max_ext ? params->max_ext : herro::EXTEND_MAX_EXT;
+  if (max_ext > herro::EXTEND_MAX_EXT_LIMIT) { ctx->err = "herro_extend_overlaps: max_ext must be at most 2^20"; return HERRO_E_INVALID; }
+  if (const int rc = check_records(ctx, who, n, in)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::unique_ptr<herro_extended> h(new herro_extended());
+  h->alns.assign(in, in + n);
+  h->ext.assign((size_t)n * 4, 0);
+  h->scores.assign((size_t)n * 2, 0);
+  const uint32_t cap = std::min(n, SLICE);
+  std::vector<herro::ExtIn> sides((size_t)cap * 2);
+  std::vector<herro::ExtOut> res((size_t)cap * 2);
+  herro::Bufs B;
+  herro::ExtIn* d_in = nullptr;
+  herro::ExtOut* d_out = nullptr;
+  if (n) FRONT_TRY(ctx, who, "sides", B.bytes(&d_in, sizeof(herro::ExtIn) * sides.size()));
+  if (n) FRONT_TRY(ctx, who, "results", B.bytes(&d_out, sizeof(herro::ExtOut) * res.size()));
+  for (uint32_t r0 = 0; r0 < n; r0 += SLICE) {
+    const uint32_t cnt = std::min(SLICE, n - r0);
+    for (uint32_t x = 0; x < cnt; x++) {
+      const herro_alignment& a = in[r0 + x];
+      const uint64_t tw = ctx->h_word_off[a.tid], qw = ctx->h_word_off[a.qid];
+      const uint32_t t_below = a.tstart, t_above = ctx->read_len[a.tid] - a.tend;
+      const uint32_t q_below = a.qstart, q_above = ctx->read_len[a.qid] - a.qend;
+      // left: the target below tstart read downwards; the oriented query in front of the span read backwards — the forward bases below qstart read
+      // downwards (strand 0) or those from qend upwards (strand 1), complemented like the target's (T rev = 1, Q rev = !strand: the same equalities)
+      const uint32_t ml = std::min(t_below, max_ext), nl = std::min(a.strand ? q_above : q_below, max_ext);
+      sides[2 * x] = herro::ExtIn{tw, qw, a.tstart - ml, ml, a.strand ? a.qend : a.qstart - nl, nl, 1u, a.strand ? 0u : 1u};
+      // right: the target from tend upwards; the oriented query behind the span
+      const uint32_t mr = std::min(t_above, max_ext), nr = std::min(a.strand ? q_below : q_above, max_ext);
+      sides[2 * x + 1] = herro::ExtIn{tw, qw, a.tend, mr, a.strand ? a.qstart - nr : a.qend, nr, 0u, a.strand};
+    }
+    FRONT_TRY(ctx, who, "side upload", hipMemcpyAsync(d_in, sides.data(), sizeof(herro::ExtIn) * 2 * cnt, hipMemcpyHostToDevice, ctx->stream));
+    herro::launch_extend(ctx->d_words, d_in, d_out, zdrop, 2 * cnt, ctx->stream);
+    FRONT_TRY(ctx, who, "k_extend launch", hipGetLastError());
+    FRONT_TRY(ctx, who, "results", hipMemcpyAsync(res.data(), d_out, sizeof(herro::ExtOut) * 2 * cnt, hipMemcpyDeviceToHost, ctx->stream));
+    FRONT_TRY(ctx, who, "k_extend", hipStreamSynchronize(ctx->stream));
+    for (uint32_t x = 0; x < cnt; x++) {
+      herro_alignment& a = h->alns[r0 + x];
+      const herro::ExtOut &l = res[2 * x], &r = res[2 * x + 1];
+      a.cigar = nullptr; a.cigar_len = 0;
+      a.tstart -= l.j; a.tend += r.j;
+      if (a.strand == 0) { a.qstart -= l.i; a.qend += r.i; }
+      else { a.qend += l.i; a.qstart -= r.i; }
+      uint32_t* ex = &h->ext[(size_t)(r0 + x) * 4];
+      ex[0] = l.j; ex[1] = l.i; ex[2] = r.j; ex[3] = r.i;
+      h->scores[(size_t)(r0 + x) * 2] = l.score;
+      h->scores[(size_t)(r0 + x) * 2 + 1] = r.score;
+    }
+  }
+  *out = h.release();
+  return HERRO_OK;
+}
+
+uint32_t herro_extended_n(const herro_extended* x) { return x ? (uint32_t)x->alns.size() : 0; }
+const herro_alignment* herro_extended_alignments(const herro_extended* x) { return x ? x->alns.data() : nullptr; }
+const uint32_t* herro_extended_ext(const herro_extended* x) { return x ? x->ext.data() : nullptr; }
+const int32_t* herro_extended_scores(const herro_extended* x) { return x ? x->scores.data() : nullptr; }
+void herro_extended_free(herro_extended* x) { delete x; }
+
+// ---- device-resident hand-off: the aligner's ops stay where k_align wrote them, the job builder reads them there ----------------
+int herro_align_overlaps_dev(herro_ctx* ctx, uint32_t n, const herro_alignment* in, herro_aligned_dev** out) {
+  if (!ctx || !out || (n && !in)) return HERRO_E_INVALID;
+  *out = nullptr;
+  AlignedDevPtr h = new_aligned_dev(ctx);
+  std::vector<herro::AlignOut> res;
+  // The store grows by chunks: the first chunk's ops per record, projected over all records plus an eighth, sizes it; a chunk that does not fit moves it
+  // to twice the projection (device to device, behind the chunk's synchronisation: nothing reads the old block any more).
+  const int rc = align_chunks(ctx, n, in, res, h->op_off, [&](uint32_t total, const uint32_t* d_dense, uint32_t r_done, uint64_t& at) {
+    at = h->used;
+    if (!total) return hipSuccess;
+    hipError_t e;
+    if (h->used + total > h->cap) {
+      const uint64_t proj = (h->used + total) * (uint64_t)n / std::max(r_done, 1u);
+      const uint64_t cap = std::max<uint64_t>(h->used + total, (h->cap ? 2 : 1) * (proj + proj / 8)) + 1024;
+      uint32_t* const old = h->d_ops;
+      uint32_t* d = nullptr;
+      if ((e = hipMalloc((void**)&d, cap * 4)) != hipSuccess) return e;
+      h->d_ops = d; h->cap = cap;   // (the handle's from here on, whatever follows)
+      e = h->used ? hipMemcpyAsync(d, old, h->used * 4, hipMemcpyDeviceToDevice, ctx->stream) : hipSuccess;
+      if (old) {
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        (void)hipFree(old);
+      }
+      if (e != hipSuccess) return e;
+    }
+    // (stream order: the next chunk's kernel, which overwrites d_dense, queues behind this copy)
+    if ((e = hipMemcpyAsync(h->d_ops + h->used, d_dense, 4ull * total, hipMemcpyDeviceToDevice, ctx->stream)) != hipSuccess) return e;
+    h->used += total;
+    return hipSuccess;
+  });
+  if (rc != HERRO_OK) return rc;
+  h->alns.assign(in, in + n);
+  h->scores.resize(n);
+  h->n_ops.resize(n);
+  for (uint32_t r = 0; r < n; r++) {
+    h->alns[r].cigar = nullptr; h->alns[r].cigar_len = 0;
+    fold_result(res[r], h->alns[r], h->scores[r], h->n_ops[r], h->failed);
+  }
+  *out = h.release();
+  return HERRO_OK;
+}
+
+int herro_aligned_dev_from_ops(herro_ctx* ctx, uint32_t n, const herro_alignment* alns, const uint64_t* op_off, const uint32_t* ops, herro_aligned_dev** out) {
+  if (!ctx || !out || !op_off || (n && !alns)) return HERRO_E_INVALID;
+  *out = nullptr;
+  for (uint32_t r = 0; r < n; r++)
+    if (op_off[r + 1] < op_off[r] || op_off[r + 1] - op_off[r] > 0xffffffffull) {
+      ctx->err = "herro_aligned_dev_from_ops: record " + std::to_string(r) + ": op_off must ascend";
+      return HERRO_E_INVALID;
+    }
+  const uint64_t lo = op_off[0], total = op_off[n] - lo;
+  if (total && !ops) return HERRO_E_INVALID;
+  AlignedDevPtr h = new_aligned_dev(ctx);
+  h->alns.assign(alns, alns + n);
+  h->scores.assign(n, 0);
+  h->n_ops.resize(n);
+  h->op_off.resize(n);
+  for (uint32_t r = 0; r < n; r++) {
+    h->alns[r].cigar = nullptr; h->alns[r].cigar_len = 0;
+    h->n_ops[r] = (uint32_t)(op_off[r + 1] - op_off[r]);
+    h->op_off[r] = op_off[r] - lo;
+    if (!h->n_ops[r]) { h->scores[r] = INT32_MIN; h->failed++; }
+  }
+  h->used = h->cap = total;
+  if (ctx->host_only) {
+    h->h_ops.assign(ops + lo, ops + lo + total);
+  } else if (total) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMalloc((void**)&h->d_ops, total * 4));
+    HIP_TRY(ctx, hipMemcpy(h->d_ops, ops + lo, total * 4, hipMemcpyHostToDevice));
+  }
+  *out = h.release();
+  return HERRO_OK;
+}
+
+// ---- mirrored records (k_mirror in align_dev.hip): every record's alignment the other way round, without a second sweep ----------
+// The new handle's store is src's ops (device to device) and behind them one reservation per mirror — the prefix sum of src's n_ops, since a mirror never
+// has more ops than its source.  Records go through in slices of 2^20, one synchronisation per slice to fetch the results.
+int herro_aligned_dev_mirror(herro_ctx* ctx, const herro_aligned_dev* src, herro_aligned_dev** out) {
+  if (!ctx || !src || !out) return HERRO_E_INVALID;
+  *out = nullptr;
+  const char* const who = "herro_aligned_dev_mirror";
+  if (src->ctx != ctx) { ctx->err = "herro_aligned_dev_mirror: the handle belongs to another context"; return HERRO_E_INVALID; }
+  if (src->host_only) { ctx->err = "herro_aligned_dev_mirror: the context has no device"; return HERRO_E_NO_DEVICE; }
+  if (src->alns.size() > 0x7fffffffull) { ctx->err = "herro_aligned_dev_mirror: more than 2^31 - 1 records"; return HERRO_E_INVALID; }
+  const uint32_t n = (uint32_t)src->alns.size();
+  if (const int rc = check_records(ctx, who, n, src->alns.data())) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  AlignedDevPtr h = new_aligned_dev(ctx);
+  h->alns = src->alns; h->scores = src->scores; h->n_ops = src->n_ops; h->op_off = src->op_off;
+  h->failed = src->failed;
+  h->alns.resize(2 * (size_t)n); h->scores.resize(2 * (size_t)n, INT32_MIN); h->n_ops.resize(2 * (size_t)n, 0); h->op_off.resize(2 * (size_t)n, 0);
+  uint64_t total = src->used;
+  for (uint32_t r = 0; r < n; r++) {
+    const herro_alignment& s = src->alns[r];
+    herro_alignment& a = h->alns[n + r];
+    a = herro_alignment{};
+    a.qid = s.tid; a.qlen = s.tlen; a.qstart = s.tstart; a.qend = s.tend; a.strand = s.strand;
+    a.tid = s.qid; a.tlen = s.qlen; a.tstart = s.qstart; a.tend = s.qend;
+    h->op_off[n + r] = total;
+    total += src->n_ops[r];
+  }
+  h->used = h->cap = total;
+  const uint32_t cap = std::min(n, SLICE);
+  std::vector<herro::MirrorIn> recs(cap);
+  std::vector<herro::AlignOut> res(cap);
+  herro::Bufs B;
+  herro::MirrorIn* d_in = nullptr;
+  herro::AlignOut* d_out = nullptr;
+  if (total) FRONT_TRY(ctx, who, "op store", hipMalloc((void**)&h->d_ops, total * 4));
+  if (src->used) FRONT_TRY(ctx, who, "op copy", hipMemcpyAsync(h->d_ops, src->d_ops, src->used * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  if (n) FRONT_TRY(ctx, who, "records", B.bytes(&d_in, sizeof(herro::MirrorIn) * cap));
+  if (n) FRONT_TRY(ctx, who, "results", B.bytes(&d_out, sizeof(herro::AlignOut) * cap));
+  for (uint32_t r0 = 0; r0 < n; r0 += SLICE) {
+    const uint32_t cnt = std::min(SLICE, n - r0);
+    for (uint32_t x = 0; x < cnt; x++) {
+      const uint32_t r = r0 + x;
+      const herro_alignment& s = src->alns[r];
+      // the mirror's target is the source's query read, forward; its query the source's target read, reversed and complemented on strand 1
+      recs[x] = herro::MirrorIn{ctx->h_word_off[s.qid], ctx->h_word_off[s.tid], src->op_off[r], h->op_off[n + r], s.qstart, s.qend - s.qstart,
+                                s.tstart, s.tend - s.tstart, s.strand, src->n_ops[r], src->n_ops[r] ? src->scores[r] : 0, 0u};
+    }
+    FRONT_TRY(ctx, who, "record upload", hipMemcpyAsync(d_in, recs.data(), sizeof(herro::MirrorIn) * cnt, hipMemcpyHostToDevice, ctx->stream));
+    herro::launch_mirror(ctx->d_words, d_in, d_out, h->d_ops, cnt, ctx->stream);
+    FRONT_TRY(ctx, who, "k_mirror launch", hipGetLastError());
+    FRONT_TRY(ctx, who, "results", hipMemcpyAsync(res.data(), d_out, sizeof(herro::AlignOut) * cnt, hipMemcpyDeviceToHost, ctx->stream));
+    FRONT_TRY(ctx, who, "k_mirror", hipStreamSynchronize(ctx->stream));
+    // (a failed mirror: n_ops 0, INT32_MIN and the swapped coordinates, untrimmed)
+    for (uint32_t x = 0; x < cnt; x++) fold_result(res[x], h->alns[n + r0 + x], h->scores[n + r0 + x], h->n_ops[n + r0 + x], h->failed);
+  }
+  FRONT_TRY(ctx, who, "op copy", hipStreamSynchronize(ctx->stream));   // (n = 0 with ops in src's store: the copy has landed)
+  *out = h.release();
+  return HERRO_OK;
+}
+
+uint32_t herro_aligned_dev_n(const herro_aligned_dev* a) { return a ? (uint32_t)a->alns.size() : 0; }
+const herro_alignment* herro_aligned_dev_alignments(const herro_aligned_dev* a) { return a ? a->alns.data() : nullptr; }
+const int32_t* herro_aligned_dev_scores(const herro_aligned_dev* a) { return a ? a->scores.data() : nullptr; }
+const uint32_t* herro_aligned_dev_n_ops(const herro_aligned_dev* a) { return a ? a->n_ops.data() : nullptr; }
+uint32_t herro_aligned_dev_failed(const herro_aligned_dev* a) { return a ? a->failed : 0; }
+
+void herro_aligned_dev_free(herro_aligned_dev* a) {
+  if (!a) return;
+  if (a->d_ops && hipSetDevice(a->device) == hipSuccess) (void)hipFree(a->d_ops);   // (hipFree waits for the device: no kernel is still reading the store)
+  delete a;
+}
+
+int64_t herro_aligned_dev_cigar(const herro_aligned_dev* a, uint32_t r, char* out, uint64_t cap) {
+  if (!a || r >= a->alns.size()) return HERRO_E_INVALID;
+  std::vector<uint32_t> v;
+  const int rc = aligned_dev_fetch(a, a->op_off[r], a->op_off[r] + a->n_ops[r], v);
+  if (rc != HERRO_OK) return rc;
+  const uint64_t need = ops_text_bytes(v.data(), (uint32_t)v.size());
+  if (out && need <= cap) ops_text(v.data(), (uint32_t)v.size(), out);
+  return (int64_t)need;
+}
+
+// ---- overlap finding (overlap_dev.hip) ---------------------------------------------------------------------------------------
+// The seeding and chaining the reference leaves to `minimap2 -x ava-ont` (mm2.rs:15-30): the device returns the kept chains per
+// (t, q, strand); the strand choice, the dual records and their grouping by target are a few lines of host code over them.
+struct herro_overlaps {
+  std::vector<uint32_t> rids;
+  std::vector<uint64_t> aln_off;
+  std::vector<herro_alignment> alns;
+  std::vector<int32_t> scores;
+};
+
+int herro_find_overlaps(herro_ctx* ctx, const herro_overlap_params* params, herro_overlaps** out) {
+  if (!ctx || !out) return HERRO_E_INVALID;
+  *out = nullptr;
+  herro::OvlParams P;
+  if (int rc = overlap_params(ctx, params, P)) return rc;
+  if (int rc = device_ready(ctx, "herro_find_overlaps")) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::vector<herro::OvlPair> chains;
+  herro::OvlStats stats;
+  std::string msg;
+  if (int rc = overlap_rc(ctx, herro::ovl_find(ovl_store(ctx), P, scratch_budget("HERRO_OVL_SCRATCH_MB"), ctx->stream, chains, stats, msg), msg)) return rc;
+  if (const char* e = getenv("HERRO_OVL_STATS"))   // tools/overlaprate.py: the sizes of the stages, one line on stderr
+    if (atoi(e)) fprintf(stderr, "OVL kmers=%llu minimizers=%llu anchors=%llu groups=%llu chained=%llu chunks=%llu\n", (unsigned long long)stats.kmers,
+                         (unsigned long long)stats.minimizers, (unsigned long long)stats.anchors, (unsigned long long)stats.groups,
+                         (unsigned long long)stats.chained, (unsigned long long)stats.chunks);
+  // one overlap per pair: chains arrive in ascending (t, q, rel), so the two strands of a pair are neighbours
+  std::vector<herro::OvlPair> best;
+  for (const herro::OvlPair& c : chains) {
+    if (!best.empty() && best.back().t == c.t && best.back().q == c.q) {
+      if (c.score > best.back().score) best.back() = c;
+    } else {
+      best.push_back(c);
+    }
+  }
+  struct Rec { herro_alignment a; int32_t score; };
+  std::vector<Rec> recs;
+  recs.reserve(best.size() * 2);
+  for (const herro::OvlPair& c : best) {
+    const uint32_t tl = ctx->read_len[c.t], ql = ctx->read_len[c.q];
+    recs.push_back(Rec{herro_alignment{c.q, ql, c.qstart, c.qend, c.rel, c.t, tl, c.tstart, c.tend, 0, nullptr}, c.score});
+    recs.push_back(Rec{herro_alignment{c.t, tl, c.tstart, c.tend, c.rel, c.q, ql, c.qstart, c.qend, 0, nullptr}, c.score});   // the dual
+  }
+  std::sort(recs.begin(), recs.end(), [](const Rec& x, const Rec& y) { return x.a.tid != y.a.tid ? x.a.tid < y.a.tid : x.a.qid < y.a.qid; });
+  auto* h = new herro_overlaps();
+  h->alns.reserve(recs.size());
+  h->scores.reserve(recs.size());
+  for (const Rec& r : recs) {
+    if (h->rids.empty() || h->rids.back() != r.a.tid) { h->rids.push_back(r.a.tid); h->aln_off.push_back(h->alns.size()); }
+    h->alns.push_back(r.a);
+    h->scores.push_back(r.score);
+  }
+  h->aln_off.push_back(h->alns.size());
+  *out = h;
+  return HERRO_OK;
+}
+
+uint32_t herro_overlaps_n(const herro_overlaps* o) { return o ? (uint32_t)o->alns.size() : 0; }
+uint32_t herro_overlaps_n_targets(const herro_overlaps* o) { return o ? (uint32_t)o->rids.size() : 0; }
+const uint32_t* herro_overlaps_target_ids(const herro_overlaps* o) { return o ? o->rids.data() : nullptr; }
+const uint64_t* herro_overlaps_aln_off(const herro_overlaps* o) { return o ? o->aln_off.data() : nullptr; }
+const herro_alignment* herro_overlaps_alignments(const herro_overlaps* o) { return o ? o->alns.data() : nullptr; }
+const int32_t* herro_overlaps_scores(const herro_overlaps* o) { return o ? o->scores.data() : nullptr; }
+void herro_overlaps_free(herro_overlaps* o) { delete o; }
+
+int64_t herro_debug_sketch(herro_ctx* ctx, const herro_overlap_params* params, uint64_t* hash, uint32_t* rid, uint32_t* pos,
+                           uint8_t* strand, uint64_t cap) {
+  if (!ctx) return HERRO_E_INVALID;
+  herro::OvlParams P;
+  if (int rc = overlap_params(ctx, params, P)) return rc;
+  if (int rc = device_ready(ctx, "herro_debug_sketch")) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::vector<uint64_t> h, m;
+  std::string msg;
+  if (int rc = overlap_rc(ctx, herro::ovl_sketch(ovl_store(ctx), P, ctx->stream, h, m, msg), msg)) return rc;
+  if (h.size() <= cap && hash && rid && pos && strand) {
+    for (size_t i = 0; i < h.size(); i++) {
+      hash[i] = h[i];
+      rid[i] = (uint32_t)(m[i] >> 32);
+      pos[i] = ((uint32_t)m[i]) >> 1;
+      strand[i] = (uint8_t)(m[i] & 1u);
+    }
+  }
+  return (int64_t)h.size();
+}
+
+}  // extern "C"

@@ -19,6 +19,8 @@
 #include <vector>
 
 #include "../../include/herro_amd.h"
+#include "api_ctx.h"
+#include "aligned_dev.h"
 #include "host_cpus.h"
 #include "job_dev.h"
 #include "model_dev.h"
@@ -42,31 +44,6 @@ struct ProfSpan {
   ~ProfSpan() { if (level() >= 2) { const double t1 = now_ms(); fprintf(stderr, "TL %p %-14s %.3f %.3f\n", who, name, fmod(t0, 1e6), t1 - t0); } }
 };
 
-// Last-error text of a context.  Job creation may run on a second thread (herro_amd.h, "Threading"), so assignment is
-// serialised; the text read back is the most recent failure of either thread, kept in a buffer that only assignment replaces.
-struct ErrSlot {
-  std::mutex mu;
-  std::string s;
-  ErrSlot& operator=(const std::string& v) { std::lock_guard<std::mutex> lk(mu); s = v; return *this; }
-  ErrSlot& operator=(const char* v) { std::lock_guard<std::mutex> lk(mu); s = v; return *this; }
-  // the text handed out is a per-thread copy: an assignment by another thread (job creation may run beside the execution
-  // calls) cannot pull the buffer away under the reader
-  const char* c_str() const {
-    thread_local std::string snap;
-    { std::lock_guard<std::mutex> lk(const_cast<std::mutex&>(mu)); snap = s; }
-    return snap.c_str();
-  }
-};
-
-#define HIP_TRY(ctx, expr)                                                              \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) {                                                             \
-      (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(_e);                   \
-      return HERRO_E_NO_DEVICE;                                                         \
-    }                                                                                   \
-  } while (0)
-
 template <typename T>
 T* dev_alloc_copy(const std::vector<T>& v, hipStream_t st, hipError_t& err) {
   T* p = nullptr;
@@ -77,128 +54,6 @@ T* dev_alloc_copy(const std::vector<T>& v, hipStream_t st, hipError_t& err) {
   return p;
 }
 }  // namespace
-
-// ---- host thread pool, one per context (created on first use).  herro_job_create used to start and join
-// min(cores, 64) std::threads twice per call; on a 256-core box that alone was ~3 of its 15 ms per 4096 windows.
-struct HostPool {
-  std::vector<std::thread> th;
-  std::mutex m;
-  std::condition_variable cv, done_cv;
-  const std::function<void(uint32_t)>* fn = nullptr;
-  std::atomic<uint32_t> next{0};
-  uint32_t n = 0, active = 0;
-  uint64_t gen = 0;
-  bool stop = false;
-  explicit HostPool(uint32_t workers) {
-    for (uint32_t i = 0; i < workers; i++) th.emplace_back([this] { loop(); });
-  }
-  ~HostPool() {
-    { std::lock_guard<std::mutex> lk(m); stop = true; }
-    cv.notify_all();
-    for (auto& t : th) t.join();
-  }
-  void work() {
-    for (;;) {
-      const uint32_t i = next.fetch_add(1, std::memory_order_relaxed);
-      if (i >= n) break;
-      (*fn)(i);
-    }
-  }
-  void loop() {
-    uint64_t seen = 0;
-    for (;;) {
-      {
-        std::unique_lock<std::mutex> lk(m);
-        cv.wait(lk, [&] { return stop || gen != seen; });
-        if (stop) return;
-        seen = gen;
-      }
-      work();
-      std::lock_guard<std::mutex> lk(m);
-      if (--active == 0) done_cv.notify_one();
-    }
-  }
-  // fn(i) for i in [0, count), on the workers and the calling thread; returns when all are done.  One run at a time: a second
-  // caller (herro_set_reads beside a herro_job_create of another thread on the same context) waits its turn.
-  std::mutex run_mu;
-  void run(uint32_t count, const std::function<void(uint32_t)>& f) {
-    if (count == 0) return;
-    if (th.empty() || count == 1) { for (uint32_t i = 0; i < count; i++) f(i); return; }
-    std::lock_guard<std::mutex> one_run(run_mu);
-    {
-      std::lock_guard<std::mutex> lk(m);
-      fn = &f; n = count; next.store(0); active = (uint32_t)th.size(); gen++;
-    }
-    cv.notify_all();
-    work();
-    std::unique_lock<std::mutex> lk(m);
-    done_cv.wait(lk, [&] { return active == 0; });
-  }
-};
-
-struct Arena { void* p = nullptr; size_t cap = 0; };
-
-struct herro_ctx {
-  int device = 0;
-  uint32_t n_cu = 256;   // compute units of the device: one round of the fused stack (plan_tiles)
-  hipStream_t own_stream = nullptr, stream = nullptr;
-  ErrSlot err;
-  // read store
-  uint32_t n_reads = 0;
-  std::vector<uint32_t> read_len, name_class;
-  std::vector<uint64_t> h_word_off, h_qual_off;  // host copies: overlap descriptors carry them (saves the kernel a dependent load)
-  bool host_only = false;  // herro_debug_host_ctx: no device; herro_job_create stops after the host half
-  // lean: herro_job_featurize derives informative rows, votes and receptive fields without writing the token planes (k_rows); the planes are
-  // built when somebody asks for them.  HERRO_FEATURIZE_PLANES=1 (or herro_debug_set_featurize_planes): the planes path of rounds 3-4 (A/B, parity tests)
-  bool lean = [] { const char* e = getenv("HERRO_FEATURIZE_PLANES"); return !e || atoi(e) == 0; }();
-  bool tile_packing = ab_env("HERRO_TILE_PACK", 1) != 0;  // 0 (A/B builds): windows in batch order
-  uint64_t* d_words = nullptr;
-  uint32_t* d_p0 = nullptr;
-  uint32_t* d_p1 = nullptr;
-  uint64_t* d_word_off = nullptr;
-  uint8_t* d_qual = nullptr;
-  uint64_t* d_qual_off = nullptr;
-  double* d_ln = nullptr;
-  uint32_t ln_n = 0;
-  uint64_t read_bytes = 0, qual_bytes = 0, n_words = 0;
-  // the device arrays of the read store belong to this owner: the contexts of one device can share ONE store (herro_share_reads);
-  // its memory is freed when the last context holding it lets go
-  std::shared_ptr<void> store_owner;
-  // model
-  bool has_model = false;
-  ModelDev M{};
-  std::vector<void*> model_allocs;
-  int precision = 1;
-  bool precision_set = false;   // herro_set_precision was called: herro_load_model keeps the caller's choice
-  bool debug_force_precision = false;   // herro_debug_force_precision: herro_set_precision skips the calibration gate (tests measure the modes a model's calibration refuses)
-  float wmax = 0.f;             // largest |weight| of the loaded model
-  float calib[9] = {-1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f};   // [mode]: max |logit difference| of f16 mode 4 .. 8 vs mode 0 (f32 MFMA) on the calibration batch (-1: not run)
-  std::string calib_note;
-  ModelScratch S{};
-  uint32_t scratch_cap = 0;
-  void* sib_kv = nullptr;       // sibling tiles of the f16 stack (ensure_sib): K / V exchange, flags + error word
-  void* sib_flag = nullptr;
-  uint32_t sib_cap = 0;
-  std::vector<void*> scratch_allocs;
-  KernelTimer timer;
-  // job memory: ONE device arena and ONE pinned host arena per job, recycled through these free lists (a job used to
-  // cost 36 hipMallocs + a hipHostMalloc, ~4 ms per 4096 windows, and its descriptors went up from pageable memory)
-  std::unique_ptr<HostPool> pool;
-  std::mutex arena_mu;
-  std::vector<Arena> free_scan, free_stage;            // device op array + staged CIGAR text of a job; pinned staging of one herro_job_create
-  hipStream_t prep_stream = nullptr;                   // CIGAR scan of the job being created: its own (high-priority) stream, so that it does not queue behind the pileup / model kernels of earlier jobs
-  hipEvent_t prep_ev = nullptr;
-  unsigned long long* d_prof = nullptr;                // HERRO_PROF_BUILD + HERRO_PROF=1: per-kernel phase cycles (job_dev.h PROF_MARK), printed by herro_destroy
-  bool dev_scan = true;                                // HERRO_HOST_SCAN=1: decode the text on the host instead (A/B, debugging)
-  bool dev_build = true;                               // windows and descriptors on the device behind the scan (build_dev.hip); herro_debug_set_host_build(ctx, 1): by the host from the cut records, as until round 5
-  std::vector<Arena> free_dev, free_pin, free_small;   // free_small: the buffers a job needs only once its counts are known (logits, batch descriptors)
-  std::atomic<uint32_t> live_jobs{0};   // herro_job_create may run on another thread than the context's execution calls
-  uint64_t reads_gen = 0;   // bumped by herro_set_reads: a job built on an older store refuses to run
-  uint32_t n_sib_retry = 0;        // model passes repeated without sibling tiles (sib_retry)
-  std::vector<herro_job*> sib_suspects;   // jobs whose last model pass launched sibling tiles and has not been seen clean yet (check_sib): a raised error word is theirs
-  std::atomic<int> n_pending{0};   // jobs of this context that are featurized and not yet inferred: > 0 when herro_job_featurize is called means the caller pipelines its jobs
-  std::atomic<int> create_code{0};   // HERRO_E_* of the last herro_job_create that returned NULL (herro_job_create_status)
-};
 
 struct BatchPlan {
   std::vector<uint32_t> wins;  // job window indices
@@ -302,7 +157,7 @@ struct herro_job {
 static int job_sync(herro_job* job);
 static int ensure_logits(herro_job* job, uint64_t rows);
 
-static HostPool& host_pool(herro_ctx* ctx) {
+HostPool& host_pool(herro_ctx* ctx) {
   if (!ctx->pool) {
     const uint32_t cpus = usable_cpus();
     const char* env = getenv("HERRO_HOST_THREADS");
@@ -3314,465 +3169,7 @@ int herro_job_stats(herro_job* job, uint64_t* out) {
   return HERRO_OK;
 }
 
-}  // extern "C"
-
-// ---- base-level alignment of coordinate-only overlaps (align_dev.hip) ------------------------------------------------
-// The step `herro inference` hands to `minimap2 -cx ava-ont` when it is not given --read-alns (mm2.rs:15-30), followed by
-// fix_cigar (aligners.rs:138-250): records in chunks that fit HERRO_ALIGN_SCRATCH_MB of traceback scratch, one kernel per
-// chunk on the context's stream, the ops back to the host and formatted into one text block there.
-struct herro_aligned {
-  std::vector<herro_alignment> alns;
-  std::vector<int32_t> scores;
-  std::string text;
-  uint32_t failed = 0;
-};
-
-// The same records with their ops left on the device (herro_align_overlaps_dev), or a caller's own binary CIGARs (herro_aligned_dev_from_ops).
-struct herro_aligned_dev {
-  herro_ctx* ctx = nullptr;
-  int device = 0;
-  bool host_only = false;              // a handle of herro_debug_host_ctx (from_ops only): the store is h_ops
-  std::vector<herro_alignment> alns;   // trimmed coordinates; cigar = NULL, cigar_len = 0
-  std::vector<int32_t> scores;
-  std::vector<uint32_t> n_ops;         // 0: failed
-  std::vector<uint64_t> op_off;        // first op of every record in the store
-  uint32_t failed = 0;
-  uint32_t* d_ops = nullptr;           // the op store: every record's ops, `len << 2 | type`
-  uint64_t used = 0, cap = 0;          // ... in ops
-  std::vector<uint32_t> h_ops;
-};
-
-namespace {
-uint32_t dec_digits(uint32_t v) { uint32_t k = 1; while (v >= 10) { v /= 10; k++; } return k; }
-// bytes of "<len><M|I|D>" per op
-uint64_t ops_text_bytes(const uint32_t* ops, uint32_t n) {
-  uint64_t b = 0;
-  for (uint32_t x = 0; x < n; x++) b += dec_digits(ops[x] >> 2) + 1;
-  return b;
-}
-char* ops_text(const uint32_t* ops, uint32_t n, char* p) {
-  for (uint32_t x = 0; x < n; x++) {
-    p += snprintf(p, 12, "%u", ops[x] >> 2);
-    *p++ = "MID?"[ops[x] & 3u];   // ('?': type 3 of a caller's own ops; herro_job_create refuses the letter)
-  }
-  return p;
-}
-// coordinates after fix_cigar dropped a leading / trailing indel
-void apply_trim(herro_alignment& a, const herro::AlignOut& o) {
-  a.tstart += o.tdrop0;
-  a.tend -= o.tdrop1;
-  if (a.strand == 0) { a.qstart += o.qdrop0; a.qend -= o.qdrop1; }
-  else { a.qend -= o.qdrop0; a.qstart += o.qdrop1; }
-}
-
-// Validation, chunking (HERRO_ALIGN_SCRATCH_MB) and the kernel runs of herro_align_overlaps and herro_align_overlaps_dev.  Behind every chunk the host
-// reads its op total and its AlignOut records and hands the chunk's dense ops, still on the device, to take(total, d_dense, r_done, at): it stores them and
-// says where (at: the chunk's first op in the caller's store; r_done: records aligned so far, this chunk's included).  ops_at[r]: record r's first op there.
-// What herro_align_overlaps[_dev] and herro_extend_overlaps (`who`) ask of a context and of coordinate-only records before anything runs.
-int check_records(herro_ctx* ctx, const char* who, uint32_t n, const herro_alignment* in) {
-  if (ctx->host_only) { ctx->err = std::string(who) + ": the context has no device"; return HERRO_E_NO_DEVICE; }
-  if (!ctx->d_words) { ctx->err = "herro_set_reads must be called first"; return HERRO_E_STATE; }
-  for (uint32_t r = 0; r < n; r++) {
-    const herro_alignment& a = in[r];
-    std::string why;
-    if (a.qid >= ctx->n_reads || a.tid >= ctx->n_reads) why = "read id outside the read store";
-    else if (a.qstart > a.qend || a.qend > ctx->read_len[a.qid]) why = "query coordinates outside the read";
-    else if (a.tstart > a.tend || a.tend > ctx->read_len[a.tid]) why = "target coordinates outside the read";
-    else if (a.strand > 1) why = "strand must be 0 or 1";
-    else if ((uint64_t)(a.qend - a.qstart) + (a.tend - a.tstart) > herro::ALIGN_MAX_CELLS) why = "overlap longer than 2^25 bases in all";
-    if (!why.empty()) {
-      ctx->err = std::string(who) + ": record " + std::to_string(r) + ": " + why;
-      return HERRO_E_INVALID;
-    }
-  }
-  return HERRO_OK;
-}
-
-template <class Take>
-int align_chunks(herro_ctx* ctx, uint32_t n, const herro_alignment* in, std::vector<herro::AlignOut>& res, std::vector<uint64_t>& ops_at, Take take) {
-  if (const int rc = check_records(ctx, "herro_align_overlaps", n, in)) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  uint64_t budget = 4096ull << 20;
-  if (const char* e = getenv("HERRO_ALIGN_SCRATCH_MB")) budget = (uint64_t)std::max(1ll, atoll(e)) << 20;
-  std::vector<herro::AlignIn> recs(n);
-  res.resize(n);
-  ops_at.assign(n, 0);
-  // chunks: consecutive records whose scratch fits the budget (a record larger than the budget runs alone)
-  uint64_t max_scr = 0, max_dense = 0;
-  std::vector<uint32_t> cut{0};
-  {
-    uint64_t acc = 0, dn = 0;
-    for (uint32_t r = 0; r < n; r++) {
-      const uint32_t qn = in[r].qend - in[r].qstart, tm = in[r].tend - in[r].tstart;
-      const uint64_t need = herro::align_scratch_bytes(qn, tm);
-      if (acc && acc + need > budget) { cut.push_back(r); acc = 0; dn = 0; }
-      recs[r] = herro::AlignIn{ctx->h_word_off[in[r].tid], ctx->h_word_off[in[r].qid], acc, in[r].tstart, tm, in[r].qstart, qn, in[r].strand, 0};
-      acc += need;
-      dn += (uint64_t)qn + tm + 1;
-      max_scr = std::max(max_scr, acc);
-      max_dense = std::max(max_dense, dn);
-    }
-    if (cut.back() != n) cut.push_back(n);
-  }
-  uint8_t* d_scr = nullptr;
-  herro::AlignIn* d_in = nullptr;
-  herro::AlignOut* d_out = nullptr;
-  uint32_t* d_dense = nullptr;
-  uint32_t* d_count = nullptr;
-  auto release = [&]() {
-    if (d_scr) (void)hipFree(d_scr);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (d_dense) (void)hipFree(d_dense);
-    if (d_count) (void)hipFree(d_count);
-  };
-  auto hip_fail = [&](hipError_t e, const char* what) {
-    ctx->err = std::string("herro_align_overlaps: ") + what + ": " + hipGetErrorString(e);
-    release();
-    return HERRO_E_NO_DEVICE;
-  };
-  hipError_t e = hipSuccess;
-  if (n) {
-    if ((e = hipMalloc((void**)&d_scr, std::max<uint64_t>(max_scr, 256))) != hipSuccess) return hip_fail(e, "scratch");
-    if ((e = hipMalloc((void**)&d_in, sizeof(herro::AlignIn) * n)) != hipSuccess) return hip_fail(e, "records");
-    if ((e = hipMalloc((void**)&d_out, sizeof(herro::AlignOut) * n)) != hipSuccess) return hip_fail(e, "results");
-    if ((e = hipMalloc((void**)&d_dense, 4 * std::max<uint64_t>(max_dense, 1))) != hipSuccess) return hip_fail(e, "ops");
-    if ((e = hipMalloc((void**)&d_count, 4)) != hipSuccess) return hip_fail(e, "counter");
-    if ((e = hipMemcpyAsync(d_in, recs.data(), sizeof(herro::AlignIn) * n, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
-      return hip_fail(e, "record upload");
-  }
-  for (size_t c = 0; c + 1 < cut.size(); c++) {
-    const uint32_t r0 = cut[c], r1 = cut[c + 1];
-    if ((e = hipMemsetAsync(d_count, 0, 4, ctx->stream)) != hipSuccess) return hip_fail(e, "counter reset");
-    herro::launch_align(ctx->d_words, d_in + r0, d_out + r0, d_scr, d_dense, d_count, r1 - r0, ctx->stream);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_align launch");
-    uint32_t total = 0;
-    if ((e = hipMemcpyAsync(&total, d_count, 4, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) return hip_fail(e, "count");
-    if ((e = hipMemcpyAsync(res.data() + r0, d_out + r0, sizeof(herro::AlignOut) * (r1 - r0), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess)
-      return hip_fail(e, "results");
-    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return hip_fail(e, "k_align");
-    uint64_t at = 0;
-    if ((e = take(total, d_dense, r1, at)) != hipSuccess) return hip_fail(e, "ops");
-    for (uint32_t r = r0; r < r1; r++) ops_at[r] = at + res[r].ops_off;
-  }
-  if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return hip_fail(e, "ops");   // (a device-resident store: its last copy has landed)
-  release();
-  return HERRO_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int herro_align_overlaps(herro_ctx* ctx, uint32_t n, const herro_alignment* in, herro_aligned** out) {
-  if (!ctx || !out || (n && !in)) return HERRO_E_INVALID;
-  *out = nullptr;
-  std::vector<herro::AlignOut> res;
-  std::vector<uint32_t> ops;            // every record's final ops, record order
-  std::vector<uint64_t> ops_at;
-  const int rc = align_chunks(ctx, n, in, res, ops_at, [&](uint32_t total, const uint32_t* d_dense, uint32_t, uint64_t& at) {
-    at = ops.size();
-    ops.resize(at + total);
-    return total ? hipMemcpy(ops.data() + at, d_dense, 4ull * total, hipMemcpyDeviceToHost) : hipSuccess;
-  });
-  if (rc != HERRO_OK) return rc;
-  // text: "<len><M|I|D>" per op, records back to back
-  std::vector<uint64_t> toff(n + 1, 0);
-  for (uint32_t r = 0; r < n; r++) toff[r + 1] = toff[r] + (res[r].failed ? 0 : ops_text_bytes(ops.data() + ops_at[r], res[r].n_ops));
-  auto* h = new herro_aligned();
-  h->text.resize(std::max<uint64_t>(toff[n], 1));
-  h->alns.assign(in, in + n);
-  h->scores.resize(n);
-  host_pool(ctx).run(n, [&](uint32_t r) {
-    herro_alignment& a = h->alns[r];
-    const herro::AlignOut& o = res[r];
-    a.cigar = reinterpret_cast<const uint8_t*>(h->text.data() + toff[r]);
-    a.cigar_len = (uint32_t)(toff[r + 1] - toff[r]);
-    if (o.failed) { h->scores[r] = INT32_MIN; a.cigar_len = 0; return; }
-    h->scores[r] = o.score;
-    ops_text(ops.data() + ops_at[r], o.n_ops, &h->text[toff[r]]);
-    apply_trim(a, o);
-  });
-  for (uint32_t r = 0; r < n; r++) h->failed += res[r].failed ? 1u : 0u;
-  *out = h;
-  return HERRO_OK;
-}
-
-const herro_alignment* herro_aligned_alignments(const herro_aligned* a) { return a ? a->alns.data() : nullptr; }
-const int32_t* herro_aligned_scores(const herro_aligned* a) { return a ? a->scores.data() : nullptr; }
-uint32_t herro_aligned_failed(const herro_aligned* a) { return a ? a->failed : 0; }
-void herro_aligned_free(herro_aligned* a) { delete a; }
-
-// ---- extension of coordinate-only overlaps to the read ends (k_extend in align_dev.hip) ----------------------------------------
-// Two sides per record, one wave each; the host turns the four flank lengths into coordinates.  Records go through in slices of 2^20, so the side
-// descriptors and results (72 B per side) stay small whatever n is.
-struct herro_extended {
-  std::vector<herro_alignment> alns;   // extended coordinates; cigar = NULL, cigar_len = 0
-  std::vector<uint32_t> ext;           // [n][4]: t_left, q_left, t_right, q_right
-  std::vector<int32_t> scores;         // [n][2]: left, right
-};
-
-int herro_extend_overlaps(herro_ctx* ctx, uint32_t n, const herro_alignment* in, const herro_extend_params* params, herro_extended** out) {
-  if (!ctx || !out || (n && !in)) return HERRO_E_INVALID;
-  *out = nullptr;
-  const uint32_t zdrop = params && params->zdrop ? params->zdrop : herro::EXTEND_ZDROP;
-  const uint32_t max_ext = params && params->max_ext ? params->max_ext : herro::EXTEND_MAX_EXT;
-  if (max_ext > herro::EXTEND_MAX_EXT_LIMIT) { ctx->err = "herro_extend_overlaps: max_ext must be at most 2^20"; return HERRO_E_INVALID; }
-  if (const int rc = check_records(ctx, "herro_extend_overlaps", n, in)) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  std::unique_ptr<herro_extended> h(new herro_extended());
-  h->alns.assign(in, in + n);
-  h->ext.assign((size_t)n * 4, 0);
-  h->scores.assign((size_t)n * 2, 0);
-  constexpr uint32_t SLICE = 1u << 20;
-  const uint32_t cap = std::min(n, SLICE);
-  std::vector<herro::ExtIn> sides((size_t)cap * 2);
-  std::vector<herro::ExtOut> res((size_t)cap * 2);
-  herro::ExtIn* d_in = nullptr;
-  herro::ExtOut* d_out = nullptr;
-  auto hip_fail = [&](hipError_t e, const char* what) {
-    ctx->err = std::string("herro_extend_overlaps: ") + what + ": " + hipGetErrorString(e);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    return HERRO_E_NO_DEVICE;
-  };
-  hipError_t e = hipSuccess;
-  if (n) {
-    if ((e = hipMalloc((void**)&d_in, sizeof(herro::ExtIn) * sides.size())) != hipSuccess) return hip_fail(e, "sides");
-    if ((e = hipMalloc((void**)&d_out, sizeof(herro::ExtOut) * res.size())) != hipSuccess) return hip_fail(e, "results");
-  }
-  for (uint32_t r0 = 0; r0 < n; r0 += SLICE) {
-    const uint32_t cnt = std::min(SLICE, n - r0);
-    for (uint32_t x = 0; x < cnt; x++) {
-      const herro_alignment& a = in[r0 + x];
-      const uint64_t tw = ctx->h_word_off[a.tid], qw = ctx->h_word_off[a.qid];
-      const uint32_t t_below = a.tstart, t_above = ctx->read_len[a.tid] - a.tend;
-      const uint32_t q_below = a.qstart, q_above = ctx->read_len[a.qid] - a.qend;
-      // left: the target below tstart read downwards; the oriented query in front of the span read backwards — the forward bases below qstart read
-      // downwards (strand 0) or those from qend upwards (strand 1), complemented like the target's (T rev = 1, Q rev = !strand: the same equalities)
-      const uint32_t ml = std::min(t_below, max_ext), nl = std::min(a.strand ? q_above : q_below, max_ext);
-      sides[2 * x] = herro::ExtIn{tw, qw, a.tstart - ml, ml, a.strand ? a.qend : a.qstart - nl, nl, 1u, a.strand ? 0u : 1u};
-      // right: the target from tend upwards; the oriented query behind the span
-      const uint32_t mr = std::min(t_above, max_ext), nr = std::min(a.strand ? q_below : q_above, max_ext);
-      sides[2 * x + 1] = herro::ExtIn{tw, qw, a.tend, mr, a.strand ? a.qstart - nr : a.qend, nr, 0u, a.strand};
-    }
-    if ((e = hipMemcpyAsync(d_in, sides.data(), sizeof(herro::ExtIn) * 2 * cnt, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) return hip_fail(e, "side upload");
-    herro::launch_extend(ctx->d_words, d_in, d_out, zdrop, 2 * cnt, ctx->stream);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_extend launch");
-    if ((e = hipMemcpyAsync(res.data(), d_out, sizeof(herro::ExtOut) * 2 * cnt, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) return hip_fail(e, "results");
-    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return hip_fail(e, "k_extend");
-    for (uint32_t x = 0; x < cnt; x++) {
-      herro_alignment& a = h->alns[r0 + x];
-      const herro::ExtOut &l = res[2 * x], &r = res[2 * x + 1];
-      a.cigar = nullptr; a.cigar_len = 0;
-      a.tstart -= l.j; a.tend += r.j;
-      if (a.strand == 0) { a.qstart -= l.i; a.qend += r.i; }
-      else { a.qend += l.i; a.qstart -= r.i; }
-      uint32_t* ex = &h->ext[(size_t)(r0 + x) * 4];
-      ex[0] = l.j; ex[1] = l.i; ex[2] = r.j; ex[3] = r.i;
-      h->scores[(size_t)(r0 + x) * 2] = l.score;
-      h->scores[(size_t)(r0 + x) * 2 + 1] = r.score;
-    }
-  }
-  if (d_in) (void)hipFree(d_in);
-  if (d_out) (void)hipFree(d_out);
-  *out = h.release();
-  return HERRO_OK;
-}
-
-uint32_t herro_extended_n(const herro_extended* x) { return x ? (uint32_t)x->alns.size() : 0; }
-const herro_alignment* herro_extended_alignments(const herro_extended* x) { return x ? x->alns.data() : nullptr; }
-const uint32_t* herro_extended_ext(const herro_extended* x) { return x ? x->ext.data() : nullptr; }
-const int32_t* herro_extended_scores(const herro_extended* x) { return x ? x->scores.data() : nullptr; }
-void herro_extended_free(herro_extended* x) { delete x; }
-
-// ---- device-resident hand-off: the aligner's ops stay where k_align wrote them, the job builder reads them there ----------------
-int herro_align_overlaps_dev(herro_ctx* ctx, uint32_t n, const herro_alignment* in, herro_aligned_dev** out) {
-  if (!ctx || !out || (n && !in)) return HERRO_E_INVALID;
-  *out = nullptr;
-  std::unique_ptr<herro_aligned_dev, void (*)(herro_aligned_dev*)> h(new herro_aligned_dev(), herro_aligned_dev_free);
-  h->ctx = ctx; h->device = ctx->device;
-  std::vector<herro::AlignOut> res;
-  // The store grows by chunks: the first chunk's ops per record, projected over all records plus an eighth, sizes it; a chunk that does not fit moves it
-  // to twice the projection (device to device, behind the chunk's synchronisation: nothing reads the old block any more).
-  const int rc = align_chunks(ctx, n, in, res, h->op_off, [&](uint32_t total, const uint32_t* d_dense, uint32_t r_done, uint64_t& at) {
-    at = h->used;
-    if (!total) return hipSuccess;
-    hipError_t e;
-    if (h->used + total > h->cap) {
-      const uint64_t proj = (h->used + total) * (uint64_t)n / std::max(r_done, 1u);
-      const uint64_t cap = std::max<uint64_t>(h->used + total, (h->cap ? 2 : 1) * (proj + proj / 8)) + 1024;
-      uint32_t* d = nullptr;
-      if ((e = hipMalloc((void**)&d, cap * 4)) != hipSuccess) return e;
-      if (h->used && (e = hipMemcpyAsync(d, h->d_ops, h->used * 4, hipMemcpyDeviceToDevice, ctx->stream)) != hipSuccess) { (void)hipFree(d); return e; }
-      if (h->d_ops) {
-        if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) { (void)hipFree(d); return e; }
-        (void)hipFree(h->d_ops);
-      }
-      h->d_ops = d; h->cap = cap;
-    }
-    // (stream order: the next chunk's kernel, which overwrites d_dense, queues behind this copy)
-    if ((e = hipMemcpyAsync(h->d_ops + h->used, d_dense, 4ull * total, hipMemcpyDeviceToDevice, ctx->stream)) != hipSuccess) return e;
-    h->used += total;
-    return hipSuccess;
-  });
-  if (rc != HERRO_OK) return rc;
-  h->alns.assign(in, in + n);
-  h->scores.resize(n);
-  h->n_ops.resize(n);
-  for (uint32_t r = 0; r < n; r++) {
-    herro_alignment& a = h->alns[r];
-    const herro::AlignOut& o = res[r];
-    a.cigar = nullptr; a.cigar_len = 0;
-    if (o.failed) { h->scores[r] = INT32_MIN; h->n_ops[r] = 0; h->failed++; continue; }
-    h->scores[r] = o.score;
-    h->n_ops[r] = o.n_ops;
-    apply_trim(a, o);
-  }
-  *out = h.release();
-  return HERRO_OK;
-}
-
-int herro_aligned_dev_from_ops(herro_ctx* ctx, uint32_t n, const herro_alignment* alns, const uint64_t* op_off, const uint32_t* ops, herro_aligned_dev** out) {
-  if (!ctx || !out || !op_off || (n && !alns)) return HERRO_E_INVALID;
-  *out = nullptr;
-  for (uint32_t r = 0; r < n; r++)
-    if (op_off[r + 1] < op_off[r] || op_off[r + 1] - op_off[r] > 0xffffffffull) {
-      ctx->err = "herro_aligned_dev_from_ops: record " + std::to_string(r) + ": op_off must ascend";
-      return HERRO_E_INVALID;
-    }
-  const uint64_t lo = op_off[0], total = op_off[n] - lo;
-  if (total && !ops) return HERRO_E_INVALID;
-  std::unique_ptr<herro_aligned_dev, void (*)(herro_aligned_dev*)> h(new herro_aligned_dev(), herro_aligned_dev_free);
-  h->ctx = ctx; h->device = ctx->device; h->host_only = ctx->host_only;
-  h->alns.assign(alns, alns + n);
-  h->scores.assign(n, 0);
-  h->n_ops.resize(n);
-  h->op_off.resize(n);
-  for (uint32_t r = 0; r < n; r++) {
-    h->alns[r].cigar = nullptr; h->alns[r].cigar_len = 0;
-    h->n_ops[r] = (uint32_t)(op_off[r + 1] - op_off[r]);
-    h->op_off[r] = op_off[r] - lo;
-    if (!h->n_ops[r]) { h->scores[r] = INT32_MIN; h->failed++; }
-  }
-  h->used = h->cap = total;
-  if (ctx->host_only) {
-    h->h_ops.assign(ops + lo, ops + lo + total);
-  } else if (total) {
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMalloc((void**)&h->d_ops, total * 4));
-    HIP_TRY(ctx, hipMemcpy(h->d_ops, ops + lo, total * 4, hipMemcpyHostToDevice));
-  }
-  *out = h.release();
-  return HERRO_OK;
-}
-
-// ---- mirrored records (k_mirror in align_dev.hip): every record's alignment the other way round, without a second sweep ----------
-// The new handle's store is src's ops (device to device) and behind them one reservation per mirror — the prefix sum of src's n_ops, since a mirror never
-// has more ops than its source.  Records go through in slices of 2^20, one synchronisation per slice to fetch the results.
-int herro_aligned_dev_mirror(herro_ctx* ctx, const herro_aligned_dev* src, herro_aligned_dev** out) {
-  if (!ctx || !src || !out) return HERRO_E_INVALID;
-  *out = nullptr;
-  if (src->ctx != ctx) { ctx->err = "herro_aligned_dev_mirror: the handle belongs to another context"; return HERRO_E_INVALID; }
-  if (src->host_only) { ctx->err = "herro_aligned_dev_mirror: the context has no device"; return HERRO_E_NO_DEVICE; }
-  if (src->alns.size() > 0x7fffffffull) { ctx->err = "herro_aligned_dev_mirror: more than 2^31 - 1 records"; return HERRO_E_INVALID; }
-  const uint32_t n = (uint32_t)src->alns.size();
-  if (const int rc = check_records(ctx, "herro_aligned_dev_mirror", n, src->alns.data())) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  std::unique_ptr<herro_aligned_dev, void (*)(herro_aligned_dev*)> h(new herro_aligned_dev(), herro_aligned_dev_free);
-  h->ctx = ctx; h->device = ctx->device;
-  h->alns = src->alns; h->scores = src->scores; h->n_ops = src->n_ops; h->op_off = src->op_off;
-  h->failed = src->failed;
-  h->alns.resize(2 * (size_t)n); h->scores.resize(2 * (size_t)n, INT32_MIN); h->n_ops.resize(2 * (size_t)n, 0); h->op_off.resize(2 * (size_t)n, 0);
-  uint64_t total = src->used;
-  for (uint32_t r = 0; r < n; r++) {
-    const herro_alignment& s = src->alns[r];
-    herro_alignment& a = h->alns[n + r];
-    a = herro_alignment{};
-    a.qid = s.tid; a.qlen = s.tlen; a.qstart = s.tstart; a.qend = s.tend; a.strand = s.strand;
-    a.tid = s.qid; a.tlen = s.qlen; a.tstart = s.qstart; a.tend = s.qend;
-    h->op_off[n + r] = total;
-    total += src->n_ops[r];
-  }
-  h->used = h->cap = total;
-  constexpr uint32_t SLICE = 1u << 20;
-  const uint32_t cap = std::min(n, SLICE);
-  std::vector<herro::MirrorIn> recs(cap);
-  std::vector<herro::AlignOut> res(cap);
-  herro::MirrorIn* d_in = nullptr;
-  herro::AlignOut* d_out = nullptr;
-  auto hip_fail = [&](hipError_t e, const char* what) {
-    ctx->err = std::string("herro_aligned_dev_mirror: ") + what + ": " + hipGetErrorString(e);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    return HERRO_E_NO_DEVICE;
-  };
-  hipError_t e = hipSuccess;
-  if (total && (e = hipMalloc((void**)&h->d_ops, total * 4)) != hipSuccess) return hip_fail(e, "op store");
-  if (src->used && (e = hipMemcpyAsync(h->d_ops, src->d_ops, src->used * 4, hipMemcpyDeviceToDevice, ctx->stream)) != hipSuccess) return hip_fail(e, "op copy");
-  if (n) {
-    if ((e = hipMalloc((void**)&d_in, sizeof(herro::MirrorIn) * cap)) != hipSuccess) return hip_fail(e, "records");
-    if ((e = hipMalloc((void**)&d_out, sizeof(herro::AlignOut) * cap)) != hipSuccess) return hip_fail(e, "results");
-  }
-  for (uint32_t r0 = 0; r0 < n; r0 += SLICE) {
-    const uint32_t cnt = std::min(SLICE, n - r0);
-    for (uint32_t x = 0; x < cnt; x++) {
-      const uint32_t r = r0 + x;
-      const herro_alignment& s = src->alns[r];
-      // the mirror's target is the source's query read, forward; its query the source's target read, reversed and complemented on strand 1
-      recs[x] = herro::MirrorIn{ctx->h_word_off[s.qid], ctx->h_word_off[s.tid], src->op_off[r], h->op_off[n + r], s.qstart, s.qend - s.qstart,
-                                s.tstart, s.tend - s.tstart, s.strand, src->n_ops[r], src->n_ops[r] ? src->scores[r] : 0, 0u};
-    }
-    if ((e = hipMemcpyAsync(d_in, recs.data(), sizeof(herro::MirrorIn) * cnt, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) return hip_fail(e, "record upload");
-    herro::launch_mirror(ctx->d_words, d_in, d_out, h->d_ops, cnt, ctx->stream);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_mirror launch");
-    if ((e = hipMemcpyAsync(res.data(), d_out, sizeof(herro::AlignOut) * cnt, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) return hip_fail(e, "results");
-    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return hip_fail(e, "k_mirror");
-    for (uint32_t x = 0; x < cnt; x++) {
-      const herro::AlignOut& o = res[x];
-      if (o.failed) { h->failed++; continue; }   // n_ops 0, INT32_MIN and the swapped coordinates, untrimmed
-      h->scores[n + r0 + x] = o.score;
-      h->n_ops[n + r0 + x] = o.n_ops;
-      apply_trim(h->alns[n + r0 + x], o);
-    }
-  }
-  if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return hip_fail(e, "op copy");   // (n = 0 with ops in src's store: the copy has landed)
-  if (d_in) (void)hipFree(d_in);
-  if (d_out) (void)hipFree(d_out);
-  *out = h.release();
-  return HERRO_OK;
-}
-
-uint32_t herro_aligned_dev_n(const herro_aligned_dev* a) { return a ? (uint32_t)a->alns.size() : 0; }
-const herro_alignment* herro_aligned_dev_alignments(const herro_aligned_dev* a) { return a ? a->alns.data() : nullptr; }
-const int32_t* herro_aligned_dev_scores(const herro_aligned_dev* a) { return a ? a->scores.data() : nullptr; }
-const uint32_t* herro_aligned_dev_n_ops(const herro_aligned_dev* a) { return a ? a->n_ops.data() : nullptr; }
-uint32_t herro_aligned_dev_failed(const herro_aligned_dev* a) { return a ? a->failed : 0; }
-
-void herro_aligned_dev_free(herro_aligned_dev* a) {
-  if (!a) return;
-  if (a->d_ops && hipSetDevice(a->device) == hipSuccess) (void)hipFree(a->d_ops);   // (hipFree waits for the device: no kernel is still reading the store)
-  delete a;
-}
-
-// ops [lo, hi) of the handle's store on the host
-static int aligned_dev_fetch(const herro_aligned_dev* a, uint64_t lo, uint64_t hi, std::vector<uint32_t>& v) {
-  v.resize(hi - lo);
-  if (hi == lo) return HERRO_OK;
-  if (a->host_only) { std::memcpy(v.data(), a->h_ops.data() + lo, (hi - lo) * 4); return HERRO_OK; }
-  if (hipSetDevice(a->device) != hipSuccess || hipMemcpy(v.data(), a->d_ops + lo, (hi - lo) * 4, hipMemcpyDeviceToHost) != hipSuccess) return HERRO_E_NO_DEVICE;
-  return HERRO_OK;
-}
-
-int64_t herro_aligned_dev_cigar(const herro_aligned_dev* a, uint32_t r, char* out, uint64_t cap) {
-  if (!a || r >= a->alns.size()) return HERRO_E_INVALID;
-  std::vector<uint32_t> v;
-  const int rc = aligned_dev_fetch(a, a->op_off[r], a->op_off[r] + a->n_ops[r], v);
-  if (rc != HERRO_OK) return rc;
-  const uint64_t need = ops_text_bytes(v.data(), (uint32_t)v.size());
-  if (out && need <= cap) ops_text(v.data(), (uint32_t)v.size(), out);
-  return (int64_t)need;
-}
-
+// ---- a job from device-resident alignments (the handle and its helpers: aligned_dev.h, frontend_api.hip) ----------------------
 herro_job* herro_job_create_aligned(herro_ctx* ctx, uint32_t n_targets, const uint32_t* rids, const uint64_t* aln_off, const uint32_t* rec,
                                     const herro_aligned_dev* a, uint32_t W) {
   if (!ctx) return nullptr;
@@ -3818,140 +3215,12 @@ herro_job* herro_job_create_aligned(herro_ctx* ctx, uint32_t n_targets, const ui
     const int rc = aligned_dev_fetch(a, lo, hi, ops);
     if (rc != HERRO_OK) return fail(rc, "herro_job_create_aligned: copying the ops down failed");
   }
-  std::vector<uint64_t> toff(a1 + 1, 0);
-  for (uint64_t g = a0; g < a1; g++) toff[g + 1] = toff[g] + ops_text_bytes(ops.data() + (off[g] - lo), nops[g]);
-  std::string text(toff[a1] + 1, '\0');
-  host_pool(ctx).run((uint32_t)((a1 - a0 + 63) / 64), [&](uint32_t b) {
-    for (uint64_t g = a0 + (uint64_t)b * 64; g < std::min(a1, a0 + (uint64_t)(b + 1) * 64); g++) {
-      ops_text(ops.data() + (off[g] - lo), nops[g], &text[toff[g]]);
-      sel[g].cigar = reinterpret_cast<const uint8_t*>(text.data() + toff[g]);
-      sel[g].cigar_len = (uint32_t)(toff[g + 1] - toff[g]);
-    }
-  });
+  for (uint64_t g = a0; g < a1; g++) off[g] -= lo;
+  std::string text;
+  ops_text_block(ctx, ops.data(), off.data(), nops.data(), a0, a1, sel.data(), text);
   herro_job* job = herro_job_create(ctx, n_targets, rids, aln_off, sel.data(), W);
   if (job) job->from_ops_text = true;
   return job;
-}
-
-}  // extern "C"
-
-// ---- overlap finding (overlap_dev.hip) ---------------------------------------------------------------------------------------
-// The seeding and chaining the reference leaves to `minimap2 -x ava-ont` (mm2.rs:15-30): the device returns the kept chains per
-// (t, q, strand); the strand choice, the dual records and their grouping by target are a few lines of host code over them.
-struct herro_overlaps {
-  std::vector<uint32_t> rids;
-  std::vector<uint64_t> aln_off;
-  std::vector<herro_alignment> alns;
-  std::vector<int32_t> scores;
-};
-
-static int overlap_params(herro_ctx* ctx, const herro_overlap_params* in, herro::OvlParams& P) {
-  const herro_overlap_params z{};
-  const herro_overlap_params& p = in ? *in : z;
-  P.k = p.k ? p.k : 25;
-  P.w = p.w ? p.w : 17;
-  P.max_occ = p.max_occ ? p.max_occ : 128;
-  P.bandwidth = p.bandwidth ? p.bandwidth : 150;
-  P.max_gap = p.max_gap ? p.max_gap : 5000;
-  P.min_score = p.min_score ? p.min_score : 2500;
-  P.min_anchors = p.min_anchors ? p.min_anchors : 3;
-  if (P.k < 5 || P.k > 31 || P.w > 64) {
-    ctx->err = "overlap parameters: 5 <= k <= 31 and 1 <= w <= 64";
-    return HERRO_E_INVALID;
-  }
-  return HERRO_OK;
-}
-
-static int overlap_ready(herro_ctx* ctx, const char* who) {
-  if (ctx->host_only) { ctx->err = std::string(who) + ": the context has no device"; return HERRO_E_NO_DEVICE; }
-  if (!ctx->d_words) { ctx->err = "herro_set_reads must be called first"; return HERRO_E_STATE; }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  return HERRO_OK;
-}
-
-static int overlap_rc(herro_ctx* ctx, int rc, const std::string& msg) {
-  if (rc == herro::OVL_OK) return HERRO_OK;
-  ctx->err = msg;
-  return rc == herro::OVL_UNSUPPORTED ? HERRO_E_UNSUPPORTED : HERRO_E_NO_DEVICE;
-}
-
-extern "C" {
-
-int herro_find_overlaps(herro_ctx* ctx, const herro_overlap_params* params, herro_overlaps** out) {
-  if (!ctx || !out) return HERRO_E_INVALID;
-  *out = nullptr;
-  herro::OvlParams P;
-  if (int rc = overlap_params(ctx, params, P)) return rc;
-  if (int rc = overlap_ready(ctx, "herro_find_overlaps")) return rc;
-  uint64_t budget = 4096ull << 20;
-  if (const char* e = getenv("HERRO_OVL_SCRATCH_MB")) budget = (uint64_t)std::max(1ll, atoll(e)) << 20;
-  const herro::OvlStore S{ctx->d_words, ctx->d_word_off, ctx->d_qual_off, ctx->read_len.data(), ctx->n_reads};
-  std::vector<herro::OvlPair> chains;
-  herro::OvlStats stats;
-  std::string msg;
-  if (int rc = overlap_rc(ctx, herro::ovl_find(S, P, budget, ctx->stream, chains, stats, msg), msg)) return rc;
-  if (const char* e = getenv("HERRO_OVL_STATS"))   // tools/overlaprate.py: the sizes of the stages, one line on stderr
-    if (atoi(e)) fprintf(stderr, "OVL kmers=%llu minimizers=%llu anchors=%llu groups=%llu chained=%llu chunks=%llu\n", (unsigned long long)stats.kmers,
-                         (unsigned long long)stats.minimizers, (unsigned long long)stats.anchors, (unsigned long long)stats.groups,
-                         (unsigned long long)stats.chained, (unsigned long long)stats.chunks);
-  // one overlap per pair: chains arrive in ascending (t, q, rel), so the two strands of a pair are neighbours
-  std::vector<herro::OvlPair> best;
-  for (const herro::OvlPair& c : chains) {
-    if (!best.empty() && best.back().t == c.t && best.back().q == c.q) {
-      if (c.score > best.back().score) best.back() = c;
-    } else {
-      best.push_back(c);
-    }
-  }
-  struct Rec { herro_alignment a; int32_t score; };
-  std::vector<Rec> recs;
-  recs.reserve(best.size() * 2);
-  for (const herro::OvlPair& c : best) {
-    const uint32_t tl = ctx->read_len[c.t], ql = ctx->read_len[c.q];
-    recs.push_back(Rec{herro_alignment{c.q, ql, c.qstart, c.qend, c.rel, c.t, tl, c.tstart, c.tend, 0, nullptr}, c.score});
-    recs.push_back(Rec{herro_alignment{c.t, tl, c.tstart, c.tend, c.rel, c.q, ql, c.qstart, c.qend, 0, nullptr}, c.score});   // the dual
-  }
-  std::sort(recs.begin(), recs.end(), [](const Rec& x, const Rec& y) { return x.a.tid != y.a.tid ? x.a.tid < y.a.tid : x.a.qid < y.a.qid; });
-  auto* h = new herro_overlaps();
-  h->alns.reserve(recs.size());
-  h->scores.reserve(recs.size());
-  for (const Rec& r : recs) {
-    if (h->rids.empty() || h->rids.back() != r.a.tid) { h->rids.push_back(r.a.tid); h->aln_off.push_back(h->alns.size()); }
-    h->alns.push_back(r.a);
-    h->scores.push_back(r.score);
-  }
-  h->aln_off.push_back(h->alns.size());
-  *out = h;
-  return HERRO_OK;
-}
-
-uint32_t herro_overlaps_n(const herro_overlaps* o) { return o ? (uint32_t)o->alns.size() : 0; }
-uint32_t herro_overlaps_n_targets(const herro_overlaps* o) { return o ? (uint32_t)o->rids.size() : 0; }
-const uint32_t* herro_overlaps_target_ids(const herro_overlaps* o) { return o ? o->rids.data() : nullptr; }
-const uint64_t* herro_overlaps_aln_off(const herro_overlaps* o) { return o ? o->aln_off.data() : nullptr; }
-const herro_alignment* herro_overlaps_alignments(const herro_overlaps* o) { return o ? o->alns.data() : nullptr; }
-const int32_t* herro_overlaps_scores(const herro_overlaps* o) { return o ? o->scores.data() : nullptr; }
-void herro_overlaps_free(herro_overlaps* o) { delete o; }
-
-int64_t herro_debug_sketch(herro_ctx* ctx, const herro_overlap_params* params, uint64_t* hash, uint32_t* rid, uint32_t* pos,
-                           uint8_t* strand, uint64_t cap) {
-  if (!ctx) return HERRO_E_INVALID;
-  herro::OvlParams P;
-  if (int rc = overlap_params(ctx, params, P)) return rc;
-  if (int rc = overlap_ready(ctx, "herro_debug_sketch")) return rc;
-  const herro::OvlStore S{ctx->d_words, ctx->d_word_off, ctx->d_qual_off, ctx->read_len.data(), ctx->n_reads};
-  std::vector<uint64_t> h, m;
-  std::string msg;
-  if (int rc = overlap_rc(ctx, herro::ovl_sketch(S, P, ctx->stream, h, m, msg), msg)) return rc;
-  if (h.size() <= cap && hash && rid && pos && strand) {
-    for (size_t i = 0; i < h.size(); i++) {
-      hash[i] = h[i];
-      rid[i] = (uint32_t)(m[i] >> 32);
-      pos[i] = ((uint32_t)m[i]) >> 1;
-      strand[i] = (uint8_t)(m[i] & 1u);
-    }
-  }
-  return (int64_t)h.size();
 }
 
 }  // extern "C"

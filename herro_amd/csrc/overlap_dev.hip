@@ -11,6 +11,7 @@
 //   k_walk       back through the stored predecessors: first anchor, anchor count, coordinates.
 // Nothing an atomic orders reaches the output: the only atomics are integer sums (histograms, anchors per read).
 #include "overlap_dev.h"
+#include "dev_bufs.h"
 
 #include <algorithm>
 #include <climits>
@@ -426,19 +427,6 @@ __global__ __launch_bounds__(256) void k_walk(const uint64_t* __restrict__ A, co
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-struct Bufs {   // device allocations of one call, freed together
-  std::vector<void*> p;
-  ~Bufs() { for (void* q : p) if (q) (void)hipFree(q); }
-  template <typename T>
-  hipError_t get(T** out, uint64_t count) {
-    void* q = nullptr;
-    const hipError_t e = hipMalloc(&q, std::max<uint64_t>(count, 1) * sizeof(T) + 64);
-    if (e == hipSuccess) p.push_back(q);
-    *out = (T*)q;
-    return e;
-  }
-};
-
 #define OVL_TRY(expr)                                                                  \
   do {                                                                                 \
     const hipError_t _e = (expr);                                                      \

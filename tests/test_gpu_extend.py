@@ -11,6 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import gpu_common as G  # noqa: E402
 import extend_ref as E  # noqa: E402
+import frontend_cases as FC  # noqa: E402
 from herro_amd import api, synth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -138,6 +139,24 @@ def test_extension_equals_the_reference_bit_for_bit():
         if kw.get("zdrop") == 30:
             seen_stop = set(st["last"].ravel().tolist())
     assert {16, 32} <= seen_stop                             # z-drop fired at its first and at its second check
+
+
+def test_records_past_one_slice_equal_the_reference():
+    """The host sends the records through in slices (SLICE of frontend_api.hip): 37 records more than one slice, so the loop turns
+    twice and the second turn is a short one.  The batch's 200 records, tiled; max_ext = 64 keeps a side at 64 x 64 cells."""
+    reads, rows, codes = _batch()
+    n = FC.slice_records() + 37
+    assert n == (1 << 20) + 37
+    idx = np.arange(n) % len(rows)
+    want = E.extend_records(codes, rows, max_ext=64)
+    assert want[1].max() == 64 and (want[1][idx[n - 37:]] > 0).any()        # the cap binds, and the short turn has work to do
+    c = G.ctx()
+    _load(c, reads)
+    got = c.extend_overlaps(rows[idx], max_ext=64)
+    for name, g, w in zip(("rows", "ext", "scores"), got, want):
+        assert g.dtype == w.dtype and g.shape == (n,) + w.shape[1:], name
+        bad = np.flatnonzero((g != w[idx]).any(axis=1))
+        assert len(bad) == 0, (name, len(bad), int(bad[0]), g[bad[0]].tolist(), w[idx[bad[0]]].tolist())
 
 
 def _chain(c, sb, W, extend):

@@ -10,6 +10,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import align_ref as A  # noqa: E402
+import frontend_cases as FC  # noqa: E402
 import gpu_common as G  # noqa: E402
 import lowcomplexity as LC  # noqa: E402
 import mirror_cases as MC  # noqa: E402
@@ -96,6 +97,46 @@ def test_hand_cases_and_op_counts_from_caller_supplied_ops():
             m.close()
     h.close()
     assert runs[0] == runs[1]
+
+
+def test_records_past_one_slice_equal_the_reference():
+    """The host sends the records through in slices (SLICE of frontend_api.hip): 37 records more than one slice, so the loop turns
+    twice and the second turn is a short one.  Six records of one to three ops, tiled (about two million ops in the store)."""
+    reads, rows, off, ops = MC.build(MC.counted(np.random.default_rng(22), counts=(1, 2, 3)))
+    codes = [A.store_codes(r) for r in reads]
+    k = len(rows)
+    cnt = np.diff(off).astype(np.int64)
+    assert k == 6 and sorted(set(cnt.tolist())) == [1, 2, 3] and set(rows[:, 4].tolist()) == {0, 1}
+    c = G.ctx()
+    c.set_reads(*MC.store(reads))
+    h0 = c.aligned_dev_from_ops(rows, off, ops)                        # the untiled records: their CIGAR texts for the reference
+    src_cig = MC.handle_ops(h0)
+    w_rows, w_cig, w_sc, w_ok = MR.mirror_records(codes, h0.rows, src_cig, h0.scores)
+    src_rows, src_scores = h0.rows.copy(), h0.scores.copy()
+    h0.close()
+    n = FC.slice_records() + 37
+    assert n == (1 << 20) + 37
+    idx = np.arange(n) % k
+    t_off = np.concatenate([[0], np.cumsum(cnt[idx])]).astype(np.uint64)
+    first = np.repeat(off[idx].astype(np.int64) - t_off[:-1].astype(np.int64), cnt[idx])
+    t_ops = ops[first + np.arange(int(t_off[-1]))]                     # record r's ops are those of record idx[r]
+    h = c.aligned_dev_from_ops(rows[idx], t_off, t_ops)
+    m = h.mirror()
+    try:
+        assert m.n == 2 * n
+        w_nops = np.array([len(A.parse_cigar(x)) for x in w_cig], np.uint32)
+        assert np.array_equal(m.rows, np.concatenate([src_rows[idx], w_rows[idx]]))
+        assert np.array_equal(m.scores.astype(np.int64), np.concatenate([src_scores[idx].astype(np.int64), w_sc[idx]]))
+        assert np.array_equal(m.n_ops, np.concatenate([cnt[idx].astype(np.uint32), w_nops[idx]]))
+        assert np.array_equal(m.ok, np.concatenate([np.ones(n, bool), w_ok[idx]]))
+        assert m.failed == h.failed + int((~w_ok[idx]).sum()) and h.failed == 0
+        # the text: the 64 mirrors around the first one of the second slice, the first and the last mirror
+        lo = n + FC.slice_records() - 32
+        for r in list(range(lo, lo + 64)) + [n, 2 * n - 1]:
+            assert m.cigar(r) == w_cig[idx[r - n]], (r, m.cigar(r), w_cig[idx[r - n]])
+        assert m.cigar(n - 1) == src_cig[idx[n - 1]] and m.cigar(0) == src_cig[0]
+    finally:
+        h.close(); m.close()
 
 
 # ---- 2. the aligner's handles ----------------------------------------------------------------------------------------------------------------

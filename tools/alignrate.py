@@ -30,8 +30,6 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from herro_amd import api, synth  # noqa: E402
 
-_ALN = np.dtype([("f", np.uint32, 10), ("p", np.uint64)], align=True)
-
 
 def _job_or_raise(c, h):
     if not h:
@@ -48,7 +46,7 @@ def text_leg(c, arr, n, rids, aln_off, W):
     alns = L.herro_aligned_alignments(h)
     off = aln_off
     if L.herro_aligned_failed(h):                     # drop the failed records, keep every target's place (api.aligned_job_args)
-        v = np.frombuffer((api.Alignment * n).from_address(alns), _ALN, n)
+        v = np.frombuffer((api.Alignment * n).from_address(alns), api.ALN_DTYPE, n)
         ok = v["f"][:, 9] > 0
         kept = np.ascontiguousarray(v[ok])
         alns = kept.ctypes.data
@@ -113,9 +111,9 @@ def pairs_main(a, sb, c):
     t_pair_rows = time.perf_counter() - t0
     assert len(prim) == n and np.array_equal(prim, np.arange(n))
     arr2 = (api.Alignment * (2 * n))()
-    np.frombuffer(arr2, _ALN, 2 * n)["f"][:, :9] = both
+    np.frombuffer(arr2, api.ALN_DTYPE, 2 * n)["f"][:, :9] = both
     arr1 = (api.Alignment * n)()
-    np.frombuffer(arr1, _ALN, n)["f"][:, :9] = both[prim]
+    np.frombuffer(arr1, api.ALN_DTYPE, n)["f"][:, :9] = both[prim]
     legs = {}
     for name, run in (("dual", lambda: dev_leg(c, arr2, 2 * n, rids, aln_off, a.window)),
                       ("pair", lambda: pair_leg(c, arr1, n, rids, aln_off, rec_of_row, a.window))):
@@ -163,7 +161,7 @@ def main():
                     "ops_bytes": int(out[:, 9].astype(np.int64).sum())})
         del out, cig
     arr = (api.Alignment * max(n, 1))()
-    np.frombuffer(arr, _ALN, max(n, 1))["f"][:n, :9] = rows
+    np.frombuffer(arr, api.ALN_DTYPE, max(n, 1))["f"][:n, :9] = rows
     rids = np.ascontiguousarray(sb.tgt_rid, np.uint32)
     aln_off = np.ascontiguousarray(sb.tgt_aln_off, np.uint64)
     legs = {}
