@@ -39,6 +39,9 @@ EXPORTS = [
     "herro_find_overlaps", "herro_overlaps_n", "herro_overlaps_n_targets", "herro_overlaps_target_ids", "herro_overlaps_aln_off",
     "herro_overlaps_alignments", "herro_overlaps_scores", "herro_overlaps_free", "herro_debug_sketch",
     "herro_extend_overlaps", "herro_extended_n", "herro_extended_alignments", "herro_extended_ext", "herro_extended_scores", "herro_extended_free",
+    "herro_find_overlap_pairs", "herro_pairs_from_table", "herro_pairs_align", "herro_job_create_paired", "herro_pairs_n", "herro_pairs_primaries",
+    "herro_pairs_chain_scores", "herro_pairs_ext", "herro_pairs_ext_scores", "herro_pairs_n_targets", "herro_pairs_target_ids", "herro_pairs_aln_off",
+    "herro_pairs_rec_of_row", "herro_pairs_free",
 ]
 
 
@@ -83,6 +86,9 @@ def _job_or_raise(ctx: "Context", h, n_targets: int) -> "Job":
         code = int(msg.rsplit("[code ", 1)[1].rstrip("]")) if "[code " in msg else -1
         raise HerroError(code, msg)
     return Job(ctx, h, n_targets)
+
+
+PAIRS_NO_EXTEND = 1   # HERRO_PAIRS_NO_EXTEND
 
 
 class OverlapParams(C.Structure):  # herro_overlap_params (0 = the field's default)
@@ -245,6 +251,20 @@ def lib():
             f.argtypes = [vp]
         L.herro_extended_free.restype = None
         L.herro_extended_free.argtypes = [vp]
+        L.herro_find_overlap_pairs.argtypes = [vp, vp, vp, u32, vp]
+        L.herro_pairs_from_table.argtypes = [vp, u32, vp, vp, u32, vp, vp, vp, vp]
+        L.herro_pairs_align.argtypes = [vp, vp, vp]
+        L.herro_job_create_paired.restype = vp
+        L.herro_job_create_paired.argtypes = [vp, vp, vp, u32]
+        for f in (L.herro_pairs_n, L.herro_pairs_n_targets):
+            f.restype = u32
+            f.argtypes = [vp]
+        for f in (L.herro_pairs_primaries, L.herro_pairs_chain_scores, L.herro_pairs_ext, L.herro_pairs_ext_scores, L.herro_pairs_target_ids,
+                  L.herro_pairs_aln_off, L.herro_pairs_rec_of_row):
+            f.restype = vp
+            f.argtypes = [vp]
+        L.herro_pairs_free.restype = None
+        L.herro_pairs_free.argtypes = [vp]
         L.herro_debug_sketch.restype = C.c_int64
         L.herro_debug_sketch.argtypes = [vp, vp, vp, vp, vp, vp, u64]
         L.herro_debug_host_ctx.restype = vp
@@ -660,6 +680,42 @@ class Context:
             self._l.herro_extended_free(h)
         return out, ext, scores
 
+    def find_overlap_pairs(self, extend: bool = True, zdrop: int = 0, max_ext: int = 0, **params) -> "OverlapPairs":
+        """find_overlaps, pair_rows, extend_overlaps over the primaries and paired_job_args' table in one call that keeps the records on the
+        device (herro_find_overlap_pairs): one record per read pair and the table of the finder's two rows per pair.  params as
+        find_overlaps; zdrop, max_ext as extend_overlaps; extend=False: HERRO_PAIRS_NO_EXTEND, the chains' anchor spans as they are."""
+        p = self._overlap_params(params)
+        if not 0 <= int(zdrop) <= 0xFFFFFFFF or not 0 <= int(max_ext) <= 0xFFFFFFFF:
+            raise HerroError(-1, "extend parameters: zdrop and max_ext are unsigned 32-bit values")
+        e = ExtendParams(zdrop=int(zdrop), max_ext=int(max_ext))
+        h = C.c_void_p()
+        self._chk(self._l.herro_find_overlap_pairs(self.h, C.byref(p), C.byref(e), 0 if extend else PAIRS_NO_EXTEND, C.byref(h)))
+        return OverlapPairs(self, h)
+
+    def pairs_from_table(self, primaries: np.ndarray, chain_scores, rids, aln_off, rec_of_row) -> "OverlapPairs":
+        """A handle over a table the caller built (herro_pairs_from_table; also on a HostContext): primaries u32 [P, >= 9] as rows[prim],
+        chain_scores i32 [P] or None, (rids, aln_off) the grouping of the 2 P rows by target, rec_of_row as pair_rows returns it."""
+        rows = np.ascontiguousarray(primaries, np.uint32)
+        n = len(rows)
+        sc = None if chain_scores is None else np.ascontiguousarray(chain_scores, np.int32)
+        rids = np.ascontiguousarray(rids, np.uint32)
+        aln_off = np.ascontiguousarray(aln_off, np.uint64)
+        rec_of_row = np.ascontiguousarray(rec_of_row, np.uint32)
+        if len(aln_off) != len(rids) + 1 or len(rec_of_row) != 2 * n or (sc is not None and len(sc) != n):
+            raise ValueError("aln_off has one entry per target + 1, rec_of_row two per primary, chain_scores one")
+        arr, _ = _aln_array(rows)
+        h = C.c_void_p()
+        self._chk(self._l.herro_pairs_from_table(self.h, n, C.byref(arr), None if sc is None else sc.ctypes.data, len(rids),
+                                                 rids.ctypes.data if len(rids) else None, aln_off.ctypes.data,
+                                                 rec_of_row.ctypes.data if n else None, C.byref(h)))
+        return OverlapPairs(self, h)
+
+    def create_job_paired(self, pairs: "OverlapPairs", m: "AlignedDev", window_size: int) -> "Job":
+        """herro_job_create_paired: create_job_aligned(*paired_job_args(pairs.rids, pairs.aln_off, pairs.rec_of_row, m.ok), m, window_size)
+        inside the library; m: pairs.align() or any handle of 2 P records, primaries then mirrors."""
+        h = self._l.herro_job_create_paired(self.h, pairs.h, m.h, window_size)
+        return _job_or_raise(self, h, len(pairs.rids))
+
     def sketch(self, **params):
         """The store's minimizers sorted by (rid, pos) (herro_debug_sketch): (hash u64, rid u32, pos u32, strand u8)."""
         p = self._overlap_params(params)
@@ -893,6 +949,45 @@ class AlignedDev:
     def close(self):
         if getattr(self, "h", None):
             self._l.herro_aligned_dev_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+class OverlapPairs:
+    """herro_pairs: one record per overlapping read pair and the table of the finder's two rows per pair.  n_pairs = P; primaries u32
+    [P, 10] (ascending (tid, qid), extended unless extend=False, cigar_len 0); chain_scores i32 [P]; ext u32 [P, 4] and ext_scores i32
+    [P, 2] as extend_overlaps returns them (zeros without extension or from a table); rids u32 [n_targets], aln_off u64 [n_targets + 1],
+    rec_of_row u32 [2 P] as find_overlaps and pair_rows give them."""
+
+    def __init__(self, ctx: Context, h):
+        self.ctx, self.h, self._l = ctx, h, ctx._l
+        L = self._l
+        n = self.n_pairs = int(L.herro_pairs_n(h))
+        nt = int(L.herro_pairs_n_targets(h))
+
+        def arr(ptr, ct, dt, shape):
+            out = np.zeros(shape, dt)
+            if out.size:
+                out[...] = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ct)), shape)
+            return out
+        self.primaries = _aln_rows(L.herro_pairs_primaries(h), n)
+        self.chain_scores = arr(L.herro_pairs_chain_scores(h), C.c_int32, np.int32, (n,))
+        self.ext = arr(L.herro_pairs_ext(h), C.c_uint32, np.uint32, (n, 4))
+        self.ext_scores = arr(L.herro_pairs_ext_scores(h), C.c_int32, np.int32, (n, 2))
+        self.rids = arr(L.herro_pairs_target_ids(h), C.c_uint32, np.uint32, (nt,))
+        self.aln_off = arr(L.herro_pairs_aln_off(h), C.c_uint64, np.uint64, (nt + 1,))
+        self.rec_of_row = arr(L.herro_pairs_rec_of_row(h), C.c_uint32, np.uint32, (2 * n,))
+
+    def align(self) -> "AlignedDev":
+        """herro_pairs_align: Context.align_dev(self.primaries).mirror() — 2 P records, primaries then mirrors."""
+        h = C.c_void_p()
+        self.ctx._chk(self._l.herro_pairs_align(self.ctx.h, self.h, C.byref(h)))
+        return AlignedDev(self.ctx, h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._l.herro_pairs_free(self.h)
             self.h = None
 
     __del__ = close

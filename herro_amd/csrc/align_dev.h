@@ -71,4 +71,12 @@ struct ExtOut {           // (32 B)
 
 void launch_extend(const uint64_t* d_words, const ExtIn* d_in, ExtOut* d_out, uint32_t zdrop, uint32_t n_sides, hipStream_t st);
 
+// The same for records that are on the device (OvlRec, overlap_dev.h): k_ext_sides writes the two sides of d_rec[0 .. n_rec) — herro_extend_overlaps'
+// formulas, lengths from d_base_off — to d_sides[2 n_rec] for launch_extend; k_ext_fold applies its 2 n_rec results to the records' coordinates and
+// writes d_ext[n_rec][4] (t_left, q_left, t_right, q_right) and d_scores[n_rec][2].
+struct OvlRec;
+void launch_ext_sides(const OvlRec* d_rec, uint32_t n_rec, const uint64_t* d_word_off, const uint64_t* d_base_off, uint32_t max_ext, ExtIn* d_sides,
+                      hipStream_t st);
+void launch_ext_fold(OvlRec* d_rec, uint32_t n_rec, const ExtOut* d_res, uint32_t* d_ext, int32_t* d_scores, hipStream_t st);
+
 }  // namespace herro

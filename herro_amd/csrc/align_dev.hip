@@ -22,6 +22,7 @@
 // The walk back from (n, m) stages 64 rows at a time in the LDS; every lane walks the same path (uniform control flow,
 // broadcast LDS reads) and lane 0 writes the ops.  fix_cigar, the trim and the score then stream once over the op list.
 #include "align_dev.h"
+#include "overlap_dev.h"
 
 namespace herro {
 namespace {
@@ -434,7 +435,52 @@ __global__ __launch_bounds__(64) void k_extend(const uint64_t* __restrict__ word
   }
 }
 
+// ---- the extension of records that are on the device (herro_find_overlap_pairs): herro_extend_overlaps' two host loops, one thread per record ----
+// left: the target below tstart read downwards; the oriented query in front of the span read backwards.  right: the target from tend upwards; the
+// oriented query behind the span.  (T rev = 1, Q rev = !strand on the left; 0 and strand on the right.)
+__global__ __launch_bounds__(256) void k_ext_sides(const OvlRec* __restrict__ rec, uint32_t n, const uint64_t* __restrict__ word_off,
+                                                   const uint64_t* __restrict__ base_off, uint32_t max_ext, ExtIn* __restrict__ sides) {
+  const uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (x >= n) return;
+  const OvlRec a = rec[x];
+  const uint64_t tw = word_off[a.tid], qw = word_off[a.qid];
+  const uint32_t tlen = (uint32_t)(base_off[a.tid + 1] - base_off[a.tid]), qlen = (uint32_t)(base_off[a.qid + 1] - base_off[a.qid]);
+  const uint32_t t_below = a.tstart, t_above = tlen - a.tend;
+  const uint32_t q_below = a.qstart, q_above = qlen - a.qend;
+  const uint32_t ml = min(t_below, max_ext), nl = min(a.strand ? q_above : q_below, max_ext);
+  sides[2 * x] = ExtIn{tw, qw, a.tstart - ml, ml, a.strand ? a.qend : a.qstart - nl, nl, 1u, a.strand ? 0u : 1u};
+  const uint32_t mr = min(t_above, max_ext), nr = min(a.strand ? q_below : q_above, max_ext);
+  sides[2 * x + 1] = ExtIn{tw, qw, a.tend, mr, a.strand ? a.qstart - nr : a.qend, nr, 0u, a.strand};
+}
+
+// the two results of every record into its coordinates; ext[x] = t_left, q_left, t_right, q_right; scores[x] = left, right
+__global__ __launch_bounds__(256) void k_ext_fold(OvlRec* __restrict__ rec, uint32_t n, const ExtOut* __restrict__ res, uint32_t* __restrict__ ext,
+                                                  int32_t* __restrict__ scores) {
+  const uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (x >= n) return;
+  OvlRec a = rec[x];
+  const ExtOut l = res[2 * x], r = res[2 * x + 1];
+  a.tstart -= l.j; a.tend += r.j;
+  if (a.strand == 0) { a.qstart -= l.i; a.qend += r.i; }
+  else { a.qend += l.i; a.qstart -= r.i; }
+  rec[x] = a;
+  ext[4 * x] = l.j; ext[4 * x + 1] = l.i; ext[4 * x + 2] = r.j; ext[4 * x + 3] = r.i;
+  scores[2 * x] = l.score;
+  scores[2 * x + 1] = r.score;
+}
+
 }  // namespace
+
+void launch_ext_sides(const OvlRec* d_rec, uint32_t n_rec, const uint64_t* d_word_off, const uint64_t* d_base_off, uint32_t max_ext, ExtIn* d_sides,
+                      hipStream_t st) {
+  if (n_rec == 0) return;
+  hipLaunchKernelGGL(k_ext_sides, dim3((n_rec + 255) / 256), dim3(256), 0, st, d_rec, n_rec, d_word_off, d_base_off, max_ext, d_sides);
+}
+
+void launch_ext_fold(OvlRec* d_rec, uint32_t n_rec, const ExtOut* d_res, uint32_t* d_ext, int32_t* d_scores, hipStream_t st) {
+  if (n_rec == 0) return;
+  hipLaunchKernelGGL(k_ext_fold, dim3((n_rec + 255) / 256), dim3(256), 0, st, d_rec, n_rec, d_res, d_ext, d_scores);
+}
 
 void launch_extend(const uint64_t* d_words, const ExtIn* d_in, ExtOut* d_out, uint32_t zdrop, uint32_t n_sides, hipStream_t st) {
   if (n_sides == 0) return;

@@ -1,5 +1,5 @@
 // frontend_api.hip — the C ABI's front end (include/herro_amd.h): reads alone -> overlap records -> their ops on the device.
-// herro_find_overlaps, herro_extend_overlaps, herro_align_overlaps[_dev], herro_aligned_dev_*.  Host C++ (compiled by hipcc) over
+// herro_find_overlaps, herro_extend_overlaps, herro_align_overlaps[_dev], herro_aligned_dev_*, herro_find_overlap_pairs and herro_pairs_*.  Host C++ (compiled by hipcc) over
 // overlap_dev.hip and align_dev.hip; contexts, the model and jobs are herro_api.hip.
 #include <hip/hip_runtime.h>
 
@@ -68,8 +68,13 @@ void fold_result(const herro::AlignOut& o, herro_alignment& a, int32_t& score, u
 }
 
 // What herro_align_overlaps[_dev], herro_extend_overlaps and herro_aligned_dev_mirror (`who`) ask of a context and of coordinate-only records before anything runs.
+int check_record_fields(herro_ctx* ctx, const char* who, uint32_t n, const herro_alignment* in);
 int check_records(herro_ctx* ctx, const char* who, uint32_t n, const herro_alignment* in) {
   if (const int rc = device_ready(ctx, who)) return rc;
+  return check_record_fields(ctx, who, n, in);
+}
+// ... and of the records alone (herro_pairs_from_table, which a device-free context may call)
+int check_record_fields(herro_ctx* ctx, const char* who, uint32_t n, const herro_alignment* in) {
   for (uint32_t r = 0; r < n; r++) {
     const herro_alignment& a = in[r];
     std::string why;
@@ -160,6 +165,14 @@ int overlap_params(herro_ctx* ctx, const herro_overlap_params* in, herro::OvlPar
     return HERRO_E_INVALID;
   }
   return HERRO_OK;
+}
+
+// HERRO_OVL_STATS=1 (tools/overlaprate.py): the sizes of the finder's stages, one line on stderr
+void print_ovl_stats(const herro::OvlStats& stats) {
+  if (const char* e = getenv("HERRO_OVL_STATS"))
+    if (atoi(e)) fprintf(stderr, "OVL kmers=%llu minimizers=%llu anchors=%llu groups=%llu chained=%llu chunks=%llu\n", (unsigned long long)stats.kmers,
+                         (unsigned long long)stats.minimizers, (unsigned long long)stats.anchors, (unsigned long long)stats.groups,
+                         (unsigned long long)stats.chained, (unsigned long long)stats.chunks);
 }
 
 int overlap_rc(herro_ctx* ctx, int rc, const std::string& msg) {
@@ -483,10 +496,7 @@ int herro_find_overlaps(herro_ctx* ctx, const herro_overlap_params* params, herr
   herro::OvlStats stats;
   std::string msg;
   if (int rc = overlap_rc(ctx, herro::ovl_find(ovl_store(ctx), P, scratch_budget("HERRO_OVL_SCRATCH_MB"), ctx->stream, chains, stats, msg), msg)) return rc;
-  if (const char* e = getenv("HERRO_OVL_STATS"))   // tools/overlaprate.py: the sizes of the stages, one line on stderr
-    if (atoi(e)) fprintf(stderr, "OVL kmers=%llu minimizers=%llu anchors=%llu groups=%llu chained=%llu chunks=%llu\n", (unsigned long long)stats.kmers,
-                         (unsigned long long)stats.minimizers, (unsigned long long)stats.anchors, (unsigned long long)stats.groups,
-                         (unsigned long long)stats.chained, (unsigned long long)stats.chunks);
+  print_ovl_stats(stats);
   // one overlap per pair: chains arrive in ascending (t, q, rel), so the two strands of a pair are neighbours
   std::vector<herro::OvlPair> best;
   for (const herro::OvlPair& c : chains) {
@@ -525,6 +535,162 @@ const uint64_t* herro_overlaps_aln_off(const herro_overlaps* o) { return o ? o->
 const herro_alignment* herro_overlaps_alignments(const herro_overlaps* o) { return o ? o->alns.data() : nullptr; }
 const int32_t* herro_overlaps_scores(const herro_overlaps* o) { return o ? o->scores.data() : nullptr; }
 void herro_overlaps_free(herro_overlaps* o) { delete o; }
+
+// ---- pair overlaps ("Pairs on the device"): reads -> one record per pair and the table of its two rows -> mirrored alignments ----
+struct herro_pairs {
+  herro_ctx* ctx = nullptr;
+  std::vector<herro_alignment> alns;     // [P] primaries, ascending (tid, qid); cigar = NULL
+  std::vector<int32_t> chain_scores;     // [P]
+  std::vector<uint32_t> ext;             // [P][4]
+  std::vector<int32_t> ext_scores;       // [P][2]
+  std::vector<uint32_t> rids;            // targets of the 2 P rows
+  std::vector<uint64_t> aln_off;         // [n_targets + 1]
+  std::vector<uint32_t> rec_of_row;      // [2 P]
+};
+
+int herro_find_overlap_pairs(herro_ctx* ctx, const herro_overlap_params* params, const herro_extend_params* eparams, uint32_t flags, herro_pairs** out) {
+  if (!ctx || !out) return HERRO_E_INVALID;
+  *out = nullptr;
+  const char* const who = "herro_find_overlap_pairs";
+  herro::OvlParams P;
+  if (int rc = overlap_params(ctx, params, P)) return rc;
+  const uint32_t zdrop = eparams && eparams->zdrop ? eparams->zdrop : herro::EXTEND_ZDROP;
+  const uint32_t max_ext = eparams && eparams->max_ext ? eparams->max_ext : herro::EXTEND_MAX_EXT;
+  if (max_ext > herro::EXTEND_MAX_EXT_LIMIT) { ctx->err = "herro_find_overlap_pairs: max_ext must be at most 2^20"; return HERRO_E_INVALID; }
+  if (flags & ~HERRO_PAIRS_NO_EXTEND) { ctx->err = "herro_find_overlap_pairs: unknown flag"; return HERRO_E_INVALID; }
+  if (int rc = device_ready(ctx, who)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  herro::OvlRecs recs;
+  herro::OvlStats stats;
+  std::string msg;
+  if (int rc = overlap_rc(ctx, herro::ovl_find_pairs(ovl_store(ctx), P, scratch_budget("HERRO_OVL_SCRATCH_MB"), ctx->stream, recs, stats, msg), msg)) return rc;
+  print_ovl_stats(stats);
+  std::unique_ptr<herro_pairs> h(new herro_pairs());
+  h->ctx = ctx;
+  if (int rc = overlap_rc(ctx, herro::ovl_row_table(recs, ctx->n_reads, ctx->stream, h->rids, h->aln_off, h->rec_of_row, msg), msg)) return rc;
+  const uint32_t n = (uint32_t)recs.n;   // (<= 2^31 - 1: ovl_find_pairs)
+  h->ext.assign((size_t)n * 4, 0);
+  h->ext_scores.assign((size_t)n * 2, 0);
+  herro::Bufs B;
+  if (n && !(flags & HERRO_PAIRS_NO_EXTEND)) {
+    // the primaries are extended where they are: sides, k_extend and the fold in slices of 2^20 records, nothing in between comes down
+    const uint32_t cap = std::min(n, SLICE);
+    // one block: the sides and results of a slice (40 and 32 B per side), ext and scores of all records
+    const uint64_t b_in = sizeof(herro::ExtIn) * 2ull * cap, b_out = sizeof(herro::ExtOut) * 2ull * cap;
+    uint8_t* blk = nullptr;
+    FRONT_TRY(ctx, who, "sides, results, ext, scores", B.bytes(&blk, b_in + b_out + 24ull * n));
+    herro::ExtIn* const d_in = reinterpret_cast<herro::ExtIn*>(blk);
+    herro::ExtOut* const d_out = reinterpret_cast<herro::ExtOut*>(blk + b_in);
+    uint32_t* const d_ext = reinterpret_cast<uint32_t*>(blk + b_in + b_out);
+    int32_t* const d_sc = reinterpret_cast<int32_t*>(blk + b_in + b_out + 16ull * n);
+    for (uint32_t r0 = 0; r0 < n; r0 += SLICE) {
+      const uint32_t cnt = std::min(SLICE, n - r0);
+      herro::launch_ext_sides(recs.d + r0, cnt, ctx->d_word_off, ctx->d_qual_off, max_ext, d_in, ctx->stream);
+      herro::launch_extend(ctx->d_words, d_in, d_out, zdrop, 2 * cnt, ctx->stream);
+      herro::launch_ext_fold(recs.d + r0, cnt, d_out, d_ext + 4ull * r0, d_sc + 2ull * r0, ctx->stream);
+      FRONT_TRY(ctx, who, "k_extend launch", hipGetLastError());
+    }
+    FRONT_TRY(ctx, who, "ext", hipMemcpyAsync(h->ext.data(), d_ext, 16ull * n, hipMemcpyDeviceToHost, ctx->stream));
+    FRONT_TRY(ctx, who, "scores", hipMemcpyAsync(h->ext_scores.data(), d_sc, 8ull * n, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  std::vector<herro::OvlRec> host(n);
+  if (n) FRONT_TRY(ctx, who, "records", hipMemcpyAsync(host.data(), recs.d, sizeof(herro::OvlRec) * n, hipMemcpyDeviceToHost, ctx->stream));
+  FRONT_TRY(ctx, who, "k_extend", hipStreamSynchronize(ctx->stream));
+  h->alns.resize(n);
+  h->chain_scores.resize(n);
+  for (uint32_t p = 0; p < n; p++) {
+    const herro::OvlRec& r = host[p];
+    h->alns[p] = herro_alignment{r.qid, r.qlen, r.qstart, r.qend, r.strand, r.tid, r.tlen, r.tstart, r.tend, 0, nullptr};
+    h->chain_scores[p] = r.score;
+  }
+  *out = h.release();
+  return HERRO_OK;
+}
+
+int herro_pairs_from_table(herro_ctx* ctx, uint32_t n_pairs, const herro_alignment* primaries, const int32_t* chain_scores, uint32_t n_targets,
+                           const uint32_t* rids, const uint64_t* aln_off, const uint32_t* rec_of_row, herro_pairs** out) {
+  if (!ctx || !out || !aln_off || (n_pairs && (!primaries || !rec_of_row)) || (n_targets && !rids)) return HERRO_E_INVALID;
+  *out = nullptr;
+  const char* const who = "herro_pairs_from_table";
+  if (n_pairs > herro::OVL_MAX_PAIRS) { ctx->err = std::string(who) + ": more than 2^31 - 1 pairs"; return HERRO_E_UNSUPPORTED; }
+  if (const int rc = check_record_fields(ctx, who, n_pairs, primaries)) return rc;
+  const uint64_t n_rows = 2ull * n_pairs;
+  for (uint32_t t = 0; t <= n_targets; t++) {   // aln_off[0] = 0, aln_off[n_targets] = 2 P, ascending between
+    const uint64_t lo = t == n_targets ? n_rows : (t ? aln_off[t - 1] : 0), hi = t ? n_rows : 0;
+    if (aln_off[t] < lo || aln_off[t] > hi) {
+      ctx->err = std::string(who) + ": aln_off[" + std::to_string(t) + "] = " + std::to_string(aln_off[t]) + ": aln_off must ascend from 0 to " + std::to_string(n_rows) + " (two rows per pair)";
+      return HERRO_E_INVALID;
+    }
+  }
+  std::vector<bool> seen(n_rows, false);
+  for (uint64_t i = 0; i < n_rows; i++) {
+    const uint32_t r = rec_of_row[i];
+    if (r >= n_rows || seen[r]) {
+      ctx->err = std::string(who) + ": rec_of_row[" + std::to_string(i) + "] = " + std::to_string(r) + (r >= n_rows ? " is outside the " + std::to_string(n_rows) + " records" : " occurs twice");
+      return HERRO_E_INVALID;
+    }
+    seen[r] = true;
+  }
+  std::unique_ptr<herro_pairs> h(new herro_pairs());
+  h->ctx = ctx;
+  h->alns.assign(primaries, primaries + n_pairs);
+  for (herro_alignment& a : h->alns) { a.cigar = nullptr; a.cigar_len = 0; }
+  h->chain_scores.assign(n_pairs, 0);
+  if (chain_scores) h->chain_scores.assign(chain_scores, chain_scores + n_pairs);
+  h->ext.assign((size_t)n_pairs * 4, 0);
+  h->ext_scores.assign((size_t)n_pairs * 2, 0);
+  h->rids.assign(rids, rids + n_targets);
+  h->aln_off.assign(aln_off, aln_off + n_targets + 1);
+  h->rec_of_row.assign(rec_of_row, rec_of_row + n_rows);
+  *out = h.release();
+  return HERRO_OK;
+}
+
+int herro_pairs_align(herro_ctx* ctx, const herro_pairs* p, herro_aligned_dev** out) {
+  if (!ctx || !p || !out) return HERRO_E_INVALID;
+  *out = nullptr;
+  if (p->ctx != ctx) { ctx->err = "herro_pairs_align: the handle belongs to another context"; return HERRO_E_INVALID; }
+  herro_aligned_dev* prim = nullptr;
+  if (const int rc = herro_align_overlaps_dev(ctx, (uint32_t)p->alns.size(), p->alns.data(), &prim)) return rc;
+  const int rc = herro_aligned_dev_mirror(ctx, prim, out);
+  herro_aligned_dev_free(prim);
+  return rc;
+}
+
+herro_job* herro_job_create_paired(herro_ctx* ctx, const herro_pairs* p, const herro_aligned_dev* m, uint32_t window_size) {
+  if (!ctx) return nullptr;
+  auto fail = [&](const std::string& why) -> herro_job* {
+    ctx->err = "herro_job_create_paired: " + why + " [code " + std::to_string(HERRO_E_INVALID) + "]";
+    ctx->create_code = HERRO_E_INVALID;
+    return nullptr;
+  };
+  if (!p || !m) return fail("null handle");
+  if (p->ctx != ctx || m->ctx != ctx) return fail("the handle belongs to another context");
+  if (m->alns.size() != p->rec_of_row.size())
+    return fail("the aligned handle has " + std::to_string(m->alns.size()) + " records, the pairs need " + std::to_string(p->rec_of_row.size()) + " (primaries, then mirrors)");
+  // api.paired_job_args: a row whose record failed is dropped, the rest regrouped over the targets, which keep their place
+  const uint32_t nt = (uint32_t)p->rids.size();
+  std::vector<uint64_t> off(nt + 1ull, 0);
+  std::vector<uint32_t> rec;
+  rec.reserve(p->rec_of_row.size());
+  for (uint32_t t = 0; t < nt; t++) {
+    for (uint64_t i = p->aln_off[t]; i < p->aln_off[t + 1]; i++)
+      if (m->n_ops[p->rec_of_row[i]]) rec.push_back(p->rec_of_row[i]);
+    off[t + 1] = rec.size();
+  }
+  return herro_job_create_aligned(ctx, nt, p->rids.data(), off.data(), rec.data(), m, window_size);
+}
+
+uint32_t herro_pairs_n(const herro_pairs* p) { return p ? (uint32_t)p->alns.size() : 0; }
+const herro_alignment* herro_pairs_primaries(const herro_pairs* p) { return p ? p->alns.data() : nullptr; }
+const int32_t* herro_pairs_chain_scores(const herro_pairs* p) { return p ? p->chain_scores.data() : nullptr; }
+const uint32_t* herro_pairs_ext(const herro_pairs* p) { return p ? p->ext.data() : nullptr; }
+const int32_t* herro_pairs_ext_scores(const herro_pairs* p) { return p ? p->ext_scores.data() : nullptr; }
+uint32_t herro_pairs_n_targets(const herro_pairs* p) { return p ? (uint32_t)p->rids.size() : 0; }
+const uint32_t* herro_pairs_target_ids(const herro_pairs* p) { return p ? p->rids.data() : nullptr; }
+const uint64_t* herro_pairs_aln_off(const herro_pairs* p) { return p ? p->aln_off.data() : nullptr; }
+const uint32_t* herro_pairs_rec_of_row(const herro_pairs* p) { return p ? p->rec_of_row.data() : nullptr; }
+void herro_pairs_free(herro_pairs* p) { delete p; }
 
 int64_t herro_debug_sketch(herro_ctx* ctx, const herro_overlap_params* params, uint64_t* hash, uint32_t* rid, uint32_t* pos,
                            uint8_t* strand, uint64_t cap) {

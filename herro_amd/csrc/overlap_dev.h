@@ -46,4 +46,32 @@ int ovl_sketch(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vecto
 int ovl_find(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hipStream_t st, std::vector<OvlPair>& out, OvlStats& stats,
              std::string& err);
 
+// ---- one overlap per pair, left on the device ("Pairs on the device") -------------------------------------------------------
+constexpr uint64_t OVL_MAX_PAIRS = 0x7fffffffull;   // the mirror's record limit; 2 P rows stay inside the sort's 32-bit count
+
+struct OvlRec {              // one overlap in herro_alignment's field order (40 B): query q on target t, t < q
+  uint32_t qid, qlen, qstart, qend, strand, tid, tlen, tstart, tend;
+  int32_t score;                // chain score
+};
+
+struct OvlRecs {             // a device array of records; it owns its memory
+  OvlRec* d = nullptr;
+  uint64_t n = 0, cap = 0;
+  OvlRecs() = default;
+  OvlRecs(const OvlRecs&) = delete;
+  OvlRecs& operator=(const OvlRecs&) = delete;
+  void release() { if (d) (void)hipFree(d); d = nullptr; n = cap = 0; }
+  ~OvlRecs() { release(); }
+};
+
+// ovl_find with the strand choice on the device: the better strand of every pair (forward on a tie) as one record, in ascending
+// (t, q) order — the primaries of api.pair_rows over herro_find_overlaps' records.  The host reads one count per chunk.
+int ovl_find_pairs(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hipStream_t st, OvlRecs& out, OvlStats& stats,
+                   std::string& err);
+
+// The 2 P rows herro_find_overlaps emits for P primaries — (t, q) and (q, t) of each, by (tid, qid) — as a table: rids / aln_off group
+// them by target, rec_of_row[i] is p for the row that is primary p and P + p for its mirror.  Sorted and grouped on the device.
+int ovl_row_table(const OvlRecs& R, uint32_t n_reads, hipStream_t st, std::vector<uint32_t>& rids, std::vector<uint64_t>& aln_off,
+                  std::vector<uint32_t>& rec_of_row, std::string& err);
+
 }  // namespace herro

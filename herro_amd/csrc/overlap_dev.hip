@@ -426,6 +426,62 @@ __global__ __launch_bounds__(256) void k_walk(const uint64_t* __restrict__ A, co
   out[c] = g;
 }
 
+// ---- one overlap per pair (ovl_find_pairs) and the row table (ovl_row_table) -----------------------------------------------------------------
+// A kept chain is its pair's overlap unless the kept chain of the other strand wins: the reverse strand with a strictly greater score, the
+// forward strand with a greater or equal one (the forward strand on a tie).  The two are neighbours in g: ascending (t, q, rel).
+__global__ __launch_bounds__(256) void k_pick(const GroupOut* __restrict__ g, uint32_t nc, uint32_t* __restrict__ sel) {
+  const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= nc) return;
+  const GroupOut x = g[c];
+  uint32_t s = x.kept;
+  if (s && x.rel == 0 && c + 1 < nc) {
+    const GroupOut y = g[c + 1];
+    if (y.kept && y.t == x.t && y.q == x.q && y.score > x.score) s = 0;
+  } else if (s && x.rel != 0 && c > 0) {
+    const GroupOut y = g[c - 1];
+    if (y.kept && y.t == x.t && y.q == x.q && y.score >= x.score) s = 0;
+  }
+  sel[c] = s;
+}
+
+// the selected chains as records (query c.q on target c.t), in chain order, from out[0] on
+__global__ __launch_bounds__(256) void k_prim_write(const GroupOut* __restrict__ g, const uint32_t* __restrict__ sel,
+                                                    const uint32_t* __restrict__ soff, uint32_t nc, const uint64_t* __restrict__ base_off,
+                                                    OvlRec* __restrict__ out) {
+  const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= nc || !sel[c]) return;
+  const GroupOut x = g[c];
+  const uint32_t ql = (uint32_t)(base_off[x.q + 1] - base_off[x.q]), tl = (uint32_t)(base_off[x.t + 1] - base_off[x.t]);
+  out[soff[c]] = OvlRec{x.q, ql, x.qstart, x.qend, x.rel, x.t, tl, x.tstart, x.tend, x.score};
+}
+
+// row keys: primary p is the row (target t, query q), its mirror np + p the row (target q, query t)
+__global__ __launch_bounds__(256) void k_row_keys(const OvlRec* __restrict__ rec, uint32_t np, uint64_t* __restrict__ keys,
+                                                  uint64_t* __restrict__ pays) {
+  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= np) return;
+  const uint64_t t = rec[p].tid, q = rec[p].qid;
+  keys[p] = t << 32 | q;
+  pays[p] = p;
+  keys[np + p] = q << 32 | t;
+  pays[np + p] = np + p;
+}
+
+__global__ __launch_bounds__(256) void k_row_heads(const uint64_t* __restrict__ keys, uint32_t n, uint32_t* __restrict__ flag) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) flag[i] = (i == 0 || (keys[i] >> 32) != (keys[i - 1] >> 32)) ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_row_write(const uint64_t* __restrict__ keys, const uint64_t* __restrict__ pays,
+                                                   const uint32_t* __restrict__ flag, const uint32_t* __restrict__ tidx, uint32_t n,
+                                                   uint32_t* __restrict__ rids, uint64_t* __restrict__ aln_off, uint32_t* __restrict__ rec_of_row) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  rec_of_row[i] = (uint32_t)pays[i];
+  if (flag[i]) { rids[tidx[i]] = (uint32_t)(keys[i] >> 32); aln_off[tidx[i]] = i; }
+  if (i == 0) aln_off[tidx[n]] = n;
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 #define OVL_TRY(expr)                                                                  \
   do {                                                                                 \
@@ -556,9 +612,13 @@ int ovl_sketch(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vecto
   return OVL_OK;
 }
 
-int ovl_find(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hipStream_t st, std::vector<OvlPair>& out, OvlStats& stats,
-             std::string& err) {
-  out.clear();
+namespace {
+// Sketch, sort, frequency cut and the chunk loop of ovl_find and ovl_find_pairs.  Behind every chunk's k_walk, take(nc, gout, ccap, t_hi, B) gets the
+// chunk's nc GroupOut records, still on the device, in ascending (t, q, rel): it takes what it wants before it returns or queues its kernels on st,
+// in front of the next chunk's k_walk, which overwrites gout.  ccap: the most records any chunk has; t_hi: the targets done so far, this chunk's
+// included; B: the call's scratch.
+template <class Take>
+int find_chunks(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hipStream_t st, OvlStats& stats, std::string& err, Take take) {
   stats = OvlStats{};
   Bufs B;
   Sketch sk;
@@ -630,7 +690,6 @@ int ovl_find(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hipSt
   OVL_TRY(as.alloc(B, cap));
   uint32_t max_len = 0;
   for (uint32_t r = 0; r < S.n_reads; r++) max_len = std::max(max_len, S.h_len[r]);
-  std::vector<GroupOut> h_out;
 
   for (size_t ch = 0; ch + 1 < cut.size(); ch++) {
     const uint32_t t_lo = cut[ch], t_hi = cut[ch + 1];
@@ -673,12 +732,110 @@ int ovl_find(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hipSt
                                (int32_t)std::min<uint32_t>(P.max_gap, 0x7fffffffu));
     k_walk<<<nblk(nc, 256), 256, 0, st>>>(A0, B0, cstart, pred, ends, nc, S.d_base_off, P.k, t_lo, P.min_score, P.min_anchors, gout);
     OVL_TRY(hipGetLastError());
+    if (int rc = take(nc, gout, ccap, t_hi, B)) return rc;
+  }
+  return OVL_OK;
+}
+}  // namespace
+
+int ovl_find(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hipStream_t st, std::vector<OvlPair>& out, OvlStats& stats,
+             std::string& err) {
+  out.clear();
+  std::vector<GroupOut> h_out;
+  return find_chunks(S, P, budget_bytes, st, stats, err, [&](uint32_t nc, const GroupOut* gout, uint64_t, uint32_t, Bufs&) -> int {
     h_out.resize(nc);
     OVL_TRY(hipMemcpyAsync(h_out.data(), gout, sizeof(GroupOut) * (uint64_t)nc, hipMemcpyDeviceToHost, st));
     OVL_TRY(hipStreamSynchronize(st));
     for (const GroupOut& g : h_out)
       if (g.kept) out.push_back(OvlPair{g.t, g.q, g.rel, g.n_anchors, g.score, g.tstart, g.tend, g.qstart, g.qend});
+    return OVL_OK;
+  });
+}
+
+// ---- one overlap per pair and the row table, on the device ("Pairs on the device") ---------------------------------------
+int ovl_find_pairs(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hipStream_t st, OvlRecs& out, OvlStats& stats, std::string& err) {
+  out.release();
+  uint32_t *sel = nullptr, *soff = nullptr, *part = nullptr;
+  const int rc = find_chunks(S, P, budget_bytes, st, stats, err, [&](uint32_t nc, const GroupOut* gout, uint64_t ccap, uint32_t t_hi, Bufs& B) -> int {
+    if (!sel) {
+      OVL_TRY(B.get(&sel, ccap));
+      OVL_TRY(B.get(&soff, ccap + 1));
+      OVL_TRY(B.get(&part, (uint64_t)nblk(ccap, SC_TILE) + 2));
+    }
+    k_pick<<<nblk(nc, 256), 256, 0, st>>>(gout, nc, sel);
+    if (int rc2 = scan_u32(sel, nc, soff, part, st, err)) return rc2;
+    uint32_t ns = 0;
+    OVL_TRY(hipMemcpyAsync(&ns, soff + nc, 4, hipMemcpyDeviceToHost, st));
+    OVL_TRY(hipStreamSynchronize(st));
+    if (!ns) return OVL_OK;
+    if (out.n + ns > OVL_MAX_PAIRS) { err = "overlap finder: more than 2^31 - 1 overlapping read pairs"; return OVL_UNSUPPORTED; }
+    // The array grows by chunks as the aligner's op store does: the first chunk's primaries per target, projected over all targets plus an eighth,
+    // size it; a chunk that does not fit moves it to twice the projection (behind the synchronisation above: nothing is writing the old block).
+    if (out.n + ns > out.cap) {
+      const uint64_t proj = (out.n + ns) * (uint64_t)S.n_reads / std::max(t_hi, 1u);
+      const uint64_t cap = std::max<uint64_t>(out.n + ns, (out.cap ? 2 : 1) * (proj + proj / 8)) + 1024;
+      OvlRec* d = nullptr;
+      OVL_TRY(hipMalloc((void**)&d, cap * sizeof(OvlRec)));
+      OvlRec* const old = out.d;
+      out.d = d; out.cap = cap;
+      hipError_t e = out.n ? hipMemcpyAsync(d, old, out.n * sizeof(OvlRec), hipMemcpyDeviceToDevice, st) : hipSuccess;
+      if (old) {
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        (void)hipFree(old);
+      }
+      OVL_TRY(e);
+    }
+    k_prim_write<<<nblk(nc, 256), 256, 0, st>>>(gout, sel, soff, nc, S.d_base_off, out.d + out.n);
+    OVL_TRY(hipGetLastError());
+    out.n += ns;
+    return OVL_OK;
+  });
+  if (rc) return rc;
+  OVL_TRY(hipStreamSynchronize(st));
+  return OVL_OK;
+}
+
+int ovl_row_table(const OvlRecs& R, uint32_t n_reads, hipStream_t st, std::vector<uint32_t>& rids, std::vector<uint64_t>& aln_off,
+                  std::vector<uint32_t>& rec_of_row, std::string& err) {
+  rids.clear();
+  aln_off.assign(1, 0);
+  rec_of_row.clear();
+  if (!R.n) return OVL_OK;
+  if (R.n > OVL_MAX_PAIRS) { err = "overlap finder: more than 2^31 - 1 overlapping read pairs"; return OVL_UNSUPPORTED; }
+  const uint32_t np = (uint32_t)R.n, n = 2 * np;
+  Bufs B;
+  SortScratch ss;
+  OVL_TRY(ss.alloc(B, n));
+  // one block for the nine arrays of 2 P (+ 1) elements: 8-byte elements first, every array on a 256-byte boundary
+  const uint64_t a8 = (8ull * (n + 1ull) + 255) & ~255ull, a4 = (4ull * (n + 1ull) + 255) & ~255ull;
+  uint8_t* blk = nullptr;
+  OVL_TRY(B.bytes(&blk, 5 * a8 + 4 * a4));
+  uint64_t *k0 = (uint64_t*)blk, *p0 = (uint64_t*)(blk + a8), *k1 = (uint64_t*)(blk + 2 * a8), *p1 = (uint64_t*)(blk + 3 * a8);
+  uint64_t* d_off = (uint64_t*)(blk + 4 * a8);
+  uint32_t *flag = (uint32_t*)(blk + 5 * a8), *tidx = (uint32_t*)(blk + 5 * a8 + a4), *d_rids = (uint32_t*)(blk + 5 * a8 + 2 * a4);
+  uint32_t* d_rec = (uint32_t*)(blk + 5 * a8 + 3 * a4);
+  k_row_keys<<<nblk(np, 256), 256, 0, st>>>(R.d, np, k0, p0);
+  OVL_TRY(hipGetLastError());
+  {
+    std::vector<uint32_t> shifts;                 // keys are unique: one overlap per pair
+    field_shifts(shifts, 0, bits_of(n_reads - 1));
+    field_shifts(shifts, 32, bits_of(n_reads - 1));
+    if (int rc = radix_sort(&k0, &p0, &k1, &p1, n, shifts, ss, st, err)) return rc;
   }
+  k_row_heads<<<nblk(n, 256), 256, 0, st>>>(k0, n, flag);
+  if (int rc = scan_u32(flag, n, tidx, ss.partial, st, err)) return rc;
+  k_row_write<<<nblk(n, 256), 256, 0, st>>>(k0, p0, flag, tidx, n, d_rids, d_off, d_rec);
+  OVL_TRY(hipGetLastError());
+  uint32_t nt = 0;
+  OVL_TRY(hipMemcpyAsync(&nt, tidx + n, 4, hipMemcpyDeviceToHost, st));
+  OVL_TRY(hipStreamSynchronize(st));
+  rids.resize(nt);
+  aln_off.resize((size_t)nt + 1);
+  rec_of_row.resize(n);
+  OVL_TRY(hipMemcpyAsync(rids.data(), d_rids, 4ull * nt, hipMemcpyDeviceToHost, st));
+  OVL_TRY(hipMemcpyAsync(aln_off.data(), d_off, 8ull * (nt + 1ull), hipMemcpyDeviceToHost, st));
+  OVL_TRY(hipMemcpyAsync(rec_of_row.data(), d_rec, 4ull * n, hipMemcpyDeviceToHost, st));
+  OVL_TRY(hipStreamSynchronize(st));
   return OVL_OK;
 }
 

@@ -485,6 +485,49 @@ const uint64_t* herro_overlaps_aln_off(const herro_overlaps* o);          /* [n_
 const herro_alignment* herro_overlaps_alignments(const herro_overlaps* o);
 const int32_t* herro_overlaps_scores(const herro_overlaps* o);            /* chain score per record */
 void herro_overlaps_free(herro_overlaps* o);
+/* ---- pair overlaps: reads -> one record per read pair -> mirrored alignments -> job, in three calls ----------------------------------
+ * herro_find_overlaps writes both directions of every pair; aligning each pair once and mirroring the alignment (herro_aligned_dev_mirror)
+ * needs them paired again, and the extension between the two must see one direction only.  These entries keep that bookkeeping in the
+ * library and the records on the device from the chains to the extension: the strand choice, the compaction of the chosen chains into
+ * primaries, the table of the 2 P rows (sorted by target and query on the device) and the extension's side descriptors and fold are
+ * kernels (csrc/overlap_dev.hip, csrc/align_dev.hip; DESIGN.md section 10, "Pairs on the device"); the host reads counts and, once, the
+ * finished primaries and the table.
+ * Specification: for the same reads and parameters the handle equals, field for field, what the stepwise chain gives —
+ * herro_find_overlaps; its rows paired (row B is row A's exact swap; the first of the two is the primary: api.pair_rows of the Python
+ * binding); herro_extend_overlaps over the primaries; the table of api.paired_job_args.  That is: P primaries in ascending (tid, qid)
+ * with tid < qid, extended unless HERRO_PAIRS_NO_EXTEND; their chain scores; the extension's ext and scores (zeros with the flag); and
+ * the finder's 2 P rows as target_ids / aln_off (grouped by target, ascending tid then qid) with rec_of_row[i] = p for the row that is
+ * primary p and P + p for the row that is its mirror — the record indices of the handle herro_pairs_align returns.
+ * herro_find_overlap_pairs: parameters as herro_find_overlaps and herro_extend_overlaps (NULL: defaults), checked first, then
+ * HERRO_E_NO_DEVICE on a device-free context, then HERRO_E_STATE without reads; HERRO_E_UNSUPPORTED: the finder's limits and more than
+ * 2^31 - 1 pairs.  Scratch and chunking as herro_find_overlaps (HERRO_OVL_SCRATCH_MB; the same bytes for every budget).
+ * herro_pairs_from_table: a handle over a table the host built itself; works on a device-free context, as herro_aligned_dev_from_ops
+ * does.  HERRO_E_INVALID naming the offending index: a primary that fails the record checks of herro_align_overlaps, an aln_off that does
+ * not ascend from 0 to 2 P, a rec_of_row that does not hold every value of 0 .. 2 P - 1 once.  chain_scores may be NULL (zeros).
+ * herro_pairs_align: herro_align_overlaps_dev over the primaries, then herro_aligned_dev_mirror — their codes and messages; out holds
+ * 2 P records, primaries then mirrors.  HERRO_E_INVALID: a handle of another context.
+ * herro_job_create_paired: herro_job_create_aligned over the table with every row whose record failed (no ops) dropped; a target all of
+ * whose rows failed keeps its place.  m must hold exactly 2 P records and belong, like the pairs, to ctx: else NULL and HERRO_E_INVALID
+ * through herro_job_create_status.  Everything else as herro_job_create_aligned.  Handles may be freed once the job exists. */
+typedef struct herro_pairs herro_pairs;
+#define HERRO_PAIRS_NO_EXTEND 1u
+int herro_find_overlap_pairs(herro_ctx* ctx, const herro_overlap_params* params /* NULL: defaults */,
+                             const herro_extend_params* extend_params /* NULL: defaults */, uint32_t flags, herro_pairs** out);
+int herro_pairs_from_table(herro_ctx* ctx, uint32_t n_pairs, const herro_alignment* primaries, const int32_t* chain_scores, uint32_t n_targets,
+                           const uint32_t* rids, const uint64_t* aln_off /* [n_targets + 1] */, const uint32_t* rec_of_row /* [2 n_pairs] */,
+                           herro_pairs** out);
+int herro_pairs_align(herro_ctx* ctx, const herro_pairs* pairs, herro_aligned_dev** out);
+herro_job* herro_job_create_paired(herro_ctx* ctx, const herro_pairs* pairs, const herro_aligned_dev* m, uint32_t window_size);
+uint32_t herro_pairs_n(const herro_pairs* pairs);                          /* P */
+const herro_alignment* herro_pairs_primaries(const herro_pairs* pairs);    /* [P]; cigar = NULL, cigar_len = 0 */
+const int32_t* herro_pairs_chain_scores(const herro_pairs* pairs);         /* [P] */
+const uint32_t* herro_pairs_ext(const herro_pairs* pairs);                 /* [P][4]: t_left, q_left, t_right, q_right as herro_extended_ext */
+const int32_t* herro_pairs_ext_scores(const herro_pairs* pairs);           /* [P][2]: left, right */
+uint32_t herro_pairs_n_targets(const herro_pairs* pairs);
+const uint32_t* herro_pairs_target_ids(const herro_pairs* pairs);          /* [n_targets] */
+const uint64_t* herro_pairs_aln_off(const herro_pairs* pairs);             /* [n_targets + 1] */
+const uint32_t* herro_pairs_rec_of_row(const herro_pairs* pairs);          /* [2 P] */
+void herro_pairs_free(herro_pairs* pairs);
 /* Test hook: stage 1 alone — the store's minimizers sorted by (rid, pos); pos = index of the k-mer's last base on the forward
  * read, strand = 1 when the reverse complement is the canonical k-mer.  Returns their number (nothing is written when cap is
  * smaller) or a negative error. */
