@@ -42,6 +42,7 @@ EXPORTS = [
     "herro_find_overlap_pairs", "herro_pairs_from_table", "herro_pairs_align", "herro_job_create_paired", "herro_pairs_n", "herro_pairs_primaries",
     "herro_pairs_chain_scores", "herro_pairs_ext", "herro_pairs_ext_scores", "herro_pairs_n_targets", "herro_pairs_target_ids", "herro_pairs_aln_off",
     "herro_pairs_rec_of_row", "herro_pairs_free",
+    "herro_find_overlaps_core", "herro_find_overlap_pairs_core", "herro_pairs_from_table_core", "herro_pairs_n_rows",
 ]
 
 
@@ -265,6 +266,15 @@ def lib():
             f.argtypes = [vp]
         L.herro_pairs_free.restype = None
         L.herro_pairs_free.argtypes = [vp]
+        try:   # (an older build selected by HERRO_LIB lacks the core-mask entries: its unmasked calls still run)
+            L.herro_find_overlaps_core.argtypes = [vp, vp, vp, vp]
+            L.herro_find_overlap_pairs_core.argtypes = [vp, vp, vp, u32, vp, vp]
+            L.herro_pairs_from_table_core.argtypes = [vp, u32, vp, vp, u32, vp, vp, u64, vp, vp]
+            L.herro_pairs_n_rows.restype = u64
+            L.herro_pairs_n_rows.argtypes = [vp]
+        except AttributeError:
+            if not os.environ.get("HERRO_LIB"):
+                raise
         L.herro_debug_sketch.restype = C.c_int64
         L.herro_debug_sketch.argtypes = [vp, vp, vp, vp, vp, vp, u64]
         L.herro_debug_host_ctx.restype = vp
@@ -479,10 +489,12 @@ class Context:
         nc = None if name_class is None else np.ascontiguousarray(name_class, np.uint32)
         self._chk(self._l.herro_set_reads(self.h, len(off) - 1, seq.ctypes.data, qual.ctypes.data, off.ctypes.data,
                                           None if nc is None else nc.ctypes.data))
+        self.n_reads = len(off) - 1
 
     def share_reads(self, other: "Context"):
         """Adopt the read store of another context of the same device (herro_share_reads): one copy in HBM per device."""
         self._chk(self._l.herro_share_reads(self.h, other.h))
+        self.n_reads = getattr(other, "n_reads", None)
 
     def load_model(self, path: str):
         self._chk(self._l.herro_load_model(self.h, path.encode()))
@@ -635,14 +647,28 @@ class Context:
             setattr(p, name, v)
         return p
 
-    def find_overlaps(self, **params):
+    def _core_mask(self, core):
+        """a core mask as the library takes it: u8 [n_reads], non-zero = the read is a target.  Its length must be the store's read count."""
+        m = np.ascontiguousarray(core)
+        m = np.ascontiguousarray(m, np.uint8) if m.dtype == np.uint8 else np.ascontiguousarray(m != 0, np.uint8)
+        n = getattr(self, "n_reads", None)   # (None: no reads yet — the call answers HERRO_E_STATE)
+        if m.ndim != 1 or (n is not None and len(m) != n):
+            raise ValueError(f"core has shape {m.shape}, the read store {n} reads")
+        return m
+
+    def find_overlaps(self, core=None, **params):
         """Which reads of the store overlap, where, on which strand (herro_find_overlaps; the seeding and chaining of the
         `minimap2 -x ava-ont` run of mm2.rs:15-30).  params: k, w, max_occ, bandwidth, max_gap, min_score, min_anchors.
         Returns (rids u32 [n_targets], rows u32 [n, 10] in create_job's layout with cigar_len 0, aln_off u64 [n_targets + 1],
-        scores i32 [n]): rows goes into Context.align, (rids, aln_off) with its result into aligned_job_args."""
+        scores i32 [n]): rows goes into Context.align, (rids, aln_off) with its result into aligned_job_args.
+        core: u8 [n_reads], non-zero = the read is a target (herro_find_overlaps_core): the records whose tid is core; None: all."""
         p = self._overlap_params(params)
         h = C.c_void_p()
-        self._chk(self._l.herro_find_overlaps(self.h, C.byref(p), C.byref(h)))
+        if core is None:
+            self._chk(self._l.herro_find_overlaps(self.h, C.byref(p), C.byref(h)))
+        else:
+            m = self._core_mask(core)
+            self._chk(self._l.herro_find_overlaps_core(self.h, C.byref(p), m.ctypes.data, C.byref(h)))
         try:
             n, nt = self._l.herro_overlaps_n(h), self._l.herro_overlaps_n_targets(h)
             rids = np.ctypeslib.as_array(C.cast(self._l.herro_overlaps_target_ids(h), C.POINTER(C.c_uint32)), (nt,)).copy() if nt else np.zeros(0, np.uint32)
@@ -680,31 +706,44 @@ class Context:
             self._l.herro_extended_free(h)
         return out, ext, scores
 
-    def find_overlap_pairs(self, extend: bool = True, zdrop: int = 0, max_ext: int = 0, **params) -> "OverlapPairs":
+    def find_overlap_pairs(self, extend: bool = True, zdrop: int = 0, max_ext: int = 0, core=None, **params) -> "OverlapPairs":
         """find_overlaps, pair_rows, extend_overlaps over the primaries and paired_job_args' table in one call that keeps the records on the
         device (herro_find_overlap_pairs): one record per read pair and the table of the finder's two rows per pair.  params as
-        find_overlaps; zdrop, max_ext as extend_overlaps; extend=False: HERRO_PAIRS_NO_EXTEND, the chains' anchor spans as they are."""
+        find_overlaps; zdrop, max_ext as extend_overlaps; extend=False: HERRO_PAIRS_NO_EXTEND, the chains' anchor spans as they are.
+        core: u8 [n_reads], non-zero = the read is a target (herro_find_overlap_pairs_core): only pairs with a core read are chained, extended
+        and later aligned, and the table holds only the rows whose target is core — a selection of the unmasked handle; None: all reads."""
         p = self._overlap_params(params)
         if not 0 <= int(zdrop) <= 0xFFFFFFFF or not 0 <= int(max_ext) <= 0xFFFFFFFF:
             raise HerroError(-1, "extend parameters: zdrop and max_ext are unsigned 32-bit values")
         e = ExtendParams(zdrop=int(zdrop), max_ext=int(max_ext))
         h = C.c_void_p()
-        self._chk(self._l.herro_find_overlap_pairs(self.h, C.byref(p), C.byref(e), 0 if extend else PAIRS_NO_EXTEND, C.byref(h)))
+        flags = 0 if extend else PAIRS_NO_EXTEND
+        if core is None:
+            self._chk(self._l.herro_find_overlap_pairs(self.h, C.byref(p), C.byref(e), flags, C.byref(h)))
+        else:
+            m = self._core_mask(core)
+            self._chk(self._l.herro_find_overlap_pairs_core(self.h, C.byref(p), C.byref(e), flags, m.ctypes.data, C.byref(h)))
         return OverlapPairs(self, h)
 
-    def pairs_from_table(self, primaries: np.ndarray, chain_scores, rids, aln_off, rec_of_row) -> "OverlapPairs":
+    def pairs_from_table(self, primaries: np.ndarray, chain_scores, rids, aln_off, rec_of_row, n_rows: int | None = None) -> "OverlapPairs":
         """A handle over a table the caller built (herro_pairs_from_table; also on a HostContext): primaries u32 [P, >= 9] as rows[prim],
-        chain_scores i32 [P] or None, (rids, aln_off) the grouping of the 2 P rows by target, rec_of_row as pair_rows returns it."""
+        chain_scores i32 [P] or None, (rids, aln_off) the grouping of the 2 P rows by target, rec_of_row as pair_rows returns it.
+        n_rows: a table of core targets (herro_pairs_from_table_core) — n_rows <= 2 P rows, rec_of_row has n_rows entries."""
         rows = np.ascontiguousarray(primaries, np.uint32)
         n = len(rows)
         sc = None if chain_scores is None else np.ascontiguousarray(chain_scores, np.int32)
         rids = np.ascontiguousarray(rids, np.uint32)
         aln_off = np.ascontiguousarray(aln_off, np.uint64)
         rec_of_row = np.ascontiguousarray(rec_of_row, np.uint32)
-        if len(aln_off) != len(rids) + 1 or len(rec_of_row) != 2 * n or (sc is not None and len(sc) != n):
-            raise ValueError("aln_off has one entry per target + 1, rec_of_row two per primary, chain_scores one")
+        if len(aln_off) != len(rids) + 1 or len(rec_of_row) != (2 * n if n_rows is None else int(n_rows)) or (sc is not None and len(sc) != n):
+            raise ValueError("aln_off has one entry per target + 1, rec_of_row two per primary (n_rows with n_rows), chain_scores one")
         arr, _ = _aln_array(rows)
         h = C.c_void_p()
+        if n_rows is not None:
+            self._chk(self._l.herro_pairs_from_table_core(self.h, n, C.byref(arr), None if sc is None else sc.ctypes.data, len(rids),
+                                                          rids.ctypes.data if len(rids) else None, aln_off.ctypes.data, int(n_rows),
+                                                          rec_of_row.ctypes.data if len(rec_of_row) else None, C.byref(h)))
+            return OverlapPairs(self, h)
         self._chk(self._l.herro_pairs_from_table(self.h, n, C.byref(arr), None if sc is None else sc.ctypes.data, len(rids),
                                                  rids.ctypes.data if len(rids) else None, aln_off.ctypes.data,
                                                  rec_of_row.ctypes.data if n else None, C.byref(h)))
@@ -958,13 +997,15 @@ class OverlapPairs:
     """herro_pairs: one record per overlapping read pair and the table of the finder's two rows per pair.  n_pairs = P; primaries u32
     [P, 10] (ascending (tid, qid), extended unless extend=False, cigar_len 0); chain_scores i32 [P]; ext u32 [P, 4] and ext_scores i32
     [P, 2] as extend_overlaps returns them (zeros without extension or from a table); rids u32 [n_targets], aln_off u64 [n_targets + 1],
-    rec_of_row u32 [2 P] as find_overlaps and pair_rows give them."""
+    rec_of_row u32 [n_rows] as find_overlaps and pair_rows give them; n_rows = 2 P, fewer for a handle of core targets (find_overlap_pairs(core=...):
+    the rows whose target is core)."""
 
     def __init__(self, ctx: Context, h):
         self.ctx, self.h, self._l = ctx, h, ctx._l
         L = self._l
         n = self.n_pairs = int(L.herro_pairs_n(h))
         nt = int(L.herro_pairs_n_targets(h))
+        self.n_rows = int(L.herro_pairs_n_rows(h)) if hasattr(L, "herro_pairs_n_rows") else 2 * n
 
         def arr(ptr, ct, dt, shape):
             out = np.zeros(shape, dt)
@@ -977,7 +1018,7 @@ class OverlapPairs:
         self.ext_scores = arr(L.herro_pairs_ext_scores(h), C.c_int32, np.int32, (n, 2))
         self.rids = arr(L.herro_pairs_target_ids(h), C.c_uint32, np.uint32, (nt,))
         self.aln_off = arr(L.herro_pairs_aln_off(h), C.c_uint64, np.uint64, (nt + 1,))
-        self.rec_of_row = arr(L.herro_pairs_rec_of_row(h), C.c_uint32, np.uint32, (2 * n,))
+        self.rec_of_row = arr(L.herro_pairs_rec_of_row(h), C.c_uint32, np.uint32, (self.n_rows,))
 
     def align(self) -> "AlignedDev":
         """herro_pairs_align: Context.align_dev(self.primaries).mirror() — 2 P records, primaries then mirrors."""
@@ -1008,6 +1049,7 @@ class HostContext(Context):
         rl = np.ascontiguousarray(read_len, np.uint32)
         nc = None if name_class is None else np.ascontiguousarray(name_class, np.uint32)
         self.h = self._l.herro_debug_host_ctx(len(rl), rl.ctypes.data, None if nc is None else nc.ctypes.data)
+        self.n_reads = len(rl)
 
 class NameIndex:
     """read name -> read id, built once per read set (herro_name_index_create; the reference's `name_to_id`, lib.rs:136-140)."""

@@ -1,5 +1,5 @@
 // frontend_api.hip — the C ABI's front end (include/herro_amd.h): reads alone -> overlap records -> their ops on the device.
-// herro_find_overlaps, herro_extend_overlaps, herro_align_overlaps[_dev], herro_aligned_dev_*, herro_find_overlap_pairs and herro_pairs_*.  Host C++ (compiled by hipcc) over
+// herro_find_overlaps[_core], herro_extend_overlaps, herro_align_overlaps[_dev], herro_aligned_dev_*, herro_find_overlap_pairs[_core] and herro_pairs_*.  Host C++ (compiled by hipcc) over
 // overlap_dev.hip and align_dev.hip; contexts, the model and jobs are herro_api.hip.
 #include <hip/hip_runtime.h>
 
@@ -173,6 +173,15 @@ void print_ovl_stats(const herro::OvlStats& stats) {
     if (atoi(e)) fprintf(stderr, "OVL kmers=%llu minimizers=%llu anchors=%llu groups=%llu chained=%llu chunks=%llu\n", (unsigned long long)stats.kmers,
                          (unsigned long long)stats.minimizers, (unsigned long long)stats.anchors, (unsigned long long)stats.groups,
                          (unsigned long long)stats.chained, (unsigned long long)stats.chunks);
+}
+
+// A call's core mask (n_reads bytes, non-zero: the read is a target) goes up once, into the call's scratch; NULL stays NULL: every read is core.
+int upload_core(herro_ctx* ctx, const char* who, const uint8_t* core, herro::Bufs& B, uint8_t** d_core) {
+  *d_core = nullptr;
+  if (!core) return HERRO_OK;
+  FRONT_TRY(ctx, who, "core mask", B.bytes(d_core, std::max<uint64_t>(ctx->n_reads, 1)));
+  FRONT_TRY(ctx, who, "core mask upload", hipMemcpyAsync(*d_core, core, ctx->n_reads, hipMemcpyHostToDevice, ctx->stream));
+  return HERRO_OK;
 }
 
 int overlap_rc(herro_ctx* ctx, int rc, const std::string& msg) {
@@ -485,7 +494,10 @@ struct herro_overlaps {
   std::vector<int32_t> scores;
 };
 
-int herro_find_overlaps(herro_ctx* ctx, const herro_overlap_params* params, herro_overlaps** out) {
+int herro_find_overlaps(herro_ctx* ctx, const herro_overlap_params* params, herro_overlaps** out) { return herro_find_overlaps_core(ctx, params, nullptr, out); }
+
+// core: the targets (overlaps.rs:154-159) — chains exist only for pairs with a core read, and a record only where its target is core
+int herro_find_overlaps_core(herro_ctx* ctx, const herro_overlap_params* params, const uint8_t* core, herro_overlaps** out) {
   if (!ctx || !out) return HERRO_E_INVALID;
   *out = nullptr;
   herro::OvlParams P;
@@ -495,7 +507,10 @@ int herro_find_overlaps(herro_ctx* ctx, const herro_overlap_params* params, herr
   std::vector<herro::OvlPair> chains;
   herro::OvlStats stats;
   std::string msg;
-  if (int rc = overlap_rc(ctx, herro::ovl_find(ovl_store(ctx), P, scratch_budget("HERRO_OVL_SCRATCH_MB"), ctx->stream, chains, stats, msg), msg)) return rc;
+  herro::Bufs CB;
+  uint8_t* d_core = nullptr;
+  if (int rc = upload_core(ctx, "herro_find_overlaps", core, CB, &d_core)) return rc;
+  if (int rc = overlap_rc(ctx, herro::ovl_find(ovl_store(ctx), P, d_core, scratch_budget("HERRO_OVL_SCRATCH_MB"), ctx->stream, chains, stats, msg), msg)) return rc;
   print_ovl_stats(stats);
   // one overlap per pair: chains arrive in ascending (t, q, rel), so the two strands of a pair are neighbours
   std::vector<herro::OvlPair> best;
@@ -511,8 +526,8 @@ int herro_find_overlaps(herro_ctx* ctx, const herro_overlap_params* params, herr
   recs.reserve(best.size() * 2);
   for (const herro::OvlPair& c : best) {
     const uint32_t tl = ctx->read_len[c.t], ql = ctx->read_len[c.q];
-    recs.push_back(Rec{herro_alignment{c.q, ql, c.qstart, c.qend, c.rel, c.t, tl, c.tstart, c.tend, 0, nullptr}, c.score});
-    recs.push_back(Rec{herro_alignment{c.t, tl, c.tstart, c.tend, c.rel, c.q, ql, c.qstart, c.qend, 0, nullptr}, c.score});   // the dual
+    if (!core || core[c.t]) recs.push_back(Rec{herro_alignment{c.q, ql, c.qstart, c.qend, c.rel, c.t, tl, c.tstart, c.tend, 0, nullptr}, c.score});
+    if (!core || core[c.q]) recs.push_back(Rec{herro_alignment{c.t, tl, c.tstart, c.tend, c.rel, c.q, ql, c.qstart, c.qend, 0, nullptr}, c.score});   // the dual
   }
   std::sort(recs.begin(), recs.end(), [](const Rec& x, const Rec& y) { return x.a.tid != y.a.tid ? x.a.tid < y.a.tid : x.a.qid < y.a.qid; });
   auto* h = new herro_overlaps();
@@ -545,10 +560,16 @@ struct herro_pairs {
   std::vector<int32_t> ext_scores;       // [P][2]
   std::vector<uint32_t> rids;            // targets of the 2 P rows
   std::vector<uint64_t> aln_off;         // [n_targets + 1]
-  std::vector<uint32_t> rec_of_row;      // [2 P]
+  std::vector<uint32_t> rec_of_row;      // [n_rows]: 2 P, fewer with a core mask
 };
 
 int herro_find_overlap_pairs(herro_ctx* ctx, const herro_overlap_params* params, const herro_extend_params* eparams, uint32_t flags, herro_pairs** out) {
+  return herro_find_overlap_pairs_core(ctx, params, eparams, flags, nullptr, out);
+}
+
+// core: the pairs with a core read, the rows with a core target (include/herro_amd.h, "a core set of targets")
+int herro_find_overlap_pairs_core(herro_ctx* ctx, const herro_overlap_params* params, const herro_extend_params* eparams, uint32_t flags, const uint8_t* core,
+                                  herro_pairs** out) {
   if (!ctx || !out) return HERRO_E_INVALID;
   *out = nullptr;
   const char* const who = "herro_find_overlap_pairs";
@@ -563,11 +584,14 @@ int herro_find_overlap_pairs(herro_ctx* ctx, const herro_overlap_params* params,
   herro::OvlRecs recs;
   herro::OvlStats stats;
   std::string msg;
-  if (int rc = overlap_rc(ctx, herro::ovl_find_pairs(ovl_store(ctx), P, scratch_budget("HERRO_OVL_SCRATCH_MB"), ctx->stream, recs, stats, msg), msg)) return rc;
+  herro::Bufs CB;
+  uint8_t* d_core = nullptr;
+  if (int rc = upload_core(ctx, who, core, CB, &d_core)) return rc;
+  if (int rc = overlap_rc(ctx, herro::ovl_find_pairs(ovl_store(ctx), P, d_core, scratch_budget("HERRO_OVL_SCRATCH_MB"), ctx->stream, recs, stats, msg), msg)) return rc;
   print_ovl_stats(stats);
   std::unique_ptr<herro_pairs> h(new herro_pairs());
   h->ctx = ctx;
-  if (int rc = overlap_rc(ctx, herro::ovl_row_table(recs, ctx->n_reads, ctx->stream, h->rids, h->aln_off, h->rec_of_row, msg), msg)) return rc;
+  if (int rc = overlap_rc(ctx, herro::ovl_row_table(recs, ctx->n_reads, d_core, ctx->stream, h->rids, h->aln_off, h->rec_of_row, msg), msg)) return rc;
   const uint32_t n = (uint32_t)recs.n;   // (<= 2^31 - 1: ovl_find_pairs)
   h->ext.assign((size_t)n * 4, 0);
   h->ext_scores.assign((size_t)n * 2, 0);
@@ -607,26 +631,29 @@ int herro_find_overlap_pairs(herro_ctx* ctx, const herro_overlap_params* params,
   return HERRO_OK;
 }
 
-int herro_pairs_from_table(herro_ctx* ctx, uint32_t n_pairs, const herro_alignment* primaries, const int32_t* chain_scores, uint32_t n_targets,
-                           const uint32_t* rids, const uint64_t* aln_off, const uint32_t* rec_of_row, herro_pairs** out) {
-  if (!ctx || !out || !aln_off || (n_pairs && (!primaries || !rec_of_row)) || (n_targets && !rids)) return HERRO_E_INVALID;
+namespace {
+// herro_pairs_from_table (`strict`: exactly 2 P rows, every record in one) and herro_pairs_from_table_core (n_rows <= 2 P rows, no record in two)
+int pairs_from_table(herro_ctx* ctx, const char* who, bool strict, uint32_t n_pairs, const herro_alignment* primaries, const int32_t* chain_scores,
+                     uint32_t n_targets, const uint32_t* rids, const uint64_t* aln_off, uint64_t n_rows, const uint32_t* rec_of_row, herro_pairs** out) {
+  if (!ctx || !out || !aln_off || (n_pairs && !primaries) || (n_rows && !rec_of_row) || (n_targets && !rids)) return HERRO_E_INVALID;
   *out = nullptr;
-  const char* const who = "herro_pairs_from_table";
   if (n_pairs > herro::OVL_MAX_PAIRS) { ctx->err = std::string(who) + ": more than 2^31 - 1 pairs"; return HERRO_E_UNSUPPORTED; }
   if (const int rc = check_record_fields(ctx, who, n_pairs, primaries)) return rc;
-  const uint64_t n_rows = 2ull * n_pairs;
-  for (uint32_t t = 0; t <= n_targets; t++) {   // aln_off[0] = 0, aln_off[n_targets] = 2 P, ascending between
+  const uint64_t n_recs = 2ull * n_pairs;
+  if (n_rows > n_recs) { ctx->err = std::string(who) + ": " + std::to_string(n_rows) + " rows for " + std::to_string(n_pairs) + " pairs: at most two rows per pair"; return HERRO_E_INVALID; }
+  for (uint32_t t = 0; t <= n_targets; t++) {   // aln_off[0] = 0, aln_off[n_targets] = n_rows, ascending between
     const uint64_t lo = t == n_targets ? n_rows : (t ? aln_off[t - 1] : 0), hi = t ? n_rows : 0;
     if (aln_off[t] < lo || aln_off[t] > hi) {
-      ctx->err = std::string(who) + ": aln_off[" + std::to_string(t) + "] = " + std::to_string(aln_off[t]) + ": aln_off must ascend from 0 to " + std::to_string(n_rows) + " (two rows per pair)";
+      ctx->err = std::string(who) + ": aln_off[" + std::to_string(t) + "] = " + std::to_string(aln_off[t]) + ": aln_off must ascend from 0 to " + std::to_string(n_rows) +
+                 (strict ? " (two rows per pair)" : " (the rows)");
       return HERRO_E_INVALID;
     }
   }
-  std::vector<bool> seen(n_rows, false);
+  std::vector<bool> seen(n_recs, false);
   for (uint64_t i = 0; i < n_rows; i++) {
     const uint32_t r = rec_of_row[i];
-    if (r >= n_rows || seen[r]) {
-      ctx->err = std::string(who) + ": rec_of_row[" + std::to_string(i) + "] = " + std::to_string(r) + (r >= n_rows ? " is outside the " + std::to_string(n_rows) + " records" : " occurs twice");
+    if (r >= n_recs || seen[r]) {
+      ctx->err = std::string(who) + ": rec_of_row[" + std::to_string(i) + "] = " + std::to_string(r) + (r >= n_recs ? " is outside the " + std::to_string(n_recs) + " records" : " occurs twice");
       return HERRO_E_INVALID;
     }
     seen[r] = true;
@@ -644,6 +671,17 @@ int herro_pairs_from_table(herro_ctx* ctx, uint32_t n_pairs, const herro_alignme
   h->rec_of_row.assign(rec_of_row, rec_of_row + n_rows);
   *out = h.release();
   return HERRO_OK;
+}
+}  // namespace
+
+int herro_pairs_from_table(herro_ctx* ctx, uint32_t n_pairs, const herro_alignment* primaries, const int32_t* chain_scores, uint32_t n_targets,
+                           const uint32_t* rids, const uint64_t* aln_off, const uint32_t* rec_of_row, herro_pairs** out) {
+  return pairs_from_table(ctx, "herro_pairs_from_table", true, n_pairs, primaries, chain_scores, n_targets, rids, aln_off, 2ull * n_pairs, rec_of_row, out);
+}
+
+int herro_pairs_from_table_core(herro_ctx* ctx, uint32_t n_pairs, const herro_alignment* primaries, const int32_t* chain_scores, uint32_t n_targets,
+                                const uint32_t* rids, const uint64_t* aln_off, uint64_t n_rows, const uint32_t* rec_of_row, herro_pairs** out) {
+  return pairs_from_table(ctx, "herro_pairs_from_table_core", false, n_pairs, primaries, chain_scores, n_targets, rids, aln_off, n_rows, rec_of_row, out);
 }
 
 int herro_pairs_align(herro_ctx* ctx, const herro_pairs* p, herro_aligned_dev** out) {
@@ -666,8 +704,8 @@ herro_job* herro_job_create_paired(herro_ctx* ctx, const herro_pairs* p, const h
   };
   if (!p || !m) return fail("null handle");
   if (p->ctx != ctx || m->ctx != ctx) return fail("the handle belongs to another context");
-  if (m->alns.size() != p->rec_of_row.size())
-    return fail("the aligned handle has " + std::to_string(m->alns.size()) + " records, the pairs need " + std::to_string(p->rec_of_row.size()) + " (primaries, then mirrors)");
+  if (m->alns.size() != 2 * p->alns.size())   // (not the row count: a table of core targets has fewer rows than records)
+    return fail("the aligned handle has " + std::to_string(m->alns.size()) + " records, the pairs need " + std::to_string(2 * p->alns.size()) + " (primaries, then mirrors)");
   // api.paired_job_args: a row whose record failed is dropped, the rest regrouped over the targets, which keep their place
   const uint32_t nt = (uint32_t)p->rids.size();
   std::vector<uint64_t> off(nt + 1ull, 0);
@@ -690,6 +728,7 @@ uint32_t herro_pairs_n_targets(const herro_pairs* p) { return p ? (uint32_t)p->r
 const uint32_t* herro_pairs_target_ids(const herro_pairs* p) { return p ? p->rids.data() : nullptr; }
 const uint64_t* herro_pairs_aln_off(const herro_pairs* p) { return p ? p->aln_off.data() : nullptr; }
 const uint32_t* herro_pairs_rec_of_row(const herro_pairs* p) { return p ? p->rec_of_row.data() : nullptr; }
+uint64_t herro_pairs_n_rows(const herro_pairs* p) { return p ? p->rec_of_row.size() : 0; }
 void herro_pairs_free(herro_pairs* p) { delete p; }
 
 int64_t herro_debug_sketch(herro_ctx* ctx, const herro_overlap_params* params, uint64_t* hash, uint32_t* rid, uint32_t* pos,

@@ -43,8 +43,12 @@ int ovl_sketch(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vecto
                std::string& err);
 
 // every kept (t, q) chain per strand, ascending (t, q, rel); the caller picks the strand and writes the dual records
-int ovl_find(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hipStream_t st, std::vector<OvlPair>& out, OvlStats& stats,
-             std::string& err);
+// d_core (here and below): NULL — every read is a target — or the core mask on the device, n_reads bytes, non-zero = core (the PAF
+// entries' `core`: overlaps.rs:154-159).  No anchor is created between two non-core reads (k_runs, k_expand), so the sorts, the chains and
+// all behind them see only pairs with a core read; max_occ stays the whole store's cut, chains are independent per (t, q, rel), and the
+// result is therefore the unmasked one restricted to those pairs.  OvlStats.anchors and the limits count the masked anchors.
+int ovl_find(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uint64_t budget_bytes, hipStream_t st, std::vector<OvlPair>& out,
+             OvlStats& stats, std::string& err);
 
 // ---- one overlap per pair, left on the device ("Pairs on the device") -------------------------------------------------------
 constexpr uint64_t OVL_MAX_PAIRS = 0x7fffffffull;   // the mirror's record limit; 2 P rows stay inside the sort's 32-bit count
@@ -66,12 +70,13 @@ struct OvlRecs {             // a device array of records; it owns its memory
 
 // ovl_find with the strand choice on the device: the better strand of every pair (forward on a tie) as one record, in ascending
 // (t, q) order — the primaries of api.pair_rows over herro_find_overlaps' records.  The host reads one count per chunk.
-int ovl_find_pairs(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hipStream_t st, OvlRecs& out, OvlStats& stats,
-                   std::string& err);
+int ovl_find_pairs(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uint64_t budget_bytes, hipStream_t st, OvlRecs& out,
+                   OvlStats& stats, std::string& err);
 
 // The 2 P rows herro_find_overlaps emits for P primaries — (t, q) and (q, t) of each, by (tid, qid) — as a table: rids / aln_off group
 // them by target, rec_of_row[i] is p for the row that is primary p and P + p for its mirror.  Sorted and grouped on the device.
-int ovl_row_table(const OvlRecs& R, uint32_t n_reads, hipStream_t st, std::vector<uint32_t>& rids, std::vector<uint64_t>& aln_off,
-                  std::vector<uint32_t>& rec_of_row, std::string& err);
+// With d_core only the rows whose target is core: one or two per primary, rec_of_row.size() <= 2 P.
+int ovl_row_table(const OvlRecs& R, uint32_t n_reads, const uint8_t* d_core, hipStream_t st, std::vector<uint32_t>& rids,
+                  std::vector<uint64_t>& aln_off, std::vector<uint32_t>& rec_of_row, std::string& err);
 
 }  // namespace herro

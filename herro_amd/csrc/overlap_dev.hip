@@ -9,6 +9,8 @@
 //                sorted by A carrying B, then by B carrying A (stable): order (t, q, rel, tpos, qpos).
 //   k_chain      one wave64 per (t, q, rel) group: the 64 predecessors of an anchor are the 64 lanes.
 //   k_walk       back through the stored predecessors: first anchor, anchor count, coordinates.
+// A core mask (one byte per read, non-zero: the read is a target) keeps k_runs / k_expand from creating an anchor between two non-core
+// reads, so everything behind the anchors sees wanted pairs only; without a mask (CORE = false) the two kernels are what they were.
 // Nothing an atomic orders reaches the output: the only atomics are integer sums (histograms, anchors per read).
 #include "overlap_dev.h"
 #include "dev_bufs.h"
@@ -240,9 +242,12 @@ __global__ __launch_bounds__(256) void k_rs_scatter(const uint64_t* __restrict__
 // ---- runs of one hash, frequency cut, anchors per occurrence --------------------------------------------------------------
 // cnt[x]: anchors occurrence x has as the target side = occurrences behind it in its run that lie in another (later) read;
 // run_end[x]: end of its run.  Runs longer than max_occ (and single occurrences) keep cnt 0 (cleared before the launch).
+// CORE: an occurrence in a non-core read counts only the later occurrences whose read is core — none of them is in its own read, which is
+// not core.  An occurrence in a core read keeps the count above.  The frequency cut is the whole store's, whatever the mask.
+template <bool CORE>
 __global__ __launch_bounds__(256) void k_runs(const uint64_t* __restrict__ hash, const uint64_t* __restrict__ meta, uint32_t n,
                                               uint32_t max_occ, uint32_t* __restrict__ cnt, uint32_t* __restrict__ run_end,
-                                              unsigned long long* __restrict__ per_read) {
+                                              unsigned long long* __restrict__ per_read, const uint8_t* __restrict__ core) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const uint64_t h = hash[i];
@@ -253,11 +258,17 @@ __global__ __launch_bounds__(256) void k_runs(const uint64_t* __restrict__ hash,
   if (c < 2 || c > max_occ) return;
   uint64_t nxt = e;                            // first occurrence of the next read
   uint32_t rid_after = 0;
+  uint32_t core_after = 0;                     // CORE: occurrences behind j whose read is core
   for (uint64_t j = e; j-- > i;) {
     const uint32_t rid = (uint32_t)(meta[j] >> 32);
     if (j + 1 < e && rid != rid_after) nxt = j + 1;
     rid_after = rid;
-    const uint32_t m = (uint32_t)(e - nxt);
+    uint32_t m = (uint32_t)(e - nxt);
+    if constexpr (CORE) {
+      const bool is_core = core[rid] != 0;
+      if (!is_core) m = core_after;
+      core_after += is_core ? 1u : 0u;
+    }
     cnt[j] = m;
     run_end[j] = (uint32_t)e;
     if (m) atomicAdd(&per_read[rid], (unsigned long long)m);
@@ -272,10 +283,13 @@ __global__ __launch_bounds__(256) void k_mask(const uint64_t* __restrict__ meta,
   out[i] = rid >= t_lo && rid < t_hi ? cnt[i] : 0u;
 }
 
+// CORE: a non-core occurrence has its cntm[x] partners scattered over the rest of its run — the occurrences of core reads; it walks the
+// run from itself on (at most max_occ steps) and skips the others, those of its own read among them.
+template <bool CORE>
 __global__ __launch_bounds__(256) void k_expand(const uint64_t* __restrict__ meta, const uint32_t* __restrict__ cntm,
                                                 const uint32_t* __restrict__ run_end, const uint32_t* __restrict__ aoff, uint32_t n,
                                                 const uint64_t* __restrict__ base_off, uint32_t k, uint32_t t_lo,
-                                                uint64_t* __restrict__ A, uint64_t* __restrict__ B) {
+                                                uint64_t* __restrict__ A, uint64_t* __restrict__ B, const uint8_t* __restrict__ core) {
   const uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (x >= n) return;
   const uint32_t c = cntm[x];
@@ -284,13 +298,21 @@ __global__ __launch_bounds__(256) void k_expand(const uint64_t* __restrict__ met
   const uint32_t t = (uint32_t)(mx >> 32), tpos = ((uint32_t)mx) >> 1, st = (uint32_t)mx & 1u;
   const uint32_t e = run_end[x];
   uint32_t at = aoff[x];
-  for (uint32_t y = e - c; y < e; y++, at++) {
+  bool sparse = false;
+  if constexpr (CORE) sparse = core[t] == 0;
+  const uint32_t at_end = at + c;
+  for (uint32_t y = sparse ? (uint32_t)x + 1 : e - c; y < e; y++) {
     const uint64_t my = meta[y];
     const uint32_t q = (uint32_t)(my >> 32), qp = ((uint32_t)my) >> 1, rel = ((uint32_t)my & 1u) ^ st;
+    if constexpr (CORE) {
+      if (at == at_end) break;                              // (its c partners are written: nothing behind them is core)
+      if (sparse && core[q] == 0) continue;
+    }
     const uint32_t qlen = (uint32_t)(base_off[q + 1] - base_off[q]);
     const uint32_t qpos = rel ? qlen - qp + k - 2 : qp;     // last base of the same k-mer on the query's reverse complement
     A[at] = ((uint64_t)tpos << 32) | qpos;
     B[at] = ((uint64_t)(t - t_lo) << 33) | ((uint64_t)q << 1) | rel;
+    at++;
   }
 }
 
@@ -467,6 +489,24 @@ __global__ __launch_bounds__(256) void k_row_keys(const OvlRec* __restrict__ rec
   pays[np + p] = np + p;
 }
 
+// ... with a core mask: the row (t, q) only if t is core, the row (q, t) only if q is — rows_of[p] rows, written densely from row_at[p] on
+__global__ __launch_bounds__(256) void k_row_count(const OvlRec* __restrict__ rec, uint32_t np, const uint8_t* __restrict__ core,
+                                                   uint32_t* __restrict__ rows_of) {
+  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p < np) rows_of[p] = (core[rec[p].tid] ? 1u : 0u) + (core[rec[p].qid] ? 1u : 0u);
+}
+
+__global__ __launch_bounds__(256) void k_row_keys_core(const OvlRec* __restrict__ rec, uint32_t np, const uint8_t* __restrict__ core,
+                                                       const uint32_t* __restrict__ row_at, uint64_t* __restrict__ keys,
+                                                       uint64_t* __restrict__ pays) {
+  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= np) return;
+  const uint64_t t = rec[p].tid, q = rec[p].qid;
+  uint32_t at = row_at[p];
+  if (core[t]) { keys[at] = t << 32 | q; pays[at] = p; at++; }
+  if (core[q]) { keys[at] = q << 32 | t; pays[at] = np + p; }
+}
+
 __global__ __launch_bounds__(256) void k_row_heads(const uint64_t* __restrict__ keys, uint32_t n, uint32_t* __restrict__ flag) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) flag[i] = (i == 0 || (keys[i] >> 32) != (keys[i - 1] >> 32)) ? 1u : 0u;
@@ -616,9 +656,10 @@ namespace {
 // Sketch, sort, frequency cut and the chunk loop of ovl_find and ovl_find_pairs.  Behind every chunk's k_walk, take(nc, gout, ccap, t_hi, B) gets the
 // chunk's nc GroupOut records, still on the device, in ascending (t, q, rel): it takes what it wants before it returns or queues its kernels on st,
 // in front of the next chunk's k_walk, which overwrites gout.  ccap: the most records any chunk has; t_hi: the targets done so far, this chunk's
-// included; B: the call's scratch.
+// included; B: the call's scratch.  d_core: the core mask on the device (n_reads bytes) or NULL — every read is core.
 template <class Take>
-int find_chunks(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hipStream_t st, OvlStats& stats, std::string& err, Take take) {
+int find_chunks(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uint64_t budget_bytes, hipStream_t st, OvlStats& stats, std::string& err,
+                Take take) {
   stats = OvlStats{};
   Bufs B;
   Sketch sk;
@@ -648,7 +689,8 @@ int find_chunks(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hi
   OVL_TRY(B.get(&d_per_read, S.n_reads));
   OVL_TRY(hipMemsetAsync(d_cnt, 0, 4ull * nm, st));
   OVL_TRY(hipMemsetAsync(d_per_read, 0, 8ull * S.n_reads, st));
-  k_runs<<<nblk(nm, 256), 256, 0, st>>>(sk.hash, sk.meta, nm, P.max_occ, d_cnt, d_run_end, d_per_read);
+  if (d_core) k_runs<true><<<nblk(nm, 256), 256, 0, st>>>(sk.hash, sk.meta, nm, P.max_occ, d_cnt, d_run_end, d_per_read, d_core);
+  else k_runs<false><<<nblk(nm, 256), 256, 0, st>>>(sk.hash, sk.meta, nm, P.max_occ, d_cnt, d_run_end, d_per_read, nullptr);
   OVL_TRY(hipGetLastError());
   std::vector<unsigned long long> per_read(S.n_reads);
   OVL_TRY(hipMemcpyAsync(per_read.data(), d_per_read, 8ull * S.n_reads, hipMemcpyDeviceToHost, st));
@@ -700,7 +742,8 @@ int find_chunks(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hi
     const uint32_t na = (uint32_t)na64;
     k_mask<<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cnt, nm, t_lo, t_hi, d_cntm);
     if (int rc = scan_u32(d_cntm, nm, d_aoff, ms.partial, st, err)) return rc;
-    k_expand<<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0);
+    if (d_core) k_expand<true><<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, d_core);
+    else k_expand<false><<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, nullptr);
     OVL_TRY(hipGetLastError());
     {
       std::vector<uint32_t> sa, sb;
@@ -738,11 +781,11 @@ int find_chunks(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hi
 }
 }  // namespace
 
-int ovl_find(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hipStream_t st, std::vector<OvlPair>& out, OvlStats& stats,
-             std::string& err) {
+int ovl_find(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uint64_t budget_bytes, hipStream_t st, std::vector<OvlPair>& out,
+             OvlStats& stats, std::string& err) {
   out.clear();
   std::vector<GroupOut> h_out;
-  return find_chunks(S, P, budget_bytes, st, stats, err, [&](uint32_t nc, const GroupOut* gout, uint64_t, uint32_t, Bufs&) -> int {
+  return find_chunks(S, P, d_core, budget_bytes, st, stats, err, [&](uint32_t nc, const GroupOut* gout, uint64_t, uint32_t, Bufs&) -> int {
     h_out.resize(nc);
     OVL_TRY(hipMemcpyAsync(h_out.data(), gout, sizeof(GroupOut) * (uint64_t)nc, hipMemcpyDeviceToHost, st));
     OVL_TRY(hipStreamSynchronize(st));
@@ -753,10 +796,11 @@ int ovl_find(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hipSt
 }
 
 // ---- one overlap per pair and the row table, on the device ("Pairs on the device") ---------------------------------------
-int ovl_find_pairs(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hipStream_t st, OvlRecs& out, OvlStats& stats, std::string& err) {
+int ovl_find_pairs(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uint64_t budget_bytes, hipStream_t st, OvlRecs& out, OvlStats& stats,
+                   std::string& err) {
   out.release();
   uint32_t *sel = nullptr, *soff = nullptr, *part = nullptr;
-  const int rc = find_chunks(S, P, budget_bytes, st, stats, err, [&](uint32_t nc, const GroupOut* gout, uint64_t ccap, uint32_t t_hi, Bufs& B) -> int {
+  const int rc = find_chunks(S, P, d_core, budget_bytes, st, stats, err, [&](uint32_t nc, const GroupOut* gout, uint64_t ccap, uint32_t t_hi, Bufs& B) -> int {
     if (!sel) {
       OVL_TRY(B.get(&sel, ccap));
       OVL_TRY(B.get(&soff, ccap + 1));
@@ -795,14 +839,15 @@ int ovl_find_pairs(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes,
   return OVL_OK;
 }
 
-int ovl_row_table(const OvlRecs& R, uint32_t n_reads, hipStream_t st, std::vector<uint32_t>& rids, std::vector<uint64_t>& aln_off,
+int ovl_row_table(const OvlRecs& R, uint32_t n_reads, const uint8_t* d_core, hipStream_t st, std::vector<uint32_t>& rids, std::vector<uint64_t>& aln_off,
                   std::vector<uint32_t>& rec_of_row, std::string& err) {
   rids.clear();
   aln_off.assign(1, 0);
   rec_of_row.clear();
   if (!R.n) return OVL_OK;
   if (R.n > OVL_MAX_PAIRS) { err = "overlap finder: more than 2^31 - 1 overlapping read pairs"; return OVL_UNSUPPORTED; }
-  const uint32_t np = (uint32_t)R.n, n = 2 * np;
+  const uint32_t np = (uint32_t)R.n;
+  uint32_t n = 2 * np;                            // rows; fewer with a core mask (counted below), the arrays are sized for 2 P
   Bufs B;
   SortScratch ss;
   OVL_TRY(ss.alloc(B, n));
@@ -814,8 +859,18 @@ int ovl_row_table(const OvlRecs& R, uint32_t n_reads, hipStream_t st, std::vecto
   uint64_t* d_off = (uint64_t*)(blk + 4 * a8);
   uint32_t *flag = (uint32_t*)(blk + 5 * a8), *tidx = (uint32_t*)(blk + 5 * a8 + a4), *d_rids = (uint32_t*)(blk + 5 * a8 + 2 * a4);
   uint32_t* d_rec = (uint32_t*)(blk + 5 * a8 + 3 * a4);
-  k_row_keys<<<nblk(np, 256), 256, 0, st>>>(R.d, np, k0, p0);
-  OVL_TRY(hipGetLastError());
+  if (d_core) {                                   // (flag / tidx hold the rows per primary and their scan until the keys are written)
+    k_row_count<<<nblk(np, 256), 256, 0, st>>>(R.d, np, d_core, flag);
+    if (int rc = scan_u32(flag, np, tidx, ss.partial, st, err)) return rc;
+    k_row_keys_core<<<nblk(np, 256), 256, 0, st>>>(R.d, np, d_core, tidx, k0, p0);
+    OVL_TRY(hipGetLastError());
+    OVL_TRY(hipMemcpyAsync(&n, tidx + np, 4, hipMemcpyDeviceToHost, st));
+    OVL_TRY(hipStreamSynchronize(st));
+    if (!n) return OVL_OK;
+  } else {
+    k_row_keys<<<nblk(np, 256), 256, 0, st>>>(R.d, np, k0, p0);
+    OVL_TRY(hipGetLastError());
+  }
   {
     std::vector<uint32_t> shifts;                 // keys are unique: one overlap per pair
     field_shifts(shifts, 0, bits_of(n_reads - 1));

@@ -677,6 +677,71 @@ def hip_corrector(ctxs, window_size: int, batch: int, read_name, group_targets: 
     return fn
 
 
+# =====================================================================================================================
+# Reads-only sharding: no alignments are ingested at all.  Every rank holds the read store and a CORE MASK — its share of the
+# reads as targets (core_masks: the partition above) — and runs the whole front end for those targets only
+# (Context.find_overlap_pairs(core=mask): overlaps.rs:154-159's core set on the device finder).  A pair whose two reads
+# belong to two ranks is chained and aligned once on each of them; a pair inside one rank once; a pair of two foreign reads
+# never.  Nothing is exchanged but the FASTA records, gathered as correct_sharded_local gathers them.
+# =====================================================================================================================
+def core_masks(read_lens, window_size: int, world: int) -> list[np.ndarray]:
+    """One core mask per rank (u8 [n_reads], 1 = the read is this rank's target): partition_targets over the reads' window counts.
+    Deterministic; every read is in exactly one mask; world = 1: all ones."""
+    n = len(read_lens)
+    out = []
+    for part in partition_targets(windows_of(read_lens, window_size), world):
+        m = np.zeros(n, np.uint8)
+        m[part] = 1
+        out.append(m)
+    return out
+
+
+def correct_reads_shard(ctx, mask, window_size: int, batch: int, batch_mode: int, read_name, group_targets: int = 1024, **finder_params):
+    """Reads-only correction of one shard on `ctx` (reads and model loaded): find_overlap_pairs(core=mask) -> align -> jobs of at most
+    `group_targets` targets cut from the table -> featurize -> infer -> consensus -> FASTA.  Rows whose record failed are dropped
+    (api.paired_job_args).  finder_params: find_overlap_pairs' keywords.  Returns (rids, ends, text) as merge_records takes them."""
+    from . import api
+    pairs = ctx.find_overlap_pairs(core=mask, **finder_params)
+    m = pairs.align()
+    try:
+        rids, off, rec = api.paired_job_args(pairs.rids, pairs.aln_off, pairs.rec_of_row, m.ok)
+        parts = []
+        for t0 in range(0, len(rids), group_targets):
+            t1 = min(t0 + group_targets, len(rids))
+            a0, a1 = int(off[t0]), int(off[t1])
+            job = ctx.create_job_aligned(rids[t0:t1], off[t0:t1 + 1] - off[t0], rec[a0:a1], m, window_size)
+            try:
+                job.featurize()
+                job.infer(batch, batch_mode)
+                job.consensus()
+                text, ends = job.fasta([read_name(int(r)) for r in rids[t0:t1]], with_ends=True, as_array=True)
+                parts.append((rids[t0:t1].copy(), ends, text))
+            finally:
+                job.close()
+    finally:
+        m.close()
+        pairs.close()
+    return merge_records(parts)
+
+
+def correct_reads_sharded(ctx, read_lens, window_size: int, batch: int, batch_mode: int, read_name, group=None, group_targets: int = 1024,
+                          **finder_params):
+    """correct_reads_shard for this rank's mask of core_masks, then correct_sharded_local's gather of the records to rank 0.
+    Returns ((rids, ends, text) on rank 0 else None, this rank's core reads)."""
+    dist = _dist()
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    mask = core_masks(read_lens, window_size, world)[rank]
+    rec = correct_reads_shard(ctx, mask, window_size, batch, batch_mode, read_name, group_targets=group_targets, **finder_params)
+    n_mine = int(np.count_nonzero(mask))
+    if _alone(world):
+        return merge_records([rec]), n_mine
+    gathered = gather_bytes(pack_records(*rec), group)
+    if rank != 0:
+        return None, n_mine
+    return merge_records([unpack_records(g) for g in gathered]), n_mine
+
+
 def strong_leg(args, rank: int, world: int, local: int, n_windows: int, n_ctx: int | None = None, model_path: str | None = None) -> dict | None:
     """ONE fixed set of `n_windows` synthetic windows (BASELINE configs[3]) sharded over the ranks.  Default (--strong-ingest local):
     every rank holds its own share of the parsed alignments (handed out once, outside the timed region — what per-rank ingestion of its

@@ -526,8 +526,40 @@ const int32_t* herro_pairs_ext_scores(const herro_pairs* pairs);           /* [P
 uint32_t herro_pairs_n_targets(const herro_pairs* pairs);
 const uint32_t* herro_pairs_target_ids(const herro_pairs* pairs);          /* [n_targets] */
 const uint64_t* herro_pairs_aln_off(const herro_pairs* pairs);             /* [n_targets + 1] */
-const uint32_t* herro_pairs_rec_of_row(const herro_pairs* pairs);          /* [2 P] */
+const uint32_t* herro_pairs_rec_of_row(const herro_pairs* pairs);          /* [2 P]; [herro_pairs_n_rows] of a core handle */
 void herro_pairs_free(herro_pairs* pairs);
+/* ---- a core set of targets: overlaps found and aligned for the core reads only ---------------------------------------------------------
+ * The PAF entries take `core` (one byte per read; overlaps.rs:154-159 drops the targets outside it, as `-c cluster` does: lib.rs:132-133,
+ * haec_io.rs:62-68 — a store of a core set plus its neighbours).  These entries take the same mask for the device front end, so that N
+ * ranks which hold the read store and correct 1/N of the reads each do not each chain, extend, align and mirror every pair of the store.
+ * core: n_reads bytes, non-zero = the read is core, i.e. a target; NULL = every read is core, and exactly the entry without `_core`.
+ *   A read pair is wanted iff at least one of its two reads is core; a row (target, query) is wanted iff its target is core.
+ * The finder creates no anchor between two non-core reads (k_runs, k_expand in csrc/overlap_dev.hip), so the sorts, the groups, the
+ * chains, the strand choice, the extension, the aligner and the mirror see wanted pairs only.  Chains are independent per (t, q, strand)
+ * and max_occ stays the cut of the whole store's index, so the result is a selection of the unmasked one.  With F the handle
+ * herro_find_overlap_pairs returns for the same reads and parameters:
+ *   primaries   those of F with core[tid] | core[qid], in F's order; chain_scores, ext and ext_scores the same selection; P' of them.
+ *   rows        F's rows whose target is core, in F's order: target_ids is F's targets that are core, aln_off counts the kept rows,
+ *               herro_pairs_n_rows = R' = sum over the kept primaries of core[tid] + core[qid] <= 2 P'.
+ *   rec_of_row  the new index of its primary for a primary row, P' + that index for a mirror row.
+ * herro_pairs_align is unchanged: 2 P' records, primaries then mirrors (the mirror kernel is ~1.5 % of the aligner: selecting mirrors is
+ * not worth a second layout).  herro_job_create_paired wants 2 P' records in m, whatever the number of rows.
+ * herro_find_overlaps_core: herro_find_overlaps' records whose tid is core, same order, same scores.
+ * The `anchors` figure of HERRO_OVL_STATS=1 and the limits (2^32 anchors per target or chunk, 2^31 - 1 pairs) count the masked anchors
+ * and pairs; chunking by HERRO_OVL_SCRATCH_MB stays byte-neutral.  Checks, codes and messages are those of the entries without `_core`.
+ * herro_pairs_from_table_core: herro_pairs_from_table for a table of n_rows <= 2 P rows; works on a device-free context.  HERRO_E_INVALID
+ * naming the index: aln_off does not ascend from 0 to n_rows, a rec_of_row value is >= 2 P or occurs twice; also n_rows > 2 P.
+ * herro_pairs_from_table keeps its stricter rule (every record in exactly one row).
+ * herro_pairs_n_rows: the rows of the table = entries of rec_of_row; 2 P for every handle made without a mask. */
+int herro_find_overlaps_core(herro_ctx* ctx, const herro_overlap_params* params /* NULL: defaults */, const uint8_t* core /* [n_reads] or NULL */,
+                             herro_overlaps** out);
+int herro_find_overlap_pairs_core(herro_ctx* ctx, const herro_overlap_params* params /* NULL: defaults */,
+                                  const herro_extend_params* extend_params /* NULL: defaults */, uint32_t flags,
+                                  const uint8_t* core /* [n_reads] or NULL */, herro_pairs** out);
+int herro_pairs_from_table_core(herro_ctx* ctx, uint32_t n_pairs, const herro_alignment* primaries, const int32_t* chain_scores, uint32_t n_targets,
+                                const uint32_t* rids, const uint64_t* aln_off /* [n_targets + 1] */, uint64_t n_rows,
+                                const uint32_t* rec_of_row /* [n_rows] */, herro_pairs** out);
+uint64_t herro_pairs_n_rows(const herro_pairs* pairs);
 /* Test hook: stage 1 alone — the store's minimizers sorted by (rid, pos); pos = index of the k-mer's last base on the forward
  * read, strand = 1 when the reverse complement is the canonical k-mer.  Returns their number (nothing is written when cap is
  * smaller) or a negative error. */
