@@ -43,6 +43,7 @@ EXPORTS = [
     "herro_pairs_chain_scores", "herro_pairs_ext", "herro_pairs_ext_scores", "herro_pairs_n_targets", "herro_pairs_target_ids", "herro_pairs_aln_off",
     "herro_pairs_rec_of_row", "herro_pairs_free",
     "herro_find_overlaps_core", "herro_find_overlap_pairs_core", "herro_pairs_from_table_core", "herro_pairs_n_rows",
+    "herro_overlaps_occ_cut", "herro_pairs_occ_cut", "herro_debug_occ_census",
 ]
 
 
@@ -93,7 +94,7 @@ PAIRS_NO_EXTEND = 1   # HERRO_PAIRS_NO_EXTEND
 
 
 class OverlapParams(C.Structure):  # herro_overlap_params (0 = the field's default)
-    _fields_ = [(n, C.c_uint32) for n in ("k", "w", "max_occ", "bandwidth", "max_gap", "min_score", "min_anchors", "reserved")]
+    _fields_ = [(n, C.c_uint32) for n in ("k", "w", "max_occ", "bandwidth", "max_gap", "min_score", "min_anchors", "occ_frac_ppm")]
 
 
 class ExtendParams(C.Structure):  # herro_extend_params (0 = the field's default)
@@ -272,6 +273,14 @@ def lib():
             L.herro_pairs_from_table_core.argtypes = [vp, u32, vp, vp, u32, vp, vp, u64, vp, vp]
             L.herro_pairs_n_rows.restype = u64
             L.herro_pairs_n_rows.argtypes = [vp]
+        except AttributeError:
+            if not os.environ.get("HERRO_LIB"):
+                raise
+        try:   # (an older build selected by HERRO_LIB lacks the fraction cut: its calls with occ_frac_ppm left out still run)
+            for f in (L.herro_overlaps_occ_cut, L.herro_pairs_occ_cut):
+                f.restype = u32
+                f.argtypes = [vp]
+            L.herro_debug_occ_census.argtypes = [vp, vp, vp, vp]
         except AttributeError:
             if not os.environ.get("HERRO_LIB"):
                 raise
@@ -456,6 +465,8 @@ class Window:
 
 
 class Context:
+    last_occ_cut = None   # the frequency cut of the latest find_overlaps
+
     def __init__(self, device: int = 0):
         self._l = lib()
         self.h = self._l.herro_create(device)
@@ -634,10 +645,13 @@ class Context:
 
     def _overlap_params(self, params: dict) -> OverlapParams:
         """keyword arguments -> herro_overlap_params.  A field left out (or None) takes its default, which the struct spells 0; an
-        explicit k or w outside 5 .. 31 / 1 .. 64 — 0 included, which the struct could not carry — is HERRO_E_INVALID here."""
+        explicit k or w outside 5 .. 31 / 1 .. 64 — 0 included, which the struct could not carry — is HERRO_E_INVALID here.
+        occ_frac_ppm (0 or left out: the fixed cut max_occ): the cut is taken from the store's index so that at most this many parts per
+        million of the distinct minimizers lie above it (minimap2's -f; 5000 = the reference's -f0.005), max_occ becomes its ceiling
+        (0: none); values outside 0 .. 999999 are the library's HERRO_E_INVALID."""
         p = OverlapParams()
         for name, v in params.items():
-            if name not in ("k", "w", "max_occ", "bandwidth", "max_gap", "min_score", "min_anchors"):
+            if name not in ("k", "w", "max_occ", "bandwidth", "max_gap", "min_score", "min_anchors", "occ_frac_ppm"):
                 raise TypeError(f"unknown overlap parameter {name!r}")
             if v is None:
                 continue
@@ -658,7 +672,8 @@ class Context:
 
     def find_overlaps(self, core=None, **params):
         """Which reads of the store overlap, where, on which strand (herro_find_overlaps; the seeding and chaining of the
-        `minimap2 -x ava-ont` run of mm2.rs:15-30).  params: k, w, max_occ, bandwidth, max_gap, min_score, min_anchors.
+        `minimap2 -x ava-ont` run of mm2.rs:15-30).  params: k, w, max_occ, bandwidth, max_gap, min_score, min_anchors, occ_frac_ppm.
+        The frequency cut the call used (max_occ, or the one occ_frac_ppm gave) is left in self.last_occ_cut.
         Returns (rids u32 [n_targets], rows u32 [n, 10] in create_job's layout with cigar_len 0, aln_off u64 [n_targets + 1],
         scores i32 [n]): rows goes into Context.align, (rids, aln_off) with its result into aligned_job_args.
         core: u8 [n_reads], non-zero = the read is a target (herro_find_overlaps_core): the records whose tid is core; None: all."""
@@ -671,6 +686,8 @@ class Context:
             self._chk(self._l.herro_find_overlaps_core(self.h, C.byref(p), m.ctypes.data, C.byref(h)))
         try:
             n, nt = self._l.herro_overlaps_n(h), self._l.herro_overlaps_n_targets(h)
+            if hasattr(self._l, "herro_overlaps_occ_cut"):
+                self.last_occ_cut = int(self._l.herro_overlaps_occ_cut(h))
             rids = np.ctypeslib.as_array(C.cast(self._l.herro_overlaps_target_ids(h), C.POINTER(C.c_uint32)), (nt,)).copy() if nt else np.zeros(0, np.uint32)
             aln_off = np.ctypeslib.as_array(C.cast(self._l.herro_overlaps_aln_off(h), C.POINTER(C.c_uint64)), (nt + 1,)).copy()
             rows = _aln_rows(self._l.herro_overlaps_alignments(h), n)
@@ -754,6 +771,14 @@ class Context:
         inside the library; m: pairs.align() or any handle of 2 P records, primaries then mirrors."""
         h = self._l.herro_job_create_paired(self.h, pairs.h, m.h, window_size)
         return _job_or_raise(self, h, len(pairs.rids))
+
+    def occ_census(self, **params):
+        """The census and the pick of occ_frac_ppm alone (herro_debug_occ_census): (hist u32 [65536] over min(occurrences, 65535) of the
+        distinct minimizer hashes, dict(cut, distinct, cut_runs, cut_minimizers))."""
+        p = self._overlap_params(params)
+        hist, out = np.zeros(65536, np.uint32), np.zeros(4, np.uint64)
+        self._chk(self._l.herro_debug_occ_census(self.h, C.byref(p), hist.ctypes.data, out.ctypes.data))
+        return hist, dict(zip(("cut", "distinct", "cut_runs", "cut_minimizers"), (int(x) for x in out)))
 
     def sketch(self, **params):
         """The store's minimizers sorted by (rid, pos) (herro_debug_sketch): (hash u64, rid u32, pos u32, strand u8)."""
@@ -998,7 +1023,7 @@ class OverlapPairs:
     [P, 10] (ascending (tid, qid), extended unless extend=False, cigar_len 0); chain_scores i32 [P]; ext u32 [P, 4] and ext_scores i32
     [P, 2] as extend_overlaps returns them (zeros without extension or from a table); rids u32 [n_targets], aln_off u64 [n_targets + 1],
     rec_of_row u32 [n_rows] as find_overlaps and pair_rows give them; n_rows = 2 P, fewer for a handle of core targets (find_overlap_pairs(core=...):
-    the rows whose target is core)."""
+    the rows whose target is core); occ_cut: the frequency cut the finder used (0 for a handle over a table)."""
 
     def __init__(self, ctx: Context, h):
         self.ctx, self.h, self._l = ctx, h, ctx._l
@@ -1006,6 +1031,7 @@ class OverlapPairs:
         n = self.n_pairs = int(L.herro_pairs_n(h))
         nt = int(L.herro_pairs_n_targets(h))
         self.n_rows = int(L.herro_pairs_n_rows(h)) if hasattr(L, "herro_pairs_n_rows") else 2 * n
+        self.occ_cut = int(L.herro_pairs_occ_cut(h)) if hasattr(L, "herro_pairs_occ_cut") else 0
 
         def arr(ptr, ct, dt, shape):
             out = np.zeros(shape, dt)

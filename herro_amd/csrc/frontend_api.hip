@@ -1,5 +1,5 @@
 // frontend_api.hip — the C ABI's front end (include/herro_amd.h): reads alone -> overlap records -> their ops on the device.
-// herro_find_overlaps[_core], herro_extend_overlaps, herro_align_overlaps[_dev], herro_aligned_dev_*, herro_find_overlap_pairs[_core] and herro_pairs_*.  Host C++ (compiled by hipcc) over
+// herro_find_overlaps[_core], herro_extend_overlaps, herro_align_overlaps[_dev], herro_aligned_dev_*, herro_find_overlap_pairs[_core], herro_pairs_* and the test hooks herro_debug_sketch and herro_debug_occ_census.  Host C++ (compiled by hipcc) over
 // overlap_dev.hip and align_dev.hip; contexts, the model and jobs are herro_api.hip.
 #include <hip/hip_runtime.h>
 
@@ -155,7 +155,8 @@ int overlap_params(herro_ctx* ctx, const herro_overlap_params* in, herro::OvlPar
   const herro_overlap_params& p = in ? *in : z;
   P.k = p.k ? p.k : 25;
   P.w = p.w ? p.w : 17;
-  P.max_occ = p.max_occ ? p.max_occ : 128;
+  P.occ_frac_ppm = p.occ_frac_ppm;
+  P.max_occ = p.max_occ ? p.max_occ : (P.occ_frac_ppm ? 0 : 128);   // (with a fraction: the ceiling of the cut, 0 = none)
   P.bandwidth = p.bandwidth ? p.bandwidth : 150;
   P.max_gap = p.max_gap ? p.max_gap : 5000;
   P.min_score = p.min_score ? p.min_score : 2500;
@@ -164,15 +165,23 @@ int overlap_params(herro_ctx* ctx, const herro_overlap_params* in, herro::OvlPar
     ctx->err = "overlap parameters: 5 <= k <= 31 and 1 <= w <= 64";
     return HERRO_E_INVALID;
   }
+  if (P.occ_frac_ppm > 999999) {
+    ctx->err = "overlap parameters: occ_frac_ppm must be below 1000000 (0: the fixed cut max_occ)";
+    return HERRO_E_INVALID;
+  }
   return HERRO_OK;
 }
 
-// HERRO_OVL_STATS=1 (tools/overlaprate.py): the sizes of the finder's stages, one line on stderr
-void print_ovl_stats(const herro::OvlStats& stats) {
-  if (const char* e = getenv("HERRO_OVL_STATS"))
-    if (atoi(e)) fprintf(stderr, "OVL kmers=%llu minimizers=%llu anchors=%llu groups=%llu chained=%llu chunks=%llu\n", (unsigned long long)stats.kmers,
-                         (unsigned long long)stats.minimizers, (unsigned long long)stats.anchors, (unsigned long long)stats.groups,
-                         (unsigned long long)stats.chained, (unsigned long long)stats.chunks);
+// HERRO_OVL_STATS=1 (tools/overlaprate.py): the sizes of the finder's stages, one line on stderr; a second one for the cut taken from the index
+void print_ovl_stats(const herro::OvlParams& P, const herro::OvlStats& stats) {
+  const char* e = getenv("HERRO_OVL_STATS");
+  if (!e || !atoi(e)) return;
+  fprintf(stderr, "OVL kmers=%llu minimizers=%llu anchors=%llu groups=%llu chained=%llu chunks=%llu\n", (unsigned long long)stats.kmers,
+          (unsigned long long)stats.minimizers, (unsigned long long)stats.anchors, (unsigned long long)stats.groups,
+          (unsigned long long)stats.chained, (unsigned long long)stats.chunks);
+  if (P.occ_frac_ppm)
+    fprintf(stderr, "OVLOCC cut=%llu distinct=%llu cut_runs=%llu cut_minimizers=%llu\n", (unsigned long long)stats.occ_cut,
+            (unsigned long long)stats.distinct, (unsigned long long)stats.cut_runs, (unsigned long long)stats.cut_minimizers);
 }
 
 // A call's core mask (n_reads bytes, non-zero: the read is a target) goes up once, into the call's scratch; NULL stays NULL: every read is core.
@@ -492,6 +501,7 @@ struct herro_overlaps {
   std::vector<uint64_t> aln_off;
   std::vector<herro_alignment> alns;
   std::vector<int32_t> scores;
+  uint32_t occ_cut = 0;                  // the frequency cut the call used
 };
 
 int herro_find_overlaps(herro_ctx* ctx, const herro_overlap_params* params, herro_overlaps** out) { return herro_find_overlaps_core(ctx, params, nullptr, out); }
@@ -511,7 +521,7 @@ int herro_find_overlaps_core(herro_ctx* ctx, const herro_overlap_params* params,
   uint8_t* d_core = nullptr;
   if (int rc = upload_core(ctx, "herro_find_overlaps", core, CB, &d_core)) return rc;
   if (int rc = overlap_rc(ctx, herro::ovl_find(ovl_store(ctx), P, d_core, scratch_budget("HERRO_OVL_SCRATCH_MB"), ctx->stream, chains, stats, msg), msg)) return rc;
-  print_ovl_stats(stats);
+  print_ovl_stats(P, stats);
   // one overlap per pair: chains arrive in ascending (t, q, rel), so the two strands of a pair are neighbours
   std::vector<herro::OvlPair> best;
   for (const herro::OvlPair& c : chains) {
@@ -531,6 +541,7 @@ int herro_find_overlaps_core(herro_ctx* ctx, const herro_overlap_params* params,
   }
   std::sort(recs.begin(), recs.end(), [](const Rec& x, const Rec& y) { return x.a.tid != y.a.tid ? x.a.tid < y.a.tid : x.a.qid < y.a.qid; });
   auto* h = new herro_overlaps();
+  h->occ_cut = (uint32_t)stats.occ_cut;
   h->alns.reserve(recs.size());
   h->scores.reserve(recs.size());
   for (const Rec& r : recs) {
@@ -549,6 +560,7 @@ const uint32_t* herro_overlaps_target_ids(const herro_overlaps* o) { return o ? 
 const uint64_t* herro_overlaps_aln_off(const herro_overlaps* o) { return o ? o->aln_off.data() : nullptr; }
 const herro_alignment* herro_overlaps_alignments(const herro_overlaps* o) { return o ? o->alns.data() : nullptr; }
 const int32_t* herro_overlaps_scores(const herro_overlaps* o) { return o ? o->scores.data() : nullptr; }
+uint32_t herro_overlaps_occ_cut(const herro_overlaps* o) { return o ? o->occ_cut : 0; }
 void herro_overlaps_free(herro_overlaps* o) { delete o; }
 
 // ---- pair overlaps ("Pairs on the device"): reads -> one record per pair and the table of its two rows -> mirrored alignments ----
@@ -561,6 +573,7 @@ struct herro_pairs {
   std::vector<uint32_t> rids;            // targets of the 2 P rows
   std::vector<uint64_t> aln_off;         // [n_targets + 1]
   std::vector<uint32_t> rec_of_row;      // [n_rows]: 2 P, fewer with a core mask
+  uint32_t occ_cut = 0;                  // the frequency cut the finder used; 0: a handle over the caller's table
 };
 
 int herro_find_overlap_pairs(herro_ctx* ctx, const herro_overlap_params* params, const herro_extend_params* eparams, uint32_t flags, herro_pairs** out) {
@@ -588,9 +601,10 @@ int herro_find_overlap_pairs_core(herro_ctx* ctx, const herro_overlap_params* pa
   uint8_t* d_core = nullptr;
   if (int rc = upload_core(ctx, who, core, CB, &d_core)) return rc;
   if (int rc = overlap_rc(ctx, herro::ovl_find_pairs(ovl_store(ctx), P, d_core, scratch_budget("HERRO_OVL_SCRATCH_MB"), ctx->stream, recs, stats, msg), msg)) return rc;
-  print_ovl_stats(stats);
+  print_ovl_stats(P, stats);
   std::unique_ptr<herro_pairs> h(new herro_pairs());
   h->ctx = ctx;
+  h->occ_cut = (uint32_t)stats.occ_cut;
   if (int rc = overlap_rc(ctx, herro::ovl_row_table(recs, ctx->n_reads, d_core, ctx->stream, h->rids, h->aln_off, h->rec_of_row, msg), msg)) return rc;
   const uint32_t n = (uint32_t)recs.n;   // (<= 2^31 - 1: ovl_find_pairs)
   h->ext.assign((size_t)n * 4, 0);
@@ -729,6 +743,7 @@ const uint32_t* herro_pairs_target_ids(const herro_pairs* p) { return p ? p->rid
 const uint64_t* herro_pairs_aln_off(const herro_pairs* p) { return p ? p->aln_off.data() : nullptr; }
 const uint32_t* herro_pairs_rec_of_row(const herro_pairs* p) { return p ? p->rec_of_row.data() : nullptr; }
 uint64_t herro_pairs_n_rows(const herro_pairs* p) { return p ? p->rec_of_row.size() : 0; }
+uint32_t herro_pairs_occ_cut(const herro_pairs* p) { return p ? p->occ_cut : 0; }
 void herro_pairs_free(herro_pairs* p) { delete p; }
 
 int64_t herro_debug_sketch(herro_ctx* ctx, const herro_overlap_params* params, uint64_t* hash, uint32_t* rid, uint32_t* pos,
@@ -750,6 +765,20 @@ int64_t herro_debug_sketch(herro_ctx* ctx, const herro_overlap_params* params, u
     }
   }
   return (int64_t)h.size();
+}
+
+int herro_debug_occ_census(herro_ctx* ctx, const herro_overlap_params* params, uint32_t* hist, uint64_t out[4]) {
+  if (!ctx || !out) return HERRO_E_INVALID;
+  herro::OvlParams P;
+  if (int rc = overlap_params(ctx, params, P)) return rc;
+  if (!P.occ_frac_ppm) { ctx->err = "herro_debug_occ_census: occ_frac_ppm is 0 (the fixed cut takes no census)"; return HERRO_E_INVALID; }
+  if (int rc = device_ready(ctx, "herro_debug_occ_census")) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::vector<uint32_t> h;
+  std::string msg;
+  if (int rc = overlap_rc(ctx, herro::ovl_occ_census(ovl_store(ctx), P, ctx->stream, hist ? &h : nullptr, out, msg), msg)) return rc;
+  if (hist) std::memcpy(hist, h.data(), 4ull * herro::OVL_OCC_BINS);
+  return HERRO_OK;
 }
 
 }  // extern "C"

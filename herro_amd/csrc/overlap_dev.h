@@ -3,6 +3,8 @@
 // Minimizer sketch of the resident 2-bit store, radix sort by hash, frequency cut, anchor expansion, radix sort by
 // (t, q, rel, tpos, qpos), one wave64 per (t, q, rel) group for the chain.  The specification is DESIGN.md §10 and
 // tests/overlap_ref.py; the kernels equal it bit for bit, whatever the scratch budget.
+// The frequency cut is max_occ, or — occ_frac_ppm != 0, minimap2's -f — taken from the store's own index: the census of the run lengths
+// and the pick of DESIGN.md §10, "The cut as a fraction" (tests/occ_ref.py), two kernels between the sort and k_runs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,7 +20,12 @@ constexpr uint64_t OVL_MAX_KMERS = 0xfffff000ull;   // k-mers of the whole store
 constexpr uint32_t OVL_MAX_READ_LEN = 0x7fffffffu;  // pos << 1 | strand is one 32-bit field
 constexpr uint32_t OVL_MAX_READS = 0x7fffffffu;     // q << 1 | rel is one 33-bit field of the anchor key
 
-struct OvlParams { uint32_t k, w, max_occ, bandwidth, max_gap, min_score, min_anchors; };   // defaults already filled in
+// defaults already filled in.  occ_frac_ppm 0: runs longer than max_occ are dropped.  Else the cut is the census's (ovl_occ_census) and max_occ
+// its ceiling, 0 = none.
+struct OvlParams { uint32_t k, w, max_occ, bandwidth, max_gap, min_score, min_anchors, occ_frac_ppm; };
+
+constexpr uint32_t OVL_OCC_BINS = 65536;       // census counts of a hash run: min(length, 65535)
+constexpr uint32_t OVL_OCC_FLOOR = 10;         // the least cut the fraction may give (minimap2's min_mid_occ)
 
 struct OvlStore {            // the context's read store
   const uint64_t* d_words;      // 2-bit codes, 32 bases per word (+ one pad word)
@@ -34,7 +41,11 @@ struct OvlPair {             // one kept chain, t < q, forward coordinates on bo
   uint32_t tstart, tend, qstart, qend;
 };
 
-struct OvlStats { uint64_t kmers = 0, minimizers = 0, anchors = 0, groups = 0, chained = 0, chunks = 0; };
+struct OvlStats {
+  uint64_t kmers = 0, minimizers = 0, anchors = 0, groups = 0, chained = 0, chunks = 0;
+  uint64_t occ_cut = 0;                                       // the cut the call used: max_occ, or the census's
+  uint64_t distinct = 0, cut_runs = 0, cut_minimizers = 0;    // occ_frac_ppm != 0: hash runs of the index, those above the cut, their minimizers
+};
 
 enum { OVL_OK = 0, OVL_HIP = 1, OVL_UNSUPPORTED = 2 };
 
@@ -42,10 +53,14 @@ enum { OVL_OK = 0, OVL_HIP = 1, OVL_UNSUPPORTED = 2 };
 int ovl_sketch(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vector<uint64_t>& hash, std::vector<uint64_t>& meta,
                std::string& err);
 
+// The census and the pick alone (occ_frac_ppm != 0): rec = {cut, distinct hashes, runs above the cut, minimizers in them}; hist (or NULL): the
+// OVL_OCC_BINS bins of min(run length, 65535).
+int ovl_occ_census(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vector<uint32_t>* hist, uint64_t rec[4], std::string& err);
+
 // every kept (t, q) chain per strand, ascending (t, q, rel); the caller picks the strand and writes the dual records
 // d_core (here and below): NULL — every read is a target — or the core mask on the device, n_reads bytes, non-zero = core (the PAF
 // entries' `core`: overlaps.rs:154-159).  No anchor is created between two non-core reads (k_runs, k_expand), so the sorts, the chains and
-// all behind them see only pairs with a core read; max_occ stays the whole store's cut, chains are independent per (t, q, rel), and the
+// all behind them see only pairs with a core read; the frequency cut stays the whole store's, chains are independent per (t, q, rel), and the
 // result is therefore the unmasked one restricted to those pairs.  OvlStats.anchors and the limits count the masked anchors.
 int ovl_find(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uint64_t budget_bytes, hipStream_t st, std::vector<OvlPair>& out,
              OvlStats& stats, std::string& err);

@@ -4,6 +4,8 @@
 //                minimum of a window it lies in is selected.  Run twice: count per tile, scan, write — so the output is in
 //                (rid, pos) order without any atomic deciding a place.
 //   radix sort   LSD, 8-bit digits, 64-bit key + 64-bit payload, stable (per-block histogram, scan, ranked scatter).
+//   k_occ_census, k_occ_pick   occ_frac_ppm only: the histogram of the run lengths (LDS bins below 2048, the table beyond) and, in one workgroup, the
+//                cut that leaves the given fraction of the distinct hashes above it; k_runs_occ reads it where k_occ_pick left it.
 //   k_runs       per hash run: length, frequency cut, anchors every occurrence has with the later reads of its run.
 //   k_expand     the anchors of the targets of one chunk: A = tpos << 32 | qpos, B = (t - t_lo) << 33 | q << 1 | rel;
 //                sorted by A carrying B, then by B carrying A (stable): order (t, q, rel, tpos, qpos).
@@ -245,9 +247,9 @@ __global__ __launch_bounds__(256) void k_rs_scatter(const uint64_t* __restrict__
 // CORE: an occurrence in a non-core read counts only the later occurrences whose read is core — none of them is in its own read, which is
 // not core.  An occurrence in a core read keeps the count above.  The frequency cut is the whole store's, whatever the mask.
 template <bool CORE>
-__global__ __launch_bounds__(256) void k_runs(const uint64_t* __restrict__ hash, const uint64_t* __restrict__ meta, uint32_t n,
-                                              uint32_t max_occ, uint32_t* __restrict__ cnt, uint32_t* __restrict__ run_end,
-                                              unsigned long long* __restrict__ per_read, const uint8_t* __restrict__ core) {
+__device__ inline void runs_of_head(const uint64_t* __restrict__ hash, const uint64_t* __restrict__ meta, uint32_t n, uint32_t max_occ,
+                                    uint32_t* __restrict__ cnt, uint32_t* __restrict__ run_end, unsigned long long* __restrict__ per_read,
+                                    const uint8_t* __restrict__ core) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const uint64_t h = hash[i];
@@ -273,6 +275,87 @@ __global__ __launch_bounds__(256) void k_runs(const uint64_t* __restrict__ hash,
     run_end[j] = (uint32_t)e;
     if (m) atomicAdd(&per_read[rid], (unsigned long long)m);
   }
+}
+
+template <bool CORE>
+__global__ __launch_bounds__(256) void k_runs(const uint64_t* __restrict__ hash, const uint64_t* __restrict__ meta, uint32_t n,
+                                              uint32_t max_occ, uint32_t* __restrict__ cnt, uint32_t* __restrict__ run_end,
+                                              unsigned long long* __restrict__ per_read, const uint8_t* __restrict__ core) {
+  runs_of_head<CORE>(hash, meta, n, max_occ, cnt, run_end, per_read, core);
+}
+
+// ... with the cut k_occ_pick left in occ[0] (at most 65534: the walk to the end of a run stays bounded)
+template <bool CORE>
+__global__ __launch_bounds__(256) void k_runs_occ(const uint64_t* __restrict__ hash, const uint64_t* __restrict__ meta, uint32_t n,
+                                                  const uint64_t* __restrict__ occ, uint32_t* __restrict__ cnt, uint32_t* __restrict__ run_end,
+                                                  unsigned long long* __restrict__ per_read, const uint8_t* __restrict__ core) {
+  runs_of_head<CORE>(hash, meta, n, (uint32_t)occ[0], cnt, run_end, per_read, core);
+}
+
+// ---- the cut as a fraction of the distinct hashes (occ_frac_ppm; DESIGN.md section 10, tests/occ_ref.py) -------------------------------------
+constexpr uint32_t OCC_LDS_BINS = 2048;      // bins of the census a block keeps in LDS (8 KB); a longer run is rare and goes to the table itself
+constexpr uint32_t OCC_GRID = 1024;          // blocks of the census at most: each flushes its LDS bins once
+
+// the floor, the caller's ceiling (0: none), and never the last bin, whose runs have no known length
+__host__ __device__ inline uint32_t occ_final_cut(uint32_t q, uint32_t max_occ) {
+  uint32_t cut = q > OVL_OCC_FLOOR ? q : OVL_OCC_FLOOR;
+  if (max_occ && cut > max_occ) cut = max_occ;
+  return cut < OVL_OCC_BINS - 2 ? cut : OVL_OCC_BINS - 2;
+}
+
+// hist[min(length, 65535)] += 1 for every hash run.  rstart[r]: first minimizer of run r (k_heads, the scan, k_gstart), rstart[*n_runs] = n:
+// a run's length is a difference, no thread walks a run.
+__global__ __launch_bounds__(256) void k_occ_census(const uint32_t* __restrict__ rstart, const uint32_t* __restrict__ n_runs,
+                                                    uint32_t* __restrict__ hist) {
+  __shared__ uint32_t h[OCC_LDS_BINS];
+  for (uint32_t b = threadIdx.x; b < OCC_LDS_BINS; b += 256) h[b] = 0;
+  __syncthreads();
+  const uint32_t nr = *n_runs;
+  for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < nr; r += (uint64_t)gridDim.x * 256) {
+    const uint32_t c = min(rstart[r + 1] - rstart[r], OVL_OCC_BINS - 1);
+    if (c < OCC_LDS_BINS) atomicAdd(&h[c], 1u);
+    else atomicAdd(&hist[c], 1u);
+  }
+  __syncthreads();
+  for (uint32_t b = threadIdx.x; b < OCC_LDS_BINS; b += 256)
+    if (h[b]) atomicAdd(&hist[b], h[b]);
+}
+
+// One workgroup.  Thread t owns the 256 bins from 256 (255 - t) on, so the exclusive scan over the threads is a suffix sum: above = the runs in
+// all higher bins.  q = the least v with no more than drop runs above it; occ = {cut, distinct, runs above the cut, minimizers in them}.
+__global__ __launch_bounds__(256) void k_occ_pick(const uint32_t* __restrict__ hist, uint32_t n, uint32_t ppm, uint32_t max_occ,
+                                                  uint64_t* __restrict__ occ) {
+  __shared__ uint32_t lds4[4];
+  __shared__ uint32_t s_q, s_runs;
+  __shared__ unsigned long long s_kept;
+  const uint32_t b0 = 256u * (255u - threadIdx.x);
+  if (threadIdx.x == 0) { s_q = OVL_OCC_BINS - 1; s_runs = 0; s_kept = 0; }
+  uint32_t s = 0;
+  for (uint32_t b = 0; b < 256; b += 4) {
+    const uint4 v = *reinterpret_cast<const uint4*>(hist + b0 + b);
+    s += v.x + v.y + v.z + v.w;
+  }
+  uint32_t distinct;
+  uint32_t above = block_excl_scan(s, lds4, distinct);
+  const uint64_t drop = (uint64_t)distinct * ppm / 1000000u;
+  uint32_t q = OVL_OCC_BINS;
+  for (uint32_t b = 256; b-- > 0 && above <= drop;) {
+    q = b0 + b;
+    above += hist[b0 + b];
+  }
+  if (q < OVL_OCC_BINS) atomicMin(&s_q, q);
+  __syncthreads();
+  const uint32_t cut = occ_final_cut(s_q, max_occ);
+  uint32_t runs = 0;
+  uint64_t kept = 0;                             // minimizers in runs of at most cut (<= 65534: the bin is the length)
+  for (uint32_t b = 0; b < 256; b++) {
+    const uint32_t v = b0 + b, c = hist[v];
+    if (v > cut) runs += c; else kept += (uint64_t)v * c;
+  }
+  if (runs) atomicAdd(&s_runs, runs);
+  if (kept) atomicAdd(&s_kept, (unsigned long long)kept);
+  __syncthreads();
+  if (threadIdx.x == 0) { occ[0] = cut; occ[1] = distinct; occ[2] = s_runs; occ[3] = n - s_kept; }
 }
 
 __global__ __launch_bounds__(256) void k_mask(const uint64_t* __restrict__ meta, const uint32_t* __restrict__ cnt, uint32_t n,
@@ -653,6 +736,35 @@ int ovl_sketch(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vecto
 }
 
 namespace {
+// the minimizers by hash (stable: (rid, pos) order inside a hash); ms: the sort's scratch, for sk.n elements, which the callers go on using
+int sort_by_hash(Sketch& sk, uint32_t k, hipStream_t st, Bufs& B, SortScratch& ms, std::string& err) {
+  uint64_t *mk1, *mp1;
+  OVL_TRY(B.get(&mk1, sk.n));
+  OVL_TRY(B.get(&mp1, sk.n));
+  OVL_TRY(ms.alloc(B, sk.n));
+  std::vector<uint32_t> shifts;
+  field_shifts(shifts, 0, 2 * k);
+  return radix_sort(&sk.hash, &sk.meta, &mk1, &mp1, sk.n, shifts, ms, st, err);
+}
+
+// The census of the run lengths of hash[0 .. n) (sorted, n >= 1) and the pick, queued on st: *d_occ = {cut, distinct, runs above the cut, minimizers
+// in them} and *d_hist, on the device.  flag [n] and gidx [n + 1] are the caller's, free to use again once this is queued in front of their next writer.
+int occ_census_dev(const uint64_t* hash, uint32_t n, const OvlParams& P, hipStream_t st, Bufs& B, const SortScratch& ms, uint32_t* flag, uint32_t* gidx,
+                   uint64_t** d_occ, uint32_t** d_hist, std::string& err) {
+  uint32_t* rstart;
+  OVL_TRY(B.get(&rstart, (uint64_t)n + 1));
+  OVL_TRY(B.get(d_hist, OVL_OCC_BINS));
+  OVL_TRY(B.get(d_occ, 4));
+  OVL_TRY(hipMemsetAsync(*d_hist, 0, 4ull * OVL_OCC_BINS, st));
+  k_heads<<<nblk(n, 256), 256, 0, st>>>(hash, n, flag);
+  if (int rc = scan_u32(flag, n, gidx, ms.partial, st, err)) return rc;
+  k_gstart<<<nblk(n, 256), 256, 0, st>>>(flag, gidx, n, rstart);
+  k_occ_census<<<std::min(nblk(n, 256), OCC_GRID), 256, 0, st>>>(rstart, gidx + n, *d_hist);
+  k_occ_pick<<<1, 256, 0, st>>>(*d_hist, n, P.occ_frac_ppm, P.max_occ, *d_occ);
+  OVL_TRY(hipGetLastError());
+  return OVL_OK;
+}
+
 // Sketch, sort, frequency cut and the chunk loop of ovl_find and ovl_find_pairs.  Behind every chunk's k_walk, take(nc, gout, ccap, t_hi, B) gets the
 // chunk's nc GroupOut records, still on the device, in ascending (t, q, rel): it takes what it wants before it returns or queues its kernels on st,
 // in front of the next chunk's k_walk, which overwrites gout.  ccap: the most records any chunk has; t_hi: the targets done so far, this chunk's
@@ -667,19 +779,13 @@ int find_chunks(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, ui
   stats.kmers = sk.kmers;
   stats.minimizers = sk.n;
   const uint32_t nm = sk.n;
+  const bool frac = P.occ_frac_ppm != 0;
+  stats.occ_cut = frac ? occ_final_cut(nm, P.max_occ) : P.max_occ;     // (fewer than two minimizers: as many runs of one)
+  stats.distinct = frac ? nm : 0;
   if (nm < 2) { OVL_TRY(hipStreamSynchronize(st)); return OVL_OK; }
 
-  // minimizers by hash (stable: (rid, pos) order inside a hash)
-  uint64_t *mk1, *mp1;
-  OVL_TRY(B.get(&mk1, nm));
-  OVL_TRY(B.get(&mp1, nm));
   SortScratch ms;
-  OVL_TRY(ms.alloc(B, nm));
-  {
-    std::vector<uint32_t> shifts;
-    field_shifts(shifts, 0, 2 * P.k);
-    if (int rc = radix_sort(&sk.hash, &sk.meta, &mk1, &mp1, nm, shifts, ms, st, err)) return rc;
-  }
+  if (int rc = sort_by_hash(sk, P.k, st, B, ms, err)) return rc;
   uint32_t *d_cnt, *d_run_end, *d_cntm, *d_aoff;
   unsigned long long* d_per_read;
   OVL_TRY(B.get(&d_cnt, nm));
@@ -689,12 +795,22 @@ int find_chunks(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, ui
   OVL_TRY(B.get(&d_per_read, S.n_reads));
   OVL_TRY(hipMemsetAsync(d_cnt, 0, 4ull * nm, st));
   OVL_TRY(hipMemsetAsync(d_per_read, 0, 8ull * S.n_reads, st));
-  if (d_core) k_runs<true><<<nblk(nm, 256), 256, 0, st>>>(sk.hash, sk.meta, nm, P.max_occ, d_cnt, d_run_end, d_per_read, d_core);
+  uint64_t* d_occ = nullptr;
+  uint64_t occ[4] = {0, 0, 0, 0};
+  if (frac) {
+    // census, pick and k_runs_occ queue one behind the other: the cut stays on the device and comes back with per_read (d_cntm / d_aoff are free until the chunks)
+    uint32_t* d_hist;
+    if (int rc = occ_census_dev(sk.hash, nm, P, st, B, ms, d_cntm, d_aoff, &d_occ, &d_hist, err)) return rc;
+    if (d_core) k_runs_occ<true><<<nblk(nm, 256), 256, 0, st>>>(sk.hash, sk.meta, nm, d_occ, d_cnt, d_run_end, d_per_read, d_core);
+    else k_runs_occ<false><<<nblk(nm, 256), 256, 0, st>>>(sk.hash, sk.meta, nm, d_occ, d_cnt, d_run_end, d_per_read, nullptr);
+  } else if (d_core) k_runs<true><<<nblk(nm, 256), 256, 0, st>>>(sk.hash, sk.meta, nm, P.max_occ, d_cnt, d_run_end, d_per_read, d_core);
   else k_runs<false><<<nblk(nm, 256), 256, 0, st>>>(sk.hash, sk.meta, nm, P.max_occ, d_cnt, d_run_end, d_per_read, nullptr);
   OVL_TRY(hipGetLastError());
   std::vector<unsigned long long> per_read(S.n_reads);
   OVL_TRY(hipMemcpyAsync(per_read.data(), d_per_read, 8ull * S.n_reads, hipMemcpyDeviceToHost, st));
+  if (frac) OVL_TRY(hipMemcpyAsync(occ, d_occ, sizeof(occ), hipMemcpyDeviceToHost, st));
   OVL_TRY(hipStreamSynchronize(st));
+  if (frac) { stats.occ_cut = occ[0]; stats.distinct = occ[1]; stats.cut_runs = occ[2]; stats.cut_minimizers = occ[3]; }
 
   // chunks: consecutive targets whose anchors fit the budget (a target with more runs alone)
   const uint64_t want = std::max<uint64_t>(budget_bytes / OVL_ANCHOR_BYTES, 1);
@@ -780,6 +896,27 @@ int find_chunks(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, ui
   return OVL_OK;
 }
 }  // namespace
+
+int ovl_occ_census(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vector<uint32_t>* hist, uint64_t rec[4], std::string& err) {
+  Bufs B;
+  Sketch sk;
+  if (int rc = sketch_dev(S, P, st, B, sk, err)) return rc;
+  if (hist) hist->assign(OVL_OCC_BINS, 0);
+  rec[0] = occ_final_cut(0, P.max_occ);
+  rec[1] = rec[2] = rec[3] = 0;
+  if (!sk.n) { OVL_TRY(hipStreamSynchronize(st)); return OVL_OK; }
+  SortScratch ms;
+  if (int rc = sort_by_hash(sk, P.k, st, B, ms, err)) return rc;
+  uint32_t *flag, *gidx, *d_hist;
+  uint64_t* d_occ;
+  OVL_TRY(B.get(&flag, sk.n));
+  OVL_TRY(B.get(&gidx, (uint64_t)sk.n + 1));
+  if (int rc = occ_census_dev(sk.hash, sk.n, P, st, B, ms, flag, gidx, &d_occ, &d_hist, err)) return rc;
+  if (hist) OVL_TRY(hipMemcpyAsync(hist->data(), d_hist, 4ull * OVL_OCC_BINS, hipMemcpyDeviceToHost, st));
+  OVL_TRY(hipMemcpyAsync(rec, d_occ, 32, hipMemcpyDeviceToHost, st));
+  OVL_TRY(hipStreamSynchronize(st));
+  return OVL_OK;
+}
 
 int ovl_find(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uint64_t budget_bytes, hipStream_t st, std::vector<OvlPair>& out,
              OvlStats& stats, std::string& err) {

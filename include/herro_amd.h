@@ -453,10 +453,10 @@ void herro_extended_free(herro_extended* x);
 /* ---- overlap finding on the device (csrc/overlap_dev.hip) ------------------------------------------------------------------------
  * Stands in for the seeding and chaining half of the `minimap2 -x ava-ont` run `herro inference` starts itself without --read-alns
  * (AlnMode::None, overlaps.rs:340-344 -> generate_batches -> call_mm2, mm2.rs:15-30): which reads of the context's store overlap,
- * where, on which strand.  Not minimap2's output (no two-piece gaps, no z-drop extension, no -f fraction, no secondary chains) but
+ * where, on which strand.  Not minimap2's output (no two-piece gaps, no z-drop extension, no secondary chains) but
  * a small specification of its own, DESIGN.md section 10 and tests/overlap_ref.py, which the kernels equal bit for bit: (k, w)
- * minimizers under minimap2's hash64 with every tied window minimum selected; hashes with more than max_occ occurrences in the
- * store dropped; anchors between every two occurrences in different reads; per (t, q, strand) a chain over the 64 nearest
+ * minimizers under minimap2's hash64 with every tied window minimum selected; hashes with more occurrences in the store than the
+ * frequency cut dropped (max_occ, or a fraction of the distinct hashes: below); anchors between every two occurrences in different reads; per (t, q, strand) a chain over the 64 nearest
  * predecessors (gaps <= max_gap, diagonal drift <= bandwidth, minimap2's one-piece gap cost); kept with score >= min_score and
  * >= min_anchors anchors.  Coordinates are the anchor span of the chain: the finder itself does not extend it to the read ends —
  * herro_extend_overlaps (above) does, as a step of its own between this call and herro_align_overlaps.  One overlap per
@@ -466,16 +466,25 @@ void herro_extended_free(herro_extended* x);
  * herro_align_overlaps unchanged.
  * Parameters: a 0 field means its default — k 25, w 17, bandwidth 150, min_score 2500 (the -k -w -r -m of mm2.rs:22-26), max_gap
  * 5000, min_anchors 3 (minimap2's -g, -n), max_occ 128.  5 <= k <= 31 and 1 <= w <= 64, else HERRO_E_INVALID (checked before
- * anything else).  min_score 2500 is a threshold for reads of ~10 kb and more; short reads need their own.  max_occ must stay above
- * the read depth: a true minimizer occurs once per read that covers it, and a cut below the depth removes the anchors of true
- * overlaps.  Known limit: the chain looks back 64 ANCHORS, not bases — a tandem repeat that survives max_occ (a set of very few
+ * anything else).  min_score 2500 is a threshold for reads of ~10 kb and more; short reads need their own.  A fixed max_occ must stay
+ * above the read depth: a true minimizer occurs once per read that covers it, and a cut below the depth removes the anchors of true
+ * overlaps.
+ * occ_frac_ppm (0: off, the fixed cut max_occ) takes the cut from the store's own index instead, as minimap2's -f does (mm2.rs:27 runs
+ * -f0.005 = 5000): parts per million of the DISTINCT minimizer hashes that may lie above it.  With D distinct hashes (singletons included)
+ * and c' = min(occurrences, 65535) per hash: drop = floor(D * ppm / 10^6); q = the least v with at most drop hashes of c' > v (the
+ * (D - drop)-th smallest c'; every hash tied with it is kept); cut = max(q, 10), then min(cut, max_occ) if max_occ is not 0 — in this mode
+ * max_occ is a ceiling and 0 means none, not 128 —, then min(cut, 65534): a hash of 65535 or more occurrences is never used.  A hash is
+ * used iff it occurs 2 .. cut times.  1 <= occ_frac_ppm <= 999999, else HERRO_E_INVALID (checked with k and w).  The cut is that of the
+ * whole store whatever the core mask and the scratch budget; herro_overlaps_occ_cut / herro_pairs_occ_cut return it (max_occ in the
+ * fixed mode; 0 for a handle made by herro_pairs_from_table*), and HERRO_OVL_STATS=1 adds a line `OVLOCC cut= distinct= cut_runs=
+ * cut_minimizers=` to its `OVL ` line.  Known limit: the chain looks back 64 ANCHORS, not bases — a tandem repeat that survives max_occ (a set of very few
  * reads) can put more than 64 off-diagonal anchors between two anchors of the true diagonal, and the overlap comes out shorter.
  * Limits (HERRO_E_UNSUPPORTED): 2^31 - 1 reads, reads of 2^31 - 1 bases, 2^32 k-mers in the store, 2^32 anchors per target.
  * Scratch: 128 bytes per anchor, targets processed in read-id ranges that fit HERRO_OVL_SCRATCH_MB (default 4096; a target that
  * needs more runs alone) — the result is byte-identical for every budget — plus 40 bytes per minimizer of the store.
  * Runs on the context's execution stream and returns when done.  HERRO_E_STATE: no reads; HERRO_E_NO_DEVICE: a context without
  * a device. */
-typedef struct { uint32_t k, w, max_occ, bandwidth, max_gap, min_score, min_anchors, reserved; } herro_overlap_params;
+typedef struct { uint32_t k, w, max_occ, bandwidth, max_gap, min_score, min_anchors, occ_frac_ppm; } herro_overlap_params;
 typedef struct herro_overlaps herro_overlaps;
 int herro_find_overlaps(herro_ctx* ctx, const herro_overlap_params* params /* NULL: defaults */, herro_overlaps** out);
 uint32_t herro_overlaps_n(const herro_overlaps* o);                       /* records (two per pair) */
@@ -484,6 +493,7 @@ const uint32_t* herro_overlaps_target_ids(const herro_overlaps* o);
 const uint64_t* herro_overlaps_aln_off(const herro_overlaps* o);          /* [n_targets + 1] */
 const herro_alignment* herro_overlaps_alignments(const herro_overlaps* o);
 const int32_t* herro_overlaps_scores(const herro_overlaps* o);            /* chain score per record */
+uint32_t herro_overlaps_occ_cut(const herro_overlaps* o);                 /* the frequency cut the call used */
 void herro_overlaps_free(herro_overlaps* o);
 /* ---- pair overlaps: reads -> one record per read pair -> mirrored alignments -> job, in three calls ----------------------------------
  * herro_find_overlaps writes both directions of every pair; aligning each pair once and mirroring the alignment (herro_aligned_dev_mirror)
@@ -536,7 +546,7 @@ void herro_pairs_free(herro_pairs* pairs);
  *   A read pair is wanted iff at least one of its two reads is core; a row (target, query) is wanted iff its target is core.
  * The finder creates no anchor between two non-core reads (k_runs, k_expand in csrc/overlap_dev.hip), so the sorts, the groups, the
  * chains, the strand choice, the extension, the aligner and the mirror see wanted pairs only.  Chains are independent per (t, q, strand)
- * and max_occ stays the cut of the whole store's index, so the result is a selection of the unmasked one.  With F the handle
+ * and the frequency cut (max_occ or occ_frac_ppm's) stays that of the whole store's index, so the result is a selection of the unmasked one.  With F the handle
  * herro_find_overlap_pairs returns for the same reads and parameters:
  *   primaries   those of F with core[tid] | core[qid], in F's order; chain_scores, ext and ext_scores the same selection; P' of them.
  *   rows        F's rows whose target is core, in F's order: target_ids is F's targets that are core, aln_off counts the kept rows,
@@ -560,6 +570,10 @@ int herro_pairs_from_table_core(herro_ctx* ctx, uint32_t n_pairs, const herro_al
                                 const uint32_t* rids, const uint64_t* aln_off /* [n_targets + 1] */, uint64_t n_rows,
                                 const uint32_t* rec_of_row /* [n_rows] */, herro_pairs** out);
 uint64_t herro_pairs_n_rows(const herro_pairs* pairs);
+uint32_t herro_pairs_occ_cut(const herro_pairs* pairs);                    /* the frequency cut the finder used; 0: a handle over a table */
+/* Test hook: the census and the pick of occ_frac_ppm alone (occ_frac_ppm 0: HERRO_E_INVALID).  hist: the 65536 bins of min(occurrences,
+ * 65535) over the distinct hashes; out = {cut, distinct hashes, hashes above the cut, minimizers in them}. */
+int herro_debug_occ_census(herro_ctx* ctx, const herro_overlap_params* params, uint32_t* hist /* [65536] or NULL */, uint64_t out[4]);
 /* Test hook: stage 1 alone — the store's minimizers sorted by (rid, pos); pos = index of the k-mer's last base on the forward
  * read, strand = 1 when the reverse complement is the canonical k-mer.  Returns their number (nothing is written when cap is
  * smaller) or a negative error. */

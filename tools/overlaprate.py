@@ -3,8 +3,11 @@ call (sketch, both sorts, chaining, results back; the call returns when the devi
 call), next to herro_align_overlaps on the records it emitted.  Two sets: the bench's shape (targets of 4096 bp with 32
 overlaps each) and reads of >= 30 kb.  Prints one JSON line per set; run it under `rocprofv3 --kernel-trace --stats` for the
 kernels alone.
+--occ-frac-ppm N: every set is measured three times on one context — with the fixed cut, with the cut taken from the index (occ_frac_ppm = N)
+and with the fixed cut set to the value the index gave, so that the last two differ by the census and the pick alone (`occ_share`).
+--deep: one short genome under many reads (--deep-reads 200 of --deep-len 400 bases), the shape a fixed cut below the depth finds nothing in.
 
-    python tools/overlaprate.py [--targets 256] [--long-targets 8] [--reps 5] [--no-align]"""
+    python tools/overlaprate.py [--targets 256] [--long-targets 8] [--reps 5] [--no-align] [--occ-frac-ppm 5000] [--deep]"""
 from __future__ import annotations
 
 import argparse
@@ -36,13 +39,51 @@ def stage_sizes(fn):
             os.close(saved)
         f.seek(0)
         text = f.read().decode(errors="replace")
-    m = re.search(r"OVL (.*)", text)
-    return r, {k: int(v) for k, v in (kv.split("=") for kv in m.group(1).split())} if m else {}
+    sizes = {}
+    for tag, prefix in (("OVL", ""), ("OVLOCC", "occ_")):
+        m = re.search(tag + r" (.*)", text)
+        if m:
+            sizes.update({prefix + k: int(v) for k, v in (kv.split("=") for kv in m.group(1).split())})
+    return r, sizes
 
 
-def measure(name, sb, reps, params, align):
+class Deep:
+    """n reads of one genome of L bases with 0.5 % substitutions, every third one reversed and complemented: what set_reads takes"""
+
+    def __init__(self, n, L, seed=43):
+        rng = np.random.default_rng(seed)
+        g = rng.integers(0, 4, L)
+        comp = bytes.maketrans(b"ACGT", b"TGCA")
+        reads = []
+        for r in range(n):
+            x = g.copy()
+            at = np.flatnonzero(rng.random(L) < 0.005)
+            x[at] = (x[at] + rng.integers(1, 4, len(at))) % 4
+            b = bytes(b"ACGT"[v] for v in x)
+            reads.append(b.translate(comp)[::-1] if r % 3 == 2 else b)
+        self.n_reads = n
+        self.seq = np.frombuffer(b"".join(reads), np.uint8)
+        self.qual = np.full(len(self.seq), 40 + 33, np.uint8)
+        self.off = (np.arange(n + 1) * L).astype(np.uint64)
+
+
+def measure(name, sb, reps, params, align, occ_frac_ppm=0):
     c = api.Context(0)
     c.set_reads(sb.seq, sb.qual, sb.off)
+    if occ_frac_ppm:
+        fixed = measure_on(c, name, sb, reps, params, False)
+        frac = measure_on(c, name, sb, reps, dict({k: v for k, v in params.items() if k != "max_occ"}, occ_frac_ppm=occ_frac_ppm), align)
+        same = measure_on(c, name, sb, reps, dict(params, max_occ=frac["occ_cut"]), False)
+        print(json.dumps({"set": name, "occ_frac_ppm": occ_frac_ppm, "cut": frac["occ_cut"], "seconds_fixed": fixed["seconds_median"],
+                          "seconds_frac": frac["seconds_median"], "seconds_fixed_at_the_cut": same["seconds_median"],
+                          "same_records": frac["records"] == same["records"] and frac["anchors"] == same["anchors"],
+                          "occ_share": (frac["seconds_median"] - same["seconds_median"]) / frac["seconds_median"]}), flush=True)
+    else:
+        measure_on(c, name, sb, reps, params, align)
+    c.close()
+
+
+def measure_on(c, name, sb, reps, params, align):
     (rids, rows, off, sc), sizes = stage_sizes(lambda: c.find_overlaps(**params))     # also the warm-up (code objects, allocator)
     times = []
     for _ in range(reps):
@@ -65,7 +106,7 @@ def measure(name, sb, reps, params, align):
         res.update({"align_seconds_median": ta, "align_seconds_min": min(at), "align_seconds_max": max(at), "align_records_per_s": len(rows) / ta,
                     "align_failed": int((~ok).sum()), "find_over_align": t / ta})
     print(json.dumps(res), flush=True)
-    c.close()
+    return res
 
 
 def main():
@@ -77,13 +118,20 @@ def main():
     ap.add_argument("--long-len", type=int, default=30000)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-align", action="store_true")
+    ap.add_argument("--occ-frac-ppm", type=int, default=0, help="also measure with the cut taken from the index (5000 = minimap2 -f0.005)")
+    ap.add_argument("--deep", action="store_true", help="only the deep shape: one short genome under many reads")
+    ap.add_argument("--deep-reads", type=int, default=200)
+    ap.add_argument("--deep-len", type=int, default=400)
     a = ap.parse_args()
+    if a.deep:
+        measure("deep", Deep(a.deep_reads, a.deep_len), a.reps, dict(k=15, w=5, max_occ=128, min_score=60), not a.no_align, a.occ_frac_ppm)
+        return
     if a.targets:
         measure("bench shape", synth.generate_parallel(a.targets, a.target_len, a.overlaps, chunk=64), a.reps,
-                dict(max_occ=128, min_score=100), not a.no_align)
+                dict(max_occ=128, min_score=100), not a.no_align, a.occ_frac_ppm)
     if a.long_targets:
         measure(">= 30 kb", synth.generate_parallel(a.long_targets, a.long_len, 16, chunk=4, flank_min=200, flank_max=400), a.reps,
-                dict(max_occ=128), not a.no_align)
+                dict(max_occ=128), not a.no_align, a.occ_frac_ppm)
 
 
 if __name__ == "__main__":
