@@ -44,6 +44,8 @@ EXPORTS = [
     "herro_pairs_rec_of_row", "herro_pairs_free",
     "herro_find_overlaps_core", "herro_find_overlap_pairs_core", "herro_pairs_from_table_core", "herro_pairs_n_rows",
     "herro_overlaps_occ_cut", "herro_pairs_occ_cut", "herro_debug_occ_census",
+    "herro_aligned_dev_paf", "herro_pairs_paf", "herro_paf_text_data", "herro_paf_text_len", "herro_paf_text_lines", "herro_paf_text_free",
+    "herro_pairs_write_alns",
 ]
 
 
@@ -91,6 +93,7 @@ def _job_or_raise(ctx: "Context", h, n_targets: int) -> "Job":
 
 
 PAIRS_NO_EXTEND = 1   # HERRO_PAIRS_NO_EXTEND
+ALNS_OEC = 1          # HERRO_ALNS_OEC
 
 
 class OverlapParams(C.Structure):  # herro_overlap_params (0 = the field's default)
@@ -281,6 +284,20 @@ def lib():
                 f.restype = u32
                 f.argtypes = [vp]
             L.herro_debug_occ_census.argtypes = [vp, vp, vp, vp]
+        except AttributeError:
+            if not os.environ.get("HERRO_LIB"):
+                raise
+        try:   # (an older build selected by HERRO_LIB lacks the PAF writer: everything else still runs)
+            L.herro_aligned_dev_paf.argtypes = [vp, vp, u64, vp, C.c_char_p, vp, vp]
+            L.herro_pairs_paf.argtypes = [vp, vp, vp, C.c_char_p, vp, vp]
+            L.herro_paf_text_data.restype = vp
+            L.herro_paf_text_data.argtypes = [vp]
+            for f in (L.herro_paf_text_len, L.herro_paf_text_lines):
+                f.restype = u64
+                f.argtypes = [vp]
+            L.herro_paf_text_free.restype = None
+            L.herro_paf_text_free.argtypes = [vp]
+            L.herro_pairs_write_alns.argtypes = [vp, vp, vp, C.c_char_p, vp, C.c_char_p, u32, vp, vp]
         except AttributeError:
             if not os.environ.get("HERRO_LIB"):
                 raise
@@ -977,6 +994,23 @@ class Job:
         return {a: int(b) for a, b in zip(k, o)}
 
 
+def _name_blob(ctx: "Context", names: list[bytes]):
+    """(names back to back, name_off u64 [n_reads + 1]) as the PAF writer and herro_name_index_create take them"""
+    if len(names) != getattr(ctx, "n_reads", len(names)):
+        raise ValueError(f"{len(names)} names for {ctx.n_reads} reads")
+    off = np.zeros(len(names) + 1, np.uint64)
+    off[1:] = np.cumsum([len(n) for n in names])
+    return b"".join(names), off
+
+
+def _paf_text_bytes(L, h) -> bytes:
+    try:
+        n = int(L.herro_paf_text_len(h))
+        return C.string_at(L.herro_paf_text_data(h), n) if n else b""
+    finally:
+        L.herro_paf_text_free(h)
+
+
 class AlignedDev:
     """herro_aligned_dev: aligned records whose ops live on the device.  rows u32 [n, 10] (trimmed coordinates, cigar_len 0),
     scores i32 [n], n_ops u32 [n], ok bool [n] (False: failed, no ops)."""
@@ -1001,6 +1035,21 @@ class AlignedDev:
         if n < 0:
             raise HerroError(int(n), "herro_aligned_dev_cigar")
         return C.string_at(buf, n)
+
+    def paf(self, names: list[bytes], rec=None) -> bytes:
+        """herro_aligned_dev_paf: the PAF lines (with cg:Z:) of records rec, in that order (None: all of them) — formed on the device for a
+        device handle, by the host formatter for a HostContext's; failed records give no line.  names: the read names, index = read id."""
+        blob, off = _name_blob(self.ctx, names)
+        if rec is None:
+            n_rows, rp = self.n, None
+        else:
+            rec = np.ascontiguousarray(rec, np.uint32)
+            n_rows = len(rec)
+            buf = rec if n_rows else np.zeros(1, np.uint32)   # (never a NULL pointer: that would mean "row i is record i")
+            rp = buf.ctypes.data
+        h = C.c_void_p()
+        self.ctx._chk(self._l.herro_aligned_dev_paf(self.ctx.h, self.h, n_rows, rp, blob, off.ctypes.data, C.byref(h)))
+        return _paf_text_bytes(self._l, h)
 
     def mirror(self) -> "AlignedDev":
         """herro_aligned_dev_mirror: a new handle of 2n records — record r is this handle's record r, record n + r its mirror, the
@@ -1051,6 +1100,26 @@ class OverlapPairs:
         h = C.c_void_p()
         self.ctx._chk(self._l.herro_pairs_align(self.ctx.h, self.h, C.byref(h)))
         return AlignedDev(self.ctx, h)
+
+    def paf(self, m: "AlignedDev", names: list[bytes]) -> bytes:
+        """herro_pairs_paf: the PAF lines of the table's rows, in its order, from the handle align() returned — the alignments
+        Context.create_job_paired builds its job from (rows whose record failed give no line)."""
+        blob, off = _name_blob(self.ctx, names)
+        h = C.c_void_p()
+        self.ctx._chk(self._l.herro_pairs_paf(self.ctx.h, self.h, m.h, blob, off.ctypes.data, C.byref(h)))
+        return _paf_text_bytes(self._l, h)
+
+    def write_alns(self, m: "AlignedDev", names: list[bytes], path: str, oec: bool | None = None) -> tuple[int, int]:
+        """herro_pairs_write_alns: the lines of paf() streamed to `path` — as the reference's batch file (one zstd frame: target count, target
+        names, lines; what `--write-alns` writes and `--read-alns` / Paf(path=...) read) when oec, which None decides by the suffix
+        .oec.zst; plain PAF otherwise.  Returns (lines, bytes of the file)."""
+        blob, off = _name_blob(self.ctx, names)
+        if oec is None:
+            oec = str(path).endswith(".oec.zst")
+        lines, size = C.c_uint64(), C.c_uint64()
+        self.ctx._chk(self._l.herro_pairs_write_alns(self.ctx.h, self.h, m.h, blob, off.ctypes.data, os.fsencode(path), ALNS_OEC if oec else 0,
+                                                     C.byref(lines), C.byref(size)))
+        return int(lines.value), int(size.value)
 
     def close(self):
         if getattr(self, "h", None):

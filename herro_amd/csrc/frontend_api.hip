@@ -1,6 +1,7 @@
 // frontend_api.hip — the C ABI's front end (include/herro_amd.h): reads alone -> overlap records -> their ops on the device.
-// herro_find_overlaps[_core], herro_extend_overlaps, herro_align_overlaps[_dev], herro_aligned_dev_*, herro_find_overlap_pairs[_core], herro_pairs_* and the test hooks herro_debug_sketch and herro_debug_occ_census.  Host C++ (compiled by hipcc) over
-// overlap_dev.hip and align_dev.hip; contexts, the model and jobs are herro_api.hip.
+// herro_find_overlaps[_core], herro_extend_overlaps, herro_align_overlaps[_dev], herro_aligned_dev_*, herro_find_overlap_pairs[_core], herro_pairs_*, the PAF / .oec.zst
+// writer (herro_aligned_dev_paf, herro_pairs_paf, herro_pairs_write_alns) and the test hooks herro_debug_sketch and herro_debug_occ_census.  Host C++ (compiled by
+// hipcc) over overlap_dev.hip, align_dev.hip and paf_dev.hip; contexts, the model and jobs are herro_api.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,8 +10,10 @@
 
 #include "aligned_dev.h"
 #include "align_dev.h"
+#include "alns_file.h"
 #include "dev_bufs.h"
 #include "overlap_dev.h"
+#include "paf_dev.h"
 
 namespace {
 constexpr uint32_t SLICE = 1u << 20;   // records per turn of herro_extend_overlaps and herro_aligned_dev_mirror: their descriptors and results stay small whatever n is
@@ -29,8 +32,8 @@ int device_ready(herro_ctx* ctx, const char* who) {
   return HERRO_OK;
 }
 
-// 4 GiB of device scratch per call, or what the environment says (in MiB, at least 1)
-uint64_t scratch_budget(const char* env_name) { const char* e = getenv(env_name); return e ? (uint64_t)std::max(1ll, atoll(e)) << 20 : 4096ull << 20; }
+// 4 GiB of device scratch per call (the writer: default_mb), or what the environment says (in MiB, at least 1)
+uint64_t scratch_budget(const char* env_name, uint64_t default_mb = 4096) { const char* e = getenv(env_name); return e ? (uint64_t)std::max(1ll, atoll(e)) << 20 : default_mb << 20; }
 
 herro::OvlStore ovl_store(const herro_ctx* ctx) { return herro::OvlStore{ctx->d_words, ctx->d_word_off, ctx->d_qual_off, ctx->read_len.data(), ctx->n_reads}; }
 
@@ -745,6 +748,281 @@ const uint32_t* herro_pairs_rec_of_row(const herro_pairs* p) { return p ? p->rec
 uint64_t herro_pairs_n_rows(const herro_pairs* p) { return p ? p->rec_of_row.size() : 0; }
 uint32_t herro_pairs_occ_cut(const herro_pairs* p) { return p ? p->occ_cut : 0; }
 void herro_pairs_free(herro_pairs* p) { delete p; }
+
+// ---- PAF / .oec.zst of found alignments (paf_dev.hip) ----------------------------------------------------------------------------
+// What `herro inference --write-alns` keeps of a batch (AlnMode::Write: overlaps.rs:248-286, the lines themselves 349-352): one PAF line with `cg:Z:` per
+// alignment.  Line format: paf_dev.h.  Columns 10 and 11 are the summed M lengths and the summed op lengths, not minimap2's residue matches and block
+// length; the reference reads neither (overlaps.rs:135-172).  A device handle's lines are formed by k_paf_len / k_paf_write in chunks of text that
+// fit HERRO_PAF_SCRATCH_MB and come down through two pinned buffers; a device-free handle's by paf_line_host below, which is the specification.
+struct herro_paf_text {
+  std::string text;
+  uint64_t lines = 0;
+};
+
+namespace {
+struct PafStats { uint64_t rows = 0, lines = 0, bytes = 0, chunks = 0; };
+using PafSink = std::function<int(const char*, uint64_t)>;   // whole lines, in order; HERRO_OK, or the code whose message it left in ctx->err
+constexpr uint64_t PAF_BUDGET_CHUNKS = 16;                   // a chunk's text is this fraction of the budget (64 MiB at the default): the two pinned halves stay small, and a text as large as the budget still overlaps its copies with the next chunk's kernels
+constexpr uint64_t PAF_HOST_ROWS = 16384;                    // rows of a turn of the host formatter
+
+int paf_invalid(herro_ctx* ctx, const char* who, const std::string& why) {
+  ctx->err = std::string(who) + ": " + why;
+  return HERRO_E_INVALID;
+}
+
+// a name is a PAF field: not empty, no tab, no newline
+int check_names(herro_ctx* ctx, const char* who, const char* names, const uint64_t* name_off) {
+  for (uint32_t r = 0; r < ctx->n_reads; r++) {
+    const uint64_t b = name_off[r], e = name_off[r + 1];
+    if (e <= b) return paf_invalid(ctx, who, "read " + std::to_string(r) + ": empty name");
+    if (memchr(names + b, '\t', e - b) || memchr(names + b, '\n', e - b))
+      return paf_invalid(ctx, who, "read " + std::to_string(r) + ": a name must not contain a tab or a newline");
+  }
+  return HERRO_OK;
+}
+
+// The specification of a line: row `a` with its ops, appended to out.
+void paf_line_host(const herro_alignment& a, const uint32_t* ops, uint32_t n_ops, const char* names, const uint64_t* name_off, std::string& out) {
+  if (!n_ops) return;
+  uint64_t mbases = 0, blocklen = 0;
+  for (uint32_t x = 0; x < n_ops; x++) {
+    blocklen += ops[x] >> 2;
+    if ((ops[x] & 3u) == 0) mbases += ops[x] >> 2;
+  }
+  char buf[160];
+  out.append(names + name_off[a.qid], name_off[a.qid + 1] - name_off[a.qid]);
+  out.append(buf, snprintf(buf, sizeof buf, "\t%u\t%u\t%u\t%c\t", a.qlen, a.qstart, a.qend, a.strand ? '-' : '+'));
+  out.append(names + name_off[a.tid], name_off[a.tid + 1] - name_off[a.tid]);
+  out.append(buf, snprintf(buf, sizeof buf, "\t%u\t%u\t%u\t%llu\t%llu\t255\tcg:Z:", a.tlen, a.tstart, a.tend, (unsigned long long)mbases, (unsigned long long)blocklen));
+  const size_t at = out.size();
+  out.resize(at + ops_text_bytes(ops, n_ops) + 1);   // (+ 1: snprintf's terminator of the last op lands where the newline goes)
+  ops_text(ops, n_ops, &out[at]);
+  out.back() = '\n';
+}
+
+int paf_emit_host(herro_ctx* ctx, const herro_aligned_dev* a, const std::vector<uint32_t>& recs, const char* names, const uint64_t* name_off, const PafSink& sink,
+                  PafStats& st) {
+  std::vector<std::string> part;
+  std::string turn;
+  for (uint64_t r0 = 0; r0 < recs.size(); r0 += PAF_HOST_ROWS) {
+    const uint64_t r1 = std::min<uint64_t>(recs.size(), r0 + PAF_HOST_ROWS);
+    part.assign((r1 - r0 + 63) / 64, std::string());
+    host_pool(ctx).run((uint32_t)part.size(), [&](uint32_t b) {
+      for (uint64_t i = r0 + (uint64_t)b * 64; i < std::min(r1, r0 + (uint64_t)(b + 1) * 64); i++)
+        paf_line_host(a->alns[recs[i]], a->h_ops.data() + a->op_off[recs[i]], a->n_ops[recs[i]], names, name_off, part[b]);
+    });
+    turn.clear();
+    for (const std::string& s : part) turn += s;
+    for (uint64_t i = r0; i < r1; i++) st.lines += a->n_ops[recs[i]] != 0;
+    if (turn.empty()) continue;
+    st.bytes += turn.size(); st.chunks++;
+    if (const int rc = sink(turn.data(), turn.size())) return rc;
+  }
+  return HERRO_OK;
+}
+
+// the pinned halves and events of paf_emit_dev: nothing of the stream is in flight when they go
+struct PafStage {
+  hipStream_t st = nullptr;
+  char* pin[2] = {nullptr, nullptr};
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~PafStage() {
+    (void)hipStreamSynchronize(st);
+    for (int b = 0; b < 2; b++) {
+      if (pin[b]) (void)hipHostFree(pin[b]);
+      if (ev[b]) (void)hipEventDestroy(ev[b]);
+    }
+  }
+};
+
+int paf_emit_dev(herro_ctx* ctx, const char* who, const herro_aligned_dev* a, const std::vector<uint32_t>& recs, const char* names, const uint64_t* name_off,
+                 const PafSink& sink, PafStats& st) {
+  const uint32_t n = (uint32_t)recs.size();   // (<= PAF_MAX_ROWS: paf_emit)
+  if (!n) return HERRO_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::vector<herro::PafRow> rows(n);
+  for (uint32_t i = 0; i < n; i++) {
+    const herro_alignment& x = a->alns[recs[i]];
+    rows[i] = herro::PafRow{a->op_off[recs[i]], a->n_ops[recs[i]], x.qid, x.qlen, x.qstart, x.qend, x.strand, x.tid, x.tlen, x.tstart, x.tend};
+  }
+  std::vector<uint64_t> noff(ctx->n_reads + 1ull);   // the names from their first byte
+  for (uint32_t r = 0; r <= ctx->n_reads; r++) noff[r] = name_off[r] - name_off[0];
+  herro::Bufs B;
+  PafStage S;
+  S.st = ctx->stream;
+  herro::PafRow* d_rows = nullptr;
+  herro::PafSums* d_sums = nullptr;
+  uint32_t* d_len = nullptr;
+  uint64_t* d_noff = nullptr;
+  char* d_names = nullptr;
+  FRONT_TRY(ctx, who, "rows", B.bytes(&d_rows, sizeof(herro::PafRow) * (uint64_t)n));
+  FRONT_TRY(ctx, who, "sums", B.bytes(&d_sums, sizeof(herro::PafSums) * (uint64_t)n));
+  FRONT_TRY(ctx, who, "line bytes", B.bytes(&d_len, 4ull * n));
+  FRONT_TRY(ctx, who, "name offsets", B.bytes(&d_noff, 8ull * noff.size()));
+  FRONT_TRY(ctx, who, "names", B.bytes(&d_names, std::max<uint64_t>(noff.back(), 1)));
+  FRONT_TRY(ctx, who, "row upload", hipMemcpyAsync(d_rows, rows.data(), sizeof(herro::PafRow) * (uint64_t)n, hipMemcpyHostToDevice, ctx->stream));
+  FRONT_TRY(ctx, who, "name offset upload", hipMemcpyAsync(d_noff, noff.data(), 8ull * noff.size(), hipMemcpyHostToDevice, ctx->stream));
+  if (noff.back()) FRONT_TRY(ctx, who, "name upload", hipMemcpyAsync(d_names, names + name_off[0], noff.back(), hipMemcpyHostToDevice, ctx->stream));
+  herro::launch_paf_len(d_rows, a->d_ops, d_noff, n, d_len, d_sums, ctx->stream);
+  FRONT_TRY(ctx, who, "k_paf_len launch", hipGetLastError());
+  std::vector<uint32_t> len(n);
+  FRONT_TRY(ctx, who, "line bytes", hipMemcpyAsync(len.data(), d_len, 4ull * n, hipMemcpyDeviceToHost, ctx->stream));
+  FRONT_TRY(ctx, who, "k_paf_len", hipStreamSynchronize(ctx->stream));
+  // chunks: consecutive rows whose text fits a sixteenth of the budget (two such buffers are resident); a longer line runs alone
+  // ... and no chunk reaches 2^32 bytes whatever the budget: its line offsets are a 32-bit scan (a line alone is at most PAF_MAX_CHUNK, checked below)
+  const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(scratch_budget("HERRO_PAF_SCRATCH_MB", 1024) / PAF_BUDGET_CHUNKS, 1), herro::PAF_MAX_CHUNK);
+  std::vector<uint32_t> cut{0};
+  std::vector<uint64_t> cbytes;
+  uint64_t acc = 0, max_bytes = 0;
+  uint32_t max_rows = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    if (len[i] > herro::PAF_MAX_CHUNK) {
+      ctx->err = std::string(who) + ": row " + std::to_string(i) + ": a line of 2^32 bytes or more";
+      return HERRO_E_UNSUPPORTED;
+    }
+    if (acc && acc + len[i] > cap) { cut.push_back(i); cbytes.push_back(acc); acc = 0; }
+    acc += len[i];
+    st.lines += len[i] != 0;
+  }
+  cut.push_back(n); cbytes.push_back(acc);
+  for (size_t c = 0; c < cbytes.size(); c++) {
+    max_bytes = std::max(max_bytes, cbytes[c]);
+    max_rows = std::max(max_rows, cut[c + 1] - cut[c]);
+  }
+  if (!max_bytes) return HERRO_OK;   // every row failed
+  char* d_text[2] = {nullptr, nullptr};
+  uint32_t *d_off[2] = {nullptr, nullptr}, *d_part[2] = {nullptr, nullptr};
+  const int halves = cbytes.size() > 1 ? 2 : 1;
+  for (int b = 0; b < halves; b++) {
+    FRONT_TRY(ctx, who, "text", B.bytes(&d_text[b], max_bytes));
+    FRONT_TRY(ctx, who, "line offsets", B.bytes(&d_off[b], 4ull * (max_rows + 1ull)));
+    FRONT_TRY(ctx, who, "scan scratch", B.bytes(&d_part[b], 4ull * herro::ovl_scan_partials(max_rows) + 64));
+    FRONT_TRY(ctx, who, "pinned text", hipHostMalloc((void**)&S.pin[b], max_bytes, hipHostMallocDefault));
+    FRONT_TRY(ctx, who, "event", hipEventCreateWithFlags(&S.ev[b], hipEventDisableTiming));
+  }
+  std::string msg;
+  // chunk c: offsets, text, the copy into pinned half c & 1 and the event behind it.  The stream orders a half's reuse on the device; the host has
+  // consumed the pinned half of chunk c - 2 before chunk c is queued.
+  auto queue = [&](size_t c) -> int {
+    if (!cbytes[c]) return HERRO_OK;
+    const int b = (int)(c & 1);
+    const uint32_t r0 = cut[c], cnt = cut[c + 1] - cut[c];
+    if (herro::ovl_scan_u32(d_len + r0, cnt, d_off[b], d_part[b], ctx->stream, msg) != herro::OVL_OK) { ctx->err = std::string(who) + ": " + msg; return HERRO_E_NO_DEVICE; }
+    herro::launch_paf_write(d_rows + r0, a->d_ops, d_names, d_noff, d_off[b], d_sums + r0, cnt, d_text[b], cbytes[c], ctx->stream);
+    FRONT_TRY(ctx, who, "k_paf_write launch", hipGetLastError());
+    FRONT_TRY(ctx, who, "text copy", hipMemcpyAsync(S.pin[b], d_text[b], cbytes[c], hipMemcpyDeviceToHost, ctx->stream));
+    FRONT_TRY(ctx, who, "event", hipEventRecord(S.ev[b], ctx->stream));
+    return HERRO_OK;
+  };
+  if (const int rc = queue(0)) return rc;
+  for (size_t c = 0; c < cbytes.size(); c++) {
+    if (c + 1 < cbytes.size())
+      if (const int rc = queue(c + 1)) return rc;
+    if (!cbytes[c]) continue;
+    FRONT_TRY(ctx, who, "k_paf_write", hipEventSynchronize(S.ev[c & 1]));
+    st.bytes += cbytes[c]; st.chunks++;
+    if (const int rc = sink(S.pin[c & 1], cbytes[c])) return rc;
+  }
+  return HERRO_OK;
+}
+
+// Checks in the order of include/herro_amd.h, then the lines of rows rec[0 .. n_rows) (NULL: row i is record i) to the sink, chunk by chunk.
+int paf_emit(herro_ctx* ctx, const char* who, const herro_aligned_dev* a, uint64_t n_rows, const uint32_t* rec, const char* names, const uint64_t* name_off,
+             const PafSink& sink, PafStats& st) {
+  if (a->ctx != ctx) return paf_invalid(ctx, who, "the handle belongs to another context");
+  if (!ctx->n_reads || (!ctx->host_only && !ctx->d_words)) { ctx->err = "herro_set_reads must be called first"; return HERRO_E_STATE; }   // (device-free: made over no read)
+  if (n_rows > herro::PAF_MAX_ROWS) { ctx->err = std::string(who) + ": more than 2^31 - 1 rows"; return HERRO_E_UNSUPPORTED; }
+  std::vector<uint32_t> recs(n_rows);
+  for (uint64_t i = 0; i < n_rows; i++) {
+    const uint64_t r = rec ? rec[i] : i;
+    if (r >= a->alns.size()) return paf_invalid(ctx, who, "rec[" + std::to_string(i) + "] = " + std::to_string(r) + " is outside the " + std::to_string(a->alns.size()) + " records");
+    if (a->alns[r].qid >= ctx->n_reads || a->alns[r].tid >= ctx->n_reads)
+      return paf_invalid(ctx, who, "row " + std::to_string(i) + " (record " + std::to_string(r) + "): read id outside the read store");
+    recs[i] = (uint32_t)r;
+  }
+  st.rows = n_rows;
+  const int rc = a->host_only ? paf_emit_host(ctx, a, recs, names, name_off, sink, st) : paf_emit_dev(ctx, who, a, recs, names, name_off, sink, st);
+  if (rc != HERRO_OK) return rc;
+  const char* e = getenv("HERRO_PAF_STATS");   // (tools/pafwriterate.py, the budget test): one line on stderr
+  if (e && atoi(e))
+    fprintf(stderr, "PAF rows=%llu lines=%llu bytes=%llu chunks=%llu\n", (unsigned long long)st.rows, (unsigned long long)st.lines, (unsigned long long)st.bytes,
+            (unsigned long long)st.chunks);
+  return HERRO_OK;
+}
+
+// what the pair entries ask before anything runs: the names, then the two handles
+int check_pairs_paf(herro_ctx* ctx, const char* who, const herro_pairs* p, const herro_aligned_dev* m, const char* names, const uint64_t* name_off) {
+  if (const int rc = check_names(ctx, who, names, name_off)) return rc;
+  if (p->ctx != ctx || m->ctx != ctx) return paf_invalid(ctx, who, "the handle belongs to another context");
+  if (m->alns.size() != 2 * p->alns.size())
+    return paf_invalid(ctx, who, "the aligned handle has " + std::to_string(m->alns.size()) + " records, the pairs need " + std::to_string(2 * p->alns.size()) + " (primaries, then mirrors)");
+  return HERRO_OK;
+}
+
+int paf_to_text(herro_ctx* ctx, const char* who, const herro_aligned_dev* a, uint64_t n_rows, const uint32_t* rec, const char* names, const uint64_t* name_off,
+                herro_paf_text** out) {
+  std::unique_ptr<herro_paf_text> h(new herro_paf_text());
+  PafStats st;
+  const int rc = paf_emit(ctx, who, a, n_rows, rec, names, name_off, [&](const char* p, uint64_t n) { h->text.append(p, n); return HERRO_OK; }, st);
+  if (rc != HERRO_OK) return rc;
+  h->lines = st.lines;
+  *out = h.release();
+  return HERRO_OK;
+}
+}  // namespace
+
+int herro_aligned_dev_paf(herro_ctx* ctx, const herro_aligned_dev* a, uint64_t n_rows, const uint32_t* rec, const char* names, const uint64_t* name_off,
+                          herro_paf_text** out) {
+  if (!ctx || !a || !out || !name_off || (ctx->n_reads && !names)) return HERRO_E_INVALID;
+  *out = nullptr;
+  const char* const who = "herro_aligned_dev_paf";
+  if (const int rc = check_names(ctx, who, names, name_off)) return rc;
+  return paf_to_text(ctx, who, a, n_rows, rec, names, name_off, out);
+}
+
+int herro_pairs_paf(herro_ctx* ctx, const herro_pairs* p, const herro_aligned_dev* m, const char* names, const uint64_t* name_off, herro_paf_text** out) {
+  if (!ctx || !p || !m || !out || !name_off || (ctx->n_reads && !names)) return HERRO_E_INVALID;
+  *out = nullptr;
+  const char* const who = "herro_pairs_paf";
+  if (const int rc = check_pairs_paf(ctx, who, p, m, names, name_off)) return rc;
+  return paf_to_text(ctx, who, m, p->rec_of_row.size(), p->rec_of_row.data(), names, name_off, out);
+}
+
+const char* herro_paf_text_data(const herro_paf_text* t) { return t ? t->text.data() : nullptr; }
+uint64_t herro_paf_text_len(const herro_paf_text* t) { return t ? t->text.size() : 0; }
+uint64_t herro_paf_text_lines(const herro_paf_text* t) { return t ? t->lines : 0; }
+void herro_paf_text_free(herro_paf_text* t) { delete t; }
+
+// The batch file of AlnMode::Write (overlaps.rs:270-282): "<n_targets>\n", the targets' names, the lines — one zstd frame (HERRO_ALNS_OEC), or the lines alone.
+int herro_pairs_write_alns(herro_ctx* ctx, const herro_pairs* p, const herro_aligned_dev* m, const char* names, const uint64_t* name_off, const char* path,
+                           uint32_t flags, uint64_t* lines, uint64_t* bytes) {
+  if (!ctx || !p || !m || !path || !name_off || (ctx->n_reads && !names)) return HERRO_E_INVALID;
+  const char* const who = "herro_pairs_write_alns";
+  if (const int rc = check_pairs_paf(ctx, who, p, m, names, name_off)) return rc;
+  if (flags & ~HERRO_ALNS_OEC) return paf_invalid(ctx, who, "unknown flag");
+  for (size_t t = 0; t < p->rids.size(); t++)
+    if (p->rids[t] >= ctx->n_reads) return paf_invalid(ctx, who, "target " + std::to_string(t) + ": read id outside the read store");
+  AlnsFile f;   // (leaves no file unless committed)
+  std::string why;
+  bool unsupported = false;
+  auto file_failed = [&]() { ctx->err = std::string(who) + ": " + why; return unsupported ? HERRO_E_UNSUPPORTED : HERRO_E_INVALID; };
+  if (!f.open(path, (flags & HERRO_ALNS_OEC) != 0, why, unsupported)) return file_failed();
+  if (flags & HERRO_ALNS_OEC) {
+    std::string head = std::to_string(p->rids.size()) + "\n";
+    for (const uint32_t t : p->rids) { head.append(names + name_off[t], name_off[t + 1] - name_off[t]); head += '\n'; }
+    if (!f.write(head.data(), head.size(), why)) return file_failed();
+  }
+  PafStats st;
+  const int rc = paf_emit(ctx, who, m, p->rec_of_row.size(), p->rec_of_row.data(), names, name_off,
+                          [&](const char* q, uint64_t n) { return f.write(q, n, why) ? HERRO_OK : file_failed(); }, st);
+  if (rc != HERRO_OK) return rc;
+  if (!f.commit(why)) return file_failed();
+  const char* e = getenv("HERRO_PAF_STATS");
+  if (e && atoi(e)) fprintf(stderr, "PAFFILE file_bytes=%llu zstd_s=%.6f\n", (unsigned long long)f.file_bytes, f.zstd_seconds);
+  if (lines) *lines = st.lines;
+  if (bytes) *bytes = f.file_bytes;
+  return HERRO_OK;
+}
 
 int64_t herro_debug_sketch(herro_ctx* ctx, const herro_overlap_params* params, uint64_t* hash, uint32_t* rid, uint32_t* pos,
                            uint8_t* strand, uint64_t cap) {

@@ -37,6 +37,9 @@
 #include <unordered_set>
 #include <vector>
 
+#include <chrono>
+
+#include "alns_file.h"
 #include "host_cpus.h"
 #include "../../include/herro_amd.h"
 
@@ -283,7 +286,14 @@ struct Zstd {
   size_t (*decompressStream)(void*, ZOut*, ZIn*) = nullptr;
   unsigned (*isError)(size_t) = nullptr;
   const char* (*getErrorName)(size_t) = nullptr;
-  bool ok = false;
+  // the streaming compressor (AlnsFile)
+  void* (*createCStream)() = nullptr;
+  size_t (*freeCStream)(void*) = nullptr;
+  size_t (*initCStream)(void*, int) = nullptr;
+  size_t (*compressStream)(void*, ZOut*, ZIn*) = nullptr;
+  size_t (*endStream)(void*, ZOut*) = nullptr;
+  size_t (*CStreamOutSize)() = nullptr;
+  bool ok = false, c_ok = false;
   Zstd() {
     for (const char* n : {"libzstd.so.1", "libzstd.so"}) {
       h = dlopen(n, RTLD_NOW | RTLD_LOCAL);
@@ -297,11 +307,19 @@ struct Zstd {
     isError = (unsigned (*)(size_t))dlsym(h, "ZSTD_isError");
     getErrorName = (const char* (*)(size_t))dlsym(h, "ZSTD_getErrorName");
     ok = createDStream && freeDStream && initDStream && decompressStream && isError && getErrorName;
+    createCStream = (void* (*)())dlsym(h, "ZSTD_createCStream");
+    freeCStream = (size_t(*)(void*))dlsym(h, "ZSTD_freeCStream");
+    initCStream = (size_t(*)(void*, int))dlsym(h, "ZSTD_initCStream");
+    compressStream = (size_t(*)(void*, ZOut*, ZIn*))dlsym(h, "ZSTD_compressStream");
+    endStream = (size_t(*)(void*, ZOut*))dlsym(h, "ZSTD_endStream");
+    CStreamOutSize = (size_t(*)())dlsym(h, "ZSTD_CStreamOutSize");
+    c_ok = isError && getErrorName && createCStream && freeCStream && initCStream && compressStream && endStream && CStreamOutSize;
   }
 };
+Zstd& zstd_lib() { static Zstd z; return z; }
 
 bool zstd_decode_file(const char* path, std::string& out, std::string& why) {
-  static Zstd z;
+  Zstd& z = zstd_lib();
   if (!z.ok) { why = "libzstd.so.1 not available"; return false; }
   FILE* f = fopen(path, "rb");
   if (!f) { why = std::string("cannot open ") + path; return false; }
@@ -327,6 +345,80 @@ bool zstd_decode_file(const char* path, std::string& out, std::string& why) {
 }
 
 }  // namespace
+
+// ---- the writer's file (alns_file.h): the counterpart of zstd_decode_file ---------------------------------------------------------
+AlnsFile::~AlnsFile() {
+  if (cs_) zstd_lib().freeCStream(cs_);
+  if (f_) fclose(f_);
+  if (!tmp_.empty()) remove(tmp_.c_str());   // (not committed)
+}
+
+bool AlnsFile::open(const char* path, bool zstd, std::string& why, bool& unsupported) {
+  unsupported = false;
+  if (zstd) {
+    Zstd& z = zstd_lib();
+    if (!z.c_ok) { why = "libzstd.so.1 not available"; unsupported = true; return false; }
+    cs_ = z.createCStream();
+    if (!cs_) { why = "zstd: no compression stream"; return false; }
+    const size_t rc = z.initCStream(cs_, 0);   // level 0: the library's default, as the reference's Encoder::new(w, 0)
+    if (z.isError(rc)) { why = std::string("zstd: ") + z.getErrorName(rc); return false; }
+    ob_.resize(std::max<size_t>(z.CStreamOutSize(), 1 << 17));
+  }
+  path_ = path;
+  const std::string tmp = path_ + ".tmp";
+  f_ = fopen(tmp.c_str(), "wb");
+  if (!f_) { why = "cannot create " + tmp; return false; }
+  tmp_ = tmp;
+  return true;
+}
+
+bool AlnsFile::flush_out(size_t n, std::string& why) {
+  if (n && fwrite(ob_.data(), 1, n, f_) != n) { why = "cannot write " + tmp_; return false; }
+  file_bytes += n;
+  return true;
+}
+
+bool AlnsFile::write(const char* p, size_t n, std::string& why) {
+  if (!f_) { why = "the file is not open"; return false; }
+  if (!cs_) {
+    if (n && fwrite(p, 1, n, f_) != n) { why = "cannot write " + tmp_; return false; }
+    file_bytes += n;
+    return true;
+  }
+  Zstd& z = zstd_lib();
+  ZIn in{p, n, 0};
+  while (in.pos < in.size) {
+    ZOut o{ob_.data(), ob_.size(), 0};
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t rc = z.compressStream(cs_, &o, &in);
+    zstd_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (z.isError(rc)) { why = std::string("zstd: ") + z.getErrorName(rc); return false; }
+    if (!flush_out(o.pos, why)) return false;
+  }
+  return true;
+}
+
+bool AlnsFile::commit(std::string& why) {
+  if (!f_) { why = "the file is not open"; return false; }
+  if (cs_) {
+    Zstd& z = zstd_lib();
+    for (;;) {   // the frame's epilogue: until nothing is left to flush
+      ZOut o{ob_.data(), ob_.size(), 0};
+      const auto t0 = std::chrono::steady_clock::now();
+      const size_t left = z.endStream(cs_, &o);
+      zstd_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      if (z.isError(left)) { why = std::string("zstd: ") + z.getErrorName(left); return false; }
+      if (!flush_out(o.pos, why)) return false;
+      if (!left) break;
+    }
+  }
+  const int rc = fclose(f_);
+  f_ = nullptr;
+  if (rc != 0) { why = "cannot write " + tmp_; return false; }
+  if (rename(tmp_.c_str(), path_.c_str()) != 0) { why = "cannot rename " + tmp_ + " to " + path_; return false; }
+  tmp_.clear();
+  return true;
+}
 
 extern "C" {
 

@@ -49,6 +49,11 @@ struct OvlStats {
 
 enum { OVL_OK = 0, OVL_HIP = 1, OVL_UNSUPPORTED = 2 };
 
+// The finder's own exclusive scan of u32 (k_scan_partial / k_scan_top / k_scan_final), for the other device code of the front end (paf_dev.hip's line
+// offsets): out[0 .. n] from in[0 .. n), out[n] = the total; partial: ovl_scan_partials(n) entries of scratch.  Queued on st; nothing is awaited.
+uint32_t ovl_scan_partials(uint32_t n);
+int ovl_scan_u32(const uint32_t* in, uint32_t n, uint32_t* out, uint32_t* partial, hipStream_t st, std::string& err);
+
 // minimizers of the whole store sorted by (rid, pos): hash[i], meta[i] = rid << 32 | pos << 1 | strand (host vectors)
 int ovl_sketch(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vector<uint64_t>& hash, std::vector<uint64_t>& meta,
                std::string& err);

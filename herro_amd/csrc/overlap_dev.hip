@@ -720,6 +720,9 @@ int sketch_dev(const OvlStore& S, const OvlParams& P, hipStream_t st, Bufs& B, S
 
 }  // namespace
 
+uint32_t ovl_scan_partials(uint32_t n) { return nblk(n, SC_TILE) + 1; }
+int ovl_scan_u32(const uint32_t* in, uint32_t n, uint32_t* out, uint32_t* partial, hipStream_t st, std::string& err) { return scan_u32(in, n, out, partial, st, err); }
+
 int ovl_sketch(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vector<uint64_t>& hash, std::vector<uint64_t>& meta,
                std::string& err) {
   Bufs B;

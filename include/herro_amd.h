@@ -407,7 +407,7 @@ const herro_alignment* herro_aligned_dev_alignments(const herro_aligned_dev* a);
 const int32_t* herro_aligned_dev_scores(const herro_aligned_dev* a);               /* INT32_MIN: failed */
 const uint32_t* herro_aligned_dev_n_ops(const herro_aligned_dev* a);               /* per record; 0: failed */
 uint32_t herro_aligned_dev_failed(const herro_aligned_dev* a);
-/* One record's CIGAR text on demand (the only way its ops reach the host): returns its length in bytes — 0 for a failed record — and
+/* One record's CIGAR text on demand (one copy per call; herro_aligned_dev_paf below brings all of them down at once): returns its length in bytes — 0 for a failed record — and
  * writes it, without a terminator, when out != NULL and cap is large enough; < 0: HERRO_E_*. */
 int64_t herro_aligned_dev_cigar(const herro_aligned_dev* a, uint32_t r, char* out, uint64_t cap);
 /* Safe once herro_job_create_aligned has returned: the job owns a copy of its ops. */
@@ -571,6 +571,46 @@ int herro_pairs_from_table_core(herro_ctx* ctx, uint32_t n_pairs, const herro_al
                                 const uint32_t* rec_of_row /* [n_rows] */, herro_pairs** out);
 uint64_t herro_pairs_n_rows(const herro_pairs* pairs);
 uint32_t herro_pairs_occ_cut(const herro_pairs* pairs);                    /* the frequency cut the finder used; 0: a handle over a table */
+
+/* ---- found alignments as PAF / .oec.zst --------------------------------------------------------------------
+ * What `herro inference --write-alns DIR` keeps of a batch (AlnMode::Write, overlaps.rs:248-286; the lines, 349-352), for the alignments this
+ * library found itself: herro_oec_read / herro_paf_parse* read the result back, and so does the reference's --read-alns.  One line per row,
+ *   qname qlen qstart qend +|- tname tlen tstart tend mbases blocklen 255 cg:Z:<cigar>
+ * tab separated, closed by a newline: the nine coordinate fields are the record's herro_aligned_dev_alignments entry (trimmed), decimal;
+ * <cigar> is byte for byte what herro_aligned_dev_cigar returns ('?' for type 3 of a caller's own ops); a record without ops (failed) gives NO
+ * line.  mbases is the sum of the record's M op lengths and blocklen the sum of all its op lengths (64 bits) — NOT minimap2's residue matches
+ * and alignment block length; the reference reads nine fields and the last one (overlaps.rs:135-172) and ignores columns 10 to 12.
+ * names / name_off[n_reads + 1]: the read names as herro_name_index_create takes them, index = read id.  An empty name or one with a tab or a
+ * newline is HERRO_E_INVALID naming the read, checked before anything else.
+ * On a device handle the text is formed on the GPU (k_paf_len, k_paf_write) in chunks that fit HERRO_PAF_SCRATCH_MB of device memory (MiB,
+ * default 1024; the same bytes for every budget) and comes down through two pinned buffers; HERRO_PAF_STATS=1 prints `PAF rows= lines= bytes=
+ * chunks=` on stderr.  On a handle of a device-free context the same lines come from the host formatter: the specification of the kernels.
+ * HERRO_E_INVALID: a null argument, a handle of another context, rec[i] >= the handle's records (names i), an aligned handle that does not
+ * hold exactly 2 P records (pair entries), a bad name, a row whose qid or tid is outside the read store, an unknown flag; HERRO_E_STATE: no
+ * reads set; HERRO_E_UNSUPPORTED: more than 2^31 - 1 rows, a line of 2^32 bytes or more, HERRO_ALNS_OEC without libzstd.so.1.  The file entry
+ * also answers HERRO_E_INVALID when the file cannot be created, written or renamed or the compressor reports an error (a full disk as much as a
+ * bad path): the message begins "herro_pairs_write_alns: cannot create / cannot write / cannot rename / zstd:" and tells them apart.  An error
+ * leaves no handle and no file.  n_rows = 0: an empty text. */
+typedef struct herro_paf_text herro_paf_text;
+/* rows: n_rows record indices of `a` in output order (NULL: row i is record i, n_rows of them) */
+int herro_aligned_dev_paf(herro_ctx* ctx, const herro_aligned_dev* a, uint64_t n_rows, const uint32_t* rec, const char* names,
+                          const uint64_t* name_off /* [n_reads + 1] */, herro_paf_text** out);
+/* the rows of the table in its order (target ascending, query ascending), rec = rec_of_row: exactly the alignments herro_job_create_paired
+ * builds its job from */
+int herro_pairs_paf(herro_ctx* ctx, const herro_pairs* pairs, const herro_aligned_dev* m, const char* names,
+                    const uint64_t* name_off /* [n_reads + 1] */, herro_paf_text** out);
+const char* herro_paf_text_data(const herro_paf_text* text);   /* herro_paf_text_len bytes, no terminator promised */
+uint64_t herro_paf_text_len(const herro_paf_text* text);
+uint64_t herro_paf_text_lines(const herro_paf_text* text);
+void herro_paf_text_free(herro_paf_text* text);
+/* The same lines streamed to a file chunk by chunk (the whole text is never resident): written to path + ".tmp" and renamed.  Without a flag
+ * plain PAF; HERRO_ALNS_OEC: the reference's batch file (overlaps.rs:270-282) — ONE zstd frame at level 0 (through libzstd.so.1, loaded as the
+ * reader loads it) holding "<n_targets>" and a newline, the name of every target of the table and a newline each, then the lines.  The frame is
+ * decodable by any zstd; it is not byte-equal to the reference encoder's.  lines / bytes (NULL: not wanted): lines written, bytes of the file. */
+#define HERRO_ALNS_OEC 1u
+int herro_pairs_write_alns(herro_ctx* ctx, const herro_pairs* pairs, const herro_aligned_dev* m, const char* names,
+                           const uint64_t* name_off /* [n_reads + 1] */, const char* path, uint32_t flags, uint64_t* lines, uint64_t* bytes);
+
 /* Test hook: the census and the pick of occ_frac_ppm alone (occ_frac_ppm 0: HERRO_E_INVALID).  hist: the 65536 bins of min(occurrences,
  * 65535) over the distinct hashes; out = {cut, distinct hashes, hashes above the cut, minimizers in them}. */
 int herro_debug_occ_census(herro_ctx* ctx, const herro_overlap_params* params, uint32_t* hist /* [65536] or NULL */, uint64_t out[4]);
