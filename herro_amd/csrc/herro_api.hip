@@ -1083,6 +1083,12 @@ int herro_load_model(herro_ctx* ctx, const char* path) {
       M.pe_rows = rows;
     } else (void)hipGetLastError();
   }
+  // the activation scratch is sized by the hyper-parameters of the model that was loaded when it was allocated (ensure_scratch: kw * c1, c2, d_model, d_ff per
+  // token): it goes with that model.  Kept, a larger model loaded into the same context wrote its y1 / y2 / ff rows past the ends of the smaller model's
+  // buffers as long as the token count fitted (a kw 1 model, then the default one: three times y1) — tests/test_gpu_rf_models.py, which loads one model
+  // behind another, met it as an illegal memory access.  (The stream is idle here: synchronised above.)
+  free_all(ctx->scratch_allocs);
+  ctx->scratch_cap = 0;
   ctx->M = M;
   ctx->has_model = true;
   ctx->wmax = wmax_seen;
@@ -2187,7 +2193,10 @@ int herro_job_infer(herro_job* job, uint32_t batch_size, int batch_mode) {
         return HERRO_E_REFERENCE_PANIC;
       }
   // the receptive fields k_rows gathered behind featurize are usable if every window got its records (none above RW_SUPCAP rows, the buffer was large enough)
-  bool rf_fused_ok = job->rf_fused && job->rf_total == total_sup && total_sup <= job->rf_fused_cap;
+  // ... and were gathered for the field of the model that is loaded NOW (herro_load_model between featurize and infer: the slots k_rows handed out are not
+  // the ones k_rfq fills when infer gathers again, so rf_base must not point at them)
+  const uint32_t rf_half = 2 * (ctx->M.h.kw / 2);   // the qualities the model will read: rows within 2 * (kw / 2) of an informative row (two stacked convs)
+  bool rf_fused_ok = job->rf_fused && job->rf_fused_half == rf_half && job->rf_total == total_sup && total_sup <= job->rf_fused_cap;
   uint32_t rf_left = 0;   // windows whose slots k_rows reserved but did not fill (above the rows it stages): k_rfq fills exactly those (round 6)
   if (rf_fused_ok)
     for (uint32_t w = 0; w < n && rf_fused_ok; w++) {
@@ -2321,8 +2330,6 @@ int herro_job_infer(herro_job* job, uint32_t batch_size, int batch_mode) {
   rc = ensure_scratch(ctx, max_tok);
   if (rc) return rc;
   if (max_tiles_b && (rc = ensure_sib(ctx, max_tiles_b))) return rc;
-  // the qualities the model will read: rows within 2 * (kw / 2) of an informative row (two stacked convs)
-  const uint32_t rf_half = 2 * (ctx->M.h.kw / 2);
   const bool rf_compact = job->d_rfq && 2 * rf_half + 1 <= 8;   // the model reads the compact receptive fields (tokens + qualities); else the planes
   const bool rfq_there = rf_compact && ((rf_fused_ok && job->rf_fused_half == rf_half) ||   // gathered by k_rows
                                         (job->rfq_spec && job->rfq_spec_half == rf_half && job->rfq_spec_cap >= total_sup));   // ... by k_rfq behind featurize

@@ -28,11 +28,17 @@ namespace herro {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 
-// inference.rs:16-21,153: x = QUAL_SCALE * q - QUAL_OFFSET evaluated in f32, two roundings.
+// inference.rs:16-21,153: x = QUAL_SCALE * q - QUAL_OFFSET in f32 — as ONE fused multiply-add, spelled out.  The reference rounds twice (a product, then a
+// difference); this function used to say so with __fmul_rn / __fsub_rn, but those are a plain `*` and `-` in the HIP headers, and the compiler contracted them into
+// one v_fmac wherever the argument is a run-time value (127 of the 256 byte values one ulp away from the two-rounding result: 126 -> 0.99999994, not 1.0) while it
+// folded a constant argument with two roundings.  So a batch-padding cell that the job's front end supplies by addressing (norm_qual(126u) below) and the same cell
+// read from a caller's dense planes (herro_model_forward) differed in the last bit (tests/test_gpu_rf_models.py).  The fused form is what every kernel has computed
+// on real cells all along, and what the load-time calibration figures were measured with; writing it explicitly makes constants and run-time values agree and
+// takes the result out of the compiler's contraction setting.  (Against the reference's two roundings that is at most 6e-8 on an input in [-1, 1].)
 __device__ __forceinline__ float norm_qual(uint32_t q) {
   const float QS = (float)(2.0 / 93.0);
   const float QO = (float)(2.0 * 33.0 / 93.0 + 1.0);
-  return __fsub_rn(__fmul_rn(QS, (float)q), QO);
+  return __builtin_fmaf(QS, (float)q, -QO);
 }
 
 // gfx950 converts f32 -> bf16 (round to nearest even) in hardware: v_cvt_pk_bf16_f32, one instruction per

@@ -124,16 +124,17 @@ for _i, _ch in enumerate("ACGT*acgt#."):     # inference.rs BASES_MAP: the token
     TOKMAP[ord(_ch)] = _i
 
 
-def records_against_the_oracles_cells(rf, ow, tag):
-    """One window's receptive-field records [n_supported, 31, 16] against the five rows around every informative row of the oracle's window; returns the cells compared."""
+def records_against_the_oracles_cells(rf, ow, tag, half=2):
+    """One window's receptive-field records [n_supported, 31, 16] against the 2 * half + 1 rows around every informative row of the oracle's window (five for the
+    default model); returns the cells compared."""
     enc = TOKMAP[ow.bases]
     L = enc.shape[0]
     tidx = np.flatnonzero(enc[:, 0] != 4)
     r0 = (tidx[ow.sup_pos.astype(np.int64)] + ow.sup_ins).astype(np.int64)
     assert rf.shape[0] == len(r0), tag
     n_cells = 0
-    for d in range(5):
-        r = r0 - 2 + d
+    for d in range(2 * half + 1):
+        r = r0 - half + d
         ok = (r >= 0) & (r < L)
         assert np.array_equal(rf[ok][:, :, d], enc[r[ok]]), (tag, d, "tokens")
         assert np.array_equal(rf[ok][:, :, 8 + d], ow.quals[r[ok]]), (tag, d, "qualities")
