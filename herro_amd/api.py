@@ -26,7 +26,7 @@ EXPORTS = [
     "herro_timing_get", "herro_job_stats", "herro_debug_extract_windows",
     "herro_paf_parse", "herro_oec_read", "herro_paf_n_targets", "herro_paf_target_ids", "herro_paf_aln_off",
     "herro_paf_alignments", "herro_paf_free", "herro_name_index_create", "herro_name_index_free", "herro_paf_parse_indexed",
-    "herro_oec_read_indexed", "herro_paf_parse_view", "herro_debug_host_ctx", "herro_debug_job_array", "herro_debug_tile_plan", "herro_debug_tile_plan_sib",
+    "herro_oec_read_indexed", "herro_paf_parse_view", "herro_debug_host_ctx", "herro_debug_job_array", "herro_debug_tile_plan", "herro_debug_tile_plan_sib", "herro_debug_launch_plan",
     "herro_debug_set_featurize_planes", "herro_debug_set_host_build", "herro_debug_job_dev_built", "herro_debug_job_rf", "herro_debug_job_cwd", "herro_debug_job_set_base_logits", "herro_debug_job_rf_fused", "herro_debug_job_rf_left", "herro_debug_e4m3", "herro_debug_sib_fault", "herro_debug_sib_retries", "herro_debug_base_row_votes", "herro_debug_vote5",
     "herro_pool_create", "herro_pool_destroy", "herro_pool_last_error", "herro_pool_size", "herro_pool_ctx", "herro_pool_set_reads", "herro_pool_load_model",
     "herro_pool_correct", "herro_pool_result", "herro_pool_groups_taken", "herro_pool_skipped", "herro_debug_pool_fake", "herro_job_create_status", "herro_host_register", "herro_host_unregister", "herro_debug_zero_copy_jobs",
@@ -328,6 +328,8 @@ def lib():
         L.herro_debug_tile_plan.argtypes = [vp, u32, i32, u32, vp, vp, vp]
         L.herro_debug_tile_plan_sib.restype = i32
         L.herro_debug_tile_plan_sib.argtypes = [vp, u32, i32, u32, vp, vp, vp, vp]
+        L.herro_debug_launch_plan.restype = C.c_int64
+        L.herro_debug_launch_plan.argtypes = [vp, vp, u32, vp, u32, u32, i32, i32, u32, i32, u32, vp, vp, vp]
         _LIB = L
     return _LIB
 
@@ -394,6 +396,21 @@ def debug_tile_plan_sib(counts, packed: bool = True, qmode: int = 1, n_cu: int =
         raise HerroError(int(rc), "herro_debug_tile_plan_sib")
     nb, n64, n32 = (int(x) for x in n_tiles)
     return nb, n64, n32, order[:len(c)], tok[:nb + n64 + n32 + 1], grp[:nb]
+
+
+def debug_launch_plan(nsup, Lf, tgt_win_off, batch_size: int, batch_mode: int = 0, fused: bool = True, fused_rows: int = 512,
+                      packed: bool = True, qmode: int = 1, n_cu: int = 256):
+    """The launch plan of herro_job_infer for a job of such windows (host only, herro_debug_launch_plan):
+    (number of launches, launch of each window or 0xffffffff, its position in that launch's window stream, its padding length)."""
+    ns, lf = np.ascontiguousarray(nsup, np.uint32), np.ascontiguousarray(Lf, np.uint32)
+    two = np.ascontiguousarray(tgt_win_off, np.uint32)
+    assert len(ns) == len(lf) and len(two) >= 1
+    launch, pos, lmax = (np.zeros(max(len(ns), 1), np.uint32) for _ in range(3))
+    n = lib().herro_debug_launch_plan(ns.ctypes.data, lf.ctypes.data, len(ns), two.ctypes.data, len(two) - 1, batch_size, batch_mode, int(fused), fused_rows,
+                                      int(packed) | (qmode << 1), n_cu, launch.ctypes.data, pos.ctypes.data, lmax.ctypes.data)
+    if n < 0:
+        raise HerroError(int(n), "herro_debug_launch_plan")
+    return int(n), launch[:len(ns)], pos[:len(ns)], lmax[:len(ns)]
 
 
 class Pool:

@@ -24,6 +24,7 @@
 #include "host_cpus.h"
 #include "job_dev.h"
 #include "model_dev.h"
+#include "infer_plan.h"
 #include "windowing.hpp"
 #include "build_dev.h"
 #include "cigar_dev.h"
@@ -55,12 +56,6 @@ T* dev_alloc_copy(const std::vector<T>& v, hipStream_t st, hipError_t& err) {
 }
 }  // namespace
 
-struct BatchPlan {
-  std::vector<uint32_t> wins;  // job window indices
-  uint32_t n_tok = 0, lmax = 0;
-  size_t desc_off = 0;  // byte offset of this batch's descriptor block in d_bdesc
-};
-
 // vector whose resize() leaves trivially-constructible elements uninitialised: the big job arrays are filled by
 // the thread pool right after, so zeroing them (and first-touching their pages) on one thread was pure cost
 template <class T>
@@ -83,8 +78,14 @@ struct harr {
   const T* data() const { return p; }
 };
 
+// What herro_job_featurize gathered of the model's receptive fields ahead of herro_job_infer: at most one of k_rows itself on the lean path (records placed by one
+// atomic per window, JobDev::win_rfbase) and k_rfq right behind the featurize kernels (records at the device prefix of the informative rows), for a receptive field
+// of half width `half`, into room for `cap` informative rows.  rf_resolve decides in herro_job_infer whether the records serve the pass.
+struct RfGather { enum Who : uint8_t { NONE, BY_ROWS, BY_RFQ } who = NONE; uint32_t half = 0; uint64_t cap = 0; };
+
 struct herro_job {
   herro_ctx* ctx = nullptr;
+  // ---- build (herro_job_create*): descriptors, arenas, what was left out
   uint32_t W = 0, n_targets = 0;
   harr<WinDesc> win;
   harr<OwDesc> ow;
@@ -103,55 +104,47 @@ struct herro_job {
   uint64_t reads_gen = 0;
   uint32_t n_skipped_alns = 0, n_failed_targets = 0;  // inputs the library does not support, left out (herro_job_skipped)
   std::string first_skip;
+  uint64_t row_elems = 0;
+  uint64_t alg_read_bytes = 0, alg_op_bytes = 0;
+  // ---- featurize results (herro_job_featurize, job_sync)
   bool featurized = false, synced = false, inferred = false;
-  uint32_t host_max_cols = 0, host_n_cls = 0;   // filled for host-only jobs (herro_debug_host_ctx)
-  uint64_t host_scr_ops = 0, host_fin_bytes = 0;
-  bool quals_full = false;   // the complete quality planes exist (featurize never writes them)
-  bool rf_fused = false;     // ... and k_rows gathered the receptive fields itself (records at win_rfbase, room for rf_fused_cap rows, half width rf_fused_half)
-  uint64_t rf_fused_cap = 0;
-  uint32_t rf_fused_half = 0, rf_total = 0;
-  bool pending = false;         // counted in herro_ctx::n_pending
-  bool rf_fused_used = false;   // herro_job_infer read the records k_rows gathered (herro_debug_job_rf_fused)
-  uint32_t rf_left_windows = 0; // ... of which this many windows were filled by k_rfq behind it (above the rows k_rows stages; herro_debug_job_rf_left)
-  bool sib_stale = false;       // the context's sibling-tile error word was found raised while this job's pass was unchecked: its logits are not to be trusted (sib_retry repeats the pass)
-  bool no_sib = false;          // a sibling tile of this job timed out once: its windows above 64 rows go layer by layer from now on (sib_retry)
-  uint32_t last_batch_size = 0; // arguments of the last herro_job_infer (sib_retry repeats it)
-  int last_batch_mode = 0;
-  std::vector<uint32_t> h_rfbase;
-  std::vector<uint64_t> rf_base;   // per window: first record of its receptive fields in d_rfq (whichever kernel wrote them), valid after herro_job_infer
+  bool pending = false;      // counted in herro_ctx::n_pending
   bool lean = false;         // the last featurize pass ran the lean path (k_rows): votes in position space, no row map
   bool tokens_full = false;  // the token planes + row map exist (planes path, or launch_full_tokens behind a lean pass)
-  // host copies after sync
-  std::vector<uint32_t> h_Lf, h_nsup, h_nkept;
-  std::vector<uint64_t> sup_off;  // [n_win+1] prefix of nsup
-  float* d_info = nullptr;   // inside a_logits
-  float* d_base = nullptr;
-  uint8_t* d_rfq = nullptr;  // inside a_logits: qualities of the receptive fields, compact (BatchDev::rf_q)
-  Arena a_logits{}, a_bdesc{}, a_supoff{};
-  std::vector<float> h_info, h_base;
-  bool logits_on_host = false;
-  std::vector<BatchPlan> batches;
-  void* d_bdesc = nullptr;
-  uint64_t bdesc_cap = 0;
-  std::vector<unsigned char> blob;   // host image of d_bdesc (kept alive: its upload is asynchronous)
-  hipEvent_t ev_blob = nullptr;      // upload of blob finished
-  uint64_t* d_supoff = nullptr;
-  const uint64_t* d_supoff_blob = nullptr;  // sup_off inside d_bdesc (valid once infer has run)
-  uint32_t* d_counts = nullptr;      // [3][n_win]: L', informative rows, kept overlaps (one D2H per job)
+  bool quals_full = false;   // the complete quality planes exist (featurize never writes them)
+  uint32_t* d_counts = nullptr;      // [4][n_win] + 1: L', informative rows, kept overlaps, k_rows' first record (win_rfbase), then the records it handed out in all (one D2H per job)
   uint32_t* h_counts = nullptr;      // pinned
   hipEvent_t ev_counts = nullptr;    // featurize + the copy of the counts finished
-  uint64_t logit_cap = 0;
-  // herro_job_featurize gathers the receptive-field qualities right behind its kernels, in front of the host's count of the informative
-  // rows (device prefix, buffer sized by an estimate): the host then plans the batches while k_rfq runs, instead of the GPU idling
-  bool rfq_spec = false;            // ... done for this pass, with rf_half = rfq_spec_half and room for rfq_spec_cap rows
-  uint32_t rfq_spec_half = 0;
-  uint64_t rfq_spec_cap = 0;
-  Arena a_supoff_dev{};             // u64[n_win + 1] written by k_supoff
+  std::vector<uint32_t> h_Lf, h_nsup, h_nkept;   // host copies after sync
+  std::vector<uint64_t> sup_off;     // [n_win+1] prefix of nsup
+  // ---- gather of the receptive fields
+  RfGather gather;                   // what featurize gathered early
+  std::vector<uint32_t> h_rfbase;    // per window: first record k_rows reserved (bit 31: left to k_rfq, above the rows k_rows stages; 0xffffffff: none, the buffer was full)
+  uint32_t rf_total = 0;             // records k_rows handed out, in informative rows
+  Arena a_supoff_dev{};              // u64[n_win + 1] written by k_supoff for the early k_rfq
+  bool rf_fused_used = false;        // herro_job_infer read the records k_rows gathered (herro_debug_job_rf_fused)
+  uint32_t rf_left_windows = 0;      // ... of which this many windows were filled by k_rfq behind it (herro_debug_job_rf_left)
+  std::vector<uint64_t> rf_base;     // per window: first record of its receptive fields in d_rfq (whichever kernel wrote them), valid after herro_job_infer
+  // ---- inference (herro_job_infer, the fetch of the logits)
+  uint64_t logit_cap = 0;    // informative rows a_logits has room for
+  Arena a_logits{};
+  float *d_info = nullptr, *d_base = nullptr;   // inside a_logits
+  uint8_t* d_rfq = nullptr;  // inside a_logits: the receptive fields, compact (BatchDev::rf_q)
+  std::vector<float> h_info, h_base;
+  bool logits_on_host = false;
+  Arena a_bdesc{};                   // device: the descriptor image of the pass (infer_plan.h: build_launch) + sup_off
+  std::vector<unsigned char> blob;   // its host image (kept alive: its upload is asynchronous)
+  hipEvent_t ev_blob = nullptr;      // upload of blob finished
+  bool sib_stale = false;       // the context's sibling-tile error word was found raised while this job's pass was unchecked: its logits are not to be trusted (sib_retry repeats the pass)
+  bool no_sib = false;          // a sibling tile of this job timed out once: its windows above 64 rows go layer by layer from now on (sib_retry)
+  uint32_t last_batch_size = 0; int last_batch_mode = 0;   // arguments of the last herro_job_infer (sib_retry repeats it)
+  // ---- consensus
+  Arena a_supoff{};
+  uint64_t* d_supoff = nullptr;
+  const uint64_t* d_supoff_blob = nullptr;  // sup_off inside a_bdesc (valid once infer has run)
   bool consensus_done = false, consensus_on_host = false;
   uint32_t* h_cons_len = nullptr;   // pinned (inside the host arena): landing zone of the corrected bases
   uint8_t* h_cons_seq = nullptr;
-  uint64_t row_elems = 0;
-  uint64_t alg_read_bytes = 0, alg_op_bytes = 0;
 };
 
 static int job_sync(herro_job* job);
@@ -220,192 +213,7 @@ struct ArenaReturn {
   }
 };
 
-// Tiles of whole windows for the fused transformer stack: consecutive windows packed greedily into at
-// most `cap` tokens.  Returns the first token of each tile (+ end) for windows [w0, w1) of the token stream.  Callers pass
-// windows of <= FUSED_MAX_TOK informative rows only (larger windows run layer by layer, see split_launch).
-static constexpr uint32_t FUSED_MAX_TOK = 64;
-static constexpr uint32_t FUSED_HALF_TOK = 32;   // tile of k_layers_p<., 2> (the short last round of a launch)
-static constexpr uint32_t FUSED_MAX_SIB = 8;     // sibling tiles of one window in the f16 stack (k_layers_p<., 4, true>): windows of up to 512 informative rows stay fused
-static std::vector<uint32_t> token_tiles(const std::vector<uint32_t>& tok_off, size_t w0 = 0, size_t w1 = ~size_t(0), uint32_t cap = FUSED_MAX_TOK) {
-  w1 = std::min(w1, tok_off.size() - 1);
-  if (w0 >= w1) return std::vector<uint32_t>();
-  std::vector<uint32_t> t(1, tok_off[w0]);
-  for (size_t w = w0; w < w1; w++) {
-    if (tok_off[w + 1] - t.back() > cap) t.push_back(tok_off[w]);
-  }
-  if (tok_off[w1] > t.back()) t.push_back(tok_off[w1]);
-  return t.size() > 1 ? t : std::vector<uint32_t>();
-}
-
-// Order in which the windows of a launch enter the token stream so that token_tiles' consecutive packing comes out as
-// best-fit-decreasing bins: every tile of the fused stack costs the same whatever it holds (the MFMAs run over all its token
-// slots), so the launch time is the NUMBER of tiles.  A tile is opened with the largest window left and filled with the
-// largest window that still fits, repeatedly; the window that opens the next tile is the largest one left, which did not fit
-// (or it would have been taken), so the greedy split of token_tiles falls exactly on these bins.  cnt[i] in 1..cap; the indices
-// appended to `order` are those of `idx` (all windows when idx is null).
-// At the bench workload (informative rows per window 4..30, mean 15.2): 999 tiles of 64 instead of 1098 for 4096 windows
-// (ideal 975), which is 4 rounds of 256 compute units instead of 5.
-static void tile_pack_bins(const std::vector<uint32_t>& cnt, std::vector<std::vector<uint32_t>>& by, size_t left, uint32_t cap, std::vector<uint32_t>& order) {
-  uint32_t top = cap;                  // no window above `top` is left
-  while (top && by[top].empty()) top--;
-  while (left && top) {
-    uint32_t room = cap, s = top;
-    while (room) {
-      s = std::min(s, room);
-      while (s && by[s].empty()) s--;
-      if (!s) break;
-      order.push_back(by[s].back());
-      by[s].pop_back();
-      room -= s;
-      left--;
-    }
-    while (top && by[top].empty()) top--;
-  }
-}
-static std::vector<uint32_t> tile_pack_order(const std::vector<uint32_t>& cnt) {
-  std::vector<std::vector<uint32_t>> by(FUSED_MAX_TOK + 1);
-  for (size_t i = cnt.size(); i-- > 0;) by[std::min(cnt[i], FUSED_MAX_TOK)].push_back((uint32_t)i);  // pop_back: ascending index
-  std::vector<uint32_t> order;
-  order.reserve(cnt.size());
-  for (uint32_t i : by[0]) order.push_back(i);   // (not produced by the planner: windows without informative rows are skipped)
-  tile_pack_bins(cnt, by, cnt.size() - by[0].size(), FUSED_MAX_TOK, order);
-  return order;
-}
-
-// The token stream of one fused launch: `order[k]` = index (into cnt) of its k-th window, `tiles` the 64-token tiles at its
-// head (first tokens + end), `tiles_q` the 32-token tiles behind them (k_layers_p<., 2>; empty when qmode = 0).
-// A launch of the fused stack runs in rounds of one 64-token tile per compute unit; a 32-token tile costs about half a round
-// (half the MFMAs and LDS traffic for the same weight stream).
-// qmode 1 (default with the f16 stack): when the LAST round would fill at most half of the compute units, the windows of its
-// tiles go into 32-token tiles instead, one per compute unit (2560 windows of the bench: 625 tiles = 2 rounds + 113 -> 2 rounds
-// + 226 half tiles).  qmode 2 (A/B): every window of <= 32 rows goes into 32-token tiles; a window of 33..64 opens a 64-token
-// tile and takes the best-fitting small windows along.  Without `pack` the windows keep their batch order inside each class.
-// Windows above 64 rows (the caller admits them up to 64 * FUSED_MAX_SIB, f16 stack only) come FIRST in the stream, each one alone
-// on ceil(rows / 64) consecutive tiles (`tiles_b`; grp[t] = first tile of the window's group | tiles in it << 20 | its tokens in the last tile << 24);
-// small windows may share that last tile.
-struct TilePlan { std::vector<uint32_t> order, tiles, tiles_q, tiles_b, grp; };
-static TilePlan plan_tiles_small(const std::vector<uint32_t>& cnt, bool pack, int qmode, uint32_t n_cu, uint32_t n_busy = 0);
-static TilePlan plan_tiles(const std::vector<uint32_t>& cnt, bool pack, int qmode, uint32_t n_cu) {
-  std::vector<uint32_t> big, small;
-  for (size_t i = 0; i < cnt.size(); i++) (cnt[i] > FUSED_MAX_TOK ? big : small).push_back((uint32_t)i);
-  if (big.empty()) return plan_tiles_small(cnt, pack, qmode, n_cu);
-  // the head of the stream: every large window, its last (partial) tile filled with the best-fitting small windows (pack only) — the
-  // sibling code masks a tile's own block by window id like any tile, and the other siblings see only its first `nbig` tokens
-  std::vector<std::vector<uint32_t>> by(FUSED_MAX_TOK + 1);
-  if (pack) for (size_t k = small.size(); k-- > 0;) by[cnt[small[k]]].push_back(small[k]);   // pop_back: ascending index
-  std::vector<uint32_t> head, tiles_b(1, 0), grp;
-  std::vector<char> taken(cnt.size(), 0);
-  uint32_t tok = 0;
-  for (uint32_t i : big) {
-    const uint32_t k = (cnt[i] + FUSED_MAX_TOK - 1) / FUSED_MAX_TOK, g0 = (uint32_t)grp.size(), last = cnt[i] - (k - 1) * FUSED_MAX_TOK;
-    head.push_back(i);
-    for (uint32_t j = 0; j + 1 < k; j++) tiles_b.push_back(tok + (j + 1) * FUSED_MAX_TOK);
-    tok += cnt[i];
-    uint32_t room = FUSED_MAX_TOK - last, f = room;
-    while (room) {
-      f = std::min(f, room);
-      while (f && by[f].empty()) f--;
-      if (!f) break;
-      const uint32_t w = by[f].back();
-      by[f].pop_back();
-      head.push_back(w);
-      taken[w] = 1;
-      tok += f;
-      room -= f;
-    }
-    tiles_b.push_back(tok);
-    for (uint32_t j = 0; j < k; j++) grp.push_back(g0 | (k << 20) | (last << 24));   // first tile | tiles (<= 15) | the window's tokens in its last tile
-  }
-  std::vector<uint32_t> rest, rest_cnt;
-  for (uint32_t i : small) if (!taken[i]) { rest.push_back(i); rest_cnt.push_back(cnt[i]); }
-  TilePlan P = plan_tiles_small(rest_cnt, pack, qmode, n_cu, (uint32_t)grp.size());   // the sibling tiles share the grid of the 64-token tiles: they count in its rounds
-  for (uint32_t& o : P.order) o = rest[o];
-  for (uint32_t& t : P.tiles) t += tok;
-  for (uint32_t& t : P.tiles_q) t += tok;
-  P.order.insert(P.order.begin(), head.begin(), head.end());
-  P.tiles_b.swap(tiles_b);
-  P.grp.swap(grp);
-  return P;
-}
-static TilePlan plan_tiles_small(const std::vector<uint32_t>& cnt, bool pack, int qmode, uint32_t n_cu, uint32_t n_busy) {
-  TilePlan P;
-  const size_t n = cnt.size();
-  std::vector<uint32_t> tok_off(1, 0);
-  auto finish = [&](size_t n_head) {   // n_head windows in 64-token tiles
-    tok_off.assign(1, 0);
-    for (size_t k = 0; k < n; k++) tok_off.push_back(tok_off.back() + cnt[P.order[k]]);
-    P.tiles = token_tiles(tok_off, 0, n_head, FUSED_MAX_TOK);
-    P.tiles_q.clear();
-    if (n_head < n) P.tiles_q = token_tiles(tok_off, n_head, n, FUSED_HALF_TOK);
-  };
-  if (qmode != 2) {
-    if (pack) P.order = tile_pack_order(cnt);
-    else { P.order.resize(n); for (size_t i = 0; i < n; i++) P.order[i] = (uint32_t)i; }
-    finish(n);
-    const size_t n64 = P.tiles.empty() ? 0 : P.tiles.size() - 1;
-    const size_t rr = n_cu ? (n64 + n_busy) % n_cu : 0;   // tiles of the last round (n_busy: sibling tiles at the head of the same grid)
-    if (qmode == 0 || rr == 0 || 2 * rr > n_cu) return P;
-    const size_t r = std::min(rr, n64);
-    if (r == 0) return P;
-    // windows of the last r tiles: the small ones leave for 32-token tiles, a large one stays (in front of them)
-    const uint32_t cut_tok = P.tiles[n64 - r];
-    size_t k0 = 0;
-    while (tok_off[k0] < cut_tok) k0++;
-    std::vector<uint32_t> keep, tail;
-    for (size_t k = k0; k < n; k++) (cnt[P.order[k]] > FUSED_HALF_TOK ? keep : tail).push_back(P.order[k]);
-    if (tail.empty()) return P;
-    if (pack) {  // best-fit-decreasing into bins of 32
-      std::vector<std::vector<uint32_t>> by(FUSED_HALF_TOK + 1);
-      for (size_t i = tail.size(); i-- > 0;) by[cnt[tail[i]]].push_back(tail[i]);
-      std::vector<uint32_t> t2;
-      for (uint32_t i : by[0]) t2.push_back(i);
-      tile_pack_bins(cnt, by, tail.size() - by[0].size(), FUSED_HALF_TOK, t2);
-      tail.swap(t2);
-    }
-    P.order.resize(k0);
-    P.order.insert(P.order.end(), keep.begin(), keep.end());
-    const size_t n_head = P.order.size();
-    P.order.insert(P.order.end(), tail.begin(), tail.end());
-    finish(n_head);
-    return P;
-  }
-  P.order.reserve(n);
-  if (!pack) {
-    for (size_t i = 0; i < n; i++) if (cnt[i] > FUSED_HALF_TOK) P.order.push_back((uint32_t)i);
-    const size_t n_head = P.order.size();
-    for (size_t i = 0; i < n; i++) if (cnt[i] <= FUSED_HALF_TOK) P.order.push_back((uint32_t)i);
-    finish(n_head);
-    return P;
-  }
-  std::vector<std::vector<uint32_t>> by(FUSED_MAX_TOK + 1);
-  for (size_t i = n; i-- > 0;) by[std::min(cnt[i], FUSED_MAX_TOK)].push_back((uint32_t)i);
-  size_t small_left = 0;
-  for (uint32_t s = 0; s <= FUSED_HALF_TOK; s++) small_left += by[s].size();
-  for (uint32_t s = FUSED_MAX_TOK; s > FUSED_HALF_TOK; s--)
-    while (!by[s].empty()) {   // a 64-token tile: one large window + the small ones that fit best
-      P.order.push_back(by[s].back());
-      by[s].pop_back();
-      uint32_t room = FUSED_MAX_TOK - s, f = room;
-      while (room) {
-        f = std::min(f, room);
-        while (f && by[f].empty()) f--;
-        if (!f) break;
-        P.order.push_back(by[f].back());
-        by[f].pop_back();
-        room -= f;
-        small_left--;
-      }
-    }
-  const size_t n_head = P.order.size();
-  for (uint32_t i : by[0]) { P.order.push_back(i); small_left--; }
-  tile_pack_bins(cnt, by, small_left, FUSED_HALF_TOK, P.order);
-  finish(n_head);
-  return P;
-}
-
-// One model launch over a set of windows.  Fused stacks (precision 1, 4, 5) take tiles of whole windows of at most
-// 64 informative rows; a window above that does not make the launch group fall off the fused path any more: the
-// group is split into its small windows (tiles) and its large ones (layer-by-layer bf16x3 kernels, precision 3).
+static constexpr uint32_t FUSED_MAX_SIB = 8;     // sibling tiles of one window in the f16 stack (k_layers_p<., 4, true>): windows of up to 512 informative rows stay fused (the plan in infer_plan.h never reads it; tests/capacity_cases.py reads it here)
 // Most informative rows of a window that stays on the fused stack: 64 (one tile), or 64 * FUSED_MAX_SIB with the f16 stack, which
 // spreads a larger window over sibling tiles (HERRO_FUSED_BIG=0: such windows go layer by layer as before, for A/B).
 static uint32_t fused_tok_cap(const herro_ctx* ctx) {
@@ -1932,7 +1740,6 @@ static herro_job* job_create_from(herro_ctx* ctx, uint32_t n_targets, const uint
 
   auto t_merged = tnow();
   if (ctx->host_only) {  // test hook: the host half (descriptors) only
-    job->host_max_cols = max_cols; job->host_n_cls = n_cls; job->host_scr_ops = scr_ops; job->host_fin_bytes = fin_bytes;
     ctx->live_jobs++;
     if (prof) {
       auto ms = [](auto a_, auto b_) { return std::chrono::duration<double, std::milli>(b_ - a_).count(); };
@@ -2092,13 +1899,13 @@ int herro_job_featurize(herro_job* job) {
   static const int fuse_rf = ab_env("HERRO_RF_FUSED", -1) < 0 ? -1 : (ab_env("HERRO_RF_FUSED", -1) != 0 ? 1 : 0);
   const bool pipelined = ctx->n_pending.load() - (job->pending ? 1 : 0) > 0;
   if (!job->pending) { job->pending = true; ctx->n_pending++; }
-  job->rf_fused = false;
+  job->gather = RfGather{};   // nothing is gathered for this pass yet
   job->J.rf = nullptr;
   if (job->lean && (fuse_rf == 1 || (fuse_rf < 0 && pipelined)) && ctx->has_model && rf_half == 2) {
     const uint64_t want = job->logit_cap > 1 ? job->logit_cap : (uint64_t)job->J.n_win * 24;   // ~15 informative rows per window at the bench workload
     if (ensure_logits(job, want) == HERRO_OK) {
       job->J.rf = job->d_rfq; job->J.rf_cap = std::min<uint64_t>(job->logit_cap, 0xfffffff0ull / HERRO_ROWS); job->J.rf_half = rf_half;
-      job->rf_fused = true; job->rf_fused_cap = job->J.rf_cap; job->rf_fused_half = rf_half;
+      job->gather = RfGather{RfGather::BY_ROWS, rf_half, job->J.rf_cap};
       HIP_TRY(ctx, hipMemsetAsync(job->J.rf_alloc, 0, 4, ctx->stream));
     }
   }
@@ -2113,9 +1920,8 @@ int herro_job_featurize(herro_job* job) {
   // prefix — not the batch plan): by the time the host has the counts and has planned the batches, the GPU is through this
   // kernel instead of having waited for the plan.  The buffer is sized by the job's previous pass or by an estimate; if the
   // count turns out larger, herro_job_infer gathers again.  HERRO_RFQ_EARLY=0: gather in herro_job_infer (A/B).
-  job->rfq_spec = false;
   static const bool early = ab_env("HERRO_RFQ_EARLY", 1) != 0;
-  if (early && !job->rf_fused && ctx->has_model && 2 * rf_half + 1 <= 8) {
+  if (early && job->gather.who == RfGather::NONE && ctx->has_model && 2 * rf_half + 1 <= 8) {
     const uint32_t n = job->J.n_win;
     if (!job->a_supoff_dev.p) job->a_supoff_dev = small_acquire(ctx, ((uint64_t)n + 1) * 8);
     const uint64_t want = job->logit_cap > 1 ? job->logit_cap : (uint64_t)n * 24;   // ~15 informative rows per window at the bench workload
@@ -2123,7 +1929,7 @@ int herro_job_featurize(herro_job* job) {
       launch_supoff(job->J, (uint64_t*)job->a_supoff_dev.p, ctx->stream);
       launch_rf_quals(job->J, rf_half, (const uint64_t*)job->a_supoff_dev.p, job->d_rfq, job->logit_cap, job->lean, ctx->stream, &ctx->timer);
       HIP_TRY(ctx, hipGetLastError());
-      job->rfq_spec = true; job->rfq_spec_half = rf_half; job->rfq_spec_cap = job->logit_cap;
+      job->gather = RfGather{RfGather::BY_RFQ, rf_half, job->logit_cap};
     }
   }
   return HERRO_OK;
@@ -2165,9 +1971,54 @@ static int ensure_logits(herro_job* job, uint64_t rows) {
   job->d_info = (float*)job->a_logits.p;
   job->d_base = (float*)((unsigned char*)job->a_logits.p + o_base);
   job->d_rfq = (uint8_t*)job->a_logits.p + o_rfq;
-  job->rfq_spec = false;   // whatever was gathered lived in the old block
-  job->rf_fused = false;
+  job->gather = RfGather{};   // whatever was gathered lived in the old block
   return HERRO_OK;
+}
+
+// Which gather serves this pass (model with receptive-field half width rf_half, total_sup informative rows), from what herro_job_featurize left in job->gather.
+// compact: the model reads the compact records (tokens + qualities) in d_rfq, else the planes; todo: what herro_job_infer still has to gather — every window, the
+// windows k_rows reserved but left to k_rfq, nothing.  Fills job->rf_base, rf_fused_used and rf_left_windows.
+struct RfPlan { bool compact; enum { ALL, LEFT, NOTHING } todo; };
+static RfPlan rf_resolve(herro_job* job, uint32_t rf_half, uint64_t total_sup) {
+  const uint32_t n = job->J.n_win;
+  const RfGather& g = job->gather;
+  RfPlan r{job->d_rfq && 2 * rf_half + 1 <= 8, RfPlan::ALL};
+  // the records k_rows placed are usable if they were gathered for the field of the model that is loaded NOW (herro_load_model between featurize and infer:
+  // the slots k_rows handed out are not the ones k_rfq fills when infer gathers again, so rf_base must not point at them), the buffer had room and every
+  // window got its slots (k_rows gathers for a half width of 2 only, which is compact)
+  bool by_rows = g.who == RfGather::BY_ROWS && g.half == rf_half && job->rf_total == total_sup && total_sup <= g.cap;
+  uint32_t left = 0;   // windows whose slots k_rows reserved but did not fill (above the rows it stages): k_rfq fills exactly those
+  for (uint32_t w = 0; w < n && by_rows; w++) {
+    if (job->h_nsup[w] == 0) continue;
+    by_rows = job->h_rfbase[w] != 0xffffffffu;
+    left += by_rows && (job->h_rfbase[w] & 0x80000000u) ? 1u : 0u;
+  }
+  const bool by_rfq = r.compact && g.who == RfGather::BY_RFQ && g.half == rf_half && g.cap >= total_sup;   // k_rfq behind featurize covers the pass
+  job->rf_fused_used = by_rows;
+  job->rf_left_windows = by_rows ? left : 0;
+  job->rf_base.resize(n);
+  for (uint32_t w = 0; w < n; w++) job->rf_base[w] = by_rows ? (uint64_t)(job->h_rfbase[w] & 0x7fffffffu) : job->sup_off[w];
+  if (by_rows) r.todo = left ? RfPlan::LEFT : RfPlan::NOTHING;
+  else if (by_rfq || (!r.compact && job->quals_full)) r.todo = RfPlan::NOTHING;   // (the planes path reads the complete quality planes once they exist)
+  return r;
+}
+
+// The arrays of one launch inside the descriptor image at d_image (build_launch); the caller adds the buffers the launch reads and writes.
+static BatchDev batch_dev(const void* d_image, const LaunchOffs& o) {
+  const unsigned char* base = (const unsigned char*)d_image;
+  auto u32 = [&](size_t off) { return (const uint32_t*)(base + off); };
+  auto u64 = [&](size_t off) { return off == NO_ARRAY ? nullptr : (const uint64_t*)(base + off); };
+  BatchDev B{};
+  B.n_win = o.n_win; B.n_tok = o.n_tok; B.max_win_tok = o.max_win_tok;
+  B.plane_off = u64(o.plane_off); B.plane_ld = u32(o.plane_ld); B.len = u32(o.len); B.lmax = u32(o.lmax); B.tok_off = u32(o.tok_off);
+  B.sup_off = u64(o.sup_off); B.out_off = u64(o.out_off); B.rf_base = u64(o.rf_base);
+  B.n_tiles = o.n_tiles; B.tile_tok0 = u32(o.tiles);
+  B.n_tiles_q = o.n_tiles_q; B.tile_tok0_q = u32(o.tiles_q);
+  B.n_tiles_b = o.n_tiles_b; B.tile_tok0_b = u32(o.tiles_b); B.tile_grp = u32(o.grp);
+  return B;
+}
+static LaunchCfg launch_cfg(const herro_ctx* ctx, uint32_t fused_rows, bool with_rf_base) {
+  return LaunchCfg{ctx->precision == 1 || ctx->precision >= 4, fused_rows, ctx->tile_packing, ctx->precision >= 4 ? model_h_half_tiles(ctx->M) : 0, ctx->n_cu, with_rf_base};
 }
 
 extern "C" {
@@ -2192,176 +2043,54 @@ int herro_job_infer(herro_job* job, uint32_t batch_size, int batch_mode) {
         ctx->err = "a window of " + std::to_string(job->h_Lf[w]) + " rows exceeds the model's learned position table (" + std::to_string(ctx->M.pe_learned_rows) + " rows): the archive would raise an index error";
         return HERRO_E_REFERENCE_PANIC;
       }
-  // the receptive fields k_rows gathered behind featurize are usable if every window got its records (none above RW_SUPCAP rows, the buffer was large enough)
-  // ... and were gathered for the field of the model that is loaded NOW (herro_load_model between featurize and infer: the slots k_rows handed out are not
-  // the ones k_rfq fills when infer gathers again, so rf_base must not point at them)
   const uint32_t rf_half = 2 * (ctx->M.h.kw / 2);   // the qualities the model will read: rows within 2 * (kw / 2) of an informative row (two stacked convs)
-  bool rf_fused_ok = job->rf_fused && job->rf_fused_half == rf_half && job->rf_total == total_sup && total_sup <= job->rf_fused_cap;
-  uint32_t rf_left = 0;   // windows whose slots k_rows reserved but did not fill (above the rows it stages): k_rfq fills exactly those (round 6)
-  if (rf_fused_ok)
-    for (uint32_t w = 0; w < n && rf_fused_ok; w++) {
-      rf_fused_ok = job->h_nsup[w] == 0 || job->h_rfbase[w] != 0xffffffffu;
-      rf_left += job->h_nsup[w] && job->h_rfbase[w] != 0xffffffffu && (job->h_rfbase[w] & 0x80000000u) ? 1u : 0u;
-    }
-  job->rf_fused_used = rf_fused_ok;
-  job->rf_left_windows = rf_fused_ok ? rf_left : 0;
-  job->rf_base.assign(n, 0);
-  for (uint32_t w = 0; w < n; w++) job->rf_base[w] = rf_fused_ok ? (uint64_t)(job->h_rfbase[w] & 0x7fffffffu) : job->sup_off[w];
-  // ---- plan batches (prepare_examples, inference.rs:241-250; flush rule features.rs:884-893)
-  job->batches.clear();
-  auto flush = [&](std::vector<uint32_t>& cur) {
-    if (cur.empty()) return;
-    BatchPlan bp;
-    bp.wins = cur;
-    for (uint32_t w : cur) { bp.n_tok += job->h_nsup[w]; bp.lmax = std::max(bp.lmax, job->h_Lf[w]); }
-    job->batches.push_back(std::move(bp));
-    cur.clear();
-  };
-  std::vector<uint32_t> cur;
-  if (batch_mode == 0) {
-    for (uint32_t t = 0; t < job->n_targets; t++) {
-      uint32_t seen = 0;
-      for (uint32_t w = job->tgt_win_off[t]; w < job->tgt_win_off[t + 1]; w++) {
-        if (job->h_nsup[w] > 0) cur.push_back(w);
-        if (++seen == batch_size) { flush(cur); seen = 0; }  // InferenceOutput::update flush
-      }
-      flush(cur);  // InferenceOutput::emit at end of read
-    }
-  } else {
-    for (uint32_t w = 0; w < n; w++) {
-      if (job->h_nsup[w] == 0) continue;
-      cur.push_back(w);
-      if (cur.size() == batch_size) flush(cur);
-    }
-    flush(cur);
-  }
-  // ---- all batches of the job go through ONE set of launches: a window's batch only matters
-  // through the padding length lmax (the longest window of its batch), which travels per window.
-  // Launch groups are capped at TOK_CAP tokens to bound the activation scratch.
-  const uint32_t TOK_CAP = 1u << 16;
-  struct Group { size_t b0, b1; uint32_t n_win, n_tok; };
-  std::vector<Group> groups;
-  for (size_t bi = 0; bi < job->batches.size();) {
-    Group g{bi, bi, 0, 0};
-    while (g.b1 < job->batches.size() && (g.b1 == g.b0 || g.n_tok + job->batches[g.b1].n_tok <= TOK_CAP)) {
-      g.n_win += (uint32_t)job->batches[g.b1].wins.size();
-      g.n_tok += job->batches[g.b1].n_tok;
-      g.b1++;
-    }
-    groups.push_back(g);
-    bi = g.b1;
-  }
-  if (job->d_bdesc) HIP_TRY(ctx, hipEventSynchronize(job->ev_blob));  // a previous upload of the blob is over
+  const RfPlan rf = rf_resolve(job, rf_half, total_sup);
+  // ---- the plan (infer_plan.h): batches, launch groups, per group the descriptor arrays of its launches
+  const std::vector<BatchPlan> batches = plan_batches(job->h_nsup, job->h_Lf, job->tgt_win_off, batch_size, batch_mode);
+  const std::vector<LaunchGroup> groups = group_batches(batches);
+  if (job->a_bdesc.p) HIP_TRY(ctx, hipEventSynchronize(job->ev_blob));  // a previous upload of the blob is over
   std::vector<unsigned char>& blob = job->blob;
   blob.clear();
-  auto put = [&](const void* p, size_t bytes) {
-    const size_t o = (blob.size() + 15) & ~size_t(15);
-    blob.resize(o + bytes);
-    std::memcpy(blob.data() + o, p, bytes);
-    return o;
-  };
-  struct Offs { size_t plane_off, plane_ld, len, lmax, tok_off, sup_off, out_off, rf_base, tiles, tiles_q, tiles_b, grp; uint32_t n_tiles, n_tiles_q, n_tiles_b, n_win, n_tok, max_win_tok; bool tiled; };
-  std::vector<Offs> offs;
-  uint32_t max_tok = 0, max_tiles_b = 0;
-  const bool fused_mode = ctx->precision == 1 || ctx->precision >= 4;
-  const uint32_t tok_cap = job->no_sib ? FUSED_MAX_TOK : fused_tok_cap(ctx);   // most informative rows of a window on the fused stack
-  const int qmode = ctx->precision >= 4 ? model_h_half_tiles(ctx->M) : 0;
-  for (auto& g : groups) {
-    for (int part = 0; part < 2; part++) {  // 0: windows that fit a fused tile (all of them in the unfused modes), 1: the rest
-      std::vector<uint64_t> plane_off, sup_o, out_o, rfb;
-      std::vector<uint32_t> ld, len, lmax, tok_off(1, 0), sel, sel_lmax, sel_cnt;
-      for (size_t bi = g.b0; bi < g.b1; bi++) {
-        const BatchPlan& bp = job->batches[bi];
-        for (uint32_t w : bp.wins) {
-          const bool large = fused_mode && job->h_nsup[w] > tok_cap;
-          if ((int)large != part) continue;
-          sel.push_back(w);
-          sel_lmax.push_back(bp.lmax);   // the padding length is that of the window's BATCH, whichever launch it runs in
-          sel_cnt.push_back(job->h_nsup[w]);
-        }
-      }
-      const size_t B = sel.size();
-      if (B == 0) continue;
-      // a window's place in the launch is free (its planes, padding length and output slots travel with it): the fused
-      // stacks take them in the order that packs the fewest 64-token tiles
-      TilePlan plan;
-      if (fused_mode && part == 0) plan = plan_tiles(sel_cnt, ctx->tile_packing, qmode, ctx->n_cu);
-      const std::vector<uint32_t>& order = plan.order;
-      plane_off.reserve(B); sup_o.reserve(B); out_o.reserve(B); ld.reserve(B); len.reserve(B); lmax.reserve(B); tok_off.reserve(B + 1);
-      for (size_t k = 0; k < B; k++) {
-        const size_t i = order.empty() ? k : order[k];
-        const uint32_t w = sel[i];
+  const LaunchCfg cfg = launch_cfg(ctx, job->no_sib ? FUSED_MAX_TOK : fused_tok_cap(ctx), true);
+  std::vector<LaunchOffs> offs;
+  std::vector<PlanWin> wins;
+  for (const LaunchGroup& g : groups) {
+    wins.clear(); wins.reserve(g.n_win);   // (exactly: a vector grown by doubling would cross the allocator's mmap threshold at the bench's job size, on every pass)
+    for (size_t bi = g.b0; bi < g.b1; bi++)
+      for (uint32_t w : batches[bi].wins) {
         const WinDesc& wd = job->win[w];
-        plane_off.push_back(wd.fin_off); ld.push_back(wd.lub); len.push_back(job->h_Lf[w]);
-        lmax.push_back(sel_lmax[i]);
-        tok_off.push_back(tok_off.back() + job->h_nsup[w]);
-        sup_o.push_back(wd.row_off); out_o.push_back(job->sup_off[w]); rfb.push_back(job->rf_base[w]);
+        wins.push_back(PlanWin{job->h_nsup[w], wd.lub, job->h_Lf[w], batches[bi].lmax, wd.fin_off, wd.row_off, job->sup_off[w], job->rf_base[w]});
       }
-      Offs o;
-      o.n_win = (uint32_t)B; o.n_tok = tok_off.back(); o.tiled = fused_mode && part == 0;
-      o.max_win_tok = *std::max_element(sel_cnt.begin(), sel_cnt.end());
-      o.plane_off = put(plane_off.data(), B * 8); o.plane_ld = put(ld.data(), B * 4);
-      o.len = put(len.data(), B * 4); o.lmax = put(lmax.data(), B * 4);
-      o.tok_off = put(tok_off.data(), (B + 1) * 4);
-      o.sup_off = put(sup_o.data(), B * 8); o.out_off = put(out_o.data(), B * 8); o.rf_base = put(rfb.data(), B * 8);
-      o.n_tiles = plan.tiles.empty() ? 0u : (uint32_t)plan.tiles.size() - 1;
-      o.tiles = put(plan.tiles.data(), plan.tiles.size() * 4);
-      o.n_tiles_q = plan.tiles_q.empty() ? 0u : (uint32_t)plan.tiles_q.size() - 1;
-      o.tiles_q = put(plan.tiles_q.data(), plan.tiles_q.size() * 4);
-      o.n_tiles_b = (uint32_t)plan.grp.size();
-      o.tiles_b = put(plan.tiles_b.data(), plan.tiles_b.size() * 4);
-      o.grp = put(plan.grp.data(), plan.grp.size() * 4);
-      offs.push_back(o);
-      max_tok = std::max(max_tok, o.n_tok);
-      max_tiles_b = std::max(max_tiles_b, o.n_tiles_b);
-    }
+    build_launch(wins, cfg, blob, offs);
   }
-  const size_t supoff_at = put(job->sup_off.data(), ((size_t)n + 1) * 8);  // consensus reads it from the same blob
-  if (job->bdesc_cap < blob.size()) {
-    if (job->d_bdesc) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); small_release(ctx, job->a_bdesc); job->d_bdesc = nullptr; }
+  uint32_t max_tok = 0, max_tiles_b = 0;
+  for (const LaunchOffs& o : offs) { max_tok = std::max(max_tok, o.n_tok); max_tiles_b = std::max(max_tiles_b, o.n_tiles_b); }
+  const size_t supoff_at = image_put(blob, job->sup_off);  // consensus reads it from the same blob
+  if (job->a_bdesc.cap < blob.size()) {
+    if (job->a_bdesc.p) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); small_release(ctx, job->a_bdesc); }
     job->a_bdesc = small_acquire(ctx, blob.size() + blob.size() / 4 + 4096);
     if (!job->a_bdesc.p) { ctx->err = "out of device memory for the batch descriptors"; return HERRO_E_NO_DEVICE; }
-    job->d_bdesc = job->a_bdesc.p;
-    job->bdesc_cap = job->a_bdesc.cap;
   }
-  HIP_TRY(ctx, hipMemcpyAsync(job->d_bdesc, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(job->a_bdesc.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipEventRecord(job->ev_blob, ctx->stream));
-  job->d_supoff_blob = (const uint64_t*)((const unsigned char*)job->d_bdesc + supoff_at);
-  rc = ensure_scratch(ctx, max_tok);
-  if (rc) return rc;
+  job->d_supoff_blob = (const uint64_t*)((const unsigned char*)job->a_bdesc.p + supoff_at);
+  if ((rc = ensure_scratch(ctx, max_tok))) return rc;
   if (max_tiles_b && (rc = ensure_sib(ctx, max_tiles_b))) return rc;
-  const bool rf_compact = job->d_rfq && 2 * rf_half + 1 <= 8;   // the model reads the compact receptive fields (tokens + qualities); else the planes
-  const bool rfq_there = rf_compact && ((rf_fused_ok && job->rf_fused_half == rf_half) ||   // gathered by k_rows
-                                        (job->rfq_spec && job->rfq_spec_half == rf_half && job->rfq_spec_cap >= total_sup));   // ... by k_rfq behind featurize
-  if (!rf_compact && !job->tokens_full && !groups.empty()) {   // a receptive field above 8 rows: token planes + row map first
-    launch_full_tokens(job->J, ctx->stream, &ctx->timer);
-    job->tokens_full = true;
+  // ---- the gather, unless featurize did it
+  if (!groups.empty()) {
+    if (!rf.compact && !job->tokens_full) {   // a receptive field above 8 rows: token planes + row map first
+      launch_full_tokens(job->J, ctx->stream, &ctx->timer);
+      job->tokens_full = true;
+    }
+    uint8_t* const rfq = rf.compact ? job->d_rfq : nullptr;
+    if (rf.todo == RfPlan::ALL) launch_rf_quals(job->J, rf_half, job->d_supoff_blob, rfq, job->logit_cap, job->lean, ctx->stream, &ctx->timer);
+    else if (rf.todo == RfPlan::LEFT) launch_rf_quals(job->J, rf_half, job->d_supoff_blob, rfq, job->logit_cap, job->lean, ctx->stream, &ctx->timer, /*left_only=*/true);
+    // RfPlan::NOTHING: the records (or the complete quality planes) are there
   }
-  if (!(job->quals_full && !rf_compact) && !groups.empty() && !rfq_there)
-    launch_rf_quals(job->J, rf_half, job->d_supoff_blob, rf_compact ? job->d_rfq : nullptr, job->logit_cap, job->lean, ctx->stream, &ctx->timer);
-  else if (rf_compact && rf_fused_ok && job->rf_fused_half == rf_half && job->rf_left_windows && !groups.empty())
-    launch_rf_quals(job->J, rf_half, job->d_supoff_blob, job->d_rfq, job->logit_cap, job->lean, ctx->stream, &ctx->timer, /*left_only=*/true);
-  for (const Offs& o : offs) {
-    const unsigned char* base = (const unsigned char*)job->d_bdesc;
-    BatchDev B{};
-    B.n_win = o.n_win; B.n_tok = o.n_tok; B.max_win_tok = o.max_win_tok;
-    B.plane_off = (const uint64_t*)(base + o.plane_off);
-    B.plane_ld = (const uint32_t*)(base + o.plane_ld);
-    B.len = (const uint32_t*)(base + o.len);
-    B.lmax = (const uint32_t*)(base + o.lmax);
-    B.tok_off = (const uint32_t*)(base + o.tok_off);
-    B.sup_off = (const uint64_t*)(base + o.sup_off);
-    B.out_off = (const uint64_t*)(base + o.out_off);
-    B.rf_base = (const uint64_t*)(base + o.rf_base);
-    B.n_tiles = o.n_tiles;
-    B.tile_tok0 = (const uint32_t*)(base + o.tiles);
-    B.n_tiles_q = o.n_tiles_q;
-    B.tile_tok0_q = (const uint32_t*)(base + o.tiles_q);
-    B.n_tiles_b = o.n_tiles_b;
-    B.tile_tok0_b = (const uint32_t*)(base + o.tiles_b);
-    B.tile_grp = (const uint32_t*)(base + o.grp);
+  for (const LaunchOffs& o : offs) {
+    BatchDev B = batch_dev(job->a_bdesc.p, o);
     B.planes_b = job->J.fin_b; B.planes_q = job->J.fin_q; B.sup_row = job->J.sup_row;
-    B.rf_q = rf_compact ? job->d_rfq : nullptr;
+    B.rf_q = rf.compact ? job->d_rfq : nullptr;
     B.out_info = job->d_info; B.out_base = job->d_base;
     if (o.tiled && o.n_tiles_b && std::find(ctx->sib_suspects.begin(), ctx->sib_suspects.end(), job) == ctx->sib_suspects.end()) ctx->sib_suspects.push_back(job);
     run_model(ctx, B, o.tiled);
@@ -2815,52 +2544,20 @@ int herro_model_forward(herro_ctx* ctx, uint32_t B, uint32_t L, const uint8_t* b
   launch_transpose_blr(d_src_q, d_pq, B, L, st);
   int rc = HERRO_OK;
   if ((rc = ensure_scratch(ctx, (uint32_t)N))) return done(rc);
-  // the host arrays of both parts must outlive their asynchronous uploads
-  struct Part { std::vector<uint64_t> plane_off, sup_off, out_off; std::vector<uint32_t> ld, len, lmax, tok_off; TilePlan plan; };
-  Part parts[2];
-  const bool fused_mode = ctx->precision == 1 || ctx->precision >= 4;
-  for (int part = 0; part < 2; part++) {  // 0: windows that fit a fused tile (all windows in the unfused modes), 1: larger ones
-    Part& P = parts[part];
-    P.tok_off.assign(1, 0);
-    const bool tiled = fused_mode && part == 0;
-    std::vector<uint32_t> sel, sel_cnt;
-    for (uint32_t b = 0; b < B; b++) {
-      const bool large = fused_mode && (uint32_t)lens[b] > fused_tok_cap(ctx);
-      if ((int)large != part) continue;
-      sel.push_back(b);
-      sel_cnt.push_back((uint32_t)lens[b]);
-    }
-    if (tiled) P.plan = plan_tiles(sel_cnt, ctx->tile_packing, ctx->precision >= 4 ? model_h_half_tiles(ctx->M) : 0, ctx->n_cu);   // as herro_job_infer
-    const std::vector<uint32_t>& order = P.plan.order;
-    for (size_t k = 0; k < sel.size(); k++) {
-      const uint32_t b = sel[order.empty() ? k : order[k]];
-      P.plane_off.push_back((uint64_t)b * HERRO_ROWS * L); P.ld.push_back(L); P.len.push_back(L); P.lmax.push_back(L);
-      P.sup_off.push_back(tok_off[b]); P.out_off.push_back(tok_off[b]);
-      P.tok_off.push_back(P.tok_off.back() + (uint32_t)lens[b]);
-    }
-    const size_t nb = P.plane_off.size();
-    if (nb == 0 || P.tok_off.back() == 0) continue;
-    BatchDev bd{};
-    bd.n_win = (uint32_t)nb; bd.n_tok = P.tok_off.back(); bd.max_win_tok = *std::max_element(sel_cnt.begin(), sel_cnt.end());
-    bd.plane_off = (const uint64_t*)up(P.plane_off.data(), nb * 8); bd.plane_ld = (const uint32_t*)up(P.ld.data(), nb * 4);
-    bd.len = (const uint32_t*)up(P.len.data(), nb * 4); bd.lmax = (const uint32_t*)up(P.lmax.data(), nb * 4);
-    bd.tok_off = (const uint32_t*)up(P.tok_off.data(), (nb + 1) * 4);
-    bd.sup_off = (const uint64_t*)up(P.sup_off.data(), nb * 8); bd.out_off = (const uint64_t*)up(P.out_off.data(), nb * 8);
-    bd.tile_tok0 = (const uint32_t*)up(P.plan.tiles.data(), P.plan.tiles.size() * 4);
-    bd.n_tiles = P.plan.tiles.empty() ? 0u : (uint32_t)P.plan.tiles.size() - 1;
-    bd.tile_tok0_q = (const uint32_t*)up(P.plan.tiles_q.data(), P.plan.tiles_q.size() * 4);
-    bd.n_tiles_q = P.plan.tiles_q.empty() ? 0u : (uint32_t)P.plan.tiles_q.size() - 1;
-    bd.tile_tok0_b = (const uint32_t*)up(P.plan.tiles_b.data(), P.plan.tiles_b.size() * 4);
-    bd.tile_grp = (const uint32_t*)up(P.plan.grp.data(), P.plan.grp.size() * 4);
-    bd.n_tiles_b = (uint32_t)P.plan.grp.size();
-    if (bd.n_tiles_b && (rc = ensure_sib(ctx, bd.n_tiles_b))) { (void)hipStreamSynchronize(st); return done(rc); }
+  // one group of B windows through the builder herro_job_infer uses.  The row cap is fused_tok_cap whatever happened before: job->no_sib is the retry of a job
+  // whose sibling tiles timed out, and a forward has no retry (check_sib below reports such a pass as failed).  No rf_base: the kernels read the planes at out_off.
+  std::vector<PlanWin> wins(B);
+  for (uint32_t b = 0; b < B; b++) wins[b] = PlanWin{(uint32_t)lens[b], L, L, L, (uint64_t)b * HERRO_ROWS * L, tok_off[b], tok_off[b], 0};
+  std::vector<unsigned char> image;   // complete before its upload, alive until the stream is synchronised below
+  std::vector<LaunchOffs> offs;
+  build_launch(wins, launch_cfg(ctx, fused_tok_cap(ctx), false), image, offs);
+  const void* d_image = up(image.data(), image.size());
+  if (!d_image || e != hipSuccess) { ctx->err = e != hipSuccess ? hipGetErrorString(e) : "out of device memory"; (void)hipStreamSynchronize(st); return done(HERRO_E_NO_DEVICE); }
+  for (const LaunchOffs& o : offs) {
+    if (o.n_tiles_b && (rc = ensure_sib(ctx, o.n_tiles_b))) { (void)hipStreamSynchronize(st); return done(rc); }
+    BatchDev bd = batch_dev(d_image, o);
     bd.planes_b = d_pb; bd.planes_q = d_pq; bd.rf_q = nullptr; bd.sup_row = d_sr; bd.out_info = d_info; bd.out_base = d_base;
-    if (!bd.plane_off || !bd.plane_ld || !bd.len || !bd.lmax || !bd.tok_off || !bd.sup_off || !bd.out_off || !bd.tile_tok0 || !bd.tile_tok0_q || !bd.tile_tok0_b || !bd.tile_grp || e != hipSuccess) {
-      ctx->err = e != hipSuccess ? hipGetErrorString(e) : "out of device memory";
-      (void)hipStreamSynchronize(st);
-      return done(HERRO_E_NO_DEVICE);
-    }
-    run_model(ctx, bd, tiled);
+    run_model(ctx, bd, o.tiled);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e == hipSuccess) e = hipGetLastError();
@@ -3117,6 +2814,35 @@ int herro_debug_tile_plan_sib(const uint32_t* cnt, uint32_t n, int packed, uint3
   }
   if (grp) for (size_t i = 0; i < nb; i++) grp[i] = P.grp[i];
   return HERRO_OK;
+}
+
+// The launch plan herro_job_infer would make of a job whose windows have nsup[w] informative rows and L' = Lf[w] (include/herro_amd.h): plan_batches,
+// group_batches and build_launch, read back from the descriptor image itself — every window enters with its index as out_off.
+int64_t herro_debug_launch_plan(const uint32_t* nsup, const uint32_t* Lf, uint32_t n_win, const uint32_t* tgt_win_off, uint32_t n_targets, uint32_t batch_size,
+                                int batch_mode, int fused, uint32_t fused_rows, int packed, uint32_t n_cu, uint32_t* launch, uint32_t* pos, uint32_t* lmax) {
+  if ((n_win && (!nsup || !Lf || !launch || !pos || !lmax)) || !tgt_win_off || batch_size == 0) return HERRO_E_INVALID;
+  for (uint32_t t = 0; t < n_targets; t++) if (tgt_win_off[t] > tgt_win_off[t + 1] || tgt_win_off[t + 1] > n_win) return HERRO_E_INVALID;
+  const std::vector<uint32_t> ns(nsup, nsup + n_win), lf(Lf, Lf + n_win);
+  const std::vector<BatchPlan> batches = plan_batches(ns, lf, std::vector<uint32_t>(tgt_win_off, tgt_win_off + n_targets + 1), batch_size, batch_mode);
+  const LaunchCfg cfg{fused != 0, fused_rows, (packed & 1) != 0, (packed >> 1) & 3, n_cu, false};
+  std::vector<unsigned char> image;
+  std::vector<LaunchOffs> offs;
+  std::vector<PlanWin> wins;
+  for (const LaunchGroup& g : group_batches(batches)) {
+    wins.clear(); wins.reserve(g.n_win);
+    for (size_t bi = g.b0; bi < g.b1; bi++)
+      for (uint32_t w : batches[bi].wins) wins.push_back(PlanWin{ns[w], 0, lf[w], batches[bi].lmax, 0, 0, w, 0});
+    build_launch(wins, cfg, image, offs);
+  }
+  for (uint32_t w = 0; w < n_win; w++) { launch[w] = 0xffffffffu; pos[w] = 0; lmax[w] = 0; }
+  for (size_t l = 0; l < offs.size(); l++)
+    for (uint32_t k = 0; k < offs[l].n_win; k++) {
+      uint64_t w;
+      std::memcpy(&w, image.data() + offs[l].out_off + 8ull * k, 8);
+      std::memcpy(&lmax[w], image.data() + offs[l].lmax + 4ull * k, 4);
+      launch[w] = (uint32_t)l; pos[w] = k;
+    }
+  return (int64_t)offs.size();
 }
 
 int64_t herro_debug_extract_windows(const herro_alignment* a, uint32_t n_windows, uint32_t W, uint64_t* out,

@@ -310,6 +310,13 @@ int64_t herro_debug_tile_plan(const uint32_t* cnt, uint32_t n, int packed, uint3
  * in the group's last tile << 24.  The sibling tiles count as busy compute units when the last round is sized. */
 int herro_debug_tile_plan_sib(const uint32_t* cnt, uint32_t n, int packed, uint32_t n_cu, uint32_t* order, uint32_t* n_tiles,
                               uint32_t* tile_tok, uint32_t* grp);
+/* Host-only test hook for the whole launch plan of herro_job_infer (needs no context): a job of n_win windows with nsup[w] informative rows and L' = Lf[w],
+ * tgt_win_off[n_targets + 1] the first window of each target.  batch_size / batch_mode as herro_job_infer takes them; fused != 0: a precision with a fused
+ * stack, whose windows of more than fused_rows informative rows leave for a launch of their own; packed and n_cu as herro_debug_tile_plan.  Per window:
+ * launch[w] = index of the launch that takes it (0xffffffff: no informative rows, it is in none), pos[w] = its position in that launch's window stream,
+ * lmax[w] = the padding length it carries (the longest window of its batch).  Returns the number of launches. */
+int64_t herro_debug_launch_plan(const uint32_t* nsup, const uint32_t* Lf, uint32_t n_win, const uint32_t* tgt_win_off, uint32_t n_targets, uint32_t batch_size,
+                                int batch_mode, int fused, uint32_t fused_rows, int packed, uint32_t n_cu, uint32_t* launch, uint32_t* pos, uint32_t* lmax);
 
 /* ---- PAF / .oec.zst ingest on the host (needs no device) ---------------------------------------
  * herro_paf_parse replaces `parse_paf` (overlaps.rs:117-202): one overlap per line, tab separated
