@@ -27,7 +27,7 @@ EXPORTS = [
     "herro_paf_parse", "herro_oec_read", "herro_paf_n_targets", "herro_paf_target_ids", "herro_paf_aln_off",
     "herro_paf_alignments", "herro_paf_free", "herro_name_index_create", "herro_name_index_free", "herro_paf_parse_indexed",
     "herro_oec_read_indexed", "herro_paf_parse_view", "herro_debug_host_ctx", "herro_debug_job_array", "herro_debug_tile_plan", "herro_debug_tile_plan_sib", "herro_debug_launch_plan",
-    "herro_debug_set_featurize_planes", "herro_debug_set_host_build", "herro_debug_job_dev_built", "herro_debug_job_rf", "herro_debug_job_cwd", "herro_debug_job_set_base_logits", "herro_debug_job_rf_fused", "herro_debug_job_rf_left", "herro_debug_e4m3", "herro_debug_sib_fault", "herro_debug_sib_retries", "herro_debug_base_row_votes", "herro_debug_vote5",
+    "herro_debug_set_featurize_planes", "herro_debug_set_conv_fc", "herro_debug_set_host_build", "herro_debug_job_dev_built", "herro_debug_job_rf", "herro_debug_job_cwd", "herro_debug_job_set_base_logits", "herro_debug_job_rf_fused", "herro_debug_job_rf_left", "herro_debug_e4m3", "herro_debug_sib_fault", "herro_debug_sib_retries", "herro_debug_base_row_votes", "herro_debug_vote5",
     "herro_pool_create", "herro_pool_destroy", "herro_pool_last_error", "herro_pool_size", "herro_pool_ctx", "herro_pool_set_reads", "herro_pool_load_model",
     "herro_pool_correct", "herro_pool_result", "herro_pool_groups_taken", "herro_pool_skipped", "herro_debug_pool_fake", "herro_job_create_status", "herro_host_register", "herro_host_unregister", "herro_debug_zero_copy_jobs",
     "herro_fastx_read", "herro_reads_count", "herro_reads_seq", "herro_reads_qual", "herro_reads_off", "herro_reads_ids",
@@ -309,6 +309,11 @@ def lib():
         L.herro_debug_job_array.argtypes = [vp, i32, vp, vp]
         L.herro_debug_set_featurize_planes.argtypes = [vp, i32]
         L.herro_debug_set_host_build.argtypes = [vp, i32]
+        try:   # (an older build selected by HERRO_LIB has the two-kernel front end only)
+            L.herro_debug_set_conv_fc.argtypes = [vp, i32]
+        except AttributeError:
+            if not os.environ.get("HERRO_LIB"):
+                raise
         L.herro_debug_job_dev_built.argtypes = [vp]
         L.herro_debug_base_row_votes.argtypes = [vp, vp, vp, u32, vp, vp]
         L.herro_debug_vote5.restype = u32
@@ -582,6 +587,10 @@ class Context:
     def featurize_planes(self, on: bool):
         """test hook: jobs featurized from now on take the planes path (k_tokens) instead of the lean one (k_rows)"""
         self._chk(self._l.herro_debug_set_featurize_planes(self.h, int(on)))
+
+    def conv_fc(self, mode: int):
+        """test hook: front end of the f16 model from now on: -1 chosen per launch, 0 k_conv_m + k_fc_r, 1 k_conv_fc wherever its shapes allow"""
+        self._chk(self._l.herro_debug_set_conv_fc(self.h, int(mode)))
 
     def register_host(self, arr: np.ndarray):
         """herro_host_register: jobs whose CIGAR pointers lie in `arr` (a contiguous u8 array the caller keeps alive) are created zero-copy."""

@@ -115,6 +115,7 @@ struct herro_ctx {
   // lean: herro_job_featurize derives informative rows, votes and receptive fields without writing the token planes (k_rows); the planes are
   // built when somebody asks for them.  HERRO_FEATURIZE_PLANES=1 (or herro_debug_set_featurize_planes): the planes path of rounds 3-4 (A/B, parity tests)
   bool lean = [] { const char* e = getenv("HERRO_FEATURIZE_PLANES"); return !e || atoi(e) == 0; }();
+  int conv_fc = -1;   // front end of the f16 model (launch_model_h): -1 chosen per launch (conv_fc_faster), 0 k_conv_m + k_fc_r, 1 k_conv_fc wherever its shapes allow (herro_debug_set_conv_fc)
   bool tile_packing = herro::ab_env("HERRO_TILE_PACK", 1) != 0;  // 0 (A/B builds): windows in batch order
   uint64_t* d_words = nullptr;
   uint32_t* d_p0 = nullptr;

@@ -277,7 +277,7 @@ static void run_model(herro_ctx* ctx, const BatchDev& B, bool tiled) {
   if (B.n_tok == 0) return;
   const int p = ctx->precision;
   if (!tiled) { launch_model(ctx->M, B, ctx->S, (p == 1 || p >= 4) ? 3 : p, ctx->stream, &ctx->timer); return; }
-  if (p >= 4) launch_model_h(ctx->M, B, ctx->S, p == 4 ? 2 : (p == 6 ? 3 : (p == 7 ? 21 : (p == 8 ? 12 : 1))), ctx->stream, &ctx->timer);
+  if (p >= 4) launch_model_h(ctx->M, B, ctx->S, p == 4 ? 2 : (p == 6 ? 3 : (p == 7 ? 21 : (p == 8 ? 12 : 1))), ctx->stream, &ctx->timer, ctx->conv_fc);
   else launch_model(ctx->M, B, ctx->S, p, ctx->stream, &ctx->timer);
 }
 
@@ -2633,6 +2633,12 @@ uint32_t herro_debug_vote5(const uint32_t* c5, uint32_t tb) {
 int herro_debug_set_featurize_planes(herro_ctx* ctx, int on) {
   if (!ctx) return HERRO_E_INVALID;
   ctx->lean = on == 0;
+  return HERRO_OK;
+}
+
+int herro_debug_set_conv_fc(herro_ctx* ctx, int mode) {
+  if (!ctx || mode < -1 || mode > 1) return HERRO_E_INVALID;
+  ctx->conv_fc = mode;
   return HERRO_OK;
 }
 

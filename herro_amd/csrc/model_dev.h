@@ -171,7 +171,8 @@ bool model_h_conv_supported(const ModelDev& M);   // ... and the f16 conv / FC k
 void launch_front_generic(const ModelDev& M, const BatchDev& B, const ModelScratch& S, hipStream_t st, KernelTimer* tm);   // model.hip
 bool model_h_f8_supported(const ModelDev& M);   // ... and every layer's proj / ff1 / ff2 has its e4m3 copy
 int model_h_half_tiles(const ModelDev& M);   // qmode of plan_tiles: 0 no 32-token tiles, 1 for a short last round (default), 2 for every small window (HERRO_LAYERS_Q)
-void launch_model_h(const ModelDev& M, const BatchDev& B, const ModelScratch& S, int terms, hipStream_t st, KernelTimer* tm);
+bool conv_fc_faster(uint32_t n_tok, uint32_t n_cu, uint32_t tile);   // the front end's selection rule: k_conv_fc, or k_conv_m + k_fc_r
+void launch_model_h(const ModelDev& M, const BatchDev& B, const ModelScratch& S, int terms, hipStream_t st, KernelTimer* tm, int conv_fc = -1);   // conv_fc: -1 by the rule, 0 two kernels, 1 k_conv_fc
 void launch_pe_table(const float* pe_div, float* tab, uint32_t rows, uint32_t d_model, hipStream_t st);   // tab[row][2 i] = sin(row * pe_div[i]), [2 i + 1] = cos
 #ifdef HERRO_PROF_BUILD
 void model_h_prof_dump();   // phase cycles of k_layers_p (model_h.hip LP_MARK), printed by herro_destroy when HERRO_PROF=1

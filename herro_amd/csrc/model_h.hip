@@ -19,6 +19,7 @@
 // Kernels (same dataflow as model.hip, re-derived for one 2-byte plane per operand):
 //   k_conv_m   embedding + quality + conv1 as a K = 96 GEMM -> (registers) -> conv2 (K = 192) -> y2 as ONE f16 plane [N*31][128]
 //   k_fc_r     y2[N][3968] . Wfc -> x[N][256]; (64 .. 128) x 256 tiles, weights L2 -> registers, activations through the LDS, 2 workgroups per CU
+//   k_conv_fc  both of the above in one kernel, y2 in LDS: the same bits; taken where it measures faster (conv_fc_faster)
 //   k_layers_p the whole encoder stack per tile of <= 64 (or 32) tokens: residual stream in registers from the FC output to
 //              the logits (positional encoding added on the way in), weight fragments one half GEMM call ahead;
 //              <., 4, true>: the same grid headed by SIBLING tiles — a window of 65 .. 512 informative rows on ceil(rows / 64) tiles
@@ -199,56 +200,60 @@ constexpr int CM_NT = 256;
 #endif
 constexpr size_t CONV_M_SHM = (size_t)48 * 1024 + 128 * 4 + 32 * 16 + 256 * 4;
 
-template <int NB, int WPS, bool RF>   // RF: the cells come as 16-byte receptive-field records (B.rf_q); else from the token / quality planes
-__global__ __launch_bounds__(CM_NT, WPS) void k_conv_m(ModelDev M, BatchDev B, ModelScratch S, uint32_t n_rows, uint32_t n_units, uint32_t unit0) {   // units [unit0, n_units) of 16 pairs; n_rows: pairs of the launch group
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  uint4* s_w2 = reinterpret_cast<uint4*>(smem);                     // conv2 weights in fragment order: fragment f, lane l at [f * 64 + l]
-  float* s_b2 = reinterpret_cast<float*>(smem + 48 * 1024);
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const uint32_t fr = lane & 15, fg = lane >> 4;
-  {
-    const uint4* src = reinterpret_cast<const uint4*>(M.conv2.ph16);
-    for (uint32_t i = tid; i < 48 * 64; i += CM_NT) s_w2[i] = src[i];
-    for (uint32_t i = tid; i < 128; i += CM_NT) s_b2[i] = M.conv2.bias[i];
+// The pieces of the conv stack that k_conv_m and k_conv_fc share (forced inline: each kernel compiles them into its own loop).
+struct CvRaw { uint32_t t[5], q[5]; uint4 rf; };
+struct CvCells { uint32_t tok[2], q[2], ok; };   // five token bytes, five quality bytes (0xff: none), validity of the three conv1 positions
+// LDS of the conv stack (CONV_M_SHM bytes): conv2 weights in fragment order (fragment f, lane l at [f * 64 + l]), conv2 bias, the one-hot operand
+// fragments by (token, lane parity) — lanes fg 0 / 2 hold slots 0..7, lanes fg 1 / 3 slots 8..15 (+ one in slot 15) — and quality byte -> normalised
+// quality as f16 hi | lo << 16 (255: no cell -> 0)
+struct CvLds { uint4* w2; float* b2; uint4* oh; uint32_t* ql; };
+__device__ __forceinline__ CvLds cv_lds(unsigned char* smem) {
+  CvLds L;
+  L.w2 = reinterpret_cast<uint4*>(smem);
+  L.b2 = reinterpret_cast<float*>(smem + 48 * 1024);
+  L.oh = reinterpret_cast<uint4*>(L.b2 + 128);
+  L.ql = reinterpret_cast<uint32_t*>(L.oh + 32);
+  return L;
+}
+template <int NT>
+__device__ __forceinline__ void cv_fill_lds(const CvLds& L, const ModelDev& M, uint32_t tid) {   // (the caller's barrier follows)
+  const uint4* src = reinterpret_cast<const uint4*>(M.conv2.ph16);
+  for (uint32_t i = tid; i < 48 * 64; i += NT) L.w2[i] = src[i];
+  for (uint32_t i = tid; i < 128; i += NT) L.b2[i] = M.conv2.bias[i];
+  if (NT == 256 || tid < 256) {
+    uint32_t qh = 0, ql = 0;
+    if (tid < 255) split_h2(norm_qual_h(tid), 0.f, qh, ql);
+    L.ql[tid] = (qh & 0xffffu) | (ql << 16);
   }
-  half8 w1[3][2][2];   // [tap][slab][jt]
-  {
-    const uint16_t* p = M.conv1g.ph16 + (uint64_t)lane * 8;
-#pragma unroll
-    for (int sl = 0; sl < 2; sl++)
-#pragma unroll
-      for (int jt = 0; jt < 2; jt++)
-#pragma unroll
-        for (int tp = 0; tp < 3; tp++) w1[tp][sl][jt] = *reinterpret_cast<const half8*>(p + (uint64_t)(((sl * 2 + jt) * 3 + tp) * 64) * 8);
+  if (tid < 32) {
+    const uint32_t tok = tid >> 1, od = tid & 1u, t = tok - 8u * od;
+    uint32_t r[4] = {0, 0, 0, od ? 0x3c000000u : 0u};
+    if (tok < 13 && (od ? t < 5u : t < 8u)) r[t >> 1] |= 0x3c00u << ((t & 1u) * 16u);
+    L.oh[tid] = make_uint4(r[0], r[1], r[2], r[3]);
   }
-  constexpr bool rfq = RF;
-  // The receptive field of pair m: rows tok_row - 2 .. + 2 of read row (m % 31) of the token's window; outside [0, lmax): token 12
-  // (zero table row) and no quality; inside the batch padding [len, lmax): pad token and quality 126 (inference.rs:86-97).
-  // Two dependent loads (the token's record, then its cells) run two and one unit ahead of the arithmetic.
-  struct Raw { uint32_t t[5], q[5]; uint4 rf; };
-  struct Cells { uint32_t tok[2], q[2], ok; };   // five token bytes, five quality bytes (0xff: none), validity of the three conv1 positions
-  auto load_meta = [&](uint32_t m) -> TokCv {
-#if HERRO_CONV_DBG & 1
-    m = lane;   // timing experiment: every wave fetches the same few cells (cache hits)
-#endif
-    return S.tok_cv[min(m, n_rows - 1u) / HERRO_ROWS];
-  };
-  auto load_raw = [&](const TokCv& tm, uint32_t m) -> Raw {
-    Raw r;
-#if HERRO_CONV_DBG & 1
-    m = lane;
-#endif
-    const uint32_t rr = min(m, n_rows - 1u) % HERRO_ROWS;
-    if constexpr (RF) {   // one 16-byte record: the pair's five tokens and five qualities (k_rfq) — no token plane exists on the lean path
-      r.rf = *reinterpret_cast<const uint4*>(B.rf_q + ((uint64_t)tm.rf_idx * HERRO_ROWS + rr) * 16);
+}
+__device__ __forceinline__ void cv_load_w1(const ModelDev& M, uint32_t lane, half8 (&w1)[3][2][2]) {   // [tap][slab][jt]
+  const uint16_t* p = M.conv1g.ph16 + (uint64_t)lane * 8;
 #pragma unroll
-      for (int i = 0; i < 5; i++) { r.t[i] = 0; r.q[i] = 0; }
-      return r;
-    } else {
-    // the plane stride and the token's row come from the token's full record: a window has up to 8192 x 51 = 417 792 rows, and until they were taken out of
-    // TokCv's packed words a stride or row of 2^16 spilled into the default token of row 4 and the validity bits (only this branch ever read them)
-    const TokMeta tf = S.tok_meta[min(m, n_rows - 1u) / HERRO_ROWS];
-    const uint32_t ld = tf.plane_ld, trow = tf.tok_row;
+  for (int sl = 0; sl < 2; sl++)
+#pragma unroll
+    for (int jt = 0; jt < 2; jt++)
+#pragma unroll
+      for (int tp = 0; tp < 3; tp++) w1[tp][sl][jt] = *reinterpret_cast<const half8*>(p + (uint64_t)(((sl * 2 + jt) * 3 + tp) * 64) * 8);
+}
+// The receptive field of a pair (token, read row rr): rows tok_row - 2 .. + 2 of read row rr of the token's window; outside [0, lmax): token 12
+// (zero table row) and no quality; inside the batch padding [len, lmax): pad token and quality 126 (inference.rs:86-97).
+// RF: one 16-byte record holds the pair's five tokens and five qualities (k_rfq) — no token plane exists on the lean path; else the cells come from the
+// planes, whose stride `ld` and the token's row `trow` come from the token's full record (TokMeta): a window has up to 8192 x 51 = 417 792 rows, and until they
+// were taken out of TokCv's packed words a stride or row of 2^16 spilled into the default token of row 4 and the validity bits
+template <bool RF>
+__device__ __forceinline__ CvRaw cv_load_raw(const BatchDev& B, const TokCv& tm, uint32_t ld, uint32_t trow, uint32_t rr) {
+  CvRaw r;
+  if constexpr (RF) {
+    r.rf = *reinterpret_cast<const uint4*>(B.rf_q + ((uint64_t)tm.rf_idx * HERRO_ROWS + rr) * 16);
+#pragma unroll
+    for (int i = 0; i < 5; i++) { r.t[i] = 0; r.q[i] = 0; }
+  } else {
     const uint8_t* pb = B.planes_b + tm.plane_off + (uint64_t)rr * ld;
     r.rf = make_uint4(0, 0, 0, 0);
     const uint8_t* pq = B.planes_q + tm.plane_off + (uint64_t)rr * ld;
@@ -258,45 +263,148 @@ __global__ __launch_bounds__(CM_NT, WPS) void k_conv_m(ModelDev M, BatchDev B, M
       r.t[i] = pb[row];
       r.q[i] = (uint32_t)pq[row];
     }
-    return r;
+  }
+  return r;
+}
+// the raw cells as four words: tokens of rows 0..3, of row 4, qualities of rows 0..3, of row 4 (RF: the record itself)
+template <bool RF>
+__device__ __forceinline__ uint4 cv_pack(const CvRaw& r) {
+  if constexpr (RF) return r.rf;
+  else return make_uint4(r.t[0] | (r.t[1] << 8) | (r.t[2] << 16) | (r.t[3] << 24), r.t[4], r.q[0] | (r.q[1] << 8) | (r.q[2] << 16) | (r.q[3] << 24), r.q[4]);
+}
+__device__ __forceinline__ CvCells cv_finish(const uint4& p, const TokCv& tm) {
+  CvCells c;
+  const uint32_t mk1 = tm.row_ok >> 24;
+  c.tok[0] = (p.x & tm.mk0) | tm.dt0; c.tok[1] = (p.y & mk1) | ((tm.ld_d1 >> 16) & 0xffu);
+  c.q[0] = (p.z & tm.mk0) | tm.dq0; c.q[1] = (p.w & mk1) | (tm.ld_d1 >> 24);
+  c.ok = (tm.row_ok >> 16) & 7u;
+  return c;
+}
+// conv1 of one block of 16 pairs (36 MFMAs): y1f[conv2 k-step = position * 2 + slab]
+__device__ __forceinline__ void cv_conv1(const CvLds& L, const half8 (&w1)[3][2][2], const CvCells& cur, uint32_t fg, half8 (&y1f)[6]) {
+  const uint32_t odd = fg & 1u, mq_hi = odd ? 0xffffu : 0u, mq_lo = fg == 1u ? 0xffffu : 0u;
+  // operand fragments of the five receptive-field rows: lanes fg 0 / 2 slots 0..7 (one-hot of tokens 0..7), lanes fg 1 / 3
+  // slots 8..15 (tokens 8..12, q_hi, q_lo | 0, one)
+  half8 rf[5];
+#pragma unroll
+  for (int i = 0; i < 5; i++) {
+    const uint32_t tok = ((i < 4 ? cur.tok[0] >> (8 * i) : cur.tok[1]) & 0xffu);
+    const uint32_t qb = ((i < 4 ? cur.q[0] >> (8 * i) : cur.q[1]) & 0xffu);
+    uint4 r = L.oh[tok * 2u + odd];
+    const uint32_t qhl = L.ql[qb];
+    r.z |= (qhl & mq_hi) << 16;                               // slot 13 (29): q_hi
+    r.w |= (qhl >> 16) & mq_lo;                               // slot 14: q_lo (30: unused)
+    rf[i] = as_half8(r.x, r.y, r.z, r.w);
+  }
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    f32x4 a[2][2];
+#pragma unroll
+    for (int sl = 0; sl < 2; sl++)
+#pragma unroll
+      for (int jt = 0; jt < 2; jt++) a[sl][jt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int tp = 0; tp < 3; tp++)
+#pragma unroll
+      for (int sl = 0; sl < 2; sl++)
+#pragma unroll
+        for (int jt = 0; jt < 2; jt++) a[sl][jt] = mma(w1[tp][sl][jt], rf[j + tp], a[sl][jt]);
+    const uint32_t okm = ((cur.ok >> j) & 1u) ? 0xffffffffu : 0u;   // conv2 sees zeros beyond the (padded) sequence ends
+#pragma unroll
+    for (int sl = 0; sl < 2; sl++) {
+      float v[8];
+#pragma unroll
+      for (int q = 0; q < 8; q++) v[q] = a[sl][q >> 2][q & 3];
+      y1f[j * 2 + sl] = relu_mask_h8(pack_h8(v), okm);   // ReLU after the rounding: the same number
+    }
+  }
+}
+// conv2, output channels 64 hs .. + 63 of NB blocks against one read of every weight fragment: y2h[block][slab] = the lane's pair, channels (hs * 2 + slab) * 32 + 8 fg .. + 7
+template <int NB>
+__device__ __forceinline__ void cv_conv2(const CvLds& L, int hs, const half8 (&y1f)[NB][6], uint32_t lane, uint32_t fg, half8 (&y2h)[NB][2]) {
+  f32x4 a2[NB][2][2];   // [block][slab][jt]
+#pragma unroll
+  for (int sl = 0; sl < 2; sl++)
+#pragma unroll
+    for (int jt = 0; jt < 2; jt++) {
+      const float4 bv = *reinterpret_cast<const float4*>(L.b2 + (hs * 2 + sl) * 32 + 8 * fg + 4 * jt);
+#pragma unroll
+      for (int b = 0; b < NB; b++) a2[b][sl][jt] = f32x4{bv.x, bv.y, bv.z, bv.w};
+    }
+  half8 wf[2][2], wn[2][2];   // the fragments of one k-step, read one k-step ahead of their MFMAs
+  auto rdw = [&](int ks, half8 (&w)[2][2]) {
+#pragma unroll
+    for (int sl = 0; sl < 2; sl++)
+#pragma unroll
+      for (int jt = 0; jt < 2; jt++) w[sl][jt] = __builtin_bit_cast(half8, L.w2[(HERRO_CONV_DBG & 2) ? lane : ((((hs * 2 + sl) * 2 + jt) * 6 + ks) * 64) + lane]);
+  };
+  rdw(0, wf);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int ks = 0; ks < 6; ks++) {
+    if (ks < 5) rdw(ks + 1, wn);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int sl = 0; sl < 2; sl++)
+#pragma unroll
+      for (int jt = 0; jt < 2; jt++)
+#pragma unroll
+        for (int b = 0; b < NB; b++) a2[b][sl][jt] = mma(wf[sl][jt], y1f[b][ks], a2[b][sl][jt]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int sl = 0; sl < 2; sl++)
+#pragma unroll
+      for (int jt = 0; jt < 2; jt++) wf[sl][jt] = wn[sl][jt];
+  }
+#pragma unroll
+  for (int b = 0; b < NB; b++)
+#pragma unroll
+    for (int sl = 0; sl < 2; sl++) {
+      float v[8];
+#pragma unroll
+      for (int q = 0; q < 8; q++) v[q] = a2[b][sl][q >> 2][q & 3];
+      y2h[b][sl] = relu_mask_h8(pack_h8(v), 0xffffffffu);
+    }
+}
+
+template <int NB, int WPS, bool RF>   // RF: the cells come as 16-byte receptive-field records (B.rf_q); else from the token / quality planes
+__global__ __launch_bounds__(CM_NT, WPS) void k_conv_m(ModelDev M, BatchDev B, ModelScratch S, uint32_t n_rows, uint32_t n_units, uint32_t unit0) {   // units [unit0, n_units) of 16 pairs; n_rows: pairs of the launch group
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const CvLds L = cv_lds(smem);
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const uint32_t fr = lane & 15, fg = lane >> 4;
+  cv_fill_lds<CM_NT>(L, M, tid);
+  half8 w1[3][2][2];   // [tap][slab][jt]
+  cv_load_w1(M, lane, w1);
+  // Two dependent loads (the token's record, then its cells) run two and one unit ahead of the arithmetic.
+  auto load_meta = [&](uint32_t m) -> TokCv {
+#if HERRO_CONV_DBG & 1
+    m = lane;   // timing experiment: every wave fetches the same few cells (cache hits)
+#endif
+    return S.tok_cv[min(m, n_rows - 1u) / HERRO_ROWS];
+  };
+  auto load_raw = [&](const TokCv& tm, uint32_t m) -> CvRaw {
+#if HERRO_CONV_DBG & 1
+    m = lane;
+#endif
+    const uint32_t rr = min(m, n_rows - 1u) % HERRO_ROWS;
+    if constexpr (RF) return cv_load_raw<true>(B, tm, 0, 0, rr);
+    else {
+      const TokMeta tf = S.tok_meta[min(m, n_rows - 1u) / HERRO_ROWS];
+      return cv_load_raw<false>(B, tm, tf.plane_ld, tf.tok_row, rr);
     }
   };
-  auto finish = [&](const Raw& r, const TokCv& tm) -> Cells {
-    Cells c;
-    const uint32_t t0 = rfq ? r.rf.x : (r.t[0] | (r.t[1] << 8) | (r.t[2] << 16) | (r.t[3] << 24)), t1 = rfq ? r.rf.y : r.t[4];
-    const uint32_t q0 = rfq ? r.rf.z : (r.q[0] | (r.q[1] << 8) | (r.q[2] << 16) | (r.q[3] << 24)), q1 = rfq ? r.rf.w : r.q[4];
-    const uint32_t mk1 = tm.row_ok >> 24;
-    c.tok[0] = (t0 & tm.mk0) | tm.dt0; c.tok[1] = (t1 & mk1) | ((tm.ld_d1 >> 16) & 0xffu);
-    c.q[0] = (q0 & tm.mk0) | tm.dq0; c.q[1] = (q1 & mk1) | (tm.ld_d1 >> 24);
-    c.ok = (tm.row_ok >> 16) & 7u;
-    return c;
-  };
-  // one-hot operand fragments by (token, lane parity): lanes fg 0 / 2 hold slots 0..7, lanes fg 1 / 3 slots 8..15 (+ one in slot 15)
-  uint4* s_oh = reinterpret_cast<uint4*>(s_b2 + 128);
-  uint32_t* s_ql = reinterpret_cast<uint32_t*>(s_oh + 32);   // quality byte -> normalised quality as f16 hi | lo << 16 (255: no cell -> 0)
-  {
-    uint32_t qh = 0, ql = 0;
-    if (tid < 255) split_h2(norm_qual_h(tid), 0.f, qh, ql);
-    s_ql[tid] = (qh & 0xffffu) | (ql << 16);
-  }
-  if (tid < 32) {
-    const uint32_t tok = tid >> 1, od = tid & 1u, t = tok - 8u * od;
-    uint32_t r[4] = {0, 0, 0, od ? 0x3c000000u : 0u};
-    if (tok < 13 && (od ? t < 5u : t < 8u)) r[t >> 1] |= 0x3c00u << ((t & 1u) * 16u);
-    s_oh[tid] = make_uint4(r[0], r[1], r[2], r[3]);
-  }
   __syncthreads();
 
-  const uint32_t odd = fg & 1u, mq_hi = odd ? 0xffffu : 0u, mq_lo = fg == 1u ? 0xffffu : 0u;
   const uint32_t stride = gridDim.x * (CM_NT / 64);
   uint32_t unit = unit0 + blockIdx.x * (CM_NT / 64) + wave;
   TokCv mt1[NB], mt2[NB];   // records of the pairs of unit + stride, unit + 2 stride
-  Cells cur[NB];
-  Raw raw[NB];
+  CvCells cur[NB];
+  CvRaw raw[NB];
 #pragma unroll
   for (int b = 0; b < NB; b++) {
     const TokCv m0 = load_meta(unit * (16 * NB) + b * 16 + fr);
-    cur[b] = finish(load_raw(m0, unit * (16 * NB) + b * 16 + fr), m0);
+    cur[b] = cv_finish(cv_pack<RF>(load_raw(m0, unit * (16 * NB) + b * 16 + fr)), m0);
     mt1[b] = load_meta((unit + stride) * (16 * NB) + b * 16 + fr);
   }
   for (; unit < n_units; unit += stride) {
@@ -307,96 +415,24 @@ __global__ __launch_bounds__(CM_NT, WPS) void k_conv_m(ModelDev M, BatchDev B, M
     }
     half8 y1f[NB][6];   // [block][conv2 k-step = position * 2 + slab]
 #pragma unroll
-    for (int b = 0; b < NB; b++) {
-      // operand fragments of the five receptive-field rows: lanes fg 0 / 2 slots 0..7 (one-hot of tokens 0..7), lanes fg 1 / 3
-      // slots 8..15 (tokens 8..12, q_hi, q_lo | 0, one)
-      half8 rf[5];
-#pragma unroll
-      for (int i = 0; i < 5; i++) {
-        const uint32_t tok = ((i < 4 ? cur[b].tok[0] >> (8 * i) : cur[b].tok[1]) & 0xffu);
-        const uint32_t qb = ((i < 4 ? cur[b].q[0] >> (8 * i) : cur[b].q[1]) & 0xffu);
-        uint4 r = s_oh[tok * 2u + odd];
-        const uint32_t qhl = s_ql[qb];
-        r.z |= (qhl & mq_hi) << 16;                               // slot 13 (29): q_hi
-        r.w |= (qhl >> 16) & mq_lo;                               // slot 14: q_lo (30: unused)
-        rf[i] = as_half8(r.x, r.y, r.z, r.w);
-      }
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        f32x4 a[2][2];
-#pragma unroll
-        for (int sl = 0; sl < 2; sl++)
-#pragma unroll
-          for (int jt = 0; jt < 2; jt++) a[sl][jt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int tp = 0; tp < 3; tp++)
-#pragma unroll
-          for (int sl = 0; sl < 2; sl++)
-#pragma unroll
-            for (int jt = 0; jt < 2; jt++) a[sl][jt] = mma(w1[tp][sl][jt], rf[j + tp], a[sl][jt]);
-        const uint32_t okm = ((cur[b].ok >> j) & 1u) ? 0xffffffffu : 0u;   // conv2 sees zeros beyond the (padded) sequence ends
-#pragma unroll
-        for (int sl = 0; sl < 2; sl++) {
-          float v[8];
-#pragma unroll
-          for (int q = 0; q < 8; q++) v[q] = a[sl][q >> 2][q & 3];
-          y1f[b][j * 2 + sl] = relu_mask_h8(pack_h8(v), okm);   // ReLU after the rounding: the same number
-        }
-      }
-    }
+    for (int b = 0; b < NB; b++) cv_conv1(L, w1, cur[b], fg, y1f[b]);
     // conv2: 64 output channels at a time, both blocks against one read of every weight fragment
     uint16_t* y2 = S.y2_hi;
 #pragma unroll
     for (int hs = 0; hs < 2; hs++) {
-      f32x4 a2[NB][2][2];   // [block][slab][jt]
-#pragma unroll
-      for (int sl = 0; sl < 2; sl++)
-#pragma unroll
-        for (int jt = 0; jt < 2; jt++) {
-          const float4 bv = *reinterpret_cast<const float4*>(s_b2 + (hs * 2 + sl) * 32 + 8 * fg + 4 * jt);
-#pragma unroll
-          for (int b = 0; b < NB; b++) a2[b][sl][jt] = f32x4{bv.x, bv.y, bv.z, bv.w};
-        }
-      half8 wf[2][2], wn[2][2];   // the fragments of one k-step, read one k-step ahead of their MFMAs
-      auto rdw = [&](int ks, half8 (&w)[2][2]) {
-#pragma unroll
-        for (int sl = 0; sl < 2; sl++)
-#pragma unroll
-          for (int jt = 0; jt < 2; jt++) w[sl][jt] = __builtin_bit_cast(half8, s_w2[(HERRO_CONV_DBG & 2) ? lane : ((((hs * 2 + sl) * 2 + jt) * 6 + ks) * 64) + lane]);
-      };
-      rdw(0, wf);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int ks = 0; ks < 6; ks++) {
-        if (ks < 5) rdw(ks + 1, wn);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int sl = 0; sl < 2; sl++)
-#pragma unroll
-          for (int jt = 0; jt < 2; jt++)
-#pragma unroll
-            for (int b = 0; b < NB; b++) a2[b][sl][jt] = mma(wf[sl][jt], y1f[b][ks], a2[b][sl][jt]);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int sl = 0; sl < 2; sl++)
-#pragma unroll
-          for (int jt = 0; jt < 2; jt++) wf[sl][jt] = wn[sl][jt];
-      }
+      half8 y2h[NB][2];
+      cv_conv2<NB>(L, hs, y1f, lane, fg, y2h);
 #pragma unroll
       for (int b = 0; b < NB; b++) {
         const uint32_t m = unit * (16 * NB) + b * 16 + fr;
 #pragma unroll
-        for (int sl = 0; sl < 2; sl++) {
-          float v[8];
-#pragma unroll
-          for (int q = 0; q < 8; q++) v[q] = a2[b][sl][q >> 2][q & 3];
-          if (m < n_rows) *reinterpret_cast<half8*>(y2 + (uint64_t)m * HC2 + (hs * 2 + sl) * 32 + 8 * fg) = relu_mask_h8(pack_h8(v), 0xffffffffu);
-        }
+        for (int sl = 0; sl < 2; sl++)
+          if (m < n_rows) *reinterpret_cast<half8*>(y2 + (uint64_t)m * HC2 + (hs * 2 + sl) * 32 + 8 * fg) = y2h[b][sl];
       }
     }
 #pragma unroll
     for (int b = 0; b < NB; b++) {
-      cur[b] = finish(raw[b], mt1[b]);
+      cur[b] = cv_finish(cv_pack<RF>(raw[b]), mt1[b]);
       mt1[b] = mt2[b];
     }
   }
@@ -423,6 +459,55 @@ constexpr size_t FC_R_SHM = (size_t)2 * FR_ROWS * 64 * 2;   // two buffers [128 
 // pe_tab (round 6): the positional encoding of a token's row is added HERE, from the table of herro_load_model (ModelDev::pe_tab), for rows inside the table — the stack's
 // prologue, where every compute unit fetches its tile at the same moment, reads 64 KB per tile instead of 128 (and ran 16 sincosf per lane before the table existed);
 // k_layers_p adds the encoding of the rows BEYOND the table itself (the same rule on both sides: row < pe_rows)
+// The pieces of a k-step and the epilogue that k_fc_r and k_conv_fc share.  `t`: one LDS tile [128 rows][64 k] f16, row r at r * 128 B, 16-byte chunk c at (c ^ (r & 7)).
+// A quarter k-step = 2 row blocks x 2 column blocks = 4 MFMAs; the fragments of the next quarter are read under them.
+template <int NB>
+__device__ __forceinline__ void fc_rd(const uint16_t* t, uint32_t kk, uint32_t g, uint32_t fr, uint32_t fg, half8 (&x)[2]) {
+#pragma unroll
+  for (int i = 0; i < 2; i++) {
+    if (g * 2 + i >= (uint32_t)NB) continue;   // (compile time: the loops around are unrolled)
+    const uint32_t r = (g * 2 + i) * 16 + fr;
+    x[i] = *reinterpret_cast<const half8*>(t + r * 64 + (((kk * 4 + fg) ^ (r & 7u)) << 3));
+  }
+}
+template <int NB>
+__device__ __forceinline__ void fc_mm(f32x4 (&acc)[NB][2], uint32_t g, const half8 (&x)[2], const half8 (&w)[2]) {
+#pragma unroll
+  for (int i = 0; i < 2; i++)
+#pragma unroll
+    for (int jt = 0; jt < 2; jt++) if (g * 2 + i < (uint32_t)NB) acc[g * 2 + i][jt] = mma(w[jt], x[i], acc[g * 2 + i][jt]);
+}
+// rows m0 .. of the tile, this wave's 32 columns: bias, then the positional encoding of rows inside the table, then C
+template <int NB>
+__device__ __forceinline__ void fc_epilogue(const f32x4 (&acc)[NB][2], const Weight& W, float* C, uint32_t ldc, uint32_t M, uint32_t m0, const uint32_t* __restrict__ tok_row,
+                                            const float* __restrict__ pe_tab, uint32_t pe_rows, uint32_t wave, uint32_t fr, uint32_t fg) {
+  float bs[8];
+  {
+    const float* bp = W.bias + wave * 32 + 8 * fg;
+#pragma unroll
+    for (int q = 0; q < 8; q++) bs[q] = W.bias ? bp[q] : 0.f;
+  }
+  uint32_t prow[NB];
+#pragma unroll
+  for (int pt = 0; pt < NB; pt++) prow[pt] = pe_tab ? tok_row[min(m0 + pt * 16 + fr, M - 1)] : 0xffffffffu;
+#pragma unroll
+  for (int pt = 0; pt < NB; pt++) {
+    const uint32_t m = m0 + pt * 16 + fr;
+    if (m < M) {
+      float4 p0 = make_float4(0.f, 0.f, 0.f, 0.f), p1 = p0;
+      if (prow[pt] < pe_rows) {
+        const float* pp = pe_tab + (uint64_t)prow[pt] * ldc + wave * 32 + 8 * fg;
+        p0 = *reinterpret_cast<const float4*>(pp);
+        p1 = *reinterpret_cast<const float4*>(pp + 4);
+      }
+      float* cp = C + (uint64_t)m * ldc + wave * 32 + 8 * fg;
+      // (bias first, then the encoding: the sum the stack's prologue used to form)
+      *reinterpret_cast<float4*>(cp) = make_float4((acc[pt][0][0] + bs[0]) + p0.x, (acc[pt][0][1] + bs[1]) + p0.y, (acc[pt][0][2] + bs[2]) + p0.z, (acc[pt][0][3] + bs[3]) + p0.w);
+      *reinterpret_cast<float4*>(cp + 4) = make_float4((acc[pt][1][0] + bs[4]) + p1.x, (acc[pt][1][1] + bs[5]) + p1.y, (acc[pt][1][2] + bs[6]) + p1.z, (acc[pt][1][3] + bs[7]) + p1.w);
+    }
+  }
+}
+
 template <int NB>
 __global__ __launch_bounds__(512, 4) void k_fc_r(const uint16_t* __restrict__ A, uint32_t lda, Weight W, float* C, uint32_t ldc, uint32_t M,
                                                  const uint32_t* __restrict__ tok_row, const float* __restrict__ pe_tab, uint32_t pe_rows) {
@@ -473,22 +558,8 @@ __global__ __launch_bounds__(512, 4) void k_fc_r(const uint16_t* __restrict__ A,
     *reinterpret_cast<uint4*>(s_a + buf * (FR_ROWS * 64) + sdst0) = r0;   // (all 128 rows are staged whatever G: rows beyond the tile are read for nothing)
     *reinterpret_cast<uint4*>(s_a + buf * (FR_ROWS * 64) + sdst1) = r1;
   };
-  // a quarter k-step = 2 row blocks x 2 column blocks = 4 MFMAs; the fragments of the next quarter are read under them
-  auto rd = [&](uint32_t buf, uint32_t kk, uint32_t g, half8 (&x)[2]) {
-    const uint16_t* t = s_a + buf * (FR_ROWS * 64);
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-      if (g * 2 + i >= (uint32_t)NB) continue;   // (compile time: the loops around are unrolled)
-      const uint32_t r = (g * 2 + i) * 16 + fr;
-      x[i] = *reinterpret_cast<const half8*>(t + r * 64 + (((kk * 4 + fg) ^ (r & 7u)) << 3));
-    }
-  };
-  auto mm = [&](uint32_t g, const half8 (&x)[2], const half8 (&w)[2]) {
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int jt = 0; jt < 2; jt++) if (g * 2 + i < (uint32_t)NB) acc[g * 2 + i][jt] = mma(w[jt], x[i], acc[g * 2 + i][jt]);
-  };
+  auto rd = [&](uint32_t buf, uint32_t kk, uint32_t g, half8 (&x)[2]) { fc_rd<NB>(s_a + buf * (FR_ROWS * 64), kk, g, fr, fg, x); };
+  auto mm = [&](uint32_t g, const half8 (&x)[2], const half8 (&w)[2]) { fc_mm<NB>(acc, g, x, w); };
   // prologue: tile 0 into LDS, tile 1 in flight, weights of k-steps 0, 1
   {
     uint4 t0, t1;
@@ -543,31 +614,110 @@ __global__ __launch_bounds__(512, 4) void k_fc_r(const uint16_t* __restrict__ A,
       }
     }
   }
-  float bs[8];
-  {
-    const float* bp = W.bias + wave * 32 + 8 * fg;
+  fc_epilogue<NB>(acc, W, C, ldc, M, m0, tok_row, pe_tab, pe_rows, wave, fr, fg);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// k_conv_fc — k_conv_m and k_fc_r in one kernel: y2 goes from the conv stack's registers into the FC's LDS tile and never to HBM (S.y2_hi is not touched).
+// One workgroup of 8 waves takes a tile of 128 consecutive tokens through the 31 read rows.  Per read row r, wave w runs conv1 / conv2 for the 16 pairs
+// (token m0 + 16 w + fr, read row r) — cv_conv1 / cv_conv2, the MFMAs and roundings of k_conv_m — and writes the pair's 128 channels as four 16-byte chunks into
+// the tile pair r & 1 ([2 macro-steps][128 rows][64 k], k_fc_r's swizzle: a lane's channels (hs * 2 + sl) * 32 + 8 fg .. + 7 are chunk sl * 4 + fg of macro-step hs);
+// behind ONE barrier every wave runs the FC k-steps 4 r .. 4 r + 3 for its 32 output columns over all row blocks (fc_rd / fc_mm in k_fc_r's order), so each element
+// of x sees the MFMA chain of k_fc_r over k = r * 128 + c: the same bits.  The two tile pairs alternate, so a wave that is through with read row r writes row r + 1
+// while others still read r; nobody can be two rows ahead (the barrier of r + 1).  In flight across the barrier: the FC weight fragments of read row r + 1 (a ring slot is
+// refilled as soon as its k-step's MFMAs are issued) and the receptive-field records / cells of read rows r + 1 and r + 2.  A lane keeps ONE token for the whole tile:
+// its TokCv / TokMeta are fetched once, not once per pair.  Tiles go front to back: what the kernel reads (31 x 16 B per token) and writes (1 KB per token) fits the
+// memory-side cache together at any launch size, there is no y2 tail to catch as in k_fc_r, and k_layers_p reads x front to back.
+// Workgroups never depend on one another; inside one, barriers only.
+// ---------------------------------------------------------------------------------------------------
+constexpr int CF_TM = 128;
+constexpr size_t CONV_FC_SHM = CONV_M_SHM + (size_t)2 * 2 * FR_ROWS * 64 * 2;   // the conv stack's tables + two tile pairs
+static_assert(CONV_M_SHM % 1024 == 0, "the FC tiles behind the conv tables keep k_fc_r's alignment");
+
+template <bool RF>
+__global__ __launch_bounds__(512) void k_conv_fc(ModelDev M, BatchDev B, ModelScratch S, uint32_t n_tok) {
+  constexpr int NB = CF_TM / 16;
+  extern __shared__ __attribute__((aligned(1024))) unsigned char smem_cf[];
+  const CvLds L = cv_lds(smem_cf);
+  uint16_t* s_t = reinterpret_cast<uint16_t*>(smem_cf + CONV_M_SHM);   // [2 (r & 1)][2 macro-steps][128][64]
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const uint32_t fr = lane & 15, fg = lane >> 4;
+  const uint32_t m0 = blockIdx.x * CF_TM;
+  cv_fill_lds<512>(L, M, tid);
+  half8 w1[3][2][2];
+  cv_load_w1(M, lane, w1);
+  // the lane's token (clamped: the rows of a partial tile beyond n_tok repeat the last token and are never stored)
+  const uint32_t tok = min(m0 + wave * 16 + fr, n_tok - 1u);
+  const TokCv tcv = S.tok_cv[tok];
+  uint32_t ld = 0, trow = 0;
+  if constexpr (!RF) { const TokMeta tf = S.tok_meta[tok]; ld = tf.plane_ld; trow = tf.tok_row; }
+  // the lane's four chunks of a tile pair: row 16 w + fr, chunk (sl * 4 + fg) ^ (row & 7), macro-step hs at + hs * 128 * 64
+  const uint32_t trw = wave * 16 + fr;
+  const uint32_t tdst[2] = {trw * 64 + ((fg ^ (trw & 7u)) << 3), trw * 64 + (((4 + fg) ^ (trw & 7u)) << 3)};
+  const Weight& W = M.fc;
+  const uint32_t nks = W.K >> 5;
+  const uint16_t* gw = W.ph16 + ((uint64_t)(wave * 2) * nks * 64 + lane) * 8;
+  auto wfrag = [&](uint32_t jt, uint32_t ks) -> half8 { return *reinterpret_cast<const half8*>(gw + (uint64_t)(jt * nks + ks) * 512); };
+  f32x4 acc[NB][2];
 #pragma unroll
-    for (int q = 0; q < 8; q++) bs[q] = W.bias ? bp[q] : 0.f;
-  }
-  uint32_t prow[NB];
+  for (int pt = 0; pt < NB; pt++)
 #pragma unroll
-  for (int pt = 0; pt < NB; pt++) prow[pt] = pe_tab ? tok_row[min(m0 + pt * 16 + fr, M - 1)] : 0xffffffffu;
+    for (int jt = 0; jt < 2; jt++) acc[pt][jt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  half8 wr[4][2];   // the four k-steps of a read row
 #pragma unroll
-  for (int pt = 0; pt < NB; pt++) {
-    const uint32_t m = m0 + pt * 16 + fr;
-    if (m < M) {
-      float4 p0 = make_float4(0.f, 0.f, 0.f, 0.f), p1 = p0;
-      if (prow[pt] < pe_rows) {
-        const float* pp = pe_tab + (uint64_t)prow[pt] * ldc + wave * 32 + 8 * fg;
-        p0 = *reinterpret_cast<const float4*>(pp);
-        p1 = *reinterpret_cast<const float4*>(pp + 4);
-      }
-      float* cp = C + (uint64_t)m * ldc + wave * 32 + 8 * fg;
-      // (bias first, then the encoding: the sum the stack's prologue used to form)
-      *reinterpret_cast<float4*>(cp) = make_float4((acc[pt][0][0] + bs[0]) + p0.x, (acc[pt][0][1] + bs[1]) + p0.y, (acc[pt][0][2] + bs[2]) + p0.z, (acc[pt][0][3] + bs[3]) + p0.w);
-      *reinterpret_cast<float4*>(cp + 4) = make_float4((acc[pt][1][0] + bs[4]) + p1.x, (acc[pt][1][1] + bs[5]) + p1.y, (acc[pt][1][2] + bs[6]) + p1.z, (acc[pt][1][3] + bs[7]) + p1.w);
+  for (int k = 0; k < 4; k++)
+#pragma unroll
+    for (int jt = 0; jt < 2; jt++) wr[k][jt] = wfrag(jt, k);
+  CvCells cur = cv_finish(cv_pack<RF>(cv_load_raw<RF>(B, tcv, ld, trow, 0)), tcv);
+  uint4 ra = cv_pack<RF>(cv_load_raw<RF>(B, tcv, ld, trow, 1));   // read row r + 1, as four words
+  __syncthreads();   // the conv tables
+  for (uint32_t r = 0; r < HERRO_ROWS; r++) {
+    // read row r + 2: a record is requested here; the ten cell bytes of the planes path (ten registers in flight) behind the conv phase, whose registers they would spill
+    CvRaw rb;
+    if constexpr (RF) rb = cv_load_raw<RF>(B, tcv, ld, trow, min(r + 2u, (uint32_t)HERRO_ROWS - 1u));
+    uint16_t* tp = s_t + (r & 1u) * (2 * FR_ROWS * 64);
+    half8 y1f[1][6];
+    cv_conv1(L, w1, cur, fg, y1f[0]);
+#pragma unroll
+    for (int hs = 0; hs < 2; hs++) {
+      half8 y2h[1][2];
+      cv_conv2<1>(L, hs, y1f, lane, fg, y2h);
+#pragma unroll
+      for (int sl = 0; sl < 2; sl++) *reinterpret_cast<half8*>(tp + hs * (FR_ROWS * 64) + tdst[sl]) = y2h[0][sl];
     }
+    // the tile pair of r is complete; the other pair is no longer read (every wave is past the FC of r - 1).  NOT __syncthreads(): its fence waits for every load in flight
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if constexpr (!RF) rb = cv_load_raw<RF>(B, tcv, ld, trow, min(r + 2u, (uint32_t)HERRO_ROWS - 1u));
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+      const uint16_t* t = tp + u * (FR_ROWS * 64);
+      constexpr int G = NB / 2;
+      half8 x[2], xn[2];
+      fc_rd<NB>(t, 0, 0, fr, fg, x);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int q = 0; q < 2 * G; q++) {   // q = G kk + g
+        if (q < 2 * G - 1) fc_rd<NB>(t, (q + 1) / G, (q + 1) % G, fr, fg, xn);
+        __builtin_amdgcn_sched_barrier(0);
+        const int ws = u * 2 + q / G;
+        fc_mm<NB>(acc, q % G, x, wr[ws]);
+        __builtin_amdgcn_sched_barrier(0);
+        if (q % G == G - 1) {   // the k-step's MFMAs have been issued: the slot takes the same k-step of the next read row
+          const uint32_t kn = min(r * 4 + 4 + ws, nks - 1);
+#pragma unroll
+          for (int jt = 0; jt < 2; jt++) wr[ws][jt] = wfrag(jt, kn);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; i++) x[i] = xn[i];
+      }
+    }
+    cur = cv_finish(ra, tcv);
+    ra = cv_pack<RF>(rb);
   }
+  // (the lane index once more, from the execution mask: fr / fg of the prologue would otherwise be held, or spilled, across the loop for the epilogue alone)
+  const uint32_t le = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  fc_epilogue<NB>(acc, W, S.x, M.h.d_model, n_tok, m0, S.tok_row, M.pe_tab, M.pe_rows, wave, le & 15u, le >> 4);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1387,9 +1537,28 @@ int model_h_half_tiles(const ModelDev& M) {
   return model_h_supported(M) ? mode : 0;
 }
 
+// The front end of a launch of n_tok tokens: true — k_conv_fc (tiles of `tile` tokens, one workgroup per compute unit); false — k_conv_m, then k_fc_r.
+// From profiles/conv_fc_ab.txt (one MI355X, 256 compute units, both paths in one call), not from an estimate:
+//     launch                    k_conv_m + k_fc_r    k_conv_fc               step
+//     1792 windows, 27 k rows        157 - 160 us    133 us (212 tiles)      - 6.6 %   (measured with the rule below in force: it confirmed its one-round range)
+//     2560 windows, 38.7 k rows      230 - 234 us    238 us (303 tiles)      no gain (inside the parent's spread)
+//     4096 windows, 62 k rows        341 - 348 us    265 - 266 us (484)      - 7.4 %
+// The fused kernel runs in ROUNDS of one tile per compute unit and a round costs the same whether 47 or 228 units take part in it — 119 us per round at
+// the smaller launch, 133 at the larger (every unit streaming the FC weights) —, while the two kernels' time follows the rows: the line through the two
+// launches above is 44 us + 4.85 us per 1000 rows.  The fused kernel is chosen where rounds x 133 us stays below 85 % of that line, a margin several times
+// the run-to-run spread of the table: 265 against 293 at 4096 windows (taken), 266 against 197 at 2560 (two kernels, as measured); in between, where nothing
+// was measured, the rule amounts to a last round that is about 70 % full (23.2 - 32.7 k rows, 55.5 - 65.5 k, 87.7 - 98.3 k ...).  Both times scale with the compute units of the device.
+bool conv_fc_faster(uint32_t n_tok, uint32_t n_cu, uint32_t tile) {
+  const uint32_t tiles = (n_tok + tile - 1) / tile, rounds = (tiles + n_cu - 1) / n_cu;
+  const double t_fused = 133.0 * rounds * ((double)tile / CF_TM);
+  const double t_two = 44.0 + 4.85e-3 * n_tok * (256.0 / n_cu);
+  return t_fused <= 0.85 * t_two;
+}
+
 // B must be tileable (windows of <= 64 informative rows in B.tile_tok0 / _q, windows of 65 .. 64 * 8 rows on sibling tiles, B.tile_tok0_b) —
 // herro_job_infer sends still larger windows through the layer-by-layer kernels of model.hip.  terms: 2 (precision 4), 1 (precision 5), 3 (6), 21 (7: FF single), 12 (8: proj single).
-void launch_model_h(const ModelDev& M, const BatchDev& B, const ModelScratch& S, int terms, hipStream_t st, KernelTimer* tm) {
+// conv_fc: -1 the rule above, 0 k_conv_m + k_fc_r, 1 k_conv_fc wherever the shapes allow (herro_debug_set_conv_fc)
+void launch_model_h(const ModelDev& M, const BatchDev& B, const ModelScratch& S, int terms, hipStream_t st, KernelTimer* tm, int conv_fc) {
   const uint32_t N = B.n_tok;
   if (N == 0 || B.n_tiles + B.n_tiles_q + B.n_tiles_b == 0) return;
   const ModelHyper& h = M.h;
@@ -1440,7 +1609,22 @@ void launch_model_h(const ModelDev& M, const BatchDev& B, const ModelScratch& S,
       default: hipLaunchKernelGGL(k_fc_r<8>, grid, dim3(512), FC_R_SHM, st, A, lda, M.fc, C, h.d_model, n, rows, M.pe_tab, M.pe_rows);
     }
   };
-  if (chunk_tok && N > chunk_tok) {
+  static const int env_cf = ab_env("HERRO_CONV_FC", -2);   // (A/B builds) overrides the context's switch
+  const int cf_mode = env_cf >= -1 ? env_cf : conv_fc;
+  const bool cf_can = h.rows == HERRO_ROWS && M.fc.K == (uint32_t)HERRO_ROWS * HC2 && M.fc.N == 256 && h.d_model == 256;   // the shapes k_conv_fc is written for
+  if (cf_can && (cf_mode > 0 || (cf_mode < 0 && !chunk_tok && conv_fc_faster(N, n_cu, CF_TM)))) {
+    // a span of its own: bench.py's roofline sets conv_fused's flops against conv_fused's time
+    KT_BEGIN(tm, "conv_fc", st);
+    const dim3 grid((N + CF_TM - 1) / CF_TM);
+    if (B.rf_q) {
+      opt_in_lds(reinterpret_cast<const void*>(k_conv_fc<true>), CONV_FC_SHM);
+      hipLaunchKernelGGL(k_conv_fc<true>, grid, dim3(512), CONV_FC_SHM, st, M, B, S, N);
+    } else {
+      opt_in_lds(reinterpret_cast<const void*>(k_conv_fc<false>), CONV_FC_SHM);
+      hipLaunchKernelGGL(k_conv_fc<false>, grid, dim3(512), CONV_FC_SHM, st, M, B, S, N);
+    }
+    KT_END(tm, st);
+  } else if (chunk_tok && N > chunk_tok) {
     KT_BEGIN(tm, "conv_fused", st);   // (the span carries both kernels of every chunk)
     for (uint32_t t0 = 0; t0 < N; t0 += chunk_tok) { conv(t0, std::min(N, t0 + chunk_tok)); fc(t0, std::min(N, t0 + chunk_tok)); }
     KT_END(tm, st);

@@ -265,6 +265,10 @@ int64_t herro_debug_job_array(herro_job* job, int which, const void** ptr, uint3
  * by tests/test_gpu_lean.py.  herro_debug_job_rf copies the 16-byte receptive-field records of window w (after herro_job_infer:
  * n_supported x 31 records, bytes 0..7 tokens / 8..15 qualities of rows sup_row - half .. ) and returns their number (<0: error). */
 int herro_debug_set_featurize_planes(herro_ctx* ctx, int on);
+/* Test hook for the two front ends of the f16 model (precisions 4 .. 8; csrc/model_h.hip): the conv stack and the FC projection as two kernels with the conv
+ * output in HBM between them (k_conv_m, k_fc_r), or as one kernel that keeps it in LDS (k_conv_fc).  Both give the same bits.  mode -1 (default): chosen per
+ * launch from the launch size (conv_fc_faster); 0: two kernels; 1: one kernel wherever the model's shapes allow it (another conv stack keeps its own path). */
+int herro_debug_set_conv_fc(herro_ctx* ctx, int mode);
 /* Test hooks for the two ways a job's windows and descriptors are built (herro_job_create): on the device behind the CIGAR scan (csrc/build_dev.hip, the
  * default since round 6) or by the host from the scan's cut records (rounds 3-5; still what runs when the device meets anything it does not settle itself —
  * a text the scan kernel flags, an input the reference panics on — and what words the error).  herro_debug_set_host_build(ctx, 1) selects the host build for
