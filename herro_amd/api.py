@@ -2,6 +2,7 @@
 missing or no GPU is present — there is no CPU fallback in this package."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 from dataclasses import dataclass
@@ -27,7 +28,7 @@ EXPORTS = [
     "herro_paf_parse", "herro_oec_read", "herro_paf_n_targets", "herro_paf_target_ids", "herro_paf_aln_off",
     "herro_paf_alignments", "herro_paf_free", "herro_name_index_create", "herro_name_index_free", "herro_paf_parse_indexed",
     "herro_oec_read_indexed", "herro_paf_parse_view", "herro_debug_host_ctx", "herro_debug_job_array", "herro_debug_tile_plan", "herro_debug_tile_plan_sib", "herro_debug_launch_plan",
-    "herro_debug_set_featurize_planes", "herro_debug_set_conv_fc", "herro_debug_set_host_build", "herro_debug_job_dev_built", "herro_debug_job_rf", "herro_debug_job_cwd", "herro_debug_job_set_base_logits", "herro_debug_job_rf_fused", "herro_debug_job_rf_left", "herro_debug_e4m3", "herro_debug_sib_fault", "herro_debug_sib_retries", "herro_debug_base_row_votes", "herro_debug_vote5",
+    "herro_debug_set_featurize_planes", "herro_debug_set_conv_fc", "herro_debug_set_front_cu", "herro_debug_front_last", "herro_debug_front_end_plan", "herro_debug_set_host_build", "herro_debug_job_dev_built", "herro_debug_job_rf", "herro_debug_job_cwd", "herro_debug_job_set_base_logits", "herro_debug_job_rf_fused", "herro_debug_job_rf_left", "herro_debug_e4m3", "herro_debug_sib_fault", "herro_debug_sib_retries", "herro_debug_base_row_votes", "herro_debug_vote5",
     "herro_pool_create", "herro_pool_destroy", "herro_pool_last_error", "herro_pool_size", "herro_pool_ctx", "herro_pool_set_reads", "herro_pool_load_model",
     "herro_pool_correct", "herro_pool_result", "herro_pool_groups_taken", "herro_pool_skipped", "herro_debug_pool_fake", "herro_job_create_status", "herro_host_register", "herro_host_unregister", "herro_debug_zero_copy_jobs",
     "herro_fastx_read", "herro_reads_count", "herro_reads_seq", "herro_reads_qual", "herro_reads_off", "herro_reads_ids",
@@ -314,6 +315,9 @@ def lib():
         except AttributeError:
             if not os.environ.get("HERRO_LIB"):
                 raise
+        L.herro_debug_set_front_cu.argtypes = [vp, u32]
+        L.herro_debug_front_last.argtypes = [vp, vp]
+        L.herro_debug_front_end_plan.argtypes = [u32, u32, u32, i32, vp]
         L.herro_debug_job_dev_built.argtypes = [vp]
         L.herro_debug_base_row_votes.argtypes = [vp, vp, vp, u32, vp, vp]
         L.herro_debug_vote5.restype = u32
@@ -416,6 +420,26 @@ def debug_launch_plan(nsup, Lf, tgt_win_off, batch_size: int, batch_mode: int = 
     if n < 0:
         raise HerroError(int(n), "herro_debug_launch_plan")
     return int(n), launch[:len(ns)], pos[:len(ns)], lmax[:len(ns)]
+
+
+FrontPlan = collections.namedtuple("FrontPlan", "fused fc_rows fc_grid conv_grid conv_units")
+
+
+def debug_front_end_plan(n_tok: int, n_cu: int = 256, mode: int = -1) -> FrontPlan:
+    """The front end of a launch of n_tok tokens on n_cu compute units (host only, herro_debug_front_end_plan; csrc/infer_plan.h front_end_plan):
+    fused — k_conv_fc on fc_grid tiles of fc_rows tokens; else k_conv_m on conv_grid workgroups over conv_units blocks of 16 pairs, then k_fc_r on
+    fc_grid tiles of fc_rows rows.  mode: -1 the selection rule, 0 two kernels, 1 k_conv_fc."""
+    out = debug_front_end_plans(n_tok, 1, n_cu, mode)[0]
+    return FrontPlan(bool(out[0]), *(int(x) for x in out[1:]))
+
+
+def debug_front_end_plans(n_tok: int, count: int, n_cu: int = 256, mode: int = -1) -> np.ndarray:
+    """... of the launches of n_tok, n_tok + 1, ... n_tok + count - 1 tokens: [count, 5] u32, the columns in FrontPlan's order"""
+    out = np.zeros((max(count, 1), 5), np.uint32)
+    rc = lib().herro_debug_front_end_plan(n_tok, count, n_cu, mode, out.ctypes.data)
+    if rc < 0:
+        raise HerroError(int(rc), "herro_debug_front_end_plan")
+    return out[:count]
 
 
 class Pool:
@@ -591,6 +615,17 @@ class Context:
     def conv_fc(self, mode: int):
         """test hook: front end of the f16 model from now on: -1 chosen per launch, 0 k_conv_m + k_fc_r, 1 k_conv_fc wherever its shapes allow"""
         self._chk(self._l.herro_debug_set_conv_fc(self.h, int(mode)))
+
+    def front_cu(self, n_cu: int):
+        """test hook: the front end (conv stack + FC projection) plans its launches for n_cu compute units from now on, 0 the device's own;
+        the encoder stack's tile plan keeps the device's count"""
+        self._chk(self._l.herro_debug_set_front_cu(self.h, int(n_cu)))
+
+    def front_last(self) -> "FrontPlan":
+        """test hook: what the front end of this context's last model launch sent out"""
+        out = np.zeros(5, np.uint32)
+        self._chk(self._l.herro_debug_front_last(self.h, out.ctypes.data))
+        return FrontPlan(bool(out[0]), *(int(x) for x in out[1:]))
 
     def register_host(self, arr: np.ndarray):
         """herro_host_register: jobs whose CIGAR pointers lie in `arr` (a contiguous u8 array the caller keeps alive) are created zero-copy."""

@@ -116,6 +116,8 @@ struct herro_ctx {
   // built when somebody asks for them.  HERRO_FEATURIZE_PLANES=1 (or herro_debug_set_featurize_planes): the planes path of rounds 3-4 (A/B, parity tests)
   bool lean = [] { const char* e = getenv("HERRO_FEATURIZE_PLANES"); return !e || atoi(e) == 0; }();
   int conv_fc = -1;   // front end of the f16 model (launch_model_h): -1 chosen per launch (conv_fc_faster), 0 k_conv_m + k_fc_r, 1 k_conv_fc wherever its shapes allow (herro_debug_set_conv_fc)
+  uint32_t front_cu = 0;   // herro_debug_set_front_cu: the compute units the FRONT END plans for (front_end_plan), 0 = n_cu; plan_tiles and LaunchCfg never see it
+  FrontEndPlan front_ran{false, 0, 0, 0, 0};   // what the front end of the last model launch sent out (herro_debug_front_last)
   bool tile_packing = herro::ab_env("HERRO_TILE_PACK", 1) != 0;  // 0 (A/B builds): windows in batch order
   uint64_t* d_words = nullptr;
   uint32_t* d_p0 = nullptr;

@@ -276,9 +276,10 @@ __global__ void k_clock_probe(unsigned long long* out, uint32_t spin) {
 static void run_model(herro_ctx* ctx, const BatchDev& B, bool tiled) {
   if (B.n_tok == 0) return;
   const int p = ctx->precision;
-  if (!tiled) { launch_model(ctx->M, B, ctx->S, (p == 1 || p >= 4) ? 3 : p, ctx->stream, &ctx->timer); return; }
-  if (p >= 4) launch_model_h(ctx->M, B, ctx->S, p == 4 ? 2 : (p == 6 ? 3 : (p == 7 ? 21 : (p == 8 ? 12 : 1))), ctx->stream, &ctx->timer, ctx->conv_fc);
-  else launch_model(ctx->M, B, ctx->S, p, ctx->stream, &ctx->timer);
+  const uint32_t cu = ctx->front_cu ? ctx->front_cu : ctx->n_cu;   // the front end's own count (herro_debug_set_front_cu); the tile plan took ctx->n_cu
+  if (!tiled) { launch_model(ctx->M, B, ctx->S, (p == 1 || p >= 4) ? 3 : p, ctx->stream, &ctx->timer, cu, &ctx->front_ran); return; }
+  if (p >= 4) launch_model_h(ctx->M, B, ctx->S, p == 4 ? 2 : (p == 6 ? 3 : (p == 7 ? 21 : (p == 8 ? 12 : 1))), ctx->stream, &ctx->timer, cu, ctx->conv_fc, &ctx->front_ran);
+  else launch_model(ctx->M, B, ctx->S, p, ctx->stream, &ctx->timer, cu, &ctx->front_ran);
 }
 
 extern "C" {
@@ -2639,6 +2640,30 @@ int herro_debug_set_featurize_planes(herro_ctx* ctx, int on) {
 int herro_debug_set_conv_fc(herro_ctx* ctx, int mode) {
   if (!ctx || mode < -1 || mode > 1) return HERRO_E_INVALID;
   ctx->conv_fc = mode;
+  return HERRO_OK;
+}
+
+// The front end's view of the device (front_end_plan, infer_plan.h): n_cu compute units from now on, 0 the device's own.  The encoder stack's tile plan
+// (plan_tiles, LaunchCfg::n_cu) keeps ctx->n_cu: its tiles, and so its bits, stay where they are.
+int herro_debug_set_front_cu(herro_ctx* ctx, uint32_t n_cu) {
+  if (!ctx || n_cu > (1u << 20)) return HERRO_E_INVALID;
+  ctx->front_cu = n_cu;
+  return HERRO_OK;
+}
+// out[5] = fused, FC tile rows, FC grid, conv grid, conv units of the front end of the context's last model launch (FrontEndPlan)
+int herro_debug_front_last(const herro_ctx* ctx, uint32_t* out) {
+  if (!ctx || !out) return HERRO_E_INVALID;
+  const FrontEndPlan& p = ctx->front_ran;
+  out[0] = p.fused; out[1] = p.fc_rows; out[2] = p.fc_grid; out[3] = p.conv_grid; out[4] = p.conv_units;
+  return HERRO_OK;
+}
+// front_end_plan without a device or a context, for the `count` launches of n_tok, n_tok + 1 ... tokens: out[count][5] as above
+int herro_debug_front_end_plan(uint32_t n_tok, uint32_t count, uint32_t n_cu, int mode, uint32_t* out) {
+  if (!out || n_tok == 0 || count == 0 || n_tok + count < n_tok || n_cu == 0 || n_cu > (1u << 20) || mode < -1 || mode > 1) return HERRO_E_INVALID;
+  for (uint32_t i = 0; i < count; i++, out += 5) {
+    const FrontEndPlan p = front_end_plan(n_tok + i, n_cu, mode);
+    out[0] = p.fused; out[1] = p.fc_rows; out[2] = p.fc_grid; out[3] = p.conv_grid; out[4] = p.conv_units;
+  }
   return HERRO_OK;
 }
 

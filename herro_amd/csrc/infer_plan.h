@@ -1,6 +1,7 @@
 // infer_plan.h — the launch plan of a model pass, host only (plain C++17 over integer arrays: no HIP call, no context): which windows form a batch
 // (plan_batches), which batches share a set of launches (group_batches), and per group the fused / unfused split, the token-tile plan, the window order and
-// the descriptor image the kernels read (build_launch: herro_job_infer and herro_model_forward).  Tested without a device through herro_debug_launch_plan.
+// the descriptor image the kernels read (build_launch: herro_job_infer and herro_model_forward); and, at the end, what the front end of a launch makes of its
+// tokens and the compute units of the device (front_end_plan).  Tested without a device through herro_debug_launch_plan and herro_debug_front_end_plan.
 #pragma once
 
 #include <algorithm>
@@ -298,4 +299,54 @@ static void build_launch(const std::vector<PlanWin>& wins, const LaunchCfg& c, s
     o.n_tiles_b = (uint32_t)plan.grp.size(); o.tiles_b = image_put(image, plan.tiles_b); o.grp = image_put(image, plan.grp);
     out.push_back(o);
   }
+}
+
+// ---- the front end of one launch (conv stack + FC projection: launch_model_h of model_h.hip, launch_front_generic of model.hip) --------------------------
+// Everything the front end decides from the launch's tokens and the compute units of the device, in one place: which kernels, their grids, the FC tile height.
+static constexpr uint32_t FRONT_ROWS = 31;         // read rows of a token (HERRO_ROWS)
+static constexpr uint32_t FRONT_FUSED_TILE = 128;  // tokens of a k_conv_fc tile (CF_TM)
+
+// The front end of a launch of n_tok tokens: true — k_conv_fc (tiles of `tile` tokens, one workgroup per compute unit); false — k_conv_m, then k_fc_r.
+// From profiles/conv_fc_ab.txt (one MI355X, 256 compute units, both paths in one call), not from an estimate:
+//     launch                    k_conv_m + k_fc_r    k_conv_fc               step
+//     1792 windows, 27 k rows        157 - 160 us    133 us (212 tiles)      - 6.6 %   (measured with the rule below in force: it confirmed its one-round range)
+//     2560 windows, 38.7 k rows      230 - 234 us    238 us (303 tiles)      no gain (inside the parent's spread)
+//     4096 windows, 62 k rows        341 - 348 us    265 - 266 us (484)      - 7.4 %
+// The fused kernel runs in ROUNDS of one tile per compute unit and a round costs the same whether 47 or 228 units take part in it — 119 us per round at
+// the smaller launch, 133 at the larger (every unit streaming the FC weights) —, while the two kernels' time follows the rows: the line through the two
+// launches above is 44 us + 4.85 us per 1000 rows.  The fused kernel is chosen where rounds x 133 us stays below 85 % of that line, a margin several times
+// the run-to-run spread of the table: 265 against 293 at 4096 windows (taken), 266 against 197 at 2560 (two kernels, as measured); in between, where nothing
+// was measured, the rule amounts to a last round that is about 70 % full (23.2 - 32.7 k rows, 55.5 - 65.5 k, 87.7 - 98.3 k ...).  Both times scale with the compute units of the device.
+inline bool conv_fc_faster(uint32_t n_tok, uint32_t n_cu, uint32_t tile) {
+  const uint32_t tiles = (n_tok + tile - 1) / tile, rounds = (tiles + n_cu - 1) / n_cu;
+  const double t_fused = 133.0 * rounds * ((double)tile / FRONT_FUSED_TILE);
+  const double t_two = 44.0 + 4.85e-3 * n_tok * (256.0 / n_cu);
+  return t_fused <= 0.85 * t_two;
+}
+
+// k_conv_m takes blocks ("units") of 16 (token, read row) pairs, one per wave and trip of its grid-stride loop, four waves per workgroup, three workgroups
+// per compute unit; k_conv_w of the generic front end takes one tile per workgroup and trip, two workgroups per compute unit.
+inline uint32_t conv_m_grid(uint32_t n_units, uint32_t n_cu) { return std::min<uint32_t>((n_units + 3) / 4, 3 * n_cu); }
+inline uint32_t conv_w_grid(uint32_t n_tiles, uint32_t n_cu) { return std::min<uint32_t>(n_tiles, 2 * n_cu); }
+
+// fused: k_conv_fc on fc_grid tiles of fc_rows (= FRONT_FUSED_TILE) tokens, conv_grid 0.  Otherwise k_conv_m on conv_grid workgroups over conv_units units,
+// then k_fc_r<fc_rows / 16> on fc_grid workgroups.  (The generic front end reports its k_conv_w launch in conv_grid / conv_units and leaves the rest 0.)
+struct FrontEndPlan { bool fused; uint32_t fc_rows, fc_grid, conv_grid, conv_units; };
+// FC tile height (16-row blocks, 4 .. 8) of k_fc_r over n tokens: the one that leaves the busiest compute unit the fewest rows — two workgroups fit a unit, a third
+// would wait for a slot —, the taller one on a tie (every workgroup streams the whole weight matrix: fewer of them, less L2 traffic).
+inline uint32_t fc_tile_blocks(uint32_t n, uint32_t n_cu) {
+  auto busiest = [&](uint32_t rows) { const uint32_t wg = (n + rows - 1) / rows; return (uint64_t)((wg + n_cu - 1) / n_cu) * rows + (wg > 2 * n_cu ? 1u << 20 : 0u); };
+  uint32_t nb = 8;
+  for (uint32_t b = 7; b >= 4; b--) if (busiest(16u * b) < busiest(16u * nb)) nb = b;
+  return nb;
+}
+// Tokens [t0, t0 + n_tok) of a launch, t0 a multiple of 16 (so that its first pair opens a unit; 0 but for the chunked A/B runs).  mode: -1 the rule
+// (conv_fc_faster), 0 the two kernels, 1 k_conv_fc; force_nb: a tile height that replaces the chosen one (A/B builds), 0 none.
+inline FrontEndPlan front_end_plan(uint32_t n_tok, uint32_t n_cu, int mode = -1, uint32_t force_nb = 0, uint32_t t0 = 0) {
+  n_cu = std::max(n_cu, 1u);
+  if (mode > 0 || (mode < 0 && conv_fc_faster(n_tok, n_cu, FRONT_FUSED_TILE)))
+    return FrontEndPlan{true, FRONT_FUSED_TILE, (n_tok + FRONT_FUSED_TILE - 1) / FRONT_FUSED_TILE, 0, 0};
+  const uint32_t nb = force_nb ? force_nb : fc_tile_blocks(n_tok, n_cu);
+  const uint32_t units = (uint32_t)(((uint64_t)(t0 + n_tok) * FRONT_ROWS + 15) / 16) - t0 / 16 * FRONT_ROWS;
+  return FrontEndPlan{false, 16 * nb, (n_tok + 16 * nb - 1) / (16 * nb), conv_m_grid(units, n_cu), units};
 }

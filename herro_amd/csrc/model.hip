@@ -1739,7 +1739,7 @@ __global__ __launch_bounds__(512) void k_layers(ModelDev M, BatchDev B, ModelScr
 
 // The front of the model in bf16x3 for ANY conv stack of the family: token table, embedding + conv1 + conv2, the projection over the 31 rows, the position
 // term -> S.x (f32).  Used by launch_model_s below and (round 6) by launch_model_h when a model has the f16 stack's encoder shapes but another conv stack.
-void launch_front_generic(const ModelDev& M, const BatchDev& B, const ModelScratch& S, hipStream_t st, KernelTimer* tm) {
+void launch_front_generic(const ModelDev& M, const BatchDev& B, const ModelScratch& S, hipStream_t st, KernelTimer* tm, uint32_t n_cu, FrontEndPlan* ran) {
   const uint32_t N = B.n_tok;
   const ModelHyper& h = M.h;
   const uint32_t D = h.d_model;
@@ -1747,11 +1747,14 @@ void launch_front_generic(const ModelDev& M, const BatchDev& B, const ModelScrat
   hipLaunchKernelGGL(k_build_tokens, dim3(B.n_win), dim3(64), 0, st, B, S);
   KT_END(tm, st);
   const uint32_t P = 4 * (h.kw / 2) + 1;
+  if (ran) *ran = FrontEndPlan{false, 0, 0, 0, 0};
   if (h.c2 == FC2 && h.c1 == 64 && h.kw == 3) {
     const uint32_t n_tiles = (N * HERRO_ROWS + CW_TP - 1) / CW_TP;
     KT_BEGIN(tm, "conv_fused", st);
-    hipLaunchKernelGGL(k_conv_w, dim3(std::min<uint32_t>(n_tiles, 512u)), dim3(256), CW_SHM, st, M, B, S, N * HERRO_ROWS, n_tiles);
+    const uint32_t grid = conv_w_grid(n_tiles, std::max(n_cu, 1u));   // a stride loop over the tiles, two workgroups per compute unit
+    hipLaunchKernelGGL(k_conv_w, dim3(grid), dim3(256), CW_SHM, st, M, B, S, N * HERRO_ROWS, n_tiles);
     KT_END(tm, st);
+    if (ran) *ran = FrontEndPlan{false, 0, 0, grid, n_tiles};
   } else {
     const size_t shm = (size_t)(h.kw * 12 * h.c1 + h.kw * h.c1 + h.c1 + HERRO_ROWS * P) * 4 + (size_t)HERRO_ROWS * P * 4;
     KT_BEGIN(tm, "patch_conv1", st);
@@ -1772,11 +1775,11 @@ void launch_front_generic(const ModelDev& M, const BatchDev& B, const ModelScrat
   KT_END(tm, st);
 }
 
-static void launch_model_s(const ModelDev& M, const BatchDev& B, const ModelScratch& S, bool fused, hipStream_t st, KernelTimer* tm) {
+static void launch_model_s(const ModelDev& M, const BatchDev& B, const ModelScratch& S, bool fused, hipStream_t st, KernelTimer* tm, uint32_t n_cu, FrontEndPlan* ran) {
   const uint32_t N = B.n_tok;
   const ModelHyper& h = M.h;
   const uint32_t D = h.d_model;
-  launch_front_generic(M, B, S, st, tm);
+  launch_front_generic(M, B, S, st, tm, n_cu, ran);
   if (fused && B.n_tiles && D == 256 && h.n_heads == 8 && h.d_ff % 256 == 0 && model_default_variant(M)) {
     opt_in_dynamic_lds(reinterpret_cast<const void*>(k_layers), LAYERS_SHM);
     KT_BEGIN(tm, "layers_fused", st);
@@ -1832,11 +1835,12 @@ static void launch_model_s(const ModelDev& M, const BatchDev& B, const ModelScra
 }
 
 void launch_model(const ModelDev& M, const BatchDev& B, const ModelScratch& S, int precision,
-                  hipStream_t st, KernelTimer* tm) {
+                  hipStream_t st, KernelTimer* tm, uint32_t n_cu, FrontEndPlan* ran) {
   const uint32_t N = B.n_tok;
   if (N == 0) return;
+  if (ran) *ran = FrontEndPlan{false, 0, 0, 0, 0};   // (the kernels below take no grid from n_cu: nothing to report)
   if (precision == 1 || precision == 3) {  // 3: bf16x3, layer by layer (the fused stack's fallback, selectable for A/B)
-    launch_model_s(M, B, S, precision == 1, st, tm);
+    launch_model_s(M, B, S, precision == 1, st, tm, n_cu, ran);
     return;
   }
   const ModelHyper& h = M.h;

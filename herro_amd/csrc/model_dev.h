@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "infer_plan.h"
 #include "job_dev.h"
 
 namespace herro {
@@ -162,17 +163,17 @@ struct ModelScratch {  // sized for n_tok tokens
   uint32_t* sib_err;
 };
 
+// n_cu: the compute units the front end plans its grids for (infer_plan.h, front_end_plan); *ran (may be null) receives what the front end launched
 void launch_model(const ModelDev& M, const BatchDev& B, const ModelScratch& S, int precision,
-                  hipStream_t st, KernelTimer* tm);
+                  hipStream_t st, KernelTimer* tm, uint32_t n_cu, FrontEndPlan* ran = nullptr);
 // f16-operand kernels (model_h.hip): terms = 2 -> precision 4, terms = 1 -> precision 5, terms = 3 -> precision 6 (f16 + an e4m3 remainder term), 21 -> precision 7 (proj on two
 // terms, FF1 / FF2 on one), 12 -> precision 8 (proj on one, FF on two).  B must be tiled (n_tiles > 0).
 bool model_h_supported(const ModelDev& M);        // the f16 encoder stack serves the model (d_model 256, 8 heads of 32, d_ff % 256 == 0, the default variant): precisions 4 .. 8 exist
 bool model_h_conv_supported(const ModelDev& M);   // ... and the f16 conv / FC kernels too (kw 3, 64 -> 128 channels); otherwise the bf16x3 front end of model.hip feeds the f16 stack
-void launch_front_generic(const ModelDev& M, const BatchDev& B, const ModelScratch& S, hipStream_t st, KernelTimer* tm);   // model.hip
+void launch_front_generic(const ModelDev& M, const BatchDev& B, const ModelScratch& S, hipStream_t st, KernelTimer* tm, uint32_t n_cu, FrontEndPlan* ran = nullptr);   // model.hip
 bool model_h_f8_supported(const ModelDev& M);   // ... and every layer's proj / ff1 / ff2 has its e4m3 copy
 int model_h_half_tiles(const ModelDev& M);   // qmode of plan_tiles: 0 no 32-token tiles, 1 for a short last round (default), 2 for every small window (HERRO_LAYERS_Q)
-bool conv_fc_faster(uint32_t n_tok, uint32_t n_cu, uint32_t tile);   // the front end's selection rule: k_conv_fc, or k_conv_m + k_fc_r
-void launch_model_h(const ModelDev& M, const BatchDev& B, const ModelScratch& S, int terms, hipStream_t st, KernelTimer* tm, int conv_fc = -1);   // conv_fc: -1 by the rule, 0 two kernels, 1 k_conv_fc
+void launch_model_h(const ModelDev& M, const BatchDev& B, const ModelScratch& S, int terms, hipStream_t st, KernelTimer* tm, uint32_t n_cu, int conv_fc = -1, FrontEndPlan* ran = nullptr);   // conv_fc: -1 by the rule (front_end_plan), 0 two kernels, 1 k_conv_fc
 void launch_pe_table(const float* pe_div, float* tab, uint32_t rows, uint32_t d_model, hipStream_t st);   // tab[row][2 i] = sin(row * pe_div[i]), [2 i + 1] = cos
 #ifdef HERRO_PROF_BUILD
 void model_h_prof_dump();   // phase cycles of k_layers_p (model_h.hip LP_MARK), printed by herro_destroy when HERRO_PROF=1

@@ -1537,35 +1537,20 @@ int model_h_half_tiles(const ModelDev& M) {
   return model_h_supported(M) ? mode : 0;
 }
 
-// The front end of a launch of n_tok tokens: true — k_conv_fc (tiles of `tile` tokens, one workgroup per compute unit); false — k_conv_m, then k_fc_r.
-// From profiles/conv_fc_ab.txt (one MI355X, 256 compute units, both paths in one call), not from an estimate:
-//     launch                    k_conv_m + k_fc_r    k_conv_fc               step
-//     1792 windows, 27 k rows        157 - 160 us    133 us (212 tiles)      - 6.6 %   (measured with the rule below in force: it confirmed its one-round range)
-//     2560 windows, 38.7 k rows      230 - 234 us    238 us (303 tiles)      no gain (inside the parent's spread)
-//     4096 windows, 62 k rows        341 - 348 us    265 - 266 us (484)      - 7.4 %
-// The fused kernel runs in ROUNDS of one tile per compute unit and a round costs the same whether 47 or 228 units take part in it — 119 us per round at
-// the smaller launch, 133 at the larger (every unit streaming the FC weights) —, while the two kernels' time follows the rows: the line through the two
-// launches above is 44 us + 4.85 us per 1000 rows.  The fused kernel is chosen where rounds x 133 us stays below 85 % of that line, a margin several times
-// the run-to-run spread of the table: 265 against 293 at 4096 windows (taken), 266 against 197 at 2560 (two kernels, as measured); in between, where nothing
-// was measured, the rule amounts to a last round that is about 70 % full (23.2 - 32.7 k rows, 55.5 - 65.5 k, 87.7 - 98.3 k ...).  Both times scale with the compute units of the device.
-bool conv_fc_faster(uint32_t n_tok, uint32_t n_cu, uint32_t tile) {
-  const uint32_t tiles = (n_tok + tile - 1) / tile, rounds = (tiles + n_cu - 1) / n_cu;
-  const double t_fused = 133.0 * rounds * ((double)tile / CF_TM);
-  const double t_two = 44.0 + 4.85e-3 * n_tok * (256.0 / n_cu);
-  return t_fused <= 0.85 * t_two;
-}
+static_assert(FRONT_ROWS == HERRO_ROWS && FRONT_FUSED_TILE == CF_TM, "infer_plan.h states the front end's shapes for front_end_plan");
 
 // B must be tileable (windows of <= 64 informative rows in B.tile_tok0 / _q, windows of 65 .. 64 * 8 rows on sibling tiles, B.tile_tok0_b) —
 // herro_job_infer sends still larger windows through the layer-by-layer kernels of model.hip.  terms: 2 (precision 4), 1 (precision 5), 3 (6), 21 (7: FF single), 12 (8: proj single).
-// conv_fc: -1 the rule above, 0 k_conv_m + k_fc_r, 1 k_conv_fc wherever the shapes allow (herro_debug_set_conv_fc)
-void launch_model_h(const ModelDev& M, const BatchDev& B, const ModelScratch& S, int terms, hipStream_t st, KernelTimer* tm, int conv_fc) {
+// n_cu: the compute units the front end plans for (front_end_plan, infer_plan.h); conv_fc: -1 its rule, 0 k_conv_m + k_fc_r, 1 k_conv_fc wherever the shapes
+// allow (herro_debug_set_conv_fc); *ran (may be null) receives the front end's launch as it went out
+void launch_model_h(const ModelDev& M, const BatchDev& B, const ModelScratch& S, int terms, hipStream_t st, KernelTimer* tm, uint32_t n_cu, int conv_fc, FrontEndPlan* ran) {
   const uint32_t N = B.n_tok;
   if (N == 0 || B.n_tiles + B.n_tiles_q + B.n_tiles_b == 0) return;
   const ModelHyper& h = M.h;
   const bool f16_front = model_h_conv_supported(M);
   ModelDev M_enc = M;
   if (!f16_front) {
-    launch_front_generic(M, B, S, st, tm);   // token table, conv stack, projection, position term: S.x complete
+    launch_front_generic(M, B, S, st, tm, n_cu, ran);   // token table, conv stack, projection, position term: S.x complete
     M_enc.pe_rows = 0xffffffffu;             // (the stack's prologue adds the encoding of rows >= pe_rows itself: nothing left to add)
   } else {
   KT_BEGIN(tm, "build_tokens", st);
@@ -1574,34 +1559,32 @@ void launch_model_h(const ModelDev& M, const BatchDev& B, const ModelScratch& S,
   // conv and FC over the whole launch group, or (A/B builds, HERRO_CONV_CHUNK = tokens per chunk, a multiple of 16) chunk by chunk — conv(k), FC(k), conv(k + 1) ... —
   // so that a chunk's y2 (7936 B per token) is read back while it can still sit in the 256 MB memory-side cache (measured: profiles/r5_ab_runs.json r5p)
   static const uint32_t chunk_tok = (uint32_t)std::max(0, ab_env("HERRO_CONV_CHUNK", 0)) & ~15u;
+  // HERRO_FC_G forces a tile height of k_fc_r in A/B builds (3 | 4: the 96 | 128 rows of the kernel's first version, 5 .. 8 and 14 (= 4): blocks)
   static const int force_g = ab_env("HERRO_FC_G", 0);
-  static const uint32_t n_cu = [] { int dev = 0, c = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev); return (uint32_t)std::max(c, 1); }();
+  static const uint32_t force_nb = force_g == 3 ? 6 : (force_g == 4 ? 8 : (force_g == 14 ? 4 : (force_g >= 5 && force_g <= 8 ? (uint32_t)force_g : 0)));
+  static const int env_cf = ab_env("HERRO_CONV_FC", -2);   // (A/B builds) overrides the context's switch
+  const int cf_mode = env_cf >= -1 ? env_cf : conv_fc;
+  const bool cf_can = h.rows == HERRO_ROWS && M.fc.K == (uint32_t)HERRO_ROWS * HC2 && M.fc.N == 256 && h.d_model == 256;   // the shapes k_conv_fc is written for
   const uint32_t n_rows = N * HERRO_ROWS;
-  auto conv = [&](uint32_t t0, uint32_t t1) {   // tokens [t0, t1): t0 a multiple of 16 (so that its first pair opens a unit of 16)
-    const uint32_t unit0 = t0 * HERRO_ROWS / 16, n_units = (std::min(t1 * HERRO_ROWS, n_rows) + 15) / 16, nu = n_units - unit0;
+  FrontEndPlan P = front_end_plan(N, n_cu, cf_can && !(cf_mode < 0 && chunk_tok) ? cf_mode : 0, force_nb);   // the whole launch; a chunk of it: conv / fc below
+  auto conv = [&](uint32_t t0) {   // the tokens P was made for, from t0 on: t0 a multiple of 16 (so that its first pair opens a unit of 16)
+    const uint32_t unit0 = t0 / 16 * HERRO_ROWS, n_units = unit0 + P.conv_units;
     // one block of 16 pairs per step, three workgroups per compute unit
     if (B.rf_q) {
       opt_in_lds(reinterpret_cast<const void*>(k_conv_m<1, 3, true>), CONV_M_SHM);
-      hipLaunchKernelGGL((k_conv_m<1, 3, true>), dim3(std::min<uint32_t>((nu + 3) / 4, 768u)), dim3(CM_NT), CONV_M_SHM, st, M, B, S, n_rows, n_units, unit0);
+      hipLaunchKernelGGL((k_conv_m<1, 3, true>), dim3(P.conv_grid), dim3(CM_NT), CONV_M_SHM, st, M, B, S, n_rows, n_units, unit0);
     } else {
       opt_in_lds(reinterpret_cast<const void*>(k_conv_m<1, 3, false>), CONV_M_SHM);
-      hipLaunchKernelGGL((k_conv_m<1, 3, false>), dim3(std::min<uint32_t>((nu + 3) / 4, 768u)), dim3(CM_NT), CONV_M_SHM, st, M, B, S, n_rows, n_units, unit0);
+      hipLaunchKernelGGL((k_conv_m<1, 3, false>), dim3(P.conv_grid), dim3(CM_NT), CONV_M_SHM, st, M, B, S, n_rows, n_units, unit0);
     }
   };
   auto fc = [&](uint32_t t0, uint32_t t1) {
-    // tile height (16-row blocks, 4 .. 8): the one that leaves the busiest compute unit the fewest rows — two workgroups fit a unit, a third would wait for a slot —, the taller
-    // one on a tie (every workgroup streams the whole weight matrix: fewer of them, less L2 traffic).  HERRO_FC_G forces a height in A/B builds (3 | 4: the 96 | 128 rows of
-    // the kernel's first version, 5 .. 8 and 14 (= 4): blocks)
     const uint32_t n = t1 - t0, lda = HERRO_ROWS * h.c2;
-    auto busiest = [&](uint32_t rows) { const uint32_t wg = (n + rows - 1) / rows; return (uint64_t)((wg + n_cu - 1) / n_cu) * rows + (wg > 2 * n_cu ? 1u << 20 : 0u); };
-    int nb = 8;
-    for (int b = 7; b >= 4; b--) if (busiest(16u * b) < busiest(16u * nb)) nb = b;
-    if (force_g == 3) nb = 6; else if (force_g == 4) nb = 8; else if (force_g == 14) nb = 4; else if (force_g >= 5 && force_g <= 8) nb = force_g;
     const uint16_t* A = S.y2_hi + (uint64_t)t0 * lda;
     float* C = S.x + (uint64_t)t0 * h.d_model;
     const uint32_t* rows = S.tok_row + t0;
-    const dim3 grid((n + 16u * nb - 1) / (16u * nb));
-    switch (nb) {
+    const dim3 grid(P.fc_grid);
+    switch (P.fc_rows / 16) {
       case 4: hipLaunchKernelGGL(k_fc_r<4>, grid, dim3(512), FC_R_SHM, st, A, lda, M.fc, C, h.d_model, n, rows, M.pe_tab, M.pe_rows); break;
       case 5: hipLaunchKernelGGL(k_fc_r<5>, grid, dim3(512), FC_R_SHM, st, A, lda, M.fc, C, h.d_model, n, rows, M.pe_tab, M.pe_rows); break;
       case 6: hipLaunchKernelGGL(k_fc_r<6>, grid, dim3(512), FC_R_SHM, st, A, lda, M.fc, C, h.d_model, n, rows, M.pe_tab, M.pe_rows); break;
@@ -1609,13 +1592,10 @@ void launch_model_h(const ModelDev& M, const BatchDev& B, const ModelScratch& S,
       default: hipLaunchKernelGGL(k_fc_r<8>, grid, dim3(512), FC_R_SHM, st, A, lda, M.fc, C, h.d_model, n, rows, M.pe_tab, M.pe_rows);
     }
   };
-  static const int env_cf = ab_env("HERRO_CONV_FC", -2);   // (A/B builds) overrides the context's switch
-  const int cf_mode = env_cf >= -1 ? env_cf : conv_fc;
-  const bool cf_can = h.rows == HERRO_ROWS && M.fc.K == (uint32_t)HERRO_ROWS * HC2 && M.fc.N == 256 && h.d_model == 256;   // the shapes k_conv_fc is written for
-  if (cf_can && (cf_mode > 0 || (cf_mode < 0 && !chunk_tok && conv_fc_faster(N, n_cu, CF_TM)))) {
+  if (P.fused) {
     // a span of its own: bench.py's roofline sets conv_fused's flops against conv_fused's time
     KT_BEGIN(tm, "conv_fc", st);
-    const dim3 grid((N + CF_TM - 1) / CF_TM);
+    const dim3 grid(P.fc_grid);
     if (B.rf_q) {
       opt_in_lds(reinterpret_cast<const void*>(k_conv_fc<true>), CONV_FC_SHM);
       hipLaunchKernelGGL(k_conv_fc<true>, grid, dim3(512), CONV_FC_SHM, st, M, B, S, N);
@@ -1626,16 +1606,22 @@ void launch_model_h(const ModelDev& M, const BatchDev& B, const ModelScratch& S,
     KT_END(tm, st);
   } else if (chunk_tok && N > chunk_tok) {
     KT_BEGIN(tm, "conv_fused", st);   // (the span carries both kernels of every chunk)
-    for (uint32_t t0 = 0; t0 < N; t0 += chunk_tok) { conv(t0, std::min(N, t0 + chunk_tok)); fc(t0, std::min(N, t0 + chunk_tok)); }
+    for (uint32_t t0 = 0; t0 < N; t0 += chunk_tok) {
+      const uint32_t t1 = std::min(N, t0 + chunk_tok);
+      P = front_end_plan(t1 - t0, n_cu, 0, force_nb, t0);
+      conv(t0);
+      fc(t0, t1);
+    }
     KT_END(tm, st);
   } else {
     KT_BEGIN(tm, "conv_fused", st);
-    conv(0, N);
+    conv(0);
     KT_END(tm, st);
     KT_BEGIN(tm, "fc_gemm", st);
     fc(0, N);
     KT_END(tm, st);
   }
+  if (ran) *ran = P;
   }
   KT_BEGIN(tm, "layers_fused", st);   // one span: the 64-token tiles (windows of 33..64 informative rows and what shares their tiles), then the 32-token ones
   auto launch = [&](auto kern, uint32_t n_tiles, int tokens) {

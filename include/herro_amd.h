@@ -269,6 +269,16 @@ int herro_debug_set_featurize_planes(herro_ctx* ctx, int on);
  * output in HBM between them (k_conv_m, k_fc_r), or as one kernel that keeps it in LDS (k_conv_fc).  Both give the same bits.  mode -1 (default): chosen per
  * launch from the launch size (conv_fc_faster); 0: two kernels; 1: one kernel wherever the model's shapes allow it (another conv stack keeps its own path). */
 int herro_debug_set_conv_fc(herro_ctx* ctx, int mode);
+/* Test hooks for what the front end of a model launch decides from the launch's tokens and the compute units of the device (csrc/infer_plan.h, front_end_plan):
+ * k_conv_fc or k_conv_m + k_fc_r, the grid of k_conv_m's stride loop (three workgroups per unit), the tile height of k_fc_r (64 .. 128 rows), and the grid of
+ * k_conv_w for a conv stack the f16 kernels do not serve (two workgroups per unit).  herro_debug_set_front_cu: the front end plans for n_cu compute units from
+ * now on (0: the device's own count), so that a launch of a few hundred tokens takes the kernels and loop trips of a large one; the encoder stack's tile plan
+ * never sees the number.  herro_debug_front_last: out[5] = fused (1: k_conv_fc), FC tile rows, FC grid, conv grid, conv units (blocks of 16 pairs of k_conv_m,
+ * tiles of k_conv_w) of the context's last model launch (all 0: a path that plans nothing from the compute units).  herro_debug_front_end_plan: the same five
+ * numbers for each of the `count` launches of n_tok, n_tok + 1, ... tokens on n_cu units (out[count][5]), without a device; mode as herro_debug_set_conv_fc. */
+int herro_debug_set_front_cu(herro_ctx* ctx, uint32_t n_cu);
+int herro_debug_front_last(const herro_ctx* ctx, uint32_t* out);
+int herro_debug_front_end_plan(uint32_t n_tok, uint32_t count, uint32_t n_cu, int mode, uint32_t* out);
 /* Test hooks for the two ways a job's windows and descriptors are built (herro_job_create): on the device behind the CIGAR scan (csrc/build_dev.hip, the
  * default since round 6) or by the host from the scan's cut records (rounds 3-5; still what runs when the device meets anything it does not settle itself —
  * a text the scan kernel flags, an input the reference panics on — and what words the error).  herro_debug_set_host_build(ctx, 1) selects the host build for

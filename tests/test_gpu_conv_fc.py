@@ -4,7 +4,8 @@ k_conv_fc (csrc/model_h.hip) runs the conv stack and the FC projection in one ke
 two kernels with that output in HBM.  Every element of the FC output sees the same MFMAs in the same order on both paths, so the logits must be
 equal bit for bit: herro_debug_set_conv_fc(0) against (1) at the token counts where a clamp, a store guard or the second tile of the fused
 kernel can go wrong, on the stand-alone forward (cells from the planes) and on jobs (16-byte records from k_rfq and from k_rows' own gather);
-a model whose conv stack the f16 kernels do not serve keeps its path whatever the switch says; and the automatic choice changes no bit."""
+a model whose conv stack the f16 kernels do not serve keeps its path whatever the switch says; and the automatic choice changes no bit (at these sizes it
+takes the two kernels on a real device: launches the rule itself gives to k_conv_fc are in test_gpu_front_plan.py)."""
 import numpy as np
 import pytest
 

@@ -1,6 +1,6 @@
 // infer_plan_check — seeded random jobs through plan_batches, group_batches and build_launch (herro_amd/csrc/infer_plan.h) on the CPU, meant for a
 // sanitizer build; it also checks what must hold of any plan: every informative window sits in exactly one launch, the token prefix matches the row
-// counts, no tile exceeds its size and every array of the image starts on 16 bytes.
+// counts, no tile exceeds its size and every array of the image starts on 16 bytes; and of the front end's plan of each launch (front_end_plan).
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -o /tmp/infer_plan_check tools/infer_plan_check.cpp && /tmp/infer_plan_check
 #include <cstdio>
 #include <cstdlib>
@@ -78,6 +78,28 @@ int main(int argc, char** argv) {
     }
     for (size_t w = 0; w < nsup.size(); w++) CHECK(hits[w] == (nsup[w] > 0 && (mode == 1 || (n_targets && w >= two[0])) ? 1u : 0u));
     CHECK(launched_tok == grouped_tok);
+    // the front end of each launch (front_end_plan): tiles and units cover the tokens, grids within their caps, and chunks of a launch add up to it
+    const uint32_t cu_pool[] = {1, 2, 3, 4, 8, 64, 256, 304};
+    for (const LaunchOffs& o : offs) {
+      const uint32_t n = o.n_tok, cu = cu_pool[pick(0, 7)];
+      const int fmode = (int)pick(0, 2) - 1;
+      const FrontEndPlan p = front_end_plan(n, cu, fmode);
+      CHECK(p.fc_grid >= 1 && (uint64_t)p.fc_grid * p.fc_rows >= n && (uint64_t)(p.fc_grid - 1) * p.fc_rows < n);
+      if (p.fused) { CHECK(fmode != 0 && p.fc_rows == FRONT_FUSED_TILE && p.conv_grid == 0 && p.conv_units == 0 && (fmode > 0 || conv_fc_faster(n, cu, FRONT_FUSED_TILE))); continue; }
+      CHECK(fmode <= 0 && p.fc_rows % 16 == 0 && p.fc_rows >= 64 && p.fc_rows <= 128 && p.fc_rows == 16 * fc_tile_blocks(n, cu));
+      CHECK(p.conv_units == ((uint64_t)n * FRONT_ROWS + 15) / 16);
+      CHECK(p.conv_grid >= 1 && p.conv_grid <= 3 * cu && (uint64_t)(p.conv_grid - 1) * 4 < p.conv_units && (p.conv_grid == 3 * cu || 4ull * p.conv_grid >= p.conv_units));
+      const uint32_t chunk = 16 * pick(1, 64);
+      uint32_t units = 0;
+      for (uint32_t t0 = 0; t0 < n; t0 += chunk) {
+        const FrontEndPlan c = front_end_plan(std::min(n, t0 + chunk) - t0, cu, 0, 4 + pick(0, 4), t0);
+        CHECK(!c.fused && c.conv_units > 0 && c.conv_grid >= 1 && c.conv_grid <= 3 * cu && (uint64_t)c.fc_grid * c.fc_rows >= std::min(n, t0 + chunk) - t0);
+        CHECK(t0 / 16 * FRONT_ROWS == units);   // a chunk opens the unit behind the last one of the chunk before it
+        units += c.conv_units;
+      }
+      CHECK(units == p.conv_units);
+      CHECK(conv_w_grid(n, cu) >= 1 && conv_w_grid(n, cu) <= std::min(n, 2 * cu));
+    }
     launches += offs.size();
   }
   std::printf("%d jobs, %zu launches: ok\n", n_jobs, launches);
