@@ -3,6 +3,7 @@ missing or no GPU is present — there is no CPU fallback in this package."""
 from __future__ import annotations
 
 import collections
+import contextlib
 import ctypes as C
 import os
 from dataclasses import dataclass
@@ -47,6 +48,7 @@ EXPORTS = [
     "herro_overlaps_occ_cut", "herro_pairs_occ_cut", "herro_debug_occ_census",
     "herro_aligned_dev_paf", "herro_pairs_paf", "herro_paf_text_data", "herro_paf_text_len", "herro_paf_text_lines", "herro_paf_text_free",
     "herro_pairs_write_alns",
+    "herro_set_seed_rescue", "herro_overlaps_rescued", "herro_pairs_rescued", "herro_debug_seed_rescue",
 ]
 
 
@@ -99,6 +101,10 @@ ALNS_OEC = 1          # HERRO_ALNS_OEC
 
 class OverlapParams(C.Structure):  # herro_overlap_params (0 = the field's default)
     _fields_ = [(n, C.c_uint32) for n in ("k", "w", "max_occ", "bandwidth", "max_gap", "min_score", "min_anchors", "occ_frac_ppm")]
+
+
+class SeedRescueParams(C.Structure):  # herro_seed_rescue_params (occ_dist 0 = off, rescue_max_occ 0 = 4095)
+    _fields_ = [("occ_dist", C.c_uint32), ("rescue_max_occ", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
 class ExtendParams(C.Structure):  # herro_extend_params (0 = the field's default)
@@ -285,6 +291,16 @@ def lib():
                 f.restype = u32
                 f.argtypes = [vp]
             L.herro_debug_occ_census.argtypes = [vp, vp, vp, vp]
+        except AttributeError:
+            if not os.environ.get("HERRO_LIB"):
+                raise
+        try:   # (an older build selected by HERRO_LIB lacks the rescue: every call that leaves it off still runs)
+            L.herro_set_seed_rescue.argtypes = [vp, vp]
+            for f in (L.herro_overlaps_rescued, L.herro_pairs_rescued):
+                f.restype = u32
+                f.argtypes = [vp]
+            L.herro_debug_seed_rescue.restype = C.c_int64
+            L.herro_debug_seed_rescue.argtypes = [vp, vp, vp, vp, u64]
         except AttributeError:
             if not os.environ.get("HERRO_LIB"):
                 raise
@@ -748,24 +764,70 @@ class Context:
             raise ValueError(f"core has shape {m.shape}, the read store {n} reads")
         return m
 
+    def set_seed_rescue(self, occ_dist: int | None = 200, rescue_max_occ: int | None = None):
+        """The rescue of high-frequency minimizers for every later find_overlaps / find_overlap_pairs of this context (herro_set_seed_rescue;
+        minimap2's -e, the reference's -e200: mm2.rs:24): of a stretch of a read whose minimizers all lie above the frequency cut the least
+        frequent ones stay, about one per occ_dist bases, among the hashes of at most rescue_max_occ (None / 0: 4095) occurrences.
+        occ_dist None or 0: off.  Values outside 0 .. 2^20 / 0 .. 65534 are the library's HERRO_E_INVALID."""
+        d, m = int(occ_dist or 0), int(rescue_max_occ or 0)
+        if not 0 <= d <= 0xFFFFFFFF or not 0 <= m <= 0xFFFFFFFF:
+            raise HerroError(-1, "seed rescue: occ_dist and rescue_max_occ are unsigned 32-bit values")
+        p = SeedRescueParams(occ_dist=d, rescue_max_occ=m)
+        self._chk(self._l.herro_set_seed_rescue(self.h, C.byref(p) if d or m else None))
+        self._seed_rescue = (d, m)
+
+    @contextlib.contextmanager
+    def _rescue_keywords(self, params: dict):
+        """occ_dist= / rescue_max_occ= of one finder call: taken out of params, set for the call, the context's setting restored behind it"""
+        if "occ_dist" not in params and "rescue_max_occ" not in params:
+            yield
+            return
+        before = getattr(self, "_seed_rescue", (0, 0))
+        d, m = params.pop("occ_dist", before[0]), params.pop("rescue_max_occ", before[1])
+        self.set_seed_rescue(d, m)
+        try:
+            yield
+        finally:
+            self.set_seed_rescue(*before)
+
+    def seed_rescue(self, **params):
+        """The rescue alone (herro_debug_seed_rescue) under the context's setting, or the occ_dist= / rescue_max_occ= given here: for the
+        minimizers in sketch()'s order, (occ u32 = min(occurrences of the hash in the store, 65535), rescued u8)."""
+        with self._rescue_keywords(params):
+            p = self._overlap_params(params)
+            n = self._l.herro_debug_seed_rescue(self.h, C.byref(p), None, None, 0)
+            if n < 0:
+                self._chk(int(n))
+            occ, resc = np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+            if n:
+                got = self._l.herro_debug_seed_rescue(self.h, C.byref(p), occ.ctypes.data, resc.ctypes.data, n)
+                if got < 0:
+                    self._chk(int(got))
+                assert got == n
+        return occ, resc
+
     def find_overlaps(self, core=None, **params):
         """Which reads of the store overlap, where, on which strand (herro_find_overlaps; the seeding and chaining of the
-        `minimap2 -x ava-ont` run of mm2.rs:15-30).  params: k, w, max_occ, bandwidth, max_gap, min_score, min_anchors, occ_frac_ppm.
+        `minimap2 -x ava-ont` run of mm2.rs:15-30).  params: k, w, max_occ, bandwidth, max_gap, min_score, min_anchors, occ_frac_ppm, and
+        occ_dist / rescue_max_occ: set_seed_rescue for this call alone (the minimizers it rescued are left in self.last_rescued).
         The frequency cut the call used (max_occ, or the one occ_frac_ppm gave) is left in self.last_occ_cut.
         Returns (rids u32 [n_targets], rows u32 [n, 10] in create_job's layout with cigar_len 0, aln_off u64 [n_targets + 1],
         scores i32 [n]): rows goes into Context.align, (rids, aln_off) with its result into aligned_job_args.
         core: u8 [n_reads], non-zero = the read is a target (herro_find_overlaps_core): the records whose tid is core; None: all."""
-        p = self._overlap_params(params)
         h = C.c_void_p()
-        if core is None:
-            self._chk(self._l.herro_find_overlaps(self.h, C.byref(p), C.byref(h)))
-        else:
-            m = self._core_mask(core)
-            self._chk(self._l.herro_find_overlaps_core(self.h, C.byref(p), m.ctypes.data, C.byref(h)))
+        with self._rescue_keywords(params):
+            p = self._overlap_params(params)
+            if core is None:
+                self._chk(self._l.herro_find_overlaps(self.h, C.byref(p), C.byref(h)))
+            else:
+                m = self._core_mask(core)
+                self._chk(self._l.herro_find_overlaps_core(self.h, C.byref(p), m.ctypes.data, C.byref(h)))
         try:
             n, nt = self._l.herro_overlaps_n(h), self._l.herro_overlaps_n_targets(h)
             if hasattr(self._l, "herro_overlaps_occ_cut"):
                 self.last_occ_cut = int(self._l.herro_overlaps_occ_cut(h))
+            if hasattr(self._l, "herro_overlaps_rescued"):
+                self.last_rescued = int(self._l.herro_overlaps_rescued(h))
             rids = np.ctypeslib.as_array(C.cast(self._l.herro_overlaps_target_ids(h), C.POINTER(C.c_uint32)), (nt,)).copy() if nt else np.zeros(0, np.uint32)
             aln_off = np.ctypeslib.as_array(C.cast(self._l.herro_overlaps_aln_off(h), C.POINTER(C.c_uint64)), (nt + 1,)).copy()
             rows = _aln_rows(self._l.herro_overlaps_alignments(h), n)
@@ -807,17 +869,18 @@ class Context:
         find_overlaps; zdrop, max_ext as extend_overlaps; extend=False: HERRO_PAIRS_NO_EXTEND, the chains' anchor spans as they are.
         core: u8 [n_reads], non-zero = the read is a target (herro_find_overlap_pairs_core): only pairs with a core read are chained, extended
         and later aligned, and the table holds only the rows whose target is core — a selection of the unmasked handle; None: all reads."""
-        p = self._overlap_params(params)
         if not 0 <= int(zdrop) <= 0xFFFFFFFF or not 0 <= int(max_ext) <= 0xFFFFFFFF:
             raise HerroError(-1, "extend parameters: zdrop and max_ext are unsigned 32-bit values")
         e = ExtendParams(zdrop=int(zdrop), max_ext=int(max_ext))
         h = C.c_void_p()
         flags = 0 if extend else PAIRS_NO_EXTEND
-        if core is None:
-            self._chk(self._l.herro_find_overlap_pairs(self.h, C.byref(p), C.byref(e), flags, C.byref(h)))
-        else:
-            m = self._core_mask(core)
-            self._chk(self._l.herro_find_overlap_pairs_core(self.h, C.byref(p), C.byref(e), flags, m.ctypes.data, C.byref(h)))
+        with self._rescue_keywords(params):   # (occ_dist= / rescue_max_occ=: set_seed_rescue for this call alone)
+            p = self._overlap_params(params)
+            if core is None:
+                self._chk(self._l.herro_find_overlap_pairs(self.h, C.byref(p), C.byref(e), flags, C.byref(h)))
+            else:
+                m = self._core_mask(core)
+                self._chk(self._l.herro_find_overlap_pairs_core(self.h, C.byref(p), C.byref(e), flags, m.ctypes.data, C.byref(h)))
         return OverlapPairs(self, h)
 
     def pairs_from_table(self, primaries: np.ndarray, chain_scores, rids, aln_off, rec_of_row, n_rows: int | None = None) -> "OverlapPairs":
@@ -1142,6 +1205,7 @@ class OverlapPairs:
         nt = int(L.herro_pairs_n_targets(h))
         self.n_rows = int(L.herro_pairs_n_rows(h)) if hasattr(L, "herro_pairs_n_rows") else 2 * n
         self.occ_cut = int(L.herro_pairs_occ_cut(h)) if hasattr(L, "herro_pairs_occ_cut") else 0
+        self.rescued = int(L.herro_pairs_rescued(h)) if hasattr(L, "herro_pairs_rescued") else 0   # minimizers the rescue kept (0: off)
 
         def arr(ptr, ct, dt, shape):
             out = np.zeros(shape, dt)

@@ -131,6 +131,7 @@ struct herro_ctx {
   // the device arrays of the read store belong to this owner: the contexts of one device can share ONE store (herro_share_reads);
   // its memory is freed when the last context holding it lets go
   std::shared_ptr<void> store_owner;
+  herro_seed_rescue_params seed_rescue{};   // herro_set_seed_rescue: occ_dist 0 = off; rescue_max_occ as given (0 = 4095 where it is used)
   // model
   bool has_model = false;
   herro::ModelDev M{};

@@ -1,6 +1,6 @@
 // frontend_api.hip — the C ABI's front end (include/herro_amd.h): reads alone -> overlap records -> their ops on the device.
 // herro_find_overlaps[_core], herro_extend_overlaps, herro_align_overlaps[_dev], herro_aligned_dev_*, herro_find_overlap_pairs[_core], herro_pairs_*, the PAF / .oec.zst
-// writer (herro_aligned_dev_paf, herro_pairs_paf, herro_pairs_write_alns) and the test hooks herro_debug_sketch and herro_debug_occ_census.  Host C++ (compiled by
+// writer (herro_aligned_dev_paf, herro_pairs_paf, herro_pairs_write_alns) herro_set_seed_rescue and the test hooks herro_debug_sketch, herro_debug_occ_census and herro_debug_seed_rescue.  Host C++ (compiled by
 // hipcc) over overlap_dev.hip, align_dev.hip and paf_dev.hip; contexts, the model and jobs are herro_api.hip.
 #include <hip/hip_runtime.h>
 
@@ -168,6 +168,8 @@ int overlap_params(herro_ctx* ctx, const herro_overlap_params* in, herro::OvlPar
     ctx->err = "overlap parameters: 5 <= k <= 31 and 1 <= w <= 64";
     return HERRO_E_INVALID;
   }
+  P.occ_dist = ctx->seed_rescue.occ_dist;       // herro_set_seed_rescue (validated there)
+  P.rescue_max_occ = ctx->seed_rescue.rescue_max_occ ? ctx->seed_rescue.rescue_max_occ : 4095;
   if (P.occ_frac_ppm > 999999) {
     ctx->err = "overlap parameters: occ_frac_ppm must be below 1000000 (0: the fixed cut max_occ)";
     return HERRO_E_INVALID;
@@ -185,6 +187,9 @@ void print_ovl_stats(const herro::OvlParams& P, const herro::OvlStats& stats) {
   if (P.occ_frac_ppm)
     fprintf(stderr, "OVLOCC cut=%llu distinct=%llu cut_runs=%llu cut_minimizers=%llu\n", (unsigned long long)stats.occ_cut,
             (unsigned long long)stats.distinct, (unsigned long long)stats.cut_runs, (unsigned long long)stats.cut_minimizers);
+  if (P.occ_dist)
+    fprintf(stderr, "OVLRESC high=%llu rescued=%llu anchors=%llu\n", (unsigned long long)stats.resc_high, (unsigned long long)stats.rescued,
+            (unsigned long long)stats.resc_anchors);
 }
 
 // A call's core mask (n_reads bytes, non-zero: the read is a target) goes up once, into the call's scratch; NULL stays NULL: every read is core.
@@ -505,6 +510,7 @@ struct herro_overlaps {
   std::vector<herro_alignment> alns;
   std::vector<int32_t> scores;
   uint32_t occ_cut = 0;                  // the frequency cut the call used
+  uint32_t rescued = 0;                  // minimizers the rescue kept (herro_set_seed_rescue; 0: off)
 };
 
 int herro_find_overlaps(herro_ctx* ctx, const herro_overlap_params* params, herro_overlaps** out) { return herro_find_overlaps_core(ctx, params, nullptr, out); }
@@ -545,6 +551,7 @@ int herro_find_overlaps_core(herro_ctx* ctx, const herro_overlap_params* params,
   std::sort(recs.begin(), recs.end(), [](const Rec& x, const Rec& y) { return x.a.tid != y.a.tid ? x.a.tid < y.a.tid : x.a.qid < y.a.qid; });
   auto* h = new herro_overlaps();
   h->occ_cut = (uint32_t)stats.occ_cut;
+  h->rescued = (uint32_t)stats.rescued;
   h->alns.reserve(recs.size());
   h->scores.reserve(recs.size());
   for (const Rec& r : recs) {
@@ -564,7 +571,21 @@ const uint64_t* herro_overlaps_aln_off(const herro_overlaps* o) { return o ? o->
 const herro_alignment* herro_overlaps_alignments(const herro_overlaps* o) { return o ? o->alns.data() : nullptr; }
 const int32_t* herro_overlaps_scores(const herro_overlaps* o) { return o ? o->scores.data() : nullptr; }
 uint32_t herro_overlaps_occ_cut(const herro_overlaps* o) { return o ? o->occ_cut : 0; }
+uint32_t herro_overlaps_rescued(const herro_overlaps* o) { return o ? o->rescued : 0; }
 void herro_overlaps_free(herro_overlaps* o) { delete o; }
+
+// The rescue of high-frequency minimizers is a setting of the context (include/herro_amd.h): overlap_params hands it to every finder call.
+int herro_set_seed_rescue(herro_ctx* ctx, const herro_seed_rescue_params* params) {
+  if (!ctx) return HERRO_E_INVALID;
+  const herro_seed_rescue_params off{};
+  const herro_seed_rescue_params& p = params ? *params : off;
+  if (p.occ_dist > (1u << 20) || p.rescue_max_occ > herro::OVL_OCC_BINS - 2 || p.reserved[0] || p.reserved[1]) {
+    ctx->err = "herro_set_seed_rescue: occ_dist <= 2^20 (0: off), rescue_max_occ <= 65534 (0: 4095), reserved fields 0";
+    return HERRO_E_INVALID;
+  }
+  ctx->seed_rescue = p;
+  return HERRO_OK;
+}
 
 // ---- pair overlaps ("Pairs on the device"): reads -> one record per pair and the table of its two rows -> mirrored alignments ----
 struct herro_pairs {
@@ -577,6 +598,7 @@ struct herro_pairs {
   std::vector<uint64_t> aln_off;         // [n_targets + 1]
   std::vector<uint32_t> rec_of_row;      // [n_rows]: 2 P, fewer with a core mask
   uint32_t occ_cut = 0;                  // the frequency cut the finder used; 0: a handle over the caller's table
+  uint32_t rescued = 0;                  // minimizers the rescue kept; 0: off, or a handle over the caller's table
 };
 
 int herro_find_overlap_pairs(herro_ctx* ctx, const herro_overlap_params* params, const herro_extend_params* eparams, uint32_t flags, herro_pairs** out) {
@@ -608,6 +630,7 @@ int herro_find_overlap_pairs_core(herro_ctx* ctx, const herro_overlap_params* pa
   std::unique_ptr<herro_pairs> h(new herro_pairs());
   h->ctx = ctx;
   h->occ_cut = (uint32_t)stats.occ_cut;
+  h->rescued = (uint32_t)stats.rescued;
   if (int rc = overlap_rc(ctx, herro::ovl_row_table(recs, ctx->n_reads, d_core, ctx->stream, h->rids, h->aln_off, h->rec_of_row, msg), msg)) return rc;
   const uint32_t n = (uint32_t)recs.n;   // (<= 2^31 - 1: ovl_find_pairs)
   h->ext.assign((size_t)n * 4, 0);
@@ -747,6 +770,7 @@ const uint64_t* herro_pairs_aln_off(const herro_pairs* p) { return p ? p->aln_of
 const uint32_t* herro_pairs_rec_of_row(const herro_pairs* p) { return p ? p->rec_of_row.data() : nullptr; }
 uint64_t herro_pairs_n_rows(const herro_pairs* p) { return p ? p->rec_of_row.size() : 0; }
 uint32_t herro_pairs_occ_cut(const herro_pairs* p) { return p ? p->occ_cut : 0; }
+uint32_t herro_pairs_rescued(const herro_pairs* p) { return p ? p->rescued : 0; }
 void herro_pairs_free(herro_pairs* p) { delete p; }
 
 // ---- PAF / .oec.zst of found alignments (paf_dev.hip) ----------------------------------------------------------------------------
@@ -1043,6 +1067,23 @@ int64_t herro_debug_sketch(herro_ctx* ctx, const herro_overlap_params* params, u
     }
   }
   return (int64_t)h.size();
+}
+
+int64_t herro_debug_seed_rescue(herro_ctx* ctx, const herro_overlap_params* params, uint32_t* occ, uint8_t* rescued, uint64_t cap) {
+  if (!ctx) return HERRO_E_INVALID;
+  herro::OvlParams P;
+  if (int rc = overlap_params(ctx, params, P)) return rc;
+  if (int rc = device_ready(ctx, "herro_debug_seed_rescue")) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::vector<uint32_t> c;
+  std::vector<uint8_t> f;
+  std::string msg;
+  if (int rc = overlap_rc(ctx, herro::ovl_seed_rescue(ovl_store(ctx), P, ctx->stream, c, f, msg), msg)) return rc;
+  if (c.size() <= cap && occ && rescued && !c.empty()) {
+    std::memcpy(occ, c.data(), 4 * c.size());
+    std::memcpy(rescued, f.data(), f.size());
+  }
+  return (int64_t)c.size();
 }
 
 int herro_debug_occ_census(herro_ctx* ctx, const herro_overlap_params* params, uint32_t* hist, uint64_t out[4]) {

@@ -22,7 +22,9 @@ constexpr uint32_t OVL_MAX_READS = 0x7fffffffu;     // q << 1 | rel is one 33-bi
 
 // defaults already filled in.  occ_frac_ppm 0: runs longer than max_occ are dropped.  Else the cut is the census's (ovl_occ_census) and max_occ
 // its ceiling, 0 = none.
-struct OvlParams { uint32_t k, w, max_occ, bandwidth, max_gap, min_score, min_anchors, occ_frac_ppm; };
+// occ_dist != 0: the rescue of high-frequency minimizers (minimap2's -e, mm2.rs:24) — of a stretch of a read whose minimizers all lie
+// above the cut, the least frequent ones stay, about one per occ_dist bases, among those of at most rescue_max_occ occurrences (filled in: never 0).
+struct OvlParams { uint32_t k, w, max_occ, bandwidth, max_gap, min_score, min_anchors, occ_frac_ppm, occ_dist = 0, rescue_max_occ = 0; };
 
 constexpr uint32_t OVL_OCC_BINS = 65536;       // census counts of a hash run: min(length, 65535)
 constexpr uint32_t OVL_OCC_FLOOR = 10;         // the least cut the fraction may give (minimap2's min_mid_occ)
@@ -45,6 +47,7 @@ struct OvlStats {
   uint64_t kmers = 0, minimizers = 0, anchors = 0, groups = 0, chained = 0, chunks = 0;
   uint64_t occ_cut = 0;                                       // the cut the call used: max_occ, or the census's
   uint64_t distinct = 0, cut_runs = 0, cut_minimizers = 0;    // occ_frac_ppm != 0: hash runs of the index, those above the cut, their minimizers
+  uint64_t resc_high = 0, rescued = 0, resc_anchors = 0;      // occ_dist != 0: minimizers between the cut and rescue_max_occ, the rescued, the anchors of their runs
 };
 
 enum { OVL_OK = 0, OVL_HIP = 1, OVL_UNSUPPORTED = 2 };
@@ -61,6 +64,10 @@ int ovl_sketch(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vecto
 // The census and the pick alone (occ_frac_ppm != 0): rec = {cut, distinct hashes, runs above the cut, minimizers in them}; hist (or NULL): the
 // OVL_OCC_BINS bins of min(run length, 65535).
 int ovl_occ_census(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vector<uint32_t>* hist, uint64_t rec[4], std::string& err);
+
+// The rescue alone, for the minimizers in ovl_sketch's order: occ = min(occurrences of the hash in the store, 65535), rescued = 1 where the rule of
+// DESIGN.md §10, "Rescue of high-frequency minimizers" (tests/rescue_ref.py) keeps a minimizer above the cut.  occ_dist 0: no flag is set.
+int ovl_seed_rescue(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vector<uint32_t>& occ, std::vector<uint8_t>& rescued, std::string& err);
 
 // every kept (t, q) chain per strand, ascending (t, q, rel); the caller picks the strand and writes the dual records
 // d_core (here and below): NULL — every read is a target — or the core mask on the device, n_reads bytes, non-zero = core (the PAF

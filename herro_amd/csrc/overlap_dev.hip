@@ -6,6 +6,9 @@
 //   radix sort   LSD, 8-bit digits, 64-bit key + 64-bit payload, stable (per-block histogram, scan, ranked scatter).
 //   k_occ_census, k_occ_pick   occ_frac_ppm only: the histogram of the run lengths (LDS bins below 2048, the table beyond) and, in one workgroup, the
 //                cut that leaves the given fraction of the distinct hashes above it; k_runs_occ reads it where k_occ_pick left it.
+//   k_occ_place, k_rescue, k_resc_kind   the rescue of high-frequency minimizers only (OvlParams.occ_dist != 0): the run length of every minimizer put back
+//                in (rid, pos) order, one wave64 per read over its streaks of minimizers above the cut, and the outcome back in hash order for
+//                k_runs_resc / k_expand_resc (tests/rescue_ref.py).
 //   k_runs       per hash run: length, frequency cut, anchors every occurrence has with the later reads of its run.
 //   k_expand     the anchors of the targets of one chunk: A = tpos << 32 | qpos, B = (t - t_lo) << 33 | q << 1 | rel;
 //                sorted by A carrying B, then by B carrying A (stable): order (t, q, rel, tpos, qpos).
@@ -246,18 +249,49 @@ __global__ __launch_bounds__(256) void k_rs_scatter(const uint64_t* __restrict__
 // run_end[x]: end of its run.  Runs longer than max_occ (and single occurrences) keep cnt 0 (cleared before the launch).
 // CORE: an occurrence in a non-core read counts only the later occurrences whose read is core — none of them is in its own read, which is
 // not core.  An occurrence in a core read keeps the count above.  The frequency cut is the whole store's, whatever the mask.
-template <bool CORE>
+// RESCUE ("Rescue of high-frequency minimizers"): a run with max_occ < c <= rmax is kept for its rescued occurrences.  kind[x]
+// (k_resc_kind): 0 — x is in no such run, 1 — it is and is not rescued, 2 — it is rescued.  A rescued occurrence counts every later occurrence in
+// another read, one that is not rescued counts the rescued ones; the core rule holds on top.  stat[2] sums the anchors of these runs.
+template <bool CORE, bool RESCUE = false>
 __device__ inline void runs_of_head(const uint64_t* __restrict__ hash, const uint64_t* __restrict__ meta, uint32_t n, uint32_t max_occ,
                                     uint32_t* __restrict__ cnt, uint32_t* __restrict__ run_end, unsigned long long* __restrict__ per_read,
-                                    const uint8_t* __restrict__ core) {
+                                    const uint8_t* __restrict__ core, uint32_t rmax = 0, const uint8_t* __restrict__ kind = nullptr,
+                                    unsigned long long* __restrict__ stat = nullptr) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const uint64_t h = hash[i];
   if (i > 0 && hash[i - 1] == h) return;       // the head of a run does the run
+  uint32_t bound = max_occ;
+  if constexpr (RESCUE) bound = max(max_occ, rmax);
   uint64_t e = i + 1;
-  while (e < n && hash[e] == h && e - i <= max_occ) e++;
+  while (e < n && hash[e] == h && e - i <= bound) e++;
   const uint64_t c = e - i;
-  if (c < 2 || c > max_occ) return;
+  if (c < 2 || c > bound) return;
+  if constexpr (RESCUE) {
+    if (c > max_occ) {
+      // behind j: a = all occurrences, r = the rescued, c = those of core reads, cr = both; s*: the same of j's own read, which do not count
+      uint32_t ta = 0, tr = 0, tc = 0, tcr = 0, sa = 0, sr = 0, sc = 0, scr = 0, rid_after = 0xffffffffu;
+      unsigned long long sum = 0;
+      for (uint64_t j = e; j-- > i;) {
+        const uint32_t rid = (uint32_t)(meta[j] >> 32);
+        if (rid != rid_after) sa = sr = sc = scr = 0;
+        rid_after = rid;
+        const bool resc = kind[j] == 2;
+        bool is_core = true;
+        if constexpr (CORE) is_core = core[rid] != 0;
+        const uint32_t m = is_core ? (resc ? ta - sa : tr - sr) : (resc ? tc - sc : tcr - scr);
+        cnt[j] = m;
+        run_end[j] = (uint32_t)e;
+        if (m) atomicAdd(&per_read[rid], (unsigned long long)m);
+        sum += m;
+        ta++; sa++;
+        if (resc) { tr++; sr++; }
+        if (is_core) { tc++; sc++; if (resc) { tcr++; scr++; } }
+      }
+      if (sum) atomicAdd(&stat[2], sum);
+      return;
+    }
+  }
   uint64_t nxt = e;                            // first occurrence of the next read
   uint32_t rid_after = 0;
   uint32_t core_after = 0;                     // CORE: occurrences behind j whose read is core
@@ -290,6 +324,15 @@ __global__ __launch_bounds__(256) void k_runs_occ(const uint64_t* __restrict__ h
                                                   const uint64_t* __restrict__ occ, uint32_t* __restrict__ cnt, uint32_t* __restrict__ run_end,
                                                   unsigned long long* __restrict__ per_read, const uint8_t* __restrict__ core) {
   runs_of_head<CORE>(hash, meta, n, (uint32_t)occ[0], cnt, run_end, per_read, core);
+}
+
+// ... with the rescue on; occ: where k_occ_pick left the cut, or NULL — the cut is max_occ
+template <bool CORE>
+__global__ __launch_bounds__(256) void k_runs_resc(const uint64_t* __restrict__ hash, const uint64_t* __restrict__ meta, uint32_t n, uint32_t max_occ,
+                                                   const uint64_t* __restrict__ occ, uint32_t* __restrict__ cnt, uint32_t* __restrict__ run_end,
+                                                   unsigned long long* __restrict__ per_read, const uint8_t* __restrict__ core, uint32_t rmax,
+                                                   const uint8_t* __restrict__ kind, unsigned long long* __restrict__ stat) {
+  runs_of_head<CORE, true>(hash, meta, n, occ ? (uint32_t)occ[0] : max_occ, cnt, run_end, per_read, core, rmax, kind, stat);
 }
 
 // ---- the cut as a fraction of the distinct hashes (occ_frac_ppm; DESIGN.md section 10, tests/occ_ref.py) -------------------------------------
@@ -368,11 +411,13 @@ __global__ __launch_bounds__(256) void k_mask(const uint64_t* __restrict__ meta,
 
 // CORE: a non-core occurrence has its cntm[x] partners scattered over the rest of its run — the occurrences of core reads; it walks the
 // run from itself on (at most max_occ steps) and skips the others, those of its own read among them.
-template <bool CORE>
-__global__ __launch_bounds__(256) void k_expand(const uint64_t* __restrict__ meta, const uint32_t* __restrict__ cntm,
-                                                const uint32_t* __restrict__ run_end, const uint32_t* __restrict__ aoff, uint32_t n,
-                                                const uint64_t* __restrict__ base_off, uint32_t k, uint32_t t_lo,
-                                                uint64_t* __restrict__ A, uint64_t* __restrict__ B, const uint8_t* __restrict__ core) {
+// RESCUE: an occurrence of a rescued run that is not rescued itself (kind 1) has the rescued occurrences of the other reads behind it as partners,
+// scattered likewise; the walk is bounded by the run's end, at most rescue_max_occ steps.
+template <bool CORE, bool RESCUE>
+__device__ inline void expand_one(const uint64_t* __restrict__ meta, const uint32_t* __restrict__ cntm, const uint32_t* __restrict__ run_end,
+                                  const uint32_t* __restrict__ aoff, uint32_t n, const uint64_t* __restrict__ base_off, uint32_t k, uint32_t t_lo,
+                                  uint64_t* __restrict__ A, uint64_t* __restrict__ B, const uint8_t* __restrict__ core,
+                                  const uint8_t* __restrict__ kind) {
   const uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (x >= n) return;
   const uint32_t c = cntm[x];
@@ -383,13 +428,20 @@ __global__ __launch_bounds__(256) void k_expand(const uint64_t* __restrict__ met
   uint32_t at = aoff[x];
   bool sparse = false;
   if constexpr (CORE) sparse = core[t] == 0;
+  bool rsparse = false;
+  if constexpr (RESCUE) rsparse = kind[x] == 1;
   const uint32_t at_end = at + c;
-  for (uint32_t y = sparse ? (uint32_t)x + 1 : e - c; y < e; y++) {
+  for (uint32_t y = sparse || rsparse ? (uint32_t)x + 1 : e - c; y < e; y++) {
     const uint64_t my = meta[y];
     const uint32_t q = (uint32_t)(my >> 32), qp = ((uint32_t)my) >> 1, rel = ((uint32_t)my & 1u) ^ st;
-    if constexpr (CORE) {
+    if constexpr (CORE || RESCUE) {
       if (at == at_end) break;                              // (its c partners are written: nothing behind them is core)
+    }
+    if constexpr (CORE) {
       if (sparse && core[q] == 0) continue;
+    }
+    if constexpr (RESCUE) {
+      if (rsparse && (q == t || kind[y] != 2)) continue;
     }
     const uint32_t qlen = (uint32_t)(base_off[q + 1] - base_off[q]);
     const uint32_t qpos = rel ? qlen - qp + k - 2 : qp;     // last base of the same k-mer on the query's reverse complement
@@ -397,6 +449,155 @@ __global__ __launch_bounds__(256) void k_expand(const uint64_t* __restrict__ met
     B[at] = ((uint64_t)(t - t_lo) << 33) | ((uint64_t)q << 1) | rel;
     at++;
   }
+}
+
+template <bool CORE>
+__global__ __launch_bounds__(256) void k_expand(const uint64_t* __restrict__ meta, const uint32_t* __restrict__ cntm,
+                                                const uint32_t* __restrict__ run_end, const uint32_t* __restrict__ aoff, uint32_t n,
+                                                const uint64_t* __restrict__ base_off, uint32_t k, uint32_t t_lo,
+                                                uint64_t* __restrict__ A, uint64_t* __restrict__ B, const uint8_t* __restrict__ core) {
+  expand_one<CORE, false>(meta, cntm, run_end, aoff, n, base_off, k, t_lo, A, B, core, nullptr);
+}
+
+template <bool CORE>
+__global__ __launch_bounds__(256) void k_expand_resc(const uint64_t* __restrict__ meta, const uint32_t* __restrict__ cntm,
+                                                     const uint32_t* __restrict__ run_end, const uint32_t* __restrict__ aoff, uint32_t n,
+                                                     const uint64_t* __restrict__ base_off, uint32_t k, uint32_t t_lo,
+                                                     uint64_t* __restrict__ A, uint64_t* __restrict__ B, const uint8_t* __restrict__ core,
+                                                     const uint8_t* __restrict__ kind) {
+  expand_one<CORE, true>(meta, cntm, run_end, aoff, n, base_off, k, t_lo, A, B, core, kind);
+}
+
+// ---- rescue of high-frequency minimizers (tests/rescue_ref.py) ------------------------------------------------------------
+// first p with a[p] >= v
+__device__ inline uint32_t lower_bound_u64(const uint64_t* __restrict__ a, uint32_t n, uint64_t v) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (a[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// From hash order back to (rid, pos) order: meta ascends with (rid, pos) and is unique, so the place of sorted element i is its rank in the
+// unsorted copy meta_rp.  occ_rp[place] = the length of i's run (a difference of run starts: k_heads, the scan, k_gstart), perm[i] = place.
+__global__ __launch_bounds__(256) void k_occ_place(const uint64_t* __restrict__ meta, const uint64_t* __restrict__ meta_rp,
+                                                   const uint32_t* __restrict__ flag, const uint32_t* __restrict__ gidx,
+                                                   const uint32_t* __restrict__ rstart, uint32_t n, uint32_t* __restrict__ occ_rp,
+                                                   uint32_t* __restrict__ perm) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t r = gidx[i] + flag[i] - 1;
+  const uint32_t p = lower_bound_u64(meta_rp, n, meta[i]);
+  occ_rp[p] = rstart[r + 1] - rstart[r];
+  perm[i] = p;
+}
+
+// One streak: the H minimizers (cut < occ <= rmax) of [s0, s1) in (rid, pos) order, `size` of them, no U among them; ps / pe: the positions that
+// bound it.  Every argument is uniform over the wave.  Flags the m = (2 (pe - ps) + occ_dist) / (2 occ_dist) members with the least (occ, pos) —
+// all of them if m >= size — and returns how many it flagged.  T, the m-th smallest occ, is found by bisection over the value, a ballot count
+// per 64 members and step; then every occ < T is flagged and the first m - #(occ < T) of occ == T in position order.
+__device__ inline uint32_t rescue_streak(const uint32_t* __restrict__ occ_rp, uint8_t* __restrict__ resc_rp, uint32_t s0, uint32_t s1,
+                                         uint32_t size, uint32_t ps, uint32_t pe, uint32_t cut, uint32_t rmax, uint32_t occ_dist, uint32_t lane) {
+  const uint64_t m64 = (2ull * (pe - ps) + occ_dist) / (2ull * occ_dist);
+  if (!m64) return 0;
+  uint32_t T = rmax, need = 0xffffffffu;
+  if (m64 < size) {
+    const uint32_t m = (uint32_t)m64;
+    uint32_t lo = cut + 1, hi = rmax;          // the least T with #(cut < occ <= T) >= m
+    while (lo < hi) {
+      const uint32_t mid = lo + ((hi - lo) >> 1);
+      uint32_t le = 0;
+      for (uint32_t b = s0; b < s1; b += 64) {
+        const uint32_t c = b + lane < s1 ? occ_rp[b + lane] : 0u;
+        le += (uint32_t)__popcll(__ballot(c > cut && c <= mid));
+      }
+      if (le >= m) hi = mid; else lo = mid + 1;
+    }
+    T = lo;
+    uint32_t less = 0;
+    for (uint32_t b = s0; b < s1; b += 64) {
+      const uint32_t c = b + lane < s1 ? occ_rp[b + lane] : 0u;
+      less += (uint32_t)__popcll(__ballot(c > cut && c < T));
+    }
+    need = m - less;
+  }
+  uint32_t taken = 0, flagged = 0;             // taken: members with occ == T in front of this block
+  for (uint32_t b = s0; b < s1; b += 64) {
+    const uint32_t c = b + lane < s1 ? occ_rp[b + lane] : 0u;
+    const bool high = c > cut && c <= rmax, eq = high && c == T;
+    const uint64_t beq = __ballot(eq);
+    const bool f = high && (c < T || (eq && taken + (uint32_t)__popcll(beq & ((1ull << lane) - 1)) < need));
+    if (f) resc_rp[b + lane] = 1;
+    flagged += (uint32_t)__popcll(__ballot(f));
+    taken += (uint32_t)__popcll(beq);
+  }
+  return flagged;
+}
+
+// One wave64 per read: its minimizers 64 at a time in ascending pos.  U = 2 <= occ <= cut, H = cut < occ <= rmax, the others are transparent.
+// ps (the last U's pos, 0 at the start), the first member and the size of the open streak are uniform and carried from block to block; a U,
+// or the read's end, closes the streak.  resc_rp is cleared before the launch; stat[0] += the H minimizers, stat[1] += the rescued.
+__global__ __launch_bounds__(64) void k_rescue(const uint64_t* __restrict__ meta_rp, const uint32_t* __restrict__ occ_rp, uint32_t n,
+                                               const uint64_t* __restrict__ base_off, uint32_t max_occ, const uint64_t* __restrict__ occ,
+                                               uint32_t rmax, uint32_t occ_dist, uint8_t* __restrict__ resc_rp,
+                                               unsigned long long* __restrict__ stat) {
+  const uint32_t rid = blockIdx.x, lane = threadIdx.x;
+  const uint32_t cut = occ ? (uint32_t)occ[0] : max_occ;
+  if (rmax <= cut) return;
+  const uint32_t r0 = lower_bound_u64(meta_rp, n, (uint64_t)rid << 32), r1 = lower_bound_u64(meta_rp, n, ((uint64_t)rid + 1) << 32);
+  if (r0 == r1) return;
+  const uint32_t len = (uint32_t)(base_off[rid + 1] - base_off[rid]);
+  uint32_t ps = 0, s_begin = 0, s_size = 0, n_high = 0, n_resc = 0;
+  for (uint32_t base = r0; base < r1; base += 64) {
+    const bool valid = base + lane < r1;
+    const uint32_t c = valid ? occ_rp[base + lane] : 0u;
+    const uint32_t pos = valid ? ((uint32_t)meta_rp[base + lane]) >> 1 : 0u;
+    const uint64_t mu = __ballot(c >= 2 && c <= cut), mh = __ballot(c > cut && c <= rmax);
+    if (!mh && !s_size) {                       // no streak open, none begins: only the last U matters
+      if (mu) ps = __shfl(pos, 63 - __clzll(mu), 64);
+      continue;
+    }
+    n_high += (uint32_t)__popcll(mh);
+    uint64_t rest = mu, seen = 0;               // seen: the lanes up to the last U handled
+    while (rest) {
+      const uint32_t l = (uint32_t)__builtin_ctzll(rest);
+      rest &= rest - 1;
+      const uint64_t hb = mh & ((1ull << l) - 1) & ~seen;
+      if (hb) {
+        if (!s_size) s_begin = base + (uint32_t)__builtin_ctzll(hb);
+        s_size += (uint32_t)__popcll(hb);
+      }
+      const uint32_t pu = __shfl(pos, l, 64);
+      if (s_size) {
+        n_resc += rescue_streak(occ_rp, resc_rp, s_begin, base + l, s_size, ps, pu, cut, rmax, occ_dist, lane);
+        s_size = 0;
+      }
+      ps = pu;
+      seen = ((1ull << l) - 1) | (1ull << l);
+    }
+    const uint64_t hb = mh & ~seen;
+    if (hb) {
+      if (!s_size) s_begin = base + (uint32_t)__builtin_ctzll(hb);
+      s_size += (uint32_t)__popcll(hb);
+    }
+  }
+  if (s_size) n_resc += rescue_streak(occ_rp, resc_rp, s_begin, r1, s_size, ps, len, cut, rmax, occ_dist, lane);
+  if (lane == 0) {
+    if (n_high) atomicAdd(&stat[0], (unsigned long long)n_high);
+    if (n_resc) atomicAdd(&stat[1], (unsigned long long)n_resc);
+  }
+}
+
+// back in hash order: 0 — not in a rescued run, 1 — in one and not rescued, 2 — rescued
+__global__ __launch_bounds__(256) void k_resc_kind(const uint32_t* __restrict__ perm, const uint32_t* __restrict__ occ_rp,
+                                                   const uint8_t* __restrict__ resc_rp, uint32_t n, uint32_t max_occ,
+                                                   const uint64_t* __restrict__ occ, uint32_t rmax, uint8_t* __restrict__ kind) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t cut = occ ? (uint32_t)occ[0] : max_occ;
+  const uint32_t p = perm[i], c = occ_rp[p];
+  kind[i] = c > cut && c <= rmax ? (resc_rp[p] ? 2 : 1) : 0;
 }
 
 // ---- groups -------------------------------------------------------------------------------------------------------------------
@@ -752,8 +953,9 @@ int sort_by_hash(Sketch& sk, uint32_t k, hipStream_t st, Bufs& B, SortScratch& m
 
 // The census of the run lengths of hash[0 .. n) (sorted, n >= 1) and the pick, queued on st: *d_occ = {cut, distinct, runs above the cut, minimizers
 // in them} and *d_hist, on the device.  flag [n] and gidx [n + 1] are the caller's, free to use again once this is queued in front of their next writer.
+// *rstart (when asked for): the run starts the census took, for the rescue, which needs the same flag and gidx.
 int occ_census_dev(const uint64_t* hash, uint32_t n, const OvlParams& P, hipStream_t st, Bufs& B, const SortScratch& ms, uint32_t* flag, uint32_t* gidx,
-                   uint64_t** d_occ, uint32_t** d_hist, std::string& err) {
+                   uint64_t** d_occ, uint32_t** d_hist, std::string& err, uint32_t** rstart_out = nullptr) {
   uint32_t* rstart;
   OVL_TRY(B.get(&rstart, (uint64_t)n + 1));
   OVL_TRY(B.get(d_hist, OVL_OCC_BINS));
@@ -765,6 +967,49 @@ int occ_census_dev(const uint64_t* hash, uint32_t n, const OvlParams& P, hipStre
   k_occ_census<<<std::min(nblk(n, 256), OCC_GRID), 256, 0, st>>>(rstart, gidx + n, *d_hist);
   k_occ_pick<<<1, 256, 0, st>>>(*d_hist, n, P.occ_frac_ppm, P.max_occ, *d_occ);
   OVL_TRY(hipGetLastError());
+  if (rstart_out) *rstart_out = rstart;
+  return OVL_OK;
+}
+
+// The rescue (P.occ_dist != 0), queued on st behind the sort and, with occ_frac_ppm, the census.  meta_rp: the copy of the minimizers' meta taken
+// before the sort; flag / gidx / rstart: the run starts of the sorted hashes, or rstart NULL — they are taken here into the caller's flag [n] and
+// gidx [n + 1]; d_occ: where k_occ_pick left the cut, NULL with a fixed cut.  Leaves occ_rp and resc_rp in (rid, pos) order, kind in hash order
+// and stat = {H minimizers, rescued, 0}.  The selection sees neither the core mask nor the scratch budget.
+struct Rescue {
+  uint64_t* meta_rp = nullptr;
+  uint32_t *occ_rp = nullptr, *perm = nullptr;
+  uint8_t *resc_rp = nullptr, *kind = nullptr;
+  unsigned long long* stat = nullptr;
+};
+
+int rescue_dev(const Sketch& sk, const OvlStore& S, const OvlParams& P, hipStream_t st, Bufs& B, const SortScratch& ms, uint32_t* flag, uint32_t* gidx,
+               uint32_t* rstart, const uint64_t* d_occ, Rescue& R, std::string& err) {
+  const uint32_t n = sk.n;
+  if (!rstart) {
+    OVL_TRY(B.get(&rstart, (uint64_t)n + 1));
+    k_heads<<<nblk(n, 256), 256, 0, st>>>(sk.hash, n, flag);
+    if (int rc = scan_u32(flag, n, gidx, ms.partial, st, err)) return rc;
+    k_gstart<<<nblk(n, 256), 256, 0, st>>>(flag, gidx, n, rstart);
+  }
+  OVL_TRY(B.get(&R.occ_rp, n));
+  OVL_TRY(B.get(&R.perm, n));
+  OVL_TRY(B.get(&R.resc_rp, n));
+  OVL_TRY(B.get(&R.kind, n));
+  OVL_TRY(B.get(&R.stat, 3));
+  OVL_TRY(hipMemsetAsync(R.resc_rp, 0, n, st));
+  OVL_TRY(hipMemsetAsync(R.stat, 0, 24, st));
+  k_occ_place<<<nblk(n, 256), 256, 0, st>>>(sk.meta, R.meta_rp, flag, gidx, rstart, n, R.occ_rp, R.perm);
+  if (P.occ_dist)                              // (0: the test hook with the setting off — the occurrences alone)
+    k_rescue<<<S.n_reads, 64, 0, st>>>(R.meta_rp, R.occ_rp, n, S.d_base_off, P.max_occ, d_occ, P.rescue_max_occ, P.occ_dist, R.resc_rp, R.stat);
+  k_resc_kind<<<nblk(n, 256), 256, 0, st>>>(R.perm, R.occ_rp, R.resc_rp, n, P.max_occ, d_occ, P.rescue_max_occ, R.kind);
+  OVL_TRY(hipGetLastError());
+  return OVL_OK;
+}
+
+// the copy of meta the rescue searches, taken while it is still in (rid, pos) order
+int rescue_keep_meta(const Sketch& sk, hipStream_t st, Bufs& B, Rescue& R, std::string& err) {
+  OVL_TRY(B.get(&R.meta_rp, sk.n));
+  OVL_TRY(hipMemcpyAsync(R.meta_rp, sk.meta, 8ull * sk.n, hipMemcpyDeviceToDevice, st));
   return OVL_OK;
 }
 
@@ -787,6 +1032,9 @@ int find_chunks(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, ui
   stats.distinct = frac ? nm : 0;
   if (nm < 2) { OVL_TRY(hipStreamSynchronize(st)); return OVL_OK; }
 
+  const bool rescue = P.occ_dist != 0;
+  Rescue R;
+  if (rescue) if (int rc = rescue_keep_meta(sk, st, B, R, err)) return rc;
   SortScratch ms;
   if (int rc = sort_by_hash(sk, P.k, st, B, ms, err)) return rc;
   uint32_t *d_cnt, *d_run_end, *d_cntm, *d_aoff;
@@ -800,7 +1048,16 @@ int find_chunks(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, ui
   OVL_TRY(hipMemsetAsync(d_per_read, 0, 8ull * S.n_reads, st));
   uint64_t* d_occ = nullptr;
   uint64_t occ[4] = {0, 0, 0, 0};
-  if (frac) {
+  unsigned long long resc_stat[3] = {0, 0, 0};
+  if (rescue) {
+    // the run starts serve the census and the rescue; the selection is done before any chunk is cut and without the mask
+    uint32_t *d_hist, *rstart = nullptr;
+    if (frac) if (int rc = occ_census_dev(sk.hash, nm, P, st, B, ms, d_cntm, d_aoff, &d_occ, &d_hist, err, &rstart)) return rc;
+    if (int rc = rescue_dev(sk, S, P, st, B, ms, d_cntm, d_aoff, rstart, d_occ, R, err)) return rc;
+    if (d_core) k_runs_resc<true><<<nblk(nm, 256), 256, 0, st>>>(sk.hash, sk.meta, nm, P.max_occ, d_occ, d_cnt, d_run_end, d_per_read, d_core, P.rescue_max_occ, R.kind, R.stat);
+    else k_runs_resc<false><<<nblk(nm, 256), 256, 0, st>>>(sk.hash, sk.meta, nm, P.max_occ, d_occ, d_cnt, d_run_end, d_per_read, nullptr, P.rescue_max_occ, R.kind, R.stat);
+    OVL_TRY(hipMemcpyAsync(resc_stat, R.stat, sizeof(resc_stat), hipMemcpyDeviceToHost, st));
+  } else if (frac) {
     // census, pick and k_runs_occ queue one behind the other: the cut stays on the device and comes back with per_read (d_cntm / d_aoff are free until the chunks)
     uint32_t* d_hist;
     if (int rc = occ_census_dev(sk.hash, nm, P, st, B, ms, d_cntm, d_aoff, &d_occ, &d_hist, err)) return rc;
@@ -814,6 +1071,7 @@ int find_chunks(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, ui
   if (frac) OVL_TRY(hipMemcpyAsync(occ, d_occ, sizeof(occ), hipMemcpyDeviceToHost, st));
   OVL_TRY(hipStreamSynchronize(st));
   if (frac) { stats.occ_cut = occ[0]; stats.distinct = occ[1]; stats.cut_runs = occ[2]; stats.cut_minimizers = occ[3]; }
+  if (rescue) { stats.resc_high = resc_stat[0]; stats.rescued = resc_stat[1]; stats.resc_anchors = resc_stat[2]; }
 
   // chunks: consecutive targets whose anchors fit the budget (a target with more runs alone)
   const uint64_t want = std::max<uint64_t>(budget_bytes / OVL_ANCHOR_BYTES, 1);
@@ -861,7 +1119,9 @@ int find_chunks(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, ui
     const uint32_t na = (uint32_t)na64;
     k_mask<<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cnt, nm, t_lo, t_hi, d_cntm);
     if (int rc = scan_u32(d_cntm, nm, d_aoff, ms.partial, st, err)) return rc;
-    if (d_core) k_expand<true><<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, d_core);
+    if (rescue && d_core) k_expand_resc<true><<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, d_core, R.kind);
+    else if (rescue) k_expand_resc<false><<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, nullptr, R.kind);
+    else if (d_core) k_expand<true><<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, d_core);
     else k_expand<false><<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, nullptr);
     OVL_TRY(hipGetLastError());
     {
@@ -918,6 +1178,30 @@ int ovl_occ_census(const OvlStore& S, const OvlParams& P, hipStream_t st, std::v
   if (hist) OVL_TRY(hipMemcpyAsync(hist->data(), d_hist, 4ull * OVL_OCC_BINS, hipMemcpyDeviceToHost, st));
   OVL_TRY(hipMemcpyAsync(rec, d_occ, 32, hipMemcpyDeviceToHost, st));
   OVL_TRY(hipStreamSynchronize(st));
+  return OVL_OK;
+}
+
+int ovl_seed_rescue(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vector<uint32_t>& occ, std::vector<uint8_t>& rescued, std::string& err) {
+  Bufs B;
+  Sketch sk;
+  if (int rc = sketch_dev(S, P, st, B, sk, err)) return rc;
+  occ.assign(sk.n, 1);
+  rescued.assign(sk.n, 0);
+  if (sk.n < 2) { OVL_TRY(hipStreamSynchronize(st)); return OVL_OK; }
+  Rescue R;
+  if (int rc = rescue_keep_meta(sk, st, B, R, err)) return rc;
+  SortScratch ms;
+  if (int rc = sort_by_hash(sk, P.k, st, B, ms, err)) return rc;
+  uint32_t *flag, *gidx, *d_hist, *rstart = nullptr;
+  uint64_t* d_occ = nullptr;
+  OVL_TRY(B.get(&flag, sk.n));
+  OVL_TRY(B.get(&gidx, (uint64_t)sk.n + 1));
+  if (P.occ_frac_ppm) if (int rc = occ_census_dev(sk.hash, sk.n, P, st, B, ms, flag, gidx, &d_occ, &d_hist, err, &rstart)) return rc;
+  if (int rc = rescue_dev(sk, S, P, st, B, ms, flag, gidx, rstart, d_occ, R, err)) return rc;
+  OVL_TRY(hipMemcpyAsync(occ.data(), R.occ_rp, 4ull * sk.n, hipMemcpyDeviceToHost, st));
+  OVL_TRY(hipMemcpyAsync(rescued.data(), R.resc_rp, sk.n, hipMemcpyDeviceToHost, st));
+  OVL_TRY(hipStreamSynchronize(st));
+  for (uint32_t& c : occ) c = std::min(c, OVL_OCC_BINS - 1);
   return OVL_OK;
 }
 

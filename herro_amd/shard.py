@@ -699,7 +699,7 @@ def core_masks(read_lens, window_size: int, world: int) -> list[np.ndarray]:
 def correct_reads_shard(ctx, mask, window_size: int, batch: int, batch_mode: int, read_name, group_targets: int = 1024, **finder_params):
     """Reads-only correction of one shard on `ctx` (reads and model loaded): find_overlap_pairs(core=mask) -> align -> jobs of at most
     `group_targets` targets cut from the table -> featurize -> infer -> consensus -> FASTA.  Rows whose record failed are dropped
-    (api.paired_job_args).  finder_params: find_overlap_pairs' keywords.  Returns (rids, ends, text) as merge_records takes them."""
+    (api.paired_job_args).  finder_params: find_overlap_pairs' keywords, occ_dist / rescue_max_occ (the rescue of high-frequency minimizers) among them.  Returns (rids, ends, text) as merge_records takes them."""
     from . import api
     pairs = ctx.find_overlap_pairs(core=mask, **finder_params)
     m = pairs.align()

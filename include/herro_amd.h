@@ -593,6 +593,30 @@ int herro_pairs_from_table_core(herro_ctx* ctx, uint32_t n_pairs, const herro_al
 uint64_t herro_pairs_n_rows(const herro_pairs* pairs);
 uint32_t herro_pairs_occ_cut(const herro_pairs* pairs);                    /* the frequency cut the finder used; 0: a handle over a table */
 
+/* ---- rescue of high-frequency minimizers (minimap2's -e, the reference's -e200: mm2.rs:24) ---------------------
+ * Without it every hash above the frequency cut is dropped, so a read that lies inside a high-copy repeat gets no anchor at all.  With it,
+ * of a stretch of a read whose minimizers all lie above the cut the least frequent ones stay, about one per occ_dist bases.  The rule is the
+ * finder's own (tests/rescue_ref.py), all integer and independent of thread order; it does not reproduce minimap2's choice of seeds.
+ *   occ(x) = occurrences of x's hash in the whole store; cut = the frequency cut the call uses anyway (max_occ or occ_frac_ppm's).
+ *   x is U if 2 <= occ <= cut, H if cut < occ <= rescue_max_occ, transparent otherwise (singletons and hashes above rescue_max_occ
+ *   neither end a streak nor are rescued).  Per read, over its U and H minimizers in ascending pos, a streak is a maximal run of H; ps = the
+ *   pos of the U in front of it (0: none), pe = the pos of the U behind it (the read's length: none), m = (2 (pe - ps) + occ_dist) /
+ *   (2 occ_dist).  The m members with the least (occ, pos) are rescued — all of them if m >= the streak's size.
+ *   Two occurrences of one hash in reads t < q give an anchor iff 2 <= occ <= cut, or cut < occ <= rescue_max_occ and one of the two is
+ *   rescued.  The core rule is applied on top; the selection itself sees neither the mask nor the scratch budget, so a masked result is a
+ *   selection of the unmasked one and the bytes are the same for every HERRO_OVL_SCRATCH_MB.
+ * herro_overlap_params has no spare field, so the switch is a setting of the context, as herro_set_precision is: it holds for every later
+ * herro_find_overlaps[_core] and herro_find_overlap_pairs[_core].  params NULL or occ_dist 0: off — every call returns what it returned before
+ * the setting existed and launches none of the rescue's kernels.  rescue_max_occ 0 = 4095.  occ_dist > 2^20, rescue_max_occ > 65534 or a
+ * non-zero reserved field: HERRO_E_INVALID (checked here; works on a context without a device).  herro_overlaps_rescued / herro_pairs_rescued:
+ * the minimizers the call rescued (0: off, or a handle made by herro_pairs_from_table*).  HERRO_OVL_STATS=1 adds a line `OVLRESC high=
+ * rescued= anchors=`: the H minimizers, the rescued ones, the anchors of the hashes above the cut.  Known interaction: rescued hashes inside a
+ * tandem repeat add off-diagonal anchors, and the 64-anchor look-back limit above applies to them too. */
+typedef struct { uint32_t occ_dist, rescue_max_occ, reserved[2]; } herro_seed_rescue_params;
+int herro_set_seed_rescue(herro_ctx* ctx, const herro_seed_rescue_params* params /* NULL: off */);
+uint32_t herro_overlaps_rescued(const herro_overlaps* o);
+uint32_t herro_pairs_rescued(const herro_pairs* pairs);
+
 /* ---- found alignments as PAF / .oec.zst --------------------------------------------------------------------
  * What `herro inference --write-alns DIR` keeps of a batch (AlnMode::Write, overlaps.rs:248-286; the lines, 349-352), for the alignments this
  * library found itself: herro_oec_read / herro_paf_parse* read the result back, and so does the reference's --read-alns.  One line per row,
@@ -635,6 +659,10 @@ int herro_pairs_write_alns(herro_ctx* ctx, const herro_pairs* pairs, const herro
 /* Test hook: the census and the pick of occ_frac_ppm alone (occ_frac_ppm 0: HERRO_E_INVALID).  hist: the 65536 bins of min(occurrences,
  * 65535) over the distinct hashes; out = {cut, distinct hashes, hashes above the cut, minimizers in them}. */
 int herro_debug_occ_census(herro_ctx* ctx, const herro_overlap_params* params, uint32_t* hist /* [65536] or NULL */, uint64_t out[4]);
+/* Test hook: the rescue alone, under the context's herro_set_seed_rescue setting (off: no flag is set).  For the minimizers in
+ * herro_debug_sketch's (rid, pos) order: occ = min(occurrences of the hash in the store, 65535), rescued = 1 where the minimizer is rescued.
+ * Returns their number (nothing is written when cap is smaller) or a negative error. */
+int64_t herro_debug_seed_rescue(herro_ctx* ctx, const herro_overlap_params* params, uint32_t* occ, uint8_t* rescued, uint64_t cap);
 /* Test hook: stage 1 alone — the store's minimizers sorted by (rid, pos); pos = index of the k-mer's last base on the forward
  * read, strand = 1 when the reverse complement is the canonical k-mer.  Returns their number (nothing is written when cap is
  * smaller) or a negative error. */

@@ -5,9 +5,11 @@ overlaps each) and reads of >= 30 kb.  Prints one JSON line per set; run it unde
 kernels alone.
 --occ-frac-ppm N: every set is measured three times on one context — with the fixed cut, with the cut taken from the index (occ_frac_ppm = N)
 and with the fixed cut set to the value the index gave, so that the last two differ by the census and the pick alone (`occ_share`).
+--occ-dist N [--rescue-max-occ M]: every call rescues high-frequency minimizers (Context.set_seed_rescue; 200 = minimap2 -e200); the sizes gain
+resc_high, resc_rescued and resc_anchors.
 --deep: one short genome under many reads (--deep-reads 200 of --deep-len 400 bases), the shape a fixed cut below the depth finds nothing in.
 
-    python tools/overlaprate.py [--targets 256] [--long-targets 8] [--reps 5] [--no-align] [--occ-frac-ppm 5000] [--deep]"""
+    python tools/overlaprate.py [--targets 256] [--long-targets 8] [--reps 5] [--no-align] [--occ-frac-ppm 5000] [--occ-dist 200] [--deep]"""
 from __future__ import annotations
 
 import argparse
@@ -40,7 +42,7 @@ def stage_sizes(fn):
         f.seek(0)
         text = f.read().decode(errors="replace")
     sizes = {}
-    for tag, prefix in (("OVL", ""), ("OVLOCC", "occ_")):
+    for tag, prefix in (("OVL", ""), ("OVLOCC", "occ_"), ("OVLRESC", "resc_")):
         m = re.search(tag + r" (.*)", text)
         if m:
             sizes.update({prefix + k: int(v) for k, v in (kv.split("=") for kv in m.group(1).split())})
@@ -67,9 +69,12 @@ class Deep:
         self.off = (np.arange(n + 1) * L).astype(np.uint64)
 
 
-def measure(name, sb, reps, params, align, occ_frac_ppm=0):
+def measure(name, sb, reps, params, align, occ_frac_ppm=0, rescue=(0, 0)):
     c = api.Context(0)
     c.set_reads(sb.seq, sb.qual, sb.off)
+    if rescue[0]:
+        c.set_seed_rescue(*rescue)
+        name += f" occ_dist={rescue[0]}"
     if occ_frac_ppm:
         fixed = measure_on(c, name, sb, reps, params, False)
         frac = measure_on(c, name, sb, reps, dict({k: v for k, v in params.items() if k != "max_occ"}, occ_frac_ppm=occ_frac_ppm), align)
@@ -119,19 +124,22 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-align", action="store_true")
     ap.add_argument("--occ-frac-ppm", type=int, default=0, help="also measure with the cut taken from the index (5000 = minimap2 -f0.005)")
+    ap.add_argument("--occ-dist", type=int, default=0, help="rescue high-frequency minimizers, about one per N bases (200 = minimap2 -e200)")
+    ap.add_argument("--rescue-max-occ", type=int, default=0, help="with --occ-dist: hashes above this many occurrences are never rescued (0: 4095)")
     ap.add_argument("--deep", action="store_true", help="only the deep shape: one short genome under many reads")
     ap.add_argument("--deep-reads", type=int, default=200)
     ap.add_argument("--deep-len", type=int, default=400)
     a = ap.parse_args()
+    rescue = (a.occ_dist, a.rescue_max_occ)
     if a.deep:
-        measure("deep", Deep(a.deep_reads, a.deep_len), a.reps, dict(k=15, w=5, max_occ=128, min_score=60), not a.no_align, a.occ_frac_ppm)
+        measure("deep", Deep(a.deep_reads, a.deep_len), a.reps, dict(k=15, w=5, max_occ=128, min_score=60), not a.no_align, a.occ_frac_ppm, rescue)
         return
     if a.targets:
         measure("bench shape", synth.generate_parallel(a.targets, a.target_len, a.overlaps, chunk=64), a.reps,
-                dict(max_occ=128, min_score=100), not a.no_align, a.occ_frac_ppm)
+                dict(max_occ=128, min_score=100), not a.no_align, a.occ_frac_ppm, rescue)
     if a.long_targets:
         measure(">= 30 kb", synth.generate_parallel(a.long_targets, a.long_len, 16, chunk=4, flank_min=200, flank_max=400), a.reps,
-                dict(max_occ=128), not a.no_align, a.occ_frac_ppm)
+                dict(max_occ=128), not a.no_align, a.occ_frac_ppm, rescue)
 
 
 if __name__ == "__main__":
