@@ -49,6 +49,9 @@ EXPORTS = [
     "herro_aligned_dev_paf", "herro_pairs_paf", "herro_paf_text_data", "herro_paf_text_len", "herro_paf_text_lines", "herro_paf_text_free",
     "herro_pairs_write_alns",
     "herro_set_seed_rescue", "herro_overlaps_rescued", "herro_pairs_rescued", "herro_debug_seed_rescue",
+    "herro_find_adapters", "herro_adapter_hits_n", "herro_adapter_hits_data", "herro_adapter_hits_off", "herro_adapter_hits_free", "herro_debug_set_adapter_cap",
+    "herro_trim_plan", "herro_trim_n_pieces", "herro_trim_pieces", "herro_trim_piece_off", "herro_trim_stats", "herro_trim_free",
+    "herro_reads_create", "herro_reads_cut",
 ]
 
 
@@ -109,6 +112,20 @@ class SeedRescueParams(C.Structure):  # herro_seed_rescue_params (occ_dist 0 = o
 
 class ExtendParams(C.Structure):  # herro_extend_params (0 = the field's default)
     _fields_ = [("zdrop", C.c_uint32), ("max_ext", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+ADAPTERS_FORWARD_ONLY = 1    # HERRO_ADAPTERS_FORWARD_ONLY
+TRIM_DISCARD_CHIMERAS = 1    # HERRO_TRIM_DISCARD_CHIMERAS
+ADAPTER_HIT_DTYPE = np.dtype([("rid", "<u4"), ("start", "<u4"), ("end", "<u4"), ("adapter", "<u2"), ("strand", "u1"), ("errors", "u1")])   # herro_adapter_hit
+PIECE_DTYPE = np.dtype([("rid", "<u4"), ("start", "<u4"), ("end", "<u4")])   # herro_piece
+
+
+class AdapterParams(C.Structure):  # herro_adapter_params (0 = the field's default)
+    _fields_ = [("max_err_pm", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class TrimParams(C.Structure):  # herro_trim_params (0 = the field's default)
+    _fields_ = [(n, C.c_uint32) for n in ("end_window", "end_max_err_pm", "mid_max_err_pm", "min_length", "flags")] + [("reserved", C.c_uint32 * 3)]
 
 
 class WindowInfo(C.Structure):  # herro_window_info
@@ -315,6 +332,29 @@ def lib():
             L.herro_paf_text_free.restype = None
             L.herro_paf_text_free.argtypes = [vp]
             L.herro_pairs_write_alns.argtypes = [vp, vp, vp, C.c_char_p, vp, C.c_char_p, u32, vp, vp]
+        except AttributeError:
+            if not os.environ.get("HERRO_LIB"):
+                raise
+        try:   # (an older build selected by HERRO_LIB lacks the adapter step: everything else still runs)
+            L.herro_find_adapters.argtypes = [vp, u32, C.c_char_p, vp, vp, vp]
+            L.herro_adapter_hits_n.restype = u64
+            L.herro_adapter_hits_n.argtypes = [vp]
+            for f in (L.herro_adapter_hits_data, L.herro_adapter_hits_off, L.herro_trim_pieces, L.herro_trim_piece_off):
+                f.restype = vp
+                f.argtypes = [vp]
+            L.herro_adapter_hits_free.restype = None
+            L.herro_adapter_hits_free.argtypes = [vp]
+            L.herro_debug_set_adapter_cap.argtypes = [vp, u64]
+            L.herro_trim_plan.argtypes = [u32, vp, u32, vp, vp, vp, vp, vp, vp, u64]
+            L.herro_trim_n_pieces.restype = u64
+            L.herro_trim_n_pieces.argtypes = [vp]
+            L.herro_trim_stats.argtypes = [vp, vp]
+            L.herro_trim_free.restype = None
+            L.herro_trim_free.argtypes = [vp]
+            L.herro_reads_create.restype = vp
+            L.herro_reads_create.argtypes = [u32, vp, vp, vp, vp, vp, vp, u64]
+            L.herro_reads_cut.restype = vp
+            L.herro_reads_cut.argtypes = [vp, u64, vp, vp, u64]
         except AttributeError:
             if not os.environ.get("HERRO_LIB"):
                 raise
@@ -862,6 +902,33 @@ class Context:
         finally:
             self._l.herro_extended_free(h)
         return out, ext, scores
+
+    def find_adapters(self, adapters, max_err_pm: int = 0, forward_only: bool = False):
+        """Approximate matches of every adapter in every read of the store, both strands (herro_find_adapters): adapters = byte strings of 8 .. 64
+        bases ACGT, at most 32; up to floor(len * max_err_pm / 1000) errors (0: 250, at most 500); forward_only: strand 0 alone.
+        Returns (hits ADAPTER_HIT_DTYPE ascending (rid, end, start, adapter, strand), hits_off u64 [n_reads + 1]): the arguments of trim_plan."""
+        adapters = [bytes(a) for a in adapters]
+        if not 0 <= int(max_err_pm) <= 0xFFFFFFFF:
+            raise HerroError(-1, "herro_find_adapters: max_err_pm is an unsigned 32-bit value")
+        off = np.zeros(len(adapters) + 1, np.uint64)
+        off[1:] = np.cumsum([len(a) for a in adapters])
+        p = AdapterParams(max_err_pm=int(max_err_pm), flags=ADAPTERS_FORWARD_ONLY if forward_only else 0)
+        h = C.c_void_p()
+        self._chk(self._l.herro_find_adapters(self.h, len(adapters), b"".join(adapters), off.ctypes.data, C.byref(p), C.byref(h)))
+        try:
+            n = int(self._l.herro_adapter_hits_n(h))
+            hits = np.zeros(n, ADAPTER_HIT_DTYPE)
+            if n:
+                C.memmove(hits.ctypes.data, self._l.herro_adapter_hits_data(h), hits.nbytes)
+            hits_off = np.zeros(self.n_reads + 1, np.uint64)
+            C.memmove(hits_off.ctypes.data, self._l.herro_adapter_hits_off(h), hits_off.nbytes)
+        finally:
+            self._l.herro_adapter_hits_free(h)
+        return hits, hits_off
+
+    def adapter_cap(self, cap: int):
+        """Test hook (herro_debug_set_adapter_cap): the hits the first scan's buffer of every later find_adapters holds; 0: the default."""
+        self._chk(self._l.herro_debug_set_adapter_cap(self.h, int(cap)))
 
     def find_overlap_pairs(self, extend: bool = True, zdrop: int = 0, max_ext: int = 0, core=None, **params) -> "OverlapPairs":
         """find_overlaps, pair_rows, extend_overlaps over the primaries and paired_job_args' table in one call that keeps the records on the
@@ -1438,6 +1505,61 @@ def aligned_dev_job_args(rids, aln_off, ok: np.ndarray):
     ok = np.asarray(ok, bool)
     kept = np.concatenate([[0], np.cumsum(ok)]).astype(np.int64)
     return rids, kept[aln_off].astype(np.uint64), np.flatnonzero(ok).astype(np.uint32)
+
+
+TrimStats = collections.namedtuple("TrimStats", "reads_trimmed reads_split reads_dropped bases_removed")
+
+
+def trim_plan(read_len, adapter_len, hits, hits_off, end_window: int = 0, end_max_err_pm: int = 0, mid_max_err_pm: int = 0, min_length: int = 0,
+              discard_chimeras: bool = False):
+    """The pieces of every read that stay, from find_adapters' hits (herro_trim_plan; host code, no device): adapters at the read ends are trimmed,
+    a read is split at an adapter in its middle (discard_chimeras: dropped), pieces shorter than min_length are dropped.  0 = the default:
+    end_window 150, end_max_err_pm 250, mid_max_err_pm 100.  read_len u32 [n_reads], adapter_len u32 [n_adapters].
+    Returns (pieces PIECE_DTYPE grouped by read, piece_off u64 [n_reads + 1], TrimStats); ValueError with the library's message on a bad table."""
+    L = lib()
+    rl = np.ascontiguousarray(read_len, np.uint32)
+    al = np.ascontiguousarray(adapter_len, np.uint32)
+    hits = np.ascontiguousarray(hits, ADAPTER_HIT_DTYPE)
+    ho = np.ascontiguousarray(hits_off, np.uint64)
+    if len(ho) != len(rl) + 1:
+        raise ValueError("herro_trim_plan: hits_off has n_reads + 1 entries")
+    if len(ho) and int(ho.max()) > len(hits):
+        raise ValueError("herro_trim_plan: hits_off reaches beyond the hits")
+    p = TrimParams(end_window=int(end_window), end_max_err_pm=int(end_max_err_pm), mid_max_err_pm=int(mid_max_err_pm), min_length=int(min_length),
+                   flags=TRIM_DISCARD_CHIMERAS if discard_chimeras else 0)
+    return _trim_plan(L, rl, al, hits, ho, p)
+
+
+def _trim_plan(L, rl, al, hits, ho, p):
+    h, err = C.c_void_p(), C.create_string_buffer(256)
+    rc = L.herro_trim_plan(len(rl), rl.ctypes.data, len(al), al.ctypes.data, hits.ctypes.data, ho.ctypes.data, C.byref(p), C.byref(h), err, 256)
+    if rc:
+        raise ValueError(err.value.decode())
+    try:
+        n = int(L.herro_trim_n_pieces(h))
+        pieces = np.zeros(n, PIECE_DTYPE)
+        if n:
+            C.memmove(pieces.ctypes.data, L.herro_trim_pieces(h), pieces.nbytes)
+        piece_off = np.zeros(len(rl) + 1, np.uint64)
+        C.memmove(piece_off.ctypes.data, L.herro_trim_piece_off(h), piece_off.nbytes)
+        st = (C.c_uint64 * 4)()
+        L.herro_trim_stats(h, st)
+    finally:
+        L.herro_trim_free(h)
+    return pieces, piece_off, TrimStats(*[int(x) for x in st])
+
+
+def trim_reads(ctx: "Context", reads, adapters, max_err_pm: int = 0, forward_only: bool = False, **plan_params):
+    """Raw reads to a trimmed store in one call: set_reads(reads), find_adapters, trim_plan, io.cut_reads, set_reads(the cut reads).  reads: an
+    io.Reads; adapters, max_err_pm, forward_only as find_adapters; plan_params as trim_plan.  Returns (the cut io.Reads — what the store now
+    holds —, TrimStats)."""
+    from . import io
+    ctx.set_reads(reads.seq, reads.qual, reads.off)
+    hits, hits_off = ctx.find_adapters(adapters, max_err_pm=max_err_pm, forward_only=forward_only)
+    pieces, _, stats = trim_plan(np.diff(np.asarray(reads.off, np.uint64)).astype(np.uint32), [len(a) for a in adapters], hits, hits_off, **plan_params)
+    cut = io.cut_reads(reads, pieces)
+    ctx.set_reads(cut.seq, cut.qual, cut.off)
+    return cut, stats
 
 
 def pair_rows(rows: np.ndarray, exact_ids: bool = False):

@@ -132,6 +132,7 @@ struct herro_ctx {
   // its memory is freed when the last context holding it lets go
   std::shared_ptr<void> store_owner;
   herro_seed_rescue_params seed_rescue{};   // herro_set_seed_rescue: occ_dist 0 = off; rescue_max_occ as given (0 = 4095 where it is used)
+  uint64_t debug_adapter_cap = 0;           // herro_debug_set_adapter_cap: hits the first scan's buffer of herro_find_adapters holds (0: the default)
   // model
   bool has_model = false;
   herro::ModelDev M{};

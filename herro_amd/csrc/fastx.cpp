@@ -19,6 +19,8 @@
 //                           header written here is the one numpy itself writes for these arrays: magic, version 1.0, the dict
 //                           {'descr': ..., 'fortran_order': False, 'shape': (...), } padded with spaces to a multiple of 64
 //                           bytes, '\n' last.
+//   herro_reads_create, herro_trim_plan, herro_reads_cut   the host side of the adapter step: a reads handle over the caller's
+//                           arrays, the pieces that stay of every read (trim_plan.h) and the reads cut to them.
 //
 // zlib is used through the system's libz.so.1 (stable C ABI), loaded on first use: the library keeps no link-time dependency
 // beyond the HIP runtime and libstdc++.
@@ -42,6 +44,7 @@
 #include <vector>
 
 #include "host_cpus.h"
+#include "trim_plan.h"
 #include "../../include/herro_amd.h"
 
 struct herro_reads {
@@ -524,6 +527,108 @@ const uint64_t* herro_reads_off(const herro_reads* r) { return r ? r->off.data()
 const char* const* herro_reads_ids(const herro_reads* r) { return r ? r->id_ptr.data() : nullptr; }
 const char* const* herro_reads_descs(const herro_reads* r) { return r ? r->desc_ptr.data() : nullptr; }
 void herro_reads_free(herro_reads* r) { delete r; }
+
+// ---- adapters: the plan and its application (include/herro_amd.h, "adapters"; the rule itself is trim_plan.h) ---------------------------------
+static void reads_finish(herro_reads* r) {
+  for (size_t i = 0; i < r->ids.size(); i++) {
+    r->id_ptr.push_back(r->ids[i].c_str());
+    r->desc_ptr.push_back(r->has_desc[i] ? r->descs[i].c_str() : nullptr);
+  }
+}
+
+herro_reads* herro_reads_create(uint32_t n, const uint8_t* seq, const uint8_t* qual, const uint64_t* off, const char* const* ids,
+                                const char* const* descs, char* err, uint64_t err_cap) {
+  try {
+    if (!off || (n && !ids) || off[0] != 0) { set_err(err, err_cap, "herro_reads_create: null argument, or off does not ascend from 0"); return nullptr; }
+    for (uint32_t i = 0; i < n; i++) {
+      if (off[i + 1] < off[i]) { set_err(err, err_cap, "herro_reads_create: off[" + std::to_string(i + 1) + "]: off must ascend from 0"); return nullptr; }
+      if (!ids[i]) { set_err(err, err_cap, "herro_reads_create: read " + std::to_string(i) + " has no id"); return nullptr; }
+    }
+    if (off[n] && (!seq || !qual)) { set_err(err, err_cap, "herro_reads_create: null argument"); return nullptr; }
+    std::unique_ptr<herro_reads> r(new herro_reads());
+    r->seq.assign(seq, seq + off[n]);
+    r->qual.assign(qual, qual + off[n]);
+    r->off.assign(off, off + n + 1);
+    for (uint32_t i = 0; i < n; i++) {
+      r->ids.emplace_back(ids[i]);
+      const bool d = descs && descs[i];
+      r->has_desc.push_back(d);
+      r->descs.emplace_back(d ? descs[i] : "");
+    }
+    reads_finish(r.get());
+    return r.release();
+  } catch (const std::exception& e) {
+    set_err(err, err_cap, std::string("herro_reads_create: ") + e.what());
+  }
+  return nullptr;
+}
+
+herro_reads* herro_reads_cut(const herro_reads* src, uint64_t n_pieces, const herro_piece* pieces, char* err, uint64_t err_cap) {
+  try {
+    if (!src || (n_pieces && !pieces)) { set_err(err, err_cap, "herro_reads_cut: null argument"); return nullptr; }
+    if (n_pieces > 0xffffffffull) { set_err(err, err_cap, "herro_reads_cut: more than 2^32 - 1 pieces"); return nullptr; }
+    const uint32_t n = (uint32_t)src->ids.size();
+    std::vector<uint32_t> per_read(n, 0);                 // pieces of every read in the table: one keeps the id, more are numbered
+    uint64_t bases = 0;
+    for (uint64_t x = 0; x < n_pieces; x++) {
+      const herro_piece& p = pieces[x];
+      const char* bad = p.rid >= n ? "rid outside the reads" : p.start > p.end ? "start > end" :
+                        p.end > src->off[p.rid + 1] - src->off[p.rid] ? "end beyond the read" : nullptr;
+      if (bad) { set_err(err, err_cap, "herro_reads_cut: piece " + std::to_string(x) + ": " + bad); return nullptr; }
+      per_read[p.rid]++;
+      bases += p.end - p.start;
+    }
+    const uint8_t* const seq = herro_reads_seq(src);
+    const uint8_t* const qual = herro_reads_qual(src);
+    std::unique_ptr<herro_reads> r(new herro_reads());
+    r->seq.reserve(bases);
+    r->qual.reserve(bases);
+    r->off.push_back(0);
+    std::vector<uint32_t> seen(n, 0);
+    for (uint64_t x = 0; x < n_pieces; x++) {
+      const herro_piece& p = pieces[x];
+      const uint64_t at = src->off[p.rid];
+      r->seq.insert(r->seq.end(), seq + at + p.start, seq + at + p.end);
+      r->qual.insert(r->qual.end(), qual + at + p.start, qual + at + p.end);
+      r->off.push_back(r->seq.size());
+      r->ids.push_back(per_read[p.rid] > 1 ? src->ids[p.rid] + "_" + std::to_string(++seen[p.rid]) : src->ids[p.rid]);
+      r->has_desc.push_back(src->has_desc[p.rid]);
+      r->descs.push_back(src->descs[p.rid]);
+    }
+    reads_finish(r.get());
+    return r.release();
+  } catch (const std::exception& e) {
+    set_err(err, err_cap, std::string("herro_reads_cut: ") + e.what());
+  }
+  return nullptr;
+}
+
+int herro_trim_plan(uint32_t n_reads, const uint32_t* read_len, uint32_t n_adapters, const uint32_t* adapter_len, const herro_adapter_hit* hits,
+                    const uint64_t* hits_off, const herro_trim_params* params, herro_trim** out, char* err, uint64_t err_cap) {
+  if (!out) { set_err(err, err_cap, "herro_trim_plan: null argument"); return HERRO_E_INVALID; }
+  *out = nullptr;
+  try {
+    std::unique_ptr<herro_trim> t(new herro_trim());
+    std::string why;
+    const int rc = herro::trim_plan(n_reads, read_len, n_adapters, adapter_len, hits, hits_off, params, *t, why);
+    if (rc != HERRO_OK) { set_err(err, err_cap, why); return rc; }
+    *out = t.release();
+    return HERRO_OK;
+  } catch (const std::exception& e) {
+    set_err(err, err_cap, std::string("herro_trim_plan: ") + e.what());
+  }
+  return HERRO_E_INVALID;
+}
+
+uint64_t herro_trim_n_pieces(const herro_trim* t) { return t ? t->pieces.size() : 0; }
+const herro_piece* herro_trim_pieces(const herro_trim* t) { return t ? t->pieces.data() : nullptr; }
+const uint64_t* herro_trim_piece_off(const herro_trim* t) { return t ? t->piece_off.data() : nullptr; }
+int herro_trim_stats(const herro_trim* t, uint64_t out[4]) {
+  if (!t || !out) return HERRO_E_INVALID;
+  for (int i = 0; i < 4; i++) out[i] = t->stats[i];
+  return HERRO_OK;
+}
+void herro_trim_free(herro_trim* t) { delete t; }
 
 int herro_write_window_features(const char* dir, uint32_t wid, const char* const* ids, uint32_t n_ids, const uint8_t* bases,
                                 const uint8_t* quals, uint32_t length, const uint16_t* sup_pos, const uint8_t* sup_ins,

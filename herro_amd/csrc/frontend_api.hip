@@ -1,13 +1,16 @@
 // frontend_api.hip — the C ABI's front end (include/herro_amd.h): reads alone -> overlap records -> their ops on the device.
 // herro_find_overlaps[_core], herro_extend_overlaps, herro_align_overlaps[_dev], herro_aligned_dev_*, herro_find_overlap_pairs[_core], herro_pairs_*, the PAF / .oec.zst
 // writer (herro_aligned_dev_paf, herro_pairs_paf, herro_pairs_write_alns) herro_set_seed_rescue and the test hooks herro_debug_sketch, herro_debug_occ_census and herro_debug_seed_rescue.  Host C++ (compiled by
-// hipcc) over overlap_dev.hip, align_dev.hip and paf_dev.hip; contexts, the model and jobs are herro_api.hip.
+// hipcc) over overlap_dev.hip, align_dev.hip and paf_dev.hip; contexts, the model and jobs are herro_api.hip.  Ahead of them all, for raw reads:
+// herro_find_adapters and its handle, over adapter_dev.hip (the plan and the cut are host code: fastx.cpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstdio>
 #include <cstring>
 
+#include "adapter_dev.h"
 #include "aligned_dev.h"
 #include "align_dev.h"
 #include "alns_file.h"
@@ -1097,6 +1100,110 @@ int herro_debug_occ_census(herro_ctx* ctx, const herro_overlap_params* params, u
   std::string msg;
   if (int rc = overlap_rc(ctx, herro::ovl_occ_census(ovl_store(ctx), P, ctx->stream, hist ? &h : nullptr, out, msg), msg)) return rc;
   if (hist) std::memcpy(hist, h.data(), 4ull * herro::OVL_OCC_BINS);
+  return HERRO_OK;
+}
+
+// ---- adapters in the resident reads (adapter_dev.hip) --------------------------------------------------------------
+// The host's share: the pattern table (both strands, their bit planes), the segment length, and the order of the hits — the kernels append
+// them in no order, the specification's key (rid, end, start, adapter, strand) is unique per hit, and sorting by it gives the bytes.
+struct herro_adapter_hits {
+  std::vector<herro_adapter_hit> hits;
+  std::vector<uint64_t> off;             // [n_reads + 1]
+};
+
+int herro_find_adapters(herro_ctx* ctx, uint32_t n_adapters, const char* seq, const uint64_t* off, const herro_adapter_params* params,
+                        herro_adapter_hits** out) {
+  if (!ctx || !out) return HERRO_E_INVALID;
+  *out = nullptr;
+  const char* const who = "herro_find_adapters";
+  const herro_adapter_params z{};
+  const herro_adapter_params& p = params ? *params : z;
+  const uint32_t pm = p.max_err_pm ? p.max_err_pm : 250;
+  if (pm > 500 || (p.flags & ~HERRO_ADAPTERS_FORWARD_ONLY) || p.reserved[0] || p.reserved[1]) {
+    ctx->err = std::string(who) + ": max_err_pm <= 500 (0: 250), flags HERRO_ADAPTERS_FORWARD_ONLY or 0, reserved fields 0";
+    return HERRO_E_INVALID;
+  }
+  if (n_adapters < 1 || n_adapters > 32 || !seq || !off) { ctx->err = std::string(who) + ": 1 <= n_adapters <= 32, seq and off not NULL"; return HERRO_E_INVALID; }
+  std::vector<herro::AdaptPattern> pats(2 * (size_t)n_adapters, herro::AdaptPattern{});
+  for (uint32_t a = 0; a < n_adapters; a++) {
+    if (off[a + 1] < off[a] || off[a + 1] - off[a] < 8 || off[a + 1] - off[a] > 64) {
+      ctx->err = std::string(who) + ": adapter " + std::to_string(a) + ": 8 <= length <= 64";
+      return HERRO_E_INVALID;
+    }
+    const uint32_t m = (uint32_t)(off[a + 1] - off[a]);
+    uint8_t code[64];
+    for (uint32_t i = 0; i < m; i++) {
+      switch (seq[off[a] + i]) {
+        case 'A': case 'a': code[i] = 0; break;
+        case 'C': case 'c': code[i] = 1; break;
+        case 'G': case 'g': code[i] = 2; break;
+        case 'T': case 't': code[i] = 3; break;
+        default:
+          ctx->err = std::string(who) + ": adapter " + std::to_string(a) + ": base " + std::to_string(i) + " is not A, C, G or T";
+          return HERRO_E_INVALID;
+      }
+    }
+    for (uint32_t s = 0; s < ((p.flags & HERRO_ADAPTERS_FORWARD_ONLY) ? 1u : 2u); s++) {
+      uint64_t f0 = 0, f1 = 0, b0 = 0, b1 = 0;   // the planes of the pattern and of the pattern reversed
+      for (uint32_t i = 0; i < m; i++) {
+        const uint64_t c = s ? 3u - code[m - 1 - i] : code[i];   // strand 1: the reverse complement
+        f0 |= (c & 1u) << i;           f1 |= (c >> 1) << i;
+        b0 |= (c & 1u) << (m - 1 - i); b1 |= (c >> 1) << (m - 1 - i);
+      }
+      pats[2 * a + s] = herro::AdaptPattern{~f0, ~f1, ~b0, ~b1, m, (uint32_t)((uint64_t)m * pm / 1000), (uint16_t)a, (uint8_t)s, 0, 0};
+    }
+  }
+  if (int rc = device_ready(ctx, who)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  uint32_t seg = herro::ADAPT_SEG_DEFAULT;
+  if (const char* e = getenv("HERRO_ADAPT_SEG")) seg = (uint32_t)std::min<long long>(std::max<long long>(atoll(e), herro::ADAPT_SEG_MIN), herro::ADAPT_SEG_MAX);
+  std::unique_ptr<herro_adapter_hits> h(new herro_adapter_hits());
+  herro::AdaptStats stats;
+  std::string msg;
+  const herro::AdaptStore S{ctx->d_p0, ctx->d_p1, ctx->d_word_off, ctx->d_qual_off, ctx->read_len.data(), ctx->n_reads};
+  const int rc = herro::adapt_find(S, pats, seg, ctx->debug_adapter_cap, ctx->stream, h->hits, stats, msg);
+  if (rc != herro::ADAPT_OK) { ctx->err = msg; return rc == herro::ADAPT_UNSUPPORTED ? HERRO_E_UNSUPPORTED : HERRO_E_NO_DEVICE; }
+  const auto t0 = std::chrono::steady_clock::now();
+  // by read first (a counting sort: the offsets are the result's anyway), then every read's hits by the rest of the key on the pool
+  h->off.assign((size_t)ctx->n_reads + 1, 0);
+  for (const herro_adapter_hit& x : h->hits) h->off[x.rid + 1]++;
+  for (uint32_t r = 0; r < ctx->n_reads; r++) h->off[r + 1] += h->off[r];
+  {
+    std::vector<herro_adapter_hit> by_read(h->hits.size());
+    std::vector<uint64_t> at(h->off.begin(), h->off.end() - 1);
+    for (const herro_adapter_hit& x : h->hits) by_read[at[x.rid]++] = x;
+    h->hits.swap(by_read);
+  }
+  constexpr uint32_t READS_PER_TASK = 1024;
+  host_pool(ctx).run((ctx->n_reads + READS_PER_TASK - 1) / READS_PER_TASK, [&](uint32_t b) {
+    const uint32_t r1 = (uint32_t)std::min<uint64_t>((uint64_t)(b + 1) * READS_PER_TASK, ctx->n_reads);
+    for (uint32_t r = b * READS_PER_TASK; r < r1; r++)
+      std::sort(h->hits.begin() + h->off[r], h->hits.begin() + h->off[r + 1], [](const herro_adapter_hit& x, const herro_adapter_hit& y) {
+        if (x.end != y.end) return x.end < y.end;
+        if (x.start != y.start) return x.start < y.start;
+        if (x.adapter != y.adapter) return x.adapter < y.adapter;
+        return x.strand < y.strand;
+      });
+  });
+  if (const char* e = getenv("HERRO_ADAPT_STATS")) {
+    if (atoi(e))
+      fprintf(stderr, "ADAPT seg=%llu segments=%llu patterns=%u hits=%llu scans=%llu scan_ms=%.3f start_ms=%.3f host_ms=%.3f\n", (unsigned long long)stats.seg,
+              (unsigned long long)stats.segments, (uint32_t)((p.flags & HERRO_ADAPTERS_FORWARD_ONLY) ? n_adapters : 2 * n_adapters),
+              (unsigned long long)stats.hits, (unsigned long long)stats.scans, stats.scan_ms, stats.start_ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  }
+  *out = h.release();
+  return HERRO_OK;
+}
+
+uint64_t herro_adapter_hits_n(const herro_adapter_hits* h) { return h ? h->hits.size() : 0; }
+const herro_adapter_hit* herro_adapter_hits_data(const herro_adapter_hits* h) { return h ? h->hits.data() : nullptr; }
+const uint64_t* herro_adapter_hits_off(const herro_adapter_hits* h) { return h ? h->off.data() : nullptr; }
+void herro_adapter_hits_free(herro_adapter_hits* h) { delete h; }
+
+// Test hook: the hits the buffer of a call's first scan holds (0: the default), so that a small read set can outgrow it
+int herro_debug_set_adapter_cap(herro_ctx* ctx, uint64_t cap) {
+  if (!ctx) return HERRO_E_INVALID;
+  ctx->debug_adapter_cap = cap;
   return HERRO_OK;
 }
 

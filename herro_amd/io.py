@@ -65,26 +65,55 @@ def read_fastx(path: str, min_length: int = 0, core: set[str] | None = None, nei
     if not h:
         raise ValueError(err.value.decode())
     try:
-        n = L.herro_reads_count(h)
-        def take(addr, count, dt):       # one memcpy out of the library's buffer (np.ctypeslib.as_array builds a ctypes array TYPE of that length first: seconds per GB)
-            out = np.empty(count, dt)
-            if count:
-                C.memmove(out.ctypes.data, addr, out.nbytes)
-            return out
-        off = take(L.herro_reads_off(h), n + 1, np.uint64)
-        nb = int(off[-1])
-        seq = take(L.herro_reads_seq(h), nb, np.uint8)
-        qual = take(L.herro_reads_qual(h), nb, np.uint8)
-        idp = C.cast(L.herro_reads_ids(h), C.POINTER(C.c_char_p))
-        dp = C.cast(L.herro_reads_descs(h), C.POINTER(C.c_char_p))
-        ids = [idp[i] for i in range(n)]
-        descs = [dp[i] for i in range(n)]
+        return _take_reads(L, h)
     finally:
         L.herro_reads_free(h)
-    return Reads(ids, descs, seq, qual, off)
 
 
 read_fastq = read_fastx   # the name the first rounds used
+
+
+def _take_reads(L, h) -> Reads:
+    n = L.herro_reads_count(h)
+    def take(addr, count, dt):       # one memcpy out of the library's buffer (np.ctypeslib.as_array builds a ctypes array TYPE of that length first: seconds per GB)
+        out = np.empty(count, dt)
+        if count:
+            C.memmove(out.ctypes.data, addr, out.nbytes)
+        return out
+    off = take(L.herro_reads_off(h), n + 1, np.uint64)
+    nb = int(off[-1])
+    seq = take(L.herro_reads_seq(h), nb, np.uint8)
+    qual = take(L.herro_reads_qual(h), nb, np.uint8)
+    idp = C.cast(L.herro_reads_ids(h), C.POINTER(C.c_char_p))
+    dp = C.cast(L.herro_reads_descs(h), C.POINTER(C.c_char_p))
+    return Reads([idp[i] for i in range(n)], [dp[i] for i in range(n)], seq, qual, off)
+
+
+def cut_reads(reads: Reads, pieces) -> Reads:
+    """The reads cut to a piece table (herro_reads_cut over a herro_reads_create handle): read x of the result is bases [start, end) of read rid
+    of `reads`, in the order of `pieces` (api.PIECE_DTYPE, as api.trim_plan returns them).  A read with one piece keeps its id, one with n > 1
+    pieces gives <id>_1 .. <id>_n; descriptions are kept.  ValueError with the library's message on a piece outside its read."""
+    L = _lib()
+    n = len(reads.ids)
+    seq, qual = np.ascontiguousarray(reads.seq, np.uint8), np.ascontiguousarray(reads.qual, np.uint8)
+    off = np.ascontiguousarray(reads.off, np.uint64)
+    pieces = np.ascontiguousarray(pieces, api.PIECE_DTYPE)
+    ids = (C.c_char_p * max(n, 1))(*[bytes(i) for i in reads.ids])
+    descs = (C.c_char_p * max(n, 1))(*[None if d is None else bytes(d) for d in reads.descriptions])
+    err = C.create_string_buffer(256)
+    src = L.herro_reads_create(n, seq.ctypes.data, qual.ctypes.data, off.ctypes.data, ids, descs, err, 256)
+    if not src:
+        raise ValueError(err.value.decode())
+    try:
+        h = L.herro_reads_cut(src, len(pieces), pieces.ctypes.data, err, 256)
+        if not h:
+            raise ValueError(err.value.decode())
+        try:
+            return _take_reads(L, h)
+        finally:
+            L.herro_reads_free(h)
+    finally:
+        L.herro_reads_free(src)
 
 
 def write_window_features(out_dir: str, wid: int, ids: list[str], bases: np.ndarray, quals: np.ndarray,

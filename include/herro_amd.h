@@ -689,6 +689,76 @@ const uint64_t* herro_reads_off(const herro_reads* r);            /* [n + 1] */
 const char* const* herro_reads_ids(const herro_reads* r);         /* [n] */
 const char* const* herro_reads_descs(const herro_reads* r);       /* [n], NULL entries: no description */
 void herro_reads_free(herro_reads* r);
+/* The same handle over the caller's own arrays (copied): n reads, sequence and quality bytes of read i at [off[i], off[i+1]), ids[i] a C string,
+ * descs NULL or its entries NULL: no description.  NULL and a message in err: a null argument, off that does not ascend from 0, a null id. */
+herro_reads* herro_reads_create(uint32_t n, const uint8_t* seq, const uint8_t* qual, const uint64_t* off /* [n + 1] */, const char* const* ids,
+                                const char* const* descs, char* err, uint64_t err_cap);
+
+/* ---- adapters: found in the resident reads on the device, trimmed and split on the host ---------------------------
+ * The step the reference leaves to scripts/preprocess.sh (porechop, duplex_tools split_on_adapter, seqkit seq -m): adapters at the read ends
+ * are trimmed, a chimera is split at an adapter in its middle, short pieces are dropped.  The path is herro_fastx_read, herro_set_reads,
+ * herro_find_adapters, herro_trim_plan, herro_reads_cut, herro_set_reads with the cut reads, then the finder as before.  The specification is
+ * the library's own (tests/adapter_ref.py), all integer; it does not reproduce porechop's or duplex_tools' choices, and no adapter list is
+ * built in: the caller supplies the sequences.
+ *
+ * herro_find_adapters: approximate matches of every adapter in every read of the store (k_adapt_scan, k_adapt_start in csrc/adapter_dev.hip).
+ *   Patterns.  Adapter a is seq[off[a], off[a+1]), m bases, 8 <= m <= 64, 1 <= n_adapters <= 32, bases A, C, G or T in either case.  Strand 0
+ *   searches the adapter as given, strand 1 its reverse complement (not with HERRO_ADAPTERS_FORWARD_ONLY).  k = floor(m * max_err_pm / 1000),
+ *   max_err_pm <= 500 and 0 = the default 250 (k = 0: any max_err_pm below 1000 / m, e.g. 1).
+ *   Text.  A read's 2-bit codes as the store holds them — a byte that is not ACGT as herro_encode_2bit codes it.
+ *   Score.  For an end position j in 1 .. len, E(j) = min over i <= j of the edit distance (unit costs) of the pattern and T[i, j); the empty
+ *   substring is included, so E <= m.
+ *   Hit.  A maximal run of consecutive j with E(j) <= k.  end = the j of the least E in the run, the smallest such j on ties; errors = that E;
+ *   start = the largest i <= end with edit distance of the pattern and T[i, end) == errors.  start and end are forward read coordinates on
+ *   either strand.  Runs of different patterns are different hits, even where they overlap (a palindromic adapter hits on both strands).
+ *   Order.  Ascending (rid, end, start, adapter, strand); off[r] .. off[r + 1] are read r's hits.  The bytes depend neither on thread order
+ *   nor on the segment length (HERRO_ADAPT_SEG, bases per lane, 8 .. 65536, default 256: a setting of the kernel's work split only).
+ *   The hits are appended to a buffer of max(65536, segments / 8) entries; a scan that finds more is run a second time at the counted size
+ *   (herro_debug_set_adapter_cap, a test hook, sets the first buffer's entries for the context's later calls; 0: the default).  HERRO_ADAPT_STATS=1 prints `ADAPT seg= segments= patterns= hits= scans= scan_ms=
+ *   start_ms= host_ms=` on stderr.
+ * Checks: parameters and adapters first (HERRO_E_INVALID naming the adapter; works on a context without a device), then HERRO_E_NO_DEVICE,
+ * then HERRO_E_STATE without reads; more than 2^32 - 1 hits or segments: HERRO_E_UNSUPPORTED.  The call runs on the context's execution stream
+ * and returns when it is done. */
+typedef struct { uint32_t max_err_pm, flags, reserved[2]; } herro_adapter_params;   /* 0 = the field's default; reserved: 0 */
+#define HERRO_ADAPTERS_FORWARD_ONLY 1u
+typedef struct { uint32_t rid, start, end; uint16_t adapter; uint8_t strand, errors; } herro_adapter_hit;   /* 16 bytes */
+typedef struct herro_adapter_hits herro_adapter_hits;
+int herro_find_adapters(herro_ctx* ctx, uint32_t n_adapters, const char* seq, const uint64_t* off /* [n_adapters + 1] */,
+                        const herro_adapter_params* params /* NULL: defaults */, herro_adapter_hits** out);
+uint64_t herro_adapter_hits_n(const herro_adapter_hits* hits);
+const herro_adapter_hit* herro_adapter_hits_data(const herro_adapter_hits* hits);
+const uint64_t* herro_adapter_hits_off(const herro_adapter_hits* hits);      /* [n_reads + 1] */
+void herro_adapter_hits_free(herro_adapter_hits* hits);
+int herro_debug_set_adapter_cap(herro_ctx* ctx, uint64_t cap);               /* test hook, see above */
+/* herro_trim_plan: the pieces of every read that stay, from a hit table (csrc/trim_plan.h: host code, no device).  0 in a field = its default:
+ * end_window 150, end_max_err_pm 250, mid_max_err_pm 100, min_length 0 (preprocess.sh keeps reads of 10000 bases and more).
+ *   Per read of length L, a hit of an adapter of m bases is a START hit if start < end_window and errors <= floor(m * end_max_err_pm / 1000);
+ *   otherwise an END hit if end + end_window > L under the same bound; otherwise a MIDDLE hit if errors <= floor(m * mid_max_err_pm / 1000);
+ *   otherwise it is ignored.  lo = the largest end of the start hits (0: none), hi = the smallest start of the end hits (L: none).  lo >= hi:
+ *   the read gives no piece.  Middle hits are clipped to [lo, hi), overlapping or touching ones merged; the pieces are what is left of
+ *   [lo, hi), ascending.  With HERRO_TRIM_DISCARD_CHIMERAS a read with any middle hit gives no piece.  Pieces shorter than
+ *   max(min_length, 1) are dropped.
+ * pieces are grouped by read: piece_off[r] .. piece_off[r + 1].  herro_trim_stats: reads trimmed (lo > 0 or hi < L), reads split (more than one
+ * piece), reads dropped (no piece), bases removed (the reads' bases minus the pieces').
+ * HERRO_E_INVALID and a message in err: a null argument, a hit outside its read, start > end, a hit whose rid is not its group's read, an
+ * adapter index out of range, hits_off that does not ascend from 0, a non-zero reserved field, an unknown flag. */
+typedef struct { uint32_t end_window, end_max_err_pm, mid_max_err_pm, min_length, flags, reserved[3]; } herro_trim_params;
+#define HERRO_TRIM_DISCARD_CHIMERAS 1u
+typedef struct { uint32_t rid, start, end; } herro_piece;
+typedef struct herro_trim herro_trim;
+int herro_trim_plan(uint32_t n_reads, const uint32_t* read_len, uint32_t n_adapters, const uint32_t* adapter_len, const herro_adapter_hit* hits,
+                    const uint64_t* hits_off /* [n_reads + 1] */, const herro_trim_params* params /* NULL: defaults */, herro_trim** out,
+                    char* err, uint64_t err_cap);
+uint64_t herro_trim_n_pieces(const herro_trim* t);
+const herro_piece* herro_trim_pieces(const herro_trim* t);
+const uint64_t* herro_trim_piece_off(const herro_trim* t);                   /* [n_reads + 1] */
+int herro_trim_stats(const herro_trim* t, uint64_t out[4]);                  /* reads trimmed, reads split, reads dropped, bases removed */
+void herro_trim_free(herro_trim* t);
+/* herro_reads_cut: a new handle whose read x is piece x of r — sequence and quality are the slices [start, end) of read rid, in the order of
+ * `pieces` (any order).  A read with exactly one piece in the table keeps its id; one with n > 1 pieces gives <id>_1 .. <id>_n in the table's
+ * order; the description is kept.  The result goes into herro_set_reads unchanged.  NULL and a message in err: a null argument, a rid outside
+ * r, start > end, end beyond the read. */
+herro_reads* herro_reads_cut(const herro_reads* r, uint64_t n_pieces, const herro_piece* pieces, char* err, uint64_t err_cap);
 
 /* One window of `herro features` (output_features, features.rs:724-764): <dir>/<wid>.ids.txt (one id per line),
  * <wid>.features.npy = u8 [2, length, 31] (ASCII bases [length][31], then qualities), <wid>.supported.npy = records
