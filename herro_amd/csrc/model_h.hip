@@ -738,11 +738,16 @@ __device__ __forceinline__ uint32_t lsw8(uint32_t row, uint32_t chunk) { return 
 // k_layers_p — the stack with its three exposed latencies taken off the critical path (an un-pipelined first version,
 // all 16 fragment loads of a GEMM call issued at its head, took 1196 us per 4096 windows; this one 959; with x parked
 // in L2 across the GEMM phases instead of held in registers: 1068):
-//   * weights run one half-call AHEAD across GEMM calls: a call enters with the fragments of its first four k-steps
-//     already in registers (loaded under the previous call's MFMAs), issues the loads of its last four at once, and
-//     under those MFMAs fetches the first four of the NEXT call (the call sequence Q, K, V, proj, [FF1, FF2] x chunks,
-//     next layer's Q ... is static) — no L2 round trip at the head of each of the 48 calls per tile, with both waves
-//     of every SIMD waiting at the same time;
+//   * weights run one whole call AHEAD across GEMM calls, in a ring of eight k-steps (64 registers): a call enters with
+//     the fragments of all its k-steps requested, and behind the MFMAs of k-step k the slot takes k-step k of the NEXT
+//     call (the call sequence Q, K, V, proj, [FF1, FF2] x chunks, next layer's Q ... is static) — two loads per k-step,
+//     each 64 MFMAs of the wave ahead of its use; the streams of Q, proj and FF1(0) arrive during LayerNorm 1, the
+//     attention and LayerNorm 2.  (Until the ring: half a call ahead in two bursts of 64 KB per compute unit, k-steps
+//     4..7 at the head of their call and 0..3 of the next call at k == 4.  Per tile of 64 tokens, precision 5, 4096
+//     windows: the four GEMM phases 126 k -> 109 k cycles, the tile 250 k -> 236 k; profiles/layers_wstream_ab.txt.)
+//     Nothing may drain the ring between calls: the barriers do not (they wait for LDS traffic only), and the next
+//     layer's parameter vectors are requested in front of LayerNorm 2, so that their stores behind the feed-forward
+//     loop wait for no load;
 //   * LDS activation fragments are read one half k-step (8 MFMAs, >= 128 cycles) ahead of their use instead of one
 //     MFMA pair ahead;
 //   * bias vectors and LayerNorm parameters are requested before the MFMAs / reductions they follow, not after.
@@ -771,27 +776,39 @@ __device__ __forceinline__ void wload8(const WStream& s, uint32_t step, v8i (&w)
     w[jt] = v8i{(int)a.x, (int)a.y, (int)a.z, (int)a.w, (int)b.x, (int)b.y, (int)b.z, (int)b.w};
   }
 }
-__device__ __forceinline__ void wload4(const WStream& s, uint32_t k0, half8 (&w)[4][2]) {
+__device__ __forceinline__ half8 wfrag(const WStream& s, uint32_t k, uint32_t jt) { return *reinterpret_cast<const half8*>(s.p + (uint64_t)(jt * s.nks + k) * 512); }
+template <int N>
+__device__ __forceinline__ void wload(const WStream& s, uint32_t k0, half8 (*w)[2]) {   // k-steps k0 .. k0 + N - 1 of a call, in one burst
 #pragma unroll
   for (int jt = 0; jt < 2; jt++)
 #pragma unroll
-    for (int k = 0; k < 4; k++) w[k][jt] = *reinterpret_cast<const half8*>(s.p + (uint64_t)(jt * s.nks + k0 + k) * 512);
+    for (int k = 0; k < N; k++) w[k][jt] = wfrag(s, k0 + k, jt);
 }
 
+// The barriers of the stack are __syncthreads(): in this kernel it compiles to s_waitcnt lgkmcnt(0) + s_barrier (no vmcnt: the 13 barriers of
+// k_layers_p<1, 4> were read in the ISA), so the weight fragments in flight cross every one of them; an explicit asm barrier of k_fc_r's form gave the same
+// code and the same time (profiles/layers_wstream_ab.txt, which also has the A/B of the ring against the half-call lead it replaced).
+
 #ifndef HERRO_LP_DBG
-#define HERRO_LP_DBG 0   // timing experiments (wrong results): 1 every second activation fragment read from LDS is skipped, 2 every second k-step's MFMAs, 4 the weight loads inside a call,
+#define HERRO_LP_DBG 0   // timing experiments (wrong results): 1 every second activation fragment read from LDS is skipped, 2 every second k-step's MFMAs, 4 no weight loads inside a call (the ring keeps the prologue's fragments),
                          // 8 (precision 6) no K = 128 instructions, 16 (precision 6) no e4m3 conversion of the remainders (the byte planes stay as they are)
 #endif
 template <bool SWAP, int TERMS, int PT>
-__device__ __forceinline__ void tile_gemm_p(const WStream& cur, half8 (&wa)[4][2], const WStream& nxt, const uint16_t* sh,
+__device__ __forceinline__ void tile_gemm_p(const WStream& cur, half8 (&w)[8][2], const WStream& nxt, const uint16_t* sh,
                                             const uint16_t* sl, uint32_t fr, uint32_t fg, f32x4 (&acc)[PT][2]) {
-  half8 wb[4][2];
-  if (HERRO_LP_DBG & 4) {
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-#pragma unroll
-      for (int jt = 0; jt < 2; jt++) wb[k][jt] = wa[k][jt];
-  } else wload4(cur, 4, wb);
+  // The ring: on entry ALL eight k-steps of this call have been requested (slot k = k-step k); behind the MFMAs of k-step k its slot takes k-step k of
+  // the NEXT call — every fragment is requested a whole call (64 MFMAs of the wave per term) ahead of its use, two loads per k-step instead of bursts of
+  // 16.  A three-term call is the exception: its second e4m3 fragment pair lives in slots 4 and 5 from k == 6 on, and its K = 128 steps hold 64 registers of
+  // remainder fragments, so slots 4..7 are refilled behind those steps, at the end of the call — four k-steps ahead of their use, the lead every slot had before
+  // the ring (with slots 6 and 7 refilled in the loop <3, 4, true> needs 256 registers and 28 bytes of scratch).
+  auto refill = [&](int k) {   // slot k: k-step k of the next call
+    if (HERRO_LP_DBG & 4) return;
+    w[k][0] = wfrag(nxt, k, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    w[k][1] = wfrag(nxt, k, 1);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  constexpr bool LATE = TERMS == 3;   // slots 4..7 are refilled behind the e4m3 steps
   static_assert(!(SWAP && TERMS == 3), "the e4m3 term is written for weights as the A operand");
   v8i w8a[2], w8b[2], xb[PT];   // TERMS 3: the e4m3 weight fragments of the call's two K = 128 steps; the remainder fragments of the first
   auto rd8 = [&](int step, int pt) -> v8i {
@@ -825,11 +842,7 @@ __device__ __forceinline__ void tile_gemm_p(const WStream& cur, half8 (&wa)[4][2
   for (int k = 0; k < 8; k++) {
     constexpr bool dbg_rd = (HERRO_LP_DBG & 1) != 0, dbg_mm = (HERRO_LP_DBG & 2) != 0;
     if (TERMS == 3 && k == 0) { wload8(cur, 0, w8a); __builtin_amdgcn_sched_barrier(0); }   // used behind the f16 k-steps
-    if (k == 4 && !(HERRO_LP_DBG & 4)) {  // wa's last reader (k = 3) is behind us: refill it with the head of the next call
-      wload4(nxt, 0, wa);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (TERMS == 3 && k == 6) { wload8(cur, 1, w8b); __builtin_amdgcn_sched_barrier(0); }   // into the registers wb's first two k-steps have left
+    if (TERMS == 3 && k == 6) { wload8(cur, 1, w8b); __builtin_amdgcn_sched_barrier(0); }   // into the registers slots 4 and 5 have left
     if (TERMS == 3 && k == 7) {   // the remainder fragments of the first K = 128 step, under the last f16 k-step
 #pragma unroll
       for (int pt = 0; pt < PT; pt++) xb[pt] = rd8(0, pt);
@@ -838,22 +851,24 @@ __device__ __forceinline__ void tile_gemm_p(const WStream& cur, half8 (&wa)[4][2
     if (AHEAD2) {
       if (k + 2 < 8) rd(sh, k + 2, xm);
       __builtin_amdgcn_sched_barrier(0);
-      if (k < 4) mm8(xh, wa[k]); else mm8(xh, wb[k - 4]);
+      mm8(xh, w[k]);
       __builtin_amdgcn_sched_barrier(0);
+      if (!(LATE && k >= 4)) refill(k);
 #pragma unroll
       for (int pt = 0; pt < PT; pt++) { xh[pt] = xn[pt]; xn[pt] = xm[pt]; }
       continue;
     }
     if (TERMS == 2 && !(dbg_rd && (k & 1))) rd(sl, k, xl);
     __builtin_amdgcn_sched_barrier(0);
-    if (!(dbg_mm && (k & 1))) { if (k < 4) mm8(xh, wa[k]); else mm8(xh, wb[k - 4]); }
+    if (!(dbg_mm && (k & 1))) mm8(xh, w[k]);
     __builtin_amdgcn_sched_barrier(0);
     if (k < 7 && !(dbg_rd && !(k & 1))) rd(sh, k + 1, xn);
     __builtin_amdgcn_sched_barrier(0);
     if (TERMS == 2 && !(dbg_mm && (k & 1))) {
-      if (k < 4) mm8(xl, wa[k]); else mm8(xl, wb[k - 4]);
+      mm8(xl, w[k]);
       __builtin_amdgcn_sched_barrier(0);
     }
+    if (!(LATE && k >= 4)) refill(k);   // the k-step's MFMAs are issued: its slot takes the same k-step of the next call
 #pragma unroll
     for (int pt = 0; pt < PT; pt++) xh[pt] = xn[pt];
   }
@@ -879,6 +894,10 @@ __device__ __forceinline__ void tile_gemm_p(const WStream& cur, half8 (&wa)[4][2
 #pragma unroll
       for (int jt = 0; jt < 2; jt++) if (!(HERRO_LP_DBG & 8)) acc[pt][jt] = mma8(w8b[jt], xc[pt], acc[pt][jt], cur.s8);
       __builtin_amdgcn_sched_barrier(0);
+    }
+    if (LATE) {   // w8b's last reader is issued: the hand-over holds for the call that follows (all eight k-steps requested)
+#pragma unroll
+      for (int k = 4; k < 8; k++) refill(k);
     }
   }
 }
@@ -946,8 +965,7 @@ __global__ __launch_bounds__(512) void k_layers_p(ModelDev M, BatchDev B, ModelS
   if (tid < HLT) s_win[tid] = tid < nt ? S.tok_win[t0 + tid] : 0xffffff00u + tid;
   f32x4 xr[PT][2];   // the residual stream, in the accumulator layout of the GEMM calls (channel cw + 8 fg + q of token pt * 16 + fr at [pt][q / 4][q % 4]): proj and FF2 accumulate straight into it
 #define XQ(pt, q) xr[pt][(q) >> 2][(q) & 3]
-  half8 wa[4][2];  // the first four k-steps of the next GEMM call, always one call ahead
-  wload4(wstream(M.layer[0].qkv, cw, 0, lane), 0, wa);
+  half8 wa[8][2];  // the weight ring (tile_gemm_p): all eight k-steps of the next GEMM call, always one call ahead (first filled at the end of the prologue)
 
   auto lds8 = [&](uint32_t o, float (&v)[8]) {
     const float4 a = *reinterpret_cast<const float4*>(s_par + o), b = *reinterpret_cast<const float4*>(s_par + o + 4);
@@ -955,18 +973,33 @@ __global__ __launch_bounds__(512) void k_layers_p(ModelDev M, BatchDev B, ModelS
   };
   // one coalesced pass over the layer's small parameter vectors -> LDS (the GEMM epilogues and LayerNorms then read
   // them with LDS latency instead of one L2 round trip each).  Visible after the next barrier.
-  auto stage_params = [&](const LayerW& L) {
+  // In two halves, so that the next layer's parameters can be REQUESTED a feed-forward loop ahead of the barrier they are stored behind: the loads count
+  // in vmcnt in order, so a store that waits for a parameter load issued behind the ring's refills waits for the whole ring (and for its own L2 round
+  // trip, once per layer, in every wave).  The loads are unconditional (clamped indices, no branch); the stores carry the bounds.
+  struct ParRegs { float v[6], q[2], f[PAR_MAX_FF / 512]; };
+  auto fetch_params = [&](const LayerW& L, ParRegs& r) {
     uint32_t tid_ = threadIdx.x;
     asm volatile("" : "+v"(tid_));   // (opaque: the addresses below are recomputed here instead of being kept — and spilled — across the layer body)
-    const uint32_t tid = tid_;
-    for (uint32_t e = tid; e < 256; e += 512) {
-      s_par[PAR_LN1G + e] = L.ln1_g[e]; s_par[PAR_LN1B + e] = L.ln1_b[e];
-      s_par[PAR_LN2G + e] = L.ln2_g[e]; s_par[PAR_LN2B + e] = L.ln2_b[e];
-      s_par[PAR_BPROJ + e] = L.proj.bias[e]; s_par[PAR_BFF2 + e] = L.ff2.bias[e];
-    }
-    for (uint32_t e = tid; e < 768; e += 512) s_par[PAR_BQKV + e] = L.qkv.bias[e];
-    for (uint32_t e = tid; e < d_ff; e += 512) s_par[PAR_BFF1 + e] = L.ff1.bias[e];
+    const uint32_t e = tid_ & 255u;
+    r.v[0] = L.ln1_g[e]; r.v[1] = L.ln1_b[e]; r.v[2] = L.ln2_g[e]; r.v[3] = L.ln2_b[e]; r.v[4] = L.proj.bias[e]; r.v[5] = L.ff2.bias[e];
+    r.q[0] = L.qkv.bias[tid_]; r.q[1] = L.qkv.bias[512 + e];
+#pragma unroll
+    for (int j = 0; j < PAR_MAX_FF / 512; j++) r.f[j] = L.ff1.bias[min(tid_ + 512u * j, d_ff - 1)];
   };
+  auto put_params = [&](const ParRegs& r) {
+    uint32_t tid_ = threadIdx.x;
+    asm volatile("" : "+v"(tid_));
+    const uint32_t tid = tid_;
+    if (tid < 256) {
+      s_par[PAR_LN1G + tid] = r.v[0]; s_par[PAR_LN1B + tid] = r.v[1]; s_par[PAR_LN2G + tid] = r.v[2]; s_par[PAR_LN2B + tid] = r.v[3];
+      s_par[PAR_BPROJ + tid] = r.v[4]; s_par[PAR_BFF2 + tid] = r.v[5];
+      s_par[PAR_BQKV + 512 + tid] = r.q[1];
+    }
+    s_par[PAR_BQKV + tid] = r.q[0];
+#pragma unroll
+    for (int j = 0; j < PAR_MAX_FF / 512; j++) if (tid + 512u * j < d_ff) s_par[PAR_BFF1 + tid + 512u * j] = r.f[j];
+  };
+  auto stage_params = [&](const LayerW& L) { ParRegs r; fetch_params(L, r); put_params(r); };
   // LayerNorm over the 256 channels of the register-resident x, two passes (mean, then centred sum of squares).  (The one-barrier
   // form of k_layers_q — per-wave mean and M2 merged exactly — measured no faster here: 726 vs 726 us per 4096 windows.)
   auto layer_norm = [&](uint32_t og, uint32_t ob, const float* __restrict__ gp, const float* __restrict__ bp, int want_lo) {   // want_lo: 0 none, 1 an f16 plane, 2 e4m3 bytes
@@ -985,6 +1018,8 @@ __global__ __launch_bounds__(512) void k_layers_p(ModelDev M, BatchDev B, ModelS
         sm = fg_sum(sm);
         if (fg == 0) red[wave * HLT + pt * 16 + fr] = sm;
       }
+      // hands over: this pass's partial sums in s_red; pass 0 of LayerNorm 1 also the layer's parameters in s_par (put_params: LDS stores whose
+      // data comes from global loads through registers, so each store has waited for its own load — publishing them needs no vmcnt)
       __syncthreads();
 #pragma unroll
       for (int pt = 0; pt < PT; pt++) {
@@ -1028,7 +1063,7 @@ __global__ __launch_bounds__(512) void k_layers_p(ModelDev M, BatchDev B, ModelS
         *reinterpret_cast<half8*>(s_hh + o) = pack_h8(y);
       }
     }
-    __syncthreads();  // planes complete; also: everybody is past its reads of both s_red arrays
+    __syncthreads();  // hands over: the normalised planes (s_hh / s_hl); also: everybody is past its reads of both s_red arrays
   };
   auto zero = [](f32x4 (&a)[PT][2]) {
 #pragma unroll
@@ -1091,6 +1126,9 @@ __global__ __launch_bounds__(512) void k_layers_p(ModelDev M, BatchDev B, ModelS
       }
     }
   }
+  // the ring's first fill: all eight k-steps of layer 0's Q call, requested BEHIND the parameters and x (loads retire in order: in front of them it made the
+  // parameter stores and LayerNorm 1 wait for 128 KB per compute unit, on all compute units at once) — it arrives during LayerNorm 1
+  wload<8>(wstream(M.layer[0].qkv, cw, 0, lane), 0, wa);
   __syncthreads();  // s_win, s_par
 
   const float scale = 1.4426950408889634f / sqrtf(32.f);   // 1 / sqrt(head dim) and log2(e): the softmax runs on v_exp_f32 (2^x) without a multiply per score
@@ -1325,7 +1363,7 @@ __global__ __launch_bounds__(512) void k_layers_p(ModelDev M, BatchDev B, ModelS
         }
       }
     }
-    __syncthreads();
+    __syncthreads();   // hands over: the attention output in s_ah / s_al (every head's 32 channels) to proj
     LP_MARK(3);
     RELAUNDER();
     {  // ---- output projection + residual
@@ -1339,6 +1377,14 @@ __global__ __launch_bounds__(512) void k_layers_p(ModelDev M, BatchDev B, ModelS
     }
     RELAUNDER();
     LP_MARK(4);
+    // The next layer's parameters are requested HERE, a LayerNorm and the feed-forward loop ahead of their stores (behind the loop's last barrier): LayerNorm 2
+    // waits for no load, so they arrive under it.  (Requested right in front of FF1(0) they are waited for at its third k-step — loads retire in order, and the
+    // call's counted waits leave 14 in flight: the FF1 phase of the timed wave 49.4 k against 38.1 k cycles per tile, the kernel's time the same within its spread;
+    // profiles/layers_wstream_ab.txt, blocks 2 and 3.)
+    constexpr bool PAR_EARLY = TF != 3;   // (the three-term instantiations have no 12 registers to spare across the loop, 237-244 without: they request them behind it)
+    const bool stage = li + 1 < n_layers;
+    ParRegs pr;
+    if (PAR_EARLY && stage) fetch_params(Ln, pr);
     layer_norm(PAR_LN2G, PAR_LN2B, nullptr, nullptr, TF == 3 ? 2 : (TF == 2 ? 1 : 0));
     LP_MARK(5);
     {  // ---- feed-forward, 256 hidden channels at a time
@@ -1360,7 +1406,10 @@ __global__ __launch_bounds__(512) void k_layers_p(ModelDev M, BatchDev B, ModelS
       // FF2(c) goes: a wave that is through its FF2 starts FF1(c + 1) while its SIMD partner still streams — the skew a barrier removes is what overlaps one
       // wave's epilogue with the other's MFMAs.
       constexpr bool TWO_BUF = TF == 1;
-      for (uint32_t c = 0; c < d_ff; c += 256) {
+      // (a do-while: d_ff >= 256, model_h_supported.  With a zero-trip path around the loop the compiler's wait-count bookkeeping takes the parameter loads above
+      // for the youngest loads at the loop's exit and drains the ring in front of their stores)
+      uint32_t c = 0;
+      do {
         RELAUNDER();
         uint16_t* hid = (TWO_BUF && ((c >> 8) & 1u)) ? s_al : s_ah;   // (read as an f16 hi plane in either case: TF == 1 has no lo plane)
         f32x4 a1[PT][2];
@@ -1382,18 +1431,21 @@ __global__ __launch_bounds__(512) void k_layers_p(ModelDev M, BatchDev B, ModelS
           store_act(std::integral_constant<int, TF>{}, hid, s_al, hlsw(pt * 16 + fr, wave * 4 + fg), v);
         }
         LP_MARK(10);
-        __syncthreads();   // the hidden chunk is complete; TWO_BUF: ... and every wave is through FF2(c - 1), whose buffer the NEXT epilogue writes
+        __syncthreads();   // hands over: the hidden chunk (LDS); TWO_BUF: ... and every wave is through FF2(c - 1), whose buffer the NEXT epilogue writes.  FF2(c)'s weights stay in flight
         LP_MARK(6);
         const bool more = c + 256 < d_ff;
         const WStream nx = more ? wstream(L.ff1, c + 256 + cw, 0, lane) : wstream(Ln.qkv, cw, 0, lane);
         tile_gemm_p<false, TF, PT>(wstream<TF == 3>(L.ff2, cw, c, lane), wa, nx, hid, s_al, fr, fg, xr);
         LP_MARK(11);
-        if (!TWO_BUF || !more) __syncthreads();   // (the loop's last barrier stays: the next layer's parameters are staged behind it)
+        if (!TWO_BUF || !more) __syncthreads();   // every wave is through its reads of the hidden chunk and (last pass) of s_par — LDS reads only (the loop's last barrier stays: the next layer's parameters are staged behind it)
         LP_MARK(7);
+      } while ((c += 256) < d_ff);
+      // every wave is past its last read of this layer's parameters (the barrier that closed the FF loop)
+      if (stage) {   // visible after the first barrier of the next LayerNorm
+        if (!PAR_EARLY) fetch_params(Ln, pr);
+        put_params(pr);
       }
     }
-    // every wave is past its last read of this layer's parameters (the barrier that closed the FF loop)
-    if (li + 1 < n_layers) stage_params(Ln);   // visible after the first barrier of the next LayerNorm
   }
   RELAUNDER();
   // where the logits of this lane's token go, and the heads' bias: requested in front of the last LayerNorm, used behind the heads
@@ -1435,7 +1487,7 @@ __global__ __launch_bounds__(512) void k_layers_p(ModelDev M, BatchDev B, ModelS
 constexpr size_t layers_p_shm(int tokens) { return (size_t)4 * tokens * 256 * 2 + 2 * 8 * tokens * 4 + tokens * 4 + (size_t)PAR_FLOATS * 4; }
 
 // ---------------------------------------------------------------------------------------------------
-// Tiles of 32 tokens (k_layers_p<TERMS, 2>): the same organisation — 8 waves, wave = head and 32-channel slab, weights one half
+// Tiles of 32 tokens (k_layers_p<TERMS, 2>): the same organisation — 8 waves, wave = head and 32-channel slab, weights one
 // call ahead — over two row blocks instead of four: half the MFMAs and half the LDS traffic for the same weight stream.  A launch
 // runs in rounds of one 64-token tile per compute unit; when its last round would fill at most half of the chip, the windows of
 // that round go into 32-token tiles instead (plan_tiles, herro_api.hip).
@@ -1510,7 +1562,7 @@ void launch_pe_table(const float* pe_div, float* tab, uint32_t rows, uint32_t d_
 
 bool model_h_supported(const ModelDev& M) {
   const ModelHyper& h = M.h;
-  if (!(model_default_variant(M) && h.d_model == 256 && h.n_heads == 8 && h.d_ff % 256 == 0 && h.d_ff <= (uint32_t)PAR_MAX_FF && h.rows == HERRO_ROWS && M.heads.h16 && M.heads.l16)) return false;
+  if (!(model_default_variant(M) && h.d_model == 256 && h.n_heads == 8 && h.d_ff % 256 == 0 && h.d_ff >= 256 && h.d_ff <= (uint32_t)PAR_MAX_FF && h.rows == HERRO_ROWS && M.heads.h16 && M.heads.l16)) return false;
   for (uint32_t l = 0; l < h.n_layers; l++)
     if (!M.layer[l].qkv.ph16 || !M.layer[l].proj.ph16 || !M.layer[l].ff1.ph16 || !M.layer[l].ff2.ph16) return false;
   return true;
