@@ -1,5 +1,6 @@
 // api_ctx.h — what the translation units of the C ABI share (herro_api.hip: contexts, model, jobs; frontend_api.hip: reads alone ->
 // records -> ops on the device): the context, its last-error slot, HIP_TRY and the host pool.  Internal: nothing here is exported.
+// (The host half of herro_load_model — file reader, number formats, weight layouts — is model_pack.h, which knows neither a context nor HIP.)
 #pragma once
 #include <hip/hip_runtime.h>
 

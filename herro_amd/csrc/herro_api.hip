@@ -24,6 +24,7 @@
 #include "host_cpus.h"
 #include "job_dev.h"
 #include "model_dev.h"
+#include "model_pack.h"
 #include "infer_plan.h"
 #include "windowing.hpp"
 #include "build_dev.h"
@@ -578,70 +579,6 @@ int herro_set_reads_packed(herro_ctx* ctx, uint32_t n_reads, const uint64_t* wor
 }
 
 // ---- model ---------------------------------------------------------------------------------------
-namespace {
-struct HostTensor { std::vector<uint32_t> dims; std::vector<float> data; };
-
-uint16_t h_bf16(float f) {
-  uint32_t u; std::memcpy(&u, &f, 4);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-float h_bf16f(uint16_t h) { uint32_t u = (uint32_t)h << 16; float f; std::memcpy(&f, &u, 4); return f; }
-
-// f32 -> IEEE binary16, round to nearest even (subnormals kept, overflow -> inf), and back
-uint16_t h_f16(float f) {
-  uint32_t u; std::memcpy(&u, &f, 4);
-  const uint32_t sign = (u >> 16) & 0x8000u;
-  const uint32_t a = u & 0x7fffffffu;
-  if (a >= 0x7f800000u) return (uint16_t)(sign | 0x7c00u | (a > 0x7f800000u ? 0x200u : 0u));  // inf / nan
-  if (a >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                                     // rounds to >= 65520 -> inf
-  if (a < 0x33000001u) return (uint16_t)sign;                                                  // <= 2^-25 -> 0 (ties to even)
-  const int32_t e = (int32_t)(a >> 23) - 127;
-  uint32_t m = (a & 0x7fffffu) | 0x800000u;   // 24-bit significand
-  int shift;                                  // bits dropped from m
-  uint32_t base;
-  if (e >= -14) { shift = 13; base = (uint32_t)(e + 15) << 10; m &= 0x7fffffu; }   // normal: keep 10 fraction bits
-  else { shift = 13 + (-14 - e); base = 0; }                                        // subnormal: value = m * 2^(e-23), unit 2^-24
-  uint32_t q = m >> shift;
-  const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
-  if (rem > half || (rem == half && (q & 1u))) q++;
-  return (uint16_t)(sign | (base + q));       // a carry out of the fraction bumps the exponent, as it must
-}
-float h_f16f(uint16_t h) {
-  const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3ffu;
-  float f;
-  if (e == 0) f = std::ldexp((float)m, -24);
-  else if (e == 31) f = m ? NAN : INFINITY;
-  else f = std::ldexp((float)(m | 0x400u), (int)e - 25);
-  uint32_t u; std::memcpy(&u, &f, 4); u |= sign; std::memcpy(&f, &u, 4);
-  return f;
-}
-
-// f32 -> OCP e4m3 (e4m3fn: bias 7, 3 fraction bits, subnormals in units of 2^-9, largest finite 448 = 0x7e, no infinities), round to nearest even,
-// SATURATING (the weights of precision 6 are scaled below 448 first; the device's own v_cvt_pk_fp8_f32 turns >= 480 into NaN).  Values the
-// device conversion produced for the same inputs: tools/probes/mx_probe.hip (1 -> 0x38, 0.1 -> 0x1d, 3.3 -> 0x45, 0.0176 -> 0x09, 2^-9 -> 0x01, 2^-10 -> 0).
-uint8_t f32_to_e4m3(float f) {
-  const uint8_t sign = std::signbit(f) ? 0x80u : 0u;
-  const float a = std::fabs(f);
-  if (!(a == a)) return (uint8_t)(sign | 0x7fu);           // NaN
-  if (a >= 448.f) return (uint8_t)(sign | 0x7eu);
-  if (a < std::ldexp(1.f, -6)) return (uint8_t)(sign | (uint8_t)std::nearbyint(std::ldexp(a, 9)));   // subnormal (8 -> 0x08 = the smallest normal, as it must)
-  int ex;
-  const float m = std::frexp(a, &ex);                      // a = m * 2^ex, m in [0.5, 1)
-  int q = (int)std::nearbyint(std::ldexp(m, 4)) - 8;        // fraction of 1.fff in eighths, ties to even
-  int e = ex - 1 + 7;
-  if (q == 8) { q = 0; e++; }
-  const int code = (e << 3) | q;
-  return (uint8_t)(sign | (uint8_t)std::min(code, 0x7e));
-}
-
-const float* up_f32(herro_ctx* ctx, const std::vector<float>& v, hipError_t& e) {
-  float* p = dev_alloc_copy(v, ctx->stream, e);
-  if (p) ctx->model_allocs.push_back(p);
-  return p;
-}
-}  // namespace
-
 // Calibration of the f16 modes on the loaded model: 4 windows x 96 rows, 64 informative rows each (fused tiles), pileup-shaped — a target column, 30 read
 // columns that cover a stretch of the window on one strand and agree with the target but for ~3 % mismatches and ~2 % gaps, '.' outside their stretch,
 // insertion rows ('*' in the target, a base in a fifth of the reads), qualities ~N(22, 8).  Reference = mode 0 (f32 MFMA).  Fills ctx->calib[mode] for the
@@ -697,253 +634,139 @@ static int calibrate(herro_ctx* ctx, const int* modes, int n_modes) {
   return HERRO_OK;
 }
 
-int herro_load_model(herro_ctx* ctx, const char* path) {
-  if (!ctx || !path) return HERRO_E_INVALID;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  FILE* f = std::fopen(path, "rb");
-  if (!f) { ctx->err = std::string("cannot open model file ") + path; return HERRO_E_NO_MODEL; }
-  ModelHyper h;
-  std::map<std::string, HostTensor> T;
-  bool ok = std::fread(&h, sizeof(h), 1, f) == 1 && h.magic == 0x4f525248u /* 'HRRO' */ && h.version == 1;
-  for (uint32_t i = 0; ok && i < h.n_tensors; i++) {
-    char name[32];
-    uint32_t nd, dims[4];
-    ok = std::fread(name, 32, 1, f) == 1 && std::fread(&nd, 4, 1, f) == 1 && std::fread(dims, 16, 1, f) == 1 && nd <= 4;
-    if (!ok) break;
-    name[31] = 0;
-    HostTensor t;
-    size_t n = 1;
-    for (uint32_t d = 0; d < nd; d++) { t.dims.push_back(dims[d]); n *= dims[d]; }
-    t.data.resize(n);
-    ok = std::fread(t.data.data(), 4, n, f) == n;
-    T[name] = std::move(t);
+// The gate of the f16 modes (4 .. 8) on the loaded model, stated once for herro_load_model and herro_set_precision.  A mode exists when the f16 stack serves
+// the model's shapes, every weight lies inside the f16 range (|w| >= 65520 rounds to inf, the remainder term to -inf: NaN logits) and, for mode 6, the e4m3
+// copies are there; because the margin of the f16 formats to the 1e-3 contract was measured on random-init weights only, it is then held to a calibration
+// run on THIS model (ctx->calib[mode]; run here unless `measure` is off or the value is already there): within half the contract of mode 0.
+// forced: HERRO_FORCE_PRECISION=1 (A/B builds) or herro_debug_force_precision keep a mode that missed the bound, for measurements.
+struct F16Gate {
+  bool shapes, range, f8;
+  int rc = HERRO_OK;      // of the calibration run, where one was needed
+  bool within = false;
+  bool forced;
+  bool available() const { return shapes && range && f8; }
+};
+static F16Gate f16_gate(herro_ctx* ctx, int mode, bool measure = true) {
+  static const bool env_force = ab_env("HERRO_FORCE_PRECISION", 0) != 0;
+  F16Gate g;
+  g.shapes = model_h_supported(ctx->M);
+  g.range = ctx->wmax < 65504.f;
+  g.f8 = mode != 6 || model_h_f8_supported(ctx->M);
+  g.forced = env_force || ctx->debug_force_precision;
+  if (!g.available()) return g;
+  if (measure && ctx->calib[mode] < 0.f) g.rc = calibrate(ctx, &mode, 1);
+  g.within = g.rc == HERRO_OK && ctx->calib[mode] <= 5e-4f;
+  return g;
+}
+
+// Device stage of herro_load_model: every blob of the host form (model_pack.h) to the device, M's pointers from their places, the PE table.  Returns with
+// the stream idle — until then hm, which the copies read, must live.  allocs: what the caller frees on failure and keeps with the model otherwise.
+static int upload_model(herro_ctx* ctx, const HostModel& hm, ModelDev& M, std::vector<void*>& allocs) {
+  std::vector<void*> dev(hm.blobs.size(), nullptr);
+  for (size_t i = 0; i < dev.size(); i++) {
+    const Blob& b = hm.blobs[i];
+    HIP_TRY(ctx, hipMalloc(&dev[i], std::max<size_t>(b.bytes, 1)));
+    allocs.push_back(dev[i]);
+    if (b.bytes) HIP_TRY(ctx, hipMemcpyAsync(dev[i], b.p, b.bytes, hipMemcpyHostToDevice, ctx->stream));
   }
-  std::fclose(f);
-  if (!ok) { ctx->err = "malformed model file"; return HERRO_E_NO_MODEL; }
-  if (h.rows != HERRO_ROWS || h.n_layers > 16 || (h.kw & 1) == 0 || h.d_model % 64 || h.n_heads == 0 || h.d_model % h.n_heads || (h.d_model / h.n_heads != 32 && h.d_model / h.n_heads != 64) || h.n_heads > 32 ||
-      (h.kw * h.c1) % 32 || (h.rows * h.c2) % 32 || h.d_ff % 32 || h.c2 % 16) {
-    ctx->err = "unsupported model hyper-parameters";
-    return HERRO_E_UNSUPPORTED;
-  }
-  free_all(ctx->model_allocs);
-  ModelDev M{};
-  M.h = h;
-  hipError_t e = hipSuccess;
-  bool missing = false;
-  auto get = [&](const std::string& n, size_t expect) -> const std::vector<float>& {
-    static std::vector<float> empty;
-    auto it = T.find(n);
-    if (it == T.end() || it->second.data.size() != expect) { missing = true; ctx->err = "model tensor missing/mis-sized: " + n; return empty; }
-    return it->second.data;
+  auto f32 = [&](int i) { return i < 0 ? nullptr : (const float*)dev[i]; };
+  auto u16 = [&](int i) { return i < 0 ? nullptr : (const uint16_t*)dev[i]; };
+  auto weight = [&](const HostWeight& w) {
+    Weight d;
+    d.K = w.K; d.N = w.N; d.s8 = w.s8;
+    d.f32 = f32(w.blob[W_F32]); d.bias = f32(w.blob[W_BIAS]);
+    d.hi = u16(w.blob[W_HI]); d.lo = u16(w.blob[W_LO]); d.phi = u16(w.blob[W_PHI]); d.plo = u16(w.blob[W_PLO]);
+    d.h16 = u16(w.blob[W_H16]); d.l16 = u16(w.blob[W_L16]); d.ph16 = u16(w.blob[W_PH16]);
+    d.p8 = w.blob[W_P8] < 0 ? nullptr : (const uint8_t*)dev[w.blob[W_P8]];
+    return d;
   };
-  auto vec = [&](const std::string& n, size_t expect) -> const float* {
-    const auto& v = get(n, expect);
-    if (missing) return nullptr;
-    return up_f32(ctx, v, e);
-  };
-  float wmax_seen = 0.f;
-  auto weight = [&](const std::string& n, uint32_t K, uint32_t N) -> Weight {
-    Weight w;
-    w.K = K; w.N = N;
-    const auto& wt = get(n + ".wt", (size_t)K * N);
-    if (missing) return w;
-    for (float x : wt) wmax_seen = std::max(wmax_seen, std::fabs(x));
-    w.f32 = up_f32(ctx, wt, e);
-    std::vector<uint16_t> hi(wt.size()), lo(wt.size());
-    for (size_t i = 0; i < wt.size(); i++) { hi[i] = h_bf16(wt[i]); lo[i] = h_bf16(wt[i] - h_bf16f(hi[i])); }
-    uint16_t* dh = dev_alloc_copy(hi, ctx->stream, e); ctx->model_allocs.push_back(dh);
-    uint16_t* dl = dev_alloc_copy(lo, ctx->stream, e); ctx->model_allocs.push_back(dl);
-    w.hi = dh; w.lo = dl;
-    if (N % 32 == 0 && K % 32 == 0) {  // fragment-ordered copy for the kernels that stream weights into registers
-      std::vector<uint16_t> ph(wt.size()), pl(wt.size());
-      const uint32_t nks = K / 32;
-      for (uint32_t n32 = 0; n32 < N / 32; n32++)
-        for (uint32_t jt = 0; jt < 2; jt++)
-          for (uint32_t ks = 0; ks < nks; ks++)
-            for (uint32_t lane = 0; lane < 64; lane++) {
-              const uint32_t fr = lane & 15, fg = lane >> 4;
-              const size_t src = (size_t)(n32 * 32 + 8 * (fr >> 2) + 4 * jt + (fr & 3)) * K + ks * 32 + fg * 8;
-              const size_t dst = ((((size_t)n32 * 2 + jt) * nks + ks) * 64 + lane) * 8;
-              for (uint32_t e8 = 0; e8 < 8; e8++) { ph[dst + e8] = hi[src + e8]; pl[dst + e8] = lo[src + e8]; }
-            }
-      uint16_t* dph = dev_alloc_copy(ph, ctx->stream, e); ctx->model_allocs.push_back(dph);
-      uint16_t* dpl = dev_alloc_copy(pl, ctx->stream, e); ctx->model_allocs.push_back(dpl);
-      w.phi = dph; w.plo = dpl;
-    }
-    {  // f16 forms (precision 4 / 5, model_h.hip)
-      std::vector<uint16_t> h16(wt.size()), l16(wt.size());
-      for (size_t i = 0; i < wt.size(); i++) { h16[i] = h_f16(wt[i]); l16[i] = h_f16(wt[i] - h_f16f(h16[i])); }
-      uint16_t* d1 = dev_alloc_copy(h16, ctx->stream, e); ctx->model_allocs.push_back(d1);
-      uint16_t* d2 = dev_alloc_copy(l16, ctx->stream, e); ctx->model_allocs.push_back(d2);
-      w.h16 = d1; w.l16 = d2;
-      if (N % 32 == 0 && K % 32 == 0) {
-        std::vector<uint16_t> ph(wt.size());
-        const uint32_t nks = K / 32;
-        for (uint32_t n32 = 0; n32 < N / 32; n32++)
-          for (uint32_t jt = 0; jt < 2; jt++)
-            for (uint32_t ks = 0; ks < nks; ks++)
-              for (uint32_t lane = 0; lane < 64; lane++) {
-                const uint32_t fr = lane & 15, fg = lane >> 4;
-                const size_t src = (size_t)(n32 * 32 + 8 * (fr >> 2) + 4 * jt + (fr & 3)) * K + ks * 32 + fg * 8;
-                const size_t dst = ((((size_t)n32 * 2 + jt) * nks + ks) * 64 + lane) * 8;
-                for (uint32_t e8 = 0; e8 < 8; e8++) ph[dst + e8] = h16[src + e8];
-              }
-        uint16_t* d3 = dev_alloc_copy(ph, ctx->stream, e); ctx->model_allocs.push_back(d3);
-        w.ph16 = d3;
-      }
-      if (N % 32 == 0 && K % 128 == 0) {   // e4m3 copy for the remainder term of precision 6 (Weight::p8): W * 2^sw, sw the largest power of two that keeps max |W| * 2^sw <= 448
-        float wmax = 0.f;
-        for (float x : wt) wmax = std::max(wmax, std::fabs(x));
-        int sw = 0;
-        if (wmax > 0.f && std::isfinite(wmax)) { int ex; (void)std::frexp(448.0 / (double)wmax, &ex); sw = std::max(-32, std::min(32, ex - 1)); }
-        std::vector<uint8_t> p8(wt.size());
-        const uint32_t ns = K / 128;
-        const float mul = std::ldexp(1.0f, sw);
-        for (uint32_t n32 = 0; n32 < N / 32; n32++)
-          for (uint32_t jt = 0; jt < 2; jt++)
-            for (uint32_t st = 0; st < ns; st++)
-              for (uint32_t hf = 0; hf < 2; hf++)
-                for (uint32_t lane = 0; lane < 64; lane++) {
-                  const uint32_t fr = lane & 15, fg = lane >> 4;
-                  const size_t src = (size_t)(n32 * 32 + 8 * (fr >> 2) + 4 * jt + (fr & 3)) * K + st * 128 + fg * 32 + hf * 16;
-                  const size_t dst = ((((((size_t)n32 * 2 + jt) * ns + st) * 2 + hf) * 64) + lane) * 16;
-                  for (uint32_t j = 0; j < 16; j++) p8[dst + j] = f32_to_e4m3(wt[src + j] * mul);
-                }
-        uint8_t* d8 = dev_alloc_copy(p8, ctx->stream, e); ctx->model_allocs.push_back(d8);
-        w.p8 = d8;
-        w.s8 = (uint32_t)(127 - sw);
-      }
-    }
-    w.bias = vec(n + ".b", N);
-    return w;
-  };
-  const uint32_t D = h.d_model;
-  M.t1 = vec("t1", (size_t)h.kw * 12 * h.c1);
-  M.wq1 = vec("wq1", (size_t)h.kw * h.c1);
-  M.b1 = vec("b1", h.c1);
-  if (!missing && h.kw == 3 && h.c1 == 64) {   // conv1 as a GEMM (k_conv_m): W1g[c][tap * 32 + slot], slots as listed in model_h.hip
-    const auto& t1 = get("t1", (size_t)h.kw * 12 * h.c1);
-    const auto& wq = get("wq1", (size_t)h.kw * h.c1);
-    const auto& b1 = get("b1", h.c1);
-    const uint32_t K = 96, N = 64, nks = 3;
-    std::vector<uint16_t> g((size_t)N * K, 0), ph((size_t)N * K);
-    for (uint32_t c = 0; c < N && !missing; c++)
-      for (uint32_t tp = 0; tp < 3; tp++) {
-        uint16_t* row = g.data() + (size_t)c * K + tp * 32;
-        auto hl = [&](float v, uint16_t& hi, uint16_t& lo) { hi = h_f16(v); lo = h_f16(v - h_f16f(hi)); };
-        for (uint32_t tok = 0; tok < 12; tok++) hl(t1[((size_t)tp * 12 + tok) * N + c], row[tok], row[16 + tok]);
-        uint16_t qh, ql;
-        hl(wq[(size_t)tp * N + c], qh, ql);
-        row[13] = qh; row[14] = qh; row[29] = ql;
-        if (tp == 0) hl(b1[c], row[15], row[31]);
-      }
-    for (uint32_t n32 = 0; n32 < N / 32; n32++)
-      for (uint32_t jt = 0; jt < 2; jt++)
-        for (uint32_t ks = 0; ks < nks; ks++)
-          for (uint32_t lane = 0; lane < 64; lane++) {
-            const uint32_t fr = lane & 15, fg = lane >> 4;
-            const size_t src = (size_t)(n32 * 32 + 8 * (fr >> 2) + 4 * jt + (fr & 3)) * K + ks * 32 + fg * 8;
-            const size_t dst = ((((size_t)n32 * 2 + jt) * nks + ks) * 64 + lane) * 8;
-            for (uint32_t e8 = 0; e8 < 8; e8++) ph[dst + e8] = g[src + e8];
-          }
-    uint16_t* dg = dev_alloc_copy(ph, ctx->stream, e); ctx->model_allocs.push_back(dg);
-    M.conv1g.ph16 = dg; M.conv1g.K = K; M.conv1g.N = N;
+  M = ModelDev{};
+  M.h = hm.file.h;
+  M.t1 = f32(hm.t1); M.wq1 = f32(hm.wq1); M.b1 = f32(hm.b1); M.pe_div = f32(hm.pe_div);
+  M.conv1g = weight(hm.conv1g); M.conv2 = weight(hm.conv2); M.fc = weight(hm.fc); M.heads = weight(hm.heads);
+  for (uint32_t l = 0; l < M.h.n_layers; l++) {
+    const HostLayer& y = hm.layer[l];
+    M.layer[l].ln1_g = f32(y.ln1_g); M.layer[l].ln1_b = f32(y.ln1_b); M.layer[l].ln2_g = f32(y.ln2_g); M.layer[l].ln2_b = f32(y.ln2_b);
+    M.layer[l].qkv = weight(y.qkv); M.layer[l].proj = weight(y.proj); M.layer[l].ff1 = weight(y.ff1); M.layer[l].ff2 = weight(y.ff2);
   }
-  M.conv2 = weight("conv2", h.kw * h.c1, h.c2);
-  M.fc = weight("fc", h.rows * h.c2, D);
-  M.pe_div = vec("pe_div", D / 2);
-  for (uint32_t l = 0; l < h.n_layers && !missing; l++) {
-    const std::string p = "L" + std::to_string(l) + ".";
-    M.layer[l].ln1_g = vec(p + "ln1.g", D); M.layer[l].ln1_b = vec(p + "ln1.b", D);
-    M.layer[l].ln2_g = vec(p + "ln2.g", D); M.layer[l].ln2_b = vec(p + "ln2.b", D);
-    M.layer[l].qkv = weight(p + "qkv", D, 3 * D);
-    M.layer[l].proj = weight(p + "proj", D, D);
-    M.layer[l].ff1 = weight(p + "ff1", D, h.d_ff);
-    M.layer[l].ff2 = weight(p + "ff2", h.d_ff, D);
-  }
-  M.act = 0; M.norm_first = 1; M.pe_kind = 0; M.final_norm = 1; M.pe_learned = nullptr; M.pe_learned_rows = 0;
-  if (auto it = T.find("cfg"); it != T.end()) {   // a variant of the family (absent: the defaults)
-    const std::vector<float>& c = it->second.data;
-    if (c.size() < 4 || c[0] < 0 || c[0] > 2 || c[1] < 0 || c[1] > 1 || c[2] < 0 || c[2] > 2 || c[3] < 0 || c[3] > 1) { free_all(ctx->model_allocs); ctx->err = "model file: cfg tensor not understood"; return HERRO_E_UNSUPPORTED; }
-    M.act = (uint32_t)c[0]; M.norm_first = (uint32_t)c[1]; M.pe_kind = (uint32_t)c[2]; M.final_norm = (uint32_t)c[3];
-  }
-  if (M.pe_kind == 1) {
-    auto it = T.find("pe_table");
-    if (it == T.end() || it->second.dims.size() != 2 || it->second.dims[1] != D || it->second.dims[0] == 0) { free_all(ctx->model_allocs); ctx->err = "model file: learned position table missing / mis-shaped"; return HERRO_E_NO_MODEL; }
-    M.pe_learned = up_f32(ctx, it->second.data, e);
-    M.pe_learned_rows = it->second.dims[0];
-  }
-  if (M.final_norm) { M.lnf_g = vec("lnf.g", D); M.lnf_b = vec("lnf.b", D); }
-  else { M.lnf_g = nullptr; M.lnf_b = nullptr; }
-  M.heads = weight("heads", D, 16);
-  if (missing) { free_all(ctx->model_allocs); return HERRO_E_NO_MODEL; }
-  HIP_TRY(ctx, e);
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  M.pe_tab = nullptr;
-  M.pe_rows = 0;
+  M.lnf_g = f32(hm.lnf_g); M.lnf_b = f32(hm.lnf_b);
+  M.act = hm.act; M.norm_first = hm.norm_first; M.pe_kind = hm.pe_kind; M.final_norm = hm.final_norm;
+  M.pe_learned = f32(hm.pe_learned); M.pe_learned_rows = hm.pe_learned_rows;
   if (model_h_supported(M)) {   // the positional encoding of rows 0 .. 16383 (a 4096-base window has ~4700 rows, an 8192-base one ~9500), 16 MB; k_layers_p computes the rows beyond it itself
     const uint32_t rows = 16384;
     float* tab = nullptr;
-    if (hipMalloc(&tab, (size_t)rows * D * 4) == hipSuccess) {
-      ctx->model_allocs.push_back(tab);
-      launch_pe_table(M.pe_div, tab, rows, D, ctx->stream);
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (hipMalloc(&tab, (size_t)rows * M.h.d_model * 4) == hipSuccess) {
+      allocs.push_back(tab);
+      launch_pe_table(M.pe_div, tab, rows, M.h.d_model, ctx->stream);
       M.pe_tab = tab;
       M.pe_rows = rows;
     } else (void)hipGetLastError();
   }
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return HERRO_OK;
+}
+
+// Operand format of the model just loaded.  bf16 hi/lo x3 (mode 1, ~1e-5) always works; an f16 mode has to pass f16_gate.
+static void choose_precision(herro_ctx* ctx) {
+  if (ctx->precision_set) {   // the caller's choice stands — held to the same bound as the library's own (ADVICE r5: a mode set before the load used to go unchecked)
+    if (ctx->precision < 4) return;
+    F16Gate g = f16_gate(ctx, ctx->precision);
+    if (!g.shapes || !g.range) { ctx->precision = 1; ctx->calib_note = "f16 modes unavailable for this model (shapes or weight range): mode 1"; return; }
+    if (!g.f8) { ctx->precision = 4; ctx->calib_note = "no e4m3 weight copies for this model (K % 128): mode 4"; g = f16_gate(ctx, 4); }
+    if (!g.within) {
+      char buf[200];
+      snprintf(buf, sizeof buf, "requested mode %d measured %.3g (> 5e-4) against mode 0 on the calibration batch%s", ctx->precision, (double)ctx->calib[ctx->precision], g.forced ? " (forced)" : ": mode 1");
+      ctx->calib_note = buf;
+      if (!g.forced) ctx->precision = 1;
+    }
+    return;
+  }
+  ctx->precision = 1;
+  if (const F16Gate g = f16_gate(ctx, 4, false); !g.available()) {
+    ctx->calib_note = g.shapes ? "a weight lies outside the f16 range: mode 1" : "no f16 kernels for these shapes: mode 1";
+    return;
+  }
+  // the tiers, cheapest first (MFMA call-terms per encoder layer: 12, 13, 20, 21): the first one within the gate's bound of mode 0 is kept (round 6).
+  // Mode 6 (e4m3 remainder) measures no faster than 4 and is not a candidate; herro_set_precision(6) calibrates it on demand.
+  static const int tiers[4] = {5, 7, 8, 4};
+  if (calibrate(ctx, tiers, 4) != HERRO_OK) { ctx->calib_note = "calibration run failed: mode 1"; return; }   // (one run of mode 0 for the four of them)
+  for (int t : tiers) if (f16_gate(ctx, t).within) { ctx->precision = t; break; }
+  char buf[400];
+  snprintf(buf, sizeof buf, "calibration (256 pileup-shaped rows): max |logit(mode) - logit(mode 0, f32)| = %.3g (mode 5, f16 single terms) / %.3g (mode 7, FF single) / "
+           "%.3g (mode 8, proj single) / %.3g (mode 4, f16) -> mode %d (the cheapest within 5e-4)",
+           (double)ctx->calib[5], (double)ctx->calib[7], (double)ctx->calib[8], (double)ctx->calib[4], ctx->precision);
+  ctx->calib_note = buf;
+}
+
+int herro_load_model(herro_ctx* ctx, const char* path) {
+  if (!ctx || !path) return HERRO_E_INVALID;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // 1. the host form of the file (model_pack.h).  A file that is not a model leaves the context as it was: the model it holds keeps serving.
+  HostModel hm;
+  std::string why;
+  if (const int rc = load_host_model(path, hm, why)) { ctx->err = why; return rc; }
+  // 2. the old model goes, the new one goes up.  From here to the end of the upload the context has no model.
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->has_model = false;
+  ctx->M = ModelDev{};
+  free_all(ctx->model_allocs);
   // the activation scratch is sized by the hyper-parameters of the model that was loaded when it was allocated (ensure_scratch: kw * c1, c2, d_model, d_ff per
   // token): it goes with that model.  Kept, a larger model loaded into the same context wrote its y1 / y2 / ff rows past the ends of the smaller model's
   // buffers as long as the token count fitted (a kw 1 model, then the default one: three times y1) — tests/test_gpu_rf_models.py, which loads one model
   // behind another, met it as an illegal memory access.  (The stream is idle here: synchronised above.)
   free_all(ctx->scratch_allocs);
   ctx->scratch_cap = 0;
+  ModelDev M;
+  std::vector<void*> allocs;
+  if (const int rc = upload_model(ctx, hm, M, allocs)) { free_all(allocs); return rc; }
+  ctx->model_allocs = std::move(allocs);
   ctx->M = M;
+  ctx->wmax = hm.wmax;
   ctx->has_model = true;
-  ctx->wmax = wmax_seen;
   for (float& c : ctx->calib) c = -1.f;
   ctx->calib_note.clear();
-  // Operand format.  bf16 hi/lo x3 (mode 1, ~1e-5) always works.  The f16 modes need the shapes their kernels are written
-  // for, weights inside the f16 range (|w| >= 65520 rounds to inf, the remainder term to -inf: NaN logits), and — because
-  // their margin to the 1e-3 contract was measured on random-init weights only — a calibration run on THIS model.
-  const bool f16_ok = model_h_supported(M) && wmax_seen < 65504.f;
-  static const bool force = ab_env("HERRO_FORCE_PRECISION", 0) != 0;
-  if (ctx->precision_set) {   // the caller's choice stands — held to the same bound as the library's own (ADVICE r5: a mode set before the load used to go unchecked)
-    if (ctx->precision >= 4 && !f16_ok) { ctx->precision = 1; ctx->calib_note = "f16 modes unavailable for this model (shapes or weight range): mode 1"; }
-    if (ctx->precision == 6 && !model_h_f8_supported(M)) { ctx->precision = 4; ctx->calib_note = "no e4m3 weight copies for this model (K % 128): mode 4"; }
-    if (ctx->precision >= 4) {
-      const int want = ctx->precision;
-      const int modes[1] = {want};
-      const int rc = calibrate(ctx, modes, 1);
-      ctx->precision = want;
-      if (rc != HERRO_OK || !(ctx->calib[want] <= 5e-4f)) {
-        char buf[200];
-        const bool forced = force || ctx->debug_force_precision;
-        snprintf(buf, sizeof buf, "requested mode %d measured %.3g (> 5e-4) against mode 0 on the calibration batch%s", want, (double)ctx->calib[want], forced ? " (forced)" : ": mode 1");
-        ctx->calib_note = buf;
-        if (!forced) ctx->precision = 1;
-      }
-    }
-    return HERRO_OK;
-  }
-  if (!f16_ok) {
-    ctx->precision = 1;
-    ctx->calib_note = model_h_supported(M) ? "a weight lies outside the f16 range: mode 1" : "no f16 kernels for these shapes: mode 1";
-    return HERRO_OK;
-  }
-  {  // the tiers, cheapest first (MFMA call-terms per encoder layer: 12, 13, 20, 21): the first one within 5e-4 (half the contract) of mode 0 is kept (round 6).
-     // Mode 6 (e4m3 remainder) measures no faster than 4 and is not a candidate; herro_set_precision(6) calibrates it on demand.
-    static const int tiers[4] = {5, 7, 8, 4};
-    const int rc = calibrate(ctx, tiers, 4);
-    if (rc != HERRO_OK) { ctx->precision = 1; ctx->calib_note = "calibration run failed: mode 1"; return HERRO_OK; }
-    ctx->precision = 1;
-    for (int t : tiers) if (ctx->calib[t] <= 5e-4f) { ctx->precision = t; break; }
-    char buf[400];
-    snprintf(buf, sizeof buf, "calibration (256 pileup-shaped rows): max |logit(mode) - logit(mode 0, f32)| = %.3g (mode 5, f16 single terms) / %.3g (mode 7, FF single) / "
-             "%.3g (mode 8, proj single) / %.3g (mode 4, f16) -> mode %d (the cheapest within 5e-4)",
-             (double)ctx->calib[5], (double)ctx->calib[7], (double)ctx->calib[8], (double)ctx->calib[4], ctx->precision);
-    ctx->calib_note = buf;
-  }
+  // 3. the operand format
+  choose_precision(ctx);
   return HERRO_OK;
 }
 
@@ -988,35 +811,26 @@ int64_t herro_model_describe(const herro_ctx* ctx, char* out, uint64_t cap) {
 
 int herro_set_precision(herro_ctx* ctx, int mode) {
   if (!ctx || mode < 0 || mode > 8) return HERRO_E_INVALID;
-  if (mode >= 4 && ctx->has_model && ctx->wmax >= 65504.f) {
-    ctx->err = "precision 4 .. 8 (f16 operands): a weight of this model lies outside the f16 range";
-    return HERRO_E_UNSUPPORTED;
-  }
-  if (mode >= 4 && ctx->has_model && !model_h_supported(ctx->M)) {
-    ctx->err = "precision 4 .. 8 (the f16 encoder stack) need d_model 256, 8 heads of 32, d_ff % 256 == 0 and the default variant (Pre-LN, ReLU, sinusoidal position, final LayerNorm)";
-    return HERRO_E_UNSUPPORTED;
-  }
-  if (mode == 6 && ctx->has_model && !model_h_f8_supported(ctx->M)) {
-    ctx->err = "precision 6 needs the e4m3 copies of proj / ff1 / ff2 (K % 128 == 0)";
-    return HERRO_E_UNSUPPORTED;
-  }
-  // every f16 mode is held to the calibration of THIS model — measured here if the load did not (mode 6 always; any mode when the load-time choice was
-  // switched off by an earlier call) — and refused above 5e-4, half the 1e-3 contract (HERRO_FORCE_PRECISION=1 in A/B builds overrides, for measurements)
-  if (mode >= 4 && ctx->has_model) {
-    if (ctx->calib[mode] < 0.f) {
-      const int modes[1] = {mode};
-      const int rc = calibrate(ctx, modes, 1);
-      if (rc != HERRO_OK) return rc;
+  if (mode >= 4 && ctx->has_model) {   // f16_gate: the mode is measured here if the load did not (mode 6 always; any mode when the load-time choice was switched off by an earlier call)
+    const F16Gate g = f16_gate(ctx, mode);
+    if (!g.range) {
+      ctx->err = "precision 4 .. 8 (f16 operands): a weight of this model lies outside the f16 range";
+      return HERRO_E_UNSUPPORTED;
     }
-    const float cal = ctx->calib[mode];
-    if (cal > 5e-4f || std::isnan(cal)) {
-      static const bool force = ab_env("HERRO_FORCE_PRECISION", 0) != 0;
-      if (!force && !ctx->debug_force_precision) {
-        char buf[200];
-        snprintf(buf, sizeof buf, "precision %d refused: the calibration of this model measured a logit difference of %.3g (> 5e-4) for the f16 kernels", mode, (double)cal);
-        ctx->err = buf;
-        return HERRO_E_UNSUPPORTED;
-      }
+    if (!g.shapes) {
+      ctx->err = "precision 4 .. 8 (the f16 encoder stack) need d_model 256, 8 heads of 32, d_ff % 256 == 0 and the default variant (Pre-LN, ReLU, sinusoidal position, final LayerNorm)";
+      return HERRO_E_UNSUPPORTED;
+    }
+    if (!g.f8) {
+      ctx->err = "precision 6 needs the e4m3 copies of proj / ff1 / ff2 (K % 128 == 0)";
+      return HERRO_E_UNSUPPORTED;
+    }
+    if (g.rc != HERRO_OK) return g.rc;
+    if (!g.within && !g.forced) {
+      char buf[200];
+      snprintf(buf, sizeof buf, "precision %d refused: the calibration of this model measured a logit difference of %.3g (> 5e-4) for the f16 kernels", mode, (double)ctx->calib[mode]);
+      ctx->err = buf;
+      return HERRO_E_UNSUPPORTED;
     }
   }
   ctx->precision = mode;
@@ -2697,6 +2511,40 @@ int herro_clock_probe(herro_ctx* ctx, double* shader_mhz) {
   return HERRO_OK;
 }
 uint32_t herro_debug_e4m3(float x) { return f32_to_e4m3(x); }   // the host encoder of the precision-6 weight copies (tests)
+
+// One tensor of a model file through the loader's own reader and packers (model_pack.h), no device and no context (tests/test_model_pack.py).
+int64_t herro_debug_model_pack(const char* path, const char* tensor, uint32_t K, uint32_t N, int form, void* out, uint64_t cap, uint32_t* s8) {
+  if (!path || !out || form < 0 || form > 6 || (form != 6 && !tensor) || (form == 5 && !s8)) return HERRO_E_INVALID;
+  ModelFile mf;
+  std::string why;
+  if (const int rc = read_model_file(path, mf, why)) return rc;
+  auto data = [&](const char* n, size_t expect) -> const float* {
+    auto it = mf.T.find(n);
+    return it == mf.T.end() || it->second.data.size() != expect ? nullptr : it->second.data.data();
+  };
+  std::vector<uint16_t> r16;
+  std::vector<uint8_t> r8;
+  if (form == 6) {
+    const ModelHyper& h = mf.h;
+    const float *t1 = data("t1", (size_t)h.kw * 12 * h.c1), *wq1 = data("wq1", (size_t)h.kw * h.c1), *b1 = data("b1", h.c1);
+    if (h.kw != 3 || h.c1 != 64 || !t1 || !wq1 || !b1) return HERRO_E_NO_MODEL;
+    r16 = pack_frag16(conv1_gemm_rows(t1, wq1, b1).data(), 96, 64);
+  } else {
+    const float* w = data(tensor, (size_t)K * N);
+    if (!w) return HERRO_E_NO_MODEL;
+    if (form <= 2 || form == 5) if (!K || !N || N % 32 || K % (form == 5 ? 128 : 32)) return HERRO_E_INVALID;
+    if (form == 5) r8 = pack_frag8(w, K, N, *s8);
+    else {
+      Split16 s = form <= 1 ? split_bf16(w, (size_t)K * N) : split_f16(w, (size_t)K * N);
+      const std::vector<uint16_t>& plane = form == 1 || form == 4 ? s.lo : s.hi;
+      r16 = form <= 2 ? pack_frag16(plane.data(), K, N) : plane;
+    }
+  }
+  const uint64_t bytes = form == 5 ? r8.size() : r16.size() * 2;
+  if (bytes > cap) return HERRO_E_INVALID;
+  if (bytes) std::memcpy(out, form == 5 ? (const void*)r8.data() : (const void*)r16.data(), bytes);
+  return (int64_t)bytes;
+}
 int herro_debug_job_rf_fused(const herro_job* job) { return job && job->inferred ? (job->rf_fused_used ? 1 : 0) : HERRO_E_STATE; }
 int herro_debug_job_rf_left(const herro_job* job) { return job && job->inferred ? (int)job->rf_left_windows : HERRO_E_STATE; }
 

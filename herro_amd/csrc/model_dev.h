@@ -12,21 +12,12 @@
 
 #include "infer_plan.h"
 #include "job_dev.h"
+#include "model_pack.h"   // ModelHyper, and the host code that produces every array below
 
 namespace herro {
 
-struct ModelHyper {  // header of the flat weight file (tools/export_weights.py)
-  uint32_t magic;    // 'HRRO'
-  uint32_t version;
-  uint32_t rows;     // 31
-  uint32_t kw;       // conv kernel width along the window axis (odd)
-  uint32_t c1, c2;   // conv channels
-  uint32_t d_model, n_heads, d_ff, n_layers;
-  uint32_t n_tensors;
-  float ln_eps;
-};
-
-// A [K,N] row-major weight kept in three forms: f32, and its bf16 hi/lo split (w ~= hi + lo).
+// A [K,N] row-major weight kept in three forms: f32, and its bf16 hi/lo split (w ~= hi + lo).  The layouts documented here are
+// implemented once each in model_pack.h (pack_weight: pack_frag16 for phi / plo / ph16, pack_frag8 for p8), on the host, at load.
 struct Weight {
   const float* f32 = nullptr;
   const uint16_t* hi = nullptr;
@@ -60,7 +51,7 @@ struct ModelDev {
   const float* t1;      // [kw][12][c1] embedding folded through conv1 (+BN), tap-major
   const float* wq1;     // [kw][c1]     conv1 weights of the quality channel
   const float* b1;      // [c1]
-  Weight conv1g;        // conv1 as a GEMM for k_conv_m (model_h.hip): [kw*32, c1] f16 hi / lo slots of table, quality weight and bias; ph16 only
+  Weight conv1g;        // conv1 as a GEMM for k_conv_m (model_h.hip): [kw*32, c1] f16 hi / lo slots of table, quality weight and bias (model_pack.h: conv1_gemm_rows); ph16 only
   Weight conv2;         // [kw*c1, c2]  (BN folded), k = tap*c1 + c
   Weight fc;            // [rows*c2, d_model], k = row*c2 + c
   const float* pe_div;  // [d_model/2]

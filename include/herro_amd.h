@@ -299,6 +299,11 @@ int64_t herro_debug_job_cwd(herro_job* job, uint32_t ow, uint32_t* out, uint64_t
 int herro_debug_job_rf_fused(const herro_job* job);  /* 1: the last herro_job_infer read records k_rows gathered itself; 0: k_rfq's */
 int herro_debug_job_rf_left(const herro_job* job);    /* ... of which this many windows (above the 256 informative rows k_rows stages) were filled by k_rfq behind it, the others staying fused */
 uint32_t herro_debug_e4m3(float x);                   /* host f32 -> OCP e4m3 (round to nearest even, saturating) as used for the precision-6 weight copies */
+/* Host-only test hook of the model loader: reads `path` through herro_load_model's reader and packs the [N][K] tensor named `tensor` through its
+ * packers; no device, no context.  form: 0 / 1 bf16 hi / lo in MFMA fragment order, 2 f16 hi in fragment order, 3 / 4 f16 hi / lo row-major,
+ * 5 e4m3 in fragment order (*s8 = the E8M0 scale byte), 6 the conv1 GEMM matrix in fragment order (from t1 / wq1 / b1; tensor, K, N ignored).
+ * Returns the bytes written to out (cap: its room), or a negative HERRO_E_* (NO_MODEL: malformed file, tensor missing or mis-sized). */
+int64_t herro_debug_model_pack(const char* path, const char* tensor, uint32_t K, uint32_t N, int form, void* out, uint64_t cap, uint32_t* s8);
 int herro_debug_sib_fault(herro_ctx* ctx);            /* raises the context's sibling-tile error word as a tile that timed out would: the next fetch repeats its job's model pass without sibling tiles */
 int herro_debug_force_precision(herro_ctx* ctx, int on); /* tests: herro_set_precision / herro_load_model skip the calibration gate (to MEASURE a mode the model's calibration refuses) */
 int herro_debug_sib_retries(const herro_ctx* ctx);    /* model passes repeated that way on this context */
