@@ -51,7 +51,8 @@ EXPORTS = [
     "herro_set_seed_rescue", "herro_overlaps_rescued", "herro_pairs_rescued", "herro_debug_seed_rescue",
     "herro_find_adapters", "herro_adapter_hits_n", "herro_adapter_hits_data", "herro_adapter_hits_off", "herro_adapter_hits_free", "herro_debug_set_adapter_cap",
     "herro_trim_plan", "herro_trim_n_pieces", "herro_trim_pieces", "herro_trim_piece_off", "herro_trim_stats", "herro_trim_free",
-    "herro_reads_create", "herro_reads_cut",
+    "herro_reads_create", "herro_reads_cut", "herro_reads_cut_names",
+    "herro_store_cut", "herro_debug_store_copy",
 ]
 
 
@@ -355,6 +356,11 @@ def lib():
             L.herro_reads_create.argtypes = [u32, vp, vp, vp, vp, vp, vp, u64]
             L.herro_reads_cut.restype = vp
             L.herro_reads_cut.argtypes = [vp, u64, vp, vp, u64]
+            L.herro_reads_cut_names.restype = vp
+            L.herro_reads_cut_names.argtypes = [u32, vp, vp, vp, u64, vp, vp, u64]
+            L.herro_store_cut.argtypes = [vp, u64, vp, vp]
+            L.herro_debug_store_copy.restype = C.c_int64
+            L.herro_debug_store_copy.argtypes = [vp, C.c_int, vp, u64]
         except AttributeError:
             if not os.environ.get("HERRO_LIB"):
                 raise
@@ -627,6 +633,34 @@ class Context:
         """Adopt the read store of another context of the same device (herro_share_reads): one copy in HBM per device."""
         self._chk(self._l.herro_share_reads(self.h, other.h))
         self.n_reads = getattr(other, "n_reads", None)
+
+    def cut_store(self, pieces, name_class: np.ndarray | None = None):
+        """Replace the read store by pieces of it, on the device (herro_store_cut): read x of the new store is bases [start, end) of read rid of
+        the current one, in the order of `pieces` (PIECE_DTYPE, as trim_plan returns them).  What io.cut_reads + set_reads build, without a base
+        crossing PCIe."""
+        pieces = np.ascontiguousarray(pieces, PIECE_DTYPE)
+        nc = None if name_class is None else np.ascontiguousarray(name_class, np.uint32)
+        if nc is not None and len(nc) != len(pieces):
+            raise HerroError(-1, "herro_store_cut: name_class has one entry per piece")
+        self._chk(self._l.herro_store_cut(self.h, len(pieces), pieces.ctypes.data, None if nc is None else nc.ctypes.data))
+        self.n_reads = len(pieces)
+
+    STORE_ARRAYS = (("words", np.uint64), ("word_off", np.uint64), ("qual", np.uint8), ("qual_off", np.uint64), ("p0", np.uint32), ("p1", np.uint32))
+
+    def store_arrays(self) -> dict:
+        """Test hook (herro_debug_store_copy): the six arrays of the read store as they lie on the device — words (the pad word included),
+        word_off, qual (without its pad), qual_off, p0, p1 (their two pad entries included)."""
+        out = {}
+        for which, (name, dt) in enumerate(self.STORE_ARRAYS):
+            nb = int(self._l.herro_debug_store_copy(self.h, which, None, 0))
+            if nb < 0:
+                self._chk(nb)
+            a = np.zeros(nb // np.dtype(dt).itemsize, dt)
+            got = int(self._l.herro_debug_store_copy(self.h, which, a.ctypes.data, a.nbytes))
+            if got < 0:
+                self._chk(got)
+            out[name] = a
+        return out
 
     def load_model(self, path: str):
         self._chk(self._l.herro_load_model(self.h, path.encode()))
@@ -1551,14 +1585,20 @@ def _trim_plan(L, rl, al, hits, ho, p):
     return pieces, piece_off, TrimStats(*[int(x) for x in st])
 
 
-def trim_reads(ctx: "Context", reads, adapters, max_err_pm: int = 0, forward_only: bool = False, **plan_params):
+def trim_reads(ctx: "Context", reads, adapters, max_err_pm: int = 0, forward_only: bool = False, on_device: bool = False, **plan_params):
     """Raw reads to a trimmed store in one call: set_reads(reads), find_adapters, trim_plan, io.cut_reads, set_reads(the cut reads).  reads: an
     io.Reads; adapters, max_err_pm, forward_only as find_adapters; plan_params as trim_plan.  Returns (the cut io.Reads — what the store now
-    holds —, TrimStats)."""
+    holds —, TrimStats).
+    on_device: the last two steps are Context.cut_store — the store is cut where it lies and no base is copied on the host.  The io.Reads that
+    comes back then has the cut reads' ids, descriptions and offsets (io.cut_names) and seq = qual = None: the bases are in the store."""
     from . import io
     ctx.set_reads(reads.seq, reads.qual, reads.off)
     hits, hits_off = ctx.find_adapters(adapters, max_err_pm=max_err_pm, forward_only=forward_only)
     pieces, _, stats = trim_plan(np.diff(np.asarray(reads.off, np.uint64)).astype(np.uint32), [len(a) for a in adapters], hits, hits_off, **plan_params)
+    if on_device:
+        ids, descs, off = io.cut_names(reads.ids, reads.descriptions, reads.off, pieces)
+        ctx.cut_store(pieces)
+        return io.Reads(ids, descs, None, None, off), stats
     cut = io.cut_reads(reads, pieces)
     ctx.set_reads(cut.seq, cut.qual, cut.off)
     return cut, stats

@@ -171,3 +171,4 @@ struct herro_ctx {
 };
 
 HostPool& host_pool(herro_ctx* ctx);   // herro_api.hip: the context's pool, created on first use
+std::shared_ptr<void> make_store_owner(int dev, void* const ptrs[6]);   // herro_api.hip: what a context's store_owner holds (herro_set_reads, herro_store_cut)

@@ -19,8 +19,9 @@
 //                           header written here is the one numpy itself writes for these arrays: magic, version 1.0, the dict
 //                           {'descr': ..., 'fortran_order': False, 'shape': (...), } padded with spaces to a multiple of 64
 //                           bytes, '\n' last.
-//   herro_reads_create, herro_trim_plan, herro_reads_cut   the host side of the adapter step: a reads handle over the caller's
-//                           arrays, the pieces that stay of every read (trim_plan.h) and the reads cut to them.
+//   herro_reads_create, herro_trim_plan, herro_reads_cut, herro_reads_cut_names   the host side of the adapter step: a reads
+//                           handle over the caller's arrays, the pieces that stay of every read (trim_plan.h), the reads cut to them, and
+//                           the cut reads' names alone (for a store cut on the device: herro_store_cut).
 //
 // zlib is used through the system's libz.so.1 (stable C ABI), loaded on first use: the library keeps no link-time dependency
 // beyond the HIP runtime and libstdc++.
@@ -563,42 +564,73 @@ herro_reads* herro_reads_create(uint32_t n, const uint8_t* seq, const uint8_t* q
   return nullptr;
 }
 
+}  // extern "C"
+// The cut without its bases, shared by herro_reads_cut and herro_reads_cut_names (`who`): the table's checks, then ids (THE naming rule: a read
+// with one piece in the table keeps its id, one with n > 1 gives <id>_1 .. <id>_n in the table's order), descriptions and offsets of the pieces.
+// id / desc / len: those of source read i.  NULL and a message in err on a bad table.
+template <class Id, class Desc, class Len>
+static std::unique_ptr<herro_reads> cut_names(const char* who, uint32_t n, Id&& id, Desc&& desc, Len&& len, uint64_t n_pieces, const herro_piece* pieces,
+                                              char* err, uint64_t err_cap) {
+  if (n_pieces > 0xffffffffull) { set_err(err, err_cap, std::string(who) + ": more than 2^32 - 1 pieces"); return nullptr; }
+  std::vector<uint32_t> per_read(n, 0);                 // pieces of every read in the table: one keeps the id, more are numbered
+  for (uint64_t x = 0; x < n_pieces; x++) {
+    const herro_piece& p = pieces[x];
+    const char* bad = p.rid >= n ? "rid outside the reads" : p.start > p.end ? "start > end" : p.end > len(p.rid) ? "end beyond the read" : nullptr;
+    if (bad) { set_err(err, err_cap, std::string(who) + ": piece " + std::to_string(x) + ": " + bad); return nullptr; }
+    per_read[p.rid]++;
+  }
+  std::unique_ptr<herro_reads> r(new herro_reads());
+  r->off.push_back(0);
+  std::vector<uint32_t> seen(n, 0);
+  for (uint64_t x = 0; x < n_pieces; x++) {
+    const herro_piece& p = pieces[x];
+    r->off.push_back(r->off.back() + (p.end - p.start));
+    r->ids.push_back(per_read[p.rid] > 1 ? std::string(id(p.rid)) + "_" + std::to_string(++seen[p.rid]) : std::string(id(p.rid)));
+    const char* const d = desc(p.rid);
+    r->has_desc.push_back(d != nullptr);
+    r->descs.push_back(d ? d : "");
+  }
+  reads_finish(r.get());
+  return r;
+}
+extern "C" {
+
 herro_reads* herro_reads_cut(const herro_reads* src, uint64_t n_pieces, const herro_piece* pieces, char* err, uint64_t err_cap) {
   try {
     if (!src || (n_pieces && !pieces)) { set_err(err, err_cap, "herro_reads_cut: null argument"); return nullptr; }
-    if (n_pieces > 0xffffffffull) { set_err(err, err_cap, "herro_reads_cut: more than 2^32 - 1 pieces"); return nullptr; }
-    const uint32_t n = (uint32_t)src->ids.size();
-    std::vector<uint32_t> per_read(n, 0);                 // pieces of every read in the table: one keeps the id, more are numbered
-    uint64_t bases = 0;
-    for (uint64_t x = 0; x < n_pieces; x++) {
-      const herro_piece& p = pieces[x];
-      const char* bad = p.rid >= n ? "rid outside the reads" : p.start > p.end ? "start > end" :
-                        p.end > src->off[p.rid + 1] - src->off[p.rid] ? "end beyond the read" : nullptr;
-      if (bad) { set_err(err, err_cap, "herro_reads_cut: piece " + std::to_string(x) + ": " + bad); return nullptr; }
-      per_read[p.rid]++;
-      bases += p.end - p.start;
-    }
+    std::unique_ptr<herro_reads> r = cut_names("herro_reads_cut", (uint32_t)src->ids.size(), [&](uint32_t i) { return src->ids[i].c_str(); },
+                                               [&](uint32_t i) { return src->has_desc[i] ? src->descs[i].c_str() : nullptr; },
+                                               [&](uint32_t i) { return src->off[i + 1] - src->off[i]; }, n_pieces, pieces, err, err_cap);
+    if (!r) return nullptr;
     const uint8_t* const seq = herro_reads_seq(src);
     const uint8_t* const qual = herro_reads_qual(src);
-    std::unique_ptr<herro_reads> r(new herro_reads());
-    r->seq.reserve(bases);
-    r->qual.reserve(bases);
-    r->off.push_back(0);
-    std::vector<uint32_t> seen(n, 0);
+    r->seq.reserve(r->off.back());
+    r->qual.reserve(r->off.back());
     for (uint64_t x = 0; x < n_pieces; x++) {
       const herro_piece& p = pieces[x];
       const uint64_t at = src->off[p.rid];
       r->seq.insert(r->seq.end(), seq + at + p.start, seq + at + p.end);
       r->qual.insert(r->qual.end(), qual + at + p.start, qual + at + p.end);
-      r->off.push_back(r->seq.size());
-      r->ids.push_back(per_read[p.rid] > 1 ? src->ids[p.rid] + "_" + std::to_string(++seen[p.rid]) : src->ids[p.rid]);
-      r->has_desc.push_back(src->has_desc[p.rid]);
-      r->descs.push_back(src->descs[p.rid]);
     }
-    reads_finish(r.get());
     return r.release();
   } catch (const std::exception& e) {
     set_err(err, err_cap, std::string("herro_reads_cut: ") + e.what());
+  }
+  return nullptr;
+}
+
+herro_reads* herro_reads_cut_names(uint32_t n, const uint64_t* off, const char* const* ids, const char* const* descs, uint64_t n_pieces,
+                                   const herro_piece* pieces, char* err, uint64_t err_cap) {
+  try {
+    if (!off || (n && !ids) || (n_pieces && !pieces)) { set_err(err, err_cap, "herro_reads_cut_names: null argument"); return nullptr; }
+    for (uint32_t i = 0; i < n; i++) {
+      if (off[i + 1] < off[i]) { set_err(err, err_cap, "herro_reads_cut_names: off[" + std::to_string(i + 1) + "]: off must ascend"); return nullptr; }
+      if (!ids[i]) { set_err(err, err_cap, "herro_reads_cut_names: read " + std::to_string(i) + " has no id"); return nullptr; }
+    }
+    return cut_names("herro_reads_cut_names", n, [&](uint32_t i) { return ids[i]; }, [&](uint32_t i) { return descs ? descs[i] : nullptr; },
+                     [&](uint32_t i) { return off[i + 1] - off[i]; }, n_pieces, pieces, err, err_cap).release();
+  } catch (const std::exception& e) {
+    set_err(err, err_cap, std::string("herro_reads_cut_names: ") + e.what());
   }
   return nullptr;
 }

@@ -2,7 +2,8 @@
 // herro_find_overlaps[_core], herro_extend_overlaps, herro_align_overlaps[_dev], herro_aligned_dev_*, herro_find_overlap_pairs[_core], herro_pairs_*, the PAF / .oec.zst
 // writer (herro_aligned_dev_paf, herro_pairs_paf, herro_pairs_write_alns) herro_set_seed_rescue and the test hooks herro_debug_sketch, herro_debug_occ_census and herro_debug_seed_rescue.  Host C++ (compiled by
 // hipcc) over overlap_dev.hip, align_dev.hip and paf_dev.hip; contexts, the model and jobs are herro_api.hip.  Ahead of them all, for raw reads:
-// herro_find_adapters and its handle, over adapter_dev.hip (the plan and the cut are host code: fastx.cpp).
+// herro_find_adapters and its handle, over adapter_dev.hip (the plan and the cut are host code: fastx.cpp), and herro_store_cut with its test hook
+// herro_debug_store_copy, over store_dev.hip: the store cut to the plan's pieces on the device.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,6 +18,7 @@
 #include "dev_bufs.h"
 #include "overlap_dev.h"
 #include "paf_dev.h"
+#include "store_dev.h"
 
 namespace {
 constexpr uint32_t SLICE = 1u << 20;   // records per turn of herro_extend_overlaps and herro_aligned_dev_mirror: their descriptors and results stay small whatever n is
@@ -1205,6 +1207,76 @@ int herro_debug_set_adapter_cap(herro_ctx* ctx, uint64_t cap) {
   if (!ctx) return HERRO_E_INVALID;
   ctx->debug_adapter_cap = cap;
   return HERRO_OK;
+}
+
+// ---- the store cut to a piece table on the device ("The cut on the device"; store_dev.hip) ---------------------------
+// The host's share: the table's checks and the new offsets (store_cut_plan), then the context's state as herro_set_reads leaves it.
+int herro_store_cut(herro_ctx* ctx, uint64_t n_pieces, const herro_piece* pieces, const uint32_t* name_class) {
+  if (!ctx) return HERRO_E_INVALID;
+  try {
+    // everything the host allocates comes first: an allocation that fails leaves the store as it was
+    std::vector<uint64_t> word_off, qual_off;
+    std::string msg;
+    if (int rc = herro::store_cut_plan(ctx->n_reads, ctx->read_len.data(), n_pieces, pieces, word_off, qual_off, msg)) { ctx->err = msg; return rc; }
+    if (int rc = device_ready(ctx, "herro_store_cut")) return rc;
+    const uint32_t n = (uint32_t)n_pieces;
+    std::vector<uint32_t> len(n), nc(n);
+    for (uint32_t x = 0; x < n; x++) { len[x] = pieces[x].end - pieces[x].start; nc[x] = name_class ? name_class[x] : x; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // what is queued reads the store that this context is about to let go
+    const char* const e = getenv("HERRO_CUT_STATS");
+    const int stats_level = e ? atoi(e) : 0;
+    herro::StoreCutStats stats;
+    const herro::StoreArrays old{ctx->d_words, ctx->d_word_off, ctx->d_qual, ctx->d_qual_off, ctx->d_p0, ctx->d_p1};
+    herro::StoreArrays S;
+    if (herro::store_cut(old, pieces, n, word_off, qual_off, ctx->stream, S, stats_level > 0 ? &stats : nullptr, stats_level, msg) != hipSuccess) {
+      ctx->err = msg;
+      return HERRO_E_NO_DEVICE;
+    }
+    void* const ptrs[6] = {(void*)S.words, (void*)S.word_off, (void*)S.qual, (void*)S.qual_off, (void*)S.p0, (void*)S.p1};
+    std::shared_ptr<void> owner;
+    try {
+      owner = make_store_owner(ctx->device, ptrs);
+    } catch (...) {
+      for (void* q : ptrs) if (q) (void)hipFree(q);
+      throw;
+    }
+    // from here on nothing can fail
+    ctx->store_owner = std::move(owner);   // lets the old store go: freed unless another context still shares it
+    ctx->d_words = S.words; ctx->d_word_off = S.word_off; ctx->d_qual = S.qual; ctx->d_qual_off = S.qual_off; ctx->d_p0 = S.p0; ctx->d_p1 = S.p1;
+    ctx->n_reads = n;
+    ctx->read_len.swap(len);
+    ctx->name_class.swap(nc);
+    ctx->n_words = word_off[n];
+    ctx->qual_bytes = qual_off[n];
+    ctx->read_bytes = ctx->n_words * 8 + ctx->qual_bytes;
+    ctx->h_word_off.swap(word_off);
+    ctx->h_qual_off.swap(qual_off);
+    ctx->reads_gen++;   // jobs built on the previous store refuse to run from here on
+    if (stats_level > 0)
+      fprintf(stderr, "CUT pieces=%u words=%llu qual_bytes=%llu words_ms=%.4f qual_ms=%.4f copy_words_ms=%.4f copy_qual_ms=%.4f\n", n, (unsigned long long)ctx->n_words,
+              (unsigned long long)ctx->qual_bytes, stats.words_ms, stats.qual_ms, stats.copy_words_ms, stats.copy_qual_ms);
+    return HERRO_OK;
+  } catch (const std::exception& e) {   // host memory: nothing of the context was touched
+    ctx->err = std::string("herro_store_cut: ") + e.what();
+    return HERRO_E_UNSUPPORTED;
+  }
+}
+
+// Test hook: one array of the context's store as it lies on the device.
+int64_t herro_debug_store_copy(herro_ctx* ctx, int which, void* out, uint64_t cap) {
+  if (!ctx) return HERRO_E_INVALID;
+  if (which < 0 || which > 5) { ctx->err = "herro_debug_store_copy: which is 0 .. 5"; return HERRO_E_INVALID; }
+  if (int rc = device_ready(ctx, "herro_debug_store_copy")) return rc;
+  const void* const src[6] = {ctx->d_words, ctx->d_word_off, ctx->d_qual, ctx->d_qual_off, ctx->d_p0, ctx->d_p1};
+  const uint64_t bytes[6] = {8 * (ctx->n_words + 1), 8 * ((uint64_t)ctx->n_reads + 1), ctx->qual_bytes, 8 * ((uint64_t)ctx->n_reads + 1),
+                             4 * (ctx->n_words + 2), 4 * (ctx->n_words + 2)};
+  if (!out) return (int64_t)bytes[which];
+  if (cap < bytes[which]) { ctx->err = "herro_debug_store_copy: the buffer is smaller than the array"; return HERRO_E_INVALID; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (bytes[which]) HIP_TRY(ctx, hipMemcpy(out, src[which], bytes[which], hipMemcpyDeviceToHost));
+  return (int64_t)bytes[which];
 }
 
 }  // extern "C"

@@ -453,6 +453,22 @@ int herro_decode_2bit(const uint64_t* words, uint64_t length, uint64_t start, ui
 }
 
 // ---- read store ----------------------------------------------------------------------------------
+}  // extern "C"
+// The owner of a store's six device arrays (api_ctx.h): freed on their device when the last context holding the owner lets go.
+std::shared_ptr<void> make_store_owner(int dev, void* const ptrs[6]) {
+  struct Owned { int dev; void* p[6]; };
+  return std::shared_ptr<void>(new Owned{dev, {ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], ptrs[5]}}, [](void* v) {
+    Owned* o = (Owned*)v;
+    int cur = 0;
+    const bool have = hipGetDevice(&cur) == hipSuccess;
+    (void)hipSetDevice(o->dev);
+    for (void* q : o->p) if (q) (void)hipFree(q);
+    if (have) (void)hipSetDevice(cur);
+    delete o;
+  });
+}
+extern "C" {
+
 static int upload_reads(herro_ctx* ctx, uint32_t n_reads, const std::vector<uint64_t>& words,
                         const std::vector<uint64_t>& word_off, const uint8_t* qual,
                         const std::vector<uint64_t>& qual_off, const uint32_t* name_class) {
@@ -514,18 +530,8 @@ static int upload_reads(herro_ctx* ctx, uint32_t n_reads, const std::vector<uint
   ctx->read_bytes = words.size() * 8 + nq;
   ctx->reads_gen++;   // jobs built on the previous store hold descriptors into freed memory: they refuse to run from here on
   {
-    const int dev = ctx->device;
-    void* ptrs[6] = {(void*)ctx->d_words, (void*)ctx->d_word_off, (void*)ctx->d_qual, (void*)ctx->d_qual_off, (void*)ctx->d_p0, (void*)ctx->d_p1};
-    struct Owned { int dev; void* p[6]; };
-    ctx->store_owner = std::shared_ptr<void>(new Owned{dev, {ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], ptrs[5]}}, [](void* v) {
-      Owned* o = (Owned*)v;
-      int cur = 0;
-      const bool have = hipGetDevice(&cur) == hipSuccess;
-      (void)hipSetDevice(o->dev);
-      for (void* q : o->p) if (q) (void)hipFree(q);
-      if (have) (void)hipSetDevice(cur);
-      delete o;
-    });
+    void* const ptrs[6] = {(void*)ctx->d_words, (void*)ctx->d_word_off, (void*)ctx->d_qual, (void*)ctx->d_qual_off, (void*)ctx->d_p0, (void*)ctx->d_p1};
+    ctx->store_owner = make_store_owner(ctx->device, ptrs);
     partial.armed = false;
   }
   return HERRO_OK;

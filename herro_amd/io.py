@@ -116,6 +116,33 @@ def cut_reads(reads: Reads, pieces) -> Reads:
         L.herro_reads_free(src)
 
 
+def cut_names(ids, descriptions, off, pieces):
+    """ids, descriptions and offsets of the reads that a piece table makes (herro_reads_cut_names: the library's naming rule, as cut_reads
+    applies it), from the source reads' ids, descriptions and offsets alone — for a store cut on the device (Context.cut_store), whose bases
+    never come to the host.  Returns (ids, descriptions, off u64 [n_pieces + 1]); ValueError with the library's message on a bad table."""
+    L = _lib()
+    n = len(ids)
+    off = np.ascontiguousarray(off, np.uint64)
+    if len(off) != n + 1 or len(descriptions) != n:
+        raise ValueError("herro_reads_cut_names: off has n + 1 entries, descriptions n")
+    pieces = np.ascontiguousarray(pieces, api.PIECE_DTYPE)
+    idp = (C.c_char_p * max(n, 1))(*[bytes(i) for i in ids])
+    dp = (C.c_char_p * max(n, 1))(*[None if d is None else bytes(d) for d in descriptions])
+    err = C.create_string_buffer(256)
+    h = L.herro_reads_cut_names(n, off.ctypes.data, idp, dp, len(pieces), pieces.ctypes.data, err, 256)
+    if not h:
+        raise ValueError(err.value.decode())
+    try:
+        m = L.herro_reads_count(h)
+        out_off = np.empty(m + 1, np.uint64)
+        C.memmove(out_off.ctypes.data, L.herro_reads_off(h), out_off.nbytes)
+        ip = C.cast(L.herro_reads_ids(h), C.POINTER(C.c_char_p))
+        dq = C.cast(L.herro_reads_descs(h), C.POINTER(C.c_char_p))
+        return [ip[i] for i in range(m)], [dq[i] for i in range(m)], out_off
+    finally:
+        L.herro_reads_free(h)
+
+
 def write_window_features(out_dir: str, wid: int, ids: list[str], bases: np.ndarray, quals: np.ndarray,
                           sup_pos: np.ndarray, sup_ins: np.ndarray) -> None:
     """bases: ASCII u8 [L',31]; quals u8 [L',31]; supported positions in order (features.rs:724-764)."""

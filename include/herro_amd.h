@@ -702,7 +702,8 @@ herro_reads* herro_reads_create(uint32_t n, const uint8_t* seq, const uint8_t* q
 /* ---- adapters: found in the resident reads on the device, trimmed and split on the host ---------------------------
  * The step the reference leaves to scripts/preprocess.sh (porechop, duplex_tools split_on_adapter, seqkit seq -m): adapters at the read ends
  * are trimmed, a chimera is split at an adapter in its middle, short pieces are dropped.  The path is herro_fastx_read, herro_set_reads,
- * herro_find_adapters, herro_trim_plan, herro_reads_cut, herro_set_reads with the cut reads, then the finder as before.  The specification is
+ * herro_find_adapters, herro_trim_plan, herro_reads_cut, herro_set_reads with the cut reads (or herro_store_cut, below, in place of the last
+ * two: the store cut on the device), then the finder as before.  The specification is
  * the library's own (tests/adapter_ref.py), all integer; it does not reproduce porechop's or duplex_tools' choices, and no adapter list is
  * built in: the caller supplies the sequences.
  *
@@ -764,6 +765,45 @@ void herro_trim_free(herro_trim* t);
  * order; the description is kept.  The result goes into herro_set_reads unchanged.  NULL and a message in err: a null argument, a rid outside
  * r, start > end, end beyond the read. */
 herro_reads* herro_reads_cut(const herro_reads* r, uint64_t n_pieces, const herro_piece* pieces, char* err, uint64_t err_cap);
+/* herro_reads_cut_names: the handle herro_reads_cut returns WITHOUT its bases, from the ids alone — ids and descriptions by the naming rule
+ * above (the one implementation of it; both calls run it), herro_reads_off = the running sum of the piece lengths, herro_reads_seq / _qual
+ * not to be read.  The caller of herro_store_cut names its pieces with it.  Read i has off[i + 1] - off[i] bases (off need not start at 0),
+ * id ids[i], description descs[i] (descs NULL or an entry NULL: none).  NULL and a message in err as herro_reads_cut. */
+herro_reads* herro_reads_cut_names(uint32_t n, const uint64_t* off /* [n + 1] */, const char* const* ids, const char* const* descs, uint64_t n_pieces,
+                                   const herro_piece* pieces, char* err, uint64_t err_cap);
+
+/* ---- the cut on the device: herro_store_cut replaces the context's read store by pieces of it (csrc/store_dev.hip) ---
+ * Read x of the new store is bases [start, end) of read pieces[x].rid of the current store, in the table's order; any order, repeats and empty
+ * pieces (start == end) are allowed, as in herro_reads_cut.  It stands for herro_reads_cut + herro_set_reads of the cut reads: the host
+ * computes the new offset tables from the piece lengths and uploads them with the piece table, a few bytes per piece; no base and no quality
+ * byte crosses PCIe in either direction (k_store_cut_words, k_store_cut_qual).
+ * Specification (tests/cut_ref.py states it in numpy):
+ *   Codes.  Code i of new read x is code start + i of the old read AS THE STORE HOLDS IT — including what a byte that is not ACGT smeared over
+ *   its neighbours when the old store was encoded (herro_encode_2bit): a piece inherits the codes the adapters were found in.
+ *   Words.  A new read starts at a word boundary, 32 codes per 64-bit word, LSB first; the bits above a read's last base in its last word are
+ *   zero; one zero pad word follows the last read.
+ *   Planes.  p0 / p1 are the even / odd bits of every new word, compacted as herro_set_reads compacts them, with its two zero pad entries.
+ *   Qualities and offsets.  The qualities are the byte slice; word_off / qual_off are the running sums of ceil(len / 32) and len.
+ *   Against the host path.  For reads whose bytes are all ACGT / acgt the new store equals, byte for byte in all six arrays, the one that
+ *   herro_reads_cut + herro_set_reads builds.  For other reads it may differ: the host path re-encodes the ASCII slice, so a non-ACGT byte
+ *   smears from the NEW word boundaries (and herro_encode_2bit can leave smear bits above a read's end), while the device path moves the old
+ *   codes and zeroes the tail.  herro_set_reads_packed of the sliced codes is the exact equivalent in every case.
+ * Afterwards the context is in the state herro_set_reads leaves it in: the reads are the pieces, name_class as given (NULL: x), jobs created on
+ * the old store refuse with HERRO_E_STATE, and the store has a fresh owner — contexts that share the OLD store (herro_share_reads) keep it
+ * until they call herro_share_reads again, and it is freed when its last holder lets go.  The new store is built beside the old one: peak
+ * device memory is the old store plus the new one.
+ * Checks, all before anything is touched (the store is unchanged on any error): HERRO_E_INVALID for a null table with n_pieces > 0, rid >=
+ * n_reads, start > end, end beyond the read — the message names the first offending piece —, HERRO_E_UNSUPPORTED for more than 2^31 - 1
+ * pieces; then HERRO_E_NO_DEVICE on a context without a device, then HERRO_E_STATE without reads.  A HIP call that fails while the new store
+ * is built — device memory that runs out included, as everywhere in this library — is HERRO_E_NO_DEVICE with the call's name in the message,
+ * and host memory that runs out is HERRO_E_UNSUPPORTED; what was allocated is freed and the store is unchanged in both cases.  Runs on the
+ * context's execution stream and returns when it is done.  HERRO_CUT_STATS=1 prints `CUT pieces= words= qual_bytes= words_ms= qual_ms= copy_words_ms= copy_qual_ms=` on stderr
+ * (the kernels between events; 2: also a device-to-device hipMemcpyAsync of the new word array and of the new quality array, the yardstick). */
+int herro_store_cut(herro_ctx* ctx, uint64_t n_pieces, const herro_piece* pieces, const uint32_t* name_class /* [n_pieces] or NULL */);
+/* Test hook: one array of the current store copied to the host.  which: 0 words (u64 [n_words + 1], the pad word included), 1 word_off (u64
+ * [n_reads + 1]), 2 qualities (qual_bytes bytes, not the pad), 3 qual_off (u64 [n_reads + 1]), 4 p0, 5 p1 (u32 [n_words + 2]).  Returns the
+ * array's size in bytes (out NULL: nothing is copied), or a negative error: cap smaller than the array, no device, no reads. */
+int64_t herro_debug_store_copy(herro_ctx* ctx, int which, void* out, uint64_t cap);
 
 /* One window of `herro features` (output_features, features.rs:724-764): <dir>/<wid>.ids.txt (one id per line),
  * <wid>.features.npy = u8 [2, length, 31] (ASCII bases [length][31], then qualities), <wid>.supported.npy = records
