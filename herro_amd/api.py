@@ -53,6 +53,8 @@ EXPORTS = [
     "herro_trim_plan", "herro_trim_n_pieces", "herro_trim_pieces", "herro_trim_piece_off", "herro_trim_stats", "herro_trim_free",
     "herro_reads_create", "herro_reads_cut", "herro_reads_cut_names",
     "herro_store_cut", "herro_debug_store_copy",
+    "herro_cluster_graph", "herro_pairs_cluster", "herro_clusters_n_parts", "herro_clusters_n_reads", "herro_clusters_part", "herro_clusters_rank",
+    "herro_clusters_comp", "herro_clusters_level", "herro_clusters_stats", "herro_clusters_part_stats", "herro_clusters_mask", "herro_clusters_free",
 ]
 
 
@@ -113,6 +115,10 @@ class SeedRescueParams(C.Structure):  # herro_seed_rescue_params (occ_dist 0 = o
 
 class ExtendParams(C.Structure):  # herro_extend_params (0 = the field's default)
     _fields_ = [("zdrop", C.c_uint32), ("max_ext", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class ClusterParams(C.Structure):  # herro_cluster_params
+    _fields_ = [("n_parts", C.c_uint32), ("min_span", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
 ADAPTERS_FORWARD_ONLY = 1    # HERRO_ADAPTERS_FORWARD_ONLY
@@ -361,6 +367,24 @@ def lib():
             L.herro_store_cut.argtypes = [vp, u64, vp, vp]
             L.herro_debug_store_copy.restype = C.c_int64
             L.herro_debug_store_copy.argtypes = [vp, C.c_int, vp, u64]
+        except AttributeError:
+            if not os.environ.get("HERRO_LIB"):
+                raise
+        try:   # (an older build selected by HERRO_LIB lacks the clusters: everything else still runs)
+            L.herro_cluster_graph.argtypes = [vp, u64, vp, u64, vp, vp, vp, vp, vp]
+            L.herro_pairs_cluster.argtypes = [vp, vp, vp, vp, vp]
+            L.herro_clusters_n_parts.restype = u32
+            L.herro_clusters_n_parts.argtypes = [vp]
+            L.herro_clusters_n_reads.restype = u64
+            L.herro_clusters_n_reads.argtypes = [vp]
+            for f in (L.herro_clusters_part, L.herro_clusters_rank, L.herro_clusters_comp, L.herro_clusters_level):
+                f.restype = vp
+                f.argtypes = [vp]
+            L.herro_clusters_stats.argtypes = [vp, vp]
+            L.herro_clusters_part_stats.argtypes = [vp, u32, vp]
+            L.herro_clusters_mask.argtypes = [vp, u32, vp]
+            L.herro_clusters_free.restype = None
+            L.herro_clusters_free.argtypes = [vp]
         except AttributeError:
             if not os.environ.get("HERRO_LIB"):
                 raise
@@ -1010,6 +1034,23 @@ class Context:
                                                  rec_of_row.ctypes.data if n else None, C.byref(h)))
         return OverlapPairs(self, h)
 
+    def cluster_graph(self, n_reads: int, a, b, n_parts: int, weights=None, span=None, min_span: int = 0) -> "Clusters":
+        """herro_cluster_graph: the reads partitioned by an overlap graph given as arrays (also refused properly on a HostContext) — a, b u32 [E]
+        the edges, span u32 [E] or None (every edge is strong), weights u32 [n_reads] or None (all 1), n_parts parts, edges with span < min_span
+        weak.  The specification is include/herro_amd.h's, "clusters" (tests/cluster_ref.py)."""
+        a, b = np.ascontiguousarray(a, np.uint32).reshape(-1), np.ascontiguousarray(b, np.uint32).reshape(-1)
+        sp = None if span is None else np.ascontiguousarray(span, np.uint32).reshape(-1)
+        w = None if weights is None else np.ascontiguousarray(weights, np.uint32).reshape(-1)
+        if len(b) != len(a) or (sp is not None and len(sp) != len(a)) or (w is not None and len(w) != int(n_reads)):
+            raise ValueError("a, b and span have one entry per edge, weights one per read")
+        if not 0 <= int(n_parts) <= 0xFFFFFFFF or not 0 <= int(min_span) <= 0xFFFFFFFF:
+            raise HerroError(-1, "cluster parameters: n_parts and min_span are unsigned 32-bit values")
+        P = ClusterParams(n_parts=int(n_parts), min_span=int(min_span))
+        h = C.c_void_p()
+        self._chk(self._l.herro_cluster_graph(self.h, int(n_reads), None if w is None else w.ctypes.data, len(a), a.ctypes.data if len(a) else None,
+                                              b.ctypes.data if len(a) else None, None if sp is None else sp.ctypes.data, C.byref(P), C.byref(h)))
+        return Clusters(self, h)
+
     def create_job_paired(self, pairs: "OverlapPairs", m: "AlignedDev", window_size: int) -> "Job":
         """herro_job_create_paired: create_job_aligned(*paired_job_args(pairs.rids, pairs.aln_off, pairs.rec_of_row, m.ok), m, window_size)
         inside the library; m: pairs.align() or any handle of 2 P records, primaries then mirrors."""
@@ -1349,9 +1390,69 @@ class OverlapPairs:
                                                      C.byref(lines), C.byref(size)))
         return int(lines.value), int(size.value)
 
+    def cluster(self, n_parts: int, weights=None, min_span: int = 0) -> "Clusters":
+        """herro_pairs_cluster: the reads of the store partitioned by this handle's primaries — edge (tid, qid) with span min(tend - tstart,
+        qend - qstart) as the handle holds them; weights u32 [n_reads] (windows per read, say) or None.  The result does not need this handle."""
+        w = None if weights is None else np.ascontiguousarray(weights, np.uint32).reshape(-1)
+        if w is not None and len(w) != self.ctx.n_reads:
+            raise ValueError("weights has one entry per read of the store")
+        if not 0 <= int(n_parts) <= 0xFFFFFFFF or not 0 <= int(min_span) <= 0xFFFFFFFF:
+            raise HerroError(-1, "cluster parameters: n_parts and min_span are unsigned 32-bit values")
+        P = ClusterParams(n_parts=int(n_parts), min_span=int(min_span))
+        h = C.c_void_p()
+        self.ctx._chk(self._l.herro_pairs_cluster(self.ctx.h, self.h, None if w is None else w.ctypes.data, C.byref(P), C.byref(h)))
+        return Clusters(self.ctx, h)
+
     def close(self):
         if getattr(self, "h", None):
             self._l.herro_pairs_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+CLUSTER_STATS = ("n_components", "n_levels", "strong_edges", "edge_cut")
+CLUSTER_PART_STATS = ("n_core", "weight", "n_neighbours", "pairs_inside", "pairs_touching")
+
+
+class Clusters:
+    """herro_clusters: the reads partitioned by their overlap graph (Context.cluster_graph, OverlapPairs.cluster) — what the reference's
+    workflow gets from scripts/create_clusters.py.  n_parts, n_reads; part, rank, comp, level u32 [n_reads]; stats: dict of CLUSTER_STATS;
+    part_stats u64 [n_parts, 5] in the order of CLUSTER_PART_STATS.  mask(p): u8 [n_reads], 1 core, 2 neighbour, 0 neither, made on the device
+    from the graph the handle keeps there; as a `core` argument of find_overlap_pairs pass mask(p) == 1."""
+
+    def __init__(self, ctx: Context, h):
+        self.ctx, self.h, self._l = ctx, h, ctx._l
+        L = self._l
+        k = self.n_parts = int(L.herro_clusters_n_parts(h))
+        n = self.n_reads = int(L.herro_clusters_n_reads(h))
+
+        def arr(ptr):
+            out = np.zeros(n, np.uint32)
+            if n:
+                C.memmove(out.ctypes.data, ptr, out.nbytes)
+            return out
+        self.part, self.rank = arr(L.herro_clusters_part(h)), arr(L.herro_clusters_rank(h))
+        self.comp, self.level = arr(L.herro_clusters_comp(h)), arr(L.herro_clusters_level(h))
+        g = np.zeros(4, np.uint64)
+        ctx._chk(L.herro_clusters_stats(h, g.ctypes.data))
+        self.stats = {name: int(v) for name, v in zip(CLUSTER_STATS, g)}
+        self.part_stats = np.zeros((k, 5), np.uint64)
+        for p in range(k):
+            ctx._chk(L.herro_clusters_part_stats(h, p, self.part_stats[p].ctypes.data))
+
+    def mask(self, p: int) -> np.ndarray:
+        out = np.zeros(max(self.n_reads, 1), np.uint8)
+        self.ctx._chk(self._l.herro_clusters_mask(self.h, int(p), out.ctypes.data))
+        return out[:self.n_reads]
+
+    def core_masks(self) -> list[np.ndarray]:
+        """one core mask per part in the shape shard.core_masks returns (u8 [n_reads], 1 = the read is the part's target): from `part`, no device call"""
+        return [(self.part == p).astype(np.uint8) for p in range(self.n_parts)]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._l.herro_clusters_free(self.h)
             self.h = None
 
     __del__ = close

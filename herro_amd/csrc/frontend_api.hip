@@ -3,7 +3,8 @@
 // writer (herro_aligned_dev_paf, herro_pairs_paf, herro_pairs_write_alns) herro_set_seed_rescue and the test hooks herro_debug_sketch, herro_debug_occ_census and herro_debug_seed_rescue.  Host C++ (compiled by
 // hipcc) over overlap_dev.hip, align_dev.hip and paf_dev.hip; contexts, the model and jobs are herro_api.hip.  Ahead of them all, for raw reads:
 // herro_find_adapters and its handle, over adapter_dev.hip (the plan and the cut are host code: fastx.cpp), and herro_store_cut with its test hook
-// herro_debug_store_copy, over store_dev.hip: the store cut to the plan's pieces on the device.
+// herro_debug_store_copy, over store_dev.hip: the store cut to the plan's pieces on the device.  Behind the finder: herro_cluster_graph, herro_pairs_cluster and
+// herro_clusters_*, over cluster_dev.hip (the checks and the part rule are host code: cluster_plan.h): the reads partitioned by their overlap graph.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +16,8 @@
 #include "aligned_dev.h"
 #include "align_dev.h"
 #include "alns_file.h"
+#include "cluster_dev.h"
+#include "cluster_plan.h"
 #include "dev_bufs.h"
 #include "overlap_dev.h"
 #include "paf_dev.h"
@@ -1277,6 +1280,115 @@ int64_t herro_debug_store_copy(herro_ctx* ctx, int which, void* out, uint64_t ca
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (bytes[which]) HIP_TRY(ctx, hipMemcpy(out, src[which], bytes[which], hipMemcpyDeviceToHost));
   return (int64_t)bytes[which];
+}
+
+// ---- clusters: the reads partitioned by their overlap graph (cluster_dev.hip, cluster_plan.h) -----------------------------
+// The host's share: the checks (cluster_check), the edges of a pairs handle, and the handle, which keeps the graph on the device for the masks.
+struct herro_clusters {
+  herro_ctx* ctx = nullptr;
+  int device = 0;
+  herro::ClGraph G;
+  herro::ClResult R;
+};
+
+namespace {
+int cluster_run(herro_ctx* ctx, const char* who, uint64_t n_reads, const uint32_t* weights, uint64_t n_edges, const uint32_t* a, const uint32_t* b,
+                const uint32_t* span, const herro_cluster_params* params, herro_clusters** out) {
+  try {
+    std::string msg;
+    if (int rc = herro::cluster_check(who, n_reads, weights, n_edges, a, b, params, nullptr, msg)) { ctx->err = msg; return rc; }
+    if (ctx->host_only) { ctx->err = std::string(who) + ": the context has no device"; return HERRO_E_NO_DEVICE; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::unique_ptr<herro_clusters> h(new herro_clusters());
+    h->ctx = ctx;
+    h->device = ctx->device;
+    const char* const e = getenv("HERRO_CLUSTER_STATS");
+    herro::ClTimes times;
+    const bool stats = e && atoi(e) > 0;
+    if (herro::cl_build((uint32_t)n_reads, weights, (uint32_t)n_edges, a, b, span, params->n_parts, params->min_span, ctx->stream, h->G, h->R,
+                        stats ? &times : nullptr, msg) != herro::CL_OK) {
+      ctx->err = std::string(who) + ": " + msg;
+      return HERRO_E_NO_DEVICE;
+    }
+    if (stats)
+      fprintf(stderr, "CLUSTER reads=%llu edges=%llu parts=%u components=%llu levels=%llu edge_cut=%llu arcs_ms=%.4f comp_ms=%.4f bfs_ms=%.4f order_ms=%.4f stats_ms=%.4f hook_rounds=%u bfs_launches=%u host_reads=%u\n",
+              (unsigned long long)n_reads, (unsigned long long)n_edges, params->n_parts, (unsigned long long)h->R.stats[0], (unsigned long long)h->R.stats[1],
+              (unsigned long long)h->R.stats[3], times.arcs_ms, times.comp_ms, times.bfs_ms, times.order_ms, times.stats_ms, times.hook_rounds, times.bfs_launches,
+              times.host_reads);
+    *out = h.release();
+    return HERRO_OK;
+  } catch (const std::exception& e) {   // host memory (four arrays of n_reads entries): nothing was handed out
+    ctx->err = std::string(who) + ": " + e.what();
+    return HERRO_E_UNSUPPORTED;
+  }
+}
+}  // namespace
+
+int herro_cluster_graph(herro_ctx* ctx, uint64_t n_reads, const uint32_t* weights, uint64_t n_edges, const uint32_t* a, const uint32_t* b, const uint32_t* span,
+                        const herro_cluster_params* params, herro_clusters** out) {
+  if (!ctx || !out) return HERRO_E_INVALID;
+  *out = nullptr;
+  return cluster_run(ctx, "herro_cluster_graph", n_reads, weights, n_edges, a, b, span, params, out);
+}
+
+// The primaries of a handle lie on the host (herro_pairs keeps no device copy of them): their (tid, qid, span) go up as herro_cluster_graph's edges do.
+int herro_pairs_cluster(herro_ctx* ctx, const herro_pairs* pairs, const uint32_t* weights, const herro_cluster_params* params, herro_clusters** out) {
+  if (!ctx || !out) return HERRO_E_INVALID;
+  *out = nullptr;
+  const char* const who = "herro_pairs_cluster";
+  if (!pairs) { ctx->err = std::string(who) + ": pairs is NULL"; return HERRO_E_INVALID; }
+  if (pairs->ctx != ctx) { ctx->err = std::string(who) + ": the pairs handle belongs to another context"; return HERRO_E_INVALID; }
+  const size_t P = pairs->alns.size();
+  std::vector<uint32_t> a, b, span;
+  try {
+    a.resize(P); b.resize(P); span.resize(P);
+  } catch (const std::exception& e) {
+    ctx->err = std::string(who) + ": " + e.what();
+    return HERRO_E_UNSUPPORTED;
+  }
+  for (size_t p = 0; p < P; p++) {
+    const herro_alignment& r = pairs->alns[p];
+    a[p] = r.tid; b[p] = r.qid;
+    span[p] = std::min(r.tend - r.tstart, r.qend - r.qstart);
+  }
+  return cluster_run(ctx, who, ctx->n_reads, weights, P, a.data(), b.data(), span.data(), params, out);
+}
+
+uint32_t herro_clusters_n_parts(const herro_clusters* cl) { return cl ? cl->G.k : 0; }
+uint64_t herro_clusters_n_reads(const herro_clusters* cl) { return cl ? cl->R.part.size() : 0; }
+const uint32_t* herro_clusters_part(const herro_clusters* cl) { return cl ? cl->R.part.data() : nullptr; }
+const uint32_t* herro_clusters_rank(const herro_clusters* cl) { return cl ? cl->R.rank.data() : nullptr; }
+const uint32_t* herro_clusters_comp(const herro_clusters* cl) { return cl ? cl->R.comp.data() : nullptr; }
+const uint32_t* herro_clusters_level(const herro_clusters* cl) { return cl ? cl->R.level.data() : nullptr; }
+
+int herro_clusters_stats(const herro_clusters* cl, uint64_t out[4]) {
+  if (!cl || !out) return HERRO_E_INVALID;
+  for (int i = 0; i < 4; i++) out[i] = cl->R.stats[i];
+  return HERRO_OK;
+}
+
+int herro_clusters_part_stats(const herro_clusters* cl, uint32_t p, uint64_t out[5]) {
+  if (!cl || !out) return HERRO_E_INVALID;
+  if (p >= cl->G.k) { cl->ctx->err = "herro_clusters_part_stats: part " + std::to_string(p) + " of " + std::to_string(cl->G.k); return HERRO_E_INVALID; }
+  for (int i = 0; i < 5; i++) out[i] = cl->R.part_stats[(size_t)p * 5 + i];
+  return HERRO_OK;
+}
+
+int herro_clusters_mask(const herro_clusters* cl, uint32_t p, uint8_t* out) {
+  if (!cl) return HERRO_E_INVALID;
+  herro_ctx* const ctx = cl->ctx;
+  if (p >= cl->G.k) { ctx->err = "herro_clusters_mask: part " + std::to_string(p) + " of " + std::to_string(cl->G.k); return HERRO_E_INVALID; }
+  if (!out && !cl->R.part.empty()) { ctx->err = "herro_clusters_mask: out is NULL"; return HERRO_E_INVALID; }
+  HIP_TRY(ctx, hipSetDevice(cl->device));
+  std::string msg;
+  if (herro::cl_mask(cl->G, p, ctx->stream, out, msg) != herro::CL_OK) { ctx->err = "herro_clusters_mask: " + msg; return HERRO_E_NO_DEVICE; }
+  return HERRO_OK;
+}
+
+void herro_clusters_free(herro_clusters* cl) {
+  if (!cl) return;
+  if (cl->G.n && hipSetDevice(cl->device) != hipSuccess) { cl->G.d_a = cl->G.d_b = cl->G.d_part = nullptr; cl->G.d_mask = nullptr; }   // (no device to free on)
+  delete cl;
 }
 
 }  // extern "C"

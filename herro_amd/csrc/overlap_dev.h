@@ -57,6 +57,13 @@ enum { OVL_OK = 0, OVL_HIP = 1, OVL_UNSUPPORTED = 2 };
 uint32_t ovl_scan_partials(uint32_t n);
 int ovl_scan_u32(const uint32_t* in, uint32_t n, uint32_t* out, uint32_t* partial, hipStream_t st, std::string& err);
 
+// The finder's own stable LSD radix sort (k_rs_hist / k_rs_scatter over ovl_scan_u32), for the other device code of the front end (cluster_dev.hip's
+// arcs and order): n 64-bit keys with their 64-bit payloads, one 8-bit digit per entry of `shifts` in ascending significance.  The sorted arrays end
+// up in (*k0, *p0): the pointers are swapped after every pass.  scratch: ovl_sort_scratch(n) entries of u32.  Queued on st; nothing is awaited.
+uint64_t ovl_sort_scratch(uint64_t n);
+int ovl_radix_sort(uint64_t** k0, uint64_t** p0, uint64_t** k1, uint64_t** p1, uint32_t n, const std::vector<uint32_t>& shifts, uint32_t* scratch,
+                   hipStream_t st, std::string& err);
+
 // minimizers of the whole store sorted by (rid, pos): hash[i], meta[i] = rid << 32 | pos << 1 | strand (host vectors)
 int ovl_sketch(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vector<uint64_t>& hash, std::vector<uint64_t>& meta,
                std::string& err);

@@ -924,6 +924,24 @@ int sketch_dev(const OvlStore& S, const OvlParams& P, hipStream_t st, Bufs& B, S
 uint32_t ovl_scan_partials(uint32_t n) { return nblk(n, SC_TILE) + 1; }
 int ovl_scan_u32(const uint32_t* in, uint32_t n, uint32_t* out, uint32_t* partial, hipStream_t st, std::string& err) { return scan_u32(in, n, out, partial, st, err); }
 
+// SortScratch's three arrays (SortScratch::alloc's sizes) laid out in one block
+namespace {
+inline uint64_t sort_hist_entries(uint64_t n) { return 256 * (uint64_t)(nblk(n, SC_TILE) + 1); }
+}
+uint64_t ovl_sort_scratch(uint64_t n) {
+  const uint64_t h = sort_hist_entries(n), nb = nblk(n, SC_TILE) + 1;
+  return h + (h + 1) + std::max<uint64_t>(nblk(h, SC_TILE), nb) + 2;
+}
+int ovl_radix_sort(uint64_t** k0, uint64_t** p0, uint64_t** k1, uint64_t** p1, uint32_t n, const std::vector<uint32_t>& shifts, uint32_t* scratch,
+                   hipStream_t st, std::string& err) {
+  const uint64_t h = sort_hist_entries(n);
+  SortScratch S;
+  S.hist = scratch;
+  S.offs = scratch + h;
+  S.partial = scratch + h + (h + 1);
+  return radix_sort(k0, p0, k1, p1, n, shifts, S, st, err);
+}
+
 int ovl_sketch(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vector<uint64_t>& hash, std::vector<uint64_t>& meta,
                std::string& err) {
   Bufs B;

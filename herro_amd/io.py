@@ -143,6 +143,48 @@ def cut_names(ids, descriptions, off, pieces):
         L.herro_reads_free(h)
 
 
+def write_cluster(path: str, mask, names) -> None:
+    """One part of Clusters as the file scripts/create_clusters.py writes and `herro inference -c` reads (lib.rs:208-239): `0\t<name>` for every
+    core read (mask 1), then `1\t<name>` for every neighbour (mask 2), each in read order; reads with mask 0 are left out.  names[rid]: bytes or str."""
+    mask = np.asarray(mask)
+    if len(mask) != len(names):
+        raise ValueError("write_cluster: one mask byte per name")
+    if ((mask != 0) & (mask != 1) & (mask != 2)).any():
+        raise ValueError("write_cluster: a mask byte is 0, 1 (core) or 2 (neighbour)")
+    as_bytes = lambda x: x if isinstance(x, bytes) else str(x).encode()
+    with open(path, "wb") as f:
+        for kind, tag in ((1, b"0\t"), (2, b"1\t")):
+            for r in np.flatnonzero(mask == kind):
+                name = as_bytes(names[int(r)])
+                if not name or b"\t" in name or b"\n" in name:
+                    raise ValueError(f"write_cluster: read {int(r)}: a name is not empty and holds no tab or newline")
+                f.write(tag + name + b"\n")
+
+
+def read_cluster(path: str, names) -> np.ndarray:
+    """The mask (u8 [len(names)]: 1 core, 2 neighbour, 0 neither) of a cluster file.  read_cluster of lib.rs:208-239 splits every line at tabs,
+    takes `0` for core and `1` for neighbour and panics on anything else ("Invalid cluster file", lib.rs:231; a line without a tab — an empty one
+    included — dies on fields[1]): all of these are a ValueError naming the line here, and so are a name the read set does not have and a read
+    listed twice."""
+    index = {(x if isinstance(x, bytes) else str(x).encode()): i for i, x in enumerate(names)}
+    mask = np.zeros(len(names), np.uint8)
+    with open(path, "rb") as f:
+        lines = f.read().split(b"\n")
+    if lines[-1] == b"":          # (the newline that ends the last line; BufRead::lines drops it too)
+        lines.pop()
+    for no, line in enumerate(lines, 1):
+        fields = line.split(b"\t")
+        if len(fields) < 2 or fields[0] not in (b"0", b"1"):
+            raise ValueError(f"read_cluster: {path}: line {no}: invalid cluster file (expected `0<tab>name` or `1<tab>name`)")
+        r = index.get(fields[1])
+        if r is None:
+            raise ValueError(f"read_cluster: {path}: line {no}: unknown read {fields[1]!r}")
+        if mask[r]:
+            raise ValueError(f"read_cluster: {path}: line {no}: read {fields[1]!r} is listed twice")
+        mask[r] = 1 if fields[0] == b"0" else 2
+    return mask
+
+
 def write_window_features(out_dir: str, wid: int, ids: list[str], bases: np.ndarray, quals: np.ndarray,
                           sup_pos: np.ndarray, sup_ins: np.ndarray) -> None:
     """bases: ASCII u8 [L',31]; quals u8 [L',31]; supported positions in order (features.rs:724-764)."""

@@ -696,6 +696,23 @@ def core_masks(read_lens, window_size: int, world: int) -> list[np.ndarray]:
     return out
 
 
+def cluster_masks(ctx, read_lens, window_size: int, world: int, min_span: int = 0, **finder_params):
+    """core_masks from the overlap graph instead of the window counts alone: find_overlap_pairs(extend=False) over all reads — the finder costs
+    a few percent of the aligner — then OverlapPairs.cluster into `world` parts with the reads' window counts as weights (the
+    balance core_masks aims at) and chains shorter than min_span weak.  Reads that overlap land in one part where the graph allows, so far fewer
+    pairs are aligned on two ranks.  Deterministic: every rank computes the same masks from the same store.  Returns (the core
+    masks in the shape core_masks returns, the api.Clusters — neighbour masks and statistics; close it when done)."""
+    for name in ("extend", "core"):      # the graph is every read's chains as they are: neither is the caller's to set
+        if name in finder_params:
+            raise ValueError(f"cluster_masks: {name}= is not a finder parameter here (the graph is found with extend=False over all reads)")
+    pairs = ctx.find_overlap_pairs(extend=False, **finder_params)
+    try:
+        cl = pairs.cluster(world, weights=windows_of(read_lens, window_size).astype(np.uint32), min_span=min_span)
+    finally:
+        pairs.close()
+    return cl.core_masks(), cl
+
+
 def correct_reads_shard(ctx, mask, window_size: int, batch: int, batch_mode: int, read_name, group_targets: int = 1024, **finder_params):
     """Reads-only correction of one shard on `ctx` (reads and model loaded): find_overlap_pairs(core=mask) -> align -> jobs of at most
     `group_targets` targets cut from the table -> featurize -> infer -> consensus -> FASTA.  Rows whose record failed are dropped
@@ -725,13 +742,21 @@ def correct_reads_shard(ctx, mask, window_size: int, batch: int, batch_mode: int
 
 
 def correct_reads_sharded(ctx, read_lens, window_size: int, batch: int, batch_mode: int, read_name, group=None, group_targets: int = 1024,
-                          **finder_params):
-    """correct_reads_shard for this rank's mask of core_masks, then correct_sharded_local's gather of the records to rank 0.
-    Returns ((rids, ends, text) on rank 0 else None, this rank's core reads)."""
+                          partition: str = "windows", min_span: int = 0, **finder_params):
+    """correct_reads_shard for this rank's mask, then correct_sharded_local's gather of the records to rank 0.  partition: "windows" — core_masks,
+    the window counts alone —, or "overlaps" — cluster_masks(min_span=min_span), the overlap graph's clusters; the records are the same either way,
+    the pairs aligned on two ranks are not.  Returns ((rids, ends, text) on rank 0 else None, this rank's core reads)."""
     dist = _dist()
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
-    mask = core_masks(read_lens, window_size, world)[rank]
+    if partition == "windows":
+        mask = core_masks(read_lens, window_size, world)[rank]
+    elif partition == "overlaps":
+        masks, cl = cluster_masks(ctx, read_lens, window_size, world, min_span=min_span, **finder_params)
+        cl.close()
+        mask = masks[rank]
+    else:
+        raise ValueError('partition is "windows" or "overlaps"')
     rec = correct_reads_shard(ctx, mask, window_size, batch, batch_mode, read_name, group_targets=group_targets, **finder_params)
     n_mine = int(np.count_nonzero(mask))
     if _alone(world):

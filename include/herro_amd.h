@@ -805,6 +805,61 @@ int herro_store_cut(herro_ctx* ctx, uint64_t n_pieces, const herro_piece* pieces
  * array's size in bytes (out NULL: nothing is copied), or a negative error: cap smaller than the array, no device, no reads. */
 int64_t herro_debug_store_copy(herro_ctx* ctx, int which, void* out, uint64_t cap);
 
+/* ---- clusters: the reads partitioned by their overlap graph (csrc/cluster_dev.hip, csrc/cluster_plan.h) -------------------
+ * The reference's workflow runs scripts/create_clusters.py between the batched alignments and `herro inference -c <cluster>`: METIS cuts the
+ * overlap graph into k parts and every part becomes a file of `0\t<name>` lines for its core reads and `1\t<name>` lines for their neighbours,
+ * which read_cluster takes apart again (lib.rs:208-239; haec_io.rs:62-68 keeps the reads of either set, overlaps.rs:154-159 the overlaps whose
+ * target is core).  The entries below make those clusters on the device, as core masks (1 core, 2 neighbour, 0 neither) in the shape the
+ * `core` arguments of the finder above take.  This is NOT METIS: it is a small specification of our own, all integer and independent of any
+ * thread order (tests/cluster_ref.py states it in numpy), and its masks are exact whatever its quality — the corrected reads do not depend
+ * on the partition, only the amount of work does.
+ * Specification.  n reads with weights w (u32, NULL: all 1), E undirected edges (a, b, span) (span NULL: every edge is strong), n_parts k, min_span:
+ *   1. Strong edges: span >= min_span (min_span 0: all).  Weak edges count in steps 6 and 7 only.
+ *   2. comp[v]: the least read id reachable from v over strong edges.
+ *   3. d1[v]: the BFS distance over strong edges from comp[v]; far[c]: the read of component c with the greatest d1, the least id among equals;
+ *      level[v]: the BFS distance from far[comp[v]] — two sweeps from a pseudo-peripheral read, all components at once.
+ *   4. Order: ascending (comp, level, v); rank[v] is its position.
+ *   5. Cut: S[v] = the sum of w over the reads before v in the order, T the total; part[v] = min(k - 1, S[v] * k / T) in 64-bit integers, part 0
+ *      for all when T == 0.  Hence |weight of a part - T / k| < max w.
+ *   6. Mask of part p, over ALL edges (a rank needs every query of its targets): 1 where part[v] == p, 2 where v is not core and adjacent to a core
+ *      read of p, 0 otherwise.
+ *   7. Statistics.  Per part: n_core, weight, n_neighbours, pairs_inside (both ends in p), pairs_touching (at least one end in p: what the rank of
+ *      p aligns).  Global: n_components, n_levels (greatest level + 1), strong_edges, edge_cut (edges whose ends differ in part; duplicates count
+ *      as given).
+ * a > b, duplicate edges and k > n_reads are legal.  Checks, in this order: HERRO_E_INVALID — params NULL, n_parts outside 1 .. 65535, a reserved
+ * field not 0, an edge with a == b or a read id >= n_reads; the message names the first offending edge —, HERRO_E_UNSUPPORTED — n_reads or n_edges
+ * above 2^31 - 1, T >= 2^32 —, then HERRO_E_NO_DEVICE on a context without a device.  A HIP call that fails is HERRO_E_NO_DEVICE with its name,
+ * host memory that runs out HERRO_E_UNSUPPORTED; no handle is made in either case.
+ * The calls run on the context's execution stream and return when the results are on the host; the graph (edges, parts) stays on the device
+ * inside the handle, so that a mask costs two kernels and one download.  The handle needs its context until it is freed, nothing else: not the
+ * arrays it was made from, not the pairs handle.  HERRO_CLUSTER_STATS=1 prints `CLUSTER reads= edges= ... arcs_ms= comp_ms= bfs_ms= order_ms=
+ * stats_ms= hook_rounds= bfs_launches= host_reads=` on stderr (the stages between events). */
+typedef struct {
+  uint32_t n_parts;      /* k: 1 .. 65535 */
+  uint32_t min_span;     /* edges with span below it are weak; 0: every edge is strong */
+  uint32_t reserved[2];  /* 0 */
+} herro_cluster_params;
+typedef struct herro_clusters herro_clusters;
+/* herro_cluster_graph: the clusters of a graph given as host arrays — what create_clusters.py reads from its edge list; it needs no read store. */
+int herro_cluster_graph(herro_ctx* ctx, uint64_t n_reads, const uint32_t* weights /* [n_reads] or NULL */, uint64_t n_edges, const uint32_t* a,
+                        const uint32_t* b, const uint32_t* span /* [n_edges] or NULL */, const herro_cluster_params* params, herro_clusters** out);
+/* herro_pairs_cluster: the graph is the handle's P primaries (tid, qid), span = min(tend - tstart, qend - qstart) as the handle holds them (the
+ * chains' spans with HERRO_PAIRS_NO_EXTEND), n_reads the store's; weights [n_reads] or NULL (the Python layer passes windows per read).  The
+ * primaries go up from the handle's host copy: herro_pairs keeps none on the device.  A handle of another context is HERRO_E_INVALID. */
+int herro_pairs_cluster(herro_ctx* ctx, const herro_pairs* pairs, const uint32_t* weights, const herro_cluster_params* params, herro_clusters** out);
+uint32_t herro_clusters_n_parts(const herro_clusters* cl);
+uint64_t herro_clusters_n_reads(const herro_clusters* cl);
+const uint32_t* herro_clusters_part(const herro_clusters* cl);    /* [n_reads]; these four stay valid until the handle is freed */
+const uint32_t* herro_clusters_rank(const herro_clusters* cl);
+const uint32_t* herro_clusters_comp(const herro_clusters* cl);
+const uint32_t* herro_clusters_level(const herro_clusters* cl);
+int herro_clusters_stats(const herro_clusters* cl, uint64_t out[4]);                  /* n_components, n_levels, strong_edges, edge_cut */
+int herro_clusters_part_stats(const herro_clusters* cl, uint32_t p, uint64_t out[5]); /* n_core, weight, n_neighbours, pairs_inside, pairs_touching */
+/* The mask of part p (step 6) — the `core` and `neighbour` sets of read_cluster (lib.rs:208-239) as one byte per read: a non-zero byte marks a read
+ * the rank of p loads, a 1 a read it corrects.  Made on the device from the resident graph on every call. */
+int herro_clusters_mask(const herro_clusters* cl, uint32_t p, uint8_t* out /* [n_reads] */);
+void herro_clusters_free(herro_clusters* cl);
+
 /* One window of `herro features` (output_features, features.rs:724-764): <dir>/<wid>.ids.txt (one id per line),
  * <wid>.features.npy = u8 [2, length, 31] (ASCII bases [length][31], then qualities), <wid>.supported.npy = records
  * {pos: <u2, ins: u1}.  NPY format 1.0, C order, header as numpy writes it (dict padded with spaces to a multiple of 64
