@@ -6,6 +6,7 @@ import collections
 import contextlib
 import ctypes as C
 import os
+import weakref
 from dataclasses import dataclass
 
 import numpy as np
@@ -55,6 +56,8 @@ EXPORTS = [
     "herro_store_cut", "herro_debug_store_copy",
     "herro_cluster_graph", "herro_pairs_cluster", "herro_clusters_n_parts", "herro_clusters_n_reads", "herro_clusters_part", "herro_clusters_rank",
     "herro_clusters_comp", "herro_clusters_level", "herro_clusters_stats", "herro_clusters_part_stats", "herro_clusters_mask", "herro_clusters_free",
+    "herro_job_fasta_dev", "herro_fasta_text_data", "herro_fasta_text_len", "herro_fasta_text_target_end", "herro_fasta_text_stats", "herro_fasta_text_free",
+    "herro_debug_set_fasta_chunk", "herro_chop_plan",
 ]
 
 
@@ -129,6 +132,14 @@ PIECE_DTYPE = np.dtype([("rid", "<u4"), ("start", "<u4"), ("end", "<u4")])   # h
 
 class AdapterParams(C.Structure):  # herro_adapter_params (0 = the field's default)
     _fields_ = [("max_err_pm", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class ChopParams(C.Structure):  # herro_chop_params (0 = off)
+    _fields_ = [(n, C.c_uint32) for n in ("chop_len", "min_length", "line_width", "flags")] + [("reserved", C.c_uint32 * 4)]
+
+
+# scripts/postprocess_corrected.sh of the reference's workflow: `seqkit sliding -s 30000 -W 30000 -g`, then `seqkit seq -m 10000`
+POSTPROCESS = dict(chop_len=30000, min_length=10000)
 
 
 class TrimParams(C.Structure):  # herro_trim_params (0 = the field's default)
@@ -385,6 +396,22 @@ def lib():
             L.herro_clusters_mask.argtypes = [vp, u32, vp]
             L.herro_clusters_free.restype = None
             L.herro_clusters_free.argtypes = [vp]
+        except AttributeError:
+            if not os.environ.get("HERRO_LIB"):
+                raise
+        try:   # (an older build selected by HERRO_LIB lacks the device FASTA: everything else still runs)
+            L.herro_job_fasta_dev.argtypes = [vp, vp, vp, vp, vp]
+            L.herro_fasta_text_data.restype = vp
+            L.herro_fasta_text_data.argtypes = [vp]
+            L.herro_fasta_text_len.restype = u64
+            L.herro_fasta_text_len.argtypes = [vp]
+            L.herro_fasta_text_target_end.restype = vp
+            L.herro_fasta_text_target_end.argtypes = [vp]
+            L.herro_fasta_text_stats.argtypes = [vp, vp]
+            L.herro_fasta_text_free.restype = None
+            L.herro_fasta_text_free.argtypes = [vp]
+            L.herro_debug_set_fasta_chunk.argtypes = [vp, u64]
+            L.herro_chop_plan.argtypes = [u64, vp, vp, vp, vp, u64]
         except AttributeError:
             if not os.environ.get("HERRO_LIB"):
                 raise
@@ -990,6 +1017,10 @@ class Context:
         """Test hook (herro_debug_set_adapter_cap): the hits the first scan's buffer of every later find_adapters holds; 0: the default."""
         self._chk(self._l.herro_debug_set_adapter_cap(self.h, int(cap)))
 
+    def fasta_chunk(self, nbytes: int):
+        """Test hook (herro_debug_set_fasta_chunk): the text bytes of a chunk of every later Job.fasta_dev; 0: the default."""
+        self._chk(self._l.herro_debug_set_fasta_chunk(self.h, int(nbytes)))
+
     def find_overlap_pairs(self, extend: bool = True, zdrop: int = 0, max_ext: int = 0, core=None, **params) -> "OverlapPairs":
         """find_overlaps, pair_rows, extend_overlaps over the primaries and paired_job_args' table in one call that keeps the records on the
         device (herro_find_overlap_pairs): one record per read pair and the table of the finder's two rows per pair.  params as
@@ -1214,6 +1245,47 @@ class Job:
             self.ctx._chk(int(got))
         text = out[:got] if as_array else out[:got].tobytes()
         return (text, ends[:n]) if with_ends else text
+
+    def fasta_dev(self, read_ids, descs=None, chop_len: int = 0, min_length: int = 0, line_width: int = 0, with_ends: bool = False,
+                  as_array: bool = False, with_stats: bool = False):
+        """FASTA records of every target of the job, formed on the device (herro_job_fasta_dev): with the three numbers 0 the
+        text of fasta(), byte for byte; chop_len C > 0 cuts every record into pieces of C bases named <name>_sliding:<start>-<end> (seqkit sliding
+        -s C -W C -g), min_length drops the pieces below it (seqkit seq -m), line_width wraps the bodies — **POSTPROCESS is what
+        scripts/postprocess_corrected.sh runs before the assembler.  read_ids: one str / bytes per target, None: the target gives nothing; descs:
+        None, or one str / bytes / None per target.  with_ends: also the end offset of every target's records; with_stats: also a FastaStats;
+        as_array: the text as a u8 array over the library's buffer (no copy; the buffer is freed with the array)."""
+        n = len(read_ids)
+        if n != self.n_targets:
+            raise ValueError(f"read_ids has {n} entries, the job has {self.n_targets} targets")
+        if descs is not None and len(descs) != n:
+            raise ValueError(f"descs has {len(descs)} entries, the job has {n} targets")
+        ids = (C.c_char_p * max(n, 1))(*[_c_str(r) for r in read_ids])
+        ds = None if descs is None else (C.c_char_p * max(n, 1))(*[_c_str(d) for d in descs])
+        p = _chop_params(chop_len, min_length, line_width)
+        h = C.c_void_p()
+        L = self._l
+        self.ctx._chk(L.herro_job_fasta_dev(self.h, ids, ds, C.byref(p), C.byref(h)))
+        try:
+            nb = int(L.herro_fasta_text_len(h))
+            ends = np.zeros(n, np.uint64)
+            if n:
+                C.memmove(ends.ctypes.data, L.herro_fasta_text_target_end(h), ends.nbytes)
+            st = (C.c_uint64 * 6)()
+            L.herro_fasta_text_stats(h, st)
+            if as_array and nb:
+                buf = (C.c_uint8 * nb).from_address(L.herro_fasta_text_data(h))
+                weakref.finalize(buf, L.herro_fasta_text_free, h)   # the array's base keeps buf alive; the handle goes with it
+                h = None
+                text = np.frombuffer(buf, np.uint8)
+            elif as_array:
+                text = np.zeros(0, np.uint8)
+            else:
+                text = C.string_at(L.herro_fasta_text_data(h), nb) if nb else b""
+        finally:
+            if h is not None:
+                L.herro_fasta_text_free(h)
+        out = (text,) + ((ends,) if with_ends else ()) + ((FastaStats(*[int(x) for x in st]),) if with_stats else ())
+        return out[0] if len(out) == 1 else out
 
     def rf_left(self) -> int:
         """test hook: windows of the last infer whose receptive fields k_rfq filled BEHIND a fused gather (more informative rows than k_rows stages)"""
@@ -1642,6 +1714,49 @@ def aligned_dev_job_args(rids, aln_off, ok: np.ndarray):
     ok = np.asarray(ok, bool)
     kept = np.concatenate([[0], np.cumsum(ok)]).astype(np.int64)
     return rids, kept[aln_off].astype(np.uint64), np.flatnonzero(ok).astype(np.uint32)
+
+
+FastaStats = collections.namedtuple("FastaStats", "records bases pieces_dropped bases_dropped segments targets")
+ChopStats = collections.namedtuple("ChopStats", "pieces_kept pieces_dropped bases_kept bases_dropped")
+
+
+def _c_str(x):
+    return x if x is None or isinstance(x, bytes) else x.encode()
+
+
+def _chop_params(chop_len, min_length, line_width) -> ChopParams:
+    vals = dict(chop_len=int(chop_len), min_length=int(min_length), line_width=int(line_width))
+    for name, v in vals.items():
+        if not 0 <= v <= 0xFFFFFFFF:
+            raise ValueError(f"{name} = {v}: a 32-bit unsigned number")
+    return ChopParams(**vals)
+
+
+def chop_plan(lengths, chop_len: int = 0, min_length: int = 0, line_width: int = 0):
+    """The pieces Job.fasta_dev keeps of sequences of these lengths (herro_chop_plan; host code, no device): pieces of chop_len bases, the last
+    one of a sequence shorter, those below min_length dropped; chop_len 0: the sequence is its one piece.  Returns (pieces PIECE_DTYPE — rid is
+    the sequence — grouped by sequence, piece_off u64 [n + 1], ChopStats); ValueError with the library's message on a refusal."""
+    ln = np.ascontiguousarray(lengths, np.uint64)
+    return _chop_plan(lib(), ln, _chop_params(chop_len, min_length, line_width))
+
+
+def _chop_plan(L, ln, p):
+    h, err = C.c_void_p(), C.create_string_buffer(256)
+    rc = L.herro_chop_plan(len(ln), ln.ctypes.data if ln is not None else None, C.byref(p) if p is not None else None, C.byref(h), err, 256)
+    if rc:
+        raise ValueError(err.value.decode())
+    try:
+        n = int(L.herro_trim_n_pieces(h))
+        pieces = np.zeros(n, PIECE_DTYPE)
+        if n:
+            C.memmove(pieces.ctypes.data, L.herro_trim_pieces(h), pieces.nbytes)
+        piece_off = np.zeros(len(ln) + 1, np.uint64)
+        C.memmove(piece_off.ctypes.data, L.herro_trim_piece_off(h), piece_off.nbytes)
+        st = (C.c_uint64 * 4)()
+        L.herro_trim_stats(h, st)
+    finally:
+        L.herro_trim_free(h)
+    return pieces, piece_off, ChopStats(*[int(x) for x in st])
 
 
 TrimStats = collections.namedtuple("TrimStats", "reads_trimmed reads_split reads_dropped bases_removed")

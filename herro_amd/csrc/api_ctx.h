@@ -103,6 +103,34 @@ struct HostPool {
 
 struct Arena { void* p = nullptr; size_t cap = 0; };
 
+// Pinned host blocks that results handed to the caller live in (herro_fasta_text): recycled like the job arenas — hipHostMalloc of a text's size
+// costs more than forming the text —, and shared between the context and its handles, so that a handle freed after its context still has
+// somewhere to give its block back to; the blocks go with the last holder.
+struct PinPool {
+  std::mutex mu;
+  std::vector<Arena> free;
+  ~PinPool() { for (Arena& a : free) (void)hipHostFree(a.p); }
+  Arena acquire(size_t need) {
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      size_t best = free.size();
+      for (size_t i = 0; i < free.size(); i++)
+        if (free[i].cap >= need && (best == free.size() || free[i].cap < free[best].cap)) best = i;
+      if (best != free.size()) { Arena a = free[best]; free.erase(free.begin() + best); return a; }
+    }
+    Arena a;
+    a.cap = need + need / 8 + 4096;
+    if (hipHostMalloc(&a.p, a.cap, hipHostMallocDefault) != hipSuccess) { a.p = nullptr; a.cap = 0; }
+    return a;
+  }
+  void release(Arena& a) {
+    if (!a.p) return;
+    std::lock_guard<std::mutex> lk(mu);
+    if (free.size() < 4) free.push_back(a); else (void)hipHostFree(a.p);
+    a = Arena{};
+  }
+};
+
 struct herro_ctx {
   int device = 0;
   uint32_t n_cu = 256;   // compute units of the device: one round of the fused stack (plan_tiles)
@@ -134,6 +162,8 @@ struct herro_ctx {
   std::shared_ptr<void> store_owner;
   herro_seed_rescue_params seed_rescue{};   // herro_set_seed_rescue: occ_dist 0 = off; rescue_max_occ as given (0 = 4095 where it is used)
   uint64_t debug_adapter_cap = 0;           // herro_debug_set_adapter_cap: hits the first scan's buffer of herro_find_adapters holds (0: the default)
+  std::shared_ptr<PinPool> text_pin = std::make_shared<PinPool>();   // herro_job_fasta_dev: where its texts land
+  uint64_t debug_fasta_chunk = 0;           // herro_debug_set_fasta_chunk: text bytes of a chunk of herro_job_fasta_dev (0: a sixteenth of HERRO_FASTA_SCRATCH_MB)
   // model
   bool has_model = false;
   herro::ModelDev M{};

@@ -46,6 +46,7 @@
 
 #include "host_cpus.h"
 #include "trim_plan.h"
+#include "chop_plan.h"
 #include "../../include/herro_amd.h"
 
 struct herro_reads {
@@ -661,6 +662,23 @@ int herro_trim_stats(const herro_trim* t, uint64_t out[4]) {
   return HERRO_OK;
 }
 void herro_trim_free(herro_trim* t) { delete t; }
+
+// scripts/postprocess_corrected.sh as a table of pieces (chop_plan.h): what herro_job_fasta_dev writes of sequences of these lengths
+int herro_chop_plan(uint64_t n_seqs, const uint64_t* len, const herro_chop_params* params, herro_trim** out, char* err, uint64_t err_cap) {
+  if (!out) { set_err(err, err_cap, "herro_chop_plan: null argument"); return HERRO_E_INVALID; }
+  *out = nullptr;
+  try {
+    std::unique_ptr<herro_trim> t(new herro_trim());
+    std::string why;
+    const int rc = herro::chop_plan(n_seqs, len, params, *t, why);
+    if (rc != HERRO_OK) { set_err(err, err_cap, why); return rc; }
+    *out = t.release();
+    return HERRO_OK;
+  } catch (const std::exception& e) {
+    set_err(err, err_cap, std::string("herro_chop_plan: ") + e.what());
+  }
+  return HERRO_E_UNSUPPORTED;   // host memory ran out
+}
 
 int herro_write_window_features(const char* dir, uint32_t wid, const char* const* ids, uint32_t n_ids, const uint8_t* bases,
                                 const uint8_t* quals, uint32_t length, const uint16_t* sup_pos, const uint8_t* sup_ins,

@@ -31,6 +31,7 @@
 #include "cigar_dev.h"
 #include "align_dev.h"
 #include "overlap_dev.h"
+#include "fasta_dev.h"
 
 using namespace herro;
 
@@ -2289,6 +2290,98 @@ int64_t herro_job_fasta(herro_job* job, const char* const* ids, const char* cons
       if (ids[t]) fasta_from_device_consensus(job, t, ids[t], descs ? descs[t] : nullptr, out + end[t]);
   });
   return (int64_t)tot;
+}
+
+// ---- the corrected reads as FASTA formed on the device, chopped for the assembler (fasta_dev.hip, chop_plan.h) ----------------
+// herro_job_fasta's records (consensus.rs:90-111, lib.rs:282-317) and scripts/postprocess_corrected.sh behind them (`seqkit sliding -s 30000 -W 30000
+// -g`, `seqkit seq -m 10000`), written by kernels from the bases the consensus pass left on the device: no padded window slot crosses PCIe and the
+// host pool assembles nothing.  The text is copied chunk by chunk to its place in ONE pinned block that the handle owns until it is freed.
+// consensus_on_host is neither read nor set: herro_job_fasta of the same job still fetches and assembles as before.
+struct herro_fasta_text {
+  std::shared_ptr<PinPool> pool;   // the text lies in a pinned block of the context's pool (api_ctx.h) and goes back there
+  Arena block{};
+  uint64_t len = 0;
+  std::vector<uint64_t> target_end;
+  herro::FastaStats st;
+  ~herro_fasta_text() { if (pool) pool->release(block); }
+};
+
+int herro_job_fasta_dev(herro_job* job, const char* const* ids, const char* const* descs, const herro_chop_params* params, herro_fasta_text** out) {
+  if (!job || !out) return HERRO_E_INVALID;
+  *out = nullptr;
+  herro_ctx* ctx = job->ctx;
+  const char* const who = "herro_job_fasta_dev";
+  if (job->n_targets && !ids) { ctx->err = std::string(who) + ": ids is NULL"; return HERRO_E_INVALID; }
+  herro::ChopRule R;
+  {
+    std::string why;
+    if (const int rc = herro::chop_check(who, params, R, why)) { ctx->err = why; return rc; }
+  }
+  if (!job->consensus_done) { ctx->err = "herro_job_consensus has not run"; return HERRO_E_STATE; }
+  // window slots below 2^32 bytes: the base prefixes are 32-bit, and a piece has at least one base, so there are never more than 2^32 - 1 pieces
+  if (job->row_elems > herro::FASTA_MAX_ROW_ELEMS) { ctx->err = std::string(who) + ": a job of 2^32 corrected bases or more (more than 2^32 - 1 pieces at chop_len 1)"; return HERRO_E_UNSUPPORTED; }
+  int rc = job_sync(job);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const uint32_t nt = job->n_targets;
+  herro::FastaNames names;
+  names.off.assign(2ull * nt + 1, 0);
+  names.present.assign(nt, 0);
+  for (uint32_t t = 0; t < nt; t++) {
+    names.off[2ull * t] = names.blob.size();
+    if (ids[t]) { names.present[t] = 1; names.blob += ids[t]; }
+    names.off[2ull * t + 1] = names.blob.size();
+    if (ids[t] && descs && descs[t]) names.blob += descs[t];
+  }
+  names.off[2ull * nt] = names.blob.size();
+  // the sibling-tile check of consensus_to_host, in front of the kernels instead of behind the copy: every model pass queued so far is complete
+  // once the stream is idle, and a pass that is repeated (once) is repeated before any text is formed, so the text is the second pass's
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->timer.collect();
+  if ((rc = check_sib(ctx, job)) && (rc = sib_retry(job, rc))) return rc;
+  uint64_t chunk = ctx->debug_fasta_chunk;
+  if (!chunk) {
+    const char* e = getenv("HERRO_FASTA_SCRATCH_MB");
+    const uint64_t budget = e ? (uint64_t)std::max(1ll, atoll(e)) << 20 : 1024ull << 20;
+    chunk = std::max<uint64_t>(budget / 16, 16);   // the two device halves stay an eighth of the budget (the division of herro_pairs_paf's chunks)
+  }
+  std::unique_ptr<herro_fasta_text> h(new herro_fasta_text());
+  h->pool = ctx->text_pin;
+  // recycled memory: the device blocks go back to the context's list when the call is over (the stream is idle then), the pinned block with the handle
+  std::vector<Arena> dev_blocks;
+  herro::FastaMem mem;
+  mem.dev = [&](uint64_t bytes) -> void* { dev_blocks.push_back(small_acquire(ctx, bytes)); return dev_blocks.back().p; };
+  mem.text = [&](uint64_t bytes) -> char* { h->block = h->pool->acquire(bytes); return (char*)h->block.p; };
+  std::string msg;
+  char* text = nullptr;
+  const int frc = herro::fasta_text_dev(job->J, job->row_elems, job->tgt_win_off.data(), nt, names, R, chunk, ctx->stream, mem, &text, &h->len, h->target_end, h->st, msg);
+  for (Arena& a : dev_blocks) small_release(ctx, a);
+  if (frc != herro::FASTA_OK) {
+    ctx->err = msg;
+    return HERRO_E_NO_DEVICE;
+  }
+  const char* e = getenv("HERRO_FASTA_STATS");   // (tools/fastarate.py): one line on stderr
+  if (e && atoi(e))
+    fprintf(stderr, "FASTA targets=%llu segments=%llu pieces=%llu dropped=%llu bytes=%llu chunks=%llu seg_ms=%.3f piece_ms=%.3f write_ms=%.3f\n",
+            (unsigned long long)h->st.n_targets, (unsigned long long)h->st.segments, (unsigned long long)h->st.records, (unsigned long long)h->st.dropped,
+            (unsigned long long)h->st.bytes, (unsigned long long)h->st.chunks, h->st.seg_ms, h->st.piece_ms, h->st.write_ms);
+  *out = h.release();
+  return HERRO_OK;
+}
+
+const char* herro_fasta_text_data(const herro_fasta_text* t) { return t && t->len ? (const char*)t->block.p : nullptr; }
+uint64_t herro_fasta_text_len(const herro_fasta_text* t) { return t ? t->len : 0; }
+const uint64_t* herro_fasta_text_target_end(const herro_fasta_text* t) { return t ? t->target_end.data() : nullptr; }
+int herro_fasta_text_stats(const herro_fasta_text* t, uint64_t out[6]) {
+  if (!t || !out) return HERRO_E_INVALID;
+  out[0] = t->st.records; out[1] = t->st.bases; out[2] = t->st.dropped; out[3] = t->st.bases_dropped; out[4] = t->st.segments; out[5] = t->st.targets;
+  return HERRO_OK;
+}
+void herro_fasta_text_free(herro_fasta_text* t) { delete t; }
+int herro_debug_set_fasta_chunk(herro_ctx* ctx, uint64_t bytes) {
+  if (!ctx) return HERRO_E_INVALID;
+  ctx->debug_fasta_chunk = bytes;
+  return HERRO_OK;
 }
 
 int64_t herro_job_write_features(herro_job* job, const char* base_dir, const char* const* read_names) {

@@ -713,10 +713,12 @@ def cluster_masks(ctx, read_lens, window_size: int, world: int, min_span: int = 
     return cl.core_masks(), cl
 
 
-def correct_reads_shard(ctx, mask, window_size: int, batch: int, batch_mode: int, read_name, group_targets: int = 1024, **finder_params):
+def correct_reads_shard(ctx, mask, window_size: int, batch: int, batch_mode: int, read_name, group_targets: int = 1024, postprocess=None, **finder_params):
     """Reads-only correction of one shard on `ctx` (reads and model loaded): find_overlap_pairs(core=mask) -> align -> jobs of at most
     `group_targets` targets cut from the table -> featurize -> infer -> consensus -> FASTA.  Rows whose record failed are dropped
-    (api.paired_job_args).  finder_params: find_overlap_pairs' keywords, occ_dist / rescue_max_occ (the rescue of high-frequency minimizers) among them.  Returns (rids, ends, text) as merge_records takes them."""
+    (api.paired_job_args).  postprocess: None — Job.fasta, the corrected reads as they are —, or the keywords of Job.fasta_dev (chop_len,
+    min_length, line_width; api.POSTPROCESS is scripts/postprocess_corrected.sh): the records are chopped and filtered for the assembler
+    where they are written, on the device.  finder_params: find_overlap_pairs' keywords, occ_dist / rescue_max_occ (the rescue of high-frequency minimizers) among them.  Returns (rids, ends, text) as merge_records takes them."""
     from . import api
     pairs = ctx.find_overlap_pairs(core=mask, **finder_params)
     m = pairs.align()
@@ -731,7 +733,11 @@ def correct_reads_shard(ctx, mask, window_size: int, batch: int, batch_mode: int
                 job.featurize()
                 job.infer(batch, batch_mode)
                 job.consensus()
-                text, ends = job.fasta([read_name(int(r)) for r in rids[t0:t1]], with_ends=True, as_array=True)
+                names = [read_name(int(r)) for r in rids[t0:t1]]
+                if postprocess is None:
+                    text, ends = job.fasta(names, with_ends=True, as_array=True)
+                else:
+                    text, ends = job.fasta_dev(names, with_ends=True, as_array=True, **postprocess)
                 parts.append((rids[t0:t1].copy(), ends, text))
             finally:
                 job.close()
@@ -742,10 +748,10 @@ def correct_reads_shard(ctx, mask, window_size: int, batch: int, batch_mode: int
 
 
 def correct_reads_sharded(ctx, read_lens, window_size: int, batch: int, batch_mode: int, read_name, group=None, group_targets: int = 1024,
-                          partition: str = "windows", min_span: int = 0, **finder_params):
+                          partition: str = "windows", min_span: int = 0, postprocess=None, **finder_params):
     """correct_reads_shard for this rank's mask, then correct_sharded_local's gather of the records to rank 0.  partition: "windows" — core_masks,
     the window counts alone —, or "overlaps" — cluster_masks(min_span=min_span), the overlap graph's clusters; the records are the same either way,
-    the pairs aligned on two ranks are not.  Returns ((rids, ends, text) on rank 0 else None, this rank's core reads)."""
+    the pairs aligned on two ranks are not.  postprocess: as correct_reads_shard (None: the corrected reads as they are).  Returns ((rids, ends, text) on rank 0 else None, this rank's core reads)."""
     dist = _dist()
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -757,7 +763,7 @@ def correct_reads_sharded(ctx, read_lens, window_size: int, batch: int, batch_mo
         mask = masks[rank]
     else:
         raise ValueError('partition is "windows" or "overlaps"')
-    rec = correct_reads_shard(ctx, mask, window_size, batch, batch_mode, read_name, group_targets=group_targets, **finder_params)
+    rec = correct_reads_shard(ctx, mask, window_size, batch, batch_mode, read_name, group_targets=group_targets, postprocess=postprocess, **finder_params)
     n_mine = int(np.count_nonzero(mask))
     if _alone(world):
         return merge_records([rec]), n_mine

@@ -860,6 +860,54 @@ int herro_clusters_part_stats(const herro_clusters* cl, uint32_t p, uint64_t out
 int herro_clusters_mask(const herro_clusters* cl, uint32_t p, uint8_t* out /* [n_reads] */);
 void herro_clusters_free(herro_clusters* cl);
 
+/* ---- corrected reads as FASTA formed on the device, chopped for the assembler (csrc/fasta_dev.hip, csrc/chop_plan.h) -------
+ * The reference's workflow runs scripts/postprocess_corrected.sh behind `herro inference`: `seqkit sliding -s 30000 -W 30000 -g` cuts every corrected
+ * read into pieces of 30000 bases (the last one shorter) and `seqkit seq -m 10000` drops the pieces below 10000; the result is what hifiasm is given.
+ * herro_job_fasta_dev writes that file's text — or, with all-zero parameters, herro_job_fasta's, byte for byte — on the device, from the bases
+ * herro_job_consensus left there: records are segmented, chopped, filtered, named and written by kernels, and the host receives finished text,
+ * copied to its place in one pinned block that the handle owns.  herro_job_fasta downloads every padded window slot and assembles on the host
+ * pool; it stays the default path.
+ * Specification (tests/chop_ref.py states it as a function of herro_job_fasta's text; all integer, independent of any thread order or chunk size):
+ *   Segments (consensus.rs:90-111, lib.rs:282-317, as herro_job_fasta).  Window w is corrected iff min(n_overlaps kept, 30) >= 2.  The maximal runs of
+ *   corrected windows of a target are its segments; a segment's sequence is its windows' corrected bases in order; segments of length 0 are dropped,
+ *   the rest numbered i = 0 .. n_seg - 1; the name is id if n_seg == 1, else id:i.  A target with ids[t] == NULL gives nothing.
+ *   Pieces.  A segment of n bases with chop_len C: C == 0 gives one piece [0, n) without suffix; C > 0 gives pieces k = 0 .. ceil(n / C) - 1 =
+ *   [kC, min((k + 1)C, n)), each with the suffix `_sliding:<kC + 1>-<min((k + 1)C, n)>` (1-based, inclusive, decimal, as seqkit names them; also
+ *   when there is one piece).  This is `seqkit sliding -s C -W C -g`; unequal step and window are not offered.  A piece is kept iff
+ *   end - start >= min_length.  The `:i` numbering is that of the segments, before any piece is dropped.
+ *   Record.  '>' name suffix ' ' [desc] '\n' body '\n'; the space is always there, as in herro_job_fasta.  line_width L > 0: a '\n' behind every L
+ *   bases of the body except at its end; 0: one line.  Order: target, segment, piece, ascending.
+ * herro_fasta_text_target_end: [n_targets], the offset behind every target's records, as herro_job_fasta's rec_end.  herro_fasta_text_stats: records
+ * written, bases written, pieces dropped, bases dropped, segments (non-empty), targets that gave at least one record.  The pointers stay valid
+ * until herro_fasta_text_free; the text lies in page-locked host memory that is recycled through the context (up to four blocks are kept), so a
+ * caller that keeps many texts copies them out.  A handle may be freed after its context.
+ * Checks, in this order: HERRO_E_INVALID — job or out NULL, ids NULL with targets, a parameter herro_chop_plan refuses —, HERRO_E_STATE —
+ * herro_job_consensus has not run —, HERRO_E_UNSUPPORTED — window slots of 2^32 bytes or more in the job, which keeps bases and pieces below 2^32.
+ * A HIP call that fails is HERRO_E_NO_DEVICE with the call's name; nothing stays allocated.  The call checks the sibling tiles of the job's model
+ * pass as the fetch of herro_job_fasta does, and forms the text from the repeated pass if that check repeats it.  It runs on the context's execution
+ * stream and returns when the text is on the host.  The text is formed in chunks of a sixteenth of HERRO_FASTA_SCRATCH_MB (default 1024) in two
+ * device buffers, each copied down behind its kernel;
+ * herro_debug_set_fasta_chunk, a test hook, sets the chunk's bytes for the context's later calls (0: the default) — the bytes of the text do not
+ * depend on it.  HERRO_FASTA_STATS=1 prints `FASTA targets= segments= pieces= dropped= bytes= chunks= seg_ms= piece_ms= write_ms=` on stderr. */
+typedef struct { uint32_t chop_len, min_length, line_width, flags, reserved[4]; } herro_chop_params;   /* 0 = off; reserved, flags: 0 */
+typedef struct herro_fasta_text herro_fasta_text;
+int herro_job_fasta_dev(herro_job* job, const char* const* ids, const char* const* descs /* NULL or entries NULL: none */,
+                        const herro_chop_params* params /* NULL: all zero */, herro_fasta_text** out);
+const char* herro_fasta_text_data(const herro_fasta_text* t);
+uint64_t herro_fasta_text_len(const herro_fasta_text* t);
+const uint64_t* herro_fasta_text_target_end(const herro_fasta_text* t);     /* [n_targets] */
+int herro_fasta_text_stats(const herro_fasta_text* t, uint64_t out[6]);      /* records, bases written, pieces dropped, bases dropped, segments, targets emitted */
+void herro_fasta_text_free(herro_fasta_text* t);
+int herro_debug_set_fasta_chunk(herro_ctx* ctx, uint64_t bytes);             /* test hook, see above */
+/* herro_chop_plan: the piece rule alone, over sequence lengths (csrc/chop_plan.h: host code, no device) — the pieces {seq, start, end} that
+ * herro_job_fasta_dev keeps of segments of these lengths, grouped by sequence (piece_off[s] .. piece_off[s + 1]), in a herro_trim handle (its
+ * accessors above).  herro_trim_stats of it: pieces kept, pieces dropped, bases kept, bases dropped.  An empty sequence gives no piece with
+ * chop_len > 0 and its one empty piece with chop_len == 0.  HERRO_E_INVALID and a message in err: a null argument, a non-zero reserved field or
+ * flag, chop_len or line_width above 2^31 - 1; HERRO_E_UNSUPPORTED: a sequence of 2^32 bases or more, more than 2^32 - 1 sequences or pieces
+ * (counted before the filter). */
+int herro_chop_plan(uint64_t n_seqs, const uint64_t* len, const herro_chop_params* params /* NULL: all zero */, herro_trim** out, char* err,
+                    uint64_t err_cap);
+
 /* One window of `herro features` (output_features, features.rs:724-764): <dir>/<wid>.ids.txt (one id per line),
  * <wid>.features.npy = u8 [2, length, 31] (ASCII bases [length][31], then qualities), <wid>.supported.npy = records
  * {pos: <u2, ins: u1}.  NPY format 1.0, C order, header as numpy writes it (dict padded with spaces to a multiple of 64
