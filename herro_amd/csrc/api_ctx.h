@@ -103,6 +103,18 @@ struct HostPool {
 
 struct Arena { void* p = nullptr; size_t cap = 0; };
 
+// The smallest block of a free list that holds `need` bytes, taken out of the list (null: none does).  The caller holds the list's lock; what a list's
+// fresh blocks are made of, and with how much slack, is the caller's.
+inline Arena best_fit_take(std::vector<Arena>& list, size_t need) {
+  size_t best = list.size();
+  for (size_t i = 0; i < list.size(); i++)
+    if (list[i].cap >= need && (best == list.size() || list[i].cap < list[best].cap)) best = i;
+  if (best == list.size()) return Arena{};
+  const Arena a = list[best];
+  list.erase(list.begin() + best);
+  return a;
+}
+
 // Pinned host blocks that results handed to the caller live in (herro_fasta_text): recycled like the job arenas — hipHostMalloc of a text's size
 // costs more than forming the text —, and shared between the context and its handles, so that a handle freed after its context still has
 // somewhere to give its block back to; the blocks go with the last holder.
@@ -111,14 +123,9 @@ struct PinPool {
   std::vector<Arena> free;
   ~PinPool() { for (Arena& a : free) (void)hipHostFree(a.p); }
   Arena acquire(size_t need) {
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      size_t best = free.size();
-      for (size_t i = 0; i < free.size(); i++)
-        if (free[i].cap >= need && (best == free.size() || free[i].cap < free[best].cap)) best = i;
-      if (best != free.size()) { Arena a = free[best]; free.erase(free.begin() + best); return a; }
-    }
     Arena a;
+    { std::lock_guard<std::mutex> lk(mu); a = best_fit_take(free, need); }
+    if (a.p) return a;
     a.cap = need + need / 8 + 4096;
     if (hipHostMalloc(&a.p, a.cap, hipHostMallocDefault) != hipSuccess) { a.p = nullptr; a.cap = 0; }
     return a;

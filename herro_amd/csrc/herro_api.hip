@@ -29,6 +29,7 @@
 #include "windowing.hpp"
 #include "build_dev.h"
 #include "cigar_dev.h"
+#include "job_layout.h"
 #include "align_dev.h"
 #include "overlap_dev.h"
 #include "fasta_dev.h"
@@ -86,6 +87,9 @@ struct harr {
 struct RfGather { enum Who : uint8_t { NONE, BY_ROWS, BY_RFQ } who = NONE; uint32_t half = 0; uint64_t cap = 0; };
 
 struct herro_job {
+  herro_job() = default;
+  herro_job(const herro_job&) = delete;
+  ~herro_job();   // returns the arenas, the small buffers and the events
   herro_ctx* ctx = nullptr;
   // ---- build (herro_job_create*): descriptors, arenas, what was left out
   uint32_t W = 0, n_targets = 0;
@@ -149,6 +153,16 @@ struct herro_job {
   uint8_t* h_cons_seq = nullptr;
 };
 
+// herro_debug_job_array: n elements of a job's device array, behind everything the device has in flight, into the debug vector v
+template <class T>
+static int64_t debug_fetch(herro_job* job, std::vector<T>& v, const void* d_src, size_t n, const void** ptr) {
+  v.resize(n);
+  if (hipSetDevice(job->ctx->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+      (n && hipMemcpy(v.data(), d_src, n * sizeof(T), hipMemcpyDeviceToHost) != hipSuccess)) return HERRO_E_NO_DEVICE;
+  *ptr = v.data();
+  return (int64_t)n;
+}
+
 static int job_sync(herro_job* job);
 static int ensure_logits(herro_job* job, uint64_t rows);
 
@@ -167,14 +181,9 @@ HostPool& host_pool(herro_ctx* ctx) {
 // late, small device buffers of a job (sized by results): recycled per context like the arenas — hipMalloc / hipFree
 // synchronise the whole device, which would serialise the feeder threads of a GPU on every job
 static Arena small_acquire(herro_ctx* ctx, size_t need) {
-  {
-    std::lock_guard<std::mutex> lk(ctx->arena_mu);
-    size_t best = ctx->free_small.size();
-    for (size_t i = 0; i < ctx->free_small.size(); i++)
-      if (ctx->free_small[i].cap >= need && (best == ctx->free_small.size() || ctx->free_small[i].cap < ctx->free_small[best].cap)) best = i;
-    if (best != ctx->free_small.size()) { Arena a = ctx->free_small[best]; ctx->free_small.erase(ctx->free_small.begin() + best); return a; }
-  }
   Arena a;
+  { std::lock_guard<std::mutex> lk(ctx->arena_mu); a = best_fit_take(ctx->free_small, need); }
+  if (a.p) return a;
   a.cap = need + need / 4 + 4096;
   if (hipMalloc(&a.p, a.cap) != hipSuccess) { a.p = nullptr; a.cap = 0; }
   return a;
@@ -189,14 +198,9 @@ static void small_release(herro_ctx* ctx, Arena& a) {
 // A job-sized block from one of the context's free lists (best fit), or a fresh one with 12 % slack.
 // kind: 0 pinned host, 1 device; host-only contexts get plain malloc.
 static Arena arena_acquire(herro_ctx* ctx, std::vector<Arena>& list, size_t need, int kind) {
-  {
-    std::lock_guard<std::mutex> lk(ctx->arena_mu);
-    size_t best = list.size();
-    for (size_t i = 0; i < list.size(); i++)
-      if (list[i].cap >= need && (best == list.size() || list[i].cap < list[best].cap)) best = i;
-    if (best != list.size()) { Arena a = list[best]; list.erase(list.begin() + best); return a; }
-  }
   Arena a;
+  { std::lock_guard<std::mutex> lk(ctx->arena_mu); a = best_fit_take(list, need); }
+  if (a.p) return a;
   a.cap = need + need / 8 + 4096;
   if (ctx->host_only) a.p = std::malloc(a.cap);
   else if (kind == 1) { if (hipMalloc(&a.p, a.cap) != hipSuccess) a.p = nullptr; }
@@ -204,16 +208,31 @@ static Arena arena_acquire(herro_ctx* ctx, std::vector<Arena>& list, size_t need
   if (!a.p) a.cap = 0;
   return a;
 }
-// gives a block back to its list when the scope ends, unless dismissed (the job keeps it)
-struct ArenaReturn {
-  herro_ctx* ctx; std::vector<Arena>* list; Arena* a; bool armed = true;
-  ~ArenaReturn() {
-    if (!armed || !a->p) return;
-    std::lock_guard<std::mutex> lk(ctx->arena_mu);
-    list->push_back(*a);
-    *a = Arena{};
-  }
-};
+// ... and back: a list keeps a handful of blocks for the next jobs (the bench cycles 2-4 jobs per context); the rest goes back to where it came from
+static void arena_release(herro_ctx* ctx, std::vector<Arena>& list, Arena& a, int kind) {
+  if (!a.p) return;
+  std::lock_guard<std::mutex> lk(ctx->arena_mu);
+  if (list.size() < 6) list.push_back(a);
+  else if (ctx->host_only) std::free(a.p);
+  else if (kind == 1) (void)hipFree(a.p);
+  else (void)hipHostFree(a.p);
+  a = Arena{};
+}
+
+// Whatever a job holds of its context goes back when it is destroyed, so a herro_job_create that fails half way just lets go of the job.  Nothing of the
+// job may be in flight by then: herro_job_free waits for the stream first, a failed create has waited for whatever it enqueued.
+herro_job::~herro_job() {
+  if (!ctx) return;
+  arena_release(ctx, ctx->free_dev, dev, 1);
+  arena_release(ctx, ctx->free_scan, scan, 1);
+  arena_release(ctx, ctx->free_pin, pin, 0);
+  small_release(ctx, a_logits);
+  small_release(ctx, a_bdesc);
+  small_release(ctx, a_supoff);
+  small_release(ctx, a_supoff_dev);
+  if (ev_counts) (void)hipEventDestroy(ev_counts);
+  if (ev_blob) (void)hipEventDestroy(ev_blob);
+}
 
 static constexpr uint32_t FUSED_MAX_SIB = 8;     // sibling tiles of one window in the f16 stack (k_layers_p<., 4, true>): windows of up to 512 informative rows stay fused (the plan in infer_plan.h never reads it; tests/capacity_cases.py reads it here)
 // Most informative rows of a window that stays on the fused stack: 64 (one tile), or 64 * FUSED_MAX_SIB with the f16 stack, which
@@ -1242,300 +1261,270 @@ struct OpsSrc { const uint32_t* d_store; const uint64_t* off; const uint32_t* n_
 }  // namespace
 
 // ---- job -------------------------------------------------------------------------------------------
-// herro_job_create (src == nullptr: the ops come as CIGAR text) and the direct path of herro_job_create_aligned (src: they are on the device; the caller
-// has checked that the context builds on the device).  *unsettled is raised, with nothing reported, when the direct path does not settle the job: the
-// caller then goes through the text of the job's ops.
-static herro_job* job_create_from(herro_ctx* ctx, uint32_t n_targets, const uint32_t* rids, const uint64_t* aln_off,
-                                  const herro_alignment* alns, uint32_t W, const OpsSrc* src, bool* unsettled);
+// Job creation in stages ("Job creation as built"): argument checks; the scan plan (host only); staging into the pinned mirror of the scan
+// block; the device pass (copies, scan, first phase of the device build, totals); the host build where the device did not settle the job; the job's
+// pinned arena and the merge; the device arena and the descriptors' way into it.  Where the arrays lie inside the blocks is job_layout.h's.
 
-herro_job* herro_job_create(herro_ctx* ctx, uint32_t n_targets, const uint32_t* rids, const uint64_t* aln_off,
-                            const herro_alignment* alns, uint32_t W) {
-  return job_create_from(ctx, n_targets, rids, aln_off, alns, W, nullptr, nullptr);
+// herro_job_create* return a pointer: the code of a failure travels through herro_job_create_status
+static herro_job* create_fail(herro_ctx* ctx, int code, const std::string& m) {
+  ctx->err = m + " [code " + std::to_string(code) + "]";
+  ctx->create_code = code;
+  return nullptr;
 }
 
-static herro_job* job_create_from(herro_ctx* ctx, uint32_t n_targets, const uint32_t* rids, const uint64_t* aln_off,
-                                  const herro_alignment* alns, uint32_t W, const OpsSrc* src, bool* unsettled) {
-  if (!ctx) return nullptr;
-  auto fail = [&](int code, const std::string& m) -> herro_job* {
-    ctx->err = m + " [code " + std::to_string(code) + "]";
-    ctx->create_code = code;   // herro_job_create returns a pointer: the code travels through herro_job_create_status
-    return nullptr;
-  };
-  ctx->create_code = HERRO_OK;
-  if (!ctx->d_words && !ctx->host_only) return fail(HERRO_E_STATE, "herro_set_reads must be called first");
-  if (W < 16 || W > HERRO_MAX_WINDOW) return fail(HERRO_E_UNSUPPORTED, "window_size must be in [16, 8192]");
-  if (n_targets && (!rids || !aln_off)) return fail(HERRO_E_INVALID, "null argument");
-  if (!ctx->host_only && hipSetDevice(ctx->device) != hipSuccess) return fail(HERRO_E_NO_DEVICE, "hipSetDevice failed");
+namespace {
+using HostClock = std::chrono::steady_clock;
+double ms_between(HostClock::time_point a, HostClock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+struct CreateClock { HostClock::time_point begin, staged, scanned, built, merged; };   // HERRO_HOST_PROFILE: when each stage was over
 
-  const bool prof = getenv("HERRO_HOST_PROFILE") != nullptr;
-  ProfSpan span_(ctx, "create");
-  auto tnow = [] { return std::chrono::steady_clock::now(); };
-  auto t_begin = tnow();
-  auto job = std::make_unique<herro_job>();
-  job->ctx = ctx;
-  job->W = W;
-  job->n_targets = n_targets;
-  job->tgt_win_off.assign(n_targets + 1, 0);
-  // ---- per-target host work (CIGAR parse, windowing, validation) is independent: it runs on the context's thread
-  // pool, each target into its own buffers with target-local offsets, merged in target order below.
-  HostPool& hpool = host_pool(ctx);
-  // ---- the CIGAR text goes to the GPU first (cigar_dev.hip): the bytes are staged in pinned memory, one copy up, one
-  // kernel (a workgroup per alignment) writes the binary ops into the job's op array and returns, per alignment, the
-  // totals and the ops that reach a window boundary; the host then cuts windows from those records alone.
-  Arena stage{};
-  ArenaReturn stage_ret{ctx, &ctx->free_stage, &stage};
-  ArenaReturn scan_ret{ctx, &ctx->free_scan, &job->scan};
-  DevScanView dsv{nullptr, nullptr, nullptr};
-  const DevScanView* ds = nullptr;
-  const uint64_t a0 = n_targets ? aln_off[0] : 0, nA = n_targets ? aln_off[n_targets] - a0 : 0;
-  auto t_scanned = t_begin;
-  bool try_dev = false, dev_built = false;
-  JobPrepass PP;
-  const std::vector<TgtMeta>& tmeta = PP.tmeta;
-  const std::vector<AlnMeta>& ameta = PP.ameta;
-  const std::vector<uint32_t>& pre_skip = PP.skip;
-  const std::vector<std::string>& pre_first = PP.first;
-  const uint32_t &pre_nwin = PP.n_win, &pre_ncls = PP.n_cls;
-  BuildDev BD{};
-  BuildTotals btot{};
-  if (!ctx->host_only && ctx->dev_scan && nA) {
-    if (!alns) return fail(HERRO_E_INVALID, "null argument");
-    if (nA > 0x7fffffffull) return fail(HERRO_E_UNSUPPORTED, "job too large (alignments)");
-    auto up256 = [](uint64_t x) { return (x + 255) & ~uint64_t(255); };
-    std::vector<CigIn> in(nA);
-    uint64_t txt = 0, opn = 0, cutn = 0, txt_sum = 0;
-    const unsigned char *t_lo = nullptr, *t_hi = nullptr;   // the range of the caller's memory that holds the job's texts
-    for (uint64_t g = 0; g < nA; g++) {
-      const herro_alignment& al = alns[a0 + g];
-      const uint32_t cap = (al.tend >= al.tstart ? (al.tend - al.tstart) / W : 0u) + 3u;   // one cut per window boundary the coordinates span, + slack
-      if (src) {   // binary ops on the device (k_ops_scan): the slice's first word and its op count; the job's op array has room for exactly that many
-        in[g] = CigIn{src->off[a0 + g], src->n_ops[a0 + g], al.tstart, (uint32_t)opn, (uint32_t)cutn, cap, 0};
-        opn += src->n_ops[a0 + g];
-        cutn += cap;
-        continue;
-      }
-      if (al.cigar_len && !al.cigar) return fail(HERRO_E_INVALID, "alignment without cigar");
-      in[g] = CigIn{txt, al.cigar_len, al.tstart, (uint32_t)opn, (uint32_t)cutn, cap, 0};
-      txt += ((uint64_t)al.cigar_len + 15) & ~uint64_t(15);
-      opn += (uint64_t)al.cigar_len / 2 + 1;
+struct CreateArgs {   // the arguments of herro_job_create*; src: see job_create_from
+  herro_ctx* ctx; uint32_t n_targets; const uint32_t* rids; const uint64_t* aln_off; const herro_alignment* alns; uint32_t W; const OpsSrc* src;
+  uint64_t a0, nA;    // the job's alignments are alns[a0, a0 + nA)
+};
+
+// a block of a free list for the length of a scope (the pinned staging block of one herro_job_create)
+struct ArenaHold {
+  herro_ctx* ctx; std::vector<Arena>* list; int kind; Arena a{};
+  ~ArenaHold() { arena_release(ctx, *list, a, kind); }
+};
+
+// ---- stage 2: the scan plan.  One CigIn per alignment, the totals that size the scan block, and where the text comes from.  Host only.
+struct ScanPlan {
+  std::vector<CigIn> in;
+  uint64_t txt = 0, opn = 0, cutn = 0;   // text bytes of the block, op slots, cut slots
+  // Zero-copy (round 5): when the texts lie densely inside a range the caller registered (herro_host_register: the PAF text of
+  // herro_paf_parse_view, a CIGAR blob), that range goes up in ONE copy from where it is — no staging pass over the bytes (0.9 of the
+  // 3.4 ms an unloaded herro_job_create of 4096 windows took, and the part that fights the other feeders for memory bandwidth).  A
+  // text keeps its alignment modulo 16: the scan kernel reads aligned 16-byte pieces and skips the bytes in front of the text.
+  const unsigned char* t_lo = nullptr;   // the range of the caller's memory that holds the job's texts: [t_lo, t_lo + span)
+  uint64_t span = 0, lead = 0;           // lead: t_lo modulo 16
+  bool direct = false;                   // the range goes up as it is
+  bool read_host = false;                // ... or not at all: the scan kernel reads it at t_dev over PCIe
+  const unsigned char* t_dev = nullptr;
+};
+
+// (the totals run in locals: one pass over some 10^5 alignments per job on the feeder's own thread, where sums kept in S would go through memory every step)
+bool plan_scan(const CreateArgs& A, ScanPlan& S) {
+  herro_ctx* ctx = A.ctx;
+  if (!A.alns) return create_fail(ctx, HERRO_E_INVALID, "null argument"), false;
+  if (A.nA > 0x7fffffffull) return create_fail(ctx, HERRO_E_UNSUPPORTED, "job too large (alignments)"), false;
+  const herro_alignment* alns = A.alns + A.a0;
+  const uint64_t nA = A.nA;
+  const uint32_t W = A.W;
+  const OpsSrc* src = A.src;
+  S.in.resize(nA);
+  CigIn* in = S.in.data();
+  uint64_t txt = 0, opn = 0, cutn = 0, txt_sum = 0;
+  const unsigned char *t_lo = nullptr, *t_hi = nullptr;
+  for (uint64_t g = 0; g < nA; g++) {
+    const herro_alignment& al = alns[g];
+    const uint32_t cap = (al.tend >= al.tstart ? (al.tend - al.tstart) / W : 0u) + 3u;   // one cut per window boundary the coordinates span, + slack
+    if (src) {   // binary ops on the device (k_ops_scan): the slice's first word and its op count; the job's op array has room for exactly that many
+      in[g] = CigIn{src->off[A.a0 + g], src->n_ops[A.a0 + g], al.tstart, (uint32_t)opn, (uint32_t)cutn, cap, 0};
+      opn += src->n_ops[A.a0 + g];
       cutn += cap;
-      if (al.cigar_len) {
-        txt_sum += al.cigar_len;
-        if (!t_lo || al.cigar < t_lo) t_lo = al.cigar;
-        if (!t_hi || al.cigar + al.cigar_len > t_hi) t_hi = al.cigar + al.cigar_len;
-      }
+      continue;
     }
-    if (opn > 0xffffffffull || cutn > 0xffffffffull) return fail(HERRO_E_UNSUPPORTED, "job too large (ops exceed 2^32)");
-    // ---- device build (round 6): what needs no CIGAR is settled here — who is left out (parse_paf's rules), the ratio classes, the windows of every target —
-    // and goes up beside the text; anything this pass would have to report sends the job down the host path below, which words it.
-    try_dev = ctx->dev_build && job_prepass(ctx, hpool, n_targets, rids, aln_off, alns, W, job->tgt_win_off, PP);
-    if (src && !try_dev) { *unsettled = true; return nullptr; }
-    // Zero-copy (round 5): when the texts lie densely inside a range the caller registered (herro_host_register: the PAF text of
-    // herro_paf_parse_view, a CIGAR blob), that range goes up in ONE copy from where it is — no staging pass over the bytes (0.9 of the
-    // 3.4 ms an unloaded herro_job_create of 4096 windows took, and the part that fights the other feeders for memory bandwidth).  A
-    // text keeps its alignment modulo 16: the scan kernel reads aligned 16-byte pieces and skips the bytes in front of the text.
-    // HERRO_ZERO_COPY: 0 stage every text; 1 (default) copy a registered range up as it is; 2 (round 6, measured in profiles/r6_e2e_ab.txt) no copy at all — the scan kernel
-    // reads the registered range over PCIe where the caller has it (no blit kernel, no 50 MB through HBM and back per 4096 windows)
-    static const int zc_mode = [] { const char* e = getenv("HERRO_ZERO_COPY"); return e ? atoi(e) : 1; }();
-    const bool allow_direct = zc_mode != 0;
-    const uint64_t span = t_lo ? (uint64_t)(t_hi - t_lo) : 0;
-    const unsigned char* t_dev = nullptr;
-    const bool direct = allow_direct && t_lo && span <= txt_sum + txt_sum / 2 + 65536 && host_range_registered(t_lo, t_hi, &t_dev);
-    const bool read_host = direct && zc_mode == 2 && t_dev != nullptr;
-    const uint64_t lead = direct ? ((uintptr_t)t_lo & 15u) : 0;
-    if (direct) {
-      for (uint64_t g = 0; g < nA; g++) {
-        const herro_alignment& al = alns[a0 + g];
-        const uint64_t off = al.cigar_len ? lead + (uint64_t)(al.cigar - t_lo) : 0;
-        in[g].txt_off = off & ~uint64_t(15);
-        in[g].skip = (uint32_t)(off & 15u);
-      }
-      txt = (lead + span + 31) & ~uint64_t(15);
-      g_zero_copy_jobs++;
+    if (al.cigar_len && !al.cigar) return create_fail(ctx, HERRO_E_INVALID, "alignment without cigar"), false;
+    in[g] = CigIn{txt, al.cigar_len, al.tstart, (uint32_t)opn, (uint32_t)cutn, cap, 0};
+    txt += ((uint64_t)al.cigar_len + 15) & ~uint64_t(15);
+    opn += (uint64_t)al.cigar_len / 2 + 1;
+    cutn += cap;
+    if (al.cigar_len) {
+      txt_sum += al.cigar_len;
+      if (!t_lo || al.cigar < t_lo) t_lo = al.cigar;
+      if (!t_hi || al.cigar + al.cigar_len > t_hi) t_hi = al.cigar + al.cigar_len;
     }
-    // block layout: [text][CigIn][AlnMeta][TgtMeta][window -> target]  (host -> device, one copy)  |  [CigOut][cuts][totals]  (device -> host when the host builds)
-    //               |  [AlnHead][HowRec][WinAcc][window prefixes]  (device only)
-    const uint64_t o_in = up256(txt + 16), o_am = o_in + up256(nA * sizeof(CigIn)), o_tm = o_am + (try_dev ? up256(nA * sizeof(AlnMeta)) : 0);
-    const uint64_t o_wt = o_tm + (try_dev ? up256((uint64_t)n_targets * sizeof(TgtMeta)) : 0), o_out = o_wt + (try_dev ? up256((uint64_t)pre_nwin * 4) : 0);
-    const uint64_t o_cut = o_out + up256(nA * sizeof(CigOut)), o_tot = o_cut + up256(cutn * sizeof(CigCut));
-    const uint64_t blk_bytes = o_tot + 256;   // what the pinned staging block mirrors
-    const uint64_t o_head = blk_bytes, o_how = o_head + (try_dev ? up256(nA * sizeof(AlnHead)) : 0), o_wacc = o_how + (try_dev ? up256(cutn * sizeof(HowRec)) : 0);
-    const uint64_t o_pfx = o_wacc + (try_dev ? up256((uint64_t)pre_nwin * sizeof(WinAcc)) : 0);
-    const uint64_t pfx_each = up256(((uint64_t)pre_nwin + 1) * 8);
-    const uint64_t dev_blk_bytes = o_pfx + (try_dev ? 4 * pfx_each : 0), ops_bytes = up256(opn * 4);
-    stage = arena_acquire(ctx, ctx->free_stage, blk_bytes, 0);
-    job->scan = arena_acquire(ctx, ctx->free_scan, ops_bytes + dev_blk_bytes, 1);
-    if (!stage.p || !job->scan.p) return fail(HERRO_E_NO_DEVICE, "out of memory for the CIGAR scan (" + std::to_string((ops_bytes + dev_blk_bytes) >> 20) + " MiB)");
-    unsigned char* hs = (unsigned char*)stage.p;
-    unsigned char* dsb = (unsigned char*)job->scan.p + ops_bytes;
-    const uint32_t per = 32, nblk = (uint32_t)((nA + per - 1) / per);
-    if (!direct && !src) hpool.run(nblk, [&](uint32_t b) {
-      for (uint64_t g = (uint64_t)b * per; g < std::min<uint64_t>(nA, (uint64_t)(b + 1) * per); g++) {
-        const herro_alignment& al = alns[a0 + g];
-        unsigned char* d = hs + in[g].txt_off;
-        if (al.cigar_len) std::memcpy(d, al.cigar, al.cigar_len);
-        std::memset(d + al.cigar_len, 0, (size_t)((((uint64_t)al.cigar_len + 15) & ~uint64_t(15)) - al.cigar_len));
-      }
-    });
-    std::memcpy(hs + o_in, in.data(), nA * sizeof(CigIn));
-    if (try_dev) {
-      std::memcpy(hs + o_am, ameta.data(), nA * sizeof(AlnMeta));
-      std::memcpy(hs + o_tm, tmeta.data(), (size_t)n_targets * sizeof(TgtMeta));
-      uint32_t* wt = (uint32_t*)(hs + o_wt);
-      hpool.run(n_targets, [&](uint32_t t) { for (uint32_t w = 0; w < tmeta[t].n_windows; w++) wt[tmeta[t].win0 + w] = t; });
-      std::memset(hs + o_tot, 0, sizeof(BuildTotals));
-    }
-    const auto t_staged = tnow();
-    hipEvent_t pe[4] = {nullptr, nullptr, nullptr, nullptr};   // HERRO_HOST_PROFILE: copy up / kernel / copy down on the device clock
-    if (prof) for (auto& ev : pe) (void)hipEventCreate(&ev);
-    if (pe[0]) (void)hipEventRecord(pe[0], ctx->prep_stream);
-    hipError_t e;
-    if (direct) {   // the texts from the caller's registered range (same alignment modulo 16), the alignment records from the staging block
-      e = read_host ? hipSuccess : hipMemcpyAsync(dsb + lead, t_lo, span, hipMemcpyHostToDevice, ctx->prep_stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(dsb + o_in, hs + o_in, o_out - o_in, hipMemcpyHostToDevice, ctx->prep_stream);
-    } else if (src) {   // no text: the alignment records alone
-      e = hipMemcpyAsync(dsb + o_in, hs + o_in, o_out - o_in, hipMemcpyHostToDevice, ctx->prep_stream);
-    } else {
-      e = hipMemcpyAsync(dsb, hs, o_out, hipMemcpyHostToDevice, ctx->prep_stream);
-    }
-    if (try_dev && e == hipSuccess) e = hipMemcpyAsync(dsb + o_tot, hs + o_tot, sizeof(BuildTotals), hipMemcpyHostToDevice, ctx->prep_stream);
-    if (pe[1]) (void)hipEventRecord(pe[1], ctx->prep_stream);
-    if (e == hipSuccess && src) {
-      launch_ops_scan(src->d_store, (const CigIn*)(dsb + o_in), (CigOut*)(dsb + o_out), (CigCut*)(dsb + o_cut), (uint32_t*)job->scan.p,
-                      &((BuildTotals*)(dsb + o_tot))->err, BLD_SCAN_FLAG, (uint32_t)nA, W, ctx->prep_stream);
-      e = hipGetLastError();
-    } else if (e == hipSuccess) {
-      launch_cigar_scan(read_host ? t_dev - lead : dsb, (const CigIn*)(dsb + o_in), (CigOut*)(dsb + o_out), (CigCut*)(dsb + o_cut), (uint32_t*)job->scan.p, (uint32_t)nA, W, ctx->prep_stream);
-      e = hipGetLastError();
-    }
-    if (pe[2]) (void)hipEventRecord(pe[2], ctx->prep_stream);
-    if (try_dev && e == hipSuccess) {   // windows and counts behind the scan; 64 bytes of totals come down instead of the cut records
-      BD.in = (const CigIn*)(dsb + o_in); BD.out = (const CigOut*)(dsb + o_out); BD.cuts = (CigCut*)(dsb + o_cut);
-      BD.am = (const AlnMeta*)(dsb + o_am); BD.tm = (const TgtMeta*)(dsb + o_tm); BD.win_tgt = (const uint32_t*)(dsb + o_wt);
-      BD.head = (AlnHead*)(dsb + o_head); BD.how = (HowRec*)(dsb + o_how); BD.wacc = (WinAcc*)(dsb + o_wacc); BD.tot = (BuildTotals*)(dsb + o_tot);
-      BD.n_aln = (uint32_t)nA; BD.n_tgt = n_targets; BD.n_win = pre_nwin; BD.W = W;
-      BD.read_word_off = ctx->d_word_off; BD.read_qual_off = ctx->d_qual_off;
-      uint32_t* p_owb = (uint32_t*)(dsb + o_pfx);
-      uint64_t *p_ev = (uint64_t*)(dsb + o_pfx + pfx_each), *p_tile = (uint64_t*)(dsb + o_pfx + 2 * pfx_each), *p_row = (uint64_t*)(dsb + o_pfx + 3 * pfx_each);
-      BD.ow_begin = p_owb; BD.ev_off = p_ev; BD.tile_off = p_tile; BD.row_off = p_row;
-      launch_build_phase1(BD, p_owb, p_ev, p_tile, p_row, ctx->prep_stream);
-      e = hipGetLastError();
-      if (e == hipSuccess) e = hipMemcpyAsync(hs + o_tot, dsb + o_tot, sizeof(BuildTotals), hipMemcpyDeviceToHost, ctx->prep_stream);
-      if (e == hipSuccess) e = hipEventRecord(ctx->prep_ev, ctx->prep_stream);
-      if (e == hipSuccess) e = hipEventSynchronize(ctx->prep_ev);
-      if (e == hipSuccess) {
-        std::memcpy(&btot, hs + o_tot, sizeof btot);
-        dev_built = btot.err == 0;
-      }
-    }
-    if (src && e == hipSuccess && !dev_built) {   // the text path rebuilds the job (the stream is idle: the totals' event has been waited for)
-      for (auto& ev : pe) if (ev) (void)hipEventDestroy(ev);
-      *unsettled = true;
-      return nullptr;
-    }
-    if (!dev_built) {   // the host cuts the windows from the scan's records (and words whatever is wrong with the input)
-      if (e == hipSuccess) e = hipMemcpyAsync(hs + o_out, dsb + o_out, o_tot - o_out, hipMemcpyDeviceToHost, ctx->prep_stream);
-      if (pe[3]) (void)hipEventRecord(pe[3], ctx->prep_stream);
-      if (e == hipSuccess) e = hipEventRecord(ctx->prep_ev, ctx->prep_stream);
-      if (e == hipSuccess) e = hipEventSynchronize(ctx->prep_ev);
-    } else if (pe[3]) (void)hipEventRecord(pe[3], ctx->prep_stream);
-    if (prof && e == hipSuccess) {
-      float up = 0, kn = 0, dn = 0;
-      (void)hipEventElapsedTime(&up, pe[0], pe[1]); (void)hipEventElapsedTime(&kn, pe[1], pe[2]); (void)hipEventElapsedTime(&dn, pe[2], pe[3]);
-      fprintf(stderr, "  cigar scan: %.1f MiB text staged in %.2f ms; device: copy up %.2f ms, kernel %.2f, copy down %.2f (%.1f MiB); wall %.2f ms\n", txt / 1048576.0,
-              std::chrono::duration<double, std::milli>(t_staged - t_begin).count(), up, kn, dn, (dev_built ? 64.0 : (double)(o_tot - o_out)) / 1048576.0,
-              std::chrono::duration<double, std::milli>(tnow() - t_staged).count());
-    }
-    for (auto& ev : pe) if (ev) (void)hipEventDestroy(ev);
-    if (e != hipSuccess) {
-      (void)hipStreamSynchronize(ctx->prep_stream);
-      return fail(HERRO_E_NO_DEVICE, std::string("CIGAR scan failed: ") + hipGetErrorString(e));
-    }
-    dsv = DevScanView{(const CigIn*)(hs + o_in), (const CigOut*)(hs + o_out), (const CigCut*)(hs + o_cut)};
-    ds = &dsv;
-    job->scan_ops = opn;
-    t_scanned = tnow();
   }
-  std::vector<TargetOut> outs(dev_built ? 0 : n_targets);
-  if (!dev_built) hpool.run(n_targets, [&](uint32_t t) {
-    build_target(ctx, rids[t], alns + aln_off[t], (uint32_t)(aln_off[t + 1] - aln_off[t]), W, outs[t], ds, aln_off[t] - a0);
+  S.txt = txt; S.opn = opn; S.cutn = cutn; S.t_lo = t_lo;
+  if (opn > 0xffffffffull || cutn > 0xffffffffull) return create_fail(ctx, HERRO_E_UNSUPPORTED, "job too large (ops exceed 2^32)"), false;
+  // HERRO_ZERO_COPY: 0 stage every text; 1 (default) copy a registered range up as it is; 2 (round 6, measured in profiles/r6_e2e_ab.txt) no copy at all — the scan kernel
+  // reads the registered range over PCIe where the caller has it (no blit kernel, no 50 MB through HBM and back per 4096 windows)
+  static const int zc_mode = [] { const char* e = getenv("HERRO_ZERO_COPY"); return e ? atoi(e) : 1; }();
+  const uint64_t span = t_lo ? (uint64_t)(t_hi - t_lo) : 0;
+  S.span = span;
+  S.direct = zc_mode != 0 && t_lo && span <= txt_sum + txt_sum / 2 + 65536 && host_range_registered(t_lo, t_hi, &S.t_dev);
+  S.read_host = S.direct && zc_mode == 2 && S.t_dev != nullptr;
+  if (!S.direct) return true;
+  const uint64_t lead = (uintptr_t)t_lo & 15u;
+  for (uint64_t g = 0; g < nA; g++) {
+    const herro_alignment& al = alns[g];
+    const uint64_t off = al.cigar_len ? lead + (uint64_t)(al.cigar - t_lo) : 0;
+    in[g].txt_off = off & ~uint64_t(15);
+    in[g].skip = (uint32_t)(off & 15u);
+  }
+  S.lead = lead;
+  S.txt = (lead + span + 31) & ~uint64_t(15);
+  g_zero_copy_jobs++;
+  return true;
+}
+
+// ---- stage 3: staging.  The texts (unless they go up from where they are, or there are none), the records, and for the device build what the pre-pass
+// settled, into the pinned mirror `hs` of the scan block.
+void stage_scan(const CreateArgs& A, const ScanPlan& S, const JobPrepass& P, const ScanLayout& L, const ScanView& hs, HostPool& hpool) {
+  const uint32_t per = 32, nblk = (uint32_t)((A.nA + per - 1) / per);
+  if (!S.direct && !A.src) hpool.run(nblk, [&](uint32_t b) {
+    for (uint64_t g = (uint64_t)b * per; g < std::min<uint64_t>(A.nA, (uint64_t)(b + 1) * per); g++) {
+      const herro_alignment& al = A.alns[A.a0 + g];
+      unsigned char* d = hs.text + S.in[g].txt_off;
+      if (al.cigar_len) std::memcpy(d, al.cigar, al.cigar_len);
+      std::memset(d + al.cigar_len, 0, (size_t)((((uint64_t)al.cigar_len + 15) & ~uint64_t(15)) - al.cigar_len));
+    }
   });
-  auto t_built = tnow();
-  // ---- merge in target order: a serial pass over the per-target SIZES fixes every base offset; the bytes are then
-  // copied (and the target-local indices rebased) by the pool, straight into the job's PINNED host arena, whose
-  // layout is the layout of the head of the device arena: one asynchronous copy takes all descriptors up.
-  struct Base { uint64_t op, ow, win, tile, cls, scr, fin, row, pos; };
-  std::vector<Base> base(n_targets + 1);
-  uint32_t n_cls = 0, max_cols = 1;
-  uint64_t scr_ops = 0, fin_bytes = 0, row_elems = 0, pos_elems = 0;
-  if (dev_built) {   // the device's totals (build_dev.hip) stand in for the sums over the per-target outputs
-    Base b{0, btot.n_ow, pre_nwin, btot.n_tiles, pre_ncls, btot.scr_ops, btot.fin_bytes, btot.row_elems, (uint64_t)pre_nwin * ((uint64_t)W + 1)};
-    base[n_targets] = b;
-    n_cls = pre_ncls; max_cols = btot.max_cols; scr_ops = btot.scr_ops; fin_bytes = btot.fin_bytes; row_elems = btot.row_elems; pos_elems = b.pos;
-    job->alg_read_bytes = btot.rd_bytes; job->alg_op_bytes = btot.op_bytes;
-    for (uint32_t t = 0; t < n_targets; t++)
-      if (pre_skip[t]) {
-        if (!job->n_skipped_alns) job->first_skip = pre_first[t];
-        job->n_skipped_alns += pre_skip[t];
-      }
+  std::memcpy(hs.in, S.in.data(), A.nA * sizeof(CigIn));
+  if (!L.try_dev) return;
+  std::memcpy(hs.am, P.ameta.data(), A.nA * sizeof(AlnMeta));
+  std::memcpy(hs.tm, P.tmeta.data(), (size_t)A.n_targets * sizeof(TgtMeta));
+  hpool.run(A.n_targets, [&](uint32_t t) { for (uint32_t w = 0; w < P.tmeta[t].n_windows; w++) hs.win_tgt[P.tmeta[t].win0 + w] = t; });
+  std::memset(hs.tot, 0, sizeof(BuildTotals));
+}
+
+// ---- stage 4: the device pass, on the context's prep stream.  The staged part goes up, the scan kernel writes the job's op array and the cut records; with
+// the device build behind it (L.try_dev) the first build phase follows and 64 bytes of totals come down instead of the records.
+//   BUILT        the device settled the job: *btot holds its totals, BD is bound for the second phase
+//   HOST_BUILDS  the scan's records are in `hs`: the host cuts the windows from them (and words whatever is wrong with the input)
+//   UNSETTLED    (ops from the device only) the text path rebuilds the job; the stream is idle: the totals' event has been waited for
+//   FAILED       reported
+// HERRO_HOST_PROFILE: copy up / kernels / copy down on the device clock, here and nowhere else.
+enum class DevPass { BUILT, HOST_BUILDS, UNSETTLED, FAILED };
+
+DevPass device_pass(const CreateArgs& A, const ScanPlan& S, const ScanLayout& L, const ScanView& hs, const ScanView& dv, uint32_t n_win, BuildDev& BD,
+                    BuildTotals& btot, bool prof, const CreateClock& clk) {
+  herro_ctx* ctx = A.ctx;
+  const hipStream_t st = ctx->prep_stream;
+  const uint64_t up_bytes = L.at(SP_OUT) - L.at(SP_IN), down_bytes = L.at(SP_TOTALS) - L.at(SP_OUT);   // [CigIn .. window -> target], [CigOut][cuts]
+  hipEvent_t pe[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (prof) for (auto& ev : pe) (void)hipEventCreate(&ev);
+  auto drop_events = [&] { for (auto& ev : pe) if (ev) (void)hipEventDestroy(ev); };
+  if (pe[0]) (void)hipEventRecord(pe[0], st);
+  hipError_t e;
+  if (S.direct) {   // the texts from the caller's registered range (same alignment modulo 16), the alignment records from the staging block
+    e = S.read_host ? hipSuccess : hipMemcpyAsync(dv.text + S.lead, S.t_lo, S.span, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dv.in, hs.in, up_bytes, hipMemcpyHostToDevice, st);
+  } else if (A.src) {   // no text: the alignment records alone
+    e = hipMemcpyAsync(dv.in, hs.in, up_bytes, hipMemcpyHostToDevice, st);
   } else {
-    Base b{0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (uint32_t t = 0; t < n_targets; t++) {
-      const TargetOut& o = outs[t];
-      if (o.err.code != HERRO_OK) return fail(o.err.code, "target " + std::to_string(t) + " (rid " + std::to_string(rids[t]) + "): " + o.err.msg);
-      if (o.n_skipped) {
-        if (!job->n_skipped_alns && !job->n_failed_targets) job->first_skip = o.first_skip;
-        job->n_skipped_alns += o.n_skipped;
-        job->n_failed_targets += o.failed ? 1u : 0u;
-      }
-      for (auto& pt : outs[t].op_patches) {   // rare; synchronous
-        if (hipMemcpy((uint32_t*)job->scan.p + pt.first, pt.second.data(), pt.second.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-          return fail(HERRO_E_NO_DEVICE, "op upload failed");
-      }
-      base[t] = b;
-      b.op += o.ops.size(); b.ow += o.ow.size(); b.win += o.win.size(); b.cls += o.n_cls; b.scr += o.scr_ops;
-      for (const WinDesc& wd : o.win) {
-        b.tile += (wd.lub + HERRO_TILE - 1) / HERRO_TILE;
-        b.fin += (uint64_t)HERRO_ROWS * wd.lub; b.row += wd.lub; b.pos += (uint64_t)W + 1;
-        max_cols = std::max(max_cols, wd.ow_cnt + 1);
-      }
-      if (b.op > 0xffffffffull) return fail(HERRO_E_UNSUPPORTED, "job too large (ops exceed 2^32)");
-      job->alg_read_bytes += o.alg_read_bytes;
-      job->alg_op_bytes += o.alg_op_bytes;
-      job->tgt_win_off[t + 1] = (uint32_t)b.win;
+    e = hipMemcpyAsync(dv.text, hs.text, L.at(SP_OUT), hipMemcpyHostToDevice, st);
+  }
+  if (L.try_dev && e == hipSuccess) e = hipMemcpyAsync(dv.tot, hs.tot, sizeof(BuildTotals), hipMemcpyHostToDevice, st);
+  if (pe[1]) (void)hipEventRecord(pe[1], st);
+  if (e == hipSuccess && A.src) {
+    launch_ops_scan(A.src->d_store, dv.in, dv.out, dv.cuts, dv.ops, &dv.tot->err, BLD_SCAN_FLAG, (uint32_t)A.nA, A.W, st);
+    e = hipGetLastError();
+  } else if (e == hipSuccess) {
+    launch_cigar_scan(S.read_host ? S.t_dev - S.lead : dv.text, dv.in, dv.out, dv.cuts, dv.ops, (uint32_t)A.nA, A.W, st);
+    e = hipGetLastError();
+  }
+  if (pe[2]) (void)hipEventRecord(pe[2], st);
+  bool dev_built = false;
+  if (L.try_dev && e == hipSuccess) {   // windows and counts behind the scan
+    bind_build_scan(BD, dv);
+    BD.n_aln = (uint32_t)A.nA; BD.n_tgt = A.n_targets; BD.n_win = n_win; BD.W = A.W;
+    BD.read_word_off = ctx->d_word_off; BD.read_qual_off = ctx->d_qual_off;
+    launch_build_phase1(BD, dv.ow_begin, dv.ev_off, dv.tile_off, dv.row_off, st);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(hs.tot, dv.tot, sizeof(BuildTotals), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipEventRecord(ctx->prep_ev, st);
+    if (e == hipSuccess) e = hipEventSynchronize(ctx->prep_ev);
+    if (e == hipSuccess) {
+      std::memcpy(&btot, hs.tot, sizeof btot);
+      dev_built = btot.err == 0;
     }
-    base[n_targets] = b;
-    n_cls = (uint32_t)b.cls; scr_ops = b.scr; fin_bytes = b.fin; row_elems = b.row; pos_elems = b.pos;
   }
-  // the windows' event slices live behind scr_ops + 2 * n_ow slots and are indexed with 32 bits on the device (WinDesc::ev_off -> CTab::ev_off)
-  if (scr_ops + 2ull * base[n_targets].ow > 0xffffffffull) return fail(HERRO_E_UNSUPPORTED, "job too large (op scratch exceeds 2^32)");
-  // (what was left out is reported by herro_job_skipped; the error slot is for errors only)
-  const Base& tot = base[n_targets];
-  // descriptor block (host arena == head of the device arena), 256-byte aligned pieces
-  size_t cur = 0;
-  auto take = [&](size_t bytes) { const size_t o = cur; cur = (cur + std::max<size_t>(bytes, 16) + 255) & ~size_t(255); return o; };
-  const size_t o_ops = take(tot.op * 4), o_ow = take(tot.ow * sizeof(OwDesc)), o_win = take(tot.win * sizeof(WinDesc));
-  const size_t o_tw = take(tot.tile * 4), o_tr = take(tot.tile * 4);
-  const size_t desc_bytes = cur;
-  const size_t o_counts = take(tot.win * 16 + 16);   // host arena only: pinned landing zone of the per-window counts (L', informative rows, kept overlaps, first receptive-field record) + the records allocated
-  const size_t o_hclen = take(tot.win * 4), o_hcseq = take(row_elems);   // ... and of the corrected bases (device consensus)
-  const size_t pin_bytes = cur;
-  job->pin = arena_acquire(ctx, ctx->free_pin, pin_bytes, 0);
-  if (!job->pin.p) return fail(HERRO_E_NO_DEVICE, "out of pinned host memory for the job");
-  {
-    unsigned char* hb = (unsigned char*)job->pin.p;
-    job->ops.p = (uint32_t*)(hb + o_ops); job->ops.n = tot.op;
-    job->ow.p = (OwDesc*)(hb + o_ow); job->ow.n = tot.ow;
-    job->win.p = (WinDesc*)(hb + o_win); job->win.n = tot.win;
-    job->tile_win.p = (uint32_t*)(hb + o_tw); job->tile_win.n = tot.tile;
-    job->tile_r0.p = (uint32_t*)(hb + o_tr); job->tile_r0.n = tot.tile;
-    job->h_counts = (uint32_t*)(hb + o_counts);
-    job->h_cons_len = (uint32_t*)(hb + o_hclen);
-    job->h_cons_seq = hb + o_hcseq;
+  if (A.src && e == hipSuccess && !dev_built) { drop_events(); return DevPass::UNSETTLED; }
+  if (!dev_built) {
+    if (e == hipSuccess) e = hipMemcpyAsync(hs.out, dv.out, down_bytes, hipMemcpyDeviceToHost, st);
+    if (pe[3]) (void)hipEventRecord(pe[3], st);
+    if (e == hipSuccess) e = hipEventRecord(ctx->prep_ev, st);
+    if (e == hipSuccess) e = hipEventSynchronize(ctx->prep_ev);
+  } else if (pe[3]) (void)hipEventRecord(pe[3], st);
+  if (prof && e == hipSuccess) {
+    float up = 0, kn = 0, dn = 0;
+    (void)hipEventElapsedTime(&up, pe[0], pe[1]); (void)hipEventElapsedTime(&kn, pe[1], pe[2]); (void)hipEventElapsedTime(&dn, pe[2], pe[3]);
+    fprintf(stderr, "  cigar scan: %.1f MiB text staged in %.2f ms; device: copy up %.2f ms, kernel %.2f, copy down %.2f (%.1f MiB); wall %.2f ms\n", S.txt / 1048576.0,
+            ms_between(clk.begin, clk.staged), up, kn, dn, (dev_built ? 64.0 : (double)down_bytes) / 1048576.0, ms_between(clk.staged, HostClock::now()));
   }
-  if (!dev_built) hpool.run(n_targets, [&](uint32_t t) {
+  drop_events();
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    create_fail(ctx, HERRO_E_NO_DEVICE, std::string("CIGAR scan failed: ") + hipGetErrorString(e));
+    return DevPass::FAILED;
+  }
+  return dev_built ? DevPass::BUILT : DevPass::HOST_BUILDS;
+}
+
+// what the device build settled besides its totals (job_totals): the algorithmic bytes; the pre-pass knows who was left out
+void adopt_device_build(herro_job* job, const BuildTotals& btot, const JobPrepass& P) {
+  job->alg_read_bytes = btot.rd_bytes; job->alg_op_bytes = btot.op_bytes;
+  for (size_t t = 0; t < P.skip.size(); t++)
+    if (P.skip[t]) {
+      if (!job->n_skipped_alns) job->first_skip = P.first[t];
+      job->n_skipped_alns += P.skip[t];
+    }
+}
+
+// ---- stage 5: the host build.  Per-target host work (CIGAR parse or the scan's records in `ds`, windowing, validation) is independent: it runs on the
+// context's thread pool, each target into its own buffers with target-local offsets.  A serial pass over the per-target SIZES then fixes every base
+// offset: base[t] is what the targets in front of t hold, base[n_targets] the job.
+bool host_build(const CreateArgs& A, const DevScanView* ds, HostPool& hpool, herro_job* job, std::vector<TargetOut>& outs, std::vector<JobTotals>& base,
+                CreateClock& clk) {
+  herro_ctx* ctx = A.ctx;
+  outs.resize(A.n_targets);
+  hpool.run(A.n_targets, [&](uint32_t t) {
+    build_target(ctx, A.rids[t], A.alns + A.aln_off[t], (uint32_t)(A.aln_off[t + 1] - A.aln_off[t]), A.W, outs[t], ds, A.aln_off[t] - A.a0);
+  });
+  clk.built = HostClock::now();
+  base.resize(A.n_targets + 1);
+  JobTotals b;
+  for (uint32_t t = 0; t < A.n_targets; t++) {
+    const TargetOut& o = outs[t];
+    if (o.err.code != HERRO_OK) return create_fail(ctx, o.err.code, "target " + std::to_string(t) + " (rid " + std::to_string(A.rids[t]) + "): " + o.err.msg), false;
+    if (o.n_skipped) {
+      if (!job->n_skipped_alns && !job->n_failed_targets) job->first_skip = o.first_skip;
+      job->n_skipped_alns += o.n_skipped;
+      job->n_failed_targets += o.failed ? 1u : 0u;
+    }
+    for (auto& pt : o.op_patches) {   // rare; synchronous
+      if (hipMemcpy((uint32_t*)job->scan.p + pt.first, pt.second.data(), pt.second.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return create_fail(ctx, HERRO_E_NO_DEVICE, "op upload failed"), false;
+    }
+    base[t] = b;
+    b.op += o.ops.size(); b.ow += o.ow.size(); b.win += o.win.size(); b.cls += o.n_cls; b.scr += o.scr_ops;
+    for (const WinDesc& wd : o.win) {
+      b.tile += (wd.lub + HERRO_TILE - 1) / HERRO_TILE;
+      b.fin += (uint64_t)HERRO_ROWS * wd.lub; b.row += wd.lub; b.pos += (uint64_t)A.W + 1;
+      b.max_cols = std::max(b.max_cols, wd.ow_cnt + 1);
+    }
+    if (b.op > 0xffffffffull) return create_fail(ctx, HERRO_E_UNSUPPORTED, "job too large (ops exceed 2^32)"), false;
+    job->alg_read_bytes += o.alg_read_bytes;
+    job->alg_op_bytes += o.alg_op_bytes;
+    job->tgt_win_off[t + 1] = (uint32_t)b.win;
+  }
+  base[A.n_targets] = b;
+  return true;
+}
+
+// ---- stage 6: the job's pinned arena — the descriptor head, then the landing zones of the counts and of the corrected bases
+bool bind_job_pin(herro_ctx* ctx, herro_job* job, const JobLayout& L, const JobTotals& tot) {
+  job->pin = arena_acquire(ctx, ctx->free_pin, L.pin_bytes, 0);
+  if (!job->pin.p) return create_fail(ctx, HERRO_E_NO_DEVICE, "out of pinned host memory for the job"), false;
+  const JobHead H = bind_head(job->pin.p, L);
+  job->ops.p = H.ops; job->ops.n = tot.op;
+  job->ow.p = H.ow; job->ow.n = tot.ow;
+  job->win.p = H.win; job->win.n = tot.win;
+  job->tile_win.p = H.tile_win; job->tile_win.n = tot.tile;
+  job->tile_r0.p = H.tile_r0; job->tile_r0.n = tot.tile;
+  const JobPinTail T = bind_pin_tail(job->pin.p, L);
+  job->h_counts = T.counts; job->h_cons_len = T.cons_len; job->h_cons_seq = T.cons_seq;
+  return true;
+}
+
+// ... and the merge in target order (host build): the bytes are copied, and the target-local indices rebased, by the pool, straight into the head of the
+// pinned arena
+void merge_targets(herro_job* job, std::vector<TargetOut>& outs, const std::vector<JobTotals>& base, uint32_t W, HostPool& hpool) {
+  hpool.run((uint32_t)outs.size(), [&](uint32_t t) {
     TargetOut& o = outs[t];
-    const Base& b = base[t];
+    const JobTotals& b = base[t];
     if (!o.ops.empty()) std::memcpy(job->ops.data() + b.op, o.ops.data(), o.ops.size() * 4);
     for (size_t i = 0; i < o.ow.size(); i++) {
       OwDesc d = o.ow[i];
@@ -1557,101 +1546,143 @@ static herro_job* job_create_from(herro_ctx* ctx, uint32_t n_targets, const uint
     }
     o = TargetOut();  // release
   });
-  job->row_elems = row_elems;
-  job->reads_gen = ctx->reads_gen;
+}
 
-  auto t_merged = tnow();
-  if (ctx->host_only) {  // test hook: the host half (descriptors) only
-    ctx->live_jobs++;
-    if (prof) {
-      auto ms = [](auto a_, auto b_) { return std::chrono::duration<double, std::milli>(b_ - a_).count(); };
-      fprintf(stderr, "herro_job_create (host half): build %.2f ms, merge %.2f (%zu windows)\n", ms(t_begin, t_built), ms(t_built, t_merged), job->win.size());
-    }
-    return job.release();
-  }
-  // ---- device arena: descriptor block first (same layout as the host arena), then every scratch / result array
-  const uint32_t n_ow = (uint32_t)job->ow.size(), n_win = (uint32_t)job->win.size();
+// ---- stage 7: the device arena and the descriptors' way into it.  ops_in_scan: the ops lie in the job's scan arena (the device scanned them).
+// BD: bound by the device pass when it built the job (null: the host did).
+bool job_to_device(herro_ctx* ctx, herro_job* job, const JobLayout& L, const JobTotals& tot, bool ops_in_scan, BuildDev* BD) {
   JobDev& J = job->J;
   J.read_words = ctx->d_words; J.read_word_off = ctx->d_word_off; J.read_p0 = ctx->d_p0; J.read_p1 = ctx->d_p1;
   J.read_qual = ctx->d_qual; J.read_qual_off = ctx->d_qual_off; J.read_qual_bytes = ctx->qual_bytes; J.read_n_words = ctx->n_words;
   J.ln_table = ctx->d_ln; J.ln_table_n = ctx->ln_n;
   J.prof = ctx->d_prof;
-  J.n_ow = n_ow; J.n_win = n_win; J.n_cls = n_cls;
-  J.n_tiles = (uint32_t)job->tile_win.size(); J.window_size = W; J.nw = (W + 31) / 32; J.max_cols = max_cols;
+  J.n_ow = (uint32_t)tot.ow; J.n_win = (uint32_t)tot.win; J.n_cls = (uint32_t)tot.cls;
+  J.n_tiles = (uint32_t)tot.tile; J.window_size = job->W; J.nw = (job->W + 31) / 32; J.max_cols = tot.max_cols;
   { const char* e = getenv("HERRO_DEBUG_CDIR_OVERFLOW"); J.dbg_flags = (e && atoi(e)) ? 1u : 0u; }
-  cur = desc_bytes;
-  const size_t o_cw = take(((uint64_t)n_ow + 1) * J.nw * 12), o_cwd = take(((uint64_t)n_ow + 1) * J.nw * 4), o_iev = take(scr_ops * 16), o_ins_cnt = take((uint64_t)n_ow * 4);
-  const size_t o_ocol = take((uint64_t)n_ow * 16);
-  const size_t o_keep = take(n_ow), o_acc = take((uint64_t)n_ow * 4), o_ttot = take((uint64_t)n_ow * 4);
-  const size_t o_slot = take((uint64_t)n_ow * 4), o_rqid = take((uint64_t)n_ow * 4), o_sel = take((uint64_t)n_win * 32 * 4);
-  const size_t o_ctab = take((uint64_t)n_win * 32 * sizeof(CTab)), o_chdr = take((size_t)J.n_tiles * 8), o_tnsup = take((size_t)J.n_tiles * 4);
-  const size_t o_tev = take((scr_ops + 2ull * n_ow) * 16), o_tileev = take((size_t)J.n_tiles * 8);
-  const size_t o_dcounts = take((uint64_t)n_win * 16 + 16);
-  const size_t o_rop = take(pos_elems * 4), o_rmap = take(row_elems * 4);
-  const size_t o_cseq = take(row_elems), o_ctmp = take(row_elems), o_clen = take((uint64_t)n_win * 4);
-  const size_t o_srow = take(row_elems * 4), o_spi = take(row_elems * 4);
-  const size_t o_finb = take(fin_bytes), o_finq = take(fin_bytes), o_nd = take((uint64_t)n_cls * 8);
-  const size_t o_vpl = take((uint64_t)n_win * 4 * J.nw * 4), o_snr = take(row_elems * 4);
-  const size_t dev_bytes = cur;
-  job->dev = arena_acquire(ctx, ctx->free_dev, dev_bytes, 1);
-  auto give_back = [&]() {
-    std::lock_guard<std::mutex> lk(ctx->arena_mu);
-    if (job->dev.p) ctx->free_dev.push_back(job->dev);
-    if (job->pin.p) ctx->free_pin.push_back(job->pin);
-    job->dev = Arena{}; job->pin = Arena{};
-  };
-  if (!job->dev.p) { give_back(); return fail(HERRO_E_NO_DEVICE, "out of device memory for the job (" + std::to_string(dev_bytes >> 20) + " MiB)"); }
-  unsigned char* db = (unsigned char*)job->dev.p;
-  J.ops = ds ? (const uint32_t*)job->scan.p : (const uint32_t*)(db + o_ops); J.ow = (const OwDesc*)(db + o_ow); J.win = (const WinDesc*)(db + o_win);
-  J.tile_win = (const uint32_t*)(db + o_tw); J.tile_r0 = (const uint32_t*)(db + o_tr);
-  J.cw = (PlaneRec*)(db + o_cw); J.cwd = (uint32_t*)(db + o_cwd); J.iev = (uint4*)(db + o_iev); J.ins_cnt = (uint32_t*)(db + o_ins_cnt); J.ocol = (uint4*)(db + o_ocol);
-  J.ow_keep = (uint8_t*)(db + o_keep); J.ow_acc = (float*)(db + o_acc); J.ow_ttotal = (uint32_t*)(db + o_ttot);
-  J.slot_ow = (uint32_t*)(db + o_slot); J.rank_qid = (uint32_t*)(db + o_rqid); J.sel_ow = (uint32_t*)(db + o_sel);
-  J.ctab = (CTab*)(db + o_ctab); J.chdr2 = (uint2*)(db + o_chdr); J.tile_nsup = (uint32_t*)(db + o_tnsup);
-  J.tev = (uint4*)(db + o_tev); J.tile_ev = (uint2*)(db + o_tileev);
-  job->d_counts = (uint32_t*)(db + o_dcounts);
-  J.win_Lf = job->d_counts; J.win_nsup = job->d_counts + n_win; J.win_nkept = job->d_counts + 2ull * n_win;
-  J.win_rfbase = job->d_counts + 3ull * n_win; J.rf_alloc = job->d_counts + 4ull * n_win;
+  job->dev = arena_acquire(ctx, ctx->free_dev, L.dev_bytes, 1);
+  if (!job->dev.p) return create_fail(ctx, HERRO_E_NO_DEVICE, "out of device memory for the job (" + std::to_string(L.dev_bytes >> 20) + " MiB)"), false;
+  bind_job_dev(J, job->dev.p, L, tot.win);
+  if (ops_in_scan) J.ops = (const uint32_t*)job->scan.p;
+  job->d_counts = J.win_Lf;
   J.rf = nullptr; J.rf_cap = 0; J.rf_half = 0;
-  J.row_of_pos2 = (uint32_t*)(db + o_rop); J.rowmap2 = (uint32_t*)(db + o_rmap);
-  J.cons_seq = (uint8_t*)(db + o_cseq); J.cons_tmp = (uint8_t*)(db + o_ctmp); J.cons_len = (uint32_t*)(db + o_clen);
-  J.sup_row = (uint32_t*)(db + o_srow); J.sup_pi = (uint32_t*)(db + o_spi);
-  J.fin_b = (uint8_t*)(db + o_finb); J.fin_q = (uint8_t*)(db + o_finq); J.nd = (uint32_t*)(db + o_nd);
-  J.vpl = (uint32_t*)(db + o_vpl); J.sup_nr = (uint32_t*)(db + o_snr);
   hipError_t e;
-  if (dev_built) {
+  if (BD) {
     // the descriptors are written where they are read (build_dev.hip, behind the scan on the prep stream); the window descriptors come down — the host hands
     // windows out by them — and the context's stream waits for the event, so the kernels of herro_job_featurize queue behind the build in stream order
-    BD.ow = (OwDesc*)(db + o_ow); BD.win = (WinDesc*)(db + o_win); BD.tile_win = (uint32_t*)(db + o_tw); BD.tile_r0 = (uint32_t*)(db + o_tr);
-    launch_build_phase2(BD, ctx->prep_stream);
+    bind_build_head(*BD, bind_head(job->dev.p, L));
+    launch_build_phase2(*BD, ctx->prep_stream);
     e = hipGetLastError();
-    if (e == hipSuccess && n_win) e = hipMemcpyAsync(job->win.data(), db + o_win, (size_t)n_win * sizeof(WinDesc), hipMemcpyDeviceToHost, ctx->prep_stream);
+    if (e == hipSuccess && J.n_win) e = hipMemcpyAsync(job->win.data(), BD->win, (size_t)J.n_win * sizeof(WinDesc), hipMemcpyDeviceToHost, ctx->prep_stream);
     if (e == hipSuccess) e = hipEventRecord(ctx->prep_ev, ctx->prep_stream);
     if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->prep_ev, 0);
     if (e == hipSuccess) e = hipEventSynchronize(ctx->prep_ev);
     job->dev_built = true;
   } else {
-    // one copy, pinned -> device, asynchronous on the context stream: the kernels of herro_job_featurize queue behind it
-    // in stream order, nobody waits here
-    e = hipMemcpyAsync(db, job->pin.p, desc_bytes, hipMemcpyHostToDevice, ctx->stream);
+    // one copy, pinned -> device, asynchronous on the context stream: the head has the same layout in both arenas.  The kernels of herro_job_featurize
+    // queue behind it in stream order, nobody waits here
+    e = hipMemcpyAsync(job->dev.p, job->pin.p, L.desc_bytes, hipMemcpyHostToDevice, ctx->stream);
   }
   if (e == hipSuccess) e = hipEventCreateWithFlags(&job->ev_counts, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&job->ev_blob, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(ctx->stream);
-    if (job->ev_counts) (void)hipEventDestroy(job->ev_counts);
-    if (job->ev_blob) (void)hipEventDestroy(job->ev_blob);
-    give_back();
-    return fail(HERRO_E_NO_DEVICE, std::string("descriptor upload failed: ") + hipGetErrorString(e));
+  if (e == hipSuccess) return true;
+  (void)hipStreamSynchronize(ctx->stream);
+  return create_fail(ctx, HERRO_E_NO_DEVICE, std::string("descriptor upload failed: ") + hipGetErrorString(e)), false;
+}
+}  // namespace
+
+// herro_job_create (src == nullptr: the ops come as CIGAR text) and the direct path of herro_job_create_aligned (src: they are on the device; the caller
+// has checked that the context builds on the device).  *unsettled is raised, with nothing reported, when the direct path does not settle the job: the
+// caller then goes through the text of the job's ops.  A job that is let go of half way returns what it holds (~herro_job).
+static herro_job* job_create_from(herro_ctx* ctx, uint32_t n_targets, const uint32_t* rids, const uint64_t* aln_off,
+                                  const herro_alignment* alns, uint32_t W, const OpsSrc* src, bool* unsettled) {
+  if (!ctx) return nullptr;
+  ctx->create_code = HERRO_OK;
+  if (!ctx->d_words && !ctx->host_only) return create_fail(ctx, HERRO_E_STATE, "herro_set_reads must be called first");
+  if (W < 16 || W > HERRO_MAX_WINDOW) return create_fail(ctx, HERRO_E_UNSUPPORTED, "window_size must be in [16, 8192]");
+  if (n_targets && (!rids || !aln_off)) return create_fail(ctx, HERRO_E_INVALID, "null argument");
+  if (!ctx->host_only && hipSetDevice(ctx->device) != hipSuccess) return create_fail(ctx, HERRO_E_NO_DEVICE, "hipSetDevice failed");
+  const uint64_t a0 = n_targets ? aln_off[0] : 0;
+  const CreateArgs A{ctx, n_targets, rids, aln_off, alns, W, src, a0, n_targets ? aln_off[n_targets] - a0 : 0};
+
+  const bool prof = getenv("HERRO_HOST_PROFILE") != nullptr;
+  ProfSpan span_(ctx, "create");
+  CreateClock clk;
+  clk.begin = clk.scanned = HostClock::now();
+  auto job = std::make_unique<herro_job>();
+  job->ctx = ctx;
+  job->W = W;
+  job->n_targets = n_targets;
+  job->tgt_win_off.assign(n_targets + 1, 0);
+  HostPool& hpool = host_pool(ctx);
+
+  // ---- the CIGAR text goes to the GPU first (cigar_dev.hip): one kernel (a workgroup per alignment) writes the binary ops into the job's op array and
+  // returns, per alignment, the totals and the ops that reach a window boundary.  Device build (round 6): what needs no CIGAR is settled by the pre-pass
+  // and goes up beside the text; anything it would have to report sends the job down the host path, which words it.
+  ArenaHold stage{ctx, &ctx->free_stage, 0};
+  JobPrepass P;
+  BuildDev BD{};
+  BuildTotals btot{};
+  DevScanView dsv{nullptr, nullptr, nullptr};
+  bool scanned = false, dev_built = false;
+  if (!ctx->host_only && ctx->dev_scan && A.nA) {
+    ScanPlan S;
+    if (!plan_scan(A, S)) return nullptr;
+    const bool try_dev = ctx->dev_build && job_prepass(ctx, hpool, n_targets, rids, aln_off, alns, W, job->tgt_win_off, P);
+    if (src && !try_dev) { *unsettled = true; return nullptr; }
+    const ScanLayout SL = scan_layout(A.nA, n_targets, P.n_win, S.txt, S.cutn, S.opn, try_dev);
+    stage.a = arena_acquire(ctx, ctx->free_stage, SL.blk_bytes, 0);
+    job->scan = arena_acquire(ctx, ctx->free_scan, SL.ops_bytes + SL.dev_blk_bytes, 1);
+    if (!stage.a.p || !job->scan.p)
+      return create_fail(ctx, HERRO_E_NO_DEVICE, "out of memory for the CIGAR scan (" + std::to_string((SL.ops_bytes + SL.dev_blk_bytes) >> 20) + " MiB)");
+    const ScanView hs = bind_scan_host(stage.a.p, SL), dv = bind_scan_dev(job->scan.p, SL);
+    stage_scan(A, S, P, SL, hs, hpool);
+    clk.staged = HostClock::now();
+    switch (device_pass(A, S, SL, hs, dv, P.n_win, BD, btot, prof, clk)) {
+      case DevPass::FAILED: return nullptr;
+      case DevPass::UNSETTLED: *unsettled = true; return nullptr;
+      case DevPass::BUILT: dev_built = true; break;
+      case DevPass::HOST_BUILDS: break;
+    }
+    dsv = DevScanView{hs.in, hs.out, hs.cuts};
+    scanned = true;
+    job->scan_ops = S.opn;
+    clk.scanned = HostClock::now();
   }
-  if (prof) {
-    auto ms = [](auto a_, auto b_) { return std::chrono::duration<double, std::milli>(b_ - a_).count(); };
-    fprintf(stderr, "herro_job_create: scan %.2f ms, build %.2f, merge %.2f, arena + enqueue %.2f (%u windows, %zu MiB device)\n", ms(t_begin, t_scanned),
-            ms(t_scanned, t_built), ms(t_built, t_merged), ms(t_merged, tnow()), n_win, dev_bytes >> 20);
+  std::vector<TargetOut> outs;
+  std::vector<JobTotals> base;   // host build: per target, what lies in front of it
+  JobTotals tot;
+  if (dev_built) {
+    clk.built = HostClock::now();
+    adopt_device_build(job.get(), btot, P);
+    tot = job_totals(btot, P.n_win, P.n_cls, W);
+  } else {
+    if (!host_build(A, scanned ? &dsv : nullptr, hpool, job.get(), outs, base, clk)) return nullptr;
+    tot = base[n_targets];
+  }
+  // the windows' event slices live behind scr_ops + 2 * n_ow slots and are indexed with 32 bits on the device (WinDesc::ev_off -> CTab::ev_off)
+  if (tot.scr + 2ull * tot.ow > 0xffffffffull) return create_fail(ctx, HERRO_E_UNSUPPORTED, "job too large (op scratch exceeds 2^32)");
+  // (what was left out is reported by herro_job_skipped; the error slot is for errors only)
+  const JobLayout L = job_layout(tot, W);
+  if (!bind_job_pin(ctx, job.get(), L, tot)) return nullptr;
+  if (!dev_built) merge_targets(job.get(), outs, base, W, hpool);
+  job->row_elems = tot.row;
+  job->reads_gen = ctx->reads_gen;
+  clk.merged = HostClock::now();
+  if (ctx->host_only) {  // test hook: the host half (descriptors) only
+    if (prof) fprintf(stderr, "herro_job_create (host half): build %.2f ms, merge %.2f (%zu windows)\n", ms_between(clk.begin, clk.built), ms_between(clk.built, clk.merged), job->win.size());
+  } else {
+    if (!job_to_device(ctx, job.get(), L, tot, scanned, dev_built ? &BD : nullptr)) return nullptr;
+    if (prof)
+      fprintf(stderr, "herro_job_create: scan %.2f ms, build %.2f, merge %.2f, arena + enqueue %.2f (%u windows, %zu MiB device)\n", ms_between(clk.begin, clk.scanned),
+              ms_between(clk.scanned, clk.built), ms_between(clk.built, clk.merged), ms_between(clk.merged, HostClock::now()), job->J.n_win, (size_t)(L.dev_bytes >> 20));
   }
   ctx->live_jobs++;
-  scan_ret.armed = false;   // the job keeps its op array
   return job.release();
+}
+
+herro_job* herro_job_create(herro_ctx* ctx, uint32_t n_targets, const uint32_t* rids, const uint64_t* aln_off,
+                            const herro_alignment* alns, uint32_t W) {
+  return job_create_from(ctx, n_targets, rids, aln_off, alns, W, nullptr, nullptr);
 }
 
 int herro_job_create_status(const herro_ctx* ctx) { return ctx ? ctx->create_code.load() : HERRO_E_INVALID; }
@@ -1669,28 +1700,10 @@ void herro_job_free(herro_job* job) {
   if (ctx->live_jobs.load()) ctx->live_jobs--;
   if (job->pending) { job->pending = false; ctx->n_pending--; }   // featurized, never inferred
   ctx->sib_suspects.erase(std::remove(ctx->sib_suspects.begin(), ctx->sib_suspects.end(), job), ctx->sib_suspects.end());
-  if (ctx->host_only) {
-    std::lock_guard<std::mutex> lk(ctx->arena_mu);
-    if (job->pin.p) { if (ctx->free_pin.size() < 6) ctx->free_pin.push_back(job->pin); else std::free(job->pin.p); }
-    delete job;
-    return;
-  }
+  if (ctx->host_only) { delete job; return; }
   ProfSpan span_(ctx, "destroy");
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);   // nothing of this job is in flight once its memory is recycled
-  {
-    std::lock_guard<std::mutex> lk(ctx->arena_mu);
-    // keep a handful of arenas for the next jobs (the bench cycles 2-4 jobs per context); the rest goes back to HIP
-    if (job->dev.p) { if (ctx->free_dev.size() < 6) ctx->free_dev.push_back(job->dev); else (void)hipFree(job->dev.p); }
-    if (job->scan.p) { if (ctx->free_scan.size() < 6) ctx->free_scan.push_back(job->scan); else (void)hipFree(job->scan.p); }
-    if (job->pin.p) { if (ctx->free_pin.size() < 6) ctx->free_pin.push_back(job->pin); else (void)hipHostFree(job->pin.p); }
-  }
-  small_release(ctx, job->a_logits);
-  small_release(ctx, job->a_bdesc);
-  small_release(ctx, job->a_supoff);
-  small_release(ctx, job->a_supoff_dev);
-  if (job->ev_counts) (void)hipEventDestroy(job->ev_counts);
-  if (job->ev_blob) (void)hipEventDestroy(job->ev_blob);
   delete job;
 }
 
@@ -1787,12 +1800,11 @@ static int ensure_logits(herro_job* job, uint64_t rows) {
   if (job->d_info && job->logit_cap >= rows) return HERRO_OK;
   if (job->d_info) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); small_release(ctx, job->a_logits); job->d_info = job->d_base = nullptr; }
   job->logit_cap = std::max<uint64_t>(rows + rows / 8, 1);
-  const uint64_t o_base = (job->logit_cap * 4 + 255) & ~(uint64_t)255, o_rfq = (o_base + job->logit_cap * 20 + 255) & ~(uint64_t)255;
-  job->a_logits = small_acquire(ctx, o_rfq + job->logit_cap * HERRO_ROWS * 16 + 256);   // 16-byte receptive-field records: 8 tokens + 8 qualities
+  const LogitsLayout L = logits_layout(job->logit_cap);
+  job->a_logits = small_acquire(ctx, L.bytes);
   if (!job->a_logits.p) { ctx->err = "out of device memory for the logits"; return HERRO_E_NO_DEVICE; }
-  job->d_info = (float*)job->a_logits.p;
-  job->d_base = (float*)((unsigned char*)job->a_logits.p + o_base);
-  job->d_rfq = (uint8_t*)job->a_logits.p + o_rfq;
+  const LogitsView V = bind_logits(job->a_logits.p, L);
+  job->d_info = V.info; job->d_base = V.base; job->d_rfq = V.rfq;
   job->gather = RfGather{};   // whatever was gathered lived in the old block
   return HERRO_OK;
 }
@@ -2701,38 +2713,20 @@ int64_t herro_debug_job_array(herro_job* job, int which, const void** ptr, uint3
   switch (which) {
     case 0:
       *elem_bytes = 4;
-      if (job->scan.p) {   // ops written by the device scan: the whole (gapped) op array, so that OwDesc::op_begin indexes it
-        job->dbg_ops.resize(job->scan_ops);
-        if (hipSetDevice(job->ctx->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-            hipMemcpy(job->dbg_ops.data(), job->scan.p, job->scan_ops * 4, hipMemcpyDeviceToHost) != hipSuccess) return HERRO_E_NO_DEVICE;
-        *ptr = job->dbg_ops.data();
-        return (int64_t)job->dbg_ops.size();
-      }
+      // ops written by the device scan: the whole (gapped) op array, so that OwDesc::op_begin indexes it
+      if (job->scan.p) return debug_fetch(job, job->dbg_ops, job->scan.p, job->scan_ops, ptr);
       *ptr = job->ops.data();
       return (int64_t)job->ops.size();
     case 1:
       *elem_bytes = sizeof(OwDesc);
-      if (job->dev_built) {
-        job->dbg_ow.resize(job->J.n_ow);
-        if (hipSetDevice(job->ctx->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-            (job->J.n_ow && hipMemcpy(job->dbg_ow.data(), job->J.ow, (size_t)job->J.n_ow * sizeof(OwDesc), hipMemcpyDeviceToHost) != hipSuccess)) return HERRO_E_NO_DEVICE;
-        *ptr = job->dbg_ow.data();
-        return (int64_t)job->dbg_ow.size();
-      }
+      if (job->dev_built) return debug_fetch(job, job->dbg_ow, job->J.ow, job->J.n_ow, ptr);
       *ptr = job->ow.data();
       return (int64_t)job->ow.size();
     case 2: *ptr = job->win.data(); *elem_bytes = sizeof(WinDesc); return (int64_t)job->win.size();
     case 3:
     case 4:
       *elem_bytes = 4;
-      if (job->dev_built) {
-        std::vector<uint32_t>& v = which == 3 ? job->dbg_tw : job->dbg_tr;
-        v.resize(job->J.n_tiles);
-        if (hipSetDevice(job->ctx->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-            (job->J.n_tiles && hipMemcpy(v.data(), which == 3 ? job->J.tile_win : job->J.tile_r0, (size_t)job->J.n_tiles * 4, hipMemcpyDeviceToHost) != hipSuccess)) return HERRO_E_NO_DEVICE;
-        *ptr = v.data();
-        return (int64_t)v.size();
-      }
+      if (job->dev_built) return debug_fetch(job, which == 3 ? job->dbg_tw : job->dbg_tr, which == 3 ? job->J.tile_win : job->J.tile_r0, job->J.n_tiles, ptr);
       *ptr = which == 3 ? job->tile_win.data() : job->tile_r0.data();
       return (int64_t)(which == 3 ? job->tile_win.size() : job->tile_r0.size());
     case 5: *ptr = job->tgt_win_off.data(); *elem_bytes = 4; return (int64_t)job->tgt_win_off.size();
@@ -2884,11 +2878,7 @@ int herro_job_stats(herro_job* job, uint64_t* out) {
 herro_job* herro_job_create_aligned(herro_ctx* ctx, uint32_t n_targets, const uint32_t* rids, const uint64_t* aln_off, const uint32_t* rec,
                                     const herro_aligned_dev* a, uint32_t W) {
   if (!ctx) return nullptr;
-  auto fail = [&](int code, const std::string& m) -> herro_job* {
-    ctx->err = m + " [code " + std::to_string(code) + "]";
-    ctx->create_code = code;
-    return nullptr;
-  };
+  auto fail = [&](int code, const std::string& m) { return create_fail(ctx, code, m); };
   ctx->create_code = HERRO_OK;
   if (!a) return fail(HERRO_E_INVALID, "herro_job_create_aligned: null handle");
   if (n_targets && (!rids || !aln_off)) return fail(HERRO_E_INVALID, "null argument");

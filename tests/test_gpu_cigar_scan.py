@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 import gpu_common as G
-from herro_amd import api, synth
-from test_host_job_layout import _hand_alignment
+from herro_amd import api, model_io, synth
+from test_host_job_layout import _hand_alignment, failed_creates_then_a_good_one
 
 pytestmark = pytest.mark.gpu
 
@@ -88,3 +88,39 @@ def test_device_scan_text_corner_cases():
     assert jd.skipped() == jh.skipped() == (0, 0)
     _same_jobs(hc, jd, jh)
     jd.close(); jh.close(); hc.close()
+
+
+def test_failed_creates_leave_nothing_behind_on_the_device():
+    """the device twin of tests/test_host_job_layout.py's: eight creates in a row fail on malformed text (the device scan flags it,
+    the host words it; each lets go of its scan arena and staging block), then the good job — its descriptors, logits and FASTA are
+    those of the same job on a fresh context"""
+    W = 64
+    sb = synth.generate(2, 300, 8, seed=11, flank_min=10, flank_max=40, p_snp=0.05)   # (the variants give the windows informative rows)
+    used = G.ctx()
+    fresh = api.Context(0)
+    fresh.load_model(model_io.default_model_file(G.CACHE)[0])
+    fresh.set_precision(api.DEFAULT_PRECISION)
+    out = []
+    for c in (fresh, used):
+        G.load_synth(c, sb)
+        job = api.job_from_synth(c, sb, W) if c is fresh else failed_creates_then_a_good_one(c, sb, W)
+        arrays = c.job_arrays(job)
+        job.featurize()
+        job.infer(64, 1)
+        job.consensus()
+        logits = [job.logits(w) for w in range(job.n_windows)]
+        fasta = [job.consensus_fasta(t, "read%d" % t) for t in range(sb.n_targets)]
+        out.append((arrays, logits, fasta))
+        job.close()
+    fresh.close()
+    (a0, l0, f0), (a1, l1, f1) = out
+    assert len(a0["ow"]) > 0 and len(a0["win"]) == 10 and sum(len(i) for i, _ in l0) > 0
+    for k in a0:
+        if k != "ops":      # the scan's op array has gaps behind every alignment's ops that nobody writes or reads
+            assert np.array_equal(a0[k], a1[k]), k
+    for d in a0["ow"]:
+        lo, hi = int(d["op_begin"]), int(d["op_begin"]) + int(d["op_cnt"])
+        assert np.array_equal(a0["ops"][lo:hi], a1["ops"][lo:hi])
+    for (i0, b0), (i1, b1) in zip(l0, l1):
+        assert np.array_equal(i0, i1) and np.array_equal(b0, b1)
+    assert f0 == f1

@@ -463,3 +463,35 @@ def test_two_threads_create_jobs_on_one_context():
     for t in th:
         t.join()
     assert not errs and not bad
+
+
+def failed_creates_then_a_good_one(c, sb, W, n_failed=8):
+    """n_failed creates in a row that fail on a malformed CIGAR (one more than a free list keeps), then the good create
+    over the same alignments: the good job.  Shared with tests/test_gpu_cigar_scan.py."""
+    n = int(sb.tgt_aln_off[sb.n_targets])
+    rows, off = sb.aln[:n], sb.tgt_aln_off[:sb.n_targets + 1].astype(np.uint64)
+    good = [sb.cigar(a) for a in range(n)]
+    bad = list(good)
+    bad[n - 1] = good[n - 1].replace(b"M", b"X", 1)
+    for _ in range(n_failed):
+        with pytest.raises(api.HerroError) as e:
+            c.create_job(sb.tgt_rid, rows, off, bad, W)
+        assert "Unexpected cigar operation" in str(e.value)
+    return c.create_job(sb.tgt_rid, rows, off, good, W)
+
+
+def test_failed_creates_leave_nothing_behind():
+    """a create that fails half way lets go of the job, which returns what it held: the job created after eight
+    failures carries the descriptors of the same create on a fresh context, element for element"""
+    W = 64
+    sb = synth.generate(2, 300, 5, seed=11, flank_min=10, flank_max=40)
+    lens = (sb.off[1:] - sb.off[:-1]).astype(np.uint32)
+    fresh, used = api.HostContext(lens), api.HostContext(lens)
+    jf = api.job_from_synth(fresh, sb, W)
+    ju = failed_creates_then_a_good_one(used, sb, W)
+    want, got = fresh.job_arrays(jf), used.job_arrays(ju)
+    assert len(want["ow"]) > 0 and len(want["win"]) == 10
+    assert got.keys() == want.keys()
+    for k in want:
+        assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), k
+    jf.close(); ju.close(); fresh.close(); used.close()
