@@ -53,7 +53,7 @@ EXPORTS = [
     "herro_find_adapters", "herro_adapter_hits_n", "herro_adapter_hits_data", "herro_adapter_hits_off", "herro_adapter_hits_free", "herro_debug_set_adapter_cap",
     "herro_trim_plan", "herro_trim_n_pieces", "herro_trim_pieces", "herro_trim_piece_off", "herro_trim_stats", "herro_trim_free",
     "herro_reads_create", "herro_reads_cut", "herro_reads_cut_names",
-    "herro_store_cut", "herro_debug_store_copy",
+    "herro_store_cut", "herro_debug_store_copy", "herro_debug_scan_u32", "herro_debug_radix_sort", "herro_debug_offsets64",
     "herro_cluster_graph", "herro_pairs_cluster", "herro_clusters_n_parts", "herro_clusters_n_reads", "herro_clusters_part", "herro_clusters_rank",
     "herro_clusters_comp", "herro_clusters_level", "herro_clusters_stats", "herro_clusters_part_stats", "herro_clusters_mask", "herro_clusters_free",
     "herro_job_fasta_dev", "herro_fasta_text_data", "herro_fasta_text_len", "herro_fasta_text_target_end", "herro_fasta_text_stats", "herro_fasta_text_free",
@@ -378,6 +378,9 @@ def lib():
             L.herro_store_cut.argtypes = [vp, u64, vp, vp]
             L.herro_debug_store_copy.restype = C.c_int64
             L.herro_debug_store_copy.argtypes = [vp, C.c_int, vp, u64]
+            L.herro_debug_scan_u32.argtypes = [vp, vp, u64, vp, vp]
+            L.herro_debug_radix_sort.argtypes = [vp, vp, vp, u64, vp, u32, vp]
+            L.herro_debug_offsets64.argtypes = [vp, vp, u64, vp, vp]
         except AttributeError:
             if not os.environ.get("HERRO_LIB"):
                 raise
@@ -712,6 +715,31 @@ class Context:
                 self._chk(got)
             out[name] = a
         return out
+
+    def debug_scan_u32(self, values):
+        """Test hook (herro_debug_scan_u32): the front end's exclusive scan of u32 on `values` -> (out u32 [n + 1], guard_hits)."""
+        v = np.ascontiguousarray(values, np.uint32).reshape(-1)
+        out, hits = np.zeros(len(v) + 1, np.uint32), C.c_uint32(0xFFFFFFFF)
+        self._chk(self._l.herro_debug_scan_u32(self.h, v.ctypes.data if len(v) else None, len(v), out.ctypes.data, C.byref(hits)))
+        return out, int(hits.value)
+
+    def debug_radix_sort(self, keys, pays, shifts):
+        """Test hook (herro_debug_radix_sort): the front end's stable LSD radix sort by the 8-bit digits at `shifts` -> (keys, pays, guard_hits),
+        copies of the arrays (*k0, *p0) name afterwards."""
+        k, p = np.array(keys, np.uint64).reshape(-1), np.array(pays, np.uint64).reshape(-1)
+        if len(k) != len(p):
+            raise ValueError("one payload per key")
+        sh, hits = np.ascontiguousarray(shifts, np.uint32).reshape(-1), C.c_uint32(0xFFFFFFFF)
+        self._chk(self._l.herro_debug_radix_sort(self.h, k.ctypes.data if len(k) else None, p.ctypes.data if len(k) else None, len(k),
+                                                 sh.ctypes.data if len(sh) else None, len(sh), C.byref(hits)))
+        return k, p, int(hits.value)
+
+    def debug_offsets64(self, nbytes):
+        """Test hook (herro_debug_offsets64): the device FASTA's 64-bit offsets of pieces of `nbytes` bytes -> (off u64 [n + 1], guard_hits)."""
+        b = np.ascontiguousarray(nbytes, np.uint64).reshape(-1)
+        off, hits = np.zeros(len(b) + 1, np.uint64), C.c_uint32(0xFFFFFFFF)
+        self._chk(self._l.herro_debug_offsets64(self.h, b.ctypes.data if len(b) else None, len(b), off.ctypes.data, C.byref(hits)))
+        return off, int(hits.value)
 
     def load_model(self, path: str):
         self._chk(self._l.herro_load_model(self.h, path.encode()))

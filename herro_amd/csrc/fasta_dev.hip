@@ -283,6 +283,26 @@ struct Carver {
 #define FA_SCAN(in, n, out) do { if (ovl_scan_u32(in, n, out, d_partial, st, err) != OVL_OK) { (void)hipStreamSynchronize(st); err = "herro_job_fasta_dev: " + err; return FASTA_HIP; } } while (0)
 #define FA_MEM(ptr, what) do { if (!(ptr)) { (void)hipStreamSynchronize(st); err = std::string("herro_job_fasta_dev: out of memory for ") + what; return FASTA_HIP; } } while (0)
 
+// The 64-bit offsets of D.P pieces out of two 32-bit scans (the stages' "(scans)" of the pieces): lo_in / hi_in hold the halves of every piece's
+// bytes; hi_in takes the carries.  partial: ovl_scan_partials(D.P) entries.  Queued on st.
+static int offsets64(const FaDev& D, uint32_t* d_partial, hipStream_t st, std::string& err) {
+  const uint32_t P = D.P;
+  FA_SCAN(D.lo_in, P, D.lo);
+  k_fa_carry<<<blocks(P), 256, 0, st>>>(D);
+  FA_TRY("k_fa_carry launch", hipGetLastError());
+  FA_SCAN(D.hi_in, P, D.hi);
+  k_fa_off<<<blocks((uint64_t)P + 1), 256, 0, st>>>(D);
+  FA_TRY("k_fa_off launch", hipGetLastError());
+  return FASTA_OK;
+}
+
+int fasta_offsets64(uint32_t* lo_in, uint32_t* hi_in, uint32_t n, uint32_t* lo, uint32_t* hi, uint64_t* off, uint32_t* partial, hipStream_t st,
+                    std::string& err) {
+  FaDev D{};
+  D.P = n; D.lo_in = lo_in; D.hi_in = hi_in; D.lo = lo; D.hi = hi; D.off = off;
+  return offsets64(D, partial, st, err);
+}
+
 int fasta_text_dev(const JobDev& J, uint64_t row_elems, const uint32_t* tgt_win_off, uint32_t n_targets, const FastaNames& names, const ChopRule& R,
                    uint64_t chunk, hipStream_t st, const FastaMem& mem, char** text, uint64_t* text_len, std::vector<uint64_t>& target_end,
                    FastaStats& stats, std::string& err) {
@@ -357,12 +377,7 @@ int fasta_text_dev(const JobDev& J, uint64_t row_elems, const uint32_t* tgt_win_
   lay_b(cb);
   k_fa_piece<<<blocks(P), 256, 0, st>>>(D);
   FA_TRY("k_fa_piece launch", hipGetLastError());
-  FA_SCAN(D.lo_in, P, D.lo);
-  k_fa_carry<<<blocks(P), 256, 0, st>>>(D);
-  FA_TRY("k_fa_carry launch", hipGetLastError());
-  FA_SCAN(D.hi_in, P, D.hi);
-  k_fa_off<<<blocks((uint64_t)P + 1), 256, 0, st>>>(D);
-  FA_TRY("k_fa_off launch", hipGetLastError());
+  if (int rc = offsets64(D, d_partial, st, err)) return rc;
   k_fa_tgt<<<blocks(n_targets), 256, 0, st>>>(D);
   FA_TRY("k_fa_tgt launch", hipGetLastError());
   uint64_t T = 0;

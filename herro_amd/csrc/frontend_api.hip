@@ -3,7 +3,8 @@
 // writer (herro_aligned_dev_paf, herro_pairs_paf, herro_pairs_write_alns) herro_set_seed_rescue and the test hooks herro_debug_sketch, herro_debug_occ_census and herro_debug_seed_rescue.  Host C++ (compiled by
 // hipcc) over overlap_dev.hip, align_dev.hip and paf_dev.hip; contexts, the model and jobs are herro_api.hip.  Ahead of them all, for raw reads:
 // herro_find_adapters and its handle, over adapter_dev.hip (the plan and the cut are host code: fastx.cpp), and herro_store_cut with its test hook
-// herro_debug_store_copy, over store_dev.hip: the store cut to the plan's pieces on the device.  Behind the finder: herro_cluster_graph, herro_pairs_cluster and
+// herro_debug_store_copy, over store_dev.hip: the store cut to the plan's pieces on the device.  The primitives every device stage stands on have hooks of
+// their own: herro_debug_scan_u32, herro_debug_radix_sort (overlap_dev.hip) and herro_debug_offsets64 (fasta_dev.hip's offset join).  Behind the finder: herro_cluster_graph, herro_pairs_cluster and
 // herro_clusters_*, over cluster_dev.hip (the checks and the part rule are host code: cluster_plan.h): the reads partitioned by their overlap graph.
 #include <hip/hip_runtime.h>
 
@@ -19,6 +20,7 @@
 #include "cluster_dev.h"
 #include "cluster_plan.h"
 #include "dev_bufs.h"
+#include "fasta_dev.h"
 #include "overlap_dev.h"
 #include "paf_dev.h"
 #include "store_dev.h"
@@ -1280,6 +1282,143 @@ int64_t herro_debug_store_copy(herro_ctx* ctx, int which, void* out, uint64_t ca
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (bytes[which]) HIP_TRY(ctx, hipMemcpy(out, src[which], bytes[which], hipMemcpyDeviceToHost));
   return (int64_t)bytes[which];
+}
+
+// ---- test hooks: the shared scan and radix sort (overlap_dev.hip) and the 64-bit offset join (fasta_dev.hip) on arrays of the caller's ----------
+// The arrays are carved from ONE device block, as fasta_dev.hip's Carver and cluster_dev.hip's Bufs lay theirs next to live arrays, every one
+// exactly as large as its client sizes it and with GUARD_WORDS words of a fixed pattern directly behind it: a store one entry past an array or past
+// ovl_scan_partials(n) / ovl_sort_scratch(n) lands in a guard and is counted, where in a client it would change a neighbour without any fault.
+namespace {
+constexpr uint32_t GUARD_WORDS = 64;
+inline uint32_t guard_word(uint32_t i) { return 0xA5C3E1F0u ^ (i * 0x01010101u); }
+
+struct Guarded {
+  struct Part { uint64_t at, bytes; };
+  std::vector<Part> parts;
+  uint64_t total = 0;
+  char* base = nullptr;
+  size_t add(uint64_t bytes) {                       // an array of `bytes` (a multiple of 4) at an 8-byte boundary, its guard behind it
+    total = (total + 7) & ~7ull;
+    parts.push_back(Part{total, bytes});
+    total += bytes + 4ull * GUARD_WORDS;
+    return parts.size() - 1;
+  }
+  uint32_t* u32(size_t i) const { return (uint32_t*)(base + parts[i].at); }
+  uint64_t* u64(size_t i) const { return (uint64_t*)(base + parts[i].at); }
+  hipError_t alloc(herro::Bufs& B, hipStream_t st) {  // the block, and the pattern into every guard
+    hipError_t e = B.bytes(&base, total);
+    uint32_t g[GUARD_WORDS];
+    for (uint32_t i = 0; i < GUARD_WORDS; i++) g[i] = guard_word(i);
+    for (size_t i = 0; e == hipSuccess && i < parts.size(); i++) e = hipMemcpyAsync(base + parts[i].at + parts[i].bytes, g, sizeof g, hipMemcpyHostToDevice, st);
+    return e == hipSuccess ? hipStreamSynchronize(st) : e;   // (g leaves the stack)
+  }
+  hipError_t hits(hipStream_t st, uint32_t* n_changed) {    // waits for the stream; counts the guard words that no longer hold the pattern
+    std::vector<uint32_t> g((size_t)GUARD_WORDS * parts.size());
+    hipError_t e = hipSuccess;
+    for (size_t i = 0; e == hipSuccess && i < parts.size(); i++)
+      e = hipMemcpyAsync(g.data() + i * GUARD_WORDS, base + parts[i].at + parts[i].bytes, 4ull * GUARD_WORDS, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    *n_changed = 0;
+    for (size_t i = 0; e == hipSuccess && i < g.size(); i++) *n_changed += g[i] != guard_word((uint32_t)(i % GUARD_WORDS));
+    return e;
+  }
+};
+
+// What the three hooks (`who`) ask before anything runs: a context with a device, and at most 2^31 - 1 elements.
+int debug_prims_ready(herro_ctx* ctx, const char* who, uint64_t n) {
+  if (ctx->host_only) { ctx->err = std::string(who) + ": the context has no device"; return HERRO_E_NO_DEVICE; }
+  if (n > 0x7fffffffull) { ctx->err = std::string(who) + ": more than 2^31 - 1 elements"; return HERRO_E_UNSUPPORTED; }
+  return HERRO_OK;
+}
+}  // namespace
+
+int herro_debug_scan_u32(herro_ctx* ctx, const uint32_t* in, uint64_t n, uint32_t* out, uint32_t* guard_hits) {
+  if (!ctx) return HERRO_E_INVALID;
+  const char* const who = "herro_debug_scan_u32";
+  if (!out || !guard_hits || (n && !in)) { ctx->err = std::string(who) + ": null argument"; return HERRO_E_INVALID; }
+  if (int rc = debug_prims_ready(ctx, who, n)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  herro::Bufs B;
+  Guarded Q;
+  const size_t a_in = Q.add(4 * n), a_out = Q.add(4 * (n + 1)), a_part = Q.add(4ull * herro::ovl_scan_partials((uint32_t)n));
+  FRONT_TRY(ctx, who, "device block", Q.alloc(B, ctx->stream));
+  if (n) FRONT_TRY(ctx, who, "upload", hipMemcpyAsync(Q.u32(a_in), in, 4 * n, hipMemcpyHostToDevice, ctx->stream));
+  std::string msg;
+  if (herro::ovl_scan_u32(Q.u32(a_in), (uint32_t)n, Q.u32(a_out), Q.u32(a_part), ctx->stream, msg) != herro::OVL_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    ctx->err = std::string(who) + ": " + msg;
+    return HERRO_E_NO_DEVICE;
+  }
+  FRONT_TRY(ctx, who, "download", hipMemcpyAsync(out, Q.u32(a_out), 4 * (n + 1), hipMemcpyDeviceToHost, ctx->stream));
+  FRONT_TRY(ctx, who, "guards", Q.hits(ctx->stream, guard_hits));
+  return HERRO_OK;
+}
+
+int herro_debug_radix_sort(herro_ctx* ctx, uint64_t* keys, uint64_t* pays, uint64_t n, const uint32_t* shifts, uint32_t n_shifts, uint32_t* guard_hits) {
+  if (!ctx) return HERRO_E_INVALID;
+  const char* const who = "herro_debug_radix_sort";
+  if (!guard_hits || (n && (!keys || !pays)) || (n_shifts && !shifts)) { ctx->err = std::string(who) + ": null argument"; return HERRO_E_INVALID; }
+  for (uint32_t i = 0; i < n_shifts; i++)
+    if (shifts[i] > 63) { ctx->err = std::string(who) + ": shift " + std::to_string(i) + " is above 63"; return HERRO_E_INVALID; }
+  if (int rc = debug_prims_ready(ctx, who, n)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  herro::Bufs B;
+  Guarded Q;
+  size_t arr[4];                                     // k0, p0, k1, p1
+  for (size_t& a : arr) a = Q.add(8 * n);
+  const size_t a_scr = Q.add(4ull * herro::ovl_sort_scratch(n));
+  FRONT_TRY(ctx, who, "device block", Q.alloc(B, ctx->stream));
+  uint64_t *k0 = Q.u64(arr[0]), *p0 = Q.u64(arr[1]), *k1 = Q.u64(arr[2]), *p1 = Q.u64(arr[3]);
+  if (n) {
+    FRONT_TRY(ctx, who, "key upload", hipMemcpyAsync(k0, keys, 8 * n, hipMemcpyHostToDevice, ctx->stream));
+    FRONT_TRY(ctx, who, "payload upload", hipMemcpyAsync(p0, pays, 8 * n, hipMemcpyHostToDevice, ctx->stream));
+  }
+  std::string msg;
+  const std::vector<uint32_t> sh(shifts, shifts + n_shifts);
+  if (herro::ovl_radix_sort(&k0, &p0, &k1, &p1, (uint32_t)n, sh, Q.u32(a_scr), ctx->stream, msg) != herro::OVL_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    ctx->err = std::string(who) + ": " + msg;
+    return HERRO_E_NO_DEVICE;
+  }
+  if (n) {
+    FRONT_TRY(ctx, who, "key download", hipMemcpyAsync(keys, k0, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+    FRONT_TRY(ctx, who, "payload download", hipMemcpyAsync(pays, p0, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  FRONT_TRY(ctx, who, "guards", Q.hits(ctx->stream, guard_hits));
+  return HERRO_OK;
+}
+
+int herro_debug_offsets64(herro_ctx* ctx, const uint64_t* bytes, uint64_t n, uint64_t* off, uint32_t* guard_hits) {
+  if (!ctx) return HERRO_E_INVALID;
+  const char* const who = "herro_debug_offsets64";
+  if (!off || !guard_hits || (n && !bytes)) { ctx->err = std::string(who) + ": null argument"; return HERRO_E_INVALID; }
+  if (int rc = debug_prims_ready(ctx, who, n)) return rc;
+  *guard_hits = 0;
+  if (!n) { off[0] = 0; return HERRO_OK; }           // (fasta_text_dev never gets here without a piece)
+  try {
+    std::vector<uint32_t> halves(2 * n);             // what k_fa_piece leaves: lo_in, then hi_in
+    for (uint64_t p = 0; p < n; p++) { halves[p] = (uint32_t)bytes[p]; halves[n + p] = (uint32_t)(bytes[p] >> 32); }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    herro::Bufs B;
+    Guarded Q;
+    const size_t a_off = Q.add(8 * (n + 1)), a_lo_in = Q.add(4 * n), a_hi_in = Q.add(4 * n), a_lo = Q.add(4 * (n + 1)), a_hi = Q.add(4 * (n + 1)),
+                 a_part = Q.add(4ull * herro::ovl_scan_partials((uint32_t)n));
+    FRONT_TRY(ctx, who, "device block", Q.alloc(B, ctx->stream));
+    FRONT_TRY(ctx, who, "upload", hipMemcpyAsync(Q.u32(a_lo_in), halves.data(), 4 * n, hipMemcpyHostToDevice, ctx->stream));
+    FRONT_TRY(ctx, who, "upload", hipMemcpyAsync(Q.u32(a_hi_in), halves.data() + n, 4 * n, hipMemcpyHostToDevice, ctx->stream));
+    std::string msg;
+    if (herro::fasta_offsets64(Q.u32(a_lo_in), Q.u32(a_hi_in), (uint32_t)n, Q.u32(a_lo), Q.u32(a_hi), Q.u64(a_off),
+                               Q.u32(a_part), ctx->stream, msg) != herro::FASTA_OK) {
+      ctx->err = std::string(who) + ": " + msg;      // (the stream is idle: fasta_dev.hip waits before it reports)
+      return HERRO_E_NO_DEVICE;
+    }
+    FRONT_TRY(ctx, who, "download", hipMemcpyAsync(off, Q.u64(a_off), 8 * (n + 1), hipMemcpyDeviceToHost, ctx->stream));
+    FRONT_TRY(ctx, who, "guards", Q.hits(ctx->stream, guard_hits));
+    return HERRO_OK;
+  } catch (const std::exception& e) {
+    ctx->err = std::string(who) + ": " + e.what();
+    return HERRO_E_UNSUPPORTED;
+  }
 }
 
 // ---- clusters: the reads partitioned by their overlap graph (cluster_dev.hip, cluster_plan.h) -----------------------------

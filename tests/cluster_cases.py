@@ -4,6 +4,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from scan_sort_cases import SCAN_SEAM     # elements above which the scan under cl_build (overlap_dev.hip: k_scan_top) runs a second round
+
 
 def case(n, edges, k, w=None, span=None, min_span=0):
     e = np.asarray(edges, np.uint32).reshape(-1, 2)
@@ -64,6 +66,12 @@ def star_graph(leaves: int, k: int):
     hub = leaves // 2
     others = np.array([v for v in range(leaves + 1) if v != hub])
     return case(leaves + 1, np.stack([np.full(leaves, hub), others], 1), k)
+
+
+def edge_free_graph(n: int = SCAN_SEAM + 1, k: int = 7, seed: int = 14):
+    """n reads without an edge, weights 0 .. 4095 (T below 2^32 up to a million reads): the sort of the n order keys and the scan of the n weights
+    are the only work, and at the default n both pass the seam of the scan.  (cluster_ref.cluster takes two seconds for it: no closed form is needed.)"""
+    return case(n, [], k, w=np.random.default_rng(seed).integers(0, 4096, n))
 
 
 def genome_graph(seed: int, n: int, chromosomes: int, shortcuts: int, chrom_len: int = 1_000_000, min_overlap: int = 2000):

@@ -145,6 +145,30 @@ def test_a_hub_with_3000_neighbours():
     _check(g, "hubs")
 
 
+def test_half_a_million_reads_without_an_edge_pass_the_seam_of_the_scan():
+    """n = 256 * 2048 + 1: the order sort's keys and the weight prefix both take k_scan_top (overlap_dev.hip) into its second round; without an edge
+    the order is the ids, so every field shows where the sort or the scan slipped"""
+    g = CC.edge_free_graph()
+    assert g["n"] == CC.SCAN_SEAM + 1 == 524289 and g["n_parts"] == 7 and len(g["a"]) == 0 and int(g["w"].sum()) < 1 << 32
+    want = CR.cluster(**g)
+    assert np.array_equal(want.rank, np.arange(g["n"])) and want.stats["n_components"] == g["n"] and want.part[-1] == 6
+    c = G.ctx()
+    cl = _run(c, g)
+    _same_as_ref(cl, want, "edge_free 524289")
+    cl.close()
+
+
+def test_more_parts_than_the_edge_statistics_hold_in_lds():
+    """k = 1025: k_cl_edge_stats sums up to 1 024 parts in LDS first and goes to global atomics above"""
+    g = dict(_genome(20), n_parts=1025)
+    want = CR.cluster(**g)
+    assert (want.part_stats[:, 0] > 0).sum() > 1000 and want.stats["edge_cut"] > 0 and int(want.part_stats[:, 3].sum()) > 0
+    c = G.ctx()
+    cl = _run(c, g)
+    _same_as_ref(cl, want, "genome k=1025")
+    cl.close()
+
+
 # ---- 4. from reads, W = 256 -------------------------------------------------------------------------------------------------------------------
 W = 256
 READS = [("A", dict(max_occ=64, min_score=200)), ("B", PC.DEFAULTS)]
