@@ -50,6 +50,7 @@ EXPORTS = [
     "herro_aligned_dev_paf", "herro_pairs_paf", "herro_paf_text_data", "herro_paf_text_len", "herro_paf_text_lines", "herro_paf_text_free",
     "herro_pairs_write_alns",
     "herro_set_seed_rescue", "herro_overlaps_rescued", "herro_pairs_rescued", "herro_debug_seed_rescue",
+    "herro_set_chain_params", "herro_debug_chain",
     "herro_find_adapters", "herro_adapter_hits_n", "herro_adapter_hits_data", "herro_adapter_hits_off", "herro_adapter_hits_free", "herro_debug_set_adapter_cap",
     "herro_trim_plan", "herro_trim_n_pieces", "herro_trim_pieces", "herro_trim_piece_off", "herro_trim_stats", "herro_trim_free",
     "herro_reads_create", "herro_reads_cut", "herro_reads_cut_names",
@@ -114,6 +115,10 @@ class OverlapParams(C.Structure):  # herro_overlap_params (0 = the field's defau
 
 class SeedRescueParams(C.Structure):  # herro_seed_rescue_params (occ_dist 0 = off, rescue_max_occ 0 = 4095)
     _fields_ = [("occ_dist", C.c_uint32), ("rescue_max_occ", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class ChainParams(C.Structure):  # herro_chain_params (lookback 0 = 64)
+    _fields_ = [("lookback", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 class ExtendParams(C.Structure):  # herro_extend_params (0 = the field's default)
@@ -336,6 +341,12 @@ def lib():
                 f.argtypes = [vp]
             L.herro_debug_seed_rescue.restype = C.c_int64
             L.herro_debug_seed_rescue.argtypes = [vp, vp, vp, vp, u64]
+        except AttributeError:
+            if not os.environ.get("HERRO_LIB"):
+                raise
+        try:   # (an older build selected by HERRO_LIB lacks the chain look-back: every call that leaves it at 64 still runs)
+            L.herro_set_chain_params.argtypes = [vp, vp]
+            L.herro_debug_chain.argtypes = [vp, u64, vp, vp, vp, vp, vp]
         except AttributeError:
             if not os.environ.get("HERRO_LIB"):
                 raise
@@ -945,6 +956,56 @@ class Context:
         finally:
             self.set_seed_rescue(*before)
 
+    def set_chain_lookback(self, n: int | None = 0):
+        """The predecessors a chain step of every later find_overlaps / find_overlap_pairs of this context looks at (herro_set_chain_params;
+        minimap2's max_chain_iter): a multiple of 64 in 64 .. 1024; None or 0: 64, the default, which runs the kernels that always ran.  A
+        tandem repeat whose anchors survive the frequency cut breaks a chain at 64; DESIGN.md section 10, "A longer look-back".  Any other
+        value is the library's HERRO_E_INVALID, and the setting stays as it was."""
+        n = int(n or 0)
+        if not 0 <= n <= 0xFFFFFFFF:
+            raise HerroError(-1, "chain look-back: an unsigned 32-bit value")
+        p = ChainParams(lookback=n)
+        self._chk(self._l.herro_set_chain_params(self.h, C.byref(p)))
+        self._chain_lookback = n or 64
+
+    @property
+    def chain_lookback(self) -> int:
+        """the look-back in force (set_chain_lookback; 64 unless set)"""
+        return getattr(self, "_chain_lookback", 64)
+
+    @contextlib.contextmanager
+    def _chain_keywords(self, params: dict):
+        """lookback= of one finder call: taken out of params, set for the call, the context's setting restored behind it"""
+        if "lookback" not in params:
+            yield
+            return
+        before = self.chain_lookback
+        n = params.pop("lookback")
+        self.set_chain_lookback(before if n is None else n)
+        try:
+            yield
+        finally:
+            self.set_chain_lookback(before)
+
+    def chain(self, groups, **params):
+        """Test hook (herro_debug_chain): the chain stage alone under the context's look-back, or the lookback= given here.  groups: a list of
+        (tpos, qpos) array pairs, each not empty and strictly ascending by (tpos, qpos) with coordinates below 2^31; params: k, bandwidth,
+        max_gap.  Returns i32 [n_groups, 4]: score, first anchor, last anchor, anchors in the chain — tests/overlap_ref.py::chain."""
+        tps = [np.ascontiguousarray(t, np.uint32).reshape(-1) for t, _ in groups]
+        qps = [np.ascontiguousarray(q, np.uint32).reshape(-1) for _, q in groups]
+        if any(len(t) != len(q) for t, q in zip(tps, qps)):
+            raise ValueError("one qpos per tpos")
+        off = np.zeros(len(tps) + 1, np.uint64)
+        off[1:] = np.cumsum([len(t) for t in tps])
+        tp = np.concatenate(tps) if tps else np.zeros(0, np.uint32)
+        qp = np.concatenate(qps) if qps else np.zeros(0, np.uint32)
+        out = np.zeros((len(tps), 4), np.int32)
+        with self._chain_keywords(params):
+            p = self._overlap_params(params)
+            self._chk(self._l.herro_debug_chain(self.h, len(tps), off.ctypes.data, tp.ctypes.data if len(tp) else None,
+                                                qp.ctypes.data if len(qp) else None, C.byref(p), out.ctypes.data if len(tps) else None))
+        return out
+
     def seed_rescue(self, **params):
         """The rescue alone (herro_debug_seed_rescue) under the context's setting, or the occ_dist= / rescue_max_occ= given here: for the
         minimizers in sketch()'s order, (occ u32 = min(occurrences of the hash in the store, 65535), rescued u8)."""
@@ -964,13 +1025,14 @@ class Context:
     def find_overlaps(self, core=None, **params):
         """Which reads of the store overlap, where, on which strand (herro_find_overlaps; the seeding and chaining of the
         `minimap2 -x ava-ont` run of mm2.rs:15-30).  params: k, w, max_occ, bandwidth, max_gap, min_score, min_anchors, occ_frac_ppm, and
-        occ_dist / rescue_max_occ: set_seed_rescue for this call alone (the minimizers it rescued are left in self.last_rescued).
+        occ_dist / rescue_max_occ: set_seed_rescue for this call alone (the minimizers it rescued are left in self.last_rescued);
+        lookback: set_chain_lookback for this call alone.
         The frequency cut the call used (max_occ, or the one occ_frac_ppm gave) is left in self.last_occ_cut.
         Returns (rids u32 [n_targets], rows u32 [n, 10] in create_job's layout with cigar_len 0, aln_off u64 [n_targets + 1],
         scores i32 [n]): rows goes into Context.align, (rids, aln_off) with its result into aligned_job_args.
         core: u8 [n_reads], non-zero = the read is a target (herro_find_overlaps_core): the records whose tid is core; None: all."""
         h = C.c_void_p()
-        with self._rescue_keywords(params):
+        with self._rescue_keywords(params), self._chain_keywords(params):   # (lookback=: set_chain_lookback for this call alone)
             p = self._overlap_params(params)
             if core is None:
                 self._chk(self._l.herro_find_overlaps(self.h, C.byref(p), C.byref(h)))
@@ -1060,7 +1122,7 @@ class Context:
         e = ExtendParams(zdrop=int(zdrop), max_ext=int(max_ext))
         h = C.c_void_p()
         flags = 0 if extend else PAIRS_NO_EXTEND
-        with self._rescue_keywords(params):   # (occ_dist= / rescue_max_occ=: set_seed_rescue for this call alone)
+        with self._rescue_keywords(params), self._chain_keywords(params):   # (occ_dist= / rescue_max_occ= / lookback=: set for this call alone)
             p = self._overlap_params(params)
             if core is None:
                 self._chk(self._l.herro_find_overlap_pairs(self.h, C.byref(p), C.byref(e), flags, C.byref(h)))

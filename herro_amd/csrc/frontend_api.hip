@@ -1,6 +1,6 @@
 // frontend_api.hip — the C ABI's front end (include/herro_amd.h): reads alone -> overlap records -> their ops on the device.
 // herro_find_overlaps[_core], herro_extend_overlaps, herro_align_overlaps[_dev], herro_aligned_dev_*, herro_find_overlap_pairs[_core], herro_pairs_*, the PAF / .oec.zst
-// writer (herro_aligned_dev_paf, herro_pairs_paf, herro_pairs_write_alns) herro_set_seed_rescue and the test hooks herro_debug_sketch, herro_debug_occ_census and herro_debug_seed_rescue.  Host C++ (compiled by
+// writer (herro_aligned_dev_paf, herro_pairs_paf, herro_pairs_write_alns) herro_set_seed_rescue, herro_set_chain_params and the test hooks herro_debug_sketch, herro_debug_occ_census, herro_debug_seed_rescue and herro_debug_chain.  Host C++ (compiled by
 // hipcc) over overlap_dev.hip, align_dev.hip and paf_dev.hip; contexts, the model and jobs are herro_api.hip.  Ahead of them all, for raw reads:
 // herro_find_adapters and its handle, over adapter_dev.hip (the plan and the cut are host code: fastx.cpp), and herro_store_cut with its test hook
 // herro_debug_store_copy, over store_dev.hip: the store cut to the plan's pieces on the device.  The primitives every device stage stands on have hooks of
@@ -180,6 +180,7 @@ int overlap_params(herro_ctx* ctx, const herro_overlap_params* in, herro::OvlPar
   }
   P.occ_dist = ctx->seed_rescue.occ_dist;       // herro_set_seed_rescue (validated there)
   P.rescue_max_occ = ctx->seed_rescue.rescue_max_occ ? ctx->seed_rescue.rescue_max_occ : 4095;
+  P.lookback = ctx->chain_lookback;             // herro_set_chain_params (validated there)
   if (P.occ_frac_ppm > 999999) {
     ctx->err = "overlap parameters: occ_frac_ppm must be below 1000000 (0: the fixed cut max_occ)";
     return HERRO_E_INVALID;
@@ -200,6 +201,8 @@ void print_ovl_stats(const herro::OvlParams& P, const herro::OvlStats& stats) {
   if (P.occ_dist)
     fprintf(stderr, "OVLRESC high=%llu rescued=%llu anchors=%llu\n", (unsigned long long)stats.resc_high, (unsigned long long)stats.rescued,
             (unsigned long long)stats.resc_anchors);
+  if (P.lookback != herro::OVL_LOOKBACK)
+    fprintf(stderr, "OVLCHAIN lookback=%u chained=%llu\n", P.lookback, (unsigned long long)stats.chained);
 }
 
 // A call's core mask (n_reads bytes, non-zero: the read is a target) goes up once, into the call's scratch; NULL stays NULL: every read is core.
@@ -594,6 +597,20 @@ int herro_set_seed_rescue(herro_ctx* ctx, const herro_seed_rescue_params* params
     return HERRO_E_INVALID;
   }
   ctx->seed_rescue = p;
+  return HERRO_OK;
+}
+
+// The chain look-back is a setting of the context too: overlap_params hands it to every finder call and to herro_debug_chain.
+int herro_set_chain_params(herro_ctx* ctx, const herro_chain_params* params) {
+  if (!ctx) return HERRO_E_INVALID;
+  const herro_chain_params dflt{};
+  const herro_chain_params& p = params ? *params : dflt;
+  const uint32_t h = p.lookback ? p.lookback : herro::OVL_LOOKBACK;
+  if (h % 64 || h > herro::OVL_MAX_LOOKBACK || p.reserved[0] || p.reserved[1] || p.reserved[2]) {
+    ctx->err = "herro_set_chain_params: lookback is a multiple of 64 in 64 .. 1024 (0: 64), reserved fields 0";
+    return HERRO_E_INVALID;
+  }
+  ctx->chain_lookback = h;
   return HERRO_OK;
 }
 
@@ -1352,6 +1369,37 @@ int herro_debug_scan_u32(herro_ctx* ctx, const uint32_t* in, uint64_t n, uint32_
   FRONT_TRY(ctx, who, "download", hipMemcpyAsync(out, Q.u32(a_out), 4 * (n + 1), hipMemcpyDeviceToHost, ctx->stream));
   FRONT_TRY(ctx, who, "guards", Q.hits(ctx->stream, guard_hits));
   return HERRO_OK;
+}
+
+int herro_debug_chain(herro_ctx* ctx, uint64_t n_groups, const uint64_t* group_off, const uint32_t* tpos, const uint32_t* qpos,
+                      const herro_overlap_params* params, int32_t* out) {
+  if (!ctx) return HERRO_E_INVALID;
+  const char* const who = "herro_debug_chain";
+  if (!group_off || (n_groups && (!out || !tpos || !qpos))) { ctx->err = std::string(who) + ": null argument"; return HERRO_E_INVALID; }
+  herro::OvlParams P;
+  if (int rc = overlap_params(ctx, params, P)) return rc;
+  if (group_off[0] != 0) { ctx->err = std::string(who) + ": group_off[0] must be 0"; return HERRO_E_INVALID; }
+  for (uint64_t g = 0; g < n_groups; g++) {
+    const uint64_t a = group_off[g], b = group_off[g + 1];
+    std::string why;
+    if (b <= a) why = "is empty";
+    for (uint64_t i = a; why.empty() && i < b; i++) {
+      if ((tpos[i] | qpos[i]) >> 31) why = "holds a coordinate of 2^31 or more";
+      else if (i > a && ((uint64_t)tpos[i] << 32 | qpos[i]) <= ((uint64_t)tpos[i - 1] << 32 | qpos[i - 1])) why = "is not strictly ascending by (tpos, qpos)";
+    }
+    if (!why.empty()) { ctx->err = std::string(who) + ": group " + std::to_string(g) + " " + why; return HERRO_E_INVALID; }
+  }
+  if (n_groups > 0x7fffffffull) { ctx->err = std::string(who) + ": more than 2^31 - 1 groups"; return HERRO_E_UNSUPPORTED; }
+  if (int rc = debug_prims_ready(ctx, who, group_off[n_groups])) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  try {
+    std::string msg;
+    const int rc = herro::ovl_chain_groups(n_groups, group_off, tpos, qpos, P, ctx->stream, out, msg);
+    return overlap_rc(ctx, rc, std::string(who) + ": " + msg);
+  } catch (const std::exception& e) {
+    ctx->err = std::string(who) + ": " + e.what();
+    return HERRO_E_UNSUPPORTED;
+  }
 }
 
 int herro_debug_radix_sort(herro_ctx* ctx, uint64_t* keys, uint64_t* pays, uint64_t n, const uint32_t* shifts, uint32_t n_shifts, uint32_t* guard_hits) {

@@ -15,6 +15,7 @@
 namespace herro {
 
 constexpr uint32_t OVL_LOOKBACK = 64;          // predecessors a chain step looks at: the lanes of a wave
+constexpr uint32_t OVL_MAX_LOOKBACK = 1024;    // ... at most, in multiples of 64, where OvlParams.lookback asks for more (k_chain_far: 64 a round)
 constexpr uint64_t OVL_ANCHOR_BYTES = 128;     // scratch the budget charges per anchor of a chunk (keys, payloads, both sort buffers, groups)
 constexpr uint64_t OVL_MAX_KMERS = 0xfffff000ull;   // k-mers of the whole store (32-bit minimizer indices)
 constexpr uint32_t OVL_MAX_READ_LEN = 0x7fffffffu;  // pos << 1 | strand is one 32-bit field
@@ -24,7 +25,9 @@ constexpr uint32_t OVL_MAX_READS = 0x7fffffffu;     // q << 1 | rel is one 33-bi
 // its ceiling, 0 = none.
 // occ_dist != 0: the rescue of high-frequency minimizers (minimap2's -e, mm2.rs:24) — of a stretch of a read whose minimizers all lie
 // above the cut, the least frequent ones stay, about one per occ_dist bases, among those of at most rescue_max_occ occurrences (filled in: never 0).
-struct OvlParams { uint32_t k, w, max_occ, bandwidth, max_gap, min_score, min_anchors, occ_frac_ppm, occ_dist = 0, rescue_max_occ = 0; };
+// lookback: the predecessors a chain step looks at, a multiple of 64 in 64 .. OVL_MAX_LOOKBACK ("A longer look-back"); 64 runs
+// k_chain and everything else as it was, any other value k_chain_far.
+struct OvlParams { uint32_t k, w, max_occ, bandwidth, max_gap, min_score, min_anchors, occ_frac_ppm, occ_dist = 0, rescue_max_occ = 0, lookback = OVL_LOOKBACK; };
 
 constexpr uint32_t OVL_OCC_BINS = 65536;       // census counts of a hash run: min(length, 65535)
 constexpr uint32_t OVL_OCC_FLOOR = 10;         // the least cut the fraction may give (minimap2's min_mid_occ)
@@ -83,6 +86,13 @@ int ovl_seed_rescue(const OvlStore& S, const OvlParams& P, hipStream_t st, std::
 // result is therefore the unmasked one restricted to those pairs.  OvlStats.anchors and the limits count the masked anchors.
 int ovl_find(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uint64_t budget_bytes, hipStream_t st, std::vector<OvlPair>& out,
              OvlStats& stats, std::string& err);
+
+// The chain stage alone on anchor groups the caller gives (herro_debug_chain): group g is tpos / qpos [group_off[g], group_off[g + 1]), not empty,
+// strictly ascending by (tpos, qpos), coordinates below 2^31, fewer than 2^31 anchors in all (the caller has checked all that).  Runs what a
+// chunk of ovl_find runs behind k_gcompact — the groups ordered largest first, k_chain or k_chain_far by P.lookback, k_walk — and leaves
+// out[g] = {score, first anchor, last anchor, anchors in the chain}: tests/overlap_ref.py::chain.  Of P it reads k, bandwidth, max_gap, lookback.
+int ovl_chain_groups(uint64_t n_groups, const uint64_t* group_off, const uint32_t* tpos, const uint32_t* qpos, const OvlParams& P, hipStream_t st,
+                     int32_t* out, std::string& err);
 
 // ---- one overlap per pair, left on the device ("Pairs on the device") -------------------------------------------------------
 constexpr uint64_t OVL_MAX_PAIRS = 0x7fffffffull;   // the mirror's record limit; 2 P rows stay inside the sort's 32-bit count

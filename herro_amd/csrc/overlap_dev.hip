@@ -13,6 +13,7 @@
 //   k_expand     the anchors of the targets of one chunk: A = tpos << 32 | qpos, B = (t - t_lo) << 33 | q << 1 | rel;
 //                sorted by A carrying B, then by B carrying A (stable): order (t, q, rel, tpos, qpos).
 //   k_chain      one wave64 per (t, q, rel) group: the 64 predecessors of an anchor are the 64 lanes.
+//   k_chain_far  OvlParams.lookback = 64 R > 64 only: k_chain with R rounds a step, the R blocks in front of the current one in an LDS ring.
 //   k_walk       back through the stored predecessors: first anchor, anchor count, coordinates.
 // A core mask (one byte per read, non-zero: the read is a target) keeps k_runs / k_expand from creating an anchor between two non-core
 // reads, so everything behind the anchors sees wanted pairs only; without a mask (CORE = false) the two kernels are what they were.
@@ -702,10 +703,94 @@ __global__ __launch_bounds__(64) void k_chain(const uint64_t* __restrict__ A, co
   if (lane == 0) ends[c] = ChainEnd{best_f, best_i};
 }
 
+// The score of one predecessor (t_j, q_j, f_j) of anchor (t_i, q_i): k_chain's conditions and cost, INT32_MIN where it is no candidate.
+// in_gap: the predecessor exists and dt <= max_gap — what the early stop of k_chain_far asks of a round.
+__device__ inline int32_t chain_cand(int32_t ti, int32_t qi, int32_t tj, int32_t qj, int32_t fj, bool exists, int32_t k, int32_t bandwidth,
+                                     int32_t max_gap, bool& in_gap) {
+  const int32_t dt = ti - tj, dq = qi - qj;
+  const int32_t diff = dt - dq;
+  const int32_t dd = diff < 0 ? -diff : diff;
+  in_gap = exists && dt <= max_gap;
+  if (!(in_gap && dt > 0 && dq > 0 && dq <= max_gap && dd <= bandwidth)) return INT32_MIN;
+  const int64_t cost = (((int64_t)dd * k) >> 6) + ((31 - __clz(dd + 1)) >> 1);
+  const int64_t v = (int64_t)fj + min(k, min(dt, dq)) - cost;
+  return v > k ? (int32_t)v : INT32_MIN;
+}
+
+// k_chain for a look-back of H = 64 R anchors, R = 2 .. 16 (OvlParams.lookback; DESIGN.md §10, "A longer look-back").  One wave per group.
+// The current block of 64 anchors and the one before it sit in registers as in k_chain; (t, q, f) of the R finished blocks in front of the
+// current one sit in a ring in LDS, 12 B per anchor, block b in slot b mod R at index slot * 64 + lane: a lane only ever reads what it wrote
+// itself, so the ring needs no barrier.  For anchor i = base + m, round r = 0 .. R - 1 gives lane l the predecessor base + l - 64 r (l < m) or
+// base + l - 64 (r + 1) (l >= m): the rounds together are exactly i - 1 ... i - H.  A lane keeps the best of its R candidates, a farther one only
+// where it is strictly better, so the nearest wins the lane's ties; the wave's maximum and, among the lanes that hold it, the least distance
+// are one reduction each.  The anchors ascend by tpos: a round in which no lane has an existing predecessor with dt <= max_gap ends the
+// rounds of the step — every farther predecessor fails the same condition, or does not exist either.
+__global__ __launch_bounds__(64) void k_chain_far(const uint64_t* __restrict__ A, const uint64_t* __restrict__ order,
+                                                  const uint32_t* __restrict__ cstart, const uint32_t* __restrict__ csize,
+                                                  uint16_t* __restrict__ pred, ChainEnd* __restrict__ ends, int32_t k, int32_t bandwidth,
+                                                  int32_t max_gap, int32_t rounds) {
+  extern __shared__ int32_t ring[];             // [3][rounds * 64]: t, q, f
+  int32_t* const ring_t = ring;
+  int32_t* const ring_q = ring + rounds * 64;
+  int32_t* const ring_f = ring + rounds * 128;
+  const uint32_t c = (uint32_t)order[blockIdx.x];
+  const uint32_t s0 = cstart[c], n = csize[c];
+  const uint32_t lane = threadIdx.x;
+  int32_t fr = 0, cur_t = 0, cur_q = 0, prev_t = 0, prev_q = 0;
+  int32_t best_f = -1;
+  uint32_t best_i = 0;
+  int32_t slot = 0, blk = 0;                    // the current block and its slot in the ring: blk mod rounds
+  for (uint32_t base = 0; base < n; base += 64) {
+    prev_t = cur_t;
+    prev_q = cur_q;
+    if (base + lane < n) {
+      const uint64_t a = A[(uint64_t)s0 + base + lane];
+      cur_t = (int32_t)(a >> 32);
+      cur_q = (int32_t)(uint32_t)a;
+    }
+    const uint32_t m_end = min(64u, n - base);
+    uint32_t my_pd = 0;
+    for (uint32_t m = 0; m < m_end; m++) {
+      const int32_t ti = __builtin_amdgcn_readlane(cur_t, m), qi = __builtin_amdgcn_readlane(cur_q, m);
+      const bool newer = lane < m;
+      const int32_t d0 = newer ? (int32_t)(m - lane) : (int32_t)(m - lane) + 64;      // the distance of the lane's predecessor in round 0
+      bool in_gap;
+      int32_t sc = chain_cand(ti, qi, newer ? cur_t : prev_t, newer ? cur_q : prev_q, fr, newer || base >= 64, k, bandwidth, max_gap, in_gap);
+      int32_t dist = d0;
+      const int32_t older = newer ? 0 : 1;      // blocks behind the round's own
+      for (int32_t r = 1; r < rounds && __ballot(in_gap); r++) {
+        int32_t s = slot - r - older;
+        if (s < 0) s += rounds;
+        const int32_t at = s * 64 + (int32_t)lane;
+        const int32_t v = chain_cand(ti, qi, ring_t[at], ring_q[at], ring_f[at], blk - r - older >= 0, k, bandwidth, max_gap, in_gap);
+        if (v > sc) { sc = v; dist = d0 + 64 * r; }            // strictly better: the nearer round wins ties
+      }
+      const int32_t mx = wave_max_i32(sc);
+      int32_t f_i = k;
+      uint32_t pd = 0;                          // distance to the chosen predecessor, 0: none
+      if (mx > k) {
+        pd = (uint32_t)-wave_max_i32(sc == mx ? -dist : INT32_MIN);      // the nearest of the lanes that hold the maximum
+        f_i = mx;
+      }
+      if (lane == m) { fr = f_i; my_pd = pd; }
+      if (f_i > best_f) { best_f = f_i; best_i = base + m; }    // strictly better: the smallest i wins ties
+    }
+    if (base + lane < n) pred[(uint64_t)s0 + base + lane] = (uint16_t)my_pd;
+    const int32_t at = slot * 64 + (int32_t)lane;
+    ring_t[at] = cur_t;
+    ring_q[at] = cur_q;
+    ring_f[at] = fr;
+    blk++;
+    if (++slot == rounds) slot = 0;
+  }
+  if (lane == 0) ends[c] = ChainEnd{best_f, best_i};
+}
+
 struct GroupOut { uint32_t t, q, rel, n_anchors; int32_t score; uint32_t tstart, tend, qstart, qend, kept; };
 
+template <class Pred>   // uint8_t behind k_chain, uint16_t behind k_chain_far
 __global__ __launch_bounds__(256) void k_walk(const uint64_t* __restrict__ A, const uint64_t* __restrict__ B,
-                                              const uint32_t* __restrict__ cstart, const uint8_t* __restrict__ pred,
+                                              const uint32_t* __restrict__ cstart, const Pred* __restrict__ pred,
                                               const ChainEnd* __restrict__ ends, uint32_t nc, const uint64_t* __restrict__ base_off,
                                               uint32_t k, uint32_t t_lo, uint32_t min_score, uint32_t min_anchors,
                                               GroupOut* __restrict__ out) {
@@ -1031,6 +1116,33 @@ int rescue_keep_meta(const Sketch& sk, hipStream_t st, Bufs& B, Rescue& R, std::
   return OVL_OK;
 }
 
+// The chain stage of a chunk, and all of ovl_chain_groups: the nc groups (cstart, csize; ck0 / cp0 as k_gcompact leaves them) ordered largest first,
+// chained by k_chain (P.lookback == 64: pred8) or k_chain_far (pred16), walked back into gout.
+struct ChainBufs {
+  uint64_t *ck0, *cp0, *ck1, *cp1;
+  uint32_t *cstart, *csize;
+  uint8_t* pred8;
+  uint16_t* pred16;
+  ChainEnd* ends;
+  GroupOut* gout;
+};
+int chain_and_walk(const uint64_t* A0, const uint64_t* B0, ChainBufs& C, uint32_t nc, const OvlParams& P, const uint64_t* d_base_off, uint32_t t_lo,
+                   const SortScratch& as, hipStream_t st, std::string& err) {
+  if (int rc = radix_sort(&C.ck0, &C.cp0, &C.ck1, &C.cp1, nc, {0, 8, 16, 24}, as, st, err)) return rc;
+  const int32_t bandwidth = (int32_t)std::min<uint32_t>(P.bandwidth, 0x3fffffffu), max_gap = (int32_t)std::min<uint32_t>(P.max_gap, 0x7fffffffu);
+  if (P.lookback == OVL_LOOKBACK) {
+    k_chain<<<nc, 64, 0, st>>>(A0, C.cp0, C.cstart, C.csize, C.pred8, C.ends, (int32_t)P.k, bandwidth, max_gap);
+    k_walk<uint8_t><<<nblk(nc, 256), 256, 0, st>>>(A0, B0, C.cstart, C.pred8, C.ends, nc, d_base_off, P.k, t_lo, P.min_score, P.min_anchors, C.gout);
+  } else {
+    k_chain_far<<<nc, 64, 12 * P.lookback, st>>>(A0, C.cp0, C.cstart, C.csize, C.pred16, C.ends, (int32_t)P.k, bandwidth, max_gap,
+                                                 (int32_t)(P.lookback / 64));
+    k_walk<uint16_t><<<nblk(nc, 256), 256, 0, st>>>(A0, B0, C.cstart, C.pred16, C.ends, nc, d_base_off, P.k, t_lo, P.min_score, P.min_anchors, C.gout);
+  }
+  OVL_TRY(hipGetLastError());
+  return OVL_OK;
+}
+inline bool lookback_ok(uint32_t h) { return h >= OVL_LOOKBACK && h <= OVL_MAX_LOOKBACK && h % 64 == 0; }
+
 // Sketch, sort, frequency cut and the chunk loop of ovl_find and ovl_find_pairs.  Behind every chunk's k_walk, take(nc, gout, ccap, t_hi, B) gets the
 // chunk's nc GroupOut records, still on the device, in ascending (t, q, rel): it takes what it wants before it returns or queues its kernels on st,
 // in front of the next chunk's k_walk, which overwrites gout.  ccap: the most records any chunk has; t_hi: the targets done so far, this chunk's
@@ -1039,6 +1151,7 @@ template <class Take>
 int find_chunks(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uint64_t budget_bytes, hipStream_t st, OvlStats& stats, std::string& err,
                 Take take) {
   stats = OvlStats{};
+  if (!lookback_ok(P.lookback)) { err = "overlap finder: the look-back is a multiple of 64 in 64 .. 1024"; return OVL_UNSUPPORTED; }
   Bufs B;
   Sketch sk;
   if (int rc = sketch_dev(S, P, st, B, sk, err)) return rc;
@@ -1092,7 +1205,8 @@ int find_chunks(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, ui
   if (rescue) { stats.resc_high = resc_stat[0]; stats.rescued = resc_stat[1]; stats.resc_anchors = resc_stat[2]; }
 
   // chunks: consecutive targets whose anchors fit the budget (a target with more runs alone)
-  const uint64_t want = std::max<uint64_t>(budget_bytes / OVL_ANCHOR_BYTES, 1);
+  const bool far = P.lookback != OVL_LOOKBACK;      // (k_chain_far's predecessor distances take two bytes an anchor: one more than k_chain's)
+  const uint64_t want = std::max<uint64_t>(budget_bytes / (OVL_ANCHOR_BYTES + (far ? 1 : 0)), 1);
   std::vector<uint32_t> cut{0};
   uint64_t cap = 0, total = 0;
   {
@@ -1110,19 +1224,18 @@ int find_chunks(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, ui
   if (!total) return OVL_OK;
   if (cap > 0xfffff000ull) { err = "overlap finder: more than 2^32 anchors in one chunk (lower HERRO_OVL_SCRATCH_MB)"; return OVL_UNSUPPORTED; }
 
-  uint64_t *A0, *B0, *A1, *B1, *ck0, *cp0, *ck1, *cp1;
-  uint32_t *flag, *gidx, *gstart, *gf, *cidx, *cstart, *csize;
-  uint8_t* pred;
-  ChainEnd* ends;
-  GroupOut* gout;
+  uint64_t *A0, *B0, *A1, *B1;
+  uint32_t *flag, *gidx, *gstart, *gf, *cidx;
+  ChainBufs C{};
   OVL_TRY(B.get(&A0, cap)); OVL_TRY(B.get(&B0, cap)); OVL_TRY(B.get(&A1, cap)); OVL_TRY(B.get(&B1, cap));
   OVL_TRY(B.get(&flag, cap)); OVL_TRY(B.get(&gidx, cap + 1)); OVL_TRY(B.get(&gstart, cap + 1)); OVL_TRY(B.get(&gf, cap));
-  OVL_TRY(B.get(&cidx, cap + 1)); OVL_TRY(B.get(&cstart, cap)); OVL_TRY(B.get(&csize, cap));
+  OVL_TRY(B.get(&cidx, cap + 1)); OVL_TRY(B.get(&C.cstart, cap)); OVL_TRY(B.get(&C.csize, cap));
   const uint64_t ccap = cap / std::max(1u, P.min_anchors) + 1;     // groups of >= min_anchors anchors
-  OVL_TRY(B.get(&ck0, ccap)); OVL_TRY(B.get(&cp0, ccap)); OVL_TRY(B.get(&ck1, ccap)); OVL_TRY(B.get(&cp1, ccap));
-  OVL_TRY(B.get(&pred, cap));
-  OVL_TRY(B.get(&ends, ccap));
-  OVL_TRY(B.get(&gout, ccap));
+  OVL_TRY(B.get(&C.ck0, ccap)); OVL_TRY(B.get(&C.cp0, ccap)); OVL_TRY(B.get(&C.ck1, ccap)); OVL_TRY(B.get(&C.cp1, ccap));
+  if (far) OVL_TRY(B.get(&C.pred16, cap));
+  else OVL_TRY(B.get(&C.pred8, cap));
+  OVL_TRY(B.get(&C.ends, ccap));
+  OVL_TRY(B.get(&C.gout, ccap));
   SortScratch as;
   OVL_TRY(as.alloc(B, cap));
   uint32_t max_len = 0;
@@ -1165,14 +1278,10 @@ int find_chunks(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, ui
     OVL_TRY(hipStreamSynchronize(st));
     if (!nc) continue;
     stats.chained += nc;
-    k_gcompact<<<nblk(ng, 256), 256, 0, st>>>(gstart, gf, cidx, ng, cstart, csize, ck0, cp0);
+    k_gcompact<<<nblk(ng, 256), 256, 0, st>>>(gstart, gf, cidx, ng, C.cstart, C.csize, C.ck0, C.cp0);
     OVL_TRY(hipGetLastError());
-    if (int rc = radix_sort(&ck0, &cp0, &ck1, &cp1, nc, {0, 8, 16, 24}, as, st, err)) return rc;
-    k_chain<<<nc, 64, 0, st>>>(A0, cp0, cstart, csize, pred, ends, (int32_t)P.k, (int32_t)std::min<uint32_t>(P.bandwidth, 0x3fffffffu),
-                               (int32_t)std::min<uint32_t>(P.max_gap, 0x7fffffffu));
-    k_walk<<<nblk(nc, 256), 256, 0, st>>>(A0, B0, cstart, pred, ends, nc, S.d_base_off, P.k, t_lo, P.min_score, P.min_anchors, gout);
-    OVL_TRY(hipGetLastError());
-    if (int rc = take(nc, gout, ccap, t_hi, B)) return rc;
+    if (int rc = chain_and_walk(A0, B0, C, nc, P, S.d_base_off, t_lo, as, st, err)) return rc;
+    if (int rc = take(nc, C.gout, ccap, t_hi, B)) return rc;
   }
   return OVL_OK;
 }
@@ -1235,6 +1344,60 @@ int ovl_find(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uint6
       if (g.kept) out.push_back(OvlPair{g.t, g.q, g.rel, g.n_anchors, g.score, g.tstart, g.tend, g.qstart, g.qend});
     return OVL_OK;
   });
+}
+
+// The chain stage alone on the caller's groups (herro_debug_chain).  The keys k_walk decodes are those of target 0, query 0, forward strand, whose
+// length it then does not ask for; it leaves the first anchor's coordinates, and the keys of a group are strictly ascending: its index is looked up.
+int ovl_chain_groups(uint64_t n_groups, const uint64_t* group_off, const uint32_t* tpos, const uint32_t* qpos, const OvlParams& P, hipStream_t st,
+                     int32_t* out, std::string& err) {
+  if (!lookback_ok(P.lookback)) { err = "overlap finder: the look-back is a multiple of 64 in 64 .. 1024"; return OVL_UNSUPPORTED; }
+  if (!n_groups) return OVL_OK;
+  const uint32_t nc = (uint32_t)n_groups;
+  const uint64_t na = group_off[n_groups];
+  std::vector<uint64_t> hA(na), key(nc), pay(nc);
+  std::vector<uint32_t> start(nc), size(nc);
+  for (uint64_t i = 0; i < na; i++) hA[i] = (uint64_t)tpos[i] << 32 | qpos[i];
+  for (uint32_t g = 0; g < nc; g++) {           // (what k_gcompact leaves)
+    start[g] = (uint32_t)group_off[g];
+    size[g] = (uint32_t)(group_off[g + 1] - group_off[g]);
+    key[g] = 0xffffffffu - size[g];
+    pay[g] = g;
+  }
+  Bufs B;
+  uint64_t *A0, *B0, *d_base_off;
+  ChainBufs C{};
+  OVL_TRY(B.get(&A0, na)); OVL_TRY(B.get(&B0, na)); OVL_TRY(B.get(&d_base_off, 2));
+  OVL_TRY(B.get(&C.cstart, nc)); OVL_TRY(B.get(&C.csize, nc));
+  OVL_TRY(B.get(&C.ck0, nc)); OVL_TRY(B.get(&C.cp0, nc)); OVL_TRY(B.get(&C.ck1, nc)); OVL_TRY(B.get(&C.cp1, nc));
+  if (P.lookback != OVL_LOOKBACK) OVL_TRY(B.get(&C.pred16, na));
+  else OVL_TRY(B.get(&C.pred8, na));
+  OVL_TRY(B.get(&C.ends, nc));
+  OVL_TRY(B.get(&C.gout, nc));
+  SortScratch as;
+  OVL_TRY(as.alloc(B, nc));
+  OVL_TRY(hipMemcpyAsync(A0, hA.data(), 8 * na, hipMemcpyHostToDevice, st));
+  OVL_TRY(hipMemsetAsync(B0, 0, 8 * na, st));
+  OVL_TRY(hipMemsetAsync(d_base_off, 0, 16, st));
+  OVL_TRY(hipMemcpyAsync(C.cstart, start.data(), 4ull * nc, hipMemcpyHostToDevice, st));
+  OVL_TRY(hipMemcpyAsync(C.csize, size.data(), 4ull * nc, hipMemcpyHostToDevice, st));
+  OVL_TRY(hipMemcpyAsync(C.ck0, key.data(), 8ull * nc, hipMemcpyHostToDevice, st));
+  OVL_TRY(hipMemcpyAsync(C.cp0, pay.data(), 8ull * nc, hipMemcpyHostToDevice, st));
+  if (int rc = chain_and_walk(A0, B0, C, nc, P, d_base_off, 0, as, st, err)) { (void)hipStreamSynchronize(st); return rc; }
+  std::vector<GroupOut> h_out(nc);
+  std::vector<ChainEnd> h_ends(nc);
+  OVL_TRY(hipMemcpyAsync(h_out.data(), C.gout, sizeof(GroupOut) * (uint64_t)nc, hipMemcpyDeviceToHost, st));
+  OVL_TRY(hipMemcpyAsync(h_ends.data(), C.ends, sizeof(ChainEnd) * (uint64_t)nc, hipMemcpyDeviceToHost, st));
+  OVL_TRY(hipStreamSynchronize(st));
+  for (uint32_t g = 0; g < nc; g++) {
+    const GroupOut& o = h_out[g];
+    const uint64_t first_key = (uint64_t)(o.tstart + P.k - 1) << 32 | (uint32_t)(o.qstart + P.k - 1);
+    const uint64_t* a = hA.data() + start[g];
+    out[4 * g] = o.score;
+    out[4 * g + 1] = (int32_t)(std::lower_bound(a, a + size[g], first_key) - a);
+    out[4 * g + 2] = (int32_t)h_ends[g].last;
+    out[4 * g + 3] = (int32_t)o.n_anchors;
+  }
+  return OVL_OK;
 }
 
 // ---- one overlap per pair and the row table, on the device ("Pairs on the device") ---------------------------------------

@@ -616,11 +616,27 @@ uint32_t herro_pairs_occ_cut(const herro_pairs* pairs);                    /* th
  * non-zero reserved field: HERRO_E_INVALID (checked here; works on a context without a device).  herro_overlaps_rescued / herro_pairs_rescued:
  * the minimizers the call rescued (0: off, or a handle made by herro_pairs_from_table*).  HERRO_OVL_STATS=1 adds a line `OVLRESC high=
  * rescued= anchors=`: the H minimizers, the rescued ones, the anchors of the hashes above the cut.  Known interaction: rescued hashes inside a
- * tandem repeat add off-diagonal anchors, and the 64-anchor look-back limit above applies to them too. */
+ * tandem repeat add off-diagonal anchors, and the 64-anchor look-back limit above applies to them too (herro_set_chain_params lifts it to
+ * 1024). */
 typedef struct { uint32_t occ_dist, rescue_max_occ, reserved[2]; } herro_seed_rescue_params;
 int herro_set_seed_rescue(herro_ctx* ctx, const herro_seed_rescue_params* params /* NULL: off */);
 uint32_t herro_overlaps_rescued(const herro_overlaps* o);
 uint32_t herro_pairs_rescued(const herro_pairs* pairs);
+
+/* ---- a longer chain look-back ("A longer look-back"; minimap2's max_chain_iter, 5000 there) -------------------------
+ * A chain step looks at the 64 nearest predecessors of an anchor.  Where a tandem repeat survives the frequency cut — a cut taken from the
+ * index (occ_frac_ppm) or the rescue above keeps its minimizers on purpose — more than 64 off-diagonal anchors can lie between two anchors of
+ * the true diagonal: the chain breaks there and the overlap comes out short, silently.  lookback = H, a multiple of 64 in 64 .. 1024, makes every
+ * later herro_find_overlaps[_core] and herro_find_overlap_pairs[_core] of the context chain over the H nearest predecessors instead.  The
+ * specification is otherwise unchanged (tests/overlap_ref.py::chain(..., lookback=H)): the same conditions and cost, the nearest predecessor
+ * wins ties, the chain ends at the smallest anchor that holds the maximum; the records equal the reference's bit for bit and are the same
+ * bytes for every HERRO_OVL_SCRATCH_MB.  params NULL or lookback 0: 64, the default, which runs exactly the kernels that ran before the setting
+ * existed; any other H runs k_chain_far, whose cost per anchor grows with H where predecessors lie within max_gap.  A look-back that is no
+ * multiple of 64 in 64 .. 1024, or a non-zero reserved field: HERRO_E_INVALID with the legal values in the message, and the setting stays as it
+ * was (checked here; works on a context without a device).  HERRO_OVL_STATS=1 adds a line `OVLCHAIN lookback= chained=` when H is not 64.
+ * What remains: an array with more than 1024 anchors between diagonal neighbours still breaks the chain. */
+typedef struct { uint32_t lookback, reserved[3]; } herro_chain_params;   /* lookback 0 = 64; reserved: 0 */
+int herro_set_chain_params(herro_ctx* ctx, const herro_chain_params* params /* NULL: defaults */);
 
 /* ---- found alignments as PAF / .oec.zst --------------------------------------------------------------------
  * What `herro inference --write-alns DIR` keeps of a batch (AlnMode::Write, overlaps.rs:248-286; the lines, 349-352), for the alignments this
@@ -668,6 +684,15 @@ int herro_debug_occ_census(herro_ctx* ctx, const herro_overlap_params* params, u
  * herro_debug_sketch's (rid, pos) order: occ = min(occurrences of the hash in the store, 65535), rescued = 1 where the minimizer is rescued.
  * Returns their number (nothing is written when cap is smaller) or a negative error. */
 int64_t herro_debug_seed_rescue(herro_ctx* ctx, const herro_overlap_params* params, uint32_t* occ, uint8_t* rescued, uint64_t cap);
+/* Test hook: the chain stage alone, on anchor groups the caller gives, under the context's herro_set_chain_params setting.  Group g is
+ * tpos / qpos [group_off[g], group_off[g + 1]): not empty, strictly ascending by (tpos, qpos) — what the finder's sort leaves —, coordinates
+ * below 2^31.  Runs exactly what a finder call runs behind its groups: they are ordered largest first, chained by k_chain (look-back 64) or
+ * k_chain_far, and walked back by k_walk.  Of params it reads k, bandwidth and max_gap (0 / NULL: the defaults).  out[g] = {score, first anchor,
+ * last anchor, anchors in the chain}, the anchors as indices into their group: tests/overlap_ref.py::chain.  HERRO_E_INVALID for a null
+ * argument, group_off[0] != 0, or a group that is empty, not ascending or holds a coordinate >= 2^31 (the message names the first such group);
+ * HERRO_E_UNSUPPORTED for 2^31 groups or anchors or more; then HERRO_E_NO_DEVICE on a context without a device.  No reads are needed. */
+int herro_debug_chain(herro_ctx* ctx, uint64_t n_groups, const uint64_t* group_off /* [n_groups + 1] */, const uint32_t* tpos,
+                      const uint32_t* qpos, const herro_overlap_params* params, int32_t* out /* [n_groups][4] */);
 /* Test hook: stage 1 alone — the store's minimizers sorted by (rid, pos); pos = index of the k-mer's last base on the forward
  * read, strand = 1 when the reverse complement is the canonical k-mer.  Returns their number (nothing is written when cap is
  * smaller) or a negative error. */

@@ -7,9 +7,14 @@ kernels alone.
 and with the fixed cut set to the value the index gave, so that the last two differ by the census and the pick alone (`occ_share`).
 --occ-dist N [--rescue-max-occ M]: every call rescues high-frequency minimizers (Context.set_seed_rescue; 200 = minimap2 -e200); the sizes gain
 resc_high, resc_rescued and resc_anchors.
+--lookback N: every call chains over the N nearest predecessors of an anchor (Context.set_chain_lookback; a multiple of 64 in 64 .. 1024, 64 = the
+default and its kernels); the sizes gain chain_lookback and chain_chained when N is not 64.
+--tandem: only read pairs around tandem arrays (--tandem-pairs 64 pairs of flank + unit x copies + flank bases, two copies of one genome each with 1 %
+substitutions), the shape a look-back of 64 cuts short; `pair_coverage` is the mean share of the target an overlap between the two reads of a
+pair covers — the true overlap is the whole read.
 --deep: one short genome under many reads (--deep-reads 200 of --deep-len 400 bases), the shape a fixed cut below the depth finds nothing in.
 
-    python tools/overlaprate.py [--targets 256] [--long-targets 8] [--reps 5] [--no-align] [--occ-frac-ppm 5000] [--occ-dist 200] [--deep]"""
+    python tools/overlaprate.py [--targets 256] [--long-targets 8] [--reps 5] [--no-align] [--occ-frac-ppm 5000] [--occ-dist 200] [--lookback 256] [--tandem] [--deep]"""
 from __future__ import annotations
 
 import argparse
@@ -42,7 +47,7 @@ def stage_sizes(fn):
         f.seek(0)
         text = f.read().decode(errors="replace")
     sizes = {}
-    for tag, prefix in (("OVL", ""), ("OVLOCC", "occ_"), ("OVLRESC", "resc_")):
+    for tag, prefix in (("OVL", ""), ("OVLOCC", "occ_"), ("OVLRESC", "resc_"), ("OVLCHAIN", "chain_")):
         m = re.search(tag + r" (.*)", text)
         if m:
             sizes.update({prefix + k: int(v) for k, v in (kv.split("=") for kv in m.group(1).split())})
@@ -69,9 +74,39 @@ class Deep:
         self.off = (np.arange(n + 1) * L).astype(np.uint64)
 
 
-def measure(name, sb, reps, params, align, occ_frac_ppm=0, rescue=(0, 0)):
+class Tandem:
+    """n read pairs, each two copies with 1 % substitutions of flank random bases + a unit of `unit` bases x copies + flank random bases
+    (the generator of tests/lookback_cases.py, one seed per pair)"""
+
+    def __init__(self, n, unit, copies, flank, seed=5):
+        reads = []
+        for p in range(n):
+            rng = np.random.default_rng(seed + p)
+            u = rng.integers(0, 4, unit)
+            g = np.concatenate([rng.integers(0, 4, flank), np.tile(u, copies), rng.integers(0, 4, flank)])
+            for _ in range(2):
+                r = g.copy()
+                m = rng.random(len(r)) < 0.01
+                r[m] = (r[m] + rng.integers(1, 4, m.sum())) & 3
+                reads.append(bytes(b"ACGT"[x] for x in r))
+        self.n_reads = len(reads)
+        self.seq = np.frombuffer(b"".join(reads), np.uint8)
+        self.qual = np.full(len(self.seq), 40 + 33, np.uint8)
+        self.off = np.concatenate([[0], np.cumsum([len(r) for r in reads])]).astype(np.uint64)
+
+
+def pair_coverage(rows):
+    """mean (tend - tstart) / tlen over the records between the two reads of a Tandem pair (reads 2 p and 2 p + 1); None: no such record"""
+    own = rows[(rows[:, 0] >> 1) == (rows[:, 5] >> 1)]
+    return float(np.mean((own[:, 8].astype(np.int64) - own[:, 7]) / own[:, 6])) if len(own) else None
+
+
+def measure(name, sb, reps, params, align, occ_frac_ppm=0, rescue=(0, 0), lookback=0):
     c = api.Context(0)
     c.set_reads(sb.seq, sb.qual, sb.off)
+    if lookback:
+        c.set_chain_lookback(lookback)
+        name += f" lookback={lookback}"
     if rescue[0]:
         c.set_seed_rescue(*rescue)
         name += f" occ_dist={rescue[0]}"
@@ -100,6 +135,8 @@ def measure_on(c, name, sb, reps, params, align):
     res = {"set": name, "reads": sb.n_reads, "bases": bases, **sizes, "records": len(rows), "params": params, "reps": reps,
            "seconds_median": t, "seconds_min": min(times), "seconds_max": max(times), "bases_per_s": bases / t,
            "anchors_per_s": sizes.get("anchors", 0) / t, "records_per_s": len(rows) / t}
+    if isinstance(sb, Tandem):
+        res["pair_coverage"] = pair_coverage(rows)
     if align and len(rows):
         c.align(rows[: min(len(rows), 4096)])
         at = []
@@ -126,20 +163,30 @@ def main():
     ap.add_argument("--occ-frac-ppm", type=int, default=0, help="also measure with the cut taken from the index (5000 = minimap2 -f0.005)")
     ap.add_argument("--occ-dist", type=int, default=0, help="rescue high-frequency minimizers, about one per N bases (200 = minimap2 -e200)")
     ap.add_argument("--rescue-max-occ", type=int, default=0, help="with --occ-dist: hashes above this many occurrences are never rescued (0: 4095)")
+    ap.add_argument("--lookback", type=int, default=0, help="chain over the N nearest predecessors (a multiple of 64 in 64 .. 1024; 0: the default, 64)")
+    ap.add_argument("--tandem", action="store_true", help="only the tandem shape: read pairs around tandem arrays")
+    ap.add_argument("--tandem-pairs", type=int, default=64)
+    ap.add_argument("--tandem-unit", type=int, default=40)
+    ap.add_argument("--tandem-copies", type=int, default=30)
+    ap.add_argument("--tandem-flank", type=int, default=2400)
     ap.add_argument("--deep", action="store_true", help="only the deep shape: one short genome under many reads")
     ap.add_argument("--deep-reads", type=int, default=200)
     ap.add_argument("--deep-len", type=int, default=400)
     a = ap.parse_args()
     rescue = (a.occ_dist, a.rescue_max_occ)
+    if a.tandem:
+        measure("tandem", Tandem(a.tandem_pairs, a.tandem_unit, a.tandem_copies, a.tandem_flank), a.reps, dict(k=15, w=5, max_occ=4096, min_score=100),
+                not a.no_align, a.occ_frac_ppm, rescue, a.lookback)
+        return
     if a.deep:
-        measure("deep", Deep(a.deep_reads, a.deep_len), a.reps, dict(k=15, w=5, max_occ=128, min_score=60), not a.no_align, a.occ_frac_ppm, rescue)
+        measure("deep", Deep(a.deep_reads, a.deep_len), a.reps, dict(k=15, w=5, max_occ=128, min_score=60), not a.no_align, a.occ_frac_ppm, rescue, a.lookback)
         return
     if a.targets:
         measure("bench shape", synth.generate_parallel(a.targets, a.target_len, a.overlaps, chunk=64), a.reps,
-                dict(max_occ=128, min_score=100), not a.no_align, a.occ_frac_ppm, rescue)
+                dict(max_occ=128, min_score=100), not a.no_align, a.occ_frac_ppm, rescue, a.lookback)
     if a.long_targets:
         measure(">= 30 kb", synth.generate_parallel(a.long_targets, a.long_len, 16, chunk=4, flank_min=200, flank_max=400), a.reps,
-                dict(max_occ=128), not a.no_align, a.occ_frac_ppm, rescue)
+                dict(max_occ=128), not a.no_align, a.occ_frac_ppm, rescue, a.lookback)
 
 
 if __name__ == "__main__":
