@@ -32,17 +32,20 @@ def odd_bytes(mask) -> np.ndarray:
 
 
 # ---- the specification ------------------------------------------------------------------------------------------------------------------
-def filter_pairs(fields: dict, core) -> dict:
-    """the fields of an OverlapPairs handle (pair_cases.pairs_fields / stepwise) under a core mask"""
+def filter_pairs(fields: dict, core, _targets_only: bool = False) -> dict:
+    """the fields of an OverlapPairs handle (pair_cases.pairs_fields / stepwise) under a core mask.  _targets_only is not part of the
+    specification: the mutant that wants a pair only where its primary's target is core (tests/test_combo_host.py)."""
     c = np.asarray(core) != 0
     pr = np.asarray(fields["primaries"])
     P = len(pr)
-    keep = c[pr[:, 5]] | c[pr[:, 0]] if P else np.zeros(0, bool)
+    keep = (c[pr[:, 5]] if _targets_only else c[pr[:, 5]] | c[pr[:, 0]]) if P else np.zeros(0, bool)
     new = np.cumsum(keep) - 1                                      # the new index of a kept primary
     Pn = int(keep.sum())
     rids, aln_off, rec = np.asarray(fields["rids"]), np.asarray(fields["aln_off"]), np.asarray(fields["rec_of_row"])
     row_t = np.repeat(rids, np.diff(aln_off.astype(np.int64)))     # the target of every row
     keep_row = c[row_t] if len(row_t) else np.zeros(0, bool)
+    if _targets_only and len(row_t):
+        keep_row = keep_row & keep[rec.astype(np.int64) % P]
     r = rec[keep_row].astype(np.int64)
     assert keep[r % P].all() if len(r) else True                   # a row with a core target belongs to a kept pair
     new_rec = np.where(r < P, new[r % P], Pn + new[r % P]) if len(r) else np.zeros(0, np.int64)

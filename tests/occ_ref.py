@@ -67,9 +67,10 @@ def census(read_codes, occ_frac_ppm: int, **kw):
     return histogram(counts), figures(counts, occ_frac_ppm, int(kw.get("max_occ") or 0))
 
 
-def find_overlaps(read_codes, occ_frac_ppm: int, stats: dict | None = None, **kw):
-    """overlap_ref.find_overlaps with the cut taken from the index: (rids, rows, aln_off, scores), cut"""
+def find_overlaps(read_codes, occ_frac_ppm: int, stats: dict | None = None, lookback: int | None = R.LOOKBACK, **kw):
+    """overlap_ref.find_overlaps with the cut taken from the index: (rids, rows, aln_off, scores), cut.  lookback: overlap_ref.find_overlaps'
+    own, handed on as it is (the census does not see it)."""
     _, fig = census(read_codes, occ_frac_ppm, **kw)
     if stats is not None:
         stats["occ"] = fig
-    return R.find_overlaps(read_codes, stats=stats, **dict(kw, max_occ=fig["cut"])), fig["cut"]
+    return R.find_overlaps(read_codes, lookback=lookback, stats=stats, **dict(kw, max_occ=fig["cut"])), fig["cut"]

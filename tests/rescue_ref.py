@@ -45,23 +45,25 @@ def streak_quota(ps: int, pe: int, occ_dist: int, _round_down: bool = False) -> 
     return (pe - ps) // occ_dist if _round_down else (2 * (pe - ps) + occ_dist) // (2 * occ_dist)
 
 
-def streaks(occ, pos, length: int, cut: int, rmax: int):
+def streaks(occ, pos, length: int, cut: int, rmax: int, _band: int | None = None):
     """the streaks of one read (occ, pos in ascending pos): a list of (member indices int64, ps, pe)"""
     out, cur, ps = [], [], 0
+    lo = cut if _band is None else _band         # (the mutant's H begins above _band, not above the cut)
     for i, (c, p) in enumerate(zip(occ, pos)):
         if 2 <= c <= cut:
             if cur:
                 out.append((np.array(cur, np.int64), ps, int(p)))
                 cur = []
             ps = int(p)
-        elif cut < c <= rmax:
+        elif lo < c <= rmax:
             cur.append(i)
     if cur:
         out.append((np.array(cur, np.int64), ps, int(length)))
     return out
 
 
-def rescue_flags(h, rid, pos, lens, cut: int, occ_dist: int, rescue_max_occ: int | None = None, _larger_pos: bool = False, _round_down: bool = False):
+def rescue_flags(h, rid, pos, lens, cut: int, occ_dist: int, rescue_max_occ: int | None = None, _larger_pos: bool = False, _round_down: bool = False,
+                 _band: int | None = None):
     """(occ int64 [n], rescued u8 [n]) for minimizers sorted by (rid, pos), as overlap_ref.sketch_store returns them"""
     d, rmax = check(occ_dist, rescue_max_occ)
     occ = occurrences(h)
@@ -72,7 +74,7 @@ def rescue_flags(h, rid, pos, lens, cut: int, occ_dist: int, rescue_max_occ: int
     bounds = np.searchsorted(rid, np.arange(len(lens) + 1))
     for r in range(len(lens)):
         b, e = int(bounds[r]), int(bounds[r + 1])
-        for idx, ps, pe in streaks(occ[b:e], pos[b:e], int(lens[r]), cut, rmax):
+        for idx, ps, pe in streaks(occ[b:e], pos[b:e], int(lens[r]), cut, rmax, _band):
             m = streak_quota(ps, pe, d, _round_down)
             if m >= len(idx):
                 take = idx
@@ -83,12 +85,12 @@ def rescue_flags(h, rid, pos, lens, cut: int, occ_dist: int, rescue_max_occ: int
     return occ, flag
 
 
-def anchors_rescue(h, rid, pos, st, lens, k: int, cut: int, flag, rescue_max_occ: int | None = None, _both: bool = False):
+def anchors_rescue(h, rid, pos, st, lens, k: int, cut: int, flag, rescue_max_occ: int | None = None, _both: bool = False, _band: int | None = None):
     """overlap_ref.anchors plus the anchors of the hashes above the cut: (t, q, rel, tpos, qpos) int64 rows sorted by that tuple"""
     rmax = check(1, rescue_max_occ)[1]
     a = [_PLAIN_ANCHORS(h, rid, pos, st, lens, k, cut)]
     occ = occurrences(h)
-    high = np.flatnonzero((occ > cut) & (occ <= rmax))
+    high = np.flatnonzero((occ > (cut if _band is None else _band)) & (occ <= rmax))
     if len(high):
         o = high[np.lexsort((pos[high], rid[high], h[high]))]
         hh, rr, pp, ss, ff = h[o], rid[o], pos[o], st[o].astype(np.int64), np.asarray(flag)[o].astype(bool)
@@ -106,9 +108,12 @@ def anchors_rescue(h, rid, pos, st, lens, k: int, cut: int, flag, rescue_max_occ
 
 
 def find_overlaps_rescue(read_codes, occ_dist: int, rescue_max_occ: int | None = None, occ_frac_ppm: int = 0, stats: dict | None = None,
-                         _larger_pos: bool = False, _round_down: bool = False, _both: bool = False, **kw):
+                         lookback: int | None = R.LOOKBACK, _larger_pos: bool = False, _round_down: bool = False, _both: bool = False,
+                         _lookback_64: bool = False, _band_from_max_occ: bool = False, **kw):
     """overlap_ref.find_overlaps with the rescue: (rids, rows, aln_off, scores).  occ_frac_ppm != 0: the cut is occ_ref's, max_occ its ceiling.
-    stats gains cut, occ, rescued (the flags) and high (the H minimizers)."""
+    lookback: overlap_ref.find_overlaps' own, handed on as it is.  stats gains cut, occ, rescued (the flags) and high (the H minimizers).
+    _lookback_64: with the rescue on, the chains look back 64 whatever was asked; _band_from_max_occ: under occ_frac_ppm, H begins above
+    max_occ instead of above the cut (what lies between is neither used nor rescued)."""
     P = R.params(**{n: v for n, v in kw.items() if not (occ_frac_ppm and n == "max_occ")})
     lens = np.array([len(c) for c in read_codes], np.int64)
     h, rid, pos, st = R.sketch_store(read_codes, P["k"], P["w"])
@@ -116,17 +121,18 @@ def find_overlaps_rescue(read_codes, occ_dist: int, rescue_max_occ: int | None =
     if occ_frac_ppm:
         import occ_ref as OR
         cut = OR.occ_cut(OR.run_counts(h), occ_frac_ppm, int(kw.get("max_occ") or 0))
-    occ, flag = rescue_flags(h, rid, pos, lens, cut, occ_dist, rescue_max_occ, _larger_pos, _round_down)
+    band = int(kw["max_occ"]) if _band_from_max_occ and occ_frac_ppm and kw.get("max_occ") else None
+    occ, flag = rescue_flags(h, rid, pos, lens, cut, occ_dist, rescue_max_occ, _larger_pos, _round_down, band)
     if stats is not None:
         rmax = check(occ_dist, rescue_max_occ)[1]
         stats.update(cut=cut, occ=occ, rescued=flag, high=int(((occ > cut) & (occ <= rmax)).sum()))
     if not check(occ_dist, rescue_max_occ)[0]:
-        return R.find_overlaps(read_codes, stats=stats, **dict(kw, max_occ=cut))
+        return R.find_overlaps(read_codes, lookback=lookback, stats=stats, **dict(kw, max_occ=cut))
 
     def with_rescue(h_, rid_, pos_, st_, lens_, k_, max_occ_):
-        return anchors_rescue(h_, rid_, pos_, st_, lens_, k_, max_occ_, flag, rescue_max_occ, _both)
+        return anchors_rescue(h_, rid_, pos_, st_, lens_, k_, max_occ_, flag, rescue_max_occ, _both, band)
     R.anchors = with_rescue              # everything behind the anchors is overlap_ref.find_overlaps itself, not a copy of it
     try:
-        return R.find_overlaps(read_codes, stats=stats, **dict(kw, max_occ=cut))
+        return R.find_overlaps(read_codes, lookback=R.LOOKBACK if _lookback_64 else lookback, stats=stats, **dict(kw, max_occ=cut))
     finally:
         R.anchors = _PLAIN_ANCHORS
