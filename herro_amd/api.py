@@ -59,6 +59,7 @@ EXPORTS = [
     "herro_clusters_comp", "herro_clusters_level", "herro_clusters_stats", "herro_clusters_part_stats", "herro_clusters_mask", "herro_clusters_free",
     "herro_job_fasta_dev", "herro_fasta_text_data", "herro_fasta_text_len", "herro_fasta_text_target_end", "herro_fasta_text_stats", "herro_fasta_text_free",
     "herro_debug_set_fasta_chunk", "herro_chop_plan",
+    "herro_set_index_params", "herro_overlaps_index_blocks", "herro_pairs_index_blocks", "herro_index_plan",
 ]
 
 
@@ -119,6 +120,10 @@ class SeedRescueParams(C.Structure):  # herro_seed_rescue_params (occ_dist 0 = o
 
 class ChainParams(C.Structure):  # herro_chain_params (lookback 0 = 64)
     _fields_ = [("lookback", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class IndexParams(C.Structure):  # herro_index_params (max_kmers 0 = off, occ_ranges 0 = chosen by the library)
+    _fields_ = [("max_kmers", C.c_uint64), ("occ_ranges", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class ExtendParams(C.Structure):  # herro_extend_params (0 = the field's default)
@@ -347,6 +352,16 @@ def lib():
         try:   # (an older build selected by HERRO_LIB lacks the chain look-back: every call that leaves it at 64 still runs)
             L.herro_set_chain_params.argtypes = [vp, vp]
             L.herro_debug_chain.argtypes = [vp, u64, vp, vp, vp, vp, vp]
+        except AttributeError:
+            if not os.environ.get("HERRO_LIB"):
+                raise
+        try:   # (an older build selected by HERRO_LIB lacks the index in parts: every call that leaves it off still runs)
+            L.herro_set_index_params.argtypes = [vp, vp]
+            for f in (L.herro_overlaps_index_blocks, L.herro_pairs_index_blocks):
+                f.restype = u32
+                f.argtypes = [vp]
+            L.herro_index_plan.restype = C.c_int64
+            L.herro_index_plan.argtypes = [vp, u64, vp, u32, u32, u64, vp, u64]
         except AttributeError:
             if not os.environ.get("HERRO_LIB"):
                 raise
@@ -987,6 +1002,33 @@ class Context:
         finally:
             self.set_chain_lookback(before)
 
+    def set_index_parts(self, max_kmers: int | None = None, occ_ranges: int = 0):
+        """The index of every later find_overlaps / find_overlap_pairs of this context in parts of at most max_kmers k-mers (herro_set_index_params;
+        minimap2's -I): the store may then hold more than 2^32 k-mers, and the index arrays are those of one part.  The result is byte for byte the
+        unpartitioned call's for every max_kmers.  occ_ranges: the hash ranges of the occurrence pass, 0: chosen by the library.  max_kmers None or
+        0: off, the default, which runs the kernels that always ran.  max_kmers > 2^32 - 4096 or occ_ranges > 65536 is the library's
+        HERRO_E_INVALID, and the setting stays as it was.  DESIGN.md section 10, "An index in parts"."""
+        m, r = int(max_kmers or 0), int(occ_ranges or 0)
+        if not 0 <= m <= 0xFFFFFFFFFFFFFFFF or not 0 <= r <= 0xFFFFFFFF:
+            raise HerroError(-1, "index parts: max_kmers is an unsigned 64-bit value, occ_ranges an unsigned 32-bit one")
+        p = IndexParams(max_kmers=m, occ_ranges=r)
+        self._chk(self._l.herro_set_index_params(self.h, C.byref(p) if m or r else None))
+        self._index_parts = (m, r)
+
+    @contextlib.contextmanager
+    def _index_keywords(self, params: dict):
+        """index_kmers= / occ_ranges= of one finder call: taken out of params, set for the call, the context's setting restored behind it"""
+        if "index_kmers" not in params and "occ_ranges" not in params:
+            yield
+            return
+        before = getattr(self, "_index_parts", (0, 0))
+        m, r = params.pop("index_kmers", before[0]), params.pop("occ_ranges", before[1])
+        self.set_index_parts(m, r)
+        try:
+            yield
+        finally:
+            self.set_index_parts(*before)
+
     def chain(self, groups, **params):
         """Test hook (herro_debug_chain): the chain stage alone under the context's look-back, or the lookback= given here.  groups: a list of
         (tpos, qpos) array pairs, each not empty and strictly ascending by (tpos, qpos) with coordinates below 2^31; params: k, bandwidth,
@@ -1008,8 +1050,9 @@ class Context:
 
     def seed_rescue(self, **params):
         """The rescue alone (herro_debug_seed_rescue) under the context's setting, or the occ_dist= / rescue_max_occ= given here: for the
-        minimizers in sketch()'s order, (occ u32 = min(occurrences of the hash in the store, 65535), rescued u8)."""
-        with self._rescue_keywords(params):
+        minimizers in sketch()'s order, (occ u32 = min(occurrences of the hash in the store, 65535), rescued u8).  index_kmers= / occ_ranges=:
+        set_index_parts for this call alone — occ then comes from the occurrence pass over hash ranges, the rescue runs block by block."""
+        with self._rescue_keywords(params), self._index_keywords(params):
             p = self._overlap_params(params)
             n = self._l.herro_debug_seed_rescue(self.h, C.byref(p), None, None, 0)
             if n < 0:
@@ -1026,13 +1069,14 @@ class Context:
         """Which reads of the store overlap, where, on which strand (herro_find_overlaps; the seeding and chaining of the
         `minimap2 -x ava-ont` run of mm2.rs:15-30).  params: k, w, max_occ, bandwidth, max_gap, min_score, min_anchors, occ_frac_ppm, and
         occ_dist / rescue_max_occ: set_seed_rescue for this call alone (the minimizers it rescued are left in self.last_rescued);
-        lookback: set_chain_lookback for this call alone.
+        lookback: set_chain_lookback for this call alone; index_kmers / occ_ranges: set_index_parts for this call alone (the read blocks of
+        the call are left in self.last_index_blocks, 0: the setting was off).
         The frequency cut the call used (max_occ, or the one occ_frac_ppm gave) is left in self.last_occ_cut.
         Returns (rids u32 [n_targets], rows u32 [n, 10] in create_job's layout with cigar_len 0, aln_off u64 [n_targets + 1],
         scores i32 [n]): rows goes into Context.align, (rids, aln_off) with its result into aligned_job_args.
         core: u8 [n_reads], non-zero = the read is a target (herro_find_overlaps_core): the records whose tid is core; None: all."""
         h = C.c_void_p()
-        with self._rescue_keywords(params), self._chain_keywords(params):   # (lookback=: set_chain_lookback for this call alone)
+        with self._rescue_keywords(params), self._chain_keywords(params), self._index_keywords(params):   # (each set for this call alone)
             p = self._overlap_params(params)
             if core is None:
                 self._chk(self._l.herro_find_overlaps(self.h, C.byref(p), C.byref(h)))
@@ -1045,6 +1089,8 @@ class Context:
                 self.last_occ_cut = int(self._l.herro_overlaps_occ_cut(h))
             if hasattr(self._l, "herro_overlaps_rescued"):
                 self.last_rescued = int(self._l.herro_overlaps_rescued(h))
+            if hasattr(self._l, "herro_overlaps_index_blocks"):
+                self.last_index_blocks = int(self._l.herro_overlaps_index_blocks(h))
             rids = np.ctypeslib.as_array(C.cast(self._l.herro_overlaps_target_ids(h), C.POINTER(C.c_uint32)), (nt,)).copy() if nt else np.zeros(0, np.uint32)
             aln_off = np.ctypeslib.as_array(C.cast(self._l.herro_overlaps_aln_off(h), C.POINTER(C.c_uint64)), (nt + 1,)).copy()
             rows = _aln_rows(self._l.herro_overlaps_alignments(h), n)
@@ -1122,7 +1168,7 @@ class Context:
         e = ExtendParams(zdrop=int(zdrop), max_ext=int(max_ext))
         h = C.c_void_p()
         flags = 0 if extend else PAIRS_NO_EXTEND
-        with self._rescue_keywords(params), self._chain_keywords(params):   # (occ_dist= / rescue_max_occ= / lookback=: set for this call alone)
+        with self._rescue_keywords(params), self._chain_keywords(params), self._index_keywords(params):   # (occ_dist= / rescue_max_occ= / lookback= / index_kmers= / occ_ranges=: set for this call alone)
             p = self._overlap_params(params)
             if core is None:
                 self._chk(self._l.herro_find_overlap_pairs(self.h, C.byref(p), C.byref(e), flags, C.byref(h)))
@@ -1180,10 +1226,12 @@ class Context:
 
     def occ_census(self, **params):
         """The census and the pick of occ_frac_ppm alone (herro_debug_occ_census): (hist u32 [65536] over min(occurrences, 65535) of the
-        distinct minimizer hashes, dict(cut, distinct, cut_runs, cut_minimizers))."""
-        p = self._overlap_params(params)
+        distinct minimizer hashes, dict(cut, distinct, cut_runs, cut_minimizers)).  index_kmers= / occ_ranges=: set_index_parts for this call
+        alone — the census is then the occurrence pass's, over hash ranges (a bin beyond 32 bits comes back as 2^32 - 1)."""
         hist, out = np.zeros(65536, np.uint32), np.zeros(4, np.uint64)
-        self._chk(self._l.herro_debug_occ_census(self.h, C.byref(p), hist.ctypes.data, out.ctypes.data))
+        with self._index_keywords(params):
+            p = self._overlap_params(params)
+            self._chk(self._l.herro_debug_occ_census(self.h, C.byref(p), hist.ctypes.data, out.ctypes.data))
         return hist, dict(zip(("cut", "distinct", "cut_runs", "cut_minimizers"), (int(x) for x in out)))
 
     def sketch(self, **params):
@@ -1512,6 +1560,7 @@ class OverlapPairs:
         self.n_rows = int(L.herro_pairs_n_rows(h)) if hasattr(L, "herro_pairs_n_rows") else 2 * n
         self.occ_cut = int(L.herro_pairs_occ_cut(h)) if hasattr(L, "herro_pairs_occ_cut") else 0
         self.rescued = int(L.herro_pairs_rescued(h)) if hasattr(L, "herro_pairs_rescued") else 0   # minimizers the rescue kept (0: off)
+        self.index_blocks = int(L.herro_pairs_index_blocks(h)) if hasattr(L, "herro_pairs_index_blocks") else 0   # read blocks of an index in parts (0: off)
 
         def arr(ptr, ct, dt, shape):
             out = np.zeros(shape, dt)
@@ -1828,6 +1877,27 @@ def chop_plan(lengths, chop_len: int = 0, min_length: int = 0, line_width: int =
     the sequence — grouped by sequence, piece_off u64 [n + 1], ChopStats); ValueError with the library's message on a refusal."""
     ln = np.ascontiguousarray(lengths, np.uint64)
     return _chop_plan(lib(), ln, _chop_params(chop_len, min_length, line_width))
+
+
+def index_plan(lens, k: int = 25, w: int = 17, max_kmers: int = 0, ctx: "Context | None" = None) -> np.ndarray:
+    """The read blocks of an index in parts (herro_index_plan; host code, no device): cuts u64 [n_blocks + 1], ascending read ids from 0 to
+    len(lens) — block b is the reads cuts[b] .. cuts[b + 1] - 1; an empty store has no block.  The rule is include/herro_amd.h's, "an index in
+    parts".  ctx: the context to ask (a HostContext does); None: a device-free one made for the call."""
+    ln = np.ascontiguousarray(lens, np.uint32).reshape(-1)
+    own = ctx is None
+    if own:
+        ctx = HostContext(ln[:1] if len(ln) else np.ones(1, np.uint32))
+    try:
+        n = ctx._l.herro_index_plan(ctx.h, len(ln), ln.ctypes.data if len(ln) else None, int(k), int(w), int(max_kmers), None, 0)
+        if n < 0:
+            ctx._chk(int(n))
+        cuts = np.zeros(n + 1, np.uint64)
+        got = ctx._l.herro_index_plan(ctx.h, len(ln), ln.ctypes.data if len(ln) else None, int(k), int(w), int(max_kmers), cuts.ctypes.data, len(cuts))
+        assert got == n
+    finally:
+        if own:
+            ctx.close()
+    return cuts
 
 
 def _chop_plan(L, ln, p):

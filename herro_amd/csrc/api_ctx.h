@@ -169,7 +169,8 @@ struct herro_ctx {
   std::shared_ptr<void> store_owner;
   herro_seed_rescue_params seed_rescue{};   // herro_set_seed_rescue: occ_dist 0 = off; rescue_max_occ as given (0 = 4095 where it is used)
   uint32_t chain_lookback = 64;             // herro_set_chain_params: the predecessors a chain step looks at, a multiple of 64 in 64 .. 1024
-  uint64_t debug_adapter_cap = 0;           // herro_debug_set_adapter_cap: hits the first scan's buffer of herro_find_adapters holds (0: the default)
+  herro_index_params index_parts{};         // herro_set_index_params: max_kmers 0 = off, the index of a finder call is built in one piece
+  uint64_t debug_adapter_cap = 0;          // herro_debug_set_adapter_cap: hits the first scan's buffer of herro_find_adapters holds (0: the default)
   std::shared_ptr<PinPool> text_pin = std::make_shared<PinPool>();   // herro_job_fasta_dev: where its texts land
   uint64_t debug_fasta_chunk = 0;           // herro_debug_set_fasta_chunk: text bytes of a chunk of herro_job_fasta_dev (0: a sixteenth of HERRO_FASTA_SCRATCH_MB)
   // model

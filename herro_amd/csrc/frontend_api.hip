@@ -1,6 +1,6 @@
 // frontend_api.hip — the C ABI's front end (include/herro_amd.h): reads alone -> overlap records -> their ops on the device.
 // herro_find_overlaps[_core], herro_extend_overlaps, herro_align_overlaps[_dev], herro_aligned_dev_*, herro_find_overlap_pairs[_core], herro_pairs_*, the PAF / .oec.zst
-// writer (herro_aligned_dev_paf, herro_pairs_paf, herro_pairs_write_alns) herro_set_seed_rescue, herro_set_chain_params and the test hooks herro_debug_sketch, herro_debug_occ_census, herro_debug_seed_rescue and herro_debug_chain.  Host C++ (compiled by
+// writer (herro_aligned_dev_paf, herro_pairs_paf, herro_pairs_write_alns) herro_set_seed_rescue, herro_set_chain_params, herro_set_index_params with herro_index_plan (csrc/index_plan.h), and the test hooks herro_debug_sketch, herro_debug_occ_census, herro_debug_seed_rescue and herro_debug_chain.  Host C++ (compiled by
 // hipcc) over overlap_dev.hip, align_dev.hip and paf_dev.hip; contexts, the model and jobs are herro_api.hip.  Ahead of them all, for raw reads:
 // herro_find_adapters and its handle, over adapter_dev.hip (the plan and the cut are host code: fastx.cpp), and herro_store_cut with its test hook
 // herro_debug_store_copy, over store_dev.hip: the store cut to the plan's pieces on the device.  The primitives every device stage stands on have hooks of
@@ -21,6 +21,7 @@
 #include "cluster_plan.h"
 #include "dev_bufs.h"
 #include "fasta_dev.h"
+#include "index_plan.h"
 #include "overlap_dev.h"
 #include "paf_dev.h"
 #include "store_dev.h"
@@ -181,6 +182,8 @@ int overlap_params(herro_ctx* ctx, const herro_overlap_params* in, herro::OvlPar
   P.occ_dist = ctx->seed_rescue.occ_dist;       // herro_set_seed_rescue (validated there)
   P.rescue_max_occ = ctx->seed_rescue.rescue_max_occ ? ctx->seed_rescue.rescue_max_occ : 4095;
   P.lookback = ctx->chain_lookback;             // herro_set_chain_params (validated there)
+  P.index_kmers = ctx->index_parts.max_kmers;   // herro_set_index_params (validated there)
+  P.occ_ranges = ctx->index_parts.occ_ranges;
   if (P.occ_frac_ppm > 999999) {
     ctx->err = "overlap parameters: occ_frac_ppm must be below 1000000 (0: the fixed cut max_occ)";
     return HERRO_E_INVALID;
@@ -203,6 +206,9 @@ void print_ovl_stats(const herro::OvlParams& P, const herro::OvlStats& stats) {
             (unsigned long long)stats.resc_anchors);
   if (P.lookback != herro::OVL_LOOKBACK)
     fprintf(stderr, "OVLCHAIN lookback=%u chained=%llu\n", P.lookback, (unsigned long long)stats.chained);
+  if (P.index_kmers)
+    fprintf(stderr, "OVLPART blocks=%llu pairs=%llu ranges=%llu peak_bytes=%llu\n", (unsigned long long)stats.blocks,
+            (unsigned long long)stats.block_pairs, (unsigned long long)stats.ranges, (unsigned long long)stats.peak_bytes);
 }
 
 // A call's core mask (n_reads bytes, non-zero: the read is a target) goes up once, into the call's scratch; NULL stays NULL: every read is core.
@@ -524,6 +530,7 @@ struct herro_overlaps {
   std::vector<int32_t> scores;
   uint32_t occ_cut = 0;                  // the frequency cut the call used
   uint32_t rescued = 0;                  // minimizers the rescue kept (herro_set_seed_rescue; 0: off)
+  uint32_t index_blocks = 0;             // read blocks of an index in parts (herro_set_index_params; 0: off)
 };
 
 int herro_find_overlaps(herro_ctx* ctx, const herro_overlap_params* params, herro_overlaps** out) { return herro_find_overlaps_core(ctx, params, nullptr, out); }
@@ -565,6 +572,7 @@ int herro_find_overlaps_core(herro_ctx* ctx, const herro_overlap_params* params,
   auto* h = new herro_overlaps();
   h->occ_cut = (uint32_t)stats.occ_cut;
   h->rescued = (uint32_t)stats.rescued;
+  h->index_blocks = P.index_kmers ? (uint32_t)stats.blocks : 0;
   h->alns.reserve(recs.size());
   h->scores.reserve(recs.size());
   for (const Rec& r : recs) {
@@ -585,6 +593,7 @@ const herro_alignment* herro_overlaps_alignments(const herro_overlaps* o) { retu
 const int32_t* herro_overlaps_scores(const herro_overlaps* o) { return o ? o->scores.data() : nullptr; }
 uint32_t herro_overlaps_occ_cut(const herro_overlaps* o) { return o ? o->occ_cut : 0; }
 uint32_t herro_overlaps_rescued(const herro_overlaps* o) { return o ? o->rescued : 0; }
+uint32_t herro_overlaps_index_blocks(const herro_overlaps* o) { return o ? o->index_blocks : 0; }
 void herro_overlaps_free(herro_overlaps* o) { delete o; }
 
 // The rescue of high-frequency minimizers is a setting of the context (include/herro_amd.h): overlap_params hands it to every finder call.
@@ -614,6 +623,37 @@ int herro_set_chain_params(herro_ctx* ctx, const herro_chain_params* params) {
   return HERRO_OK;
 }
 
+// The index in parts is a setting of the context too (include/herro_amd.h, "an index in parts"): overlap_params hands it to every finder call.
+int herro_set_index_params(herro_ctx* ctx, const herro_index_params* params) {
+  if (!ctx) return HERRO_E_INVALID;
+  const herro_index_params off{};
+  const herro_index_params& p = params ? *params : off;
+  if (p.max_kmers > herro::OVL_MAX_KMERS || p.occ_ranges > herro::INDEX_MAX_RANGES || p.reserved) {
+    ctx->err = "herro_set_index_params: max_kmers <= 2^32 - 4096 (0: off), occ_ranges <= 65536 (0: chosen by the library), reserved 0";
+    return HERRO_E_INVALID;
+  }
+  ctx->index_parts = p;
+  return HERRO_OK;
+}
+
+// The block rule alone (csrc/index_plan.h): host code, works on a context without a device.
+int64_t herro_index_plan(herro_ctx* ctx, uint64_t n_reads, const uint32_t* read_len, uint32_t k, uint32_t w, uint64_t max_kmers, uint64_t* cuts, uint64_t cap) {
+  if (!ctx) return HERRO_E_INVALID;
+  if ((n_reads && !read_len) || k < 5 || k > 31 || w < 1 || w > 64 || max_kmers > herro::OVL_MAX_KMERS || n_reads > herro::OVL_MAX_READS) {
+    ctx->err = "herro_index_plan: lengths for every read, 5 <= k <= 31, 1 <= w <= 64, max_kmers <= 2^32 - 4096, at most 2^31 - 1 reads";
+    return HERRO_E_INVALID;
+  }
+  std::vector<uint64_t> c, kmers;
+  herro::index_plan(n_reads, read_len, k, w, max_kmers, c, &kmers);
+  uint64_t bi = 0, bj = 0;
+  if (herro::index_plan_overflow(kmers, herro::OVL_MAX_KMERS, bi, bj)) {
+    ctx->err = herro::index_plan_overflow_text(c, bi, bj);
+    return HERRO_E_UNSUPPORTED;
+  }
+  if (cuts && c.size() <= cap) std::memcpy(cuts, c.data(), 8 * c.size());
+  return (int64_t)c.size() - 1;
+}
+
 // ---- pair overlaps ("Pairs on the device"): reads -> one record per pair and the table of its two rows -> mirrored alignments ----
 struct herro_pairs {
   herro_ctx* ctx = nullptr;
@@ -626,6 +666,7 @@ struct herro_pairs {
   std::vector<uint32_t> rec_of_row;      // [n_rows]: 2 P, fewer with a core mask
   uint32_t occ_cut = 0;                  // the frequency cut the finder used; 0: a handle over the caller's table
   uint32_t rescued = 0;                  // minimizers the rescue kept; 0: off, or a handle over the caller's table
+  uint32_t index_blocks = 0;             // read blocks of an index in parts; 0: off, or a handle over the caller's table
 };
 
 int herro_find_overlap_pairs(herro_ctx* ctx, const herro_overlap_params* params, const herro_extend_params* eparams, uint32_t flags, herro_pairs** out) {
@@ -658,6 +699,7 @@ int herro_find_overlap_pairs_core(herro_ctx* ctx, const herro_overlap_params* pa
   h->ctx = ctx;
   h->occ_cut = (uint32_t)stats.occ_cut;
   h->rescued = (uint32_t)stats.rescued;
+  h->index_blocks = P.index_kmers ? (uint32_t)stats.blocks : 0;
   if (int rc = overlap_rc(ctx, herro::ovl_row_table(recs, ctx->n_reads, d_core, ctx->stream, h->rids, h->aln_off, h->rec_of_row, msg), msg)) return rc;
   const uint32_t n = (uint32_t)recs.n;   // (<= 2^31 - 1: ovl_find_pairs)
   h->ext.assign((size_t)n * 4, 0);
@@ -798,6 +840,7 @@ const uint32_t* herro_pairs_rec_of_row(const herro_pairs* p) { return p ? p->rec
 uint64_t herro_pairs_n_rows(const herro_pairs* p) { return p ? p->rec_of_row.size() : 0; }
 uint32_t herro_pairs_occ_cut(const herro_pairs* p) { return p ? p->occ_cut : 0; }
 uint32_t herro_pairs_rescued(const herro_pairs* p) { return p ? p->rescued : 0; }
+uint32_t herro_pairs_index_blocks(const herro_pairs* p) { return p ? p->index_blocks : 0; }
 void herro_pairs_free(herro_pairs* p) { delete p; }
 
 // ---- PAF / .oec.zst of found alignments (paf_dev.hip) ----------------------------------------------------------------------------

@@ -22,12 +22,19 @@ constexpr uint32_t OVL_MAX_READ_LEN = 0x7fffffffu;  // pos << 1 | strand is one 
 constexpr uint32_t OVL_MAX_READS = 0x7fffffffu;     // q << 1 | rel is one 33-bit field of the anchor key
 
 // defaults already filled in.  occ_frac_ppm 0: runs longer than max_occ are dropped.  Else the cut is the census's (ovl_occ_census) and max_occ
-// its ceiling, 0 = none.
+// its ceiling, 0 = none.  With index_kmers != 0 ovl_occ_census, ovl_seed_rescue, ovl_find and ovl_find_pairs take the occurrences from a pass
+// over hash ranges and run per pair of read blocks; what they return is what they return without it (ovl_sketch and ovl_chain_groups ignore it).
 // occ_dist != 0: the rescue of high-frequency minimizers (minimap2's -e, mm2.rs:24) — of a stretch of a read whose minimizers all lie
 // above the cut, the least frequent ones stay, about one per occ_dist bases, among those of at most rescue_max_occ occurrences (filled in: never 0).
 // lookback: the predecessors a chain step looks at, a multiple of 64 in 64 .. OVL_MAX_LOOKBACK ("A longer look-back"); 64 runs
 // k_chain and everything else as it was, any other value k_chain_far.
-struct OvlParams { uint32_t k, w, max_occ, bandwidth, max_gap, min_score, min_anchors, occ_frac_ppm, occ_dist = 0, rescue_max_occ = 0, lookback = OVL_LOOKBACK; };
+// index_kmers != 0: the index is built in parts ("An index in parts"; herro_set_index_params) — the most k-mers one index of the call
+// covers, at most OVL_MAX_KMERS; occ_ranges: the hash ranges of the occurrence pass, 0 = chosen here.  0 runs everything as it was.
+struct OvlParams {
+  uint32_t k, w, max_occ, bandwidth, max_gap, min_score, min_anchors, occ_frac_ppm, occ_dist = 0, rescue_max_occ = 0, lookback = OVL_LOOKBACK;
+  uint64_t index_kmers = 0;
+  uint32_t occ_ranges = 0;
+};
 
 constexpr uint32_t OVL_OCC_BINS = 65536;       // census counts of a hash run: min(length, 65535)
 constexpr uint32_t OVL_OCC_FLOOR = 10;         // the least cut the fraction may give (minimap2's min_mid_occ)
@@ -51,6 +58,9 @@ struct OvlStats {
   uint64_t occ_cut = 0;                                       // the cut the call used: max_occ, or the census's
   uint64_t distinct = 0, cut_runs = 0, cut_minimizers = 0;    // occ_frac_ppm != 0: hash runs of the index, those above the cut, their minimizers
   uint64_t resc_high = 0, rescued = 0, resc_anchors = 0;      // occ_dist != 0: minimizers between the cut and rescue_max_occ, the rescued, the anchors of their runs
+  // index_kmers != 0: the read blocks, the block pairs run, the hash ranges run, the most device scratch the call held at once.  The figures above
+  // are then the sums over the parts and equal the unpartitioned call's, chunks excepted.
+  uint64_t blocks = 0, block_pairs = 0, ranges = 0, peak_bytes = 0;
 };
 
 enum { OVL_OK = 0, OVL_HIP = 1, OVL_UNSUPPORTED = 2 };

@@ -15,11 +15,15 @@
 //   k_chain      one wave64 per (t, q, rel) group: the 64 predecessors of an anchor are the 64 lanes.
 //   k_chain_far  OvlParams.lookback = 64 R > 64 only: k_chain with R rounds a step, the R blocks in front of the current one in an LDS ring.
 //   k_walk       back through the stored predecessors: first anchor, anchor count, coordinates.
+//   k_sketch_part, k_occ16, k_occ_pick64, k_part_cls, k_part_gather, k_part_runs, k_part_expand, k_rec_keys, k_rec_gather   OvlParams.index_kmers != 0
+//                only (herro_set_index_params): the occurrences of every minimizer's hash by hash range, then the stages above per pair of read
+//                blocks, a hash run judged by those occurrences ("an index in parts", below); host side: part_index, find_parts.
 // A core mask (one byte per read, non-zero: the read is a target) keeps k_runs / k_expand from creating an anchor between two non-core
 // reads, so everything behind the anchors sees wanted pairs only; without a mask (CORE = false) the two kernels are what they were.
 // Nothing an atomic orders reaches the output: the only atomics are integer sums (histograms, anchors per read).
 #include "overlap_dev.h"
 #include "dev_bufs.h"
+#include "index_plan.h"
 
 #include <algorithm>
 #include <climits>
@@ -891,6 +895,278 @@ __global__ __launch_bounds__(256) void k_row_write(const uint64_t* __restrict__ 
   if (i == 0) aln_off[tidx[n]] = n;
 }
 
+// ---- an index in parts (OvlParams.index_kmers != 0; DESIGN.md section 10, "An index in parts"; tests/index_parts_ref.py) ------------------------
+// Everything the finder takes from the whole store's index is occ(hash), the occurrences of a minimizer's hash in the store.  Pass A leaves
+// occ16[ordinal] = min(occ, 65535) for every minimizer, its ordinal being its place in the store's (rid, pos) order; pass B runs the finder per
+// pair of read blocks and judges every hash run by its members' occ16, never by its length inside the pair.  These kernels run only under the
+// setting: the ones above are launched exactly as before.
+
+// k_sketch over the tiles of one read block.  tile_off is the whole store's; u_at / f_at / cnt are the block's own slices, indexed by the tile
+// inside the block.  The window minimum is taken over all hashes; a hash range only filters what is selected.
+//   SKP_COUNT        cnt[tile] = the tile's minimizers
+//   SKP_COUNT_RANGE  cnt[tile] = those with h_lo <= hash <= h_hi
+//   SKP_WRITE_RANGE  the latter's hash and ordinal (ord_base + u_at[tile] + the rank in the tile), densely from out_base + f_at[tile] on
+//   SKP_WRITE_BLOCK  hash, meta and occ = occ16[ordinal] of all of them from out_base + u_at[tile] on; meta_loc (or NULL): meta with the read id
+//                    counted from the block's first read, which is what k_rescue is launched over
+enum { SKP_COUNT = 0, SKP_COUNT_RANGE = 1, SKP_WRITE_RANGE = 2, SKP_WRITE_BLOCK = 3 };
+struct SketchPart {
+  const uint64_t *words, *word_off, *base_off;
+  const uint32_t* tile_off;
+  uint32_t r_lo, r_hi, tile0, k, w;
+  uint64_t h_lo, h_hi;
+  const uint32_t *u_at, *f_at;
+  uint32_t* cnt;
+  uint64_t ord_base;
+  uint32_t out_base;
+  uint64_t *hash_out, *meta_out, *ord_out, *meta_loc;
+  uint32_t* occ_out;
+  const uint16_t* occ16;
+};
+
+template <int MODE>
+__global__ __launch_bounds__(SK_T) void k_sketch_part(const SketchPart a) {
+  __shared__ uint64_t sh[SK_H];
+  __shared__ uint64_t wm[SK_H];
+  __shared__ uint8_t ss[SK_H];
+  __shared__ uint32_t wc[2][4];
+  const uint32_t lt = blockIdx.x, b = a.tile0 + lt, tid = threadIdx.x;
+  const uint32_t k = a.k, w = a.w;
+  uint32_t lo_r = a.r_lo, hi_r = a.r_hi;      // largest r of the block with tile_off[r] <= b
+  while (hi_r - lo_r > 1) {
+    const uint32_t mid = lo_r + ((hi_r - lo_r) >> 1);
+    if (a.tile_off[mid] <= b) lo_r = mid; else hi_r = mid;
+  }
+  const uint32_t rid = lo_r;
+  const uint32_t len = (uint32_t)(a.base_off[rid + 1] - a.base_off[rid]);
+  const uint32_t nk = len - k + 1;            // >= w (the read has tiles)
+  const uint32_t base = (b - a.tile_off[rid]) * SK_T;
+  const uint64_t w0 = a.word_off[rid];
+  const uint64_t mask = (1ull << (2 * k)) - 1;
+  const uint32_t lo = base >= w - 1 ? base - (w - 1) : 0u;
+  const uint32_t hi = min(nk, base + SK_T + (w - 1));
+  for (uint32_t i = lo + tid; i < hi; i += SK_T) {
+    uint32_t s;
+    sh[i - lo] = kmer_hash(a.words, w0, i, k, mask, s);
+    ss[i - lo] = (uint8_t)s;
+  }
+  __syncthreads();
+  const uint32_t s_hi = min(nk - w, base + SK_T - 1);
+  for (uint32_t s = lo + tid; s <= s_hi; s += SK_T) {
+    uint64_t m = INF64;
+    for (uint32_t o = 0; o < w; o++) { const uint64_t v = sh[s - lo + o]; m = v < m ? v : m; }
+    wm[s - lo] = m;
+  }
+  __syncthreads();
+  const uint32_t j = base + tid;
+  bool sel = false;
+  uint64_t hj = INF64;
+  if (j < nk) {
+    hj = sh[j - lo];
+    if (hj != INF64) {
+      const uint32_t s0 = j >= w - 1 ? j - (w - 1) : 0u, s1 = min(j, nk - w);
+      for (uint32_t s = s0; s <= s1; s++) sel |= wm[s - lo] == hj;
+    }
+  }
+  const bool in_range = sel && hj >= a.h_lo && hj <= a.h_hi;
+  const uint64_t bal = __ballot(sel), bal_r = __ballot(in_range);
+  const uint32_t lane = tid & 63, wave = tid >> 6;
+  if (lane == 0) { wc[0][wave] = (uint32_t)__popcll(bal); wc[1][wave] = (uint32_t)__popcll(bal_r); }
+  __syncthreads();
+  uint32_t before = 0, total = 0, before_r = 0, total_r = 0;
+  for (uint32_t i = 0; i < 4; i++) {
+    if (i < wave) { before += wc[0][i]; before_r += wc[1][i]; }
+    total += wc[0][i];
+    total_r += wc[1][i];
+  }
+  if constexpr (MODE == SKP_COUNT) {
+    if (tid == 0) a.cnt[lt] = total;
+  } else if constexpr (MODE == SKP_COUNT_RANGE) {
+    if (tid == 0) a.cnt[lt] = total_r;
+  } else {
+    const uint32_t urank = a.u_at[lt] + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1));
+    if constexpr (MODE == SKP_WRITE_RANGE) {
+      if (in_range) {
+        const uint32_t at = a.out_base + a.f_at[lt] + before_r + (uint32_t)__popcll(bal_r & ((1ull << lane) - 1));
+        a.hash_out[at] = hj;
+        a.ord_out[at] = a.ord_base + urank;
+      }
+    } else if (sel) {
+      const uint32_t at = a.out_base + urank;
+      const uint64_t low = ((uint64_t)(j + k - 1) << 1) | ss[j - lo];
+      a.hash_out[at] = hj;
+      a.meta_out[at] = ((uint64_t)rid << 32) | low;
+      if (a.meta_loc) a.meta_loc[at] = ((uint64_t)(rid - a.r_lo) << 32) | low;
+      a.occ_out[at] = a.occ16[a.ord_base + urank];
+    }
+  }
+}
+
+// Pass A, behind the sort of a hash range by hash (run starts: k_heads, the scan, k_gstart): every member's occ16 at its ordinal — a run lies in
+// one range, so its length is the store's occ — and the run in the census, hist[min(length, 65535)] += 1, in 64-bit bins.
+__global__ __launch_bounds__(256) void k_occ16(const uint64_t* __restrict__ ord, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ gidx,
+                                               const uint32_t* __restrict__ rstart, uint32_t n, uint16_t* __restrict__ occ16,
+                                               unsigned long long* __restrict__ hist) {
+  __shared__ uint32_t h[OCC_LDS_BINS];
+  for (uint32_t b = threadIdx.x; b < OCC_LDS_BINS; b += 256) h[b] = 0;
+  __syncthreads();
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+    const uint32_t f = flag[i], r = gidx[i] + f - 1;
+    const uint32_t c = min(rstart[r + 1] - rstart[r], OVL_OCC_BINS - 1);
+    occ16[ord[i]] = (uint16_t)c;
+    if (f) {
+      if (c < OCC_LDS_BINS) atomicAdd(&h[c], 1u);
+      else atomicAdd(&hist[c], 1ull);
+    }
+  }
+  __syncthreads();
+  for (uint32_t b = threadIdx.x; b < OCC_LDS_BINS; b += 256)
+    if (h[b]) atomicAdd(&hist[b], (unsigned long long)h[b]);
+}
+
+// k_occ_pick over 64-bit bins (the singletons of a large store exceed 2^32): the same rule and occ_final_cut; n: the store's minimizers.
+__global__ __launch_bounds__(256) void k_occ_pick64(const unsigned long long* __restrict__ hist, uint64_t n, uint32_t ppm, uint32_t max_occ,
+                                                    uint64_t* __restrict__ occ) {
+  __shared__ unsigned long long sums[256];
+  __shared__ uint32_t s_q;
+  __shared__ unsigned long long s_runs, s_kept;
+  const uint32_t b0 = 256u * (255u - threadIdx.x);
+  if (threadIdx.x == 0) { s_q = OVL_OCC_BINS - 1; s_runs = 0; s_kept = 0; }
+  uint64_t s = 0;
+  for (uint32_t b = 0; b < 256; b++) s += hist[b0 + b];
+  sums[threadIdx.x] = s;
+  __syncthreads();
+  uint64_t above = 0, distinct = 0;             // above: the runs in all higher bins (the threads in front own them)
+  for (uint32_t t = 0; t < 256; t++) { const uint64_t v = sums[t]; if (t < threadIdx.x) above += v; distinct += v; }
+  const uint64_t drop = distinct * ppm / 1000000u;
+  uint32_t q = OVL_OCC_BINS;
+  for (uint32_t b = 256; b-- > 0 && above <= drop;) {
+    q = b0 + b;
+    above += hist[b0 + b];
+  }
+  if (q < OVL_OCC_BINS) atomicMin(&s_q, q);
+  __syncthreads();
+  const uint32_t cut = occ_final_cut(s_q, max_occ);
+  uint64_t runs = 0, kept = 0;
+  for (uint32_t b = 0; b < 256; b++) {
+    const uint32_t v = b0 + b;
+    const uint64_t c = hist[v];
+    if (v > cut) runs += c; else kept += (uint64_t)v * c;
+  }
+  if (runs) atomicAdd(&s_runs, (unsigned long long)runs);
+  if (kept) atomicAdd(&s_kept, (unsigned long long)kept);
+  __syncthreads();
+  if (threadIdx.x == 0) { occ[0] = cut; occ[1] = distinct; occ[2] = s_runs; occ[3] = n - s_kept; }
+}
+
+// Pass B.  The class of a minimizer of a block pair from its occ alone, in (rid, pos) order: 0 — its hash is not used (a singleton, above the cut
+// and not rescuable), 1 — used (2 <= occ <= cut), 2 — cut < occ <= rmax and not rescued, 3 — rescued.  resc NULL / rmax 0: no rescue.  idx[p] = p,
+// the payload of the sort by hash.  occ: where k_occ_pick64 left the cut, or NULL — the cut is max_occ.
+__global__ __launch_bounds__(256) void k_part_cls(const uint32_t* __restrict__ occ_rp, const uint8_t* __restrict__ resc_rp, uint32_t n, uint32_t max_occ,
+                                                  const uint64_t* __restrict__ occ, uint32_t rmax, uint8_t* __restrict__ cls, uint64_t* __restrict__ idx) {
+  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= n) return;
+  const uint32_t cut = occ ? (uint32_t)occ[0] : max_occ;
+  const uint32_t c = occ_rp[p];
+  uint8_t v = 0;
+  if (c >= 2 && c <= cut) v = 1;
+  else if (resc_rp && c > cut && c <= rmax) v = resc_rp[p] ? 3 : 2;
+  cls[p] = v;
+  idx[p] = p;
+}
+
+// behind the sort: meta and class in hash order
+__global__ __launch_bounds__(256) void k_part_gather(const uint64_t* __restrict__ idx, const uint64_t* __restrict__ meta, const uint8_t* __restrict__ cls,
+                                                     uint32_t n, uint64_t* __restrict__ meta_s, uint8_t* __restrict__ cls_s) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t p = idx[i];
+  meta_s[i] = meta[p];
+  cls_s[i] = cls[p];
+}
+
+// Does occurrence x (read t, class cx >= 1, t in front of `split` where split != 0) have an anchor with the later occurrence y of its run?
+// The pair rule: y lies in another read — behind t, the run is in (rid, pos) order —; split != 0 (blocks i < j, split = block j's first read): y
+// lies in block j; a run above the cut: one of the two is rescued; CORE: one of the two reads is core.
+template <bool CORE>
+__device__ inline bool part_pair_ok(uint32_t t, bool t_core, uint32_t cx, uint64_t my, uint32_t cy, uint32_t split, const uint8_t* __restrict__ core) {
+  const uint32_t q = (uint32_t)(my >> 32);
+  if (q == t || q < split) return false;
+  if (cx >= 2 && cx != 3 && cy != 3) return false;
+  if constexpr (CORE) {
+    if (!t_core && core[q] == 0) return false;
+  }
+  return true;
+}
+
+// k_runs for a block pair, one thread per occurrence: it walks its run to the end — at most max(cut, rmax) steps: a used run has no more members
+// in the whole store — and counts the partners the pair rule gives it.  cnt is cleared before the launch; per_read is indexed from read t0, the
+// first of block i, where every target of the pair lies; stat[2] sums the anchors of the runs above the cut.
+template <bool CORE>
+__global__ __launch_bounds__(256) void k_part_runs(const uint64_t* __restrict__ hash, const uint64_t* __restrict__ meta, const uint8_t* __restrict__ cls,
+                                                   uint32_t n, uint32_t split, uint32_t t0, uint32_t* __restrict__ cnt, uint32_t* __restrict__ run_end,
+                                                   unsigned long long* __restrict__ per_read, const uint8_t* __restrict__ core,
+                                                   unsigned long long* __restrict__ stat) {
+  const uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (x >= n) return;
+  const uint32_t cx = cls[x];
+  if (!cx) return;
+  const uint32_t t = (uint32_t)(meta[x] >> 32);
+  if (split && t >= split) return;               // (block j's reads are queries only)
+  bool t_core = true;
+  if constexpr (CORE) t_core = core[t] != 0;
+  const uint64_t h = hash[x];
+  uint32_t m = 0;
+  uint64_t y = x + 1;
+  for (; y < n && hash[y] == h; y++) m += part_pair_ok<CORE>(t, t_core, cx, meta[y], cls[y], split, core) ? 1u : 0u;
+  run_end[x] = (uint32_t)y;
+  if (!m) return;
+  cnt[x] = m;
+  atomicAdd(&per_read[t - t0], (unsigned long long)m);
+  if (cx >= 2) atomicAdd(&stat[2], (unsigned long long)m);
+}
+
+// k_expand for a block pair: the same walk writes the cntm[x] anchors of x from aoff[x] on
+template <bool CORE>
+__global__ __launch_bounds__(256) void k_part_expand(const uint64_t* __restrict__ meta, const uint8_t* __restrict__ cls, const uint32_t* __restrict__ cntm,
+                                                     const uint32_t* __restrict__ run_end, const uint32_t* __restrict__ aoff, uint32_t n, uint32_t split,
+                                                     const uint64_t* __restrict__ base_off, uint32_t k, uint32_t t_lo, uint64_t* __restrict__ A,
+                                                     uint64_t* __restrict__ B, const uint8_t* __restrict__ core) {
+  const uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (x >= n) return;
+  const uint32_t c = cntm[x];
+  if (!c) return;
+  const uint64_t mx = meta[x];
+  const uint32_t t = (uint32_t)(mx >> 32), tpos = ((uint32_t)mx) >> 1, st = (uint32_t)mx & 1u, cx = cls[x];
+  bool t_core = true;
+  if constexpr (CORE) t_core = core[t] != 0;
+  const uint32_t e = run_end[x];
+  uint32_t at = aoff[x];
+  const uint32_t at_end = at + c;
+  for (uint32_t y = (uint32_t)x + 1; y < e && at < at_end; y++) {
+    const uint64_t my = meta[y];
+    if (!part_pair_ok<CORE>(t, t_core, cx, my, cls[y], split, core)) continue;
+    const uint32_t q = (uint32_t)(my >> 32), qp = ((uint32_t)my) >> 1, rel = ((uint32_t)my & 1u) ^ st;
+    const uint32_t qlen = (uint32_t)(base_off[q + 1] - base_off[q]);
+    const uint32_t qpos = rel ? qlen - qp + k - 2 : qp;
+    A[at] = ((uint64_t)tpos << 32) | qpos;
+    B[at] = ((uint64_t)(t - t_lo) << 33) | ((uint64_t)q << 1) | rel;
+    at++;
+  }
+}
+
+// the records of all block pairs into target order: the key of the stable sort, and the gather behind it
+__global__ __launch_bounds__(256) void k_rec_keys(const OvlRec* __restrict__ rec, uint32_t n, uint64_t* __restrict__ keys, uint64_t* __restrict__ pays) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  keys[i] = rec[i].tid;
+  pays[i] = i;
+}
+
+__global__ __launch_bounds__(256) void k_rec_gather(const OvlRec* __restrict__ rec, const uint64_t* __restrict__ pays, uint32_t n, OvlRec* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = rec[pays[i]];
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 #define OVL_TRY(expr)                                                                  \
   do {                                                                                 \
@@ -1143,6 +1419,21 @@ int chain_and_walk(const uint64_t* A0, const uint64_t* B0, ChainBufs& C, uint32_
 }
 inline bool lookback_ok(uint32_t h) { return h >= OVL_LOOKBACK && h <= OVL_MAX_LOOKBACK && h % 64 == 0; }
 
+// What a run stage leaves for the chunk loop (chain_chunks, below): per occurrence in hash order its meta, the anchors it has as the target side
+// (cnt) and the end of its run; cntm [nm], aoff [nm + 1] and scan_partial are scratch of the loop.  per_read (host): the anchors of the targets
+// t0 .. t1 - 1, which are all the targets the occurrences have; max_len: the longest read of the store.
+struct RunsOut {
+  const uint64_t* meta;
+  uint32_t nm;
+  const uint32_t *cnt, *run_end;
+  uint32_t *cntm, *aoff, *scan_partial;
+  const unsigned long long* per_read;
+  uint32_t t0, t1, max_len;
+};
+template <class Expand, class Take>
+int chain_chunks(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hipStream_t st, Bufs& B, const RunsOut& RO, OvlStats& stats, std::string& err,
+                 Expand expand, Take take);
+
 // Sketch, sort, frequency cut and the chunk loop of ovl_find and ovl_find_pairs.  Behind every chunk's k_walk, take(nc, gout, ccap, t_hi, B) gets the
 // chunk's nc GroupOut records, still on the device, in ascending (t, q, rel): it takes what it wants before it returns or queues its kernels on st,
 // in front of the next chunk's k_walk, which overwrites gout.  ccap: the most records any chunk has; t_hi: the targets done so far, this chunk's
@@ -1204,23 +1495,41 @@ int find_chunks(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, ui
   if (frac) { stats.occ_cut = occ[0]; stats.distinct = occ[1]; stats.cut_runs = occ[2]; stats.cut_minimizers = occ[3]; }
   if (rescue) { stats.resc_high = resc_stat[0]; stats.rescued = resc_stat[1]; stats.resc_anchors = resc_stat[2]; }
 
-  // chunks: consecutive targets whose anchors fit the budget (a target with more runs alone)
+  uint32_t max_len = 0;
+  for (uint32_t r = 0; r < S.n_reads; r++) max_len = std::max(max_len, S.h_len[r]);
+  const RunsOut RO{sk.meta, nm, d_cnt, d_run_end, d_cntm, d_aoff, ms.partial, per_read.data(), 0, S.n_reads, max_len};
+  return chain_chunks(S, P, budget_bytes, st, B, RO, stats, err, [&](uint32_t t_lo, uint64_t* A0, uint64_t* B0) {
+    if (rescue && d_core) k_expand_resc<true><<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, d_core, R.kind);
+    else if (rescue) k_expand_resc<false><<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, nullptr, R.kind);
+    else if (d_core) k_expand<true><<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, d_core);
+    else k_expand<false><<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, nullptr);
+  }, take);
+}
+
+// The chunk loop of a run stage's outcome — all of a call, or one block pair of an index in parts: consecutive targets whose anchors fit the budget
+// (a target with more runs alone), and per chunk k_mask, the scan, expand(t_lo, A0, B0) — the caller's expanding kernel over the occurrences —,
+// the two sorts, the groups, the chains and take (find_chunks).  The figures are added to stats.
+template <class Expand, class Take>
+int chain_chunks(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hipStream_t st, Bufs& B, const RunsOut& RO, OvlStats& stats, std::string& err,
+                 Expand expand, Take take) {
+  const uint32_t nm = RO.nm;
+  const auto per_read_of = [&](uint32_t t) { return (uint64_t)RO.per_read[t - RO.t0]; };
   const bool far = P.lookback != OVL_LOOKBACK;      // (k_chain_far's predecessor distances take two bytes an anchor: one more than k_chain's)
   const uint64_t want = std::max<uint64_t>(budget_bytes / (OVL_ANCHOR_BYTES + (far ? 1 : 0)), 1);
-  std::vector<uint32_t> cut{0};
+  std::vector<uint32_t> cut{RO.t0};
   uint64_t cap = 0, total = 0;
   {
     uint64_t acc = 0;
-    for (uint32_t t = 0; t < S.n_reads; t++) {
-      if (per_read[t] > 0xfffff000ull) { err = "overlap finder: read " + std::to_string(t) + " has more than 2^32 anchors"; return OVL_UNSUPPORTED; }
-      if (acc && acc + per_read[t] > want) { cut.push_back(t); acc = 0; }
-      acc += per_read[t];
-      total += per_read[t];
+    for (uint32_t t = RO.t0; t < RO.t1; t++) {
+      if (per_read_of(t) > 0xfffff000ull) { err = "overlap finder: read " + std::to_string(t) + " has more than 2^32 anchors"; return OVL_UNSUPPORTED; }
+      if (acc && acc + per_read_of(t) > want) { cut.push_back(t); acc = 0; }
+      acc += per_read_of(t);
+      total += per_read_of(t);
       cap = std::max(cap, acc);
     }
-    cut.push_back(S.n_reads);
+    cut.push_back(RO.t1);
   }
-  stats.anchors = total;
+  stats.anchors += total;
   if (!total) return OVL_OK;
   if (cap > 0xfffff000ull) { err = "overlap finder: more than 2^32 anchors in one chunk (lower HERRO_OVL_SCRATCH_MB)"; return OVL_UNSUPPORTED; }
 
@@ -1238,22 +1547,18 @@ int find_chunks(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, ui
   OVL_TRY(B.get(&C.gout, ccap));
   SortScratch as;
   OVL_TRY(as.alloc(B, cap));
-  uint32_t max_len = 0;
-  for (uint32_t r = 0; r < S.n_reads; r++) max_len = std::max(max_len, S.h_len[r]);
+  const uint32_t max_len = RO.max_len;
 
   for (size_t ch = 0; ch + 1 < cut.size(); ch++) {
     const uint32_t t_lo = cut[ch], t_hi = cut[ch + 1];
     uint64_t na64 = 0;
-    for (uint32_t t = t_lo; t < t_hi; t++) na64 += per_read[t];
+    for (uint32_t t = t_lo; t < t_hi; t++) na64 += per_read_of(t);
     if (!na64) continue;
     stats.chunks++;
     const uint32_t na = (uint32_t)na64;
-    k_mask<<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cnt, nm, t_lo, t_hi, d_cntm);
-    if (int rc = scan_u32(d_cntm, nm, d_aoff, ms.partial, st, err)) return rc;
-    if (rescue && d_core) k_expand_resc<true><<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, d_core, R.kind);
-    else if (rescue) k_expand_resc<false><<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, nullptr, R.kind);
-    else if (d_core) k_expand<true><<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, d_core);
-    else k_expand<false><<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, nullptr);
+    k_mask<<<nblk(nm, 256), 256, 0, st>>>(RO.meta, RO.cnt, nm, t_lo, t_hi, RO.cntm);
+    if (int rc = scan_u32(RO.cntm, nm, RO.aoff, RO.scan_partial, st, err)) return rc;
+    expand(t_lo, A0, B0);
     OVL_TRY(hipGetLastError());
     {
       std::vector<uint32_t> sa, sb;
@@ -1285,9 +1590,331 @@ int find_chunks(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, ui
   }
   return OVL_OK;
 }
+
+// ---- an index in parts: the host side ("An index in parts") -------------------------------------------------------------
+constexpr uint64_t PART_MAX_MINIMIZERS = 0xfffff000ull;      // of one hash range or block pair: 32-bit places
+constexpr uint64_t PART_RANGE_FLOOR = 65536;                 // minimizers a hash range may always hold, however small index_kmers is
+
+// What pass A leaves, for the life of the call: the per-read and per-tile tables and occ16.  Block b is the reads cuts[b] .. cuts[b + 1] - 1, its
+// tiles tile0[b] .. tile0[b + 1] - 1, its minimizers the ordinals ord0[b] .. ord0[b + 1] - 1; u_at + tile0[b] + b is its slice of the prefix of
+// the minimizers per tile (tiles + 1 entries, from 0).
+struct PartIndex {
+  Bufs B;
+  std::vector<uint64_t> cuts, ord0;
+  std::vector<uint32_t> tile0;
+  uint32_t n_blocks = 0, max_tiles = 0;
+  uint64_t minimizers = 0;
+  uint32_t *d_tile_off = nullptr, *d_u_at = nullptr, *d_cnt = nullptr, *d_partial = nullptr;
+  uint16_t* d_occ16 = nullptr;
+  unsigned long long* d_hist = nullptr;         // [OVL_OCC_BINS] the census of the whole store
+  uint64_t* d_occ = nullptr;                    // occ_frac_ppm != 0: {cut, distinct, runs above the cut, minimizers in them} (k_occ_pick64)
+  explicit PartIndex(BufsPeak* acct) : B(acct) {}
+  uint32_t reads_of(uint32_t b) const { return (uint32_t)(cuts[b + 1] - cuts[b]); }
+  uint32_t tiles_of(uint32_t b) const { return tile0[b + 1] - tile0[b]; }
+  uint32_t minimizers_of(uint32_t b) const { return (uint32_t)(ord0[b + 1] - ord0[b]); }
+};
+
+SketchPart sketch_part_args(const OvlStore& S, const OvlParams& P, const PartIndex& X, uint32_t b) {
+  SketchPart a{};
+  a.words = S.d_words; a.word_off = S.d_word_off; a.base_off = S.d_base_off; a.tile_off = X.d_tile_off;
+  a.r_lo = (uint32_t)X.cuts[b]; a.r_hi = (uint32_t)X.cuts[b + 1]; a.tile0 = X.tile0[b]; a.k = P.k; a.w = P.w;
+  a.h_lo = 0; a.h_hi = INF64;
+  a.u_at = X.d_u_at + X.tile0[b] + b;
+  a.occ16 = X.d_occ16;
+  return a;
+}
+
+// One hash range [h_lo, h_hi] of pass A.  *n_out: its minimizers; with may_split and more than split_above of them nothing is written (the count
+// pass says so first) and *n_out alone comes back.  f_at: a per-tile table like u_at, this range's.
+int part_range(const OvlStore& S, const OvlParams& P, hipStream_t st, PartIndex& X, uint32_t* f_at, uint64_t h_lo, uint64_t h_hi, bool may_split,
+               uint64_t split_above, uint64_t* n_out, std::string& err) {
+  std::vector<uint32_t> ftot(X.n_blocks, 0);
+  for (uint32_t b = 0; b < X.n_blocks; b++) {
+    const uint32_t nt = X.tiles_of(b);
+    if (!nt) continue;
+    SketchPart a = sketch_part_args(S, P, X, b);
+    a.h_lo = h_lo; a.h_hi = h_hi; a.cnt = X.d_cnt;
+    k_sketch_part<SKP_COUNT_RANGE><<<nt, SK_T, 0, st>>>(a);
+    OVL_TRY(hipGetLastError());
+    if (int rc = scan_u32(X.d_cnt, nt, f_at + X.tile0[b] + b, X.d_partial, st, err)) return rc;
+    OVL_TRY(hipMemcpyAsync(&ftot[b], f_at + X.tile0[b] + b + nt, 4, hipMemcpyDeviceToHost, st));
+  }
+  OVL_TRY(hipStreamSynchronize(st));
+  uint64_t n64 = 0;
+  for (uint32_t v : ftot) n64 += v;
+  *n_out = n64;
+  if (!n64 || (may_split && n64 > split_above)) return OVL_OK;
+  if (n64 > PART_MAX_MINIMIZERS) { err = "overlap finder: a hash range of the occurrence pass holds more than 2^32 - 4096 minimizers (more occ_ranges)"; return OVL_UNSUPPORTED; }
+  const uint32_t n = (uint32_t)n64;
+  Bufs RB(X.B.acct);
+  uint64_t *hk0, *hp0, *hk1, *hp1;
+  uint32_t *flag, *gidx, *rstart;
+  SortScratch ms;
+  OVL_TRY(RB.get(&hk0, n)); OVL_TRY(RB.get(&hp0, n)); OVL_TRY(RB.get(&hk1, n)); OVL_TRY(RB.get(&hp1, n));
+  OVL_TRY(RB.get(&flag, n)); OVL_TRY(RB.get(&gidx, (uint64_t)n + 1)); OVL_TRY(RB.get(&rstart, (uint64_t)n + 1));
+  OVL_TRY(ms.alloc(RB, n));
+  uint32_t at = 0;
+  for (uint32_t b = 0; b < X.n_blocks; b++) {
+    if (!ftot[b]) continue;
+    SketchPart a = sketch_part_args(S, P, X, b);
+    a.h_lo = h_lo; a.h_hi = h_hi;
+    a.f_at = f_at + X.tile0[b] + b;
+    a.ord_base = X.ord0[b];
+    a.out_base = at;
+    a.hash_out = hk0; a.ord_out = hp0;
+    k_sketch_part<SKP_WRITE_RANGE><<<X.tiles_of(b), SK_T, 0, st>>>(a);
+    at += ftot[b];
+  }
+  OVL_TRY(hipGetLastError());
+  std::vector<uint32_t> shifts;
+  field_shifts(shifts, 0, 2 * P.k);
+  if (int rc = radix_sort(&hk0, &hp0, &hk1, &hp1, n, shifts, ms, st, err)) return rc;
+  k_heads<<<nblk(n, 256), 256, 0, st>>>(hk0, n, flag);
+  if (int rc = scan_u32(flag, n, gidx, ms.partial, st, err)) return rc;
+  k_gstart<<<nblk(n, 256), 256, 0, st>>>(flag, gidx, n, rstart);
+  k_occ16<<<std::min(nblk(n, 256), OCC_GRID), 256, 0, st>>>(hp0, flag, gidx, rstart, n, X.d_occ16, X.d_hist);
+  OVL_TRY(hipGetLastError());
+  OVL_TRY(hipStreamSynchronize(st));           // (RB goes with the return)
+  return OVL_OK;
+}
+
+// The plan and pass A.  stats gains kmers, minimizers, blocks, ranges and, with occ_frac_ppm, the census figures.
+int part_index(const OvlStore& S, const OvlParams& P, hipStream_t st, PartIndex& X, OvlStats& stats, std::string& err) {
+  if (int rc = check_store(S, err)) return rc;
+  if (P.index_kmers > OVL_MAX_KMERS || P.occ_ranges > INDEX_MAX_RANGES) { err = "overlap finder: index_kmers <= 2^32 - 4096, occ_ranges <= 65536"; return OVL_UNSUPPORTED; }
+  std::vector<uint64_t> bk;
+  index_plan(S.n_reads, S.h_len, P.k, P.w, P.index_kmers, X.cuts, &bk);
+  {
+    uint64_t bi = 0, bj = 0;
+    if (index_plan_overflow(bk, OVL_MAX_KMERS, bi, bj)) { err = index_plan_overflow_text(X.cuts, bi, bj); return OVL_UNSUPPORTED; }
+  }
+  X.n_blocks = (uint32_t)bk.size();
+  stats.blocks = X.n_blocks;
+  std::vector<uint32_t> tile_off((size_t)S.n_reads + 1, 0);
+  uint64_t tiles = 0, kmers = 0;
+  X.tile0.assign((size_t)X.n_blocks + 1, 0);
+  for (uint32_t b = 0; b < X.n_blocks; b++) {
+    X.tile0[b] = (uint32_t)tiles;
+    for (uint64_t r = X.cuts[b]; r < X.cuts[b + 1]; r++) {
+      tile_off[r] = (uint32_t)tiles;
+      const uint64_t nk = index_read_kmers(S.h_len[r], P.k, P.w);
+      kmers += nk;
+      tiles += (nk + SK_T - 1) / SK_T;
+    }
+    if (tiles + X.n_blocks > 0xfffff000ull) { err = "overlap finder: more than 2^40 k-mers in the read store"; return OVL_UNSUPPORTED; }
+    X.max_tiles = std::max(X.max_tiles, (uint32_t)tiles - X.tile0[b]);
+  }
+  tile_off[S.n_reads] = (uint32_t)tiles;
+  X.tile0[X.n_blocks] = (uint32_t)tiles;
+  stats.kmers = kmers;
+  X.ord0.assign((size_t)X.n_blocks + 1, 0);
+  if (!tiles) return OVL_OK;
+  const uint32_t nt = (uint32_t)tiles;
+  OVL_TRY(X.B.get(&X.d_tile_off, (uint64_t)S.n_reads + 1));
+  OVL_TRY(X.B.get(&X.d_u_at, (uint64_t)nt + X.n_blocks + 1));
+  OVL_TRY(X.B.get(&X.d_cnt, X.max_tiles));
+  OVL_TRY(X.B.get(&X.d_partial, nblk(X.max_tiles, SC_TILE) + 2));
+  OVL_TRY(X.B.get(&X.d_hist, OVL_OCC_BINS));
+  OVL_TRY(X.B.get(&X.d_occ, 4));
+  OVL_TRY(hipMemsetAsync(X.d_hist, 0, 8ull * OVL_OCC_BINS, st));
+  OVL_TRY(hipMemcpyAsync(X.d_tile_off, tile_off.data(), 4ull * (S.n_reads + 1), hipMemcpyHostToDevice, st));
+  std::vector<uint32_t> utot(X.n_blocks, 0);
+  for (uint32_t b = 0; b < X.n_blocks; b++) {
+    const uint32_t ntb = X.tiles_of(b);
+    if (!ntb) continue;
+    SketchPart a = sketch_part_args(S, P, X, b);
+    a.cnt = X.d_cnt;
+    k_sketch_part<SKP_COUNT><<<ntb, SK_T, 0, st>>>(a);
+    OVL_TRY(hipGetLastError());
+    if (int rc = scan_u32(X.d_cnt, ntb, X.d_u_at + X.tile0[b] + b, X.d_partial, st, err)) return rc;
+    OVL_TRY(hipMemcpyAsync(&utot[b], X.d_u_at + X.tile0[b] + b + ntb, 4, hipMemcpyDeviceToHost, st));
+  }
+  OVL_TRY(hipStreamSynchronize(st));           // (also keeps tile_off alive until its copy is done)
+  for (uint32_t b = 0; b < X.n_blocks; b++) X.ord0[b + 1] = X.ord0[b] + utot[b];
+  X.minimizers = X.ord0[X.n_blocks];
+  stats.minimizers = X.minimizers;
+  if (!X.minimizers) return OVL_OK;
+  OVL_TRY(X.B.bytes(&X.d_occ16, 2 * X.minimizers + 64));
+
+  // the hash ranges: occ_ranges as given, else as many as keep a range near the minimizers of index_kmers k-mers (two per w + 1), split where the
+  // count pass finds more than twice that
+  const uint64_t space = 1ull << (2 * P.k);     // hashes are below it (INF64 is never selected)
+  const uint64_t per_range = std::max<uint64_t>(2 * P.index_kmers / (P.w + 1), PART_RANGE_FLOOR);
+  const bool forced = P.occ_ranges != 0;
+  const uint64_t R = forced ? P.occ_ranges : std::min<uint64_t>((X.minimizers + per_range - 1) / per_range, INDEX_MAX_RANGES);
+  const uint64_t step = (space + R - 1) / R;
+  std::vector<std::pair<uint64_t, uint64_t>> todo;
+  for (uint64_t lo = 0; lo < space; lo += step) todo.emplace_back(lo, std::min(lo + step, space) - 1);
+  uint32_t* f_at;
+  OVL_TRY(X.B.get(&f_at, (uint64_t)nt + X.n_blocks + 1));
+  while (!todo.empty()) {
+    const std::pair<uint64_t, uint64_t> r = todo.back();
+    todo.pop_back();
+    uint64_t n = 0;
+    const bool may_split = !forced && r.first < r.second;
+    const uint64_t split_above = std::min<uint64_t>(2 * per_range, PART_MAX_MINIMIZERS);
+    if (int rc = part_range(S, P, st, X, f_at, r.first, r.second, may_split, split_above, &n, err)) return rc;
+    if (may_split && n > split_above) {
+      const uint64_t mid = r.first + (r.second - r.first) / 2;
+      todo.emplace_back(mid + 1, r.second);
+      todo.emplace_back(r.first, mid);
+      continue;
+    }
+    stats.ranges++;
+  }
+  if (P.occ_frac_ppm) {
+    uint64_t occ[4];
+    k_occ_pick64<<<1, 256, 0, st>>>(X.d_hist, X.minimizers, P.occ_frac_ppm, P.max_occ, X.d_occ);
+    OVL_TRY(hipGetLastError());
+    OVL_TRY(hipMemcpyAsync(occ, X.d_occ, sizeof(occ), hipMemcpyDeviceToHost, st));
+    OVL_TRY(hipStreamSynchronize(st));
+    stats.occ_cut = occ[0]; stats.distinct = occ[1]; stats.cut_runs = occ[2]; stats.cut_minimizers = occ[3];
+  } else {
+    X.d_occ = nullptr;
+  }
+  return OVL_OK;
+}
+
+// The minimizers of block b behind those already at out_base, in (rid, pos) order, each with its occ from occ16; meta_loc: see k_sketch_part
+struct PartSketch { uint64_t *hash, *meta, *meta_loc; uint32_t* occ; };
+int part_sketch_block(const OvlStore& S, const OvlParams& P, hipStream_t st, const PartIndex& X, uint32_t b, uint32_t out_base, const PartSketch& K,
+                      std::string& err) {
+  if (!X.minimizers_of(b)) return OVL_OK;
+  SketchPart a = sketch_part_args(S, P, X, b);
+  a.ord_base = X.ord0[b];
+  a.out_base = out_base;
+  a.hash_out = K.hash; a.meta_out = K.meta; a.meta_loc = K.meta_loc; a.occ_out = K.occ;
+  k_sketch_part<SKP_WRITE_BLOCK><<<X.tiles_of(b), SK_T, 0, st>>>(a);
+  OVL_TRY(hipGetLastError());
+  return OVL_OK;
+}
+
+// k_rescue over the reads of block b, whose minimizers begin at `at` of the pair's arrays: the kernel of the unpartitioned path, given the block's
+// slice, its read ids counted from the block's first read and the offsets from there on.  occ_rp holds occ16's values: the classes and the order
+// (occ, pos) among cut < occ <= rmax <= 65534 are those of the true counts.
+void part_rescue_block(const OvlStore& S, const OvlParams& P, hipStream_t st, const PartIndex& X, uint32_t b, uint32_t at, const PartSketch& K,
+                       uint8_t* resc, unsigned long long* stat) {
+  const uint32_t n = X.minimizers_of(b);
+  if (!n || !P.occ_dist) return;
+  k_rescue<<<X.reads_of(b), 64, 0, st>>>(K.meta_loc + at, K.occ + at, n, S.d_base_off + X.cuts[b], P.max_occ, X.d_occ, P.rescue_max_occ, P.occ_dist,
+                                         resc + at, stat);
+}
+
+// find_chunks with the index in parts.  reset() comes in front of every block pair: what take keeps in the scratch it is handed is gone by then.
+template <class Reset, class Take>
+int find_parts(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uint64_t budget_bytes, hipStream_t st, OvlStats& stats, std::string& err,
+               Reset reset, Take take) {
+  stats = OvlStats{};
+  if (!lookback_ok(P.lookback)) { err = "overlap finder: the look-back is a multiple of 64 in 64 .. 1024"; return OVL_UNSUPPORTED; }
+  BufsPeak acct;
+  PartIndex X(&acct);
+  const int rc_all = [&]() -> int {
+    if (int rc = part_index(S, P, st, X, stats, err)) return rc;
+    const bool frac = P.occ_frac_ppm != 0, rescue = P.occ_dist != 0;
+    if (X.minimizers < 2) {                     // (as find_chunks: fewer than two minimizers are as many runs of one)
+      stats.occ_cut = frac ? occ_final_cut((uint32_t)X.minimizers, P.max_occ) : P.max_occ;
+      stats.distinct = frac ? X.minimizers : 0;
+      stats.cut_runs = stats.cut_minimizers = 0;
+      return OVL_OK;
+    }
+    if (!frac) stats.occ_cut = P.max_occ;
+    uint32_t max_len = 0;
+    for (uint32_t r = 0; r < S.n_reads; r++) max_len = std::max(max_len, S.h_len[r]);
+    std::vector<uint8_t> has_core(X.n_blocks, 1);
+    if (d_core) {
+      std::vector<uint8_t> core(S.n_reads);
+      OVL_TRY(hipMemcpyAsync(core.data(), d_core, S.n_reads, hipMemcpyDeviceToHost, st));
+      OVL_TRY(hipStreamSynchronize(st));
+      for (uint32_t b = 0; b < X.n_blocks; b++) {
+        has_core[b] = 0;
+        for (uint64_t r = X.cuts[b]; r < X.cuts[b + 1] && !has_core[b]; r++) has_core[b] = core[r] != 0;
+      }
+    }
+    for (uint32_t bi = 0; bi < X.n_blocks; bi++) {
+      for (uint32_t bj = bi; bj < X.n_blocks; bj++) {
+        // a pair of two blocks without a core read has no wanted anchor; a block with itself always runs: the rescue's figures are counted there
+        if (bj > bi && !has_core[bi] && !has_core[bj]) continue;
+        const uint32_t ni = X.minimizers_of(bi), nj = bj > bi ? X.minimizers_of(bj) : 0;
+        if (!ni || (bj > bi && !nj)) continue;
+        stats.block_pairs++;
+        reset();
+        const uint32_t nm = ni + nj;            // (the plan keeps the k-mers of a pair, so its minimizers, within 2^32 - 4096)
+        const uint32_t t0 = (uint32_t)X.cuts[bi], t1 = (uint32_t)X.cuts[bi + 1], split = bj > bi ? (uint32_t)X.cuts[bj] : 0u;
+        Bufs B(&acct);
+        PartSketch K{};
+        uint8_t *resc = nullptr, *cls, *cls_s;
+        uint64_t *idx, *k1, *p1, *meta_s;
+        uint32_t *d_cnt, *d_run_end, *d_cntm, *d_aoff;
+        unsigned long long *d_per_read, *d_stat;
+        SortScratch ms;
+        OVL_TRY(B.get(&K.hash, nm)); OVL_TRY(B.get(&K.meta, nm)); OVL_TRY(B.get(&K.occ, nm));
+        if (rescue) { OVL_TRY(B.get(&K.meta_loc, nm)); OVL_TRY(B.get(&resc, nm)); }
+        OVL_TRY(B.get(&cls, nm)); OVL_TRY(B.get(&cls_s, nm)); OVL_TRY(B.get(&idx, nm)); OVL_TRY(B.get(&k1, nm)); OVL_TRY(B.get(&p1, nm));
+        OVL_TRY(B.get(&meta_s, nm));
+        OVL_TRY(B.get(&d_cnt, nm)); OVL_TRY(B.get(&d_run_end, nm)); OVL_TRY(B.get(&d_cntm, nm)); OVL_TRY(B.get(&d_aoff, (uint64_t)nm + 1));
+        OVL_TRY(B.get(&d_per_read, t1 - t0));
+        OVL_TRY(B.get(&d_stat, 6));             // {H minimizers, rescued, anchors of the runs above the cut}, and the same of a block counted before
+        OVL_TRY(ms.alloc(B, nm));
+        OVL_TRY(hipMemsetAsync(d_cnt, 0, 4ull * nm, st));
+        OVL_TRY(hipMemsetAsync(d_per_read, 0, 8ull * (t1 - t0), st));
+        OVL_TRY(hipMemsetAsync(d_stat, 0, 48, st));
+        if (int rc = part_sketch_block(S, P, st, X, bi, 0, K, err)) return rc;
+        if (bj > bi) if (int rc = part_sketch_block(S, P, st, X, bj, ni, K, err)) return rc;
+        if (rescue) {
+          OVL_TRY(hipMemsetAsync(resc, 0, nm, st));
+          part_rescue_block(S, P, st, X, bi, 0, K, resc, bj == bi ? d_stat : d_stat + 3);
+          if (bj > bi) part_rescue_block(S, P, st, X, bj, ni, K, resc, d_stat + 3);
+        }
+        k_part_cls<<<nblk(nm, 256), 256, 0, st>>>(K.occ, resc, nm, P.max_occ, X.d_occ, rescue ? P.rescue_max_occ : 0u, cls, idx);
+        OVL_TRY(hipGetLastError());
+        {
+          std::vector<uint32_t> shifts;
+          field_shifts(shifts, 0, 2 * P.k);
+          if (int rc = radix_sort(&K.hash, &idx, &k1, &p1, nm, shifts, ms, st, err)) return rc;
+        }
+        k_part_gather<<<nblk(nm, 256), 256, 0, st>>>(idx, K.meta, cls, nm, meta_s, cls_s);
+        if (d_core) k_part_runs<true><<<nblk(nm, 256), 256, 0, st>>>(K.hash, meta_s, cls_s, nm, split, t0, d_cnt, d_run_end, d_per_read, d_core, d_stat);
+        else k_part_runs<false><<<nblk(nm, 256), 256, 0, st>>>(K.hash, meta_s, cls_s, nm, split, t0, d_cnt, d_run_end, d_per_read, nullptr, d_stat);
+        OVL_TRY(hipGetLastError());
+        std::vector<unsigned long long> per_read(t1 - t0);
+        unsigned long long resc_stat[3] = {0, 0, 0};
+        OVL_TRY(hipMemcpyAsync(per_read.data(), d_per_read, 8ull * (t1 - t0), hipMemcpyDeviceToHost, st));
+        OVL_TRY(hipMemcpyAsync(resc_stat, d_stat, sizeof(resc_stat), hipMemcpyDeviceToHost, st));
+        OVL_TRY(hipStreamSynchronize(st));
+        if (rescue) { stats.resc_high += resc_stat[0]; stats.rescued += resc_stat[1]; stats.resc_anchors += resc_stat[2]; }
+        const RunsOut RO{meta_s, nm, d_cnt, d_run_end, d_cntm, d_aoff, ms.partial, per_read.data(), t0, t1, max_len};
+        if (int rc = chain_chunks(S, P, budget_bytes, st, B, RO, stats, err, [&](uint32_t t_lo, uint64_t* A0, uint64_t* B0) {
+          if (d_core) k_part_expand<true><<<nblk(nm, 256), 256, 0, st>>>(meta_s, cls_s, d_cntm, d_run_end, d_aoff, nm, split, S.d_base_off, P.k, t_lo, A0, B0, d_core);
+          else k_part_expand<false><<<nblk(nm, 256), 256, 0, st>>>(meta_s, cls_s, d_cntm, d_run_end, d_aoff, nm, split, S.d_base_off, P.k, t_lo, A0, B0, nullptr);
+        }, take)) return rc;
+        OVL_TRY(hipStreamSynchronize(st));     // (B goes with the pair: nothing of it is still read)
+      }
+    }
+    return OVL_OK;
+  }();
+  if (rc_all != OVL_OK) (void)hipStreamSynchronize(st);
+  stats.peak_bytes = acct.peak;
+  return rc_all;
+}
 }  // namespace
 
 int ovl_occ_census(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vector<uint32_t>* hist, uint64_t rec[4], std::string& err) {
+  if (P.index_kmers) {                          // pass A alone; a bin beyond 32 bits is reported as 2^32 - 1
+    BufsPeak acct;
+    PartIndex X(&acct);
+    OvlStats stats;
+    if (int rc = part_index(S, P, st, X, stats, err)) { (void)hipStreamSynchronize(st); return rc; }
+    if (hist) hist->assign(OVL_OCC_BINS, 0);
+    rec[0] = X.minimizers ? stats.occ_cut : occ_final_cut(0, P.max_occ);
+    rec[1] = stats.distinct; rec[2] = stats.cut_runs; rec[3] = stats.cut_minimizers;
+    if (hist && X.minimizers) {
+      std::vector<unsigned long long> h64(OVL_OCC_BINS);
+      OVL_TRY(hipMemcpyAsync(h64.data(), X.d_hist, 8ull * OVL_OCC_BINS, hipMemcpyDeviceToHost, st));
+      OVL_TRY(hipStreamSynchronize(st));
+      for (uint32_t b = 0; b < OVL_OCC_BINS; b++) (*hist)[b] = (uint32_t)std::min<unsigned long long>(h64[b], 0xffffffffull);
+    }
+    return OVL_OK;
+  }
   Bufs B;
   Sketch sk;
   if (int rc = sketch_dev(S, P, st, B, sk, err)) return rc;
@@ -1309,6 +1936,37 @@ int ovl_occ_census(const OvlStore& S, const OvlParams& P, hipStream_t st, std::v
 }
 
 int ovl_seed_rescue(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vector<uint32_t>& occ, std::vector<uint8_t>& rescued, std::string& err) {
+  if (P.index_kmers) {                          // pass A, then block by block: its sketch, occ from occ16, k_rescue
+    BufsPeak acct;
+    PartIndex X(&acct);
+    OvlStats stats;
+    const int rc_all = [&]() -> int {
+      if (int rc = part_index(S, P, st, X, stats, err)) return rc;
+      occ.assign(X.minimizers, 1);
+      rescued.assign(X.minimizers, 0);
+      for (uint32_t b = 0; b < X.n_blocks; b++) {
+        const uint32_t n = X.minimizers_of(b);
+        if (!n) continue;
+        Bufs B(&acct);
+        PartSketch K{};
+        uint8_t* resc;
+        unsigned long long* stat;
+        OVL_TRY(B.get(&K.hash, n)); OVL_TRY(B.get(&K.meta, n)); OVL_TRY(B.get(&K.meta_loc, n)); OVL_TRY(B.get(&K.occ, n));
+        OVL_TRY(B.get(&resc, n)); OVL_TRY(B.get(&stat, 3));
+        OVL_TRY(hipMemsetAsync(resc, 0, n, st));
+        OVL_TRY(hipMemsetAsync(stat, 0, 24, st));
+        if (int rc = part_sketch_block(S, P, st, X, b, 0, K, err)) return rc;
+        part_rescue_block(S, P, st, X, b, 0, K, resc, stat);
+        OVL_TRY(hipGetLastError());
+        OVL_TRY(hipMemcpyAsync(occ.data() + X.ord0[b], K.occ, 4ull * n, hipMemcpyDeviceToHost, st));
+        OVL_TRY(hipMemcpyAsync(rescued.data() + X.ord0[b], resc, n, hipMemcpyDeviceToHost, st));
+        OVL_TRY(hipStreamSynchronize(st));
+      }
+      return OVL_OK;
+    }();
+    if (rc_all != OVL_OK) (void)hipStreamSynchronize(st);
+    return rc_all;
+  }
   Bufs B;
   Sketch sk;
   if (int rc = sketch_dev(S, P, st, B, sk, err)) return rc;
@@ -1336,14 +1994,20 @@ int ovl_find(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uint6
              OvlStats& stats, std::string& err) {
   out.clear();
   std::vector<GroupOut> h_out;
-  return find_chunks(S, P, d_core, budget_bytes, st, stats, err, [&](uint32_t nc, const GroupOut* gout, uint64_t, uint32_t, Bufs&) -> int {
+  const auto take = [&](uint32_t nc, const GroupOut* gout, uint64_t, uint32_t, Bufs&) -> int {
     h_out.resize(nc);
     OVL_TRY(hipMemcpyAsync(h_out.data(), gout, sizeof(GroupOut) * (uint64_t)nc, hipMemcpyDeviceToHost, st));
     OVL_TRY(hipStreamSynchronize(st));
     for (const GroupOut& g : h_out)
       if (g.kept) out.push_back(OvlPair{g.t, g.q, g.rel, g.n_anchors, g.score, g.tstart, g.tend, g.qstart, g.qend});
     return OVL_OK;
-  });
+  };
+  if (!P.index_kmers) return find_chunks(S, P, d_core, budget_bytes, st, stats, err, take);
+  // an index in parts: a target's chains come pair by pair, (i, i), (i, i + 1), ... — in ascending q, every (t, q) in one pair; the stable sort by t
+  // gives ascending (t, q, rel)
+  if (int rc = find_parts(S, P, d_core, budget_bytes, st, stats, err, [] {}, take)) return rc;
+  std::stable_sort(out.begin(), out.end(), [](const OvlPair& a, const OvlPair& b) { return a.t < b.t; });
+  return OVL_OK;
 }
 
 // The chain stage alone on the caller's groups (herro_debug_chain).  The keys k_walk decodes are those of target 0, query 0, forward strand, whose
@@ -1405,7 +2069,7 @@ int ovl_find_pairs(const OvlStore& S, const OvlParams& P, const uint8_t* d_core,
                    std::string& err) {
   out.release();
   uint32_t *sel = nullptr, *soff = nullptr, *part = nullptr;
-  const int rc = find_chunks(S, P, d_core, budget_bytes, st, stats, err, [&](uint32_t nc, const GroupOut* gout, uint64_t ccap, uint32_t t_hi, Bufs& B) -> int {
+  const auto take = [&](uint32_t nc, const GroupOut* gout, uint64_t ccap, uint32_t t_hi, Bufs& B) -> int {
     if (!sel) {
       OVL_TRY(B.get(&sel, ccap));
       OVL_TRY(B.get(&soff, ccap + 1));
@@ -1438,9 +2102,44 @@ int ovl_find_pairs(const OvlStore& S, const OvlParams& P, const uint8_t* d_core,
     OVL_TRY(hipGetLastError());
     out.n += ns;
     return OVL_OK;
-  });
-  if (rc) return rc;
+  };
+  if (!P.index_kmers) {
+    if (int rc = find_chunks(S, P, d_core, budget_bytes, st, stats, err, take)) return rc;
+    OVL_TRY(hipStreamSynchronize(st));
+    return OVL_OK;
+  }
+  // an index in parts: the scratch of a block pair goes with the pair, and so does what take keeps in it
+  if (int rc = find_parts(S, P, d_core, budget_bytes, st, stats, err, [&] { sel = soff = part = nullptr; }, take)) return rc;
   OVL_TRY(hipStreamSynchronize(st));
+  if (stats.blocks < 2 || out.n < 2) return OVL_OK;
+  // A target's records come pair by pair — (i, i), (i, i + 1), ... —, in ascending q inside a pair and from pair to pair: one stable sort by t puts
+  // the call's records into ascending (t, q).
+  const uint32_t n = (uint32_t)out.n;            // (<= 2^31 - 1: take)
+  Bufs B;
+  uint64_t *k0, *p0, *k1, *p1;
+  uint32_t* scratch;
+  OvlRec* sorted = nullptr;
+  OVL_TRY(B.get(&k0, n)); OVL_TRY(B.get(&p0, n)); OVL_TRY(B.get(&k1, n)); OVL_TRY(B.get(&p1, n));
+  OVL_TRY(B.get(&scratch, ovl_sort_scratch(n)));
+  OVL_TRY(hipMalloc((void**)&sorted, (uint64_t)n * sizeof(OvlRec)));
+  k_rec_keys<<<nblk(n, 256), 256, 0, st>>>(out.d, n, k0, p0);
+  std::vector<uint32_t> shifts;
+  field_shifts(shifts, 0, bits_of(S.n_reads - 1));
+  int rc = ovl_radix_sort(&k0, &p0, &k1, &p1, n, shifts, scratch, st, err);
+  hipError_t e = hipSuccess;
+  if (rc == OVL_OK) {
+    k_rec_gather<<<nblk(n, 256), 256, 0, st>>>(out.d, p0, n, sorted);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (rc != OVL_OK || e != hipSuccess) {
+    (void)hipFree(sorted);
+    if (rc != OVL_OK) return rc;
+    OVL_TRY(e);
+  }
+  (void)hipFree(out.d);
+  out.d = sorted;
+  out.cap = n;
   return OVL_OK;
 }
 

@@ -718,7 +718,7 @@ def correct_reads_shard(ctx, mask, window_size: int, batch: int, batch_mode: int
     `group_targets` targets cut from the table -> featurize -> infer -> consensus -> FASTA.  Rows whose record failed are dropped
     (api.paired_job_args).  postprocess: None — Job.fasta, the corrected reads as they are —, or the keywords of Job.fasta_dev (chop_len,
     min_length, line_width; api.POSTPROCESS is scripts/postprocess_corrected.sh): the records are chopped and filtered for the assembler
-    where they are written, on the device.  finder_params: find_overlap_pairs' keywords, occ_dist / rescue_max_occ (the rescue of high-frequency minimizers) and lookback (the chain look-back) among them.  Returns (rids, ends, text) as merge_records takes them."""
+    where they are written, on the device.  finder_params: find_overlap_pairs' keywords, occ_dist / rescue_max_occ (the rescue of high-frequency minimizers) , lookback (the chain look-back) and index_kmers / occ_ranges (the index in parts) among them.  Returns (rids, ends, text) as merge_records takes them."""
     from . import api
     pairs = ctx.find_overlap_pairs(core=mask, **finder_params)
     m = pairs.align()

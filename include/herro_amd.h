@@ -505,9 +505,13 @@ void herro_extended_free(herro_extended* x);
  * fixed mode; 0 for a handle made by herro_pairs_from_table*), and HERRO_OVL_STATS=1 adds a line `OVLOCC cut= distinct= cut_runs=
  * cut_minimizers=` to its `OVL ` line.  Known limit: the chain looks back 64 ANCHORS, not bases — a tandem repeat that survives max_occ (a set of very few
  * reads) can put more than 64 off-diagonal anchors between two anchors of the true diagonal, and the overlap comes out shorter.
- * Limits (HERRO_E_UNSUPPORTED): 2^31 - 1 reads, reads of 2^31 - 1 bases, 2^32 k-mers in the store, 2^32 anchors per target.
+ * Limits (HERRO_E_UNSUPPORTED): 2^31 - 1 reads, reads of 2^31 - 1 bases, 2^32 k-mers in the store (with herro_set_index_params: in one
+ * pair of read blocks), 2^32 anchors per target.
  * Scratch: 128 bytes per anchor, targets processed in read-id ranges that fit HERRO_OVL_SCRATCH_MB (default 4096; a target that
- * needs more runs alone) — the result is byte-identical for every budget — plus 40 bytes per minimizer of the store.
+ * needs more runs alone) — the result is byte-identical for every budget — plus 40 bytes per minimizer of the store (60 with the rescue).
+ * With herro_set_index_params, in place of the latter: 2 bytes per minimizer of the store (occ16), 8 bytes per 256 k-mers of the store (two
+ * per-tile tables) and 4 per read, and beside them the arrays of ONE part at a time — 79 bytes per minimizer of a pair of read blocks (70
+ * without the rescue), or 44 per minimizer of a hash range of the occurrence pass —, each with its sort histograms (1 KiB per 2048 elements).
  * Runs on the context's execution stream and returns when done.  HERRO_E_STATE: no reads; HERRO_E_NO_DEVICE: a context without
  * a device. */
 typedef struct { uint32_t k, w, max_occ, bandwidth, max_gap, min_score, min_anchors, occ_frac_ppm; } herro_overlap_params;
@@ -637,6 +641,42 @@ uint32_t herro_pairs_rescued(const herro_pairs* pairs);
  * What remains: an array with more than 1024 anchors between diagonal neighbours still breaks the chain. */
 typedef struct { uint32_t lookback, reserved[3]; } herro_chain_params;   /* lookback 0 = 64; reserved: 0 */
 int herro_set_chain_params(herro_ctx* ctx, const herro_chain_params* params /* NULL: defaults */);
+
+/* ---- an index in parts ("An index in parts"; minimap2's -I, the reference's 50 000-read target batches) ---------------
+ * The finder's index arrays are 32-bit indexed and sized by the minimizers of the whole store: a store of more than 2^32 - 4096 k-mers is
+ * HERRO_E_UNSUPPORTED, and well below that the index no longer fits beside the store.  max_kmers != 0 makes every later
+ * herro_find_overlaps[_core] and herro_find_overlap_pairs[_core] of the context build its index in parts of at most max_kmers k-mers; the records,
+ * the cut and the rescue's figures are byte for byte those of the unpartitioned call, for every max_kmers, occ_ranges, option and scratch budget
+ * (tests/index_parts_ref.py).  Two facts carry it: the whole store enters the specification only through occ(hash), the occurrences of a
+ * minimizer's hash in the store, and chains are independent per (t, q, strand).
+ *   pass A   occ16 = min(occ, 65535) of every minimizer of the store, by hash range: the 2k-bit hash space is cut into occ_ranges equal ranges
+ *            (0: as many as keep a range near the minimizers max_kmers k-mers give, a range that still overflows is halved), the minimizers of a
+ *            range are sorted by hash, and a run's length is the store's occ, since a run lies in one range.  The census of occ_frac_ppm is taken
+ *            here, in 64-bit bins.  A forced occ_ranges one of whose ranges holds more than 2^32 - 4096 minimizers: HERRO_E_UNSUPPORTED.
+ *   blocks   nk[r] = len[r] - k + 1 if len[r] >= k + w - 1, else 0; cap = max(max_kmers / 2, 1); reads in ascending id, acc = 0: a new block
+ *            opens in front of read r iff nk[r] > 0, acc > 0 and acc + nk[r] > cap (acc restarts at 0), then acc += nk[r].  A read of more
+ *            than cap k-mers is a block alone, reads without k-mers never open one, a non-empty store has at least one block.
+ *   pass B   the block pairs (i, j), i <= j, ascending: the minimizers of the two blocks with their occ16, sorted by hash.  A hash is used iff
+ *            2 <= occ <= cut — occ, not its occurrences in the pair —, the rescue's classes are taken from occ likewise; for i < j an anchor
+ *            (t, q) exists iff t lies in block i and q in block j, for i = j iff t < q.  Chunks, sorts, chains and the strand pick are those of
+ *            the unpartitioned call; the records of all pairs are put into target order by one stable sort.  A pair of two blocks without a
+ *            core read is skipped.  Two blocks of more than 2^32 - 4096 k-mers together (only reads longer than cap): HERRO_E_UNSUPPORTED,
+ *            naming the first read of each.
+ * The cost: a block is sketched and sorted again for every pair it is in.  params NULL or max_kmers 0: off, the default — the calls launch exactly
+ * the kernels they launched before the setting existed and keep their limits.  max_kmers > 2^32 - 4096, occ_ranges > 65536 or a non-zero reserved
+ * field: HERRO_E_INVALID, and the setting stays as it was (checked here; works on a context without a device).  HERRO_OVL_STATS=1 adds a line
+ * `OVLPART blocks= pairs= ranges= peak_bytes=` — the read blocks, the block pairs run, the hash ranges run, the most device scratch the finder held
+ * at once —; the other lines' figures are the sums over the parts and equal the unpartitioned call's, `chunks` excepted.
+ * herro_overlaps_index_blocks / herro_pairs_index_blocks: the read blocks of the call; 0: the setting was off (or a handle over a table).
+ * herro_index_plan: the block rule alone (csrc/index_plan.h: host code, also on a context without a device) — writes the n_blocks + 1 cuts,
+ * ascending read ids from 0 to n_reads, where cuts is not NULL and cap holds them, and returns n_blocks (0: an empty store).  HERRO_E_INVALID:
+ * k, w or max_kmers out of range (max_kmers 0 is max_kmers 1); HERRO_E_UNSUPPORTED: two blocks exceed 2^32 - 4096 k-mers together. */
+typedef struct { uint64_t max_kmers; uint32_t occ_ranges, reserved; } herro_index_params;
+int herro_set_index_params(herro_ctx* ctx, const herro_index_params* params /* NULL or max_kmers 0: off */);
+uint32_t herro_overlaps_index_blocks(const herro_overlaps* o);   /* 0: the setting was off */
+uint32_t herro_pairs_index_blocks(const herro_pairs* pairs);     /* 0: off, or a handle over a table */
+int64_t herro_index_plan(herro_ctx* ctx, uint64_t n_reads, const uint32_t* read_len, uint32_t k, uint32_t w, uint64_t max_kmers, uint64_t* cuts,
+                         uint64_t cap);
 
 /* ---- found alignments as PAF / .oec.zst --------------------------------------------------------------------
  * What `herro inference --write-alns DIR` keeps of a batch (AlnMode::Write, overlaps.rs:248-286; the lines, 349-352), for the alignments this

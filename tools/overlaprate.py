@@ -9,12 +9,15 @@ and with the fixed cut set to the value the index gave, so that the last two dif
 resc_high, resc_rescued and resc_anchors.
 --lookback N: every call chains over the N nearest predecessors of an anchor (Context.set_chain_lookback; a multiple of 64 in 64 .. 1024, 64 = the
 default and its kernels); the sizes gain chain_lookback and chain_chained when N is not 64.
+--index-kmers N [--occ-ranges R] (or --index-blocks B: the least N that gives no more than B read blocks): every set is measured with the index
+in one piece and in parts of at most N k-mers (Context.set_index_parts) on one context; a last line has both times, their ratio, the time and share
+of the occurrence pass and the `OVLPART` line's figures (part_blocks, part_pairs, part_ranges, part_peak_bytes).
 --tandem: only read pairs around tandem arrays (--tandem-pairs 64 pairs of flank + unit x copies + flank bases, two copies of one genome each with 1 %
 substitutions), the shape a look-back of 64 cuts short; `pair_coverage` is the mean share of the target an overlap between the two reads of a
 pair covers — the true overlap is the whole read.
 --deep: one short genome under many reads (--deep-reads 200 of --deep-len 400 bases), the shape a fixed cut below the depth finds nothing in.
 
-    python tools/overlaprate.py [--targets 256] [--long-targets 8] [--reps 5] [--no-align] [--occ-frac-ppm 5000] [--occ-dist 200] [--lookback 256] [--tandem] [--deep]"""
+    python tools/overlaprate.py [--targets 256] [--long-targets 8] [--reps 5] [--no-align] [--occ-frac-ppm 5000] [--occ-dist 200] [--lookback 256] [--index-kmers N] [--occ-ranges R] [--index-blocks B] [--tandem] [--deep]"""
 from __future__ import annotations
 
 import argparse
@@ -47,7 +50,7 @@ def stage_sizes(fn):
         f.seek(0)
         text = f.read().decode(errors="replace")
     sizes = {}
-    for tag, prefix in (("OVL", ""), ("OVLOCC", "occ_"), ("OVLRESC", "resc_"), ("OVLCHAIN", "chain_")):
+    for tag, prefix in (("OVL", ""), ("OVLOCC", "occ_"), ("OVLRESC", "resc_"), ("OVLCHAIN", "chain_"), ("OVLPART", "part_")):
         m = re.search(tag + r" (.*)", text)
         if m:
             sizes.update({prefix + k: int(v) for k, v in (kv.split("=") for kv in m.group(1).split())})
@@ -101,7 +104,32 @@ def pair_coverage(rows):
     return float(np.mean((own[:, 8].astype(np.int64) - own[:, 7]) / own[:, 6])) if len(own) else None
 
 
-def measure(name, sb, reps, params, align, occ_frac_ppm=0, rescue=(0, 0), lookback=0):
+def store_kmers(sb, k=25, w=17) -> int:
+    """k-mers of the reads that have a window (the block rule's nk, include/herro_amd.h, "an index in parts")"""
+    lens = np.diff(np.asarray(sb.off).astype(np.int64))
+    return int(np.where(lens >= k + w - 1, lens - k + 1, 0).sum())
+
+
+def measure_parts(c, name, sb, reps, params, index_kmers, occ_ranges):
+    """the call with its index in parts beside the unpartitioned call on the same reads: the times, their ratio, the OVLPART line and pass A's share
+    (the occurrence pass alone is what the census hook runs under the setting)"""
+    off = measure_on(c, name, sb, reps, params, False)
+    on = measure_on(c, name + f" index_kmers={index_kmers}", sb, reps, dict(params, index_kmers=index_kmers, occ_ranges=occ_ranges), False)
+    census = dict({k: v for k, v in params.items() if k in ("k", "w")}, occ_frac_ppm=5000, index_kmers=index_kmers, occ_ranges=occ_ranges)
+    c.occ_census(**census)
+    ta = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        c.occ_census(**census)
+        ta.append(time.perf_counter() - t0)
+    same = all(on.get(f) == off.get(f) for f in ("kmers", "minimizers", "anchors", "groups", "chained", "records"))
+    print(json.dumps({"set": name, "index_kmers": index_kmers, "occ_ranges": occ_ranges, "seconds_off": off["seconds_median"],
+                      "seconds_parts": on["seconds_median"], "parts_over_off": on["seconds_median"] / off["seconds_median"],
+                      "seconds_pass_a": float(np.median(ta)), "pass_a_share": float(np.median(ta)) / on["seconds_median"], "same_figures": same,
+                      **{k: v for k, v in on.items() if k.startswith("part_")}}), flush=True)
+
+
+def measure(name, sb, reps, params, align, occ_frac_ppm=0, rescue=(0, 0), lookback=0, index_kmers=0, occ_ranges=0, index_blocks=0):
     c = api.Context(0)
     c.set_reads(sb.seq, sb.qual, sb.off)
     if lookback:
@@ -110,7 +138,20 @@ def measure(name, sb, reps, params, align, occ_frac_ppm=0, rescue=(0, 0), lookba
     if rescue[0]:
         c.set_seed_rescue(*rescue)
         name += f" occ_dist={rescue[0]}"
-    if occ_frac_ppm:
+    if index_blocks:                               # the least part size that gives no more read blocks (the count falls as the size grows)
+        k, w = params.get("k", 25), params.get("w", 17)
+        lens = np.diff(np.asarray(sb.off).astype(np.int64))
+        lo, hi = 1, 2 * max(store_kmers(sb, k, w), 1)      # (hi: one block)
+        while lo < hi:
+            mid = (lo + hi) // 2
+            if len(api.index_plan(lens, k, w, mid)) - 1 <= index_blocks:
+                hi = mid
+            else:
+                lo = mid + 1
+        index_kmers = lo
+    if index_kmers:
+        measure_parts(c, name, sb, reps, dict(params, **({"occ_frac_ppm": occ_frac_ppm} if occ_frac_ppm else {})), index_kmers, occ_ranges)
+    elif occ_frac_ppm:
         fixed = measure_on(c, name, sb, reps, params, False)
         frac = measure_on(c, name, sb, reps, dict({k: v for k, v in params.items() if k != "max_occ"}, occ_frac_ppm=occ_frac_ppm), align)
         same = measure_on(c, name, sb, reps, dict(params, max_occ=frac["occ_cut"]), False)
@@ -164,6 +205,9 @@ def main():
     ap.add_argument("--occ-dist", type=int, default=0, help="rescue high-frequency minimizers, about one per N bases (200 = minimap2 -e200)")
     ap.add_argument("--rescue-max-occ", type=int, default=0, help="with --occ-dist: hashes above this many occurrences are never rescued (0: 4095)")
     ap.add_argument("--lookback", type=int, default=0, help="chain over the N nearest predecessors (a multiple of 64 in 64 .. 1024; 0: the default, 64)")
+    ap.add_argument("--index-kmers", type=int, default=0, help="also measure with the index in parts of at most N k-mers (Context.set_index_parts)")
+    ap.add_argument("--occ-ranges", type=int, default=0, help="with --index-kmers / --index-blocks: the hash ranges of the occurrence pass (0: chosen by the library)")
+    ap.add_argument("--index-blocks", type=int, default=0, help="--index-kmers chosen so that the store falls into B read blocks")
     ap.add_argument("--tandem", action="store_true", help="only the tandem shape: read pairs around tandem arrays")
     ap.add_argument("--tandem-pairs", type=int, default=64)
     ap.add_argument("--tandem-unit", type=int, default=40)
@@ -176,17 +220,17 @@ def main():
     rescue = (a.occ_dist, a.rescue_max_occ)
     if a.tandem:
         measure("tandem", Tandem(a.tandem_pairs, a.tandem_unit, a.tandem_copies, a.tandem_flank), a.reps, dict(k=15, w=5, max_occ=4096, min_score=100),
-                not a.no_align, a.occ_frac_ppm, rescue, a.lookback)
+                not a.no_align, a.occ_frac_ppm, rescue, a.lookback, a.index_kmers, a.occ_ranges, a.index_blocks)
         return
     if a.deep:
-        measure("deep", Deep(a.deep_reads, a.deep_len), a.reps, dict(k=15, w=5, max_occ=128, min_score=60), not a.no_align, a.occ_frac_ppm, rescue, a.lookback)
+        measure("deep", Deep(a.deep_reads, a.deep_len), a.reps, dict(k=15, w=5, max_occ=128, min_score=60), not a.no_align, a.occ_frac_ppm, rescue, a.lookback, a.index_kmers, a.occ_ranges, a.index_blocks)
         return
     if a.targets:
         measure("bench shape", synth.generate_parallel(a.targets, a.target_len, a.overlaps, chunk=64), a.reps,
-                dict(max_occ=128, min_score=100), not a.no_align, a.occ_frac_ppm, rescue, a.lookback)
+                dict(max_occ=128, min_score=100), not a.no_align, a.occ_frac_ppm, rescue, a.lookback, a.index_kmers, a.occ_ranges, a.index_blocks)
     if a.long_targets:
         measure(">= 30 kb", synth.generate_parallel(a.long_targets, a.long_len, 16, chunk=4, flank_min=200, flank_max=400), a.reps,
-                dict(max_occ=128), not a.no_align, a.occ_frac_ppm, rescue, a.lookback)
+                dict(max_occ=128), not a.no_align, a.occ_frac_ppm, rescue, a.lookback, a.index_kmers, a.occ_ranges, a.index_blocks)
 
 
 if __name__ == "__main__":
