@@ -1,6 +1,6 @@
 // cluster_dev.hip — the overlap graph's clusters on the device (cluster_dev.h; specification: DESIGN.md §14, tests/cluster_ref.py).  Stages:
 //   k_cl_arcs        the 2 E arcs of the E edges: key = src << 32 | dst, payload = strong; degrees by integer atomicAdd.  Sorted by src with the finder's
-//                    stable radix sort (ovl_radix_sort), offsets by its scan (ovl_scan_u32): the CSR, adj = dst | strong << 31.
+//                    stable radix sort (dev_radix_sort), offsets by the scan (dev_scan_u32; scan_sort_dev.h): the CSR, adj = dst | strong << 31.
 //   k_cl_hook, k_cl_jump   components: every strong arc hooks the larger label (and its label's label) to the smaller by atomicMin, then every label
 //                    jumps to its label's label until it stands.  Labels only fall and stay inside their component, so the fixed point — a round
 //                    whose flag stays clear — is the least id of the component, whatever the order.
@@ -21,7 +21,7 @@
 
 #include "cluster_plan.h"
 #include "dev_bufs.h"
-#include "overlap_dev.h"
+#include "scan_sort_dev.h"
 
 namespace herro {
 namespace {
@@ -286,10 +286,6 @@ __global__ __launch_bounds__(256) void k_cl_mask_nb(const uint32_t* __restrict__
     }                                                                                 \
   } while (0)
 
-inline uint32_t nblk(uint64_t n, uint32_t per = 256) { return (uint32_t)((n + per - 1) / per); }
-inline uint32_t bits_of(uint64_t v) { uint32_t b = 0; while (v) { b++; v >>= 1; } return b; }   // bits to hold 0 .. v
-void field_shifts(std::vector<uint32_t>& v, uint32_t lo, uint32_t nbits) { for (uint32_t s = lo; s < lo + nbits; s += 8) v.push_back(s); }
-
 struct Events {              // the stage timers (HERRO_CLUSTER_STATS): nothing is recorded without `on`
   bool on = false;
   hipEvent_t ev[6] = {};
@@ -361,8 +357,8 @@ int cl_build(uint32_t n, const uint32_t* w, uint32_t E, const uint32_t* a, const
   CL_TRY(B.get(&d_deg, n)); CL_TRY(B.get(&d_off, (uint64_t)n + 1)); CL_TRY(B.get(&d_adj, m));
   CL_TRY(B.get(&d_label, n)); CL_TRY(B.get(&d_d1, n)); CL_TRY(B.get(&d_level, n)); CL_TRY(B.get(&d_q0, n)); CL_TRY(B.get(&d_q1, n));
   CL_TRY(B.get(&d_cnt, CL_LEVEL_BATCH + 1)); CL_TRY(B.get(&d_flag, CL_HOOK_BATCH)); CL_TRY(B.get(&d_nlev, 1));
-  CL_TRY(B.get(&d_sort, ovl_sort_scratch(cap)));
-  CL_TRY(B.get(&d_partial, (uint64_t)ovl_scan_partials(n) + 1));
+  CL_TRY(B.get(&d_sort, dev_sort_scratch(cap)));
+  CL_TRY(B.get(&d_partial, (uint64_t)dev_scan_partials(n) + 1));
   CL_TRY(B.get(&d_rank, n)); CL_TRY(B.get(&d_wo, n)); CL_TRY(B.get(&d_S, (uint64_t)n + 1));
   if (E) {
     CL_TRY(hipMemcpyAsync(G.d_a, a, 4ull * E, hipMemcpyHostToDevice, st));
@@ -383,11 +379,11 @@ int cl_build(uint32_t n, const uint32_t* w, uint32_t E, const uint32_t* a, const
     CL_TRY(hipGetLastError());
     std::vector<uint32_t> sh;
     field_shifts(sh, 32, id_bits);
-    if (ovl_radix_sort(&k0, &p0, &k1, &p1, m, sh, d_sort, st, err)) return CL_HIP;
+    if (dev_radix_sort(&k0, &p0, &k1, &p1, m, sh, d_sort, st, err)) return CL_HIP;
     k_cl_adj<<<nblk(m), 256, 0, st>>>(k0, p0, m, d_adj);
     CL_TRY(hipGetLastError());
   }
-  if (ovl_scan_u32(d_deg, n, d_off, d_partial, st, err)) return CL_HIP;
+  if (dev_scan_u32(d_deg, n, d_off, d_partial, st, err)) return CL_HIP;
   CL_TRY(T.mark(1, st));
   // ---- components (k0: the sorted arcs' keys, their src in the high half)
   k_cl_iota<<<nblk(n), 256, 0, st>>>(d_label, n);
@@ -430,10 +426,10 @@ int cl_build(uint32_t n, const uint32_t* w, uint32_t E, const uint32_t* a, const
     std::vector<uint32_t> sh;
     field_shifts(sh, 0, bits_of(std::min(levels2, n)));   // by level
     field_shifts(sh, 32, id_bits);                        // then by component, stable
-    if (ovl_radix_sort(&k0, &p0, &k1, &p1, n, sh, d_sort, st, err)) return CL_HIP;
+    if (dev_radix_sort(&k0, &p0, &k1, &p1, n, sh, d_sort, st, err)) return CL_HIP;
     k_cl_rank<<<nblk(n), 256, 0, st>>>(p0, d_w, n, d_rank, d_wo);
     CL_TRY(hipGetLastError());
-    if (ovl_scan_u32(d_wo, n, d_S, d_partial, st, err)) return CL_HIP;
+    if (dev_scan_u32(d_wo, n, d_S, d_partial, st, err)) return CL_HIP;
     k_cl_part<<<nblk(n), 256, 0, st>>>(p0, d_S, d_wo, n, k, G.d_part, d_rows);
     CL_TRY(hipGetLastError());
   }
@@ -446,7 +442,7 @@ int cl_build(uint32_t n, const uint32_t* w, uint32_t E, const uint32_t* a, const
     std::vector<uint32_t> sh;
     field_shifts(sh, 0, id_bits);
     field_shifts(sh, 32, bits_of(k));                     // (k itself: the part of the arcs that do not cross)
-    if (ovl_radix_sort(&k0, &p0, &k1, &p1, m, sh, d_sort, st, err)) return CL_HIP;
+    if (dev_radix_sort(&k0, &p0, &k1, &p1, m, sh, d_sort, st, err)) return CL_HIP;
     k_cl_nb_heads<<<nblk(m), 256, 0, st>>>(k0, m, k, d_rows);
     CL_TRY(hipGetLastError());
   }

@@ -1,4 +1,4 @@
-// dev_bufs.h — the device scratch of one host call (overlap_dev.hip, frontend_api.hip).
+// dev_bufs.h — the device scratch of one host call (overlap_dev.hip, scan_sort_dev.h, frontend_api.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -54,7 +54,7 @@ int fasta_text_dev(const JobDev& J, uint64_t row_elems, const uint32_t* tgt_win_
 // The 64-bit offset join of the pieces as fasta_text_dev runs it, on arrays of the caller's (the test hook herro_debug_offsets64): piece p has
 // lo_in[p] + 2^32 hi_in[p] bytes; off[0 .. n] are the running sums, off[n] the total.  The low words are scanned modulo 2^32 into lo, a piece at
 // which that prefix falls adds a carry to its hi_in (which is changed), the high words are scanned into hi, off joins them.  All on the device:
-// lo_in, hi_in [n], lo, hi, off [n + 1], partial [ovl_scan_partials(n)].  Exact while the total is below 2^64.  Queued on st; nothing is awaited.
+// lo_in, hi_in [n], lo, hi, off [n + 1], partial [dev_scan_partials(n)].  Exact while the total is below 2^64.  Queued on st; nothing is awaited.
 int fasta_offsets64(uint32_t* lo_in, uint32_t* hi_in, uint32_t n, uint32_t* lo, uint32_t* hi, uint64_t* off, uint32_t* partial, hipStream_t st,
                     std::string& err);
 

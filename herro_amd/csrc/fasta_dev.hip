@@ -1,5 +1,5 @@
 // fasta_dev.hip — FASTA text of a job's corrected reads, formed where the consensus kernel left the bases (fasta_dev.h; specification: DESIGN.md §15,
-// tests/chop_ref.py; the piece rule and the byte counts: chop_plan.h).  Stages, every prefix by the finder's scan (ovl_scan_u32):
+// tests/chop_ref.py; the piece rule and the byte counts: chop_plan.h).  Stages, every prefix by the shared scan (dev_scan_u32, scan_sort_dev.h):
 //   segments   k_fa_win     one lane per window: its target (a search in tgt_win_off), corrected or not (consensus.rs:90-101: min(n_alns, 30) >= 2, and
 //                           the target has an id), its bases, and whether it begins a run of corrected windows.
 //              (scans)      base prefix of the windows; number of the run a window begins.
@@ -22,7 +22,7 @@
 #include <algorithm>
 #include <chrono>
 
-#include "overlap_dev.h"
+#include "scan_sort_dev.h"
 
 namespace herro {
 namespace {
@@ -280,11 +280,11 @@ struct Carver {
 }  // namespace
 
 #define FA_TRY(what, expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) { (void)hipStreamSynchronize(st); err = std::string("herro_job_fasta_dev: ") + what + ": " + hipGetErrorString(_e); return FASTA_HIP; } } while (0)
-#define FA_SCAN(in, n, out) do { if (ovl_scan_u32(in, n, out, d_partial, st, err) != OVL_OK) { (void)hipStreamSynchronize(st); err = "herro_job_fasta_dev: " + err; return FASTA_HIP; } } while (0)
+#define FA_SCAN(in, n, out) do { if (dev_scan_u32(in, n, out, d_partial, st, err) != 0) { (void)hipStreamSynchronize(st); err = "herro_job_fasta_dev: " + err; return FASTA_HIP; } } while (0)
 #define FA_MEM(ptr, what) do { if (!(ptr)) { (void)hipStreamSynchronize(st); err = std::string("herro_job_fasta_dev: out of memory for ") + what; return FASTA_HIP; } } while (0)
 
 // The 64-bit offsets of D.P pieces out of two 32-bit scans (the stages' "(scans)" of the pieces): lo_in / hi_in hold the halves of every piece's
-// bytes; hi_in takes the carries.  partial: ovl_scan_partials(D.P) entries.  Queued on st.
+// bytes; hi_in takes the carries.  partial: dev_scan_partials(D.P) entries.  Queued on st.
 static int offsets64(const FaDev& D, uint32_t* d_partial, hipStream_t st, std::string& err) {
   const uint32_t P = D.P;
   FA_SCAN(D.lo_in, P, D.lo);
@@ -324,7 +324,7 @@ int fasta_text_dev(const JobDev& J, uint64_t row_elems, const uint32_t* tgt_win_
     c.take(&d_two, (uint64_t)n_targets + 1); c.take(&d_present, n_targets); c.take(&d_blob, names.blob.size()); c.take(&d_noff, names.off.size());
     uint32_t** const per_win[] = {&D.win_t, &D.wlen, &D.head, &D.wpre, &D.hidx, &D.run_a, &D.run_b, &D.run_t, &D.nonempty, &D.kept, &D.segpos, &D.piece_off};
     for (uint32_t** q : per_win) c.take(q, (uint64_t)N + 1);
-    c.take(&D.tgt_end, n_targets); c.take(&D.stats, 6); c.take(&d_partial, (uint64_t)ovl_scan_partials(N) + 1);
+    c.take(&D.tgt_end, n_targets); c.take(&D.stats, 6); c.take(&d_partial, (uint64_t)dev_scan_partials(N) + 1);
   };
   Carver ca;
   lay_a(ca);
@@ -367,7 +367,7 @@ int fasta_text_dev(const JobDev& J, uint64_t row_elems, const uint32_t* tgt_win_
     uint32_t** const per_piece[] = {&D.piece_run, &D.lo_in, &D.lo, &D.hi_in, &D.hi};
     for (uint32_t** q : per_piece) c.take(q, (uint64_t)P + 1);
     c.take(&D.off, (uint64_t)P + 1);
-    if (ovl_scan_partials(P) > ovl_scan_partials(N)) c.take(&d_partial, (uint64_t)ovl_scan_partials(P) + 1);
+    if (dev_scan_partials(P) > dev_scan_partials(N)) c.take(&d_partial, (uint64_t)dev_scan_partials(P) + 1);
   };
   Carver cb;
   lay_b(cb);

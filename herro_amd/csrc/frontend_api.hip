@@ -4,7 +4,7 @@
 // hipcc) over overlap_dev.hip, align_dev.hip and paf_dev.hip; contexts, the model and jobs are herro_api.hip.  Ahead of them all, for raw reads:
 // herro_find_adapters and its handle, over adapter_dev.hip (the plan and the cut are host code: fastx.cpp), and herro_store_cut with its test hook
 // herro_debug_store_copy, over store_dev.hip: the store cut to the plan's pieces on the device.  The primitives every device stage stands on have hooks of
-// their own: herro_debug_scan_u32, herro_debug_radix_sort (overlap_dev.hip) and herro_debug_offsets64 (fasta_dev.hip's offset join).  Behind the finder: herro_cluster_graph, herro_pairs_cluster and
+// their own: herro_debug_scan_u32, herro_debug_radix_sort (scan_sort_dev.hip) and herro_debug_offsets64 (fasta_dev.hip's offset join).  Behind the finder: herro_cluster_graph, herro_pairs_cluster and
 // herro_clusters_*, over cluster_dev.hip (the checks and the part rule are host code: cluster_plan.h): the reads partitioned by their overlap graph.
 #include <hip/hip_runtime.h>
 
@@ -24,6 +24,7 @@
 #include "index_plan.h"
 #include "overlap_dev.h"
 #include "paf_dev.h"
+#include "scan_sort_dev.h"
 #include "store_dev.h"
 
 namespace {
@@ -990,7 +991,7 @@ int paf_emit_dev(herro_ctx* ctx, const char* who, const herro_aligned_dev* a, co
   for (int b = 0; b < halves; b++) {
     FRONT_TRY(ctx, who, "text", B.bytes(&d_text[b], max_bytes));
     FRONT_TRY(ctx, who, "line offsets", B.bytes(&d_off[b], 4ull * (max_rows + 1ull)));
-    FRONT_TRY(ctx, who, "scan scratch", B.bytes(&d_part[b], 4ull * herro::ovl_scan_partials(max_rows) + 64));
+    FRONT_TRY(ctx, who, "scan scratch", B.bytes(&d_part[b], 4ull * herro::dev_scan_partials(max_rows) + 64));
     FRONT_TRY(ctx, who, "pinned text", hipHostMalloc((void**)&S.pin[b], max_bytes, hipHostMallocDefault));
     FRONT_TRY(ctx, who, "event", hipEventCreateWithFlags(&S.ev[b], hipEventDisableTiming));
   }
@@ -1001,7 +1002,7 @@ int paf_emit_dev(herro_ctx* ctx, const char* who, const herro_aligned_dev* a, co
     if (!cbytes[c]) return HERRO_OK;
     const int b = (int)(c & 1);
     const uint32_t r0 = cut[c], cnt = cut[c + 1] - cut[c];
-    if (herro::ovl_scan_u32(d_len + r0, cnt, d_off[b], d_part[b], ctx->stream, msg) != herro::OVL_OK) { ctx->err = std::string(who) + ": " + msg; return HERRO_E_NO_DEVICE; }
+    if (herro::dev_scan_u32(d_len + r0, cnt, d_off[b], d_part[b], ctx->stream, msg) != herro::OVL_OK) { ctx->err = std::string(who) + ": " + msg; return HERRO_E_NO_DEVICE; }
     herro::launch_paf_write(d_rows + r0, a->d_ops, d_names, d_noff, d_off[b], d_sums + r0, cnt, d_text[b], cbytes[c], ctx->stream);
     FRONT_TRY(ctx, who, "k_paf_write launch", hipGetLastError());
     FRONT_TRY(ctx, who, "text copy", hipMemcpyAsync(S.pin[b], d_text[b], cbytes[c], hipMemcpyDeviceToHost, ctx->stream));
@@ -1344,10 +1345,10 @@ int64_t herro_debug_store_copy(herro_ctx* ctx, int which, void* out, uint64_t ca
   return (int64_t)bytes[which];
 }
 
-// ---- test hooks: the shared scan and radix sort (overlap_dev.hip) and the 64-bit offset join (fasta_dev.hip) on arrays of the caller's ----------
+// ---- test hooks: the shared scan and radix sort (scan_sort_dev.hip) and the 64-bit offset join (fasta_dev.hip) on arrays of the caller's ----------
 // The arrays are carved from ONE device block, as fasta_dev.hip's Carver and cluster_dev.hip's Bufs lay theirs next to live arrays, every one
 // exactly as large as its client sizes it and with GUARD_WORDS words of a fixed pattern directly behind it: a store one entry past an array or past
-// ovl_scan_partials(n) / ovl_sort_scratch(n) lands in a guard and is counted, where in a client it would change a neighbour without any fault.
+// dev_scan_partials(n) / dev_sort_scratch(n) lands in a guard and is counted, where in a client it would change a neighbour without any fault.
 namespace {
 constexpr uint32_t GUARD_WORDS = 64;
 inline uint32_t guard_word(uint32_t i) { return 0xA5C3E1F0u ^ (i * 0x01010101u); }
@@ -1400,11 +1401,11 @@ int herro_debug_scan_u32(herro_ctx* ctx, const uint32_t* in, uint64_t n, uint32_
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   herro::Bufs B;
   Guarded Q;
-  const size_t a_in = Q.add(4 * n), a_out = Q.add(4 * (n + 1)), a_part = Q.add(4ull * herro::ovl_scan_partials((uint32_t)n));
+  const size_t a_in = Q.add(4 * n), a_out = Q.add(4 * (n + 1)), a_part = Q.add(4ull * herro::dev_scan_partials((uint32_t)n));
   FRONT_TRY(ctx, who, "device block", Q.alloc(B, ctx->stream));
   if (n) FRONT_TRY(ctx, who, "upload", hipMemcpyAsync(Q.u32(a_in), in, 4 * n, hipMemcpyHostToDevice, ctx->stream));
   std::string msg;
-  if (herro::ovl_scan_u32(Q.u32(a_in), (uint32_t)n, Q.u32(a_out), Q.u32(a_part), ctx->stream, msg) != herro::OVL_OK) {
+  if (herro::dev_scan_u32(Q.u32(a_in), (uint32_t)n, Q.u32(a_out), Q.u32(a_part), ctx->stream, msg) != herro::OVL_OK) {
     (void)hipStreamSynchronize(ctx->stream);
     ctx->err = std::string(who) + ": " + msg;
     return HERRO_E_NO_DEVICE;
@@ -1457,7 +1458,7 @@ int herro_debug_radix_sort(herro_ctx* ctx, uint64_t* keys, uint64_t* pays, uint6
   Guarded Q;
   size_t arr[4];                                     // k0, p0, k1, p1
   for (size_t& a : arr) a = Q.add(8 * n);
-  const size_t a_scr = Q.add(4ull * herro::ovl_sort_scratch(n));
+  const size_t a_scr = Q.add(4ull * herro::dev_sort_scratch(n));
   FRONT_TRY(ctx, who, "device block", Q.alloc(B, ctx->stream));
   uint64_t *k0 = Q.u64(arr[0]), *p0 = Q.u64(arr[1]), *k1 = Q.u64(arr[2]), *p1 = Q.u64(arr[3]);
   if (n) {
@@ -1466,7 +1467,7 @@ int herro_debug_radix_sort(herro_ctx* ctx, uint64_t* keys, uint64_t* pays, uint6
   }
   std::string msg;
   const std::vector<uint32_t> sh(shifts, shifts + n_shifts);
-  if (herro::ovl_radix_sort(&k0, &p0, &k1, &p1, (uint32_t)n, sh, Q.u32(a_scr), ctx->stream, msg) != herro::OVL_OK) {
+  if (herro::dev_radix_sort(&k0, &p0, &k1, &p1, (uint32_t)n, sh, Q.u32(a_scr), ctx->stream, msg) != herro::OVL_OK) {
     (void)hipStreamSynchronize(ctx->stream);
     ctx->err = std::string(who) + ": " + msg;
     return HERRO_E_NO_DEVICE;
@@ -1493,7 +1494,7 @@ int herro_debug_offsets64(herro_ctx* ctx, const uint64_t* bytes, uint64_t n, uin
     herro::Bufs B;
     Guarded Q;
     const size_t a_off = Q.add(8 * (n + 1)), a_lo_in = Q.add(4 * n), a_hi_in = Q.add(4 * n), a_lo = Q.add(4 * (n + 1)), a_hi = Q.add(4 * (n + 1)),
-                 a_part = Q.add(4ull * herro::ovl_scan_partials((uint32_t)n));
+                 a_part = Q.add(4ull * herro::dev_scan_partials((uint32_t)n));
     FRONT_TRY(ctx, who, "device block", Q.alloc(B, ctx->stream));
     FRONT_TRY(ctx, who, "upload", hipMemcpyAsync(Q.u32(a_lo_in), halves.data(), 4 * n, hipMemcpyHostToDevice, ctx->stream));
     FRONT_TRY(ctx, who, "upload", hipMemcpyAsync(Q.u32(a_hi_in), halves.data() + n, 4 * n, hipMemcpyHostToDevice, ctx->stream));

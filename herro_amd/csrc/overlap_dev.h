@@ -1,4 +1,4 @@
-// overlap_dev.h — which reads overlap, where, on which strand (overlap_dev.hip): the GPU counterpart of the seeding and chaining
+// overlap_dev.h — which reads overlap, where, on which strand (overlap_dev.hip; the row table: overlap_rows.hip): the GPU counterpart of the seeding and chaining
 // half of the `minimap2 -x ava-ont` run that `herro inference` starts without --read-alns (mm2.rs:15-30, overlaps.rs:340-344).
 // Minimizer sketch of the resident 2-bit store, radix sort by hash, frequency cut, anchor expansion, radix sort by
 // (t, q, rel, tpos, qpos), one wave64 per (t, q, rel) group for the chain.  The specification is DESIGN.md §10 and
@@ -63,19 +63,17 @@ struct OvlStats {
   uint64_t blocks = 0, block_pairs = 0, ranges = 0, peak_bytes = 0;
 };
 
-enum { OVL_OK = 0, OVL_HIP = 1, OVL_UNSUPPORTED = 2 };
+enum { OVL_OK = 0, OVL_HIP = 1, OVL_UNSUPPORTED = 2 };   // (the scan and the sort the finder runs on are scan_sort_dev.h's: 0 / 1 there too)
 
-// The finder's own exclusive scan of u32 (k_scan_partial / k_scan_top / k_scan_final), for the other device code of the front end (paf_dev.hip's line
-// offsets): out[0 .. n] from in[0 .. n), out[n] = the total; partial: ovl_scan_partials(n) entries of scratch.  Queued on st; nothing is awaited.
-uint32_t ovl_scan_partials(uint32_t n);
-int ovl_scan_u32(const uint32_t* in, uint32_t n, uint32_t* out, uint32_t* partial, hipStream_t st, std::string& err);
-
-// The finder's own stable LSD radix sort (k_rs_hist / k_rs_scatter over ovl_scan_u32), for the other device code of the front end (cluster_dev.hip's
-// arcs and order): n 64-bit keys with their 64-bit payloads, one 8-bit digit per entry of `shifts` in ascending significance.  The sorted arrays end
-// up in (*k0, *p0): the pointers are swapped after every pass.  scratch: ovl_sort_scratch(n) entries of u32.  Queued on st; nothing is awaited.
-uint64_t ovl_sort_scratch(uint64_t n);
-int ovl_radix_sort(uint64_t** k0, uint64_t** p0, uint64_t** k1, uint64_t** p1, uint32_t n, const std::vector<uint32_t>& shifts, uint32_t* scratch,
-                   hipStream_t st, std::string& err);
+// for the finder's own units (overlap_dev.hip, overlap_rows.hip): a failed HIP call ends the function with OVL_HIP and its text in `err`
+#define OVL_TRY(expr)                                                                  \
+  do {                                                                                 \
+    const hipError_t _e = (expr);                                                      \
+    if (_e != hipSuccess) {                                                            \
+      err = std::string("overlap finder: " #expr ": ") + hipGetErrorString(_e);        \
+      return OVL_HIP;                                                                  \
+    }                                                                                  \
+  } while (0)
 
 // minimizers of the whole store sorted by (rid, pos): hash[i], meta[i] = rid << 32 | pos << 1 | strand (host vectors)
 int ovl_sketch(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vector<uint64_t>& hash, std::vector<uint64_t>& meta,
@@ -126,6 +124,10 @@ struct OvlRecs {             // a device array of records; it owns its memory
 // (t, q) order — the primaries of api.pair_rows over herro_find_overlaps' records.  The host reads one count per chunk.
 int ovl_find_pairs(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uint64_t budget_bytes, hipStream_t st, OvlRecs& out,
                    OvlStats& stats, std::string& err);
+
+// ---- overlap_rows.hip: what needs only the records and the shared scan and sort ------------------------------------------------------------------
+// The records of all block pairs of an index in parts into target order, stably: ovl_find_pairs' last step there (n_reads bounds the target ids).
+int ovl_sort_recs(OvlRecs& R, uint32_t n_reads, hipStream_t st, std::string& err);
 
 // The 2 P rows herro_find_overlaps emits for P primaries — (t, q) and (q, t) of each, by (tid, qid) — as a table: rids / aln_off group
 // them by target, rec_of_row[i] is p for the row that is primary p and P + p for its mirror.  Sorted and grouped on the device.

@@ -3,7 +3,7 @@
 //   k_sketch     a block per 256 k-mers of one read: f / r / hash per k-mer, window minima in LDS, every k-mer equal to the
 //                minimum of a window it lies in is selected.  Run twice: count per tile, scan, write — so the output is in
 //                (rid, pos) order without any atomic deciding a place.
-//   radix sort   LSD, 8-bit digits, 64-bit key + 64-bit payload, stable (per-block histogram, scan, ranked scatter).
+//   radix sort   by hash, stable: the shared sort and scan of scan_sort_dev.h (dev_radix_sort, dev_scan_u32), as every sort and prefix below.
 //   k_occ_census, k_occ_pick   occ_frac_ppm only: the histogram of the run lengths (LDS bins below 2048, the table beyond) and, in one workgroup, the
 //                cut that leaves the given fraction of the distinct hashes above it; k_runs_occ reads it where k_occ_pick left it.
 //   k_occ_place, k_rescue, k_resc_kind   the rescue of high-frequency minimizers only (OvlParams.occ_dist != 0): the run length of every minimizer put back
@@ -15,18 +15,20 @@
 //   k_chain      one wave64 per (t, q, rel) group: the 64 predecessors of an anchor are the 64 lanes.
 //   k_chain_far  OvlParams.lookback = 64 R > 64 only: k_chain with R rounds a step, the R blocks in front of the current one in an LDS ring.
 //   k_walk       back through the stored predecessors: first anchor, anchor count, coordinates.
-//   k_sketch_part, k_occ16, k_occ_pick64, k_part_cls, k_part_gather, k_part_runs, k_part_expand, k_rec_keys, k_rec_gather   OvlParams.index_kmers != 0
-//                only (herro_set_index_params): the occurrences of every minimizer's hash by hash range, then the stages above per pair of read
-//                blocks, a hash run judged by those occurrences ("an index in parts", below); host side: part_index, find_parts.
+//   k_sketch_part, k_occ16, k_part_cls, k_part_gather, k_part_runs, k_part_expand   OvlParams.index_kmers != 0 only (herro_set_index_params): the
+//                occurrences of every minimizer's hash by hash range (the pick over 64-bit bins: k_occ_pick again), then the stages above per pair
+//                of read blocks, a hash run judged by those occurrences ("an index in parts", below); host side: part_index, find_parts.
+// The row table and the final order of the records of an index in parts are overlap_rows.hip.
 // A core mask (one byte per read, non-zero: the read is a target) keeps k_runs / k_expand from creating an anchor between two non-core
 // reads, so everything behind the anchors sees wanted pairs only; without a mask (CORE = false) the two kernels are what they were.
 // Nothing an atomic orders reaches the output: the only atomics are integer sums (histograms, anchors per read).
 #include "overlap_dev.h"
-#include "dev_bufs.h"
 #include "index_plan.h"
+#include "scan_sort_dev.h"
 
 #include <algorithm>
 #include <climits>
+#include <type_traits>
 
 namespace herro {
 namespace {
@@ -34,71 +36,6 @@ namespace {
 constexpr uint64_t INF64 = 0xffffffffffffffffull;
 constexpr int SK_T = 256;                    // k-mers (threads) of a sketch tile
 constexpr int SK_H = SK_T + 2 * 63 + 2;      // hashes a tile needs: w - 1 <= 63 on either side
-constexpr int SC_ITEMS = 8;                  // scan / sort: items per thread, 256 threads
-constexpr uint32_t SC_TILE = 256 * SC_ITEMS;
-
-// ---- block helpers (256 threads = 4 waves) ------------------------------------------------------------------------------------
-__device__ inline uint32_t block_excl_scan(uint32_t v, uint32_t* lds4, uint32_t& total) {
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(inc, o, 64);
-    if ((int)lane >= o) inc += t;
-  }
-  if (lane == 63) lds4[wave] = inc;
-  __syncthreads();
-  uint32_t base = 0;
-  total = 0;
-#pragma unroll
-  for (uint32_t i = 0; i < 4; i++) {
-    const uint32_t c = lds4[i];
-    if (i < wave) base += c;
-    total += c;
-  }
-  __syncthreads();
-  return base + inc - v;
-}
-
-// ---- exclusive scan of u32 (out has n + 1 entries: out[n] = total) ---------------------------------------------------------
-__global__ __launch_bounds__(256) void k_scan_partial(const uint32_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ partial) {
-  __shared__ uint32_t lds4[4];
-  const uint64_t i0 = (uint64_t)blockIdx.x * SC_TILE + threadIdx.x * SC_ITEMS;
-  uint32_t s = 0;
-#pragma unroll
-  for (int e = 0; e < SC_ITEMS; e++) if (i0 + e < n) s += in[i0 + e];
-  uint32_t total;
-  (void)block_excl_scan(s, lds4, total);
-  if (threadIdx.x == 0) partial[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(256) void k_scan_top(uint32_t* __restrict__ partial, uint32_t nb) {
-  __shared__ uint32_t lds4[4];
-  uint32_t carry = 0;
-  for (uint32_t b0 = 0; b0 < nb; b0 += 256) {
-    const uint32_t i = b0 + threadIdx.x;
-    const uint32_t v = i < nb ? partial[i] : 0u;
-    uint32_t total;
-    const uint32_t ex = block_excl_scan(v, lds4, total);
-    if (i < nb) partial[i] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) partial[nb] = carry;
-}
-
-__global__ __launch_bounds__(256) void k_scan_final(const uint32_t* __restrict__ in, uint32_t n, const uint32_t* __restrict__ partial,
-                                                    uint32_t nb, uint32_t* __restrict__ out) {
-  __shared__ uint32_t lds4[4];
-  const uint64_t i0 = (uint64_t)blockIdx.x * SC_TILE + threadIdx.x * SC_ITEMS;
-  uint32_t v[SC_ITEMS], s = 0;
-#pragma unroll
-  for (int e = 0; e < SC_ITEMS; e++) { v[e] = i0 + e < n ? in[i0 + e] : 0u; s += v[e]; }
-  uint32_t total;
-  uint32_t at = block_excl_scan(s, lds4, total) + partial[blockIdx.x];
-#pragma unroll
-  for (int e = 0; e < SC_ITEMS; e++) { if (i0 + e < n) out[i0 + e] = at; at += v[e]; }
-  if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = partial[nb];
-}
 
 // ---- sketch -----------------------------------------------------------------------------------------------------------------
 __device__ inline uint64_t hash64(uint64_t x, uint64_t m) {   // minimap2's invertible mix on 2k bits
@@ -128,20 +65,17 @@ __device__ inline uint64_t kmer_hash(const uint64_t* __restrict__ words, uint64_
   return hash64(f < r ? f : r, mask);
 }
 
-// tile_off[r]: first tile of read r (reads shorter than k + w - 1 have none)
-__global__ __launch_bounds__(SK_T) void k_sketch(const uint64_t* __restrict__ words, const uint64_t* __restrict__ word_off,
-                                                 const uint64_t* __restrict__ base_off, const uint32_t* __restrict__ tile_off,
-                                                 uint32_t n_reads, uint32_t k, uint32_t w, uint32_t* __restrict__ tile_cnt,
-                                                 const uint32_t* __restrict__ tile_at, uint64_t* __restrict__ hash_out,
-                                                 uint64_t* __restrict__ meta_out, int write) {
-  __shared__ uint64_t sh[SK_H];
-  __shared__ uint64_t wm[SK_H];
-  __shared__ uint8_t ss[SK_H];
-  __shared__ uint32_t wc[4];
-  const uint32_t b = blockIdx.x, tid = threadIdx.x;
-  uint32_t lo_r = 0, hi_r = n_reads;          // largest r with tile_off[r] <= b
+// The front of a sketch tile: block b of the store's tiles is 256 k-mers of one read among r_lo .. r_hi - 1 (tile_off[r]: first tile of read r;
+// reads shorter than k + w - 1 have none).  Leaves the hashes the tile needs in sh, their strands in ss and the window minima in wm, all indexed
+// from k-mer lo of the read on, and for the thread's own k-mer j its hash hj and sel: it equals the minimum of a window it lies in.
+struct SketchTile { uint32_t rid, j, lo; uint64_t hj; bool sel; };
+__device__ __forceinline__ SketchTile sketch_tile(const uint64_t* __restrict__ words, const uint64_t* __restrict__ word_off,
+                                                  const uint64_t* __restrict__ base_off, const uint32_t* __restrict__ tile_off, uint32_t r_lo,
+                                                  uint32_t r_hi, uint32_t b, uint32_t k, uint32_t w, uint64_t* sh, uint64_t* wm, uint8_t* ss) {
+  const uint32_t tid = threadIdx.x;
+  uint32_t lo_r = r_lo, hi_r = r_hi;          // largest r with tile_off[r] <= b
   while (hi_r - lo_r > 1) {
-    const uint32_t mid = (lo_r + hi_r) >> 1;
+    const uint32_t mid = (lo_r + hi_r) >> 1;  // (no more than OVL_MAX_READS = 2^31 - 1 reads: the sum fits)
     if (tile_off[mid] <= b) lo_r = mid; else hi_r = mid;
   }
   const uint32_t rid = lo_r;
@@ -175,7 +109,21 @@ __global__ __launch_bounds__(SK_T) void k_sketch(const uint64_t* __restrict__ wo
       for (uint32_t s = s0; s <= s1; s++) sel |= wm[s - lo] == hj;
     }
   }
-  const uint64_t bal = __ballot(sel);
+  return SketchTile{rid, j, lo, hj, sel};
+}
+
+__global__ __launch_bounds__(SK_T) void k_sketch(const uint64_t* __restrict__ words, const uint64_t* __restrict__ word_off,
+                                                 const uint64_t* __restrict__ base_off, const uint32_t* __restrict__ tile_off,
+                                                 uint32_t n_reads, uint32_t k, uint32_t w, uint32_t* __restrict__ tile_cnt,
+                                                 const uint32_t* __restrict__ tile_at, uint64_t* __restrict__ hash_out,
+                                                 uint64_t* __restrict__ meta_out, int write) {
+  __shared__ uint64_t sh[SK_H];
+  __shared__ uint64_t wm[SK_H];
+  __shared__ uint8_t ss[SK_H];
+  __shared__ uint32_t wc[4];
+  const uint32_t b = blockIdx.x, tid = threadIdx.x;
+  const SketchTile t = sketch_tile(words, word_off, base_off, tile_off, 0, n_reads, b, k, w, sh, wm, ss);
+  const uint64_t bal = __ballot(t.sel);
   const uint32_t lane = tid & 63, wave = tid >> 6;
   if (lane == 0) wc[wave] = (uint32_t)__popcll(bal);
   __syncthreads();
@@ -185,67 +133,10 @@ __global__ __launch_bounds__(SK_T) void k_sketch(const uint64_t* __restrict__ wo
     if (tid == 0) tile_cnt[b] = total;
     return;
   }
-  if (sel) {
+  if (t.sel) {
     const uint32_t at = tile_at[b] + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1));
-    hash_out[at] = hj;
-    meta_out[at] = ((uint64_t)rid << 32) | ((uint64_t)(j + k - 1) << 1) | ss[j - lo];
-  }
-}
-
-// ---- radix sort: one 8-bit digit per pass ----------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_rs_hist(const uint64_t* __restrict__ keys, uint32_t n, uint32_t shift, uint32_t nb,
-                                                 uint32_t* __restrict__ hist) {
-  __shared__ uint32_t h[256];
-  h[threadIdx.x] = 0;
-  __syncthreads();
-  const uint64_t i0 = (uint64_t)blockIdx.x * SC_TILE;
-#pragma unroll
-  for (int e = 0; e < SC_ITEMS; e++) {
-    const uint64_t i = i0 + e * 256 + threadIdx.x;
-    if (i < n) atomicAdd(&h[(keys[i] >> shift) & 255u], 1u);
-  }
-  __syncthreads();
-  hist[(uint64_t)threadIdx.x * nb + blockIdx.x] = h[threadIdx.x];   // digit-major: the scan gives every (digit, block) its place
-}
-
-__global__ __launch_bounds__(256) void k_rs_scatter(const uint64_t* __restrict__ keys, const uint64_t* __restrict__ pays, uint32_t n,
-                                                    uint32_t shift, uint32_t nb, const uint32_t* __restrict__ offs,
-                                                    uint64_t* __restrict__ keys_out, uint64_t* __restrict__ pays_out) {
-  __shared__ uint32_t running[256];
-  __shared__ uint32_t wcnt[4][256];
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  running[tid] = offs[(uint64_t)tid * nb + blockIdx.x];
-#pragma unroll
-  for (int v = 0; v < 4; v++) wcnt[v][tid] = 0;
-  __syncthreads();
-  const uint64_t i0 = (uint64_t)blockIdx.x * SC_TILE;
-  for (int e = 0; e < SC_ITEMS; e++) {          // elements in index order: round e holds i0 + 256 e .. + 255
-    const uint64_t i = i0 + e * 256 + tid;
-    const bool valid = i < n;
-    uint64_t key = 0, pay = 0;
-    if (valid) { key = keys[i]; pay = pays[i]; }
-    const uint32_t d = (uint32_t)(key >> shift) & 255u;
-    uint64_t peers = __ballot(valid);          // lanes of this wave with my digit
-#pragma unroll
-    for (int bit = 0; bit < 8; bit++) {
-      const bool one = (d >> bit) & 1u;
-      const uint64_t bm = __ballot(valid && one);
-      peers &= one ? bm : ~bm;
-    }
-    const uint32_t rank = (uint32_t)__popcll(peers & ((1ull << lane) - 1));
-    if (valid && rank == 0) wcnt[wave][d] = (uint32_t)__popcll(peers);
-    __syncthreads();
-    if (valid) {
-      uint32_t at = running[d] + rank;
-      for (uint32_t v = 0; v < wave; v++) at += wcnt[v][d];
-      keys_out[at] = key;
-      pays_out[at] = pay;
-    }
-    __syncthreads();
-    running[tid] += wcnt[0][tid] + wcnt[1][tid] + wcnt[2][tid] + wcnt[3][tid];
-#pragma unroll
-    for (int v = 0; v < 4; v++) wcnt[v][tid] = 0;
-    __syncthreads();
+    hash_out[at] = t.hj;
+    meta_out[at] = ((uint64_t)t.rid << 32) | ((uint64_t)(t.j + k - 1) << 1) | ss[t.j - t.lo];
   }
 }
 
@@ -351,41 +242,53 @@ __host__ __device__ inline uint32_t occ_final_cut(uint32_t q, uint32_t max_occ) 
   return cut < OVL_OCC_BINS - 2 ? cut : OVL_OCC_BINS - 2;
 }
 
-// hist[min(length, 65535)] += 1 for every hash run.  rstart[r]: first minimizer of run r (k_heads, the scan, k_gstart), rstart[*n_runs] = n:
-// a run's length is a difference, no thread walks a run.
+// The census's bins: a block counts the runs of fewer than OCC_LDS_BINS members in LDS (h) and adds them to the table (hist, u32 or 64-bit bins)
+// once, at its end; a longer run goes to the table itself.  256 threads.
+__device__ inline void occ_bins_clear(uint32_t* h) {
+  for (uint32_t b = threadIdx.x; b < OCC_LDS_BINS; b += 256) h[b] = 0;
+  __syncthreads();
+}
+template <class Bin>
+__device__ inline void occ_bins_add(uint32_t* h, Bin* __restrict__ hist, uint32_t c) {
+  if (c < OCC_LDS_BINS) atomicAdd(&h[c], 1u);
+  else atomicAdd(&hist[c], (Bin)1);
+}
+template <class Bin>
+__device__ inline void occ_bins_flush(const uint32_t* h, Bin* __restrict__ hist) {
+  __syncthreads();
+  for (uint32_t b = threadIdx.x; b < OCC_LDS_BINS; b += 256)
+    if (h[b]) atomicAdd(&hist[b], (Bin)h[b]);
+}
+
+// hist[min(length, 65535)] += 1 for every hash run.  rstart[r]: first minimizer of run r (run_starts), rstart[*n_runs] = n: a run's length is a
+// difference, no thread walks a run.
 __global__ __launch_bounds__(256) void k_occ_census(const uint32_t* __restrict__ rstart, const uint32_t* __restrict__ n_runs,
                                                     uint32_t* __restrict__ hist) {
   __shared__ uint32_t h[OCC_LDS_BINS];
-  for (uint32_t b = threadIdx.x; b < OCC_LDS_BINS; b += 256) h[b] = 0;
-  __syncthreads();
+  occ_bins_clear(h);
   const uint32_t nr = *n_runs;
-  for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < nr; r += (uint64_t)gridDim.x * 256) {
-    const uint32_t c = min(rstart[r + 1] - rstart[r], OVL_OCC_BINS - 1);
-    if (c < OCC_LDS_BINS) atomicAdd(&h[c], 1u);
-    else atomicAdd(&hist[c], 1u);
-  }
-  __syncthreads();
-  for (uint32_t b = threadIdx.x; b < OCC_LDS_BINS; b += 256)
-    if (h[b]) atomicAdd(&hist[b], h[b]);
+  for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < nr; r += (uint64_t)gridDim.x * 256)
+    occ_bins_add(h, hist, min(rstart[r + 1] - rstart[r], OVL_OCC_BINS - 1));
+  occ_bins_flush(h, hist);
 }
 
-// One workgroup.  Thread t owns the 256 bins from 256 (255 - t) on, so the exclusive scan over the threads is a suffix sum: above = the runs in
-// all higher bins.  q = the least v with no more than drop runs above it; occ = {cut, distinct, runs above the cut, minimizers in them}.
-__global__ __launch_bounds__(256) void k_occ_pick(const uint32_t* __restrict__ hist, uint32_t n, uint32_t ppm, uint32_t max_occ,
-                                                  uint64_t* __restrict__ occ) {
-  __shared__ uint32_t lds4[4];
-  __shared__ uint32_t s_q, s_runs;
-  __shared__ unsigned long long s_kept;
+// One workgroup.  Thread t owns the 256 bins from 256 (255 - t) on, so `above`, the sum over the threads in front, is the runs in all higher bins.
+// q = the least v with no more than drop runs above it; occ = {cut, distinct, runs above the cut, minimizers in them}; n: the store's minimizers.
+// Bin: uint32_t (k_occ_census) or 64 bits (k_occ16: the singletons of a large store exceed 2^32); the sums are 64-bit for both.
+template <class Bin>
+__global__ __launch_bounds__(256) void k_occ_pick(const Bin* __restrict__ hist, uint64_t n, uint32_t ppm, uint32_t max_occ, uint64_t* __restrict__ occ) {
+  __shared__ unsigned long long sums[256];
+  __shared__ uint32_t s_q;
+  __shared__ unsigned long long s_runs, s_kept;
   const uint32_t b0 = 256u * (255u - threadIdx.x);
   if (threadIdx.x == 0) { s_q = OVL_OCC_BINS - 1; s_runs = 0; s_kept = 0; }
-  uint32_t s = 0;
-  for (uint32_t b = 0; b < 256; b += 4) {
-    const uint4 v = *reinterpret_cast<const uint4*>(hist + b0 + b);
-    s += v.x + v.y + v.z + v.w;
-  }
-  uint32_t distinct;
-  uint32_t above = block_excl_scan(s, lds4, distinct);
-  const uint64_t drop = (uint64_t)distinct * ppm / 1000000u;
+  uint64_t s = 0;
+  for (uint32_t b = 0; b < 256; b++) s += hist[b0 + b];
+  sums[threadIdx.x] = s;
+  __syncthreads();
+  uint64_t above = 0, distinct = 0;             // above: the runs in all higher bins (the threads in front own them)
+  for (uint32_t t = 0; t < 256; t++) { const uint64_t v = sums[t]; if (t < threadIdx.x) above += v; distinct += v; }
+  const uint64_t drop = distinct * ppm / 1000000u;
   uint32_t q = OVL_OCC_BINS;
   for (uint32_t b = 256; b-- > 0 && above <= drop;) {
     q = b0 + b;
@@ -394,13 +297,13 @@ __global__ __launch_bounds__(256) void k_occ_pick(const uint32_t* __restrict__ h
   if (q < OVL_OCC_BINS) atomicMin(&s_q, q);
   __syncthreads();
   const uint32_t cut = occ_final_cut(s_q, max_occ);
-  uint32_t runs = 0;
-  uint64_t kept = 0;                             // minimizers in runs of at most cut (<= 65534: the bin is the length)
+  uint64_t runs = 0, kept = 0;                   // kept: minimizers in runs of at most cut (<= 65534: the bin is the length)
   for (uint32_t b = 0; b < 256; b++) {
-    const uint32_t v = b0 + b, c = hist[v];
+    const uint32_t v = b0 + b;
+    const uint64_t c = hist[v];
     if (v > cut) runs += c; else kept += (uint64_t)v * c;
   }
-  if (runs) atomicAdd(&s_runs, runs);
+  if (runs) atomicAdd(&s_runs, (unsigned long long)runs);
   if (kept) atomicAdd(&s_kept, (unsigned long long)kept);
   __syncthreads();
   if (threadIdx.x == 0) { occ[0] = cut; occ[1] = distinct; occ[2] = s_runs; occ[3] = n - s_kept; }
@@ -485,7 +388,7 @@ __device__ inline uint32_t lower_bound_u64(const uint64_t* __restrict__ a, uint3
 }
 
 // From hash order back to (rid, pos) order: meta ascends with (rid, pos) and is unique, so the place of sorted element i is its rank in the
-// unsorted copy meta_rp.  occ_rp[place] = the length of i's run (a difference of run starts: k_heads, the scan, k_gstart), perm[i] = place.
+// unsorted copy meta_rp.  occ_rp[place] = the length of i's run (a difference of run starts: run_starts), perm[i] = place.
 __global__ __launch_bounds__(256) void k_occ_place(const uint64_t* __restrict__ meta, const uint64_t* __restrict__ meta_rp,
                                                    const uint32_t* __restrict__ flag, const uint32_t* __restrict__ gidx,
                                                    const uint32_t* __restrict__ rstart, uint32_t n, uint32_t* __restrict__ occ_rp,
@@ -850,51 +753,6 @@ __global__ __launch_bounds__(256) void k_prim_write(const GroupOut* __restrict__
   out[soff[c]] = OvlRec{x.q, ql, x.qstart, x.qend, x.rel, x.t, tl, x.tstart, x.tend, x.score};
 }
 
-// row keys: primary p is the row (target t, query q), its mirror np + p the row (target q, query t)
-__global__ __launch_bounds__(256) void k_row_keys(const OvlRec* __restrict__ rec, uint32_t np, uint64_t* __restrict__ keys,
-                                                  uint64_t* __restrict__ pays) {
-  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= np) return;
-  const uint64_t t = rec[p].tid, q = rec[p].qid;
-  keys[p] = t << 32 | q;
-  pays[p] = p;
-  keys[np + p] = q << 32 | t;
-  pays[np + p] = np + p;
-}
-
-// ... with a core mask: the row (t, q) only if t is core, the row (q, t) only if q is — rows_of[p] rows, written densely from row_at[p] on
-__global__ __launch_bounds__(256) void k_row_count(const OvlRec* __restrict__ rec, uint32_t np, const uint8_t* __restrict__ core,
-                                                   uint32_t* __restrict__ rows_of) {
-  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p < np) rows_of[p] = (core[rec[p].tid] ? 1u : 0u) + (core[rec[p].qid] ? 1u : 0u);
-}
-
-__global__ __launch_bounds__(256) void k_row_keys_core(const OvlRec* __restrict__ rec, uint32_t np, const uint8_t* __restrict__ core,
-                                                       const uint32_t* __restrict__ row_at, uint64_t* __restrict__ keys,
-                                                       uint64_t* __restrict__ pays) {
-  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= np) return;
-  const uint64_t t = rec[p].tid, q = rec[p].qid;
-  uint32_t at = row_at[p];
-  if (core[t]) { keys[at] = t << 32 | q; pays[at] = p; at++; }
-  if (core[q]) { keys[at] = q << 32 | t; pays[at] = np + p; }
-}
-
-__global__ __launch_bounds__(256) void k_row_heads(const uint64_t* __restrict__ keys, uint32_t n, uint32_t* __restrict__ flag) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) flag[i] = (i == 0 || (keys[i] >> 32) != (keys[i - 1] >> 32)) ? 1u : 0u;
-}
-
-__global__ __launch_bounds__(256) void k_row_write(const uint64_t* __restrict__ keys, const uint64_t* __restrict__ pays,
-                                                   const uint32_t* __restrict__ flag, const uint32_t* __restrict__ tidx, uint32_t n,
-                                                   uint32_t* __restrict__ rids, uint64_t* __restrict__ aln_off, uint32_t* __restrict__ rec_of_row) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  rec_of_row[i] = (uint32_t)pays[i];
-  if (flag[i]) { rids[tidx[i]] = (uint32_t)(keys[i] >> 32); aln_off[tidx[i]] = i; }
-  if (i == 0) aln_off[tidx[n]] = n;
-}
-
 // ---- an index in parts (OvlParams.index_kmers != 0; DESIGN.md section 10, "An index in parts"; tests/index_parts_ref.py) ------------------------
 // Everything the finder takes from the whole store's index is occ(hash), the occurrences of a minimizer's hash in the store.  Pass A leaves
 // occ16[ordinal] = min(occ, 65535) for every minimizer, its ordinal being its place in the store's (rid, pos) order; pass B runs the finder per
@@ -929,46 +787,10 @@ __global__ __launch_bounds__(SK_T) void k_sketch_part(const SketchPart a) {
   __shared__ uint64_t wm[SK_H];
   __shared__ uint8_t ss[SK_H];
   __shared__ uint32_t wc[2][4];
-  const uint32_t lt = blockIdx.x, b = a.tile0 + lt, tid = threadIdx.x;
-  const uint32_t k = a.k, w = a.w;
-  uint32_t lo_r = a.r_lo, hi_r = a.r_hi;      // largest r of the block with tile_off[r] <= b
-  while (hi_r - lo_r > 1) {
-    const uint32_t mid = lo_r + ((hi_r - lo_r) >> 1);
-    if (a.tile_off[mid] <= b) lo_r = mid; else hi_r = mid;
-  }
-  const uint32_t rid = lo_r;
-  const uint32_t len = (uint32_t)(a.base_off[rid + 1] - a.base_off[rid]);
-  const uint32_t nk = len - k + 1;            // >= w (the read has tiles)
-  const uint32_t base = (b - a.tile_off[rid]) * SK_T;
-  const uint64_t w0 = a.word_off[rid];
-  const uint64_t mask = (1ull << (2 * k)) - 1;
-  const uint32_t lo = base >= w - 1 ? base - (w - 1) : 0u;
-  const uint32_t hi = min(nk, base + SK_T + (w - 1));
-  for (uint32_t i = lo + tid; i < hi; i += SK_T) {
-    uint32_t s;
-    sh[i - lo] = kmer_hash(a.words, w0, i, k, mask, s);
-    ss[i - lo] = (uint8_t)s;
-  }
-  __syncthreads();
-  const uint32_t s_hi = min(nk - w, base + SK_T - 1);
-  for (uint32_t s = lo + tid; s <= s_hi; s += SK_T) {
-    uint64_t m = INF64;
-    for (uint32_t o = 0; o < w; o++) { const uint64_t v = sh[s - lo + o]; m = v < m ? v : m; }
-    wm[s - lo] = m;
-  }
-  __syncthreads();
-  const uint32_t j = base + tid;
-  bool sel = false;
-  uint64_t hj = INF64;
-  if (j < nk) {
-    hj = sh[j - lo];
-    if (hj != INF64) {
-      const uint32_t s0 = j >= w - 1 ? j - (w - 1) : 0u, s1 = min(j, nk - w);
-      for (uint32_t s = s0; s <= s1; s++) sel |= wm[s - lo] == hj;
-    }
-  }
-  const bool in_range = sel && hj >= a.h_lo && hj <= a.h_hi;
-  const uint64_t bal = __ballot(sel), bal_r = __ballot(in_range);
+  const uint32_t lt = blockIdx.x, tid = threadIdx.x, k = a.k;
+  const SketchTile t = sketch_tile(a.words, a.word_off, a.base_off, a.tile_off, a.r_lo, a.r_hi, a.tile0 + lt, k, a.w, sh, wm, ss);
+  const bool in_range = t.sel && t.hj >= a.h_lo && t.hj <= a.h_hi;
+  const uint64_t bal = __ballot(t.sel), bal_r = __ballot(in_range);
   const uint32_t lane = tid & 63, wave = tid >> 6;
   if (lane == 0) { wc[0][wave] = (uint32_t)__popcll(bal); wc[1][wave] = (uint32_t)__popcll(bal_r); }
   __syncthreads();
@@ -987,80 +809,39 @@ __global__ __launch_bounds__(SK_T) void k_sketch_part(const SketchPart a) {
     if constexpr (MODE == SKP_WRITE_RANGE) {
       if (in_range) {
         const uint32_t at = a.out_base + a.f_at[lt] + before_r + (uint32_t)__popcll(bal_r & ((1ull << lane) - 1));
-        a.hash_out[at] = hj;
+        a.hash_out[at] = t.hj;
         a.ord_out[at] = a.ord_base + urank;
       }
-    } else if (sel) {
+    } else if (t.sel) {
       const uint32_t at = a.out_base + urank;
-      const uint64_t low = ((uint64_t)(j + k - 1) << 1) | ss[j - lo];
-      a.hash_out[at] = hj;
-      a.meta_out[at] = ((uint64_t)rid << 32) | low;
-      if (a.meta_loc) a.meta_loc[at] = ((uint64_t)(rid - a.r_lo) << 32) | low;
+      const uint64_t low = ((uint64_t)(t.j + k - 1) << 1) | ss[t.j - t.lo];
+      a.hash_out[at] = t.hj;
+      a.meta_out[at] = ((uint64_t)t.rid << 32) | low;
+      if (a.meta_loc) a.meta_loc[at] = ((uint64_t)(t.rid - a.r_lo) << 32) | low;
       a.occ_out[at] = a.occ16[a.ord_base + urank];
     }
   }
 }
 
-// Pass A, behind the sort of a hash range by hash (run starts: k_heads, the scan, k_gstart): every member's occ16 at its ordinal — a run lies in
-// one range, so its length is the store's occ — and the run in the census, hist[min(length, 65535)] += 1, in 64-bit bins.
+// Pass A, behind the sort of a hash range by hash (run_starts): every member's occ16 at its ordinal — a run lies in one range, so its length is the
+// store's occ — and the run in the census, hist[min(length, 65535)] += 1, in 64-bit bins.
 __global__ __launch_bounds__(256) void k_occ16(const uint64_t* __restrict__ ord, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ gidx,
                                                const uint32_t* __restrict__ rstart, uint32_t n, uint16_t* __restrict__ occ16,
                                                unsigned long long* __restrict__ hist) {
   __shared__ uint32_t h[OCC_LDS_BINS];
-  for (uint32_t b = threadIdx.x; b < OCC_LDS_BINS; b += 256) h[b] = 0;
-  __syncthreads();
+  occ_bins_clear(h);
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
     const uint32_t f = flag[i], r = gidx[i] + f - 1;
     const uint32_t c = min(rstart[r + 1] - rstart[r], OVL_OCC_BINS - 1);
     occ16[ord[i]] = (uint16_t)c;
-    if (f) {
-      if (c < OCC_LDS_BINS) atomicAdd(&h[c], 1u);
-      else atomicAdd(&hist[c], 1ull);
-    }
+    if (f) occ_bins_add(h, hist, c);
   }
-  __syncthreads();
-  for (uint32_t b = threadIdx.x; b < OCC_LDS_BINS; b += 256)
-    if (h[b]) atomicAdd(&hist[b], (unsigned long long)h[b]);
-}
-
-// k_occ_pick over 64-bit bins (the singletons of a large store exceed 2^32): the same rule and occ_final_cut; n: the store's minimizers.
-__global__ __launch_bounds__(256) void k_occ_pick64(const unsigned long long* __restrict__ hist, uint64_t n, uint32_t ppm, uint32_t max_occ,
-                                                    uint64_t* __restrict__ occ) {
-  __shared__ unsigned long long sums[256];
-  __shared__ uint32_t s_q;
-  __shared__ unsigned long long s_runs, s_kept;
-  const uint32_t b0 = 256u * (255u - threadIdx.x);
-  if (threadIdx.x == 0) { s_q = OVL_OCC_BINS - 1; s_runs = 0; s_kept = 0; }
-  uint64_t s = 0;
-  for (uint32_t b = 0; b < 256; b++) s += hist[b0 + b];
-  sums[threadIdx.x] = s;
-  __syncthreads();
-  uint64_t above = 0, distinct = 0;             // above: the runs in all higher bins (the threads in front own them)
-  for (uint32_t t = 0; t < 256; t++) { const uint64_t v = sums[t]; if (t < threadIdx.x) above += v; distinct += v; }
-  const uint64_t drop = distinct * ppm / 1000000u;
-  uint32_t q = OVL_OCC_BINS;
-  for (uint32_t b = 256; b-- > 0 && above <= drop;) {
-    q = b0 + b;
-    above += hist[b0 + b];
-  }
-  if (q < OVL_OCC_BINS) atomicMin(&s_q, q);
-  __syncthreads();
-  const uint32_t cut = occ_final_cut(s_q, max_occ);
-  uint64_t runs = 0, kept = 0;
-  for (uint32_t b = 0; b < 256; b++) {
-    const uint32_t v = b0 + b;
-    const uint64_t c = hist[v];
-    if (v > cut) runs += c; else kept += (uint64_t)v * c;
-  }
-  if (runs) atomicAdd(&s_runs, (unsigned long long)runs);
-  if (kept) atomicAdd(&s_kept, (unsigned long long)kept);
-  __syncthreads();
-  if (threadIdx.x == 0) { occ[0] = cut; occ[1] = distinct; occ[2] = s_runs; occ[3] = n - s_kept; }
+  occ_bins_flush(h, hist);
 }
 
 // Pass B.  The class of a minimizer of a block pair from its occ alone, in (rid, pos) order: 0 — its hash is not used (a singleton, above the cut
 // and not rescuable), 1 — used (2 <= occ <= cut), 2 — cut < occ <= rmax and not rescued, 3 — rescued.  resc NULL / rmax 0: no rescue.  idx[p] = p,
-// the payload of the sort by hash.  occ: where k_occ_pick64 left the cut, or NULL — the cut is max_occ.
+// the payload of the sort by hash.  occ: where k_occ_pick left the cut, or NULL — the cut is max_occ.
 __global__ __launch_bounds__(256) void k_part_cls(const uint32_t* __restrict__ occ_rp, const uint8_t* __restrict__ resc_rp, uint32_t n, uint32_t max_occ,
                                                   const uint64_t* __restrict__ occ, uint32_t rmax, uint8_t* __restrict__ cls, uint64_t* __restrict__ idx) {
   const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1154,75 +935,46 @@ __global__ __launch_bounds__(256) void k_part_expand(const uint64_t* __restrict_
   }
 }
 
-// the records of all block pairs into target order: the key of the stable sort, and the gather behind it
-__global__ __launch_bounds__(256) void k_rec_keys(const OvlRec* __restrict__ rec, uint32_t n, uint64_t* __restrict__ keys, uint64_t* __restrict__ pays) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  keys[i] = rec[i].tid;
-  pays[i] = i;
-}
-
-__global__ __launch_bounds__(256) void k_rec_gather(const OvlRec* __restrict__ rec, const uint64_t* __restrict__ pays, uint32_t n, OvlRec* __restrict__ out) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) out[i] = rec[pays[i]];
-}
-
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-#define OVL_TRY(expr)                                                                  \
-  do {                                                                                 \
-    const hipError_t _e = (expr);                                                      \
-    if (_e != hipSuccess) {                                                            \
-      err = std::string("overlap finder: " #expr ": ") + hipGetErrorString(_e);        \
-      return OVL_HIP;                                                                  \
-    }                                                                                  \
-  } while (0)
-
-inline uint32_t nblk(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
-inline uint32_t bits_of(uint64_t v) { uint32_t b = 0; while (v) { b++; v >>= 1; } return b; }   // bits to hold 0 .. v
-
-// exclusive scan of in[0 .. n) into out[0 .. n], out[n] = total; partial: nblk(n, SC_TILE) + 1 entries
-int scan_u32(const uint32_t* in, uint32_t n, uint32_t* out, uint32_t* partial, hipStream_t st, std::string& err) {
-  if (n == 0) { OVL_TRY(hipMemsetAsync(out, 0, 4, st)); return OVL_OK; }
-  const uint32_t nb = nblk(n, SC_TILE);
-  k_scan_partial<<<nb, 256, 0, st>>>(in, n, partial);
-  k_scan_top<<<1, 256, 0, st>>>(partial, nb);
-  k_scan_final<<<nb, 256, 0, st>>>(in, n, partial, nb, out);
+// Run starts of the sorted keys[0 .. n), n >= 1, queued on st: flag[i] = 1 where a run begins; gidx [n + 1] its exclusive scan — element i lies in
+// run gidx[i] + flag[i] - 1, gidx[n] is the number of runs —; rstart[r] the first element of run r, rstart[gidx[n]] = n.  partial: the scan's scratch.
+int run_starts(const uint64_t* keys, uint32_t n, uint32_t* flag, uint32_t* gidx, uint32_t* rstart, uint32_t* partial, hipStream_t st, std::string& err) {
+  k_heads<<<nblk(n), 256, 0, st>>>(keys, n, flag);
+  if (int rc = dev_scan_u32(flag, n, gidx, partial, st, err)) return rc;
+  k_gstart<<<nblk(n), 256, 0, st>>>(flag, gidx, n, rstart);
   OVL_TRY(hipGetLastError());
   return OVL_OK;
 }
 
-struct SortScratch {       // for up to `cap` elements
-  uint32_t* hist = nullptr;     // 256 x blocks
-  uint32_t* offs = nullptr;     // + 1
-  uint32_t* partial = nullptr;
-  hipError_t alloc(Bufs& B, uint64_t cap) {
-    const uint64_t nb = nblk(cap, SC_TILE) + 1;
-    hipError_t e;
-    if ((e = B.get(&hist, 256 * nb)) != hipSuccess) return e;
-    if ((e = B.get(&offs, 256 * nb + 1)) != hipSuccess) return e;
-    return B.get(&partial, std::max<uint64_t>(nblk(256 * nb, SC_TILE), nb) + 2);   // scans of the histogram and of per-element arrays
-  }
-};
+// f(std::true_type) with a core mask, f(std::false_type) without one: the launch of a kernel with a CORE variant is written once, in a generic
+// lambda, as K<decltype(core)::value><<<...>>>(..., d_core) — d_core is NULL exactly where CORE is false.
+template <class F>
+void with_core(const uint8_t* d_core, F f) { d_core ? f(std::true_type{}) : f(std::false_type{}); }
 
-// stable LSD sort by the digits at `shifts` (ascending significance).  The sorted arrays end up in (*k0, *p0): the pointers
-// are swapped after every pass.
-int radix_sort(uint64_t** k0, uint64_t** p0, uint64_t** k1, uint64_t** p1, uint32_t n, const std::vector<uint32_t>& shifts,
-               const SortScratch& S, hipStream_t st, std::string& err) {
-  if (n < 2) return OVL_OK;
-  const uint32_t nb = nblk(n, SC_TILE);
-  for (uint32_t sh : shifts) {
-    k_rs_hist<<<nb, 256, 0, st>>>(*k0, n, sh, nb, S.hist);
-    if (int rc = scan_u32(S.hist, 256 * nb, S.offs, S.partial, st, err)) return rc;
-    k_rs_scatter<<<nb, 256, 0, st>>>(*k0, *p0, n, sh, nb, S.offs, *k1, *p1);
-    OVL_TRY(hipGetLastError());
-    std::swap(*k0, *k1);
-    std::swap(*p0, *p1);
-  }
-  return OVL_OK;
+// body(), and where it fails the stream is waited for before the scratch the body queued work on goes away
+template <class F>
+int synced_on_failure(hipStream_t st, F body) {
+  const int rc = body();
+  if (rc != OVL_OK) (void)hipStreamSynchronize(st);
+  return rc;
 }
 
-void field_shifts(std::vector<uint32_t>& v, uint32_t lo, uint32_t nbits) {
-  for (uint32_t s = lo; s < lo + nbits; s += 8) v.push_back(s);
+// the digits of a hash: 2 k bits
+std::vector<uint32_t> hash_shifts(uint32_t k) {
+  std::vector<uint32_t> shifts;
+  field_shifts(shifts, 0, 2 * k);
+  return shifts;
+}
+
+uint32_t max_read_len(const OvlStore& S) { return S.n_reads ? *std::max_element(S.h_len, S.h_len + S.n_reads) : 0u; }
+
+// The figures of a call without a census of its own: the cut is max_occ, or — occ_frac_ppm != 0, which then means fewer than two minimizers — the
+// pick's over as many runs of one.
+void stats_without_census(OvlStats& stats, uint64_t minimizers, const OvlParams& P) {
+  const bool frac = P.occ_frac_ppm != 0;
+  stats.occ_cut = frac ? occ_final_cut((uint32_t)minimizers, P.max_occ) : P.max_occ;
+  stats.distinct = frac ? minimizers : 0;
+  stats.cut_runs = stats.cut_minimizers = 0;
 }
 
 struct Sketch {            // device: minimizers in (rid, pos) order
@@ -1239,21 +991,29 @@ int check_store(const OvlStore& S, std::string& err) {
   return OVL_OK;
 }
 
-// extra: elements the two arrays are allocated for beyond the minimizers (they double as a sort buffer)
-int sketch_dev(const OvlStore& S, const OvlParams& P, hipStream_t st, Bufs& B, Sketch& out, std::string& err) {
-  if (int rc = check_store(S, err)) return rc;
-  std::vector<uint32_t> tile_off(S.n_reads + 1, 0);
-  uint64_t tiles = 0, kmers = 0;
+// tile_off [n_reads + 1]: the first sketch tile of every read, tile_off[n_reads] = the tiles of the store; a read has the k-mers index_read_kmers
+// gives it (none if it is shorter than k + w - 1) in tiles of SK_T.  Returns the tiles in 64 bits and leaves the k-mers in `kmers`: the 32-bit
+// entries hold only once the caller has found the totals within its limit.
+uint64_t tile_table(const OvlStore& S, const OvlParams& P, std::vector<uint32_t>& tile_off, uint64_t& kmers) {
+  tile_off.assign((size_t)S.n_reads + 1, 0);
+  uint64_t tiles = 0;
+  kmers = 0;
   for (uint32_t r = 0; r < S.n_reads; r++) {
     tile_off[r] = (uint32_t)tiles;
-    if ((uint64_t)S.h_len[r] >= (uint64_t)P.k + P.w - 1) {
-      const uint64_t nk = (uint64_t)S.h_len[r] - P.k + 1;
-      kmers += nk;
-      tiles += (nk + SK_T - 1) / SK_T;
-    }
-    if (kmers > OVL_MAX_KMERS) { err = "overlap finder: more than 2^32 k-mers in the read store"; return OVL_UNSUPPORTED; }
+    const uint64_t nk = index_read_kmers(S.h_len[r], P.k, P.w);
+    kmers += nk;
+    tiles += (nk + SK_T - 1) / SK_T;
   }
   tile_off[S.n_reads] = (uint32_t)tiles;
+  return tiles;
+}
+
+int sketch_dev(const OvlStore& S, const OvlParams& P, hipStream_t st, Bufs& B, Sketch& out, std::string& err) {
+  if (int rc = check_store(S, err)) return rc;
+  std::vector<uint32_t> tile_off;
+  uint64_t kmers;
+  const uint64_t tiles = tile_table(S, P, tile_off, kmers);
+  if (kmers > OVL_MAX_KMERS) { err = "overlap finder: more than 2^32 k-mers in the read store"; return OVL_UNSUPPORTED; }
   out.kmers = kmers;
   out.n = 0;
   if (!tiles) return OVL_OK;
@@ -1266,7 +1026,7 @@ int sketch_dev(const OvlStore& S, const OvlParams& P, hipStream_t st, Bufs& B, S
   OVL_TRY(hipMemcpyAsync(d_tile_off, tile_off.data(), 4ull * (S.n_reads + 1), hipMemcpyHostToDevice, st));
   k_sketch<<<nt, SK_T, 0, st>>>(S.d_words, S.d_word_off, S.d_base_off, d_tile_off, S.n_reads, P.k, P.w, d_cnt, nullptr, nullptr, nullptr, 0);
   OVL_TRY(hipGetLastError());
-  if (int rc = scan_u32(d_cnt, nt, d_at, d_partial, st, err)) return rc;
+  if (int rc = dev_scan_u32(d_cnt, nt, d_at, d_partial, st, err)) return rc;
   uint32_t total = 0;
   OVL_TRY(hipMemcpyAsync(&total, d_at + nt, 4, hipMemcpyDeviceToHost, st));
   OVL_TRY(hipStreamSynchronize(st));           // (also keeps tile_off alive until its copy is done)
@@ -1281,27 +1041,6 @@ int sketch_dev(const OvlStore& S, const OvlParams& P, hipStream_t st, Bufs& B, S
 }
 
 }  // namespace
-
-uint32_t ovl_scan_partials(uint32_t n) { return nblk(n, SC_TILE) + 1; }
-int ovl_scan_u32(const uint32_t* in, uint32_t n, uint32_t* out, uint32_t* partial, hipStream_t st, std::string& err) { return scan_u32(in, n, out, partial, st, err); }
-
-// SortScratch's three arrays (SortScratch::alloc's sizes) laid out in one block
-namespace {
-inline uint64_t sort_hist_entries(uint64_t n) { return 256 * (uint64_t)(nblk(n, SC_TILE) + 1); }
-}
-uint64_t ovl_sort_scratch(uint64_t n) {
-  const uint64_t h = sort_hist_entries(n), nb = nblk(n, SC_TILE) + 1;
-  return h + (h + 1) + std::max<uint64_t>(nblk(h, SC_TILE), nb) + 2;
-}
-int ovl_radix_sort(uint64_t** k0, uint64_t** p0, uint64_t** k1, uint64_t** p1, uint32_t n, const std::vector<uint32_t>& shifts, uint32_t* scratch,
-                   hipStream_t st, std::string& err) {
-  const uint64_t h = sort_hist_entries(n);
-  SortScratch S;
-  S.hist = scratch;
-  S.offs = scratch + h;
-  S.partial = scratch + h + (h + 1);
-  return radix_sort(k0, p0, k1, p1, n, shifts, S, st, err);
-}
 
 int ovl_sketch(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vector<uint64_t>& hash, std::vector<uint64_t>& meta,
                std::string& err) {
@@ -1319,76 +1058,70 @@ int ovl_sketch(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vecto
 }
 
 namespace {
-// the minimizers by hash (stable: (rid, pos) order inside a hash); ms: the sort's scratch, for sk.n elements, which the callers go on using
-int sort_by_hash(Sketch& sk, uint32_t k, hipStream_t st, Bufs& B, SortScratch& ms, std::string& err) {
-  uint64_t *mk1, *mp1;
-  OVL_TRY(B.get(&mk1, sk.n));
-  OVL_TRY(B.get(&mp1, sk.n));
-  OVL_TRY(ms.alloc(B, sk.n));
-  std::vector<uint32_t> shifts;
-  field_shifts(shifts, 0, 2 * k);
-  return radix_sort(&sk.hash, &sk.meta, &mk1, &mp1, sk.n, shifts, ms, st, err);
-}
-
-// The census of the run lengths of hash[0 .. n) (sorted, n >= 1) and the pick, queued on st: *d_occ = {cut, distinct, runs above the cut, minimizers
-// in them} and *d_hist, on the device.  flag [n] and gidx [n + 1] are the caller's, free to use again once this is queued in front of their next writer.
-// *rstart (when asked for): the run starts the census took, for the rescue, which needs the same flag and gidx.
-int occ_census_dev(const uint64_t* hash, uint32_t n, const OvlParams& P, hipStream_t st, Bufs& B, const SortScratch& ms, uint32_t* flag, uint32_t* gidx,
-                   uint64_t** d_occ, uint32_t** d_hist, std::string& err, uint32_t** rstart_out = nullptr) {
-  uint32_t* rstart;
-  OVL_TRY(B.get(&rstart, (uint64_t)n + 1));
-  OVL_TRY(B.get(d_hist, OVL_OCC_BINS));
-  OVL_TRY(B.get(d_occ, 4));
-  OVL_TRY(hipMemsetAsync(*d_hist, 0, 4ull * OVL_OCC_BINS, st));
-  k_heads<<<nblk(n, 256), 256, 0, st>>>(hash, n, flag);
-  if (int rc = scan_u32(flag, n, gidx, ms.partial, st, err)) return rc;
-  k_gstart<<<nblk(n, 256), 256, 0, st>>>(flag, gidx, n, rstart);
-  k_occ_census<<<std::min(nblk(n, 256), OCC_GRID), 256, 0, st>>>(rstart, gidx + n, *d_hist);
-  k_occ_pick<<<1, 256, 0, st>>>(*d_hist, n, P.occ_frac_ppm, P.max_occ, *d_occ);
-  OVL_TRY(hipGetLastError());
-  if (rstart_out) *rstart_out = rstart;
-  return OVL_OK;
-}
-
-// The rescue (P.occ_dist != 0), queued on st behind the sort and, with occ_frac_ppm, the census.  meta_rp: the copy of the minimizers' meta taken
-// before the sort; flag / gidx / rstart: the run starts of the sorted hashes, or rstart NULL — they are taken here into the caller's flag [n] and
-// gidx [n + 1]; d_occ: where k_occ_pick left the cut, NULL with a fixed cut.  Leaves occ_rp and resc_rp in (rid, pos) order, kind in hash order
-// and stat = {H minimizers, rescued, 0}.  The selection sees neither the core mask nor the scratch budget.
-struct Rescue {
-  uint64_t* meta_rp = nullptr;
+// The index of the whole store, queued on st — what ovl_find / ovl_find_pairs without index_kmers, ovl_occ_census and ovl_seed_rescue start from:
+//   the sketch; with fewer than `least` minimizers that is all (built stays false: the caller's early return);
+//   rescue: the copy of meta the rescue searches, taken while it is still in (rid, pos) order;
+//   the sort by hash (stable: (rid, pos) order inside a hash); ms, the sort's scratch for sk.n elements, is the caller's to go on using;
+//   census or rescue: the run starts of the sorted hashes, which serve both;
+//   census: the histogram of the run lengths and the pick — d_occ = {cut, distinct, runs above the cut, minimizers in them}, d_hist;
+//   rescue ("Rescue of high-frequency minimizers"): occ_rp and resc_rp in (rid, pos) order, kind in hash order and stat =
+//   {H minimizers, rescued, 0}; k_rescue itself only with P.occ_dist != 0 (0 is the test hook with the setting off — the occurrences alone); the cut is
+//   d_occ's, or, without a census, max_occ.  The selection is done before any chunk is cut and sees neither the core mask nor the scratch budget.
+// flag [n] and gidx [n + 1] are allocated in every case: behind what is queued here they are free, and find_chunks' cntm and aoff.
+struct StoreIndex {
+  Sketch sk;
+  bool built = false;
+  SortScratch ms;
+  uint32_t *flag = nullptr, *gidx = nullptr, *rstart = nullptr;
+  uint32_t* d_hist = nullptr;
+  uint64_t *d_occ = nullptr, *meta_rp = nullptr;
   uint32_t *occ_rp = nullptr, *perm = nullptr;
   uint8_t *resc_rp = nullptr, *kind = nullptr;
   unsigned long long* stat = nullptr;
 };
 
-int rescue_dev(const Sketch& sk, const OvlStore& S, const OvlParams& P, hipStream_t st, Bufs& B, const SortScratch& ms, uint32_t* flag, uint32_t* gidx,
-               uint32_t* rstart, const uint64_t* d_occ, Rescue& R, std::string& err) {
+int store_index(const OvlStore& S, const OvlParams& P, bool census, bool rescue, uint32_t least, hipStream_t st, Bufs& B, StoreIndex& X,
+                std::string& err) {
+  Sketch& sk = X.sk;
+  if (int rc = sketch_dev(S, P, st, B, sk, err)) return rc;
   const uint32_t n = sk.n;
-  if (!rstart) {
-    OVL_TRY(B.get(&rstart, (uint64_t)n + 1));
-    k_heads<<<nblk(n, 256), 256, 0, st>>>(sk.hash, n, flag);
-    if (int rc = scan_u32(flag, n, gidx, ms.partial, st, err)) return rc;
-    k_gstart<<<nblk(n, 256), 256, 0, st>>>(flag, gidx, n, rstart);
+  if (n < least) return OVL_OK;
+  X.built = true;
+  if (rescue) {
+    OVL_TRY(B.get(&X.meta_rp, n));
+    OVL_TRY(hipMemcpyAsync(X.meta_rp, sk.meta, 8ull * n, hipMemcpyDeviceToDevice, st));
   }
-  OVL_TRY(B.get(&R.occ_rp, n));
-  OVL_TRY(B.get(&R.perm, n));
-  OVL_TRY(B.get(&R.resc_rp, n));
-  OVL_TRY(B.get(&R.kind, n));
-  OVL_TRY(B.get(&R.stat, 3));
-  OVL_TRY(hipMemsetAsync(R.resc_rp, 0, n, st));
-  OVL_TRY(hipMemsetAsync(R.stat, 0, 24, st));
-  k_occ_place<<<nblk(n, 256), 256, 0, st>>>(sk.meta, R.meta_rp, flag, gidx, rstart, n, R.occ_rp, R.perm);
-  if (P.occ_dist)                              // (0: the test hook with the setting off — the occurrences alone)
-    k_rescue<<<S.n_reads, 64, 0, st>>>(R.meta_rp, R.occ_rp, n, S.d_base_off, P.max_occ, d_occ, P.rescue_max_occ, P.occ_dist, R.resc_rp, R.stat);
-  k_resc_kind<<<nblk(n, 256), 256, 0, st>>>(R.perm, R.occ_rp, R.resc_rp, n, P.max_occ, d_occ, P.rescue_max_occ, R.kind);
+  uint64_t *mk1, *mp1;
+  OVL_TRY(B.get(&mk1, n));
+  OVL_TRY(B.get(&mp1, n));
+  OVL_TRY(X.ms.alloc(B, n));
+  if (int rc = dev_radix_sort(&sk.hash, &sk.meta, &mk1, &mp1, n, hash_shifts(P.k), X.ms, st, err)) return rc;
+  OVL_TRY(B.get(&X.flag, n));
+  OVL_TRY(B.get(&X.gidx, (uint64_t)n + 1));
+  if (!census && !rescue) return OVL_OK;
+  OVL_TRY(B.get(&X.rstart, (uint64_t)n + 1));
+  if (int rc = run_starts(sk.hash, n, X.flag, X.gidx, X.rstart, X.ms.partial, st, err)) return rc;
+  if (census) {
+    OVL_TRY(B.get(&X.d_hist, OVL_OCC_BINS));
+    OVL_TRY(B.get(&X.d_occ, 4));
+    OVL_TRY(hipMemsetAsync(X.d_hist, 0, 4ull * OVL_OCC_BINS, st));
+    k_occ_census<<<std::min(nblk(n), OCC_GRID), 256, 0, st>>>(X.rstart, X.gidx + n, X.d_hist);
+    k_occ_pick<<<1, 256, 0, st>>>(X.d_hist, n, P.occ_frac_ppm, P.max_occ, X.d_occ);
+  }
+  if (rescue) {
+    OVL_TRY(B.get(&X.occ_rp, n));
+    OVL_TRY(B.get(&X.perm, n));
+    OVL_TRY(B.get(&X.resc_rp, n));
+    OVL_TRY(B.get(&X.kind, n));
+    OVL_TRY(B.get(&X.stat, 3));
+    OVL_TRY(hipMemsetAsync(X.resc_rp, 0, n, st));
+    OVL_TRY(hipMemsetAsync(X.stat, 0, 24, st));
+    k_occ_place<<<nblk(n), 256, 0, st>>>(sk.meta, X.meta_rp, X.flag, X.gidx, X.rstart, n, X.occ_rp, X.perm);
+    if (P.occ_dist)
+      k_rescue<<<S.n_reads, 64, 0, st>>>(X.meta_rp, X.occ_rp, n, S.d_base_off, P.max_occ, X.d_occ, P.rescue_max_occ, P.occ_dist, X.resc_rp, X.stat);
+    k_resc_kind<<<nblk(n), 256, 0, st>>>(X.perm, X.occ_rp, X.resc_rp, n, P.max_occ, X.d_occ, P.rescue_max_occ, X.kind);
+  }
   OVL_TRY(hipGetLastError());
-  return OVL_OK;
-}
-
-// the copy of meta the rescue searches, taken while it is still in (rid, pos) order
-int rescue_keep_meta(const Sketch& sk, hipStream_t st, Bufs& B, Rescue& R, std::string& err) {
-  OVL_TRY(B.get(&R.meta_rp, sk.n));
-  OVL_TRY(hipMemcpyAsync(R.meta_rp, sk.meta, 8ull * sk.n, hipMemcpyDeviceToDevice, st));
   return OVL_OK;
 }
 
@@ -1404,20 +1137,24 @@ struct ChainBufs {
 };
 int chain_and_walk(const uint64_t* A0, const uint64_t* B0, ChainBufs& C, uint32_t nc, const OvlParams& P, const uint64_t* d_base_off, uint32_t t_lo,
                    const SortScratch& as, hipStream_t st, std::string& err) {
-  if (int rc = radix_sort(&C.ck0, &C.cp0, &C.ck1, &C.cp1, nc, {0, 8, 16, 24}, as, st, err)) return rc;
+  if (int rc = dev_radix_sort(&C.ck0, &C.cp0, &C.ck1, &C.cp1, nc, {0, 8, 16, 24}, as, st, err)) return rc;
   const int32_t bandwidth = (int32_t)std::min<uint32_t>(P.bandwidth, 0x3fffffffu), max_gap = (int32_t)std::min<uint32_t>(P.max_gap, 0x7fffffffu);
   if (P.lookback == OVL_LOOKBACK) {
     k_chain<<<nc, 64, 0, st>>>(A0, C.cp0, C.cstart, C.csize, C.pred8, C.ends, (int32_t)P.k, bandwidth, max_gap);
-    k_walk<uint8_t><<<nblk(nc, 256), 256, 0, st>>>(A0, B0, C.cstart, C.pred8, C.ends, nc, d_base_off, P.k, t_lo, P.min_score, P.min_anchors, C.gout);
+    k_walk<uint8_t><<<nblk(nc), 256, 0, st>>>(A0, B0, C.cstart, C.pred8, C.ends, nc, d_base_off, P.k, t_lo, P.min_score, P.min_anchors, C.gout);
   } else {
     k_chain_far<<<nc, 64, 12 * P.lookback, st>>>(A0, C.cp0, C.cstart, C.csize, C.pred16, C.ends, (int32_t)P.k, bandwidth, max_gap,
                                                  (int32_t)(P.lookback / 64));
-    k_walk<uint16_t><<<nblk(nc, 256), 256, 0, st>>>(A0, B0, C.cstart, C.pred16, C.ends, nc, d_base_off, P.k, t_lo, P.min_score, P.min_anchors, C.gout);
+    k_walk<uint16_t><<<nblk(nc), 256, 0, st>>>(A0, B0, C.cstart, C.pred16, C.ends, nc, d_base_off, P.k, t_lo, P.min_score, P.min_anchors, C.gout);
   }
   OVL_TRY(hipGetLastError());
   return OVL_OK;
 }
-inline bool lookback_ok(uint32_t h) { return h >= OVL_LOOKBACK && h <= OVL_MAX_LOOKBACK && h % 64 == 0; }
+bool lookback_ok(uint32_t h, std::string& err) {
+  if (h >= OVL_LOOKBACK && h <= OVL_MAX_LOOKBACK && h % 64 == 0) return true;
+  err = "overlap finder: the look-back is a multiple of 64 in 64 .. 1024";
+  return false;
+}
 
 // What a run stage leaves for the chunk loop (chain_chunks, below): per occurrence in hash order its meta, the anchors it has as the target side
 // (cnt) and the end of its run; cntm [nm], aoff [nm + 1] and scan_partial are scratch of the loop.  per_read (host): the anchors of the targets
@@ -1434,75 +1171,59 @@ template <class Expand, class Take>
 int chain_chunks(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, hipStream_t st, Bufs& B, const RunsOut& RO, OvlStats& stats, std::string& err,
                  Expand expand, Take take);
 
-// Sketch, sort, frequency cut and the chunk loop of ovl_find and ovl_find_pairs.  Behind every chunk's k_walk, take(nc, gout, ccap, t_hi, B) gets the
-// chunk's nc GroupOut records, still on the device, in ascending (t, q, rel): it takes what it wants before it returns or queues its kernels on st,
-// in front of the next chunk's k_walk, which overwrites gout.  ccap: the most records any chunk has; t_hi: the targets done so far, this chunk's
-// included; B: the call's scratch.  d_core: the core mask on the device (n_reads bytes) or NULL — every read is core.
+// The whole store's index, the run stage and the chunk loop of ovl_find and ovl_find_pairs.  Behind every chunk's k_walk, take(nc, gout, ccap, t_hi, B)
+// gets the chunk's nc GroupOut records, still on the device, in ascending (t, q, rel): it takes what it wants before it returns or queues its kernels
+// on st, in front of the next chunk's k_walk, which overwrites gout.  ccap: the most records any chunk has; t_hi: the targets done so far, this
+// chunk's included; B: the call's scratch.  d_core: the core mask on the device (n_reads bytes) or NULL — every read is core.
 template <class Take>
 int find_chunks(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uint64_t budget_bytes, hipStream_t st, OvlStats& stats, std::string& err,
                 Take take) {
-  stats = OvlStats{};
-  if (!lookback_ok(P.lookback)) { err = "overlap finder: the look-back is a multiple of 64 in 64 .. 1024"; return OVL_UNSUPPORTED; }
+  const bool frac = P.occ_frac_ppm != 0, rescue = P.occ_dist != 0;
   Bufs B;
-  Sketch sk;
-  if (int rc = sketch_dev(S, P, st, B, sk, err)) return rc;
-  stats.kmers = sk.kmers;
-  stats.minimizers = sk.n;
+  StoreIndex X;
+  if (int rc = store_index(S, P, frac, rescue, 2, st, B, X, err)) return rc;
+  const Sketch& sk = X.sk;
   const uint32_t nm = sk.n;
-  const bool frac = P.occ_frac_ppm != 0;
-  stats.occ_cut = frac ? occ_final_cut(nm, P.max_occ) : P.max_occ;     // (fewer than two minimizers: as many runs of one)
-  stats.distinct = frac ? nm : 0;
-  if (nm < 2) { OVL_TRY(hipStreamSynchronize(st)); return OVL_OK; }
+  stats.kmers = sk.kmers;
+  stats.minimizers = nm;
+  stats_without_census(stats, nm, P);
+  if (!X.built) { OVL_TRY(hipStreamSynchronize(st)); return OVL_OK; }
 
-  const bool rescue = P.occ_dist != 0;
-  Rescue R;
-  if (rescue) if (int rc = rescue_keep_meta(sk, st, B, R, err)) return rc;
-  SortScratch ms;
-  if (int rc = sort_by_hash(sk, P.k, st, B, ms, err)) return rc;
-  uint32_t *d_cnt, *d_run_end, *d_cntm, *d_aoff;
+  uint32_t *d_cnt, *d_run_end, *const d_cntm = X.flag, *const d_aoff = X.gidx;
   unsigned long long* d_per_read;
   OVL_TRY(B.get(&d_cnt, nm));
   OVL_TRY(B.get(&d_run_end, nm));
-  OVL_TRY(B.get(&d_cntm, nm));
-  OVL_TRY(B.get(&d_aoff, (uint64_t)nm + 1));
   OVL_TRY(B.get(&d_per_read, S.n_reads));
   OVL_TRY(hipMemsetAsync(d_cnt, 0, 4ull * nm, st));
   OVL_TRY(hipMemsetAsync(d_per_read, 0, 8ull * S.n_reads, st));
-  uint64_t* d_occ = nullptr;
+  // the census, the pick and the run kernel queue one behind the other: the cut stays on the device and comes back with per_read
+  with_core(d_core, [&](auto core) {
+    constexpr bool CORE = decltype(core)::value;
+    if (rescue)
+      k_runs_resc<CORE><<<nblk(nm), 256, 0, st>>>(sk.hash, sk.meta, nm, P.max_occ, X.d_occ, d_cnt, d_run_end, d_per_read, d_core, P.rescue_max_occ,
+                                                  X.kind, X.stat);
+    else if (frac) k_runs_occ<CORE><<<nblk(nm), 256, 0, st>>>(sk.hash, sk.meta, nm, X.d_occ, d_cnt, d_run_end, d_per_read, d_core);
+    else k_runs<CORE><<<nblk(nm), 256, 0, st>>>(sk.hash, sk.meta, nm, P.max_occ, d_cnt, d_run_end, d_per_read, d_core);
+  });
+  OVL_TRY(hipGetLastError());
   uint64_t occ[4] = {0, 0, 0, 0};
   unsigned long long resc_stat[3] = {0, 0, 0};
-  if (rescue) {
-    // the run starts serve the census and the rescue; the selection is done before any chunk is cut and without the mask
-    uint32_t *d_hist, *rstart = nullptr;
-    if (frac) if (int rc = occ_census_dev(sk.hash, nm, P, st, B, ms, d_cntm, d_aoff, &d_occ, &d_hist, err, &rstart)) return rc;
-    if (int rc = rescue_dev(sk, S, P, st, B, ms, d_cntm, d_aoff, rstart, d_occ, R, err)) return rc;
-    if (d_core) k_runs_resc<true><<<nblk(nm, 256), 256, 0, st>>>(sk.hash, sk.meta, nm, P.max_occ, d_occ, d_cnt, d_run_end, d_per_read, d_core, P.rescue_max_occ, R.kind, R.stat);
-    else k_runs_resc<false><<<nblk(nm, 256), 256, 0, st>>>(sk.hash, sk.meta, nm, P.max_occ, d_occ, d_cnt, d_run_end, d_per_read, nullptr, P.rescue_max_occ, R.kind, R.stat);
-    OVL_TRY(hipMemcpyAsync(resc_stat, R.stat, sizeof(resc_stat), hipMemcpyDeviceToHost, st));
-  } else if (frac) {
-    // census, pick and k_runs_occ queue one behind the other: the cut stays on the device and comes back with per_read (d_cntm / d_aoff are free until the chunks)
-    uint32_t* d_hist;
-    if (int rc = occ_census_dev(sk.hash, nm, P, st, B, ms, d_cntm, d_aoff, &d_occ, &d_hist, err)) return rc;
-    if (d_core) k_runs_occ<true><<<nblk(nm, 256), 256, 0, st>>>(sk.hash, sk.meta, nm, d_occ, d_cnt, d_run_end, d_per_read, d_core);
-    else k_runs_occ<false><<<nblk(nm, 256), 256, 0, st>>>(sk.hash, sk.meta, nm, d_occ, d_cnt, d_run_end, d_per_read, nullptr);
-  } else if (d_core) k_runs<true><<<nblk(nm, 256), 256, 0, st>>>(sk.hash, sk.meta, nm, P.max_occ, d_cnt, d_run_end, d_per_read, d_core);
-  else k_runs<false><<<nblk(nm, 256), 256, 0, st>>>(sk.hash, sk.meta, nm, P.max_occ, d_cnt, d_run_end, d_per_read, nullptr);
-  OVL_TRY(hipGetLastError());
   std::vector<unsigned long long> per_read(S.n_reads);
   OVL_TRY(hipMemcpyAsync(per_read.data(), d_per_read, 8ull * S.n_reads, hipMemcpyDeviceToHost, st));
-  if (frac) OVL_TRY(hipMemcpyAsync(occ, d_occ, sizeof(occ), hipMemcpyDeviceToHost, st));
+  if (frac) OVL_TRY(hipMemcpyAsync(occ, X.d_occ, sizeof(occ), hipMemcpyDeviceToHost, st));
+  if (rescue) OVL_TRY(hipMemcpyAsync(resc_stat, X.stat, sizeof(resc_stat), hipMemcpyDeviceToHost, st));
   OVL_TRY(hipStreamSynchronize(st));
   if (frac) { stats.occ_cut = occ[0]; stats.distinct = occ[1]; stats.cut_runs = occ[2]; stats.cut_minimizers = occ[3]; }
   if (rescue) { stats.resc_high = resc_stat[0]; stats.rescued = resc_stat[1]; stats.resc_anchors = resc_stat[2]; }
 
-  uint32_t max_len = 0;
-  for (uint32_t r = 0; r < S.n_reads; r++) max_len = std::max(max_len, S.h_len[r]);
-  const RunsOut RO{sk.meta, nm, d_cnt, d_run_end, d_cntm, d_aoff, ms.partial, per_read.data(), 0, S.n_reads, max_len};
+  const RunsOut RO{sk.meta, nm, d_cnt, d_run_end, d_cntm, d_aoff, X.ms.partial, per_read.data(), 0, S.n_reads, max_read_len(S)};
   return chain_chunks(S, P, budget_bytes, st, B, RO, stats, err, [&](uint32_t t_lo, uint64_t* A0, uint64_t* B0) {
-    if (rescue && d_core) k_expand_resc<true><<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, d_core, R.kind);
-    else if (rescue) k_expand_resc<false><<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, nullptr, R.kind);
-    else if (d_core) k_expand<true><<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, d_core);
-    else k_expand<false><<<nblk(nm, 256), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, nullptr);
+    with_core(d_core, [&](auto core) {
+      constexpr bool CORE = decltype(core)::value;
+      if (rescue)
+        k_expand_resc<CORE><<<nblk(nm), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, d_core, X.kind);
+      else k_expand<CORE><<<nblk(nm), 256, 0, st>>>(sk.meta, d_cntm, d_run_end, d_aoff, nm, S.d_base_off, P.k, t_lo, A0, B0, d_core);
+    });
   }, take);
 }
 
@@ -1556,8 +1277,8 @@ int chain_chunks(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, h
     if (!na64) continue;
     stats.chunks++;
     const uint32_t na = (uint32_t)na64;
-    k_mask<<<nblk(nm, 256), 256, 0, st>>>(RO.meta, RO.cnt, nm, t_lo, t_hi, RO.cntm);
-    if (int rc = scan_u32(RO.cntm, nm, RO.aoff, RO.scan_partial, st, err)) return rc;
+    k_mask<<<nblk(nm), 256, 0, st>>>(RO.meta, RO.cnt, nm, t_lo, t_hi, RO.cntm);
+    if (int rc = dev_scan_u32(RO.cntm, nm, RO.aoff, RO.scan_partial, st, err)) return rc;
     expand(t_lo, A0, B0);
     OVL_TRY(hipGetLastError());
     {
@@ -1566,24 +1287,22 @@ int chain_chunks(const OvlStore& S, const OvlParams& P, uint64_t budget_bytes, h
       field_shifts(sa, 32, bits_of(max_len));
       field_shifts(sb, 0, 1 + bits_of(S.n_reads - 1));
       field_shifts(sb, 33, bits_of(t_hi - t_lo - 1));
-      if (int rc = radix_sort(&A0, &B0, &A1, &B1, na, sa, as, st, err)) return rc;     // by (tpos, qpos)
-      if (int rc = radix_sort(&B0, &A0, &B1, &A1, na, sb, as, st, err)) return rc;     // then by (t, q, rel), stable
+      if (int rc = dev_radix_sort(&A0, &B0, &A1, &B1, na, sa, as, st, err)) return rc;     // by (tpos, qpos)
+      if (int rc = dev_radix_sort(&B0, &A0, &B1, &A1, na, sb, as, st, err)) return rc;     // then by (t, q, rel), stable
     }
-    k_heads<<<nblk(na, 256), 256, 0, st>>>(B0, na, flag);
-    if (int rc = scan_u32(flag, na, gidx, as.partial, st, err)) return rc;
-    k_gstart<<<nblk(na, 256), 256, 0, st>>>(flag, gidx, na, gstart);
+    if (int rc = run_starts(B0, na, flag, gidx, gstart, as.partial, st, err)) return rc;     // the (t, q, rel) groups
     uint32_t ng = 0;
     OVL_TRY(hipMemcpyAsync(&ng, gidx + na, 4, hipMemcpyDeviceToHost, st));
     OVL_TRY(hipStreamSynchronize(st));
     stats.groups += ng;
-    k_gflag<<<nblk(ng, 256), 256, 0, st>>>(gstart, ng, P.min_anchors, gf);
-    if (int rc = scan_u32(gf, ng, cidx, as.partial, st, err)) return rc;
+    k_gflag<<<nblk(ng), 256, 0, st>>>(gstart, ng, P.min_anchors, gf);
+    if (int rc = dev_scan_u32(gf, ng, cidx, as.partial, st, err)) return rc;
     uint32_t nc = 0;
     OVL_TRY(hipMemcpyAsync(&nc, cidx + ng, 4, hipMemcpyDeviceToHost, st));
     OVL_TRY(hipStreamSynchronize(st));
     if (!nc) continue;
     stats.chained += nc;
-    k_gcompact<<<nblk(ng, 256), 256, 0, st>>>(gstart, gf, cidx, ng, C.cstart, C.csize, C.ck0, C.cp0);
+    k_gcompact<<<nblk(ng), 256, 0, st>>>(gstart, gf, cidx, ng, C.cstart, C.csize, C.ck0, C.cp0);
     OVL_TRY(hipGetLastError());
     if (int rc = chain_and_walk(A0, B0, C, nc, P, S.d_base_off, t_lo, as, st, err)) return rc;
     if (int rc = take(nc, C.gout, ccap, t_hi, B)) return rc;
@@ -1599,7 +1318,8 @@ constexpr uint64_t PART_RANGE_FLOOR = 65536;                 // minimizers a has
 // tiles tile0[b] .. tile0[b + 1] - 1, its minimizers the ordinals ord0[b] .. ord0[b + 1] - 1; u_at + tile0[b] + b is its slice of the prefix of
 // the minimizers per tile (tiles + 1 entries, from 0).
 struct PartIndex {
-  Bufs B;
+  BufsPeak acct;                                // the bytes of B and of every part's scratch (OvlStats.peak_bytes)
+  Bufs B{&acct};
   std::vector<uint64_t> cuts, ord0;
   std::vector<uint32_t> tile0;
   uint32_t n_blocks = 0, max_tiles = 0;
@@ -1607,8 +1327,7 @@ struct PartIndex {
   uint32_t *d_tile_off = nullptr, *d_u_at = nullptr, *d_cnt = nullptr, *d_partial = nullptr;
   uint16_t* d_occ16 = nullptr;
   unsigned long long* d_hist = nullptr;         // [OVL_OCC_BINS] the census of the whole store
-  uint64_t* d_occ = nullptr;                    // occ_frac_ppm != 0: {cut, distinct, runs above the cut, minimizers in them} (k_occ_pick64)
-  explicit PartIndex(BufsPeak* acct) : B(acct) {}
+  uint64_t* d_occ = nullptr;                    // occ_frac_ppm != 0: {cut, distinct, runs above the cut, minimizers in them} (k_occ_pick)
   uint32_t reads_of(uint32_t b) const { return (uint32_t)(cuts[b + 1] - cuts[b]); }
   uint32_t tiles_of(uint32_t b) const { return tile0[b + 1] - tile0[b]; }
   uint32_t minimizers_of(uint32_t b) const { return (uint32_t)(ord0[b + 1] - ord0[b]); }
@@ -1624,29 +1343,39 @@ SketchPart sketch_part_args(const OvlStore& S, const OvlParams& P, const PartInd
   return a;
 }
 
-// One hash range [h_lo, h_hi] of pass A.  *n_out: its minimizers; with may_split and more than split_above of them nothing is written (the count
-// pass says so first) and *n_out alone comes back.  f_at: a per-tile table like u_at, this range's.
-int part_range(const OvlStore& S, const OvlParams& P, hipStream_t st, PartIndex& X, uint32_t* f_at, uint64_t h_lo, uint64_t h_hi, bool may_split,
-               uint64_t split_above, uint64_t* n_out, std::string& err) {
-  std::vector<uint32_t> ftot(X.n_blocks, 0);
+// A count pass of pass A over every block: the minimizers per tile (MODE SKP_COUNT: all of them, SKP_COUNT_RANGE: those with a hash in
+// [h_lo, h_hi]), their scan into the block's slice of the per-tile table `at` and, once the stream is synchronised here, tot[b], the block's total.
+template <int MODE>
+int part_count_pass(const OvlStore& S, const OvlParams& P, hipStream_t st, PartIndex& X, uint32_t* at, uint64_t h_lo, uint64_t h_hi,
+                    std::vector<uint32_t>& tot, std::string& err) {
+  tot.assign(X.n_blocks, 0);
   for (uint32_t b = 0; b < X.n_blocks; b++) {
     const uint32_t nt = X.tiles_of(b);
     if (!nt) continue;
     SketchPart a = sketch_part_args(S, P, X, b);
     a.h_lo = h_lo; a.h_hi = h_hi; a.cnt = X.d_cnt;
-    k_sketch_part<SKP_COUNT_RANGE><<<nt, SK_T, 0, st>>>(a);
+    k_sketch_part<MODE><<<nt, SK_T, 0, st>>>(a);
     OVL_TRY(hipGetLastError());
-    if (int rc = scan_u32(X.d_cnt, nt, f_at + X.tile0[b] + b, X.d_partial, st, err)) return rc;
-    OVL_TRY(hipMemcpyAsync(&ftot[b], f_at + X.tile0[b] + b + nt, 4, hipMemcpyDeviceToHost, st));
+    if (int rc = dev_scan_u32(X.d_cnt, nt, at + X.tile0[b] + b, X.d_partial, st, err)) return rc;
+    OVL_TRY(hipMemcpyAsync(&tot[b], at + X.tile0[b] + b + nt, 4, hipMemcpyDeviceToHost, st));
   }
   OVL_TRY(hipStreamSynchronize(st));
+  return OVL_OK;
+}
+
+// One hash range [h_lo, h_hi] of pass A.  *n_out: its minimizers; with may_split and more than split_above of them nothing is written (the count
+// pass says so first) and *n_out alone comes back.  f_at: a per-tile table like u_at, this range's.
+int part_range(const OvlStore& S, const OvlParams& P, hipStream_t st, PartIndex& X, uint32_t* f_at, uint64_t h_lo, uint64_t h_hi, bool may_split,
+               uint64_t split_above, uint64_t* n_out, std::string& err) {
+  std::vector<uint32_t> ftot;
+  if (int rc = part_count_pass<SKP_COUNT_RANGE>(S, P, st, X, f_at, h_lo, h_hi, ftot, err)) return rc;
   uint64_t n64 = 0;
   for (uint32_t v : ftot) n64 += v;
   *n_out = n64;
   if (!n64 || (may_split && n64 > split_above)) return OVL_OK;
   if (n64 > PART_MAX_MINIMIZERS) { err = "overlap finder: a hash range of the occurrence pass holds more than 2^32 - 4096 minimizers (more occ_ranges)"; return OVL_UNSUPPORTED; }
   const uint32_t n = (uint32_t)n64;
-  Bufs RB(X.B.acct);
+  Bufs RB(&X.acct);
   uint64_t *hk0, *hp0, *hk1, *hp1;
   uint32_t *flag, *gidx, *rstart;
   SortScratch ms;
@@ -1666,13 +1395,9 @@ int part_range(const OvlStore& S, const OvlParams& P, hipStream_t st, PartIndex&
     at += ftot[b];
   }
   OVL_TRY(hipGetLastError());
-  std::vector<uint32_t> shifts;
-  field_shifts(shifts, 0, 2 * P.k);
-  if (int rc = radix_sort(&hk0, &hp0, &hk1, &hp1, n, shifts, ms, st, err)) return rc;
-  k_heads<<<nblk(n, 256), 256, 0, st>>>(hk0, n, flag);
-  if (int rc = scan_u32(flag, n, gidx, ms.partial, st, err)) return rc;
-  k_gstart<<<nblk(n, 256), 256, 0, st>>>(flag, gidx, n, rstart);
-  k_occ16<<<std::min(nblk(n, 256), OCC_GRID), 256, 0, st>>>(hp0, flag, gidx, rstart, n, X.d_occ16, X.d_hist);
+  if (int rc = dev_radix_sort(&hk0, &hp0, &hk1, &hp1, n, hash_shifts(P.k), ms, st, err)) return rc;
+  if (int rc = run_starts(hk0, n, flag, gidx, rstart, ms.partial, st, err)) return rc;
+  k_occ16<<<std::min(nblk(n), OCC_GRID), 256, 0, st>>>(hp0, flag, gidx, rstart, n, X.d_occ16, X.d_hist);
   OVL_TRY(hipGetLastError());
   OVL_TRY(hipStreamSynchronize(st));           // (RB goes with the return)
   return OVL_OK;
@@ -1690,22 +1415,13 @@ int part_index(const OvlStore& S, const OvlParams& P, hipStream_t st, PartIndex&
   }
   X.n_blocks = (uint32_t)bk.size();
   stats.blocks = X.n_blocks;
-  std::vector<uint32_t> tile_off((size_t)S.n_reads + 1, 0);
-  uint64_t tiles = 0, kmers = 0;
+  std::vector<uint32_t> tile_off;
+  uint64_t kmers;
+  const uint64_t tiles = tile_table(S, P, tile_off, kmers);
+  if (tiles + X.n_blocks > 0xfffff000ull) { err = "overlap finder: more than 2^40 k-mers in the read store"; return OVL_UNSUPPORTED; }
   X.tile0.assign((size_t)X.n_blocks + 1, 0);
-  for (uint32_t b = 0; b < X.n_blocks; b++) {
-    X.tile0[b] = (uint32_t)tiles;
-    for (uint64_t r = X.cuts[b]; r < X.cuts[b + 1]; r++) {
-      tile_off[r] = (uint32_t)tiles;
-      const uint64_t nk = index_read_kmers(S.h_len[r], P.k, P.w);
-      kmers += nk;
-      tiles += (nk + SK_T - 1) / SK_T;
-    }
-    if (tiles + X.n_blocks > 0xfffff000ull) { err = "overlap finder: more than 2^40 k-mers in the read store"; return OVL_UNSUPPORTED; }
-    X.max_tiles = std::max(X.max_tiles, (uint32_t)tiles - X.tile0[b]);
-  }
-  tile_off[S.n_reads] = (uint32_t)tiles;
-  X.tile0[X.n_blocks] = (uint32_t)tiles;
+  for (uint32_t b = 0; b <= X.n_blocks; b++) X.tile0[b] = tile_off[X.cuts[b]];
+  for (uint32_t b = 0; b < X.n_blocks; b++) X.max_tiles = std::max(X.max_tiles, X.tiles_of(b));
   stats.kmers = kmers;
   X.ord0.assign((size_t)X.n_blocks + 1, 0);
   if (!tiles) return OVL_OK;
@@ -1718,18 +1434,8 @@ int part_index(const OvlStore& S, const OvlParams& P, hipStream_t st, PartIndex&
   OVL_TRY(X.B.get(&X.d_occ, 4));
   OVL_TRY(hipMemsetAsync(X.d_hist, 0, 8ull * OVL_OCC_BINS, st));
   OVL_TRY(hipMemcpyAsync(X.d_tile_off, tile_off.data(), 4ull * (S.n_reads + 1), hipMemcpyHostToDevice, st));
-  std::vector<uint32_t> utot(X.n_blocks, 0);
-  for (uint32_t b = 0; b < X.n_blocks; b++) {
-    const uint32_t ntb = X.tiles_of(b);
-    if (!ntb) continue;
-    SketchPart a = sketch_part_args(S, P, X, b);
-    a.cnt = X.d_cnt;
-    k_sketch_part<SKP_COUNT><<<ntb, SK_T, 0, st>>>(a);
-    OVL_TRY(hipGetLastError());
-    if (int rc = scan_u32(X.d_cnt, ntb, X.d_u_at + X.tile0[b] + b, X.d_partial, st, err)) return rc;
-    OVL_TRY(hipMemcpyAsync(&utot[b], X.d_u_at + X.tile0[b] + b + ntb, 4, hipMemcpyDeviceToHost, st));
-  }
-  OVL_TRY(hipStreamSynchronize(st));           // (also keeps tile_off alive until its copy is done)
+  std::vector<uint32_t> utot;                   // (the pass ends synchronised: tile_off's copy is done as well)
+  if (int rc = part_count_pass<SKP_COUNT>(S, P, st, X, X.d_u_at, 0, INF64, utot, err)) return rc;
   for (uint32_t b = 0; b < X.n_blocks; b++) X.ord0[b + 1] = X.ord0[b] + utot[b];
   X.minimizers = X.ord0[X.n_blocks];
   stats.minimizers = X.minimizers;
@@ -1764,7 +1470,7 @@ int part_index(const OvlStore& S, const OvlParams& P, hipStream_t st, PartIndex&
   }
   if (P.occ_frac_ppm) {
     uint64_t occ[4];
-    k_occ_pick64<<<1, 256, 0, st>>>(X.d_hist, X.minimizers, P.occ_frac_ppm, P.max_occ, X.d_occ);
+    k_occ_pick<<<1, 256, 0, st>>>(X.d_hist, X.minimizers, P.occ_frac_ppm, P.max_occ, X.d_occ);
     OVL_TRY(hipGetLastError());
     OVL_TRY(hipMemcpyAsync(occ, X.d_occ, sizeof(occ), hipMemcpyDeviceToHost, st));
     OVL_TRY(hipStreamSynchronize(st));
@@ -1804,22 +1510,13 @@ void part_rescue_block(const OvlStore& S, const OvlParams& P, hipStream_t st, co
 template <class Reset, class Take>
 int find_parts(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uint64_t budget_bytes, hipStream_t st, OvlStats& stats, std::string& err,
                Reset reset, Take take) {
-  stats = OvlStats{};
-  if (!lookback_ok(P.lookback)) { err = "overlap finder: the look-back is a multiple of 64 in 64 .. 1024"; return OVL_UNSUPPORTED; }
-  BufsPeak acct;
-  PartIndex X(&acct);
-  const int rc_all = [&]() -> int {
+  PartIndex X;
+  const int rc_all = synced_on_failure(st, [&]() -> int {
     if (int rc = part_index(S, P, st, X, stats, err)) return rc;
     const bool frac = P.occ_frac_ppm != 0, rescue = P.occ_dist != 0;
-    if (X.minimizers < 2) {                     // (as find_chunks: fewer than two minimizers are as many runs of one)
-      stats.occ_cut = frac ? occ_final_cut((uint32_t)X.minimizers, P.max_occ) : P.max_occ;
-      stats.distinct = frac ? X.minimizers : 0;
-      stats.cut_runs = stats.cut_minimizers = 0;
-      return OVL_OK;
-    }
-    if (!frac) stats.occ_cut = P.max_occ;
-    uint32_t max_len = 0;
-    for (uint32_t r = 0; r < S.n_reads; r++) max_len = std::max(max_len, S.h_len[r]);
+    if (!frac || X.minimizers < 2) stats_without_census(stats, X.minimizers, P);     // (else part_index has left the pick's figures)
+    if (X.minimizers < 2) return OVL_OK;
+    const uint32_t max_len = max_read_len(S);
     std::vector<uint8_t> has_core(X.n_blocks, 1);
     if (d_core) {
       std::vector<uint8_t> core(S.n_reads);
@@ -1840,7 +1537,7 @@ int find_parts(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uin
         reset();
         const uint32_t nm = ni + nj;            // (the plan keeps the k-mers of a pair, so its minimizers, within 2^32 - 4096)
         const uint32_t t0 = (uint32_t)X.cuts[bi], t1 = (uint32_t)X.cuts[bi + 1], split = bj > bi ? (uint32_t)X.cuts[bj] : 0u;
-        Bufs B(&acct);
+        Bufs B(&X.acct);
         PartSketch K{};
         uint8_t *resc = nullptr, *cls, *cls_s;
         uint64_t *idx, *k1, *p1, *meta_s;
@@ -1865,16 +1562,13 @@ int find_parts(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uin
           part_rescue_block(S, P, st, X, bi, 0, K, resc, bj == bi ? d_stat : d_stat + 3);
           if (bj > bi) part_rescue_block(S, P, st, X, bj, ni, K, resc, d_stat + 3);
         }
-        k_part_cls<<<nblk(nm, 256), 256, 0, st>>>(K.occ, resc, nm, P.max_occ, X.d_occ, rescue ? P.rescue_max_occ : 0u, cls, idx);
+        k_part_cls<<<nblk(nm), 256, 0, st>>>(K.occ, resc, nm, P.max_occ, X.d_occ, rescue ? P.rescue_max_occ : 0u, cls, idx);
         OVL_TRY(hipGetLastError());
-        {
-          std::vector<uint32_t> shifts;
-          field_shifts(shifts, 0, 2 * P.k);
-          if (int rc = radix_sort(&K.hash, &idx, &k1, &p1, nm, shifts, ms, st, err)) return rc;
-        }
-        k_part_gather<<<nblk(nm, 256), 256, 0, st>>>(idx, K.meta, cls, nm, meta_s, cls_s);
-        if (d_core) k_part_runs<true><<<nblk(nm, 256), 256, 0, st>>>(K.hash, meta_s, cls_s, nm, split, t0, d_cnt, d_run_end, d_per_read, d_core, d_stat);
-        else k_part_runs<false><<<nblk(nm, 256), 256, 0, st>>>(K.hash, meta_s, cls_s, nm, split, t0, d_cnt, d_run_end, d_per_read, nullptr, d_stat);
+        if (int rc = dev_radix_sort(&K.hash, &idx, &k1, &p1, nm, hash_shifts(P.k), ms, st, err)) return rc;
+        k_part_gather<<<nblk(nm), 256, 0, st>>>(idx, K.meta, cls, nm, meta_s, cls_s);
+        with_core(d_core, [&](auto core) {
+          k_part_runs<decltype(core)::value><<<nblk(nm), 256, 0, st>>>(K.hash, meta_s, cls_s, nm, split, t0, d_cnt, d_run_end, d_per_read, d_core, d_stat);
+        });
         OVL_TRY(hipGetLastError());
         std::vector<unsigned long long> per_read(t1 - t0);
         unsigned long long resc_stat[3] = {0, 0, 0};
@@ -1884,24 +1578,35 @@ int find_parts(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uin
         if (rescue) { stats.resc_high += resc_stat[0]; stats.rescued += resc_stat[1]; stats.resc_anchors += resc_stat[2]; }
         const RunsOut RO{meta_s, nm, d_cnt, d_run_end, d_cntm, d_aoff, ms.partial, per_read.data(), t0, t1, max_len};
         if (int rc = chain_chunks(S, P, budget_bytes, st, B, RO, stats, err, [&](uint32_t t_lo, uint64_t* A0, uint64_t* B0) {
-          if (d_core) k_part_expand<true><<<nblk(nm, 256), 256, 0, st>>>(meta_s, cls_s, d_cntm, d_run_end, d_aoff, nm, split, S.d_base_off, P.k, t_lo, A0, B0, d_core);
-          else k_part_expand<false><<<nblk(nm, 256), 256, 0, st>>>(meta_s, cls_s, d_cntm, d_run_end, d_aoff, nm, split, S.d_base_off, P.k, t_lo, A0, B0, nullptr);
+          with_core(d_core, [&](auto core) {
+            k_part_expand<decltype(core)::value><<<nblk(nm), 256, 0, st>>>(meta_s, cls_s, d_cntm, d_run_end, d_aoff, nm, split, S.d_base_off, P.k, t_lo, A0,
+                                                                           B0, d_core);
+          });
         }, take)) return rc;
         OVL_TRY(hipStreamSynchronize(st));     // (B goes with the pair: nothing of it is still read)
       }
     }
     return OVL_OK;
-  }();
-  if (rc_all != OVL_OK) (void)hipStreamSynchronize(st);
-  stats.peak_bytes = acct.peak;
+  });
+  stats.peak_bytes = X.acct.peak;
   return rc_all;
+}
+
+// ovl_find and ovl_find_pairs behind their take: the whole store's index, or (index_kmers != 0) an index in parts, where reset() comes in front of
+// every block pair.
+template <class Reset, class Take>
+int find_overlaps(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uint64_t budget_bytes, hipStream_t st, OvlStats& stats, std::string& err,
+                  Reset reset, Take take) {
+  stats = OvlStats{};
+  if (!lookback_ok(P.lookback, err)) return OVL_UNSUPPORTED;
+  if (!P.index_kmers) return find_chunks(S, P, d_core, budget_bytes, st, stats, err, take);
+  return find_parts(S, P, d_core, budget_bytes, st, stats, err, reset, take);
 }
 }  // namespace
 
 int ovl_occ_census(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vector<uint32_t>* hist, uint64_t rec[4], std::string& err) {
   if (P.index_kmers) {                          // pass A alone; a bin beyond 32 bits is reported as 2^32 - 1
-    BufsPeak acct;
-    PartIndex X(&acct);
+    PartIndex X;
     OvlStats stats;
     if (int rc = part_index(S, P, st, X, stats, err)) { (void)hipStreamSynchronize(st); return rc; }
     if (hist) hist->assign(OVL_OCC_BINS, 0);
@@ -1916,38 +1621,30 @@ int ovl_occ_census(const OvlStore& S, const OvlParams& P, hipStream_t st, std::v
     return OVL_OK;
   }
   Bufs B;
-  Sketch sk;
-  if (int rc = sketch_dev(S, P, st, B, sk, err)) return rc;
+  StoreIndex X;
+  if (int rc = store_index(S, P, true, false, 1, st, B, X, err)) return rc;
   if (hist) hist->assign(OVL_OCC_BINS, 0);
   rec[0] = occ_final_cut(0, P.max_occ);
   rec[1] = rec[2] = rec[3] = 0;
-  if (!sk.n) { OVL_TRY(hipStreamSynchronize(st)); return OVL_OK; }
-  SortScratch ms;
-  if (int rc = sort_by_hash(sk, P.k, st, B, ms, err)) return rc;
-  uint32_t *flag, *gidx, *d_hist;
-  uint64_t* d_occ;
-  OVL_TRY(B.get(&flag, sk.n));
-  OVL_TRY(B.get(&gidx, (uint64_t)sk.n + 1));
-  if (int rc = occ_census_dev(sk.hash, sk.n, P, st, B, ms, flag, gidx, &d_occ, &d_hist, err)) return rc;
-  if (hist) OVL_TRY(hipMemcpyAsync(hist->data(), d_hist, 4ull * OVL_OCC_BINS, hipMemcpyDeviceToHost, st));
-  OVL_TRY(hipMemcpyAsync(rec, d_occ, 32, hipMemcpyDeviceToHost, st));
+  if (!X.built) { OVL_TRY(hipStreamSynchronize(st)); return OVL_OK; }
+  if (hist) OVL_TRY(hipMemcpyAsync(hist->data(), X.d_hist, 4ull * OVL_OCC_BINS, hipMemcpyDeviceToHost, st));
+  OVL_TRY(hipMemcpyAsync(rec, X.d_occ, 32, hipMemcpyDeviceToHost, st));
   OVL_TRY(hipStreamSynchronize(st));
   return OVL_OK;
 }
 
 int ovl_seed_rescue(const OvlStore& S, const OvlParams& P, hipStream_t st, std::vector<uint32_t>& occ, std::vector<uint8_t>& rescued, std::string& err) {
   if (P.index_kmers) {                          // pass A, then block by block: its sketch, occ from occ16, k_rescue
-    BufsPeak acct;
-    PartIndex X(&acct);
+    PartIndex X;
     OvlStats stats;
-    const int rc_all = [&]() -> int {
+    return synced_on_failure(st, [&]() -> int {
       if (int rc = part_index(S, P, st, X, stats, err)) return rc;
       occ.assign(X.minimizers, 1);
       rescued.assign(X.minimizers, 0);
       for (uint32_t b = 0; b < X.n_blocks; b++) {
         const uint32_t n = X.minimizers_of(b);
         if (!n) continue;
-        Bufs B(&acct);
+        Bufs B(&X.acct);
         PartSketch K{};
         uint8_t* resc;
         unsigned long long* stat;
@@ -1963,28 +1660,17 @@ int ovl_seed_rescue(const OvlStore& S, const OvlParams& P, hipStream_t st, std::
         OVL_TRY(hipStreamSynchronize(st));
       }
       return OVL_OK;
-    }();
-    if (rc_all != OVL_OK) (void)hipStreamSynchronize(st);
-    return rc_all;
+    });
   }
   Bufs B;
-  Sketch sk;
-  if (int rc = sketch_dev(S, P, st, B, sk, err)) return rc;
-  occ.assign(sk.n, 1);
-  rescued.assign(sk.n, 0);
-  if (sk.n < 2) { OVL_TRY(hipStreamSynchronize(st)); return OVL_OK; }
-  Rescue R;
-  if (int rc = rescue_keep_meta(sk, st, B, R, err)) return rc;
-  SortScratch ms;
-  if (int rc = sort_by_hash(sk, P.k, st, B, ms, err)) return rc;
-  uint32_t *flag, *gidx, *d_hist, *rstart = nullptr;
-  uint64_t* d_occ = nullptr;
-  OVL_TRY(B.get(&flag, sk.n));
-  OVL_TRY(B.get(&gidx, (uint64_t)sk.n + 1));
-  if (P.occ_frac_ppm) if (int rc = occ_census_dev(sk.hash, sk.n, P, st, B, ms, flag, gidx, &d_occ, &d_hist, err, &rstart)) return rc;
-  if (int rc = rescue_dev(sk, S, P, st, B, ms, flag, gidx, rstart, d_occ, R, err)) return rc;
-  OVL_TRY(hipMemcpyAsync(occ.data(), R.occ_rp, 4ull * sk.n, hipMemcpyDeviceToHost, st));
-  OVL_TRY(hipMemcpyAsync(rescued.data(), R.resc_rp, sk.n, hipMemcpyDeviceToHost, st));
+  StoreIndex X;
+  if (int rc = store_index(S, P, P.occ_frac_ppm != 0, true, 2, st, B, X, err)) return rc;
+  const uint32_t n = X.sk.n;
+  occ.assign(n, 1);
+  rescued.assign(n, 0);
+  if (!X.built) { OVL_TRY(hipStreamSynchronize(st)); return OVL_OK; }
+  OVL_TRY(hipMemcpyAsync(occ.data(), X.occ_rp, 4ull * n, hipMemcpyDeviceToHost, st));
+  OVL_TRY(hipMemcpyAsync(rescued.data(), X.resc_rp, n, hipMemcpyDeviceToHost, st));
   OVL_TRY(hipStreamSynchronize(st));
   for (uint32_t& c : occ) c = std::min(c, OVL_OCC_BINS - 1);
   return OVL_OK;
@@ -2002,11 +1688,10 @@ int ovl_find(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uint6
       if (g.kept) out.push_back(OvlPair{g.t, g.q, g.rel, g.n_anchors, g.score, g.tstart, g.tend, g.qstart, g.qend});
     return OVL_OK;
   };
-  if (!P.index_kmers) return find_chunks(S, P, d_core, budget_bytes, st, stats, err, take);
-  // an index in parts: a target's chains come pair by pair, (i, i), (i, i + 1), ... — in ascending q, every (t, q) in one pair; the stable sort by t
-  // gives ascending (t, q, rel)
-  if (int rc = find_parts(S, P, d_core, budget_bytes, st, stats, err, [] {}, take)) return rc;
-  std::stable_sort(out.begin(), out.end(), [](const OvlPair& a, const OvlPair& b) { return a.t < b.t; });
+  if (int rc = find_overlaps(S, P, d_core, budget_bytes, st, stats, err, [] {}, take)) return rc;
+  // an index in parts of several blocks: a target's chains come pair by pair, (i, i), (i, i + 1), ... — in ascending q, every (t, q) in one pair; the
+  // stable sort by t gives ascending (t, q, rel)
+  if (stats.blocks > 1) std::stable_sort(out.begin(), out.end(), [](const OvlPair& a, const OvlPair& b) { return a.t < b.t; });
   return OVL_OK;
 }
 
@@ -2014,7 +1699,7 @@ int ovl_find(const OvlStore& S, const OvlParams& P, const uint8_t* d_core, uint6
 // length it then does not ask for; it leaves the first anchor's coordinates, and the keys of a group are strictly ascending: its index is looked up.
 int ovl_chain_groups(uint64_t n_groups, const uint64_t* group_off, const uint32_t* tpos, const uint32_t* qpos, const OvlParams& P, hipStream_t st,
                      int32_t* out, std::string& err) {
-  if (!lookback_ok(P.lookback)) { err = "overlap finder: the look-back is a multiple of 64 in 64 .. 1024"; return OVL_UNSUPPORTED; }
+  if (!lookback_ok(P.lookback, err)) return OVL_UNSUPPORTED;
   if (!n_groups) return OVL_OK;
   const uint32_t nc = (uint32_t)n_groups;
   const uint64_t na = group_off[n_groups];
@@ -2075,8 +1760,8 @@ int ovl_find_pairs(const OvlStore& S, const OvlParams& P, const uint8_t* d_core,
       OVL_TRY(B.get(&soff, ccap + 1));
       OVL_TRY(B.get(&part, (uint64_t)nblk(ccap, SC_TILE) + 2));
     }
-    k_pick<<<nblk(nc, 256), 256, 0, st>>>(gout, nc, sel);
-    if (int rc2 = scan_u32(sel, nc, soff, part, st, err)) return rc2;
+    k_pick<<<nblk(nc), 256, 0, st>>>(gout, nc, sel);
+    if (int rc2 = dev_scan_u32(sel, nc, soff, part, st, err)) return rc2;
     uint32_t ns = 0;
     OVL_TRY(hipMemcpyAsync(&ns, soff + nc, 4, hipMemcpyDeviceToHost, st));
     OVL_TRY(hipStreamSynchronize(st));
@@ -2098,104 +1783,16 @@ int ovl_find_pairs(const OvlStore& S, const OvlParams& P, const uint8_t* d_core,
       }
       OVL_TRY(e);
     }
-    k_prim_write<<<nblk(nc, 256), 256, 0, st>>>(gout, sel, soff, nc, S.d_base_off, out.d + out.n);
+    k_prim_write<<<nblk(nc), 256, 0, st>>>(gout, sel, soff, nc, S.d_base_off, out.d + out.n);
     OVL_TRY(hipGetLastError());
     out.n += ns;
     return OVL_OK;
   };
-  if (!P.index_kmers) {
-    if (int rc = find_chunks(S, P, d_core, budget_bytes, st, stats, err, take)) return rc;
-    OVL_TRY(hipStreamSynchronize(st));
-    return OVL_OK;
-  }
-  // an index in parts: the scratch of a block pair goes with the pair, and so does what take keeps in it
-  if (int rc = find_parts(S, P, d_core, budget_bytes, st, stats, err, [&] { sel = soff = part = nullptr; }, take)) return rc;
+  // an index in parts: the scratch of a block pair goes with the pair, and so does what take keeps in it; the records of several blocks are then
+  // put into target order
+  if (int rc = find_overlaps(S, P, d_core, budget_bytes, st, stats, err, [&] { sel = soff = part = nullptr; }, take)) return rc;
   OVL_TRY(hipStreamSynchronize(st));
-  if (stats.blocks < 2 || out.n < 2) return OVL_OK;
-  // A target's records come pair by pair — (i, i), (i, i + 1), ... —, in ascending q inside a pair and from pair to pair: one stable sort by t puts
-  // the call's records into ascending (t, q).
-  const uint32_t n = (uint32_t)out.n;            // (<= 2^31 - 1: take)
-  Bufs B;
-  uint64_t *k0, *p0, *k1, *p1;
-  uint32_t* scratch;
-  OvlRec* sorted = nullptr;
-  OVL_TRY(B.get(&k0, n)); OVL_TRY(B.get(&p0, n)); OVL_TRY(B.get(&k1, n)); OVL_TRY(B.get(&p1, n));
-  OVL_TRY(B.get(&scratch, ovl_sort_scratch(n)));
-  OVL_TRY(hipMalloc((void**)&sorted, (uint64_t)n * sizeof(OvlRec)));
-  k_rec_keys<<<nblk(n, 256), 256, 0, st>>>(out.d, n, k0, p0);
-  std::vector<uint32_t> shifts;
-  field_shifts(shifts, 0, bits_of(S.n_reads - 1));
-  int rc = ovl_radix_sort(&k0, &p0, &k1, &p1, n, shifts, scratch, st, err);
-  hipError_t e = hipSuccess;
-  if (rc == OVL_OK) {
-    k_rec_gather<<<nblk(n, 256), 256, 0, st>>>(out.d, p0, n, sorted);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (rc != OVL_OK || e != hipSuccess) {
-    (void)hipFree(sorted);
-    if (rc != OVL_OK) return rc;
-    OVL_TRY(e);
-  }
-  (void)hipFree(out.d);
-  out.d = sorted;
-  out.cap = n;
-  return OVL_OK;
-}
-
-int ovl_row_table(const OvlRecs& R, uint32_t n_reads, const uint8_t* d_core, hipStream_t st, std::vector<uint32_t>& rids, std::vector<uint64_t>& aln_off,
-                  std::vector<uint32_t>& rec_of_row, std::string& err) {
-  rids.clear();
-  aln_off.assign(1, 0);
-  rec_of_row.clear();
-  if (!R.n) return OVL_OK;
-  if (R.n > OVL_MAX_PAIRS) { err = "overlap finder: more than 2^31 - 1 overlapping read pairs"; return OVL_UNSUPPORTED; }
-  const uint32_t np = (uint32_t)R.n;
-  uint32_t n = 2 * np;                            // rows; fewer with a core mask (counted below), the arrays are sized for 2 P
-  Bufs B;
-  SortScratch ss;
-  OVL_TRY(ss.alloc(B, n));
-  // one block for the nine arrays of 2 P (+ 1) elements: 8-byte elements first, every array on a 256-byte boundary
-  const uint64_t a8 = (8ull * (n + 1ull) + 255) & ~255ull, a4 = (4ull * (n + 1ull) + 255) & ~255ull;
-  uint8_t* blk = nullptr;
-  OVL_TRY(B.bytes(&blk, 5 * a8 + 4 * a4));
-  uint64_t *k0 = (uint64_t*)blk, *p0 = (uint64_t*)(blk + a8), *k1 = (uint64_t*)(blk + 2 * a8), *p1 = (uint64_t*)(blk + 3 * a8);
-  uint64_t* d_off = (uint64_t*)(blk + 4 * a8);
-  uint32_t *flag = (uint32_t*)(blk + 5 * a8), *tidx = (uint32_t*)(blk + 5 * a8 + a4), *d_rids = (uint32_t*)(blk + 5 * a8 + 2 * a4);
-  uint32_t* d_rec = (uint32_t*)(blk + 5 * a8 + 3 * a4);
-  if (d_core) {                                   // (flag / tidx hold the rows per primary and their scan until the keys are written)
-    k_row_count<<<nblk(np, 256), 256, 0, st>>>(R.d, np, d_core, flag);
-    if (int rc = scan_u32(flag, np, tidx, ss.partial, st, err)) return rc;
-    k_row_keys_core<<<nblk(np, 256), 256, 0, st>>>(R.d, np, d_core, tidx, k0, p0);
-    OVL_TRY(hipGetLastError());
-    OVL_TRY(hipMemcpyAsync(&n, tidx + np, 4, hipMemcpyDeviceToHost, st));
-    OVL_TRY(hipStreamSynchronize(st));
-    if (!n) return OVL_OK;
-  } else {
-    k_row_keys<<<nblk(np, 256), 256, 0, st>>>(R.d, np, k0, p0);
-    OVL_TRY(hipGetLastError());
-  }
-  {
-    std::vector<uint32_t> shifts;                 // keys are unique: one overlap per pair
-    field_shifts(shifts, 0, bits_of(n_reads - 1));
-    field_shifts(shifts, 32, bits_of(n_reads - 1));
-    if (int rc = radix_sort(&k0, &p0, &k1, &p1, n, shifts, ss, st, err)) return rc;
-  }
-  k_row_heads<<<nblk(n, 256), 256, 0, st>>>(k0, n, flag);
-  if (int rc = scan_u32(flag, n, tidx, ss.partial, st, err)) return rc;
-  k_row_write<<<nblk(n, 256), 256, 0, st>>>(k0, p0, flag, tidx, n, d_rids, d_off, d_rec);
-  OVL_TRY(hipGetLastError());
-  uint32_t nt = 0;
-  OVL_TRY(hipMemcpyAsync(&nt, tidx + n, 4, hipMemcpyDeviceToHost, st));
-  OVL_TRY(hipStreamSynchronize(st));
-  rids.resize(nt);
-  aln_off.resize((size_t)nt + 1);
-  rec_of_row.resize(n);
-  OVL_TRY(hipMemcpyAsync(rids.data(), d_rids, 4ull * nt, hipMemcpyDeviceToHost, st));
-  OVL_TRY(hipMemcpyAsync(aln_off.data(), d_off, 8ull * (nt + 1ull), hipMemcpyDeviceToHost, st));
-  OVL_TRY(hipMemcpyAsync(rec_of_row.data(), d_rec, 4ull * n, hipMemcpyDeviceToHost, st));
-  OVL_TRY(hipStreamSynchronize(st));
-  return OVL_OK;
+  return stats.blocks < 2 ? OVL_OK : ovl_sort_recs(out, S.n_reads, st, err);
 }
 
 }  // namespace herro

@@ -2,7 +2,7 @@
 // frontend_api.hip, which the kernels equal byte for byte).
 //   k_paf_len    one wave64 per row: the lanes stride over the row's ops and sum digits(len) + 1, the M lengths and all lengths; lane 0 adds the
 //                fixed part of the line and writes its byte count and the two sums.
-//   (scan)       line offsets of a chunk: the finder's exclusive scan of u32 (ovl_scan_u32), hence chunks below 2^32 bytes of text.
+//   (scan)       line offsets of a chunk: the shared exclusive scan of u32 (dev_scan_u32, scan_sort_dev.h), hence chunks below 2^32 bytes of text.
 //   k_paf_write  one wave64 per row: the names by all lanes, the eight numbers by lanes 0 .. 7, the separators by lane 8, then the ops in blocks
 //                of 64 — lane l takes op base + l, its place is a wave prefix sum of digits + 1 carried across blocks in a scalar — and every lane
 //                stores its <= 11 bytes.  Plain byte stores; no LDS, no atomics.

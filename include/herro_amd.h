@@ -869,15 +869,15 @@ int herro_store_cut(herro_ctx* ctx, uint64_t n_pieces, const herro_piece* pieces
  * [n_reads + 1]), 2 qualities (qual_bytes bytes, not the pad), 3 qual_off (u64 [n_reads + 1]), 4 p0, 5 p1 (u32 [n_words + 2]).  Returns the
  * array's size in bytes (out NULL: nothing is copied), or a negative error: cap smaller than the array, no device, no reads. */
 int64_t herro_debug_store_copy(herro_ctx* ctx, int which, void* out, uint64_t cap);
-/* Test hooks: the two device primitives every stage of the front end stands on (csrc/overlap_dev.hip: the exclusive scan of u32 and the stable
+/* Test hooks: the two device primitives every stage of the front end stands on (csrc/scan_sort_dev.hip: the exclusive scan of u32 and the stable
  * LSD radix sort of 64-bit keys with 64-bit payloads) and the 64-bit offset join of the device FASTA (csrc/fasta_dev.hip), on host arrays.  Each
- * call allocates ONE device block, lays its arrays in it exactly as large as a client sizes them — the scan's scratch ovl_scan_partials(n) entries,
- * the sort's ovl_sort_scratch(n) —, with 64 u32 words of a fixed pattern directly behind every array, runs the product's own code on the
+ * call allocates ONE device block, lays its arrays in it exactly as large as a client sizes them — the scan's scratch dev_scan_partials(n) entries,
+ * the sort's dev_sort_scratch(n) —, with 64 u32 words of a fixed pattern directly behind every array, runs the product's own code on the
  * context's execution stream and copies the result back.  *guard_hits: how many of those words no longer hold the pattern afterwards (a plain
  * memory comparison; 0 unless something wrote past an array's end).
  *   herro_debug_scan_u32    out[0 .. n] = the running sums of in[0 .. n) modulo 2^32, out[0] = 0, out[n] the total.
  *   herro_debug_radix_sort  keys / pays [n] are sorted in place, stably, by the 8-bit digits (key >> shifts[i]) & 255 in the order of the list
- *                           (ascending significance: LSD); what comes back is what (*k0, *p0) name after ovl_radix_sort's pointer swaps.
+ *                           (ascending significance: LSD); what comes back is what (*k0, *p0) name after dev_radix_sort's pointer swaps.
  *                           An empty list moves nothing.
  *   herro_debug_offsets64   off[0 .. n] = the running sums of bytes[0 .. n) in 64 bits, formed as herro_job_fasta_dev forms its text offsets:
  *                           two 32-bit scans and a carry where the low prefix falls.  Exact while the total is below 2^64.

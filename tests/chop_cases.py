@@ -16,7 +16,7 @@ import numpy as np
 import chop_ref as R
 
 FLANK = 10
-SCAN_TILE = 2048          # elements of one tile of the scan the kernels use (overlap_dev.hip: 256 threads x 8)
+SCAN_TILE = 2048          # elements of one tile of the scan the kernels use (scan_sort_dev.h: 256 threads x 8)
 
 
 @dataclasses.dataclass(frozen=True)

@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from scan_sort_cases import SCAN_SEAM     # elements above which the scan under cl_build (overlap_dev.hip: k_scan_top) runs a second round
+from scan_sort_cases import SCAN_SEAM     # elements above which the scan under cl_build (scan_sort_dev.hip: k_scan_top) runs a second round
 
 
 def case(n, edges, k, w=None, span=None, min_span=0):

@@ -1,5 +1,5 @@
 """numpy restatement of the overlap finder with its index built in parts (herro_set_index_params; csrc/overlap_dev.hip: k_sketch_part, k_occ16,
-k_occ_pick64, k_part_cls, k_part_runs, k_part_expand; DESIGN.md §10, "An index in parts"), on top of overlap_ref, occ_ref and rescue_ref.  All
+k_occ_pick, k_part_cls, k_part_runs, k_part_expand; DESIGN.md §10, "An index in parts"), on top of overlap_ref, occ_ref and rescue_ref.  All
 integer.  What it must equal is the UNPARTITIONED specification — rescue_ref.find_overlaps_rescue, which is occ_ref's and overlap_ref's where the
 options are off — for every part size and every number of hash ranges.
 

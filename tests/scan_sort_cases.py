@@ -1,5 +1,5 @@
-"""Cases and references for the device primitives every stage of the front end stands on (csrc/overlap_dev.hip: the exclusive scan scan_u32 and the
-stable LSD radix sort radix_sort; csrc/fasta_dev.hip: the 64-bit offset join), as tests/test_gpu_scan_sort.py runs them through herro_debug_scan_u32,
+"""Cases and references for the device primitives every stage of the front end stands on (csrc/scan_sort_dev.hip: the exclusive scan dev_scan_u32 and the
+stable LSD radix sort dev_radix_sort; csrc/fasta_dev.hip: the 64-bit offset join), as tests/test_gpu_scan_sort.py runs them through herro_debug_scan_u32,
 herro_debug_radix_sort and herro_debug_offsets64.  The references are plain numpy in 64 bits; tests/test_scan_sort_cases_host.py proves with the
 constants below that the sizes reach every seam they are named for.
 
@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import numpy as np
 
-SC_TILE = 2048                       # elements of a scan tile and keys of a sort block (overlap_dev.hip: SC_TILE)
+SC_TILE = 2048                       # elements of a scan tile and keys of a sort block (scan_sort_dev.h: SC_TILE)
 TOP_STEP = 256                       # tile totals per round of k_scan_top (its block)
 SCAN_SEAM = TOP_STEP * SC_TILE       # 524 288: above it k_scan_top runs a second round
 U32 = 0xFFFFFFFF
@@ -116,7 +116,7 @@ def bits_of(v: int) -> int:
 
 
 def field_shifts(lo: int, nbits: int) -> list:
-    """overlap_dev.hip / cluster_dev.hip field_shifts: the digits that cover bits [lo, lo + nbits) — the last one may reach beyond the field"""
+    """scan_sort_dev.h field_shifts: the digits that cover bits [lo, lo + nbits) — the last one may reach beyond the field"""
     return list(range(lo, lo + nbits, 8))
 
 
@@ -131,7 +131,7 @@ def shift_lists() -> dict:
         L[f"cl_order_id{id_bits}"] = field_shifts(0, CL_LEVEL_BITS) + field_shifts(32, id_bits)
         for k in (3, 256):
             L[f"cl_nb_id{id_bits}_k{k}"] = field_shifts(0, id_bits) + field_shifts(32, bits_of(k))
-    # the finder (overlap_dev.hip): minimizers by hash (2 k bits, k = 15 and 28), anchors by (tpos, qpos) and then by (t, q, strand) with its field at
+    # the finder (overlap_dev.hip, overlap_rows.hip): minimizers by hash (2 k bits, k = 15 and 28), anchors by (tpos, qpos) and then by (t, q, strand) with its field at
     # bit 33, chains by score, rows by (target, query)
     L["ovl_hash_k15"] = field_shifts(0, 30)
     L["ovl_hash_k28"] = field_shifts(0, 56)

@@ -146,7 +146,7 @@ def test_a_hub_with_3000_neighbours():
 
 
 def test_half_a_million_reads_without_an_edge_pass_the_seam_of_the_scan():
-    """n = 256 * 2048 + 1: the order sort's keys and the weight prefix both take k_scan_top (overlap_dev.hip) into its second round; without an edge
+    """n = 256 * 2048 + 1: the order sort's keys and the weight prefix both take k_scan_top (scan_sort_dev.hip) into its second round; without an edge
     the order is the ids, so every field shows where the sort or the scan slipped"""
     g = CC.edge_free_graph()
     assert g["n"] == CC.SCAN_SEAM + 1 == 524289 and g["n_parts"] == 7 and len(g["a"]) == 0 and int(g["w"].sum()) < 1 << 32

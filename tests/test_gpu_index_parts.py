@@ -1,4 +1,4 @@
-"""gpu: the overlap finder with its index built in parts (herro_set_index_params; csrc/overlap_dev.hip: k_sketch_part, k_occ16, k_occ_pick64,
+"""gpu: the overlap finder with its index built in parts (herro_set_index_params; csrc/overlap_dev.hip: k_sketch_part, k_occ16, k_occ_pick,
 k_part_cls, k_part_gather, k_part_runs, k_part_expand, k_rec_keys, k_rec_gather; DESIGN.md §10, "An index in parts") against the UNPARTITIONED
 references, record for record: the combination trials of tests/test_index_parts_host.py with every option, a block per read and a single block, the
 hash ranges of the occurrence pass, the low-complexity working set, the scratch budget, the memory figure, and the setting switched off again."""

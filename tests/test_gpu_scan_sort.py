@@ -1,4 +1,4 @@
-"""gpu: the exclusive scan and the stable radix sort every device stage of the front end stands on (csrc/overlap_dev.hip: scan_u32, radix_sort) and the
+"""gpu: the exclusive scan and the stable radix sort every device stage of the front end stands on (csrc/scan_sort_dev.hip: dev_scan_u32, dev_radix_sort) and the
 64-bit offset join of the device FASTA (csrc/fasta_dev.hip), run on their own through herro_debug_scan_u32, herro_debug_radix_sort and
 herro_debug_offsets64 against the numpy references of tests/scan_sort_cases.py: whole arrays, exactly equal, at the sizes where k_scan_top begins its
 second round, where the sort's histogram scan takes a second tile and a second round, with values that wrap modulo 2^32, and with the shift lists the

@@ -15,8 +15,12 @@ from herro_amd import api
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _csrc(*names):
+    return "".join(open(os.path.join(ROOT, "herro_amd", "csrc", n)).read() for n in names)
+
+
 def test_the_constants_are_the_kernels():
-    src = open(os.path.join(ROOT, "herro_amd", "csrc", "overlap_dev.hip")).read()
+    src = _csrc("scan_sort_dev.h", "scan_sort_dev.hip")
     items = int(re.search(r"constexpr int SC_ITEMS = (\d+);", src).group(1))
     assert re.search(r"constexpr uint32_t SC_TILE = 256 \* SC_ITEMS;", src) and 256 * items == SC.SC_TILE == 2048
     assert re.search(r"for \(uint32_t b0 = 0; b0 < nb; b0 \+= 256\)", src) and SC.TOP_STEP == 256      # k_scan_top's walk
@@ -118,7 +122,7 @@ def test_shift_lists_hold_what_the_clients_build():
     assert L["cl_order_id9"] == [0, 32, 40] and L["cl_order_id17"] == [0, 32, 40, 48]
     assert L["cl_nb_id9_k3"] == [0, 8, 32] and L["cl_nb_id9_k256"] == [0, 8, 32, 40]
     assert L["cl_nb_id17_k3"] == [0, 8, 16, 32] and L["cl_nb_id17_k256"] == [0, 8, 16, 32, 40]
-    src = open(os.path.join(ROOT, "herro_amd", "csrc", "cluster_dev.hip")).read()
+    src = _csrc("cluster_dev.hip")
     for call in ("field_shifts(sh, 32, id_bits);", "field_shifts(sh, 0, bits_of(std::min(levels2, n)));", "field_shifts(sh, 0, id_bits);",
                  "field_shifts(sh, 32, bits_of(k));"):
         assert call in src, call
@@ -127,8 +131,8 @@ def test_shift_lists_hold_what_the_clients_build():
     for name in ("cl_nb_id9_k3", "cl_order_id17", "ovl_anchor_pos", "ovl_rows"):          # a field at bit 32 sorted after a field at bit 0
         v = L[name]
         assert v[0] == 0 and 32 in v and v == sorted(v)
-    # the finder's lists (overlap_dev.hip)
-    src = open(os.path.join(ROOT, "herro_amd", "csrc", "overlap_dev.hip")).read()
+    # the finder's lists (overlap_dev.hip; the row table's: overlap_rows.hip)
+    src = _csrc("overlap_dev.hip", "overlap_rows.hip")
     for call in ("field_shifts(shifts, 0, 2 * k);", "field_shifts(sa, 0, bits_of(max_len));", "field_shifts(sa, 32, bits_of(max_len));",
                  "field_shifts(sb, 0, 1 + bits_of(S.n_reads - 1));", "field_shifts(sb, 33, bits_of(t_hi - t_lo - 1));", "{0, 8, 16, 24}",
                  "field_shifts(shifts, 0, bits_of(n_reads - 1));", "field_shifts(shifts, 32, bits_of(n_reads - 1));"):
