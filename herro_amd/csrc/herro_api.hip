@@ -251,7 +251,7 @@ static int ensure_sib(herro_ctx* ctx, uint32_t n_tiles_b) {
   ctx->sib_kv = nullptr; ctx->sib_flag = nullptr; ctx->sib_cap = 0;
   const uint32_t cap = n_tiles_b + n_tiles_b / 2 + 8;
   if (hipMalloc(&ctx->sib_kv, (size_t)cap * 2 * 8 * 8 * 64 * 16) != hipSuccess || hipMalloc(&ctx->sib_flag, ((size_t)cap + 1) * 4) != hipSuccess ||
-      hipMemset(ctx->sib_flag, 0, ((size_t)cap + 1) * 4) != hipSuccess) {
+      hipMemsetAsync(ctx->sib_flag, 0, ((size_t)cap + 1) * 4, ctx->stream) != hipSuccess) {   // on the stream of the launches that read the flags: in front of them by stream order (a memset on the null stream is not ordered with a non-blocking stream, and may return before it has run)
     if (ctx->sib_kv) (void)hipFree(ctx->sib_kv);
     ctx->sib_kv = nullptr;
     ctx->err = "out of device memory for the sibling-tile buffers";
@@ -400,7 +400,17 @@ void herro_destroy(herro_ctx* ctx) {
 
 int herro_set_stream(herro_ctx* ctx, void* s) {
   if (!ctx) return HERRO_E_INVALID;
-  ctx->stream = s ? (hipStream_t)s : ctx->own_stream;
+  if (ctx->host_only) return HERRO_OK;   // no device, no stream
+  const hipStream_t to = s ? (hipStream_t)s : ctx->own_stream;
+  if (to == ctx->stream) return HERRO_OK;
+  // A switch orders: everything this context has queued on the stream it leaves is complete before anything runs on the new one.  Queued work is
+  // normal here (herro_job_featurize returns with k_rfq queued, herro_job_infer with the descriptor upload and the whole model), the next call reads
+  // what it writes, and every guard in front of recycled memory (herro_job_free, ensure_sib / ensure_logits / ensure_scratch) waits for ctx->stream
+  // alone — so the stream that is left must be idle.  The call is rare: the wait is the simple way.  (Work on prep_stream never outlives the call
+  // that queued it: herro_job_create waits for prep_ev itself.)
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->stream = to;
   return HERRO_OK;
 }
 

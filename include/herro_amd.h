@@ -65,8 +65,18 @@ const char* herro_version(void);
 herro_ctx* herro_create(int device_id);
 void herro_destroy(herro_ctx* ctx);
 const char* herro_last_error(const herro_ctx* ctx); /* ctx may be NULL (creation errors) */
-/* Run all subsequent work of this context on an externally owned hipStream_t (e.g. the
- * current torch stream).  NULL restores the context's own stream. */
+/* Run all subsequent work of this context — every kernel and every copy of every entry below — on an externally owned hipStream_t.
+ *   - NULL restores the context's own stream (created hipStreamNonBlocking with the context).
+ *   - The legacy default stream cannot be named: its handle IS 0, which reads as NULL.  torch's current stream is that stream unless the
+ *     caller entered another one, so a torch caller passes a stream it created (torch.cuda.Stream().cuda_stream, never 0); handing over
+ *     torch.cuda.current_stream().cuda_stream == 0 silently selects the context's own stream, which is not ordered with torch's work.
+ *   - A switch orders: the call returns once everything this context had queued on the stream it leaves is complete (it waits for that
+ *     stream), so work queued before the switch — herro_job_featurize and herro_job_infer return with kernels queued — is seen by whatever
+ *     runs after it, and memory recycled after it is no longer in use.  Naming the stream already in force does nothing.
+ *   - The stream must outlive every job and handle of the context, or be switched away from (to NULL or another stream) before it is
+ *     destroyed.
+ *   - Stream capture (hipStreamBeginCapture, hipGraph) is not supported: the entries synchronise, allocate and read results back.
+ * HERRO_E_INVALID for a NULL context. */
 int herro_set_stream(herro_ctx* ctx, void* hip_stream);
 int herro_synchronize(herro_ctx* ctx);
 
