@@ -7,8 +7,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libherro_amd.so")
-HIP_SOURCES = ["pileup.hip", "model.hip", "model_h.hip", "cigar_dev.hip", "build_dev.hip", "align_dev.hip", "scan_sort_dev.hip", "overlap_dev.hip", "overlap_rows.hip", "paf_dev.hip", "adapter_dev.hip", "store_dev.hip", "cluster_dev.hip", "fasta_dev.hip", "herro_api.hip", "frontend_api.hip", "ingest.cpp", "fastx.cpp", "pool.cpp"]
-HEADERS = ["herro_amd.map", "host_cpus.h", "job_dev.h", "model_dev.h", "model_pack.h", "infer_plan.h", "pileup_core.h", "windowing.hpp", "cigar_dev.h", "build_dev.h", "job_layout.h", "align_dev.h", "overlap_dev.h", "scan_sort_dev.h", "api_ctx.h", "aligned_dev.h", "dev_bufs.h", "paf_dev.h", "alns_file.h", "adapter_dev.h", "store_dev.h", "trim_plan.h", "cluster_dev.h", "cluster_plan.h", "fasta_dev.h", "chop_plan.h", "index_plan.h", os.path.join("..", "..", "include", "herro_amd.h")]
+HIP_SOURCES = ["pileup.hip", "model.hip", "model_h.hip", "cigar_dev.hip", "build_dev.hip", "align_dev.hip", "scan_sort_dev.hip", "overlap_dev.hip", "overlap_rows.hip", "paf_dev.hip", "adapter_dev.hip", "store_dev.hip", "cluster_dev.hip", "fasta_dev.hip", "herro_api.hip", "model_api.hip", "job_create.hip", "job_run.hip", "job_out.hip", "frontend_api.hip", "ingest.cpp", "fastx.cpp", "pool.cpp"]
+HEADERS = ["herro_amd.map", "host_cpus.h", "job_dev.h", "model_dev.h", "model_pack.h", "infer_plan.h", "pileup_core.h", "windowing.hpp", "cigar_dev.h", "build_dev.h", "job_layout.h", "align_dev.h", "overlap_dev.h", "scan_sort_dev.h", "api_ctx.h", "api_job.h", "aligned_dev.h", "dev_bufs.h", "paf_dev.h", "alns_file.h", "adapter_dev.h", "store_dev.h", "trim_plan.h", "cluster_dev.h", "cluster_plan.h", "fasta_dev.h", "chop_plan.h", "index_plan.h", os.path.join("..", "..", "include", "herro_amd.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall",
          "-fno-gpu-rdc", "-Wl,--version-script=" + os.path.join(CSRC, "herro_amd.map")]   # exports: the C ABI (herro_*) only
 

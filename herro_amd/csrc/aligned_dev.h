@@ -1,4 +1,4 @@
-// aligned_dev.h — what herro_job_create_aligned (herro_api.hip) takes from the front end (frontend_api.hip): the handle over
+// aligned_dev.h — what herro_job_create_aligned (job_create.hip) takes from the front end (frontend_api.hip): the handle over
 // device-resident ops, a copy of a span of its store, and the ops' CIGAR text.
 #pragma once
 #include "api_ctx.h"

@@ -1,9 +1,11 @@
-// api_ctx.h — what the translation units of the C ABI share (herro_api.hip: contexts, model, jobs; frontend_api.hip: reads alone ->
-// records -> ops on the device): the context, its last-error slot, HIP_TRY and the host pool.  Internal: nothing here is exported.
+// api_ctx.h — what the translation units of the C ABI share (herro_api.hip: contexts; model_api.hip: the model; job_create.hip, job_run.hip, job_out.hip: jobs,
+// which share api_job.h on top; frontend_api.hip: reads alone -> records -> ops on the device): the context, its last-error slot, HIP_TRY and the host pool.
+// Internal: nothing here is exported.
 // (The host half of herro_load_model — file reader, number formats, weight layouts — is model_pack.h, which knows neither a context nor HIP.)
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <cstdlib>
@@ -100,6 +102,15 @@ struct HostPool {
     done_cv.wait(lk, [&] { return active == 0; });
   }
 };
+
+// Device scratch of one call: MiB from the environment (at least 1), else default_mb
+inline uint64_t scratch_budget(const char* env_name, uint64_t default_mb = 4096) { const char* e = getenv(env_name); return e ? (uint64_t)std::max(1ll, atoll(e)) << 20 : default_mb << 20; }
+
+// a list of device allocations (the model's, the activation scratch's, the temporaries of a call) goes
+inline void free_all(std::vector<void*>& v) {
+  for (void* p : v) if (p) (void)hipFree(p);
+  v.clear();
+}
 
 struct Arena { void* p = nullptr; size_t cap = 0; };
 

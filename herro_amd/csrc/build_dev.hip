@@ -178,7 +178,7 @@ __global__ __launch_bounds__(1024) void k_scan_alns(BuildDev B) {
   }
 }
 
-// The overlap of alignment a in window wl of its target: every field of OwDesc and every check build_target makes (herro_api.hip; features.rs:585-679,
+// The overlap of alignment a in window wl of its target: every field of OwDesc and every check build_target makes (job_create.hip; features.rs:585-679,
 // 110-237).  false: an input the reference would panic on.
 __device__ inline bool make_ow(const BuildDev& B, uint32_t a, const HowRec& x, const AlnMeta& m, const TgtMeta& t, const AlnHead& h, uint32_t w, uint32_t wl,
                                uint32_t win_start, uint32_t win_len, OwDesc& d, uint64_t& tt_out) {

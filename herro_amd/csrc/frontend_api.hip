@@ -1,7 +1,7 @@
 // frontend_api.hip — the C ABI's front end (include/herro_amd.h): reads alone -> overlap records -> their ops on the device.
 // herro_find_overlaps[_core], herro_extend_overlaps, herro_align_overlaps[_dev], herro_aligned_dev_*, herro_find_overlap_pairs[_core], herro_pairs_*, the PAF / .oec.zst
 // writer (herro_aligned_dev_paf, herro_pairs_paf, herro_pairs_write_alns) herro_set_seed_rescue, herro_set_chain_params, herro_set_index_params with herro_index_plan (csrc/index_plan.h), and the test hooks herro_debug_sketch, herro_debug_occ_census, herro_debug_seed_rescue and herro_debug_chain.  Host C++ (compiled by
-// hipcc) over overlap_dev.hip, align_dev.hip and paf_dev.hip; contexts, the model and jobs are herro_api.hip.  Ahead of them all, for raw reads:
+// hipcc) over overlap_dev.hip, align_dev.hip and paf_dev.hip; contexts are herro_api.hip, the model model_api.hip, jobs job_create.hip, job_run.hip and job_out.hip.  Ahead of them all, for raw reads:
 // herro_find_adapters and its handle, over adapter_dev.hip (the plan and the cut are host code: fastx.cpp), and herro_store_cut with its test hook
 // herro_debug_store_copy, over store_dev.hip: the store cut to the plan's pieces on the device.  The primitives every device stage stands on have hooks of
 // their own: herro_debug_scan_u32, herro_debug_radix_sort (scan_sort_dev.hip) and herro_debug_offsets64 (fasta_dev.hip's offset join).  Behind the finder: herro_cluster_graph, herro_pairs_cluster and
@@ -43,9 +43,6 @@ int device_ready(herro_ctx* ctx, const char* who) {
   if (!ctx->d_words) { ctx->err = "herro_set_reads must be called first"; return HERRO_E_STATE; }
   return HERRO_OK;
 }
-
-// 4 GiB of device scratch per call (the writer: default_mb), or what the environment says (in MiB, at least 1)
-uint64_t scratch_budget(const char* env_name, uint64_t default_mb = 4096) { const char* e = getenv(env_name); return e ? (uint64_t)std::max(1ll, atoll(e)) << 20 : default_mb << 20; }
 
 herro::OvlStore ovl_store(const herro_ctx* ctx) { return herro::OvlStore{ctx->d_words, ctx->d_word_off, ctx->d_qual_off, ctx->read_len.data(), ctx->n_reads}; }
 

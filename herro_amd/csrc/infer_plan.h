@@ -68,7 +68,7 @@ static std::vector<uint32_t> tile_pack_order(const std::vector<uint32_t>& cnt) {
 // tiles go into 32-token tiles instead, one per compute unit (2560 windows of the bench: 625 tiles = 2 rounds + 113 -> 2 rounds
 // + 226 half tiles).  qmode 2 (A/B): every window of <= 32 rows goes into 32-token tiles; a window of 33..64 opens a 64-token
 // tile and takes the best-fitting small windows along.  Without `pack` the windows keep their batch order inside each class.
-// Windows above 64 rows (the caller admits them up to 64 * FUSED_MAX_SIB of herro_api.hip, f16 stack only) come FIRST in the stream, each one alone
+// Windows above 64 rows (the caller admits them up to 64 * FUSED_MAX_SIB of api_job.h, f16 stack only) come FIRST in the stream, each one alone
 // on ceil(rows / 64) consecutive tiles (`tiles_b`; grp[t] = first tile of the window's group | tiles in it << 20 | its tokens in the last tile << 24);
 // small windows may share that last tile.
 struct TilePlan { std::vector<uint32_t> order, tiles, tiles_q, tiles_b, grp; };

@@ -12,6 +12,7 @@
 #include "pileup_core.h"
 
 #define HERRO_ROWS 31
+#define HERRO_MAX_ALNS (HERRO_ROWS - 1)   // alignments of a window that get a row: all rows but the target's (n_alns; a window with fewer than 2 is not corrected)
 #define HERRO_MAX_WINDOW 8192
 #define HERRO_TILE 1024       // rows of the final matrix per k_tokens workgroup (a "tile" of the job's tile list)
 

@@ -1,4 +1,4 @@
-// job_layout.h — where every array of a job lies inside the blocks herro_job_create carves (herro_api.hip; DESIGN.md, "Job creation as built"), stated once.
+// job_layout.h — where every array of a job lies inside the blocks herro_job_create carves (job_create.hip, the logits block job_run.hip; DESIGN.md, "Job creation as built"), stated once.
 // Plain C++17 over integers, as infer_plan.h and chop_plan.h: no HIP call, no context; job_dev.h, build_dev.h and cigar_dev.h are here for the sizeof of
 // the records.  Each block has an enum that IS its order, a function that fills a layout from counts, and one bind function that turns a base pointer and
 // the layout into typed pointers — no other code casts into a block.  tools/job_layout_check.cpp drives all of it in a sanitizer build.

@@ -1490,7 +1490,7 @@ constexpr size_t layers_p_shm(int tokens) { return (size_t)4 * tokens * 256 * 2 
 // Tiles of 32 tokens (k_layers_p<TERMS, 2>): the same organisation — 8 waves, wave = head and 32-channel slab, weights one
 // call ahead — over two row blocks instead of four: half the MFMAs and half the LDS traffic for the same weight stream.  A launch
 // runs in rounds of one 64-token tile per compute unit; when its last round would fill at most half of the chip, the windows of
-// that round go into 32-token tiles instead (plan_tiles, herro_api.hip).
+// that round go into 32-token tiles instead (plan_tiles, infer_plan.h).
 //
 // What round 4 measured before settling on this (profiles/r4_layers_*): a SEPARATE design for 32-token tiles, k_layers_q — four
 // waves per workgroup, wave = 64 channels (two heads), a ring of four weight k-steps, one-barrier LayerNorm, 80 KB of LDS so that
@@ -1583,7 +1583,7 @@ bool model_h_f8_supported(const ModelDev& M) {
 }
 
 // HERRO_LAYERS_Q: 0 keeps every tile at 64 tokens, 2 puts every window of <= 32 rows into 32-token tiles (both for A/B);
-// default 1: 32-token tiles take the short last round of a launch (plan_tiles, herro_api.hip)
+// default 1: 32-token tiles take the short last round of a launch (plan_tiles, infer_plan.h)
 int model_h_half_tiles(const ModelDev& M) {
   static const int mode = std::max(0, std::min(2, ab_env("HERRO_LAYERS_Q", 1)));   // (A/B builds only)
   return model_h_supported(M) ? mode : 0;

@@ -1,7 +1,7 @@
 // model_pack.h — the host half of herro_load_model: the flat weight file -> every byte the device will hold, and nothing of a device or a
 // context.  Plain C++17 (no HIP header: a host compiler alone builds and sanitizes it).  Here are the file reader, the number formats
 // (bf16, f16, OCP e4m3), the one implementation of each layout model_dev.h documents (Weight::phi, Weight::p8, ModelDev::conv1g) and
-// load_host_model, which walks the tensors a model needs; herro_api.hip uploads what it returns.  Test hook: herro_debug_model_pack.
+// load_host_model, which walks the tensors a model needs; model_api.hip uploads what it returns.  Test hook: herro_debug_model_pack.
 #pragma once
 #include <stdint.h>
 #include <sys/stat.h>

@@ -14,7 +14,7 @@ from herro_amd import api, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PILEUP = os.path.join(ROOT, "herro_amd", "csrc", "pileup.hip")
-HERRO_API = os.path.join(ROOT, "herro_amd", "csrc", "herro_api.hip")
+API_JOB = os.path.join(ROOT, "herro_amd", "csrc", "api_job.h")
 MAX_COLS = 30   # selected overlaps per window (columns 1 .. 30 of the pileup)
 
 # crosses: RW_ICAP   k_rows runs its insertion rows in several passes and reads the informative flags back from global memory
@@ -54,7 +54,7 @@ def generate(name):
 
 def caps():
     """The capacities as the kernels are compiled with them: `constexpr uint32_t NAME = N;` in pileup.hip, HERRO_RW_ICAP's default, and
-    the fused f16 stack's row limit (FUSED_MAX_SIB sibling tiles of 64 rows, herro_api.hip)."""
+    the fused f16 stack's row limit (FUSED_MAX_SIB sibling tiles of 64 rows, api_job.h)."""
     src = open(PILEUP).read()
     val = {n: int(v) for n, v in re.findall(r"constexpr uint32_t (\w+) = (\d+)u?;", src)}
     m = re.search(r"#define HERRO_RW_ICAP (\d+)", src)
@@ -63,7 +63,7 @@ def caps():
     for k in ("CP_ICAP", "CP_OCAP", "QEVCAP"):
         assert k in val, f"{k} is no longer a constexpr of pileup.hip"
         out[k] = val[k]
-    m = re.search(r"constexpr uint32_t FUSED_MAX_SIB = (\d+);", open(HERRO_API).read())
+    m = re.search(r"constexpr uint32_t FUSED_MAX_SIB = (\d+);", open(API_JOB).read())
     assert m, "FUSED_MAX_SIB moved"
     out["FUSED_ROWS"] = int(m.group(1)) * 64
     return out

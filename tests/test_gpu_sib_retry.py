@@ -115,3 +115,66 @@ def test_two_inferred_jobs_in_flight_both_repeat():
     finally:
         a.close(); b.close(); ref.close()
         c.set_precision(api.DEFAULT_PRECISION)
+
+
+def _consensus_done_job():
+    """The case of the tests above with all three passes run, no fault yet: (context, job, ids, the synthetic batch)."""
+    sb = synth.generate(2, 2 * 4096, 32, seed=synth.SEED + 71, p_snp=0.03)
+    c = G.ctx()
+    G.load_synth(c, sb)
+    c.set_precision(4)
+    job = api.job_from_synth(c, sb, 4096)
+    try:
+        job.featurize(); job.infer(64, 1); job.consensus()
+        nsup = [job.info(w).n_supported for w in range(job.n_windows)]
+        assert max(nsup) > 64, "the case needs a window on sibling tiles"
+    except BaseException:
+        job.close()
+        c.set_precision(api.DEFAULT_PRECISION)
+        raise
+    return c, job, [f"read{t}" for t in range(sb.n_targets)], sb
+
+
+def test_fasta_dev_is_the_fetch_that_finds_the_word():
+    """herro_job_fasta_dev settles the pass in front of its kernels: the text it forms is the repeated pass's, which is what fasta() of the same job
+    reads right after — with the three chop numbers 0 the two texts are the same bytes."""
+    c, job, ids, _ = _consensus_done_job()
+    try:
+        r0 = c.sib_retries()
+        c.sib_fault()
+        text = job.fasta_dev(ids, chop_len=0, min_length=0, line_width=0)
+        assert c.sib_retries() == r0 + 1
+        assert text == job.fasta(ids)
+        job.fasta_dev(ids, chop_len=0, min_length=0, line_width=0)
+        assert c.sib_retries() == r0 + 1
+    finally:
+        job.close()
+        c.set_precision(api.DEFAULT_PRECISION)
+
+
+def test_consensus_fetch_is_the_fetch_that_finds_the_word():
+    """herro_job_consensus_fetch queues its copies in front of the settle and copies again behind the repeat: what fasta() assembles from them is the
+    text fasta_dev forms from the device's bases.  That alone would also hold for copies of the FIRST pass wherever the two kernel paths decode the same
+    bases, so the text is held to a second job's as well, whose passes ran clean and without sibling tiles from the start (a job past its one repeat
+    launches none): the same kernels on the same input, the same bytes."""
+    c, job, ids, sb = _consensus_done_job()
+    ref = api.job_from_synth(c, sb, 4096)
+    try:
+        ref.featurize(); ref.infer(64, 1)
+        c.sib_fault()
+        ref.logits(0)                                         # its one repeat: no sibling tiles from here on
+        ref.featurize(); ref.infer(64, 1); ref.consensus()    # clean passes, layer by layer above 64 rows
+        want = ref.fasta(ids)
+        job.featurize(); job.infer(64, 1); job.consensus()    # (ref's word tainted this job's unchecked pass too: a fresh one, on sibling tiles)
+        r0 = c.sib_retries()
+        c.sib_fault()
+        job.consensus_fetch()
+        assert c.sib_retries() == r0 + 1
+        got = job.fasta(ids)
+        assert got == job.fasta_dev(ids, chop_len=0, min_length=0, line_width=0)
+        assert got == want
+        assert c.sib_retries() == r0 + 1
+    finally:
+        ref.close()
+        job.close()
+        c.set_precision(api.DEFAULT_PRECISION)
